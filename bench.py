@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the TGN training step on MI355X (BASELINE.json metric: interactions/s, TGN fwd + BPR step).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic interactions, the loop body of
 main.py:160-394: candidate-negative draw -> temporal neighbour sampling -> lazy memory update (GRU)
@@ -16,17 +16,21 @@ touching any GPU - and relays rank 0's line; under ``python -m torch.distributed
 Default workload for N > 1 is the SAME headline graph (C2) with 512 interactions per GPU - a global batch of 512 N cut
 into N shards, one all-reduce of the flat gradient buffer per step (weak scaling: value(N) / (N value(1)) is the
 efficiency, on one workload).  Every N > 1 line reports the collective's own time (``config.collective_ms_per_step``,
-event-bracketed on the caller's stream) and carries, under ``secondary``, a 1 s run of the same workload with the other
-all-reduce form (one piece / two buckets); at N = 8 (or with ``--secondary``) also BASELINE.json configs[3] (C4: 500k
+event-bracketed on the caller's stream); with ``--full`` (or ``--secondary``) it carries, under ``secondary``, a 1 s run of the
+same workload with the other all-reduce form (one piece / two buckets); at N = 8 (or with ``--secondary``) also BASELINE.json configs[3] (C4: 500k
 users, 10M edges) at a FIXED global batch of 4096 interactions (strong scaling) with the same batch on ONE of
 those GPUs.  ``--no-secondary`` drops all of that; ``--config`` / ``--scaling`` override (``--config C4`` makes the
 strong-scaling case the main line).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  "roofline":     live HIP-event timing of the dominant kernel family over the timed region
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype and ms_per_step (the mean time of one timed
+step).  The timed region is exactly K steps after W warm-up steps, bracketed by barrier + synchronize; --min-seconds S > 0
+repeats the K-step block until S seconds are covered and reports the mean over all blocks.  A plain run does nothing else.
+--dump-outputs DIR writes what the last timed step handed its caller as .npy files (dump_outputs); it implies
+--deterministic, so that the same arguments write the same outputs on every run.
+--full adds everything that is not the headline figure:
+  "roofline":     live HIP-event timing of the dominant kernel family (every 8th step of the first timed block bracketed)
   "cpu_baseline": the oracle (numpy restatement of the reference) timed on this host, bounded sample
-The timed region is K steps; when K steps take less than --min-seconds (2 s) the K-step block is repeated
-(each block bracketed by barrier + synchronize) and the line reports the mean over all blocks.
+  "secondary":    one GPU: the drop-in surface (drop_in_surface); N > 1: the other all-reduce forms and scaling cases above
 """
 import argparse
 import json
@@ -62,13 +66,22 @@ def parse():
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="N > 1: weak = --batch interactions per GPU, strong = the config's batch cut into N shards "
                          "(default: strong for C4, weak otherwise)")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the K-step timed block until this much time is covered")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline figure: the roofline brackets, the CPU baseline, the drop-in surface "
+                         "(one GPU) and the secondary figures (N > 1).  Off: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one handed its caller (loss, embeddings, parameters, memory "
+                         "state) as DIR/<name>.npy, float32, at most 64 MB in all (dump_outputs).  Implies --deterministic, so that "
+                         "the same arguments write the same outputs on every run")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step timed block until this much time is covered (default 0: exactly --steps timed steps)")
     ap.add_argument("--no-secondary", action="store_true", help="N > 1: no secondary figures at all (only the main line's workload runs)")
     ap.add_argument("--secondary", action="store_true",
-                    help="N > 1: also run the other scaling case (C4 at a fixed global batch of 4 096 with its one-GPU reference, or the "
-                         "weak-scaling C2 figure when the main line is C4) - a second 10 M-edge graph per rank.  ON by default at N = 8 "
-                         "(BASELINE.json configs[3] names exactly that machine), 1 s budget; every N > 1 line also carries a 1 s run of "
-                         "the main workload with each other all-reduce form (secondary.allreduce_single / _buckets / _fused / _fused_buckets)")
+                    help="N > 1: run the secondary figures without --full, and add the other scaling case (C4 at a fixed global "
+                         "batch of 4 096 with its one-GPU reference, or the weak-scaling C2 figure when the main line is C4) - a second "
+                         "10 M-edge graph per rank.  With --full ON by default at N = 8 (BASELINE.json configs[3] names exactly that "
+                         "machine), 1 s budget; the secondary figures of every N > 1 line also carry a 1 s run of the main workload with "
+                         "each other all-reduce form (secondary.allreduce_single / _buckets / _fused / _fused_buckets)")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="replay the step from a captured HIP graph (one launch per step instead of ~85).  auto (one GPU, per-GPU "
                          "batch <= 256): capture, time ten steps either way during set-up and keep the faster form - the graph "
@@ -101,12 +114,12 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="interactions per GPU per step (default: the config's)")
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=512, help="interactions per oracle step in the CPU baseline sample")
     ap.add_argument("--cpu-steps", type=int, default=4, help="timed oracle steps (one more runs first, untimed)")
-    ap.add_argument("--no-prof", action="store_true", help="skip the HIP-event bracketing of kernel launches")
+    ap.add_argument("--no-prof", action="store_true", help="--full: skip the HIP-event bracketing of kernel launches (no roofline)")
     ap.add_argument("--no-drop-in", action="store_true",
-                    help="one GPU: skip secondary.drop_in_surface (the literal main.py:160-394 loop on the drop-in classes, ~1 s per optimizer)")
+                    help="--full, one GPU: skip secondary.drop_in_surface (the literal main.py:160-394 loop on the drop-in classes, ~1 s per optimizer)")
     ap.add_argument("--overlap-tail", type=int, default=1, choices=[0, 1],
                     help="1 (default, one rank): backward + optimizer step as ONE fused call whose end - the last side-stream launches "
                          "of the backward and the Adam kernel - stays on the library's side stream while the caller's stream goes on to "
@@ -122,9 +135,16 @@ def parse():
                          "caller's stream at named points of the step: the critical path as the GPU ran it, no tracer) and print the "
                          "per-segment means to stderr")
     ap.add_argument("--prof-every", type=int, default=8,
-                    help="bracket the kernel launches of every Nth timed step with HIP events (the brackets cost ~0.2 ms "
+                    help="--full: bracket the kernel launches of every Nth timed step with HIP events (the brackets cost ~0.2 ms "
                          "per step at C2, so the roofline sample is taken on a subset of the timed steps)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    # The default backward sums with float atomics: the parameters differ in the last bits after one step, and Adam spreads
+    # that through the training state within a few steps (lr-sized moves whatever a parameter's scale, the time encoder's
+    # 1e-9 frequencies among them).  A run that writes its outputs times the bitwise reproducible backward instead (~10 %
+    # slower at C2); a plain run keeps the default one.
+    if args.dump_outputs:
+        args.deterministic = True
+    return args
 
 
 # 256 CUs x 4 SIMD-32, one wave64 vector instruction per 2 cycles at 2.4 GHz (MI355X_MICROARCH.md:54,473) = 1 228.8 G
@@ -418,6 +438,7 @@ class Workload:
         d = graph.data
         # the CSR is built on the device (two stable sorts) - the host build takes ~10 s per 10 M edges and every rank needs one
         nf = P.NeighborFinder.from_arrays(d.sources, d.destinations, d.edge_idxs, d.timestamps, uniform=cfg.uniform, device=dev)
+        torch.manual_seed(0)                                  # the same initial parameters on every run (--dump-outputs compares runs)
         tgn = self.tgn = P.TGN(nf, graph.node_features, graph.edge_features, dev, n_layers=cfg.n_layers, n_heads=cfg.n_heads,
                                dropout=args.dropout, use_memory=cfg.use_memory, memory_dimension=cfg.dim,
                                message_function="identity", n_neighbors=cfg.n_neighbors)
@@ -449,6 +470,8 @@ class Workload:
         tgn.record_mid_event = self.prefetch in (2, 3)
         tgn.mid_event_late = self.prefetch == 3
         self.mvs = None
+        # --dump-outputs: the step keeps its batch slice and its embedding matrix (the last timed step's are written out)
+        self.keep_last, self.last_sl, self.last_emb = False, None, None
         if self.ours:
             self.mvs = P.MVSampler(graph.prices, graph.upper_u, dev, gamma=2.0, lambda_mv=0.5, p_pos_num=1, p_neg_num=3)
             self.day_all = t(graph.day_of(d.timestamps), np.int32)
@@ -502,6 +525,8 @@ class Workload:
         P, torch, tgn, cfg, B, n_neg = self.P, self.torch, self.tgn, self.cfg, self.B, self.n_neg
         lo = self.start + (i * B) % self.span
         sl = slice(lo, lo + B)
+        if self.keep_last:
+            self.last_sl, self.last_emb = sl, None            # (a replayed HIP graph keeps its embedding matrix inside the graph)
         from pfotgnrec_amd import _lib as _lm
         _lm.mark("step.begin")
         if self.gstep is not None:
@@ -515,6 +540,8 @@ class Workload:
             self._next = None
             emb, b = tgn.embed_device(self.src_all[sl], self.dst_all[sl], [neg], [n_neg], self.ts_all[sl],
                                       self.eidx_all[sl], cfg.n_neighbors)                                     # tgn.py:219-327
+            if self.keep_last:
+                self.last_emb = emb
             pos_block = 1                                                                                      # main.py:364-381
             if self.prefetch == 1:
                 # the next batch's negatives, frontier, compaction and packed memory rows on the model's second stream: the
@@ -533,6 +560,8 @@ class Workload:
             p_pos, p_neg = self.mvs.select_device(self.day_all[sl], cand, self.port_idx_all[sl], self.port_len_all[sl])   # main.py:209-304
             emb, b = tgn.embed_device(self.src_all[sl], self.dst_all[sl], [p_pos.reshape(-1), p_neg.reshape(-1)], [1, 3],
                                       self.ts_all[sl], self.eidx_all[sl], cfg.n_neighbors)                    # tgn.py:102-217
+            if self.keep_last:
+                self.last_emb = emb
             pos_block = 2                                                                                      # main.py:321-337
         # loss + loss.backward() (main.py:337,388) as two native calls: the loss kernel hands its gradient rows straight to
         # the TGN backward (P.bpr_loss(...).backward() is the autograd spelling of the same thing, tests/test_gpu_round2.py)
@@ -1087,6 +1116,57 @@ def release_workload_memory():
     torch.cuda.empty_cache()
 
 
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: every file together
+
+
+def dump_outputs(wl, loss, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs DIR: what the last timed step handed its caller, as DIR/<name>.npy in float32 - ``loss`` [1],
+    ``embeddings`` (the step's [R, D] embedding matrix, rows [src | dst | negatives]; not written when the step was replayed
+    from a HIP graph, which keeps it inside the graph), ``parameters`` (the flat parameter buffer after the optimizer step)
+    and the memory module's state after the step (``memory``, ``memory_last_update``, ``message``, ``message_time``,
+    ``message_pending``).  When the node state does not fit in ``limit`` next to the rest, it is written for a fixed set of
+    nodes - those of the last batch's interactions plus a seeded sample of the others - listed in ``node_rows``.
+    The inputs are the same on every run, and --dump-outputs implies --deterministic (parse): two runs with the same
+    arguments write the same bits."""
+    torch, tgn = wl.torch, wl.tgn
+    tgn.join()
+    torch.cuda.synchronize()
+    host = lambda t: t.detach().float().cpu().numpy()
+    out = {"loss": np.array([loss], dtype=np.float32), "parameters": host(tgn.flat_parameters)}
+    if wl.last_emb is not None:
+        out["embeddings"] = host(wl.last_emb)
+    if tgn.memory is not None:
+        m = tgn.memory
+        state = {"memory": m.memory, "memory_last_update": m.last_update, "message": m.msg_table, "message_time": m.msg_time,
+                 "message_pending": m.has_msg}
+        n = m.memory.shape[0]
+        row_bytes = 4 * sum(t[0].numel() for t in state.values())
+        room = limit - sum(a.nbytes for a in out.values()) - (1 << 20)        # (1 MB left for the .npy headers)
+        if n * row_bytes <= room:
+            rows = np.arange(n)
+        else:
+            k = room // (row_bytes + 8)                           # (+ 8: node_rows itself, float64)
+            sl = wl.last_sl
+            own = np.unique(np.concatenate([wl.src_all[sl].cpu().numpy(), wl.dst_all[sl].cpu().numpy()]))[:k]
+            others = np.setdiff1d(np.arange(n), own)
+            pick = np.random.RandomState(0).choice(others, max(0, k - len(own)), replace=False)
+            rows = np.sort(np.concatenate([own, pick]))
+            out["node_rows"] = rows.astype(np.float64)
+        idx = torch.from_numpy(rows).to(m.memory.device)
+        for name, t in state.items():
+            out[name] = host(t.index_select(0, idx))
+    total = sum(a.nbytes for a in out.values())
+    assert total <= limit, "--dump-outputs: %d bytes > %d" % (total, limit)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def side_seconds(args):
+    """Timed budget of a secondary figure: --min-seconds capped at 1 s, 1 s when the main line times exactly K steps."""
+    return min(args.min_seconds, 1.0) if args.min_seconds > 0 else 1.0
+
+
 def emulate_ranks(args, dev):
     """Compute-side ceiling of the data-parallel scaling curve on ONE GPU: for each world size N the step of rank 0 -
     sampler / forward / loss / backward for its B/N interactions, the state update and the lazy GRU rows of ALL B global
@@ -1101,7 +1181,7 @@ def emulate_ranks(args, dev):
         rows = []
         for n in worlds:
             wl = Workload(args, cfg_name, dev, 0, n, "weak", emulate=True)
-            el, nt, _, _, _ = wl.timed(args.steps, args.warmup, min(args.min_seconds, 1.0), 0, first_step=1000 * n, collective=False)
+            el, nt, _, _, _ = wl.timed(args.steps, args.warmup, side_seconds(args), 0, first_step=1000 * n, collective=False)
             ms = 1e3 * el / nt
             rows.append({"world": n, "rank": 0, "local_batch": wl.per_gpu, "global_batch": wl.B, "ms_per_step": round(ms, 4),
                          "stub_collective_us_on_side_stream": round(getattr(wl, "sleep_coll", None).us, 1) if getattr(wl, "sleep_coll", None) else 0.0,
@@ -1130,7 +1210,7 @@ def emulate_ranks(args, dev):
     rows = []
     for n in worlds:
         wl.set_world(0, n)
-        el, nt, _, _, _ = wl.timed(args.steps, args.warmup, min(args.min_seconds, 1.0), 0, first_step=1000 * n, collective=False)
+        el, nt, _, _, _ = wl.timed(args.steps, args.warmup, side_seconds(args), 0, first_step=1000 * n, collective=False)
         ms = 1e3 * el / nt
         rows.append({"world": n, "rank": 0, "local_batch": wl.B // n, "ms_per_step": round(ms, 4),
                      "stub_collective_us_on_side_stream": round(wl.sleep_coll.us, 1) if getattr(wl, "sleep_coll", None) and n > 1 else 0.0,
@@ -1168,10 +1248,15 @@ def main():
     cfg_name = args.config or "C2"       # the headline graph at every N (BASELINE.json: "1M-edge graph at 1/2/4/8 MI355X")
     scaling = args.scaling or ("strong" if (cfg_name == "C4" and world > 1) else "weak")
     wl = Workload(args, cfg_name, dev, rank, world, scaling)
-    prof_every = 0 if args.no_prof else max(1, args.prof_every)
+    wl.keep_last = bool(args.dump_outputs)
+    profile = args.full and not args.no_prof                  # the roofline's kernel brackets: --full only
+    prof_every = max(1, args.prof_every) if profile else 0
     elapsed, n_timed, blocks, final_loss, n_prof_steps = wl.timed(args.steps, args.warmup, args.min_seconds, prof_every)
-    prof = _lib.prof_collect() if not args.no_prof else None
+    prof = _lib.prof_collect() if profile else None
     _lib.prof_enable(False)
+    if args.dump_outputs and rank == 0:                       # before anything else runs a step on this model
+        dump_outputs(wl, final_loss, args.dump_outputs)
+    wl.keep_last, wl.last_emb = False, None
     if args.marks > 0:
         for k in range(5):
             wl.step(900000 + k)
@@ -1219,7 +1304,7 @@ def main():
                                                          "source": "DESIGN.md 6: emulated-rank compute table (round 4), collective on the "
                                                                    "side stream beside the next batch's head ('fused')"}
 
-    if (world > 1 or wl.force_dist) and not args.no_secondary:
+    if (world > 1 or wl.force_dist) and (args.full or args.secondary) and not args.no_secondary:
         # Secondary figures ride in the same line.  Nothing here may cost the main line: every part is bounded (1 s of timed
         # steps) and an exception is recorded instead of raised.
         sec = {}
@@ -1230,21 +1315,21 @@ def main():
                 if (other.endswith("buckets") or other.endswith("ordered")) and cfg_layers(cfg_name) < 2:
                     continue
                 wl.allreduce_mode, wl.tgn.dp_bucketed, wl.tgn.dp_ordered = other, other.endswith("buckets") or other.endswith("ordered"), other.endswith("ordered")
-                el, nb, _, _, _ = wl.timed(args.steps, 5, min(args.min_seconds, 1.0), 0, first_step=50000)
+                el, nb, _, _, _ = wl.timed(args.steps, 5, side_seconds(args), 0, first_step=50000)
                 cms, cn = wl.collective_ms()
                 sec["allreduce_" + other] = {"n_gpus": world, "value": round(nb * B / el, 1), "ms_per_step": round(1e3 * el / nb, 4),
                                             "collective_ms_per_step": None if cms is None else round(cms, 4),
                                             "workload": "the main line's workload, all-reduce form '%s'" % other}
                 wl.tgn.join()
                 wl.allreduce_mode, wl.tgn.dp_bucketed, wl.tgn.dp_ordered = args.allreduce, args.allreduce.endswith("buckets") or args.allreduce.endswith("ordered"), args.allreduce.endswith("ordered")
-            want_other_case = world > 1 and (args.secondary or world == 8)
+            want_other_case = world > 1 and (args.secondary or (args.full and world == 8))
             # (1) the same workload on ONE of these GPUs (rank 0 alone, the others wait): the denominator of the strong-scaling
             #     figure.  (2) the other scaling case.
             if want_other_case and scaling == "strong":
                 dist.barrier()
                 if rank == 0:
                     wl.set_world(0, 1)
-                    el, n1, _, _, _ = wl.timed(args.steps, 2, min(args.min_seconds, 1.0), 0, first_step=100000, collective=False)
+                    el, n1, _, _, _ = wl.timed(args.steps, 2, side_seconds(args), 0, first_step=100000, collective=False)
                     sec["strong_scaling_reference"] = {"n_gpus": 1, "value": round(n1 * B / el, 1), "ms_per_step": round(1e3 * el / n1, 4),
                                                        "workload": "the same global batch on one GPU"}
                     wl.set_world(0, world)
@@ -1253,7 +1338,7 @@ def main():
                 del wl
                 release_workload_memory()
                 w2 = Workload(args, "C2", dev, rank, world, "weak")
-                el, n2, _, _, _ = w2.timed(args.steps, args.warmup, min(args.min_seconds, 1.0), 0)
+                el, n2, _, _, _ = w2.timed(args.steps, args.warmup, side_seconds(args), 0)
                 cms, _ = w2.collective_ms()
                 sec["weak_scaling_C2"] = {"n_gpus": world, "value": round(n2 * w2.B / el, 1), "ms_per_step": round(1e3 * el / n2, 4),
                                           "collective_ms_per_step": None if cms is None else round(cms, 4),
@@ -1266,7 +1351,7 @@ def main():
                 del wl
                 release_workload_memory()
                 w4 = Workload(args, "C4", dev, rank, world, "strong")
-                el, n4, _, _, _ = w4.timed(args.steps, args.warmup, min(args.min_seconds, 1.0), 0)
+                el, n4, _, _, _ = w4.timed(args.steps, args.warmup, side_seconds(args), 0)
                 cms, _ = w4.collective_ms()
                 v4, ms4 = n4 * w4.B / el, 1e3 * el / n4
                 sec["strong_scaling_C4"] = strong_scaling_entry(v4, ms4, world, w4.describe(), w4.B, cms)
@@ -1274,7 +1359,7 @@ def main():
                 dist.barrier()
                 if rank == 0:
                     w4.set_world(0, 1)
-                    el, n1, _, _, _ = w4.timed(args.steps, 2, min(args.min_seconds, 1.0), 0, first_step=100000, collective=False)
+                    el, n1, _, _, _ = w4.timed(args.steps, 2, side_seconds(args), 0, first_step=100000, collective=False)
                     sec["strong_scaling_C4"] = dict(strong_scaling_entry(v4, ms4, world, w4.describe(), w4.B, cms, n1 * w4.B / el, 1e3 * el / n1),
                                                     workload_build_s=round(w4.build_s, 2))
                 dist.barrier()
@@ -1283,7 +1368,7 @@ def main():
             sec["error"] = repr(e)[:300]
         out["secondary"] = sec
 
-    if world == 1 and not wl_gone and not args.no_drop_in and not (wl.force_dist or args.deterministic) and wl.mvs is None and wl.cfg.use_memory and wl.gstep is None and not args.emulate_ranks:
+    if args.full and world == 1 and not wl_gone and not args.no_drop_in and not (wl.force_dist or args.deterministic) and wl.mvs is None and wl.cfg.use_memory and wl.gstep is None and not args.emulate_ranks:
         try:
             out.setdefault("secondary", {})["drop_in_surface"] = drop_in_surface(wl)
             di = out["secondary"]["drop_in_surface"]
@@ -1296,7 +1381,7 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from pfotgnrec_amd.synthetic import CONFIGS, make_graph
         try:
             threads = os.cpu_count() or 1

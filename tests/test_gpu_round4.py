@@ -32,7 +32,7 @@ def test_bench_rank_path_on_rccl_world1(allreduce):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.pop("PFO_DIST_BACKEND", None)
     out = subprocess.run(["timeout", "-k", "10", "420", sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--config", "C2",
-                          "--batch", "64", "--steps", "8", "--warmup", "3", "--min-seconds", "0.2", "--no-cpu-baseline", "--graph", "off",
+                          "--batch", "64", "--steps", "8", "--warmup", "3", "--min-seconds", "0.2", "--full", "--no-cpu-baseline", "--graph", "off",
                           "--allreduce", allreduce], env=env, capture_output=True)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     rec = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -484,7 +484,15 @@ def test_side_stream_sits_in_a_priority_class_of_its_own():
     import ctypes
     import pfotgnrec_amd  # noqa: F401
     from pfotgnrec_amd import _lib
-    assert int(os.environ["GPU_MAX_HW_QUEUES"]) >= 8
+    # (this process's environment may carry the caller's own value: the import's default is read in fresh interpreters)
+    probe = "import os, pfotgnrec_amd; print(os.environ['GPU_MAX_HW_QUEUES'])"
+    for caller, want in ((None, lambda v: v >= 8), ("5", lambda v: v == 5)):
+        env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+        if caller is not None:
+            env["GPU_MAX_HW_QUEUES"] = caller
+        out = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-c", probe], cwd=REPO, env=env, capture_output=True)
+        assert out.returncode == 0, out.stderr.decode()[-2000:]
+        assert want(int(out.stdout.decode().split()[-1])), (caller, out.stdout.decode())
     ptr = _lib.load().pfo_tgn_side_stream()
     assert ptr
     hip = ctypes.CDLL("libamdhip64.so")

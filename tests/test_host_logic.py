@@ -240,6 +240,52 @@ def test_synthetic_eight_gpu_line_carries_the_fields_the_driver_reads():
     assert b.check_line_schema({k: line[k] for k in line if k != "secondary"} | {"n_gpus": 1, "config": {}}, 1) == []
 
 
+def test_bench_plain_run_times_exactly_the_given_steps(monkeypatch):
+    """A plain run times --steps steps once and measures nothing beside the headline figure; --full brings the rest."""
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = b.parse()
+    assert args.steps == 7 and args.min_seconds == 0 and not args.full and args.dump_outputs is None and not args.deterministic
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = b.parse()
+    assert args.full and args.dump_outputs == "out"
+    assert args.deterministic                  # a run that writes its outputs writes the same ones every time
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs on a C2-sized node state (too large for 64 MB): the nodes of the last batch plus a seeded sample of the
+    others, the same rows on every run, every file float32 / float64, 64 MB in all."""
+    import os
+    import types
+    import torch
+    b = _bench()
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    n, D, B = 50501, 172, 512
+    g = torch.Generator().manual_seed(0)
+    mem = types.SimpleNamespace(memory=torch.randn(n, D, generator=g), last_update=torch.rand(n, generator=g),
+                                msg_table=torch.randn(n, 4 * D, generator=g), msg_time=torch.rand(n, generator=g),
+                                has_msg=(torch.rand(n, generator=g) > 0.5).to(torch.uint8))
+    tgn = types.SimpleNamespace(join=lambda: None, flat_parameters=torch.randn(1_500_000, generator=g), memory=mem)
+    src, dst = torch.randint(0, n, (4 * B,), dtype=torch.int32, generator=g), torch.randint(0, n, (4 * B,), dtype=torch.int32, generator=g)
+    wl = types.SimpleNamespace(torch=torch, tgn=tgn, last_emb=torch.randn(5 * B, D, generator=g), last_sl=slice(B, 2 * B),
+                               src_all=src, dst_all=dst)
+    got = []
+    for run in ("a", "b"):
+        b.dump_outputs(wl, 0.69, str(tmp_path / run))
+        files = sorted(os.listdir(tmp_path / run))
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 << 20
+        got.append({f: np.load(tmp_path / run / f) for f in files})
+    assert got[0].keys() == got[1].keys() and all(np.array_equal(got[0][f], got[1][f]) for f in got[0])
+    out = got[0]
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["loss.npy"][0] == np.float32(0.69) and out["embeddings.npy"].shape == (5 * B, D)
+    rows = out["node_rows.npy"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and len(rows) > 10000
+    assert np.isin(np.concatenate([src[B:2 * B].numpy(), dst[B:2 * B].numpy()]), rows).all()
+    assert np.array_equal(out["memory.npy"], mem.memory.numpy()[rows])
+    assert np.array_equal(out["message_pending.npy"], mem.has_msg.numpy()[rows].astype(np.float32))
+
+
 def test_predicted_ring_time_of_the_gradient_all_reduce():
     """The stub collective of --emulate-ranks spins for this long on the side stream: 6.2 MB of fp32 gradients, ring over xGMI
     (2 (N-1)/N of the buffer per link direction at ~153 GB/s + 2 (N-1) hops)."""

@@ -22,14 +22,14 @@ case $mode in
     [ $rc -ne 0 ] && grep -n "Error\|assert \|FAILED" $out/pytest.log | head -40
     exit $rc ;;
   bench)
-    timeout -k 10 600 python bench.py --no-cpu-baseline "$@" 2>$out/bench.err | tee $out/bench.jsonl | line ;;
+    timeout -k 10 600 python bench.py --full --min-seconds 2 --no-cpu-baseline "$@" 2>$out/bench.err | tee $out/bench.jsonl | line ;;
   ab)
     variants=$1; shift
     for rep in 1 2; do for v in $variants; do
       echo "== $v"
       envs=""; [ "$v" != "-" ] && envs=${v//,/ }
       case $v in lib:*) envs="PFOTGN_LIB=$GRAFT_REPO_ROOT/pfotgnrec_amd/lib/libpfotgn_${v#lib:}.so" ;; esac
-      env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-drop-in --min-seconds 1.0 "$@" 2>/dev/null | line
+      env $envs timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-drop-in --min-seconds 1.0 "$@" 2>/dev/null | line
     done; done 2>&1 | tee $out/ab.txt ;;
   stamps)
     PFOTGN_LIB=$GRAFT_REPO_ROOT/pfotgnrec_amd/lib/libpfotgn_stamps.so timeout -k 10 300 python tools/probes/runs_stamps.py "$@" 2>&1 | grep -v amdgpu.ids | tee $out/stamps.txt ;;

@@ -12,7 +12,7 @@ out=gpurun_out/${tag}_${key}
 mkdir -p $out
 CMD="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-prof --no-drop-in --min-seconds 0 $*"
 # the bench line of the SAME build on the same box (no tracer), embedded in the summary (bench_line_same_build)
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-drop-in $* 2>/dev/null | tail -1 > $out/bench_line.json
+python3 bench.py --full --steps 20 --warmup 5 --min-seconds 2 --no-cpu-baseline --no-drop-in $* 2>/dev/null | tail -1 > $out/bench_line.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- $CMD > $out/bench_under_trace.log 2>&1
 # one step kernel by kernel (before the raw per-dispatch table is dropped below)
 mkdir -p gpurun_out/profiles_out

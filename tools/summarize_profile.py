@@ -69,7 +69,7 @@ try:
     bl = json.loads(open(os.path.join(src, "bench_line.json")).read().strip().splitlines()[-1])
     bench_line = {"value": bl["value"], "unit": bl["unit"], "ms_per_step": bl["ms_per_step"], "timed_steps": bl["config"].get("timed_steps"),
                   "block_ms_per_step": bl["config"].get("block_ms_per_step"),
-                  "note": "python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-drop-in %s on the box and build of these passes, no tracer" % bench_args}
+                  "note": "python3 bench.py --full --steps 20 --warmup 5 --min-seconds 2 --no-cpu-baseline --no-drop-in %s on the box and build of these passes, no tracer" % bench_args}
 except Exception:
     pass
 out = {"workload": key,
