@@ -52,63 +52,14 @@ struct GemmDev {
   int dyn_chunk;                   // split-K chunk = f(device-side K) instead of split_chunk
   const void* b_img; int b_img_rows;   // pre-split bf16x3 image of B (source 0) and its padded row count
   const void* b_img2;                  // ... of the second K-concatenated source (same padded row count)
-  // GRU gate backward epilogue of the 32-row kernel (gemm.hpp PfoGemm::gg_*)
-  const float* gg_gates; const float* gg_h; const uint8_t* gg_hm; const float* gg_dh0; float* gg_dgi; float* gg_dgh;
 };
 
 static bool aligned4(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-#ifndef PFO_DEFAULT_TILE
-#define PFO_DEFAULT_TILE 0
-#endif
-#ifndef PFO_DEFAULT_BF16X3
-#define PFO_DEFAULT_BF16X3 1
-#endif
-#ifndef BX_EXP
-#define BX_EXP 0      // timing-only ablations of the bf16x3 kernel (wrong results): 1 = first tile only, 2 = no MFMA, 3 = no LDS refill
-#endif
-#ifndef PFO_DEFAULT_AREG
-#define PFO_DEFAULT_AREG 1
-#endif
-#ifndef BXA_NT
-#define BXA_NT 0         // A/B: nontemporal stores in the image kernels' epilogue
-#endif
-#ifndef BXA_STAGGER
-#define BXA_STAGGER 0    // A/B: the second workgroup of every CU's first round starts BXA_STAGGER x 3.4 us late (phases of the two differ)
-#endif
-#ifndef PFO_DEFAULT_TN8
-#define PFO_DEFAULT_TN8 500      // weight-gradient launches whose problems all have >= this many rows take 256-row tiles (0 = never)
-#endif
-#ifndef PFO_DEFAULT_ASTAT
-#define PFO_DEFAULT_ASTAT 1
-#endif
-#ifndef PFO_DEFAULT_AREG8
-#define PFO_DEFAULT_AREG8 512 // the image kernel's large form as eight single-strip wavefronts (gemm_bx_areg8_kernel) from this many workgroups on
-#endif
-#ifndef BXA_EPI
-#define BXA_EPI 1        // gemm_bx_areg_kernel: loads of the epilogue in front of its stores (0 = the round-3 form, kept for the A/B)
-#endif
-#ifndef BXA_STAMPS
-#define BXA_STAMPS 0     // diagnostic build: per-workgroup wall-clock stamps (100 MHz) of gemm_bx_areg_kernel, read by pfo_debug_bxa_stamps
-#endif
-#if BXA_STAMPS
-__device__ uint64_t g_bxa_stamps[4096 * 8];
-extern "C" int pfo_debug_bxa_stamps(uint64_t* host_out, int n_words) {
-  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_bxa_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;
-}
-#define BXA_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096) g_bxa_stamps[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
-#else
-#define BXA_STAMP(k) do { } while (0)
-#endif
-#ifndef BXA_ABL
-#define BXA_ABL 0        // timing-only ablations of gemm_bx_areg_kernel (wrong results), bits: 1 no MFMA, 2 no stores, 4 A rows of tile 0 only
-#endif                   //   (cache hits), 8 no image DMA after the first tile, 16 no row split after the first tile
-#ifndef PFO_BX_MIN_TILES
-#define PFO_BX_MIN_TILES 400
-#endif
-#ifndef GEMM_EXP
-#define GEMM_EXP 0       // timing-only ablations (wrong results): 1 = no global loads / LDS stores after the first tile, 2 = no MFMA,
-#endif                   //                                          3 = no barriers + no reloads
+// launch thresholds of the dispatch (pfo_gemm_launch, pfo_gemm_tn_group_launch)
+constexpr int BX_MIN_TILES = 400;   // row-major launches with images: fewer 128 x 176 tiles take the 32-row kernel, more the 128-row ones
+constexpr int BX_AREG8_MIN = 512;   // ... the 128-row form as eight single-strip wavefronts (gemm_bx_areg8_kernel) from this many tiles on
+constexpr int TN8_MIN_ROWS = 500;   // weight-gradient launches whose problems all have >= this many rows take 256-row tiles
 
 // four consecutive floats of which `nv` lie inside the matrix; `safe` is any valid 16-byte aligned address,
 // loaded instead of an out-of-range one so that the load itself needs no branch
@@ -344,7 +295,7 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& p, const int bx, const 
     }
   };
 
-  if constexpr (TINY && GEMM_EXP == 0) {
+  if constexpr (TINY) {
     // The small problems (composite weights, their gradient chains) are a handful of workgroups beside the step's large
     // launches: a k-tile costs one memory round trip, not its 16 MFMAs per wavefront.  Two tiles of loads stay in flight
     // (two register sets; the loop is unrolled by two so that the sets are compile-time names).
@@ -373,12 +324,12 @@ __device__ __forceinline__ void gemm_tile(const GemmDev& p, const int bx, const 
     store_tile(0, a_reg, b_reg);
     __syncthreads();
     for (int t = 0; t < T; ++t) {
-      const bool more = (GEMM_EXP == 1 || GEMM_EXP == 3) ? false : (t + 1 < T);
+      const bool more = t + 1 < T;
       if (more) load_tile(t + 1, a_reg, b_reg);  // global loads in flight during the MFMAs below
-      if (GEMM_EXP != 2) compute_tile(0);
-      if (GEMM_EXP != 3) __syncthreads();        // every wavefront is done reading the tile
+      compute_tile(0);
+      __syncthreads();        // every wavefront is done reading the tile
       if (more) store_tile(0, a_reg, b_reg);
-      if (GEMM_EXP != 3) __syncthreads();
+      __syncthreads();
     }
   }
 
@@ -434,16 +385,11 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_f32_kernel(const GemmDev p)
 }
 
 // ---------------------------------------------------------------------------------------------
-// fp32 contraction on the BF16 matrix cores by a 3-way split ("bf16x3"): x = x1 + x2 + x3 with x1 = hi16(x),
-// x2 = hi16(x - x1), x3 = hi16(x - x1 - x2) (24 mantissa bits in three bf16 pieces, residuals exact), and
-//   a.b ~= a1b1 + (a1b2 + a2b1) + (a2b2 + a1b3 + a3b1)          (dropped terms <= 2^-24 |a||b|)
-// accumulated in fp32 by v_mfma_f32_16x16x32_bf16.  Six bf16 MFMAs (16 cycles each) replace eight fp32 MFMAs
-// (32 cycles each) per 16x16x32 block: 2.7x the matrix rate at fp32-level accuracy (validated against fp64 in
-// tests/test_gpu_kernels.py).  Row-major A and B only (the nn.Linear layout); same tile, staging and epilogue as
-// the fp32 kernel.  LDS image per piece: [row][32 bf16] = 64-byte rows, 16-byte k-chunks XOR-swizzled with
-// f(row >> 2) = {0,3,2,1} so that every ds_read_b128 fragment read covers all 64 banks exactly once.
+// fp32 contraction on the 16-bit matrix cores by a split of every operand element into pieces ("bf16x3" in the names: the
+// round-2 form had three bf16 pieces; the format below has two fp16 ones).  LDS image per piece: [row][32 halves] = 64-byte
+// rows, 16-byte k-chunks XOR-swizzled with f(row >> 2) = {0,3,2,1} so that every ds_read_b128 fragment read covers all 64
+// banks exactly once.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define BX_A_PIECE (BM * 64)     // bytes per piece of the A tile
 #define BX_B_PIECE (BN * 64)
 
 template <int N, typename F, int I = 0>
@@ -451,35 +397,6 @@ __device__ __forceinline__ void bx_for(F&& f) {
   if constexpr (I < N) { f(std::integral_constant<int, I>{}); bx_for<N, F, I + 1>(static_cast<F&&>(f)); }
 }
 __device__ __forceinline__ int bx_swz(int row) { return (4 - ((row >> 2) & 3)) & 3; }   // {0,3,2,1}
-
-// 3-way bf16 split of four fp32 values, packed two per dword (element e in the low half of dword e/2):
-// 4 VALU per value (and, sub, and, sub: the residuals are exact) + one v_perm_b32 per pair and piece
-__device__ __forceinline__ void bx_split4(const float4 v, uint2& o1, uint2& o2, uint2& o3) {
-  const float x[4] = {v.x, v.y, v.z, v.w};
-  uint32_t p1[4], p2[4], p3[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    p1[e] = __float_as_uint(x[e]);
-    const float r1 = x[e] - __uint_as_float(p1[e] & 0xFFFF0000u);                 // exact
-    p2[e] = __float_as_uint(r1);
-    const float r2 = r1 - __uint_as_float(p2[e] & 0xFFFF0000u);                   // exact
-    p3[e] = __float_as_uint(r2);
-  }
-  constexpr uint32_t HI2 = 0x07060302u;                                            // {hi16(a), hi16(b)} -> a in the upper half
-  o1 = uint2{__builtin_amdgcn_perm(p1[1], p1[0], HI2), __builtin_amdgcn_perm(p1[3], p1[2], HI2)};
-  o2 = uint2{__builtin_amdgcn_perm(p2[1], p2[0], HI2), __builtin_amdgcn_perm(p2[3], p2[2], HI2)};
-  o3 = uint2{__builtin_amdgcn_perm(p3[1], p3[0], HI2), __builtin_amdgcn_perm(p3[3], p3[2], HI2)};
-}
-
-__device__ __forceinline__ void bx_split_store(char* base, int piece_bytes, int row, int c4, const float4 v) {
-  // float4 = 4 consecutive k of one row: k = 4*c4 .. 4*c4+3 -> 16-byte chunk c4 >> 1, half c4 & 1
-  const int off = row * 64 + (((c4 >> 1) ^ bx_swz(row)) << 4) + ((c4 & 1) << 3);
-  uint2 o1, o2, o3;
-  bx_split4(v, o1, o2, o3);
-  *reinterpret_cast<uint2*>(base + off) = o1;
-  *reinterpret_cast<uint2*>(base + piece_bytes + off) = o2;
-  *reinterpret_cast<uint2*>(base + 2 * piece_bytes + off) = o3;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Second split format (FMT 1, "fp16x2"): every fp32 operand element is the sum of TWO fp16 pieces of its value times a power of
@@ -502,19 +419,11 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define HX_EMAX 254
 #define HX_TOP 141            // a row whose exponent is E is scaled by 2^(HX_TOP - E): maximum in [2^14, 2^15)
 #define HX_GROW 2             // binades of headroom a row takes when its running maximum outgrows its scale (see bx_split_rows)
+// Every pre-split image and every kernel that reads one uses this format.  FMT stays a template parameter of those kernels
+// (their symbols carry it); 1 is its only value.
 template <int FMT> struct BxFmt;
-template <> struct BxFmt<0> { static constexpr int NP = 3; };
 template <> struct BxFmt<1> { static constexpr int NP = 2; };
-// process-wide choice of the format of every pre-split image and of the kernels that read them (A/B switch: PFO_BX_FMT=0)
-#define PFO_DEFAULT_BX_FMT 1
-#define PFO_DEFAULT_TN_FMT 1     // the weight-gradient tile: 1 = two fp16 pieces with one scale per operand and K-slab, 0 = bf16x3
-#ifndef BX_AREG_OCC
 #define BX_AREG_OCC 2
-#endif
-int pfo_bx_fmt() {
-  static const int f = getenv("PFO_BX_FMT") ? (atoi(getenv("PFO_BX_FMT")) != 0 ? 1 : 0) : PFO_DEFAULT_BX_FMT;
-  return f;
-}
 __device__ __forceinline__ int hx_exp_of(float m) {           // biased exponent of |m| (m >= 0), clamped
   return min(max((int)(__float_as_uint(m) >> 23), HX_EMIN), HX_EMAX);
 }
@@ -545,29 +454,16 @@ __device__ __forceinline__ void hx_split4(const float4 v, int se, uint2& oh, uin
 // operand), y = the other one.  FMT 0: pieces hi | mid | lo (bf16), FMT 1: hi | lo (fp16)
 template <int FMT>
 __device__ __forceinline__ f32x4 bx_mma(const u32x4 (&x)[BxFmt<FMT>::NP], const u32x4 (&y)[BxFmt<FMT>::NP], f32x4 c) {
-  if constexpr (FMT == 0) {
-    typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-#define BXM(q, w) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8, x[q]), __builtin_bit_cast(v8, y[w]), c, 0, 0, 0)
-    BXM(0, 2); BXM(2, 0); BXM(1, 1); BXM(0, 1); BXM(1, 0); BXM(0, 0);
-#undef BXM
-  } else {
 #define BXM(q, w) c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, x[q]), __builtin_bit_cast(f16x8, y[w]), c, 0, 0, 0)
-    BXM(0, 1); BXM(1, 0); BXM(0, 0);
+  BXM(0, 1); BXM(1, 0); BXM(0, 0);
 #undef BXM
-  }
   return c;
 }
 // product Q of bx_mma's list alone (two accumulators interleaved: a dependent MFMA waits for its predecessor's result)
 template <int FMT, int Q>
 __device__ __forceinline__ f32x4 bx_mma_q(const u32x4 (&x)[BxFmt<FMT>::NP], const u32x4 (&y)[BxFmt<FMT>::NP], f32x4 c) {
-  if constexpr (FMT == 0) {
-    typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-    constexpr int qx[6] = {0, 2, 1, 0, 1, 0}, qy[6] = {2, 0, 1, 1, 0, 0};
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8, x[qx[Q]]), __builtin_bit_cast(v8, y[qy[Q]]), c, 0, 0, 0);
-  } else {
-    constexpr int qx[3] = {0, 1, 0}, qy[3] = {1, 0, 0};
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, x[qx[Q]]), __builtin_bit_cast(f16x8, y[qy[Q]]), c, 0, 0, 0);
-  }
+  constexpr int qx[3] = {0, 1, 0}, qy[3] = {1, 0, 0};
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, x[qx[Q]]), __builtin_bit_cast(f16x8, y[qy[Q]]), c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x4 hx_scale4(const f32x4 a, const int4 e, int base) {          // a[c] * 2^(base + e[c])
   return f32x4{__builtin_amdgcn_ldexpf(a[0], base + e.x), __builtin_amdgcn_ldexpf(a[1], base + e.y),
@@ -581,13 +477,7 @@ __device__ __forceinline__ void bx_split_rows(const float4 (&a_raw)[S][2], u32x4
                                               const bool first) {
 #pragma unroll
   for (int i = 0; i < S; ++i) {
-    if constexpr (FMT == 0) {
-      uint2 lo[3], hi[3];
-      bx_split4(a_raw[i][0], lo[0], lo[1], lo[2]);
-      bx_split4(a_raw[i][1], hi[0], hi[1], hi[2]);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) a[i][q] = u32x4{lo[q].x, lo[q].y, hi[q].x, hi[q].y};
-    } else {
+    {
       // the row's maximum over this k-tile: 8 values here, the other 24 in the lanes 16 / 32 / 48 further on
       const int e = hx_exp_of_bits(hx_max_over_g(__float_as_uint(hx_absmax8(a_raw[i][0], a_raw[i][1]))));
       if (e > rowE[i]) {                                     // a larger value than any before: the sums so far move to the new scale
@@ -614,39 +504,6 @@ __device__ __forceinline__ void bx_split_rows(const float4 (&a_raw)[S][2], u32x4
 }
 
 // epilogue of the operand-swapped bf16x3 kernels: four consecutive columns col..col+3 of one output row
-// GRU gate backward for hidden units col .. col+3 of table row `row` (PfoGemm::gg_*): v = the row's query-side gradient
-__device__ __forceinline__ void bx_gru_gates4(const GemmDev& p, int row, int col, const f32x4 v) {
-  const int D = p.N;
-  float o[4][4] = {};                                  // [dpr | dpz | dpn | dpn r][unit]
-  if (p.gg_hm[row]) {
-    const int64_t e = (int64_t)row * D + col;
-    const float* gs = p.gg_gates + (int64_t)row * 4 * D + col;
-    const float4 h4 = *reinterpret_cast<const float4*>(p.gg_h + e), k4 = *reinterpret_cast<const float4*>(p.gg_dh0 + e);
-    const float4 r4 = *reinterpret_cast<const float4*>(gs), z4 = *reinterpret_cast<const float4*>(gs + D);
-    const float4 n4 = *reinterpret_cast<const float4*>(gs + 2 * D), g4 = *reinterpret_cast<const float4*>(gs + 3 * D);
-    const float dh[4] = {k4.x + v[0], k4.y + v[1], k4.z + v[2], k4.w + v[3]};      // key side (scattered by the attention backward) + query side
-    const float hh[4] = {h4.x, h4.y, h4.z, h4.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w}, zz[4] = {z4.x, z4.y, z4.z, z4.w};
-    const float nn[4] = {n4.x, n4.y, n4.z, n4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float dn = dh[u] * (1.f - zz[u]);
-      const float dz = dh[u] * (hh[u] - nn[u]);
-      const float dpn = dn * (1.f - nn[u] * nn[u]);
-      const float dr = dpn * gg[u];
-      o[0][u] = dr * rr[u] * (1.f - rr[u]);
-      o[1][u] = dz * zz[u] * (1.f - zz[u]);
-      o[2][u] = dpn;
-      o[3][u] = dpn * rr[u];
-    }
-  }
-  float* gis = p.gg_dgi + (int64_t)row * 3 * D + col;
-  float* ghs = p.gg_dgh + (int64_t)row * 3 * D + col;
-  const float4 a = {o[0][0], o[0][1], o[0][2], o[0][3]}, b = {o[1][0], o[1][1], o[1][2], o[1][3]};
-  const float4 c = {o[2][0], o[2][1], o[2][2], o[2][3]}, c2 = {o[3][0], o[3][1], o[3][2], o[3][3]};
-  *reinterpret_cast<float4*>(gis) = a; *reinterpret_cast<float4*>(gis + D) = b; *reinterpret_cast<float4*>(gis + 2 * D) = c;
-  *reinterpret_cast<float4*>(ghs) = a; *reinterpret_cast<float4*>(ghs + D) = b; *reinterpret_cast<float4*>(ghs + 2 * D) = c2;
-}
-
 __device__ __forceinline__ void bx_store4(const GemmDev& p, float* Cb, int64_t ldc, const float* bias, float rscale, bool zero,
                                           bool n4, int row, int col, const f32x4 a, const float* addrow = nullptr) {
   float v[4] = {a[0], a[1], a[2], a[3]};
@@ -664,8 +521,7 @@ __device__ __forceinline__ void bx_store4(const GemmDev& p, float* Cb, int64_t l
       const float4 m = *reinterpret_cast<const float4*>(p.relu_src + (int64_t)row * p.relu_ld + col);
       v[0] = m.x > 0.f ? v[0] : 0.f; v[1] = m.y > 0.f ? v[1] : 0.f; v[2] = m.z > 0.f ? v[2] : 0.f; v[3] = m.w > 0.f ? v[3] : 0.f;
     }
-    if (BXA_NT) __builtin_nontemporal_store(f32x4{v[0], v[1], v[2], v[3]}, reinterpret_cast<f32x4*>(cp));
-    else *reinterpret_cast<float4*>(cp) = float4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<float4*>(cp) = float4{v[0], v[1], v[2], v[3]};
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -687,187 +543,6 @@ __device__ __forceinline__ bool bx_n4(const GemmDev& p, const float* Cb, int64_t
          (!p.relu_src || ((p.relu_ld & 3) == 0 && (((uintptr_t)p.relu_src) & 15) == 0)) && (!bias || (((uintptr_t)bias) & 15) == 0);
 }
 
-template <bool BSPLIT>
-__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16x3_kernel(const GemmDev p) {
-  __shared__ __attribute__((aligned(16))) char lds[3 * BX_A_PIECE + 3 * BX_B_PIECE];
-  char* const As = lds;
-  char* const Bs = lds + 3 * BX_A_PIECE;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-  const int zb = blockIdx.z;
-  int Mlim = p.M;
-  if (p.m_dev) Mlim = min(Mlim, *p.m_dev);
-  if (m0 >= Mlim) return;
-  const int wrow = 32 * wave;
-
-  f32x4 acc[2][11];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 11; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int T0 = (p.K[0] + BK - 1) / BK;
-  const int T1 = (p.K[1] > 0 && p.A[1]) ? (p.K[1] + BK - 1) / BK : 0;
-  const int T = T0 + T1;
-  constexpr int NB = BSPLIT ? 9 : 6;                  // staged 16-byte units of B per thread
-  float4 a_reg[4], b_reg[6];
-  f32x4 i_reg[NB];                                    // (vector type: a struct copy here would pin the array in scratch)
-  const float* a_row[4];
-  const float* b_row[6];
-  bool a_ok[4], b_ok[6];
-  int Ks = 0, cur_src = -1;
-  const float* safe = p.A[0];
-  // pre-split B: tile t, piece q of the rows n0.. is one contiguous BX_B_PIECE-byte run of the image
-  const char* img = nullptr;                           // bound per source in bind_src
-  const int64_t img_piece = (int64_t)p.b_img_rows * 64;
-
-  auto bind_src = [&](int src) {
-    cur_src = src;
-    Ks = p.K[src];
-    const float* Ab = p.A[src] + zb * p.a_bs[src];
-    const float* Bb = p.B[src] + zb * p.b_bs[src];
-    if constexpr (BSPLIT) img = reinterpret_cast<const char*>(src == 0 ? p.b_img : p.b_img2) + (int64_t)n0 * 64;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int gm = m0 + ((tid + 256 * i) >> 3);
-      a_ok[i] = gm < Mlim;
-      int64_t ridx = a_ok[i] ? gm : 0;
-      if (a_ok[i] && p.a_idx[src]) ridx = p.a_idx[src][gm];
-      a_row[i] = Ab + ridx * p.lda[src];
-    }
-    if constexpr (!BSPLIT) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int f = tid + 256 * i;
-        const int gn = n0 + (f >> 3);
-        b_ok[i] = (f < BN * 8) && gn < p.N;
-        b_row[i] = Bb + (int64_t)(b_ok[i] ? gn : 0) * p.ldb[src];
-      }
-    }
-  };
-  auto load_tile = [&](int t) {
-    const int src = t < T0 ? 0 : 1;
-    if (src != cur_src) bind_src(src);
-    const int k0 = (src == 0) ? t * BK : (t - T0) * BK;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = k0 + 4 * ((tid + 256 * i) & 7);
-      a_reg[i] = ld4<true>(a_row[i] + k, a_ok[i] ? Ks - k : 0, safe);
-    }
-    if constexpr (BSPLIT) {
-      const char* tile = img + (int64_t)(src == 0 ? t : t - T0) * 3 * img_piece;
-      // 3 pieces x 704 units of 16 bytes = 8.25 units per thread (tail clamped); piece boundaries fall at units 704, 1408
-      bx_for<9>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        const int unit = min(tid + 256 * u, 3 * (BX_B_PIECE / 16) - 1);
-        const int q = (unit >= 2 * (BX_B_PIECE / 16)) ? 2 : (unit >= BX_B_PIECE / 16 ? 1 : 0);
-        i_reg[u] = *reinterpret_cast<const f32x4*>(tile + q * img_piece + (unit - q * (BX_B_PIECE / 16)) * 16);
-      });
-    } else {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int k = k0 + 4 * ((tid + 256 * i) & 7);
-        b_reg[i] = ld4<true>(b_row[i] + k, b_ok[i] ? Ks - k : 0, safe);
-      }
-    }
-  };
-  auto store_tile = [&]() {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int f = tid + 256 * i;
-      bx_split_store(As, BX_A_PIECE, f >> 3, f & 7, a_reg[i]);
-    }
-    if constexpr (BSPLIT) {
-      bx_for<9>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        const int unit = tid + 256 * u;
-        if (u < 8 || unit < 3 * (BX_B_PIECE / 16)) *reinterpret_cast<f32x4*>(Bs + unit * 16) = i_reg[u];
-      });
-    } else {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int f = tid + 256 * i;
-        if (f < BN * 8) bx_split_store(Bs, BX_B_PIECE, f >> 3, f & 7, b_reg[i]);
-      }
-    }
-  };
-  const int frag_off = r * 64 + ((g ^ bx_swz(r)) << 4);     // rows of a strip start at multiples of 16: same swizzle
-  const bool strip_on[2] = {m0 + wrow < p.M, m0 + wrow + 16 < p.M};
-  auto compute_tile = [&]() {
-    bf16x8 a[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) a[i][q] = *reinterpret_cast<const bf16x8*>(As + q * BX_A_PIECE + (wrow + 16 * i) * 64 + frag_off);
-    // B fragments are double-buffered in registers: the LDS reads of column tile j+1 are in flight during the 12
-    // MFMAs of tile j (with one register set the reads could only issue after those MFMAs, latency fully exposed)
-    auto ldb = [&](bf16x8 (&b)[3], int j) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) b[q] = *reinterpret_cast<const bf16x8*>(Bs + q * BX_B_PIECE + (16 * j) * 64 + frag_off);
-    };
-    auto mma = [&](const bf16x8 (&b)[3], int j) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        if (!strip_on[i]) continue;
-        f32x4 c = acc[i][j];
-        // operands swapped (weights as the MFMA "A" side): the accumulator holds the TRANSPOSED tile, lane (r, g)
-        // owns row r and the four consecutive columns 4g..4g+3 - 16-byte epilogue accesses.  Smallest terms first.
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0], a[i][2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[2], a[i][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[1], a[i][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0], a[i][1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[1], a[i][0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[0], a[i][0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
-    };
-    bf16x8 b0[3], b1[3];
-    ldb(b0, 0);
-#pragma unroll
-    for (int j = 0; j < 11; j += 2) {
-      if (j + 1 < 11) ldb(b1, j + 1);
-      mma(b0, j);
-      if (j + 2 < 11) ldb(b0, j + 2);
-      if (j + 1 < 11) mma(b1, j + 1);
-    }
-  };
-
-  if (T > 0) {
-    load_tile(0);
-    store_tile();
-    __syncthreads();
-    for (int t = 0; t < T; ++t) {
-      const bool more = (BX_EXP == 1) ? false : (t + 1 < T);
-      if (more) load_tile(t + 1);
-      if (BX_EXP != 2) compute_tile();
-      __syncthreads();
-      if (more && BX_EXP != 3) store_tile();
-      __syncthreads();
-    }
-  }
-
-  float* Cb = p.C + zb * p.c_bs;
-  const int64_t ldc = p.ldc;
-  const float* bias = p.bias ? p.bias + zb * p.bias_bs : nullptr;
-  const float* rs = p.row_scale ? p.row_scale + zb * p.rs_bs : nullptr;
-  const bool n4 = bx_n4(p, Cb, ldc, bias);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = m0 + wrow + 16 * i + r;
-    if (row >= Mlim) continue;
-    const float rscale = rs ? rs[(int64_t)row * p.rs_ld] : 1.f;
-    const bool zero = p.row_zero ? (p.row_zero[row] != 0) : false;
-    const float* addrow = p.add_src ? p.add_src + (int64_t)(p.add_idx ? p.add_idx[row] : row) * p.add_ld : nullptr;
-#pragma unroll
-    for (int j = 0; j < 11; ++j) {
-      const int col = n0 + 16 * j + 4 * g;
-      if (col < p.N) bx_store4(p, Cb, ldc, bias, rscale, zero, n4, row, col, acc[i][j], addrow);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // Second form of the pre-split-image kernel: the A tile never touches LDS.  Every wavefront loads the 32 rows it owns
 // straight in MFMA fragment order (lane (r, g): row r, k = 8g..8g+7 = two float4), splits them in registers into the
@@ -883,22 +558,6 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
   const int lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, g = lane >> 4;
   int tile_m = blockIdx.x, tile_n = blockIdx.y;
-  BXA_STAMP(0);
-#if BXA_STAMPS
-  if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096) {
-    uint32_t hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    g_bxa_stamps[blockIdx.x * 8 + 7] = ((uint64_t)xcc << 32) | hw;
-  }
-#endif
-  if (BXA_STAGGER > 0) {
-    const int lin = blockIdx.x + blockIdx.y * gridDim.x;
-    if (lin < 512 && ((lin >> 8) & 1)) {
-#pragma unroll 1
-      for (int k = 0; k < BXA_STAGGER; ++k) __builtin_amdgcn_s_sleep(127);
-    }
-  }
   if (p.xcd_tn > 0 && !xcd_tile(blockIdx.x, p.xcd_tm, p.xcd_tn, tile_m, tile_n)) return;
   const int m0 = tile_m * (16 * S * WAVES), n0 = tile_n * BN;
   int Mlim = p.M;
@@ -949,7 +608,7 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
     const int ts = src == 0 ? t : t - T0;
     const int k = ts * BK + 8 * g;
     const int Ks = p.K[src];
-    const int toff = (BXA_ABL & 4) ? 0 : ts * BK;
+    const int toff = ts * BK;
 #pragma unroll
     for (int i = 0; i < S; ++i)
 #pragma unroll
@@ -959,7 +618,6 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
   // B image tile -> LDS by asynchronous global->LDS loads (the LDS image IS the global image: a lane-linear copy, no
   // staging registers, no ds_write); `buf` is the buffer being filled for tile t
   auto load_b = [&](int t, int buf) {
-    if ((BXA_ABL & 8) && t > 0) return;
     const int src = t < T0 ? 0 : 1;
     const int ts = src == 0 ? t : t - T0;
     const char* tile = img[src] + (int64_t)ts * NP * img_piece;
@@ -980,13 +638,6 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
 #pragma unroll
   for (int i = 0; i < S; ++i) rowE[i] = HX_EMIN;    // FMT 1: biased exponent of the running maximum of this lane's two rows
   auto split_a = [&](auto setc, bool first) {
-    if ((BXA_ABL & 16) && !first) {
-#pragma unroll
-      for (int i = 0; i < S; ++i)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) asm volatile("" :: "v"(a_raw[decltype(setc)::value][i][h].x), "v"(a_raw[decltype(setc)::value][i][h].w));
-      return;
-    }
     bx_split_rows<FMT, 11, S>(a_raw[decltype(setc)::value], a, rowE, acc, first);
   };
   const int frag_off = r * 64 + ((g ^ bx_swz(r)) << 4);
@@ -997,34 +648,24 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
       for (int q = 0; q < NP; ++q) b[q] = *reinterpret_cast<const u32x4*>(Bs + q * BX_B_PIECE + (16 * j) * 64 + frag_off);
     };
     auto mma = [&](const u32x4 (&b)[NP], int j) {
-      if (BXA_ABL & 1) {
-#pragma unroll
-        for (int q = 0; q < NP; ++q) asm volatile("" :: "v"(b[q]), "v"(a[0][q]), "v"(a[1][q]));
-        return;
-      }
 #pragma unroll
       for (int i = 0; i < S; ++i) acc[i][j] = bx_mma<FMT>(b, a[i], acc[i][j]);     // operands swapped: image rows = accumulator columns
     };
     if constexpr (S == 1) {
       // one strip: the products of a column tile are ONE dependent chain - two column tiles are multiplied product by product
       // in turn, and the fragments of the next pair are read meanwhile (four register sets)
-      constexpr int NQ = FMT == 0 ? 6 : 3;
+      constexpr int NQ = 3;
       u32x4 bb[4][NP];
       ldb(bb[0], 0); ldb(bb[1], 1);
       bx_for<6>([&](auto pc) {
         constexpr int j = 2 * decltype(pc)::value, cs = (decltype(pc)::value & 1) * 2;
         if constexpr (j + 2 < 11) ldb(bb[2 - cs], j + 2);
         if constexpr (j + 3 < 11) ldb(bb[3 - cs], j + 3);
-        if (BXA_ABL & 1) {
-#pragma unroll
-          for (int q = 0; q < NP; ++q) asm volatile("" :: "v"(bb[cs][q]), "v"(bb[cs + 1][q]), "v"(a[0][q]));
-        } else {
-          bx_for<NQ>([&](auto qc) {
-            constexpr int Q = decltype(qc)::value;
-            acc[0][j] = bx_mma_q<FMT, Q>(bb[cs], a[0], acc[0][j]);
-            if constexpr (j + 1 < 11) acc[0][j + 1] = bx_mma_q<FMT, Q>(bb[cs + 1], a[0], acc[0][j + 1]);
-          });
-        }
+        bx_for<NQ>([&](auto qc) {
+          constexpr int Q = decltype(qc)::value;
+          acc[0][j] = bx_mma_q<FMT, Q>(bb[cs], a[0], acc[0][j]);
+          if constexpr (j + 1 < 11) acc[0][j + 1] = bx_mma_q<FMT, Q>(bb[cs + 1], a[0], acc[0][j + 1]);
+        });
       });
     } else {
     u32x4 b0[NP], b1[NP];
@@ -1041,10 +682,6 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
 
   using C0 = std::integral_constant<int, 0>;
   using C1 = std::integral_constant<int, 1>;
-#if BXA_STAMPS
-  uint32_t st_acc[4] = {0, 0, 0, 0};      // shader cycles of wavefront 0 in: MFMA + LDS reads | wait for the loads | row split | barrier
-  uint64_t st_loop0 = 0;
-#endif
   // one k-tile: the fragments of tile t are in `a`; queue the image of t+1 and the rows of t+2, multiply, split the rows of t+1
   auto step = [&](int t, auto curc) {
     constexpr int cur = decltype(curc)::value;                 // == t & 1
@@ -1063,33 +700,14 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
         }
       }
     }
-#if BXA_STAMPS
-    const uint64_t c0 = __builtin_amdgcn_s_memtime();
-#endif
     compute_tile(cur);
-#if BXA_STAMPS
-    asm volatile("s_nop 0" ::: "memory");
-    const uint64_t c1 = __builtin_amdgcn_s_memtime();
-    uint64_t c2 = c1, c3 = c1;
-#endif
     if (more) {
       // the DMA is ordered only by the issuing wave's vmcnt + the barrier; the four row loads of tile t+2 were issued last
       if (more2) { if constexpr (S == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if BXA_STAMPS
-      c2 = __builtin_amdgcn_s_memtime();
-#endif
       split_a(std::integral_constant<int, 1 - cur>{}, false);  // this wavefront's own fragments for tile t+1
-#if BXA_STAMPS
-      asm volatile("s_nop 0" ::: "memory");
-      c3 = __builtin_amdgcn_s_memtime();
-#endif
     }
     __syncthreads();
-#if BXA_STAMPS
-    const uint64_t c4 = __builtin_amdgcn_s_memtime();
-    st_acc[0] += (uint32_t)(c1 - c0); st_acc[1] += (uint32_t)(c2 - c1); st_acc[2] += (uint32_t)(c3 - c2); st_acc[3] += (uint32_t)(c4 - c3);
-#endif
   };
   if (T > 0) {
     load_a(0, C0{});
@@ -1098,23 +716,11 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     split_a(C0{}, true);
     __syncthreads();
-    BXA_STAMP(1);
-#if BXA_STAMPS
-    st_loop0 = __builtin_amdgcn_s_memtime();
-#endif
     for (int t = 0; t < T; t += 2) {
       step(t, C0{});
       if (t + 1 < T) step(t + 1, C1{});
     }
   }
-  BXA_STAMP(2);
-#if BXA_STAMPS
-  if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096) {
-    g_bxa_stamps[blockIdx.x * 8 + 5] = ((uint64_t)st_acc[1] << 32) | st_acc[0];
-    g_bxa_stamps[blockIdx.x * 8 + 6] = ((uint64_t)st_acc[3] << 32) | st_acc[2];
-    g_bxa_stamps[blockIdx.x * 8 + 3] = __builtin_amdgcn_s_memtime() - st_loop0;      // (overwritten by stamp 3 unless BXA_STAMPS == 2)
-  }
-#endif
 
   float* Cb = p.C;
   const int64_t ldc = p.ldc;
@@ -1122,8 +728,7 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
   const float* rs = p.row_scale;
   const bool n4 = bx_n4(p, Cb, ldc, bias);
   const int32_t* bexp_last = T1 > 0 ? bexp[1] : bexp[0];
-  if ((BXA_ABL & 2) && p.K[0] >= 0) return;
-  if (BXA_EPI && n4) {
+  if (n4) {
     // Every load of the epilogue BEFORE the first store.  The compiler may not move a load above a store that could alias it,
     // so "load the column's exponents, scale, store" 22 times over was a chain of 22 load latencies per wavefront, each behind
     // the previous store (in-kernel stamps, profiles/r5_areg_stamps.txt: 11 of a workgroup's 25 us at the d ctx' shape).
@@ -1222,11 +827,6 @@ __device__ __forceinline__ void bx_areg_body(const GemmDev& p, char* lds) {
     }
   }
   }
-#if BXA_STAMPS
-  if (BXA_STAMPS != 2) BXA_STAMP(3);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  BXA_STAMP(4);
-#endif
 }
 template <int FMT>
 __global__ __launch_bounds__(GEMM_THREADS, FMT == 1 ? BX_AREG_OCC : 2) void gemm_bx_areg_kernel(const GemmDev p) {
@@ -1344,7 +944,7 @@ __device__ __forceinline__ void bx_astat_body(const GemmDev& p, char* lds) {
   // landed when at most 4 + 2 + T younger operations are outstanding.  Members that do not exist (no stores before slot 2, no
   // DMA behind the last slot) are not counted: counting something that was never issued would make the wait too lax.
   auto wait_vm = [&](auto nc) {
-    constexpr int n = (FULL && BXA_ABL == 0) ? decltype(nc)::value : 0;
+    constexpr int n = FULL ? decltype(nc)::value : 0;
     static_assert(n <= 12, "vmcnt");
     if constexpr (n == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
     else if constexpr (n == 11) asm volatile("s_waitcnt vmcnt(11)" ::: "memory");
@@ -1360,29 +960,14 @@ __device__ __forceinline__ void bx_astat_body(const GemmDev& p, char* lds) {
     else if constexpr (n == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
-#if BXA_STAMPS
-  uint32_t st_acc[4] = {0, 0, 0, 0};
-  BXA_STAMP(1);
-  const uint64_t st_loop0 = __builtin_amdgcn_s_memtime();
-#endif
   // One slot: wait, barrier, then ONE straight-line block in which the 12 memory instructions of the slot (4 stores of the pair
   // multiplied one slot ago, 2 exponent loads, T DMA chunks of slot s+2) are spread between the k-tiles' MFMAs.  Issued in a
   // burst behind the barrier - by all four wavefronts at once - they queued in the CU's one texture-address unit for 1 430
   // cycles per slot while no wavefront multiplied (in-kernel stamps, profiles/r5_areg_stamps.txt).
   auto slot_body = [&](int s, auto hsc, auto hdc, auto nc) {
     constexpr bool HS = decltype(hsc)::value, HD = decltype(hdc)::value;
-#if BXA_STAMPS
-    const uint64_t c0 = __builtin_amdgcn_s_memtime();
-#endif
     wait_vm(nc);
-#if BXA_STAMPS
-    const uint64_t c1 = __builtin_amdgcn_s_memtime();
-#endif
     __syncthreads();                                               // DMA(s) of every wavefront has landed; slot (s-1) % RING is free
-#if BXA_STAMPS
-    const uint64_t c2 = __builtin_amdgcn_s_memtime();
-    const uint64_t c3 = c2;
-#endif
     const char* Bs = ring + (s % AS_RING) * (4 * AS_TMAX * 1024);
     char* dst = ring + ((s + 2) % AS_RING) * (4 * AS_TMAX * 1024);
     f32x4 acc[2][2];
@@ -1416,18 +1001,16 @@ __device__ __forceinline__ void bx_astat_body(const GemmDev& p, char* lds) {
         if constexpr (HS) {
           constexpr int jj = m >> 1, i = m & 1;
           const f32x4 v = hx_scale4(prev[jj][i], pexp[jj], rowE[i] - 2 * HX_TOP);
-          if ((FULL || ok[i]) && !((BXA_ABL & 2) && K > 0)) *reinterpret_cast<f32x4*>(crow[i] + 32 * (s - 1) + 16 * jj) = v;
+          if (FULL || ok[i]) *reinterpret_cast<f32x4*>(crow[i] + 32 * (s - 1) + 16 * jj) = v;
         }
       } else if constexpr (m < 6) {
         nexp[m - 4] = *reinterpret_cast<const int4*>(bexp + 32 * s + 16 * (m - 4) + 4 * g);
       } else if constexpr (m - 6 < T) {
         if constexpr (HD) {
-          if (!((BXA_ABL & 8) && K > 0)) {
-            const int c = wave + 4 * (m - 6);
-            const int q = c & 1, h = c >> 1, jj = h >= T ? 1 : 0, t = h - jj * T;
-            const char* src = img + ((int64_t)t * NP + q) * img_piece + (int64_t)(32 * (s + 2) + 16 * jj) * 64;
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + lane * 16), (lptr_t)(dst + c * 1024), 16, 0, 0);
-          }
+          const int c = wave + 4 * (m - 6);
+          const int q = c & 1, h = c >> 1, jj = h >= T ? 1 : 0, t = h - jj * T;
+          const char* src = img + ((int64_t)t * NP + q) * img_piece + (int64_t)(32 * (s + 2) + 16 * jj) * 64;
+          __builtin_amdgcn_global_load_lds((gptr_t)(src + lane * 16), (lptr_t)(dst + c * 1024), 16, 0, 0);
         }
       }
     };
@@ -1452,11 +1035,6 @@ __device__ __forceinline__ void bx_astat_body(const GemmDev& p, char* lds) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) prev[jj][i] = acc[jj][i];
     }
-#if BXA_STAMPS
-    asm volatile("s_nop 0" :: "v"(prev[0][0]), "v"(prev[1][1]) : "memory");
-    const uint64_t c4 = __builtin_amdgcn_s_memtime();
-    st_acc[0] += (uint32_t)(c1 - c0); st_acc[1] += (uint32_t)(c2 - c1); st_acc[2] += (uint32_t)(c3 - c2); st_acc[3] += (uint32_t)(c4 - c3);
-#endif
   };
   using TT_ = std::true_type; using FF_ = std::false_type;
   // NS >= 4 (launcher: N >= 352).  Slot 0: nothing to store; slot 1: no stores are outstanding yet; the last two: no DMA
@@ -1474,17 +1052,6 @@ __device__ __forceinline__ void bx_astat_body(const GemmDev& p, char* lds) {
         if (FULL || ok[i]) *reinterpret_cast<f32x4*>(crow[i] + 32 * (NS - 1) + 16 * jj) = v;
       }
   }
-#if BXA_STAMPS
-  BXA_STAMP(2);
-  if (threadIdx.x == 0 && blockIdx.x < 4096) {
-    g_bxa_stamps[blockIdx.x * 8 + 5] = ((uint64_t)st_acc[1] << 32) | st_acc[0];
-    g_bxa_stamps[blockIdx.x * 8 + 6] = ((uint64_t)st_acc[3] << 32) | st_acc[2];
-    g_bxa_stamps[blockIdx.x * 8 + 3] = (uint64_t)NS;
-    g_bxa_stamps[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - st_loop0;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  BXA_STAMP(4);
-#endif
 }
 #define AS_NMAX 1024
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bx_astat_kernel(const GemmDev p) {
@@ -1493,7 +1060,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bx_astat_kernel(const Ge
   if (p.m_dev) Mlim = min(Mlim, *p.m_dev);
   const int m0 = blockIdx.x * 128;
   if (m0 >= Mlim) return;
-  BXA_STAMP(0);
   const int T = (p.K[0] + BK - 1) / BK;                             // 1 .. AS_TMAX (launcher)
   const bool full = m0 + 128 <= Mlim;
   bx_for<AS_TMAX>([&](auto tc) {
@@ -1748,13 +1314,11 @@ int pfo_gru_fused_launch(const PfoGruFused& f, hipStream_t stream) {
   d.upd_mem = f.upd_mem; d.h0_tab = f.h0_tab; d.gates = f.gates; d.D = f.D; d.M = f.cap_rows; d.m_dev = f.n_rows;
   d.gather = f.gather;
   pfo_prof_begin(stream);
-  static const int xcd = getenv("PFO_GEMM_XCD") ? atoi(getenv("PFO_GEMM_XCD")) : 1;                        // A/B switch
   const int tmr = (int)pfo_ceil_div(f.cap_rows, BM), tnc = (int)pfo_ceil_div(f.D, 32);
   dim3 grid((unsigned)tmr, (unsigned)tnc, 1);
   d.xcd_tm = d.xcd_tn = 0;
-  if (xcd && tnc > 1) { d.xcd_tm = tmr; d.xcd_tn = tnc; grid = dim3((unsigned)(pfo_ceil_div(tmr, 8) * 8 * tnc), 1, 1); }
-  if (pfo_bx_fmt()) PFO_KLAUNCH(gru_fused_kernel<1>, grid, dim3(GEMM_THREADS), 0, stream, d);
-  else PFO_KLAUNCH(gru_fused_kernel<0>, grid, dim3(GEMM_THREADS), 0, stream, d);
+  if (tnc > 1) { d.xcd_tm = tmr; d.xcd_tn = tnc; grid = dim3((unsigned)(pfo_ceil_div(tmr, 8) * 8 * tnc), 1, 1); }
+  PFO_KLAUNCH(gru_fused_kernel<1>, grid, dim3(GEMM_THREADS), 0, stream, d);
   PFO_LAUNCH_CHECK();
   pfo_prof_end_dev(PFO_PROF_GRU_FUSED, 2.0 * 3 * f.D * ((double)f.K_msg + f.D), f.n_rows, f.cap_rows, stream);   // per-row FLOPs of the two contractions
   return PFO_OK;
@@ -1833,8 +1397,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bx_skinny_kernel(const G
     constexpr int st = decltype(sc)::value;
     char* As = lds + buf * SK_BUF_BYTES;
     char* Bs = As + NP * SK_A_PIECE;
-    if constexpr (FMT == 0) bx_split_store(As, SK_A_PIECE, a_r, a_c4, a_st[st]);
-    else {
+    {
       // the row's maximum over this k-tile sits in 8 neighbouring lanes (4 values each): quad swaps + half-row mirror
       const float4 v = a_st[st];
       uint32_t m = __float_as_uint(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
@@ -1895,17 +1458,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bx_skinny_kernel(const G
         const int j = min(wave + 4 * jj, NT - 1);             // NT = 11: wave 3 has no third tile, re-reads tile 10, result unused
         b[jj][q] = *reinterpret_cast<const u32x4*>(Bs + q * SK_B_PIECE + (16 * j) * 64 + frag_off);
       }
-    if constexpr (FMT == 0) {
-      typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-      constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};     // smallest terms first
-#pragma unroll
-      for (int t6 = 0; t6 < 6; ++t6)
-#pragma unroll
-        for (int jj = 0; jj < NJW; ++jj)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-            acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8, b[jj][PB[t6]]), __builtin_bit_cast(v8, a[i][PA[t6]]), acc[i][jj], 0, 0, 0);
-    } else {
+    {
       constexpr int PA[3] = {1, 0, 0}, PB[3] = {0, 1, 0};
 #pragma unroll
       for (int t3 = 0; t3 < 3; ++t3)
@@ -1941,7 +1494,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bx_skinny_kernel(const G
   float* Cb = p.C;
   const int64_t ldc = p.ldc;
   const bool n4 = bx_n4(p, Cb, ldc, p.bias);
-  if (BXA_EPI && n4 && !p.gg_gates) {
+  if (n4) {
     // every load of the epilogue in front of its first store (see bx_areg_body: a load may not pass a store that could alias
     // it, so the per-tile "exponents, addends, store" was a chain of load latencies)
     int colv[NJW]; bool okc[NJW];
@@ -2011,8 +1564,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bx_skinny_kernel(const G
       if (j < NT && col < p.N) {
         f32x4 v = acc[i][jj];
         if constexpr (FMT == 1) v = hx_scale4(v, *reinterpret_cast<const int4*>(bexp1 + col), accE[i] - 2 * HX_TOP);
-        if (p.gg_gates) bx_gru_gates4(p, row, col, v);           // (wave-uniform: a kernel argument)
-        else bx_store4(p, Cb, ldc, p.bias, rscale, zero, n4, row, col, v, addrow);
+        bx_store4(p, Cb, ldc, p.bias, rscale, zero, n4, row, col, v, addrow);
       }
     }
   }
@@ -2034,14 +1586,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int tx_pi(int k) { return (k & 3) + ((k >> 1) & 4); }
 
-// float4 = 4 consecutive columns (m or n) of k-row `k`: 8 bytes of bf16 per piece
-__device__ __forceinline__ void tx_split_store(char* base, int piece_bytes, int off, const float4 v) {
-  uint2 o1, o2, o3;
-  bx_split4(v, o1, o2, o3);
-  *reinterpret_cast<uint2*>(base + off) = o1;
-  *reinterpret_cast<uint2*>(base + piece_bytes + off) = o2;
-  *reinterpret_cast<uint2*>(base + 2 * piece_bytes + off) = o3;
-}
 // byte offset of columns col..col+3 of k-row `k` in a transposed-read image
 __device__ __forceinline__ int tx_off(int row_bytes, int slot_mask, int k, int col) {
   return k * row_bytes + ((((col >> 4) + tx_pi(k)) & slot_mask) << 5) + ((col & 15) << 1);
@@ -2190,13 +1734,7 @@ __device__ __forceinline__ void gemm_tile_tn_bx(const GemmDev& p, int bx, int by
     *reinterpret_cast<uint2*>(base + piece_bytes + off) = ol;
   };
   auto store_tile = [&](bool first) {
-    if constexpr (FMT == 0) {
-#pragma unroll
-      for (int i = 0; i < NA; ++i) tx_split_store(As, TXA_PIECE, a_off[i], a_reg[i]);
-#pragma unroll
-      for (int i = 0; i < NB; ++i)
-        if (b_live[i]) tx_split_store(Bs, TX_B_PIECE, b_off[i], b_reg[i]);
-    } else {
+    {
       uint32_t mwa = 0, mwb = 0;
 #pragma unroll
       for (int q4 = 0; q4 < W / 4; ++q4) {
@@ -2242,7 +1780,7 @@ __device__ __forceinline__ void gemm_tile_tn_bx(const GemmDev& p, int bx, int by
       if (strips >= 1) acc[0][j] = bx_mma<FMT>(a[0], b, acc[0][j]);
       if (strips >= 2) acc[1][j] = bx_mma<FMT>(a[1], b, acc[1][j]);
     };
-    u32x4 b0[NP], b1[NP];                     // double-buffered B fragments (see gemm_bf16x3_kernel)
+    u32x4 b0[NP], b1[NP];                     // double-buffered B fragments: the reads of tile j+1 fly during the MFMAs of tile j
     ldb(b0, 0);
 #pragma unroll
     for (int j = 0; j < 11; j += 2) {
@@ -2253,58 +1791,19 @@ __device__ __forceinline__ void gemm_tile_tn_bx(const GemmDev& p, int bx, int by
     }
   };
   if (T > 0) {
-#if BXA_STAMPS
-    uint32_t st_acc[5] = {0, 0, 0, 0, 0};      // shader cycles of wavefront 0 per phase of a k-tile step (tools/probes/tn_stamps.py)
-    BXA_STAMP(0);
-#endif
     load_tile(0);
     if constexpr (FMT == 1) { publish_max(); __syncthreads(); }
     store_tile(true);
     __syncthreads();
-#if BXA_STAMPS
-    BXA_STAMP(1);
-    const uint64_t st_loop0 = __builtin_amdgcn_s_memtime();
-#endif
     for (int t = 0; t < T; ++t) {
-      const bool more = (BX_EXP == 1) ? false : (t + 1 < T);
-#if BXA_STAMPS
-      const uint64_t c0 = __builtin_amdgcn_s_memtime();
-#endif
+      const bool more = t + 1 < T;
       if (more) load_tile(t + 1);
-#if BXA_STAMPS
-      asm volatile("s_nop 0" ::: "memory");
-      const uint64_t c1 = __builtin_amdgcn_s_memtime();
-#endif
-      if (BX_EXP != 2) compute_tile();
-#if BXA_STAMPS
-      asm volatile("s_nop 0" ::: "memory");
-      const uint64_t c2 = __builtin_amdgcn_s_memtime();
-#endif
+      compute_tile();
       if constexpr (FMT == 1) { if (more) publish_max(); }
-#if BXA_STAMPS
-      asm volatile("s_nop 0" ::: "memory");
-      const uint64_t c3 = __builtin_amdgcn_s_memtime();
-#endif
       __syncthreads();
-#if BXA_STAMPS
-      const uint64_t c4 = __builtin_amdgcn_s_memtime();
-#endif
-      if (more && BX_EXP != 3) store_tile(false);
+      if (more) store_tile(false);
       __syncthreads();
-#if BXA_STAMPS
-      const uint64_t c5 = __builtin_amdgcn_s_memtime();
-      st_acc[0] += (uint32_t)(c1 - c0); st_acc[1] += (uint32_t)(c2 - c1); st_acc[2] += (uint32_t)(c3 - c2); st_acc[3] += (uint32_t)(c4 - c3); st_acc[4] += (uint32_t)(c5 - c4);
-#endif
     }
-#if BXA_STAMPS
-    BXA_STAMP(2);
-    if (threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096) {
-      g_bxa_stamps[blockIdx.x * 8 + 5] = ((uint64_t)st_acc[1] << 32) | st_acc[0];
-      g_bxa_stamps[blockIdx.x * 8 + 6] = ((uint64_t)st_acc[3] << 32) | st_acc[2];
-      g_bxa_stamps[blockIdx.x * 8 + 3] = ((uint64_t)st_acc[4] << 32) | (uint32_t)T;
-      g_bxa_stamps[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - st_loop0;
-    }
-#endif
   }
   float* Cb = p.slab_base + (int64_t)split * (int64_t)p.M * p.N;
 #pragma unroll
@@ -2319,14 +1818,10 @@ __device__ __forceinline__ void gemm_tile_tn_bx(const GemmDev& p, int bx, int by
         if (col < p.N) Cb[(int64_t)row * p.N + col] = FMT == 1 ? __builtin_amdgcn_ldexpf(acc[i][j][reg], eA + eB - 2 * HX_TOP) : acc[i][j][reg];
       }
     }
-#if BXA_STAMPS
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  BXA_STAMP(4);
-#endif
 }
 
-// Pre-split image of a weight operand for gemm_bf16x3_kernel<true>: [k-tile][piece][row n, padded to BN][64 B],
-// the exact LDS image of the kernel (same swizzle), zero-padded in n and k.  W(n, k) = src[n*ld + k] or, with
+// Pre-split image of a weight operand for the image kernels: [k-tile][piece][row n, padded to BN][64 B],
+// the exact LDS image of those kernels (same swizzle), zero-padded in n and k.  W(n, k) = src[n*ld + k] or, with
 // `trans`, src[k*ld + n] - so a k-major ("NN") operand becomes a row-major one for free.
 struct BimgDev {
   const float* src[PFO_BIMG_MAX]; int64_t ld[PFO_BIMG_MAX]; int N[PFO_BIMG_MAX], K[PFO_BIMG_MAX], trans[PFO_BIMG_MAX];
@@ -2346,48 +1841,6 @@ __device__ __forceinline__ int bimg_gate_row(int n, int which, int D) {
   if (gt == 2) return which == 1 ? 2 * D + u : -1;
   return which == 2 ? 2 * D + u : -1;
 }
-__global__ __launch_bounds__(256) void bimg_kernel(const BimgDev g) {
-  const int z = blockIdx.y;
-  const int N = g.N[z], K = g.K[z], rows = g.rows[z];
-  const int T = (K + 31) / 32;
-  const int64_t total = (int64_t)T * rows * 4;                 // one thread per (tile, row, 16-byte chunk)
-  const float* __restrict__ src = g.src[z];
-  const int64_t ld = g.ld[z];
-  char* dst = reinterpret_cast<char*>(g.dst[z]);
-  for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    int t, n, c;
-    if (g.trans[z]) { n = (int)(i % rows); c = (int)((i / rows) & 3); t = (int)(i / (4 * (int64_t)rows)); }
-    else            { c = (int)(i & 3); n = (int)((i >> 2) % rows); t = (int)((i >> 2) / rows); }
-    uint32_t w[3][4];
-#pragma unroll
-    for (int e2 = 0; e2 < 4; ++e2) {
-      uint32_t pc[2][3];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = 32 * t + 8 * c + 2 * e2 + h;
-        float x = 0.f;
-        if (g.gate[z]) {
-          const int sr = bimg_gate_row(n, g.gate[z], g.gate_D[z]);
-          if (sr >= 0 && k < K) x = src[(int64_t)sr * ld + k];
-        } else if (n < N && k < K) x = g.trans[z] ? src[(int64_t)k * ld + n] : src[(int64_t)n * ld + k];
-        const uint32_t b1 = __float_as_uint(x) & 0xFFFF0000u;
-        const float r1 = x - __uint_as_float(b1);
-        const uint32_t b2 = __float_as_uint(r1) & 0xFFFF0000u;
-        const float r2 = r1 - __uint_as_float(b2);
-        pc[h][0] = b1; pc[h][1] = b2; pc[h][2] = __float_as_uint(r2);
-      }
-#pragma unroll
-      for (int q = 0; q < 3; ++q) w[q][e2] = (pc[1][q] & 0xFFFF0000u) | (pc[0][q] >> 16);
-    }
-    const int ng = n + g.row0[z];                               // row of the (possibly stacked) image
-    const int64_t off = (int64_t)ng * 64 + ((c ^ bx_swz(ng)) << 4);
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-      *reinterpret_cast<uint4*>(dst + ((int64_t)t * 3 + q) * g.rows_total[z] * 64 + off) = uint4{w[q][0], w[q][1], w[q][2], w[q][3]};
-  }
-}
-
-
 // The fp16x2 image (FMT 1): [k-tile][piece h | l][row][64 B] in the same swizzled layout, then one int32 per image row: the
 // biased exponent E of the row's largest magnitude (clamped); the row is stored times 2^(HX_TOP - E).
 __device__ __forceinline__ int bimg_src_row(const BimgDev& g, int z, int n) {
@@ -2437,7 +1890,7 @@ __global__ __launch_bounds__(256) void bimg_h_rows_kernel(const BimgDev g) {
 }
 // Lists with k-major ("trans") operands take two launches: the row exponents (one wavefront per image row; a k-major row is
 // a strided column of the source, its 64-byte lines shared with the neighbouring rows' wavefronts), then the conversion in
-// bimg_kernel's thread order (coalesced along n for k-major sources).
+// one thread per (tile, row, 16-byte chunk), coalesced along n for k-major sources.
 __global__ __launch_bounds__(256) void bimg_exp_kernel(const BimgDev g) {
   const int z = blockIdx.y;
   const int K = g.K[z], rows = g.rows[z];
@@ -2521,114 +1974,6 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_multi_kernel(const MultiDev
     case 1: gemm_tile<false, true, 2, VEC>(p, bx, by, zb, 0, lds_a, lds_b); break;
     case 2: gemm_tile<true, false, 2, VEC>(p, bx, by, zb, 0, lds_a, lds_b); break;
     default: gemm_tile<true, true, 2, VEC>(p, bx, by, zb, 0, lds_a, lds_b); break;
-  }
-}
-
-// DIRECT form of the same grouped launch (round 6).  These products (composite weights, their gradient chains: M, N, K <= 704,
-// operands L2-resident weights) are chains of k-tiles, each a global -> LDS -> barrier -> fragment round trip: 10-57 us per
-// launch for ~40 MFLOP, 0.32 ms per step of side-stream residency.  Here a wavefront owns ONE 16 x 16 output tile and takes
-// its MFMA fragments straight from global memory - no LDS, no barrier: lane (r, g) holds A[row r][16 q + 4 g + j] and
-// B[16 q + 4 g + j][col r], j = 0..3, as one float4 (or four dwords on a k-major operand) per 16 k; MFMA step j multiplies the
-// j-th elements, so every k of the block is taken exactly once (a permutation of the k order inside a block of 16 - the sum
-// does not care).  Loads run MULTI_PD blocks ahead; four times the workgroups (16 x 64 per workgroup instead of 32 x 64).
-#ifndef MULTI_PD
-#define MULTI_PD 4
-#endif
-template <bool A_KM, bool B_KM, bool VEC>
-__device__ __forceinline__ void gemm_direct_tile(const GemmDev& p, const int bx, const int by, const int zb) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  const int m0 = bx * 16, n0 = by * 64 + 16 * wave;
-  if (n0 >= p.N) return;                                    // (no barrier in this kernel: a wavefront may leave)
-  const int K = p.K[0];
-  const float* Ab = p.A[0] + zb * p.a_bs[0];
-  const float* Bb = p.B[0] + zb * p.b_bs[0];
-  const int64_t lda = p.lda[0], ldb = p.ldb[0];
-  const int mr = min(m0 + r, p.M - 1), nr = min(n0 + r, p.N - 1);       // clamped: rows / columns beyond the edge only feed outputs that are not stored
-  const int T = (K + 15) >> 4;
-  float a[MULTI_PD][4], b[MULTI_PD][4];
-  auto load = [&](int q, float (&av)[4], float (&bv)[4]) {
-    const int k0 = 16 * q + 4 * g;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { av[j] = 0.f; bv[j] = 0.f; }
-    if (!A_KM) {
-      const float* src = Ab + (int64_t)mr * lda + min(k0, max(K - 4, 0));
-      if (VEC) { const float4 v = *reinterpret_cast<const float4*>(src); av[0] = v.x; av[1] = v.y; av[2] = v.z; av[3] = v.w; }
-      else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) av[j] = Ab[(int64_t)mr * lda + min(k0 + j, K - 1)];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) av[j] = Ab[(int64_t)min(k0 + j, K - 1) * lda + mr];
-    }
-    if (!B_KM) {
-      const float* src = Bb + (int64_t)nr * ldb + min(k0, max(K - 4, 0));
-      if (VEC) { const float4 v = *reinterpret_cast<const float4*>(src); bv[0] = v.x; bv[1] = v.y; bv[2] = v.z; bv[3] = v.w; }
-      else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bv[j] = Bb[(int64_t)nr * ldb + min(k0 + j, K - 1)];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bv[j] = Bb[(int64_t)min(k0 + j, K - 1) * ldb + nr];
-    }
-    // beyond K both operands are zero (selects behind the unconditional loads)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bool in = k0 + j < K;
-      av[j] = in ? av[j] : 0.f;
-      bv[j] = in ? bv[j] : 0.f;
-    }
-  };
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int d = 0; d < MULTI_PD; ++d)
-    if (d < T) load(d, a[d], b[d]);
-  for (int q0 = 0; q0 < T; q0 += MULTI_PD) {
-#pragma unroll
-    for (int d = 0; d < MULTI_PD; ++d) {
-      if (q0 + d < T) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[d][j], b[d][j], acc, 0, 0, 0);
-        if (q0 + d + MULTI_PD < T) load(q0 + d + MULTI_PD, a[d], b[d]);
-      }
-    }
-  }
-  // C/D layout of 16x16x4: col = lane & 15, row = 4 * (lane >> 4) + reg
-  float* Cb = p.C + zb * p.c_bs;
-  const float* bias = p.bias ? p.bias + zb * p.bias_bs : nullptr;
-  const int col = n0 + r;
-  if (col < p.N) {
-    const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int row = m0 + 4 * g + reg;
-      if (row < p.M) {
-        float v = acc[reg];
-        if (p.accumulate) v += Cb[(int64_t)row * p.ldc + col];
-        Cb[(int64_t)row * p.ldc + col] = v + bv;
-      }
-    }
-  }
-}
-template <bool VEC>
-__global__ __launch_bounds__(GEMM_THREADS) void gemm_multi_direct_kernel(const MultiDev g) {
-  int q = 0;
-#pragma unroll
-  for (int i = 1; i < MULTI_MAX; ++i)
-    if (i < g.n && (int)blockIdx.x >= g.tile_begin[i]) q = i;
-  int t = blockIdx.x - g.tile_begin[q];
-  const int per_batch = g.tm[q] * g.tn[q];
-  const int zb = t / per_batch;
-  t -= zb * per_batch;
-  const int bx = t / g.tn[q], by = t % g.tn[q];
-  const GemmDev p = g.p[q];
-  switch (g.layout[q]) {
-    case 0: gemm_direct_tile<false, false, VEC>(p, bx, by, zb); break;
-    case 1: gemm_direct_tile<false, true, VEC>(p, bx, by, zb); break;
-    case 2: gemm_direct_tile<true, false, VEC>(p, bx, by, zb); break;
-    default: gemm_direct_tile<true, true, VEC>(p, bx, by, zb); break;
   }
 }
 
@@ -2842,17 +2187,14 @@ int pfo_gemm_tn_group_launch(const PfoTnProblem* probs, int n, int K, const int3
   memset(&g, 0, sizeof(g));
   bool vec = true;
   int tiles = 0;
-  // 256-row tiles of eight wavefronts (one workgroup per CU) when every problem is at least that tall: 0 = never  (A/B switch)
-  static const int tn8_env = getenv("PFO_TN8") ? atoi(getenv("PFO_TN8")) : PFO_DEFAULT_TN8;
-  static const int tn_fmt0 = getenv("PFO_TN_FMT") ? atoi(getenv("PFO_TN_FMT")) : PFO_DEFAULT_TN_FMT;
-  static const int bx0 = getenv("PFO_GEMM_BF16X3") ? atoi(getenv("PFO_GEMM_BF16X3")) : PFO_DEFAULT_BF16X3;
-  bool tn8 = tn8_env != 0 && tn_fmt0 != 0 && bx0 >= 1;
+  // 256-row tiles of eight wavefronts (one workgroup per CU) when every problem is at least that tall
+  bool tn8 = true;
   for (int i = 0; i < n; ++i) {
     const PfoTnProblem& q = probs[i];
-    tn8 = tn8 && q.M >= tn8_env && aligned4(q.A) && aligned4(q.B) && (q.lda % 4) == 0 && (q.ldb % 4) == 0 && (q.M % 4) == 0 && (q.N % 4) == 0;
+    tn8 = tn8 && q.M >= TN8_MIN_ROWS && aligned4(q.A) && aligned4(q.B) && (q.lda % 4) == 0 && (q.ldb % 4) == 0 && (q.M % 4) == 0 && (q.N % 4) == 0;
   }
-  static const int slots4_env = getenv("PFO_TN_SLOTS") ? atoi(getenv("PFO_TN_SLOTS")) : 512;      // A/B: workgroups of the 128-row form the split count is sized for (2 per CU; 768 = 3: LDS 3 x 49.6 KB and 3 x 120 registers fit)
-  const int tbm = tn8 ? 256 : BM, slots = tn8 ? 256 : slots4_env;
+  // workgroups the split count is sized for: 2 per CU in the 128-row form (768 = 3 per CU also fits: LDS 3 x 49.6 KB, 3 x 120 registers)
+  const int tbm = tn8 ? 256 : BM, slots = tn8 ? 256 : 512;
   int64_t per_split = 0;
   for (int i = 0; i < n; ++i) {
     const PfoTnProblem& s = probs[i];
@@ -2878,21 +2220,17 @@ int pfo_gemm_tn_group_launch(const PfoTnProblem* probs, int n, int K, const int3
   g.n = n; g.K = K; g.nsplit = nsplit; g.chunk = chunk; g.total_tiles = tiles; g.k_dev = k_dev; g.slabs = slabs;
   double flops = 0;
   for (int i = 0; i < n; ++i) flops += 2.0 * probs[i].M * probs[i].N * (double)K;
-  static const int bx = getenv("PFO_GEMM_BF16X3") ? atoi(getenv("PFO_GEMM_BF16X3")) : PFO_DEFAULT_BF16X3;
-  const bool use_bx = vec && bx >= 1;
+  const bool use_bx = vec;
   pfo_prof_begin(stream);
-  static const int tn_fmt = getenv("PFO_TN_FMT") ? atoi(getenv("PFO_TN_FMT")) : PFO_DEFAULT_TN_FMT;      // A/B switch
-  static const int xcd_map = getenv("PFO_TN_XCD") ? atoi(getenv("PFO_TN_XCD")) : 1;                      // A/B switch
-  g.xcd_map = use_bx && xcd_map && nsplit > 1;
+  g.xcd_map = use_bx && nsplit > 1;
   const dim3 grid_bx = g.xcd_map ? dim3(tiles * nsplit, 1) : dim3(tiles, nsplit);
-  if (use_bx && tn_fmt && tn8) PFO_KLAUNCH((gemm_tn_group_bx_kernel<1, 8>), grid_bx, dim3(512), 0, stream, g);
-  else if (use_bx && tn_fmt) PFO_KLAUNCH(gemm_tn_group_bx_kernel<1>, grid_bx, dim3(GEMM_THREADS), 0, stream, g);
-  else if (use_bx) PFO_KLAUNCH(gemm_tn_group_bx_kernel<0>, grid_bx, dim3(GEMM_THREADS), 0, stream, g);
+  if (use_bx && tn8) PFO_KLAUNCH((gemm_tn_group_bx_kernel<1, 8>), grid_bx, dim3(512), 0, stream, g);
+  else if (use_bx) PFO_KLAUNCH(gemm_tn_group_bx_kernel<1>, grid_bx, dim3(GEMM_THREADS), 0, stream, g);
   else if (vec) PFO_KLAUNCH(gemm_tn_group_kernel<true>, dim3(tiles, nsplit), dim3(GEMM_THREADS), 0, stream, g);
   else PFO_KLAUNCH(gemm_tn_group_kernel<false>, dim3(tiles, nsplit), dim3(GEMM_THREADS), 0, stream, g);
   PFO_LAUNCH_CHECK();
   // the GEMM kernel alone; with a device-side K bound the work is (flops per k-row) x the count read back at collect time
-  if (use_bx) pfo_prof_end_dev((tn_fmt && tn8) ? PFO_PROF_GEMM_TN_BX8 : PFO_PROF_GEMM_TN_BX, flops / (double)K, k_dev, K, stream);
+  if (use_bx) pfo_prof_end_dev(tn8 ? PFO_PROF_GEMM_TN_BX8 : PFO_PROF_GEMM_TN_BX, flops / (double)K, k_dev, K, stream);
   if (use_bx) pfo_prof_begin(stream);                           // the slab fold is a family of its own: slabs in, matrices out
   PFO_KLAUNCH(tn_group_reduce_kernel, dim3((unsigned)std::min<int64_t>(1024, pfo_ceil_div(per_split, 256))), dim3(256), 0,
                      stream, g);
@@ -2918,7 +2256,6 @@ static void to_dev(const PfoGemm& g, GemmDev& d) {
   d.c_bs = g.c_bs; d.bias_bs = g.bias_bs; d.rs_bs = g.rs_bs;
   d.n_real = g.N; d.slab_base = g.slabs; d.dyn_chunk = 0;
   d.b_img = nullptr; d.b_img_rows = 0; d.b_img2 = nullptr;
-  d.gg_gates = g.gg_gates; d.gg_h = g.gg_h; d.gg_hm = g.gg_hm; d.gg_dh0 = g.gg_dh0; d.gg_dgi = g.gg_dgi; d.gg_dgh = g.gg_dgh;
 }
 
 
@@ -2948,37 +2285,18 @@ int pfo_bimg_launch(const PfoBimg* list, int n, hipStream_t stream) {
     PFO_REQUIRE(d.row0[i] >= 0 && d.rows[i] >= list[i].N && d.row0[i] + d.rows[i] <= d.rows_total[i], "bad stacked image rows");
     most = std::max<int64_t>(most, (int64_t)pfo_ceil_div(list[i].K, 32) * d.rows[i] * 4);
   }
-  if (pfo_bx_fmt()) {
-    int most_rows = 0;
-    bool any_trans = false;
-    for (int i = 0; i < n; ++i) { most_rows = std::max(most_rows, d.rows[i]); any_trans = any_trans || d.trans[i] != 0; }
-    if (!any_trans) PFO_KLAUNCH(bimg_h_rows_kernel, dim3((unsigned)pfo_ceil_div(most_rows, 4), n), dim3(256), 0, stream, d);
-    else {
-      PFO_KLAUNCH(bimg_exp_kernel, dim3((unsigned)pfo_ceil_div(most_rows, 4), n), dim3(256), 0, stream, d);
-      PFO_KLAUNCH(bimg_h_kernel, dim3((unsigned)pfo_ceil_div(most, 256), n), dim3(256), 0, stream, d);
-    }
-  } else
-    PFO_KLAUNCH(bimg_kernel, dim3((unsigned)pfo_ceil_div(most, 256), n), dim3(256), 0, stream, d);
+  int most_rows = 0;
+  bool any_trans = false;
+  for (int i = 0; i < n; ++i) { most_rows = std::max(most_rows, d.rows[i]); any_trans = any_trans || d.trans[i] != 0; }
+  if (!any_trans) PFO_KLAUNCH(bimg_h_rows_kernel, dim3((unsigned)pfo_ceil_div(most_rows, 4), n), dim3(256), 0, stream, d);
+  else {
+    PFO_KLAUNCH(bimg_exp_kernel, dim3((unsigned)pfo_ceil_div(most_rows, 4), n), dim3(256), 0, stream, d);
+    PFO_KLAUNCH(bimg_h_kernel, dim3((unsigned)pfo_ceil_div(most, 256), n), dim3(256), 0, stream, d);
+  }
   PFO_LAUNCH_CHECK();
   return PFO_OK;
 }
 
-bool pfo_gemm_takes_skinny(int M, int N) {
-  static const int bx = getenv("PFO_GEMM_BF16X3") ? atoi(getenv("PFO_GEMM_BF16X3")) : PFO_DEFAULT_BF16X3;
-  static const int bx_min_tiles = getenv("PFO_BX_MIN_TILES") ? atoi(getenv("PFO_BX_MIN_TILES")) : PFO_BX_MIN_TILES;
-  static const bool forced = getenv("PFO_GEMM_TILE") != nullptr;
-  static const int sk = getenv("PFO_GEMM_SKINNY") ? atoi(getenv("PFO_GEMM_SKINNY")) : 1;
-  if (bx < 1 || forced || !sk) return false;
-  return (int64_t)pfo_ceil_div(M, BM) * pfo_ceil_div(N, BN) < bx_min_tiles;
-}
-bool pfo_gemm_takes_bx(int M, int N) {
-  static const int bx = getenv("PFO_GEMM_BF16X3") ? atoi(getenv("PFO_GEMM_BF16X3")) : PFO_DEFAULT_BF16X3;
-  static const int bx_min_tiles = getenv("PFO_BX_MIN_TILES") ? atoi(getenv("PFO_BX_MIN_TILES")) : PFO_BX_MIN_TILES;
-  static const bool forced = getenv("PFO_GEMM_TILE") != nullptr;
-  static const int sk = getenv("PFO_GEMM_SKINNY") ? atoi(getenv("PFO_GEMM_SKINNY")) : 1;
-  if (bx < 1 || forced) return false;
-  return sk != 0 || (int64_t)pfo_ceil_div(M, BM) * pfo_ceil_div(N, BN) >= bx_min_tiles;
-}
 
 int pfo_gemm_launch(const PfoGemm& g, hipStream_t stream) {
   PFO_REQUIRE(g.M > 0 && g.N > 0 && g.K[0] > 0 && g.batch >= 1, "bad sizes");
@@ -3026,75 +2344,41 @@ int pfo_gemm_launch(const PfoGemm& g, hipStream_t stream) {
   } else {
     // tile rows per workgroup: 128 (BIG) or 32 (SMALL: launches where 128-row tiles would leave most of the 256 CUs
     // without work)
-    static const int force = getenv("PFO_GEMM_TILE") ? (atoi(getenv("PFO_GEMM_TILE")) != 0 ? 1 : 0) : -1;   // A/B switch: 0 BIG, 1 SMALL
     const int64_t big_tiles = (int64_t)pfo_ceil_div(g.M, BM) * tn * g.batch;
-    int tile = big_tiles < 400 ? 1 : PFO_DEFAULT_TILE;
-    if (force >= 0) tile = force;
+    const int tile = big_tiles < 400 ? 1 : 0;
     const int rows = tile == 1 ? 32 : BM;
     const dim3 grid((unsigned)pfo_ceil_div(g.M, rows), tn, g.batch);
-    // bf16x3 split contraction: 1 = when the caller supplies the pre-split image of B, 2 = also for plain row-major
-    // B (split in the kernel), 0 = never (fp32 MFMA everywhere).  A/B switch.
-    static const int bx = getenv("PFO_GEMM_BF16X3") ? atoi(getenv("PFO_GEMM_BF16X3")) : PFO_DEFAULT_BF16X3;
-    static const int bx_min_tiles = getenv("PFO_BX_MIN_TILES") ? atoi(getenv("PFO_BX_MIN_TILES")) : PFO_BX_MIN_TILES;
+    // the split contraction on the caller's pre-split image of B (pfo_bimg_launch): 32-row workgroups for launches of fewer
+    // than BX_MIN_TILES 128-row tiles, the 128-row kernels above (bx_force: tests pick one)
     const bool a_rowvec = a_vec && g.batch == 1;
-    static const int sk = getenv("PFO_GEMM_SKINNY") ? atoi(getenv("PFO_GEMM_SKINNY")) : 1;                  // A/B switch
-    if (g.b_img && (g.K[1] == 0 || g.b_img2) && a_rowvec && (g.bx_force == 2 || (bx >= 1 && sk && !g.bx_force && force < 0 && big_tiles < bx_min_tiles))) {
+    const bool img_ok = g.b_img && (g.K[1] == 0 || g.b_img2) && a_rowvec;
+    if (img_ok && (g.bx_force == 2 || (!g.bx_force && big_tiles < BX_MIN_TILES))) {
       d.b_img = g.b_img; d.b_img_rows = (int)pfo_align_up(g.N, BN); d.b_img2 = g.b_img2;
       kind = PFO_PROF_GEMM_BX_SKINNY;
       // few row tiles (< one per CU even with 176-column workgroups): 64-column workgroups fill the chip three times better
-      static const int narrow = getenv("PFO_SKINNY_NARROW") ? atoi(getenv("PFO_SKINNY_NARROW")) : 512;        // A/B switch: workgroup threshold, 0 = never
       const int64_t sk_wgs = (int64_t)pfo_ceil_div(g.M, SK_ROWS) * tn;
       const dim3 g4((unsigned)pfo_ceil_div(g.M, SK_ROWS), (unsigned)pfo_ceil_div(g.N, 64), 1), g11((unsigned)pfo_ceil_div(g.M, SK_ROWS), tn, 1);
-      if (sk_wgs < narrow) {
-        if (pfo_bx_fmt()) PFO_KLAUNCH((gemm_bx_skinny_kernel<4, 1>), g4, dim3(GEMM_THREADS), 0, stream, d);
-        else PFO_KLAUNCH((gemm_bx_skinny_kernel<4, 0>), g4, dim3(GEMM_THREADS), 0, stream, d);
-      } else {
-        if (pfo_bx_fmt()) PFO_KLAUNCH((gemm_bx_skinny_kernel<11, 1>), g11, dim3(GEMM_THREADS), 0, stream, d);
-        else PFO_KLAUNCH((gemm_bx_skinny_kernel<11, 0>), g11, dim3(GEMM_THREADS), 0, stream, d);
-      }
-    } else if (g.b_img && (g.K[1] == 0 || g.b_img2) && a_rowvec && (g.bx_force || (bx >= 1 && big_tiles >= bx_min_tiles && force < 0))) {
+      if (sk_wgs < 512) PFO_KLAUNCH((gemm_bx_skinny_kernel<4, 1>), g4, dim3(GEMM_THREADS), 0, stream, d);
+      else PFO_KLAUNCH((gemm_bx_skinny_kernel<11, 1>), g11, dim3(GEMM_THREADS), 0, stream, d);
+    } else if (img_ok) {
       d.b_img = g.b_img; d.b_img_rows = (int)pfo_align_up(g.N, BN); d.b_img2 = g.b_img2;
       kind = PFO_PROF_GEMM_BX;
-      PFO_REQUIRE(!g.gg_gates, "the GRU gate epilogue exists in the 32-row image kernel only (pfo_gemm_takes_skinny)");
-      static const int areg = getenv("PFO_GEMM_AREG") ? atoi(getenv("PFO_GEMM_AREG")) : PFO_DEFAULT_AREG;    // A/B switch
-      if (areg && g.batch == 1)
-      {
-        static const int xcd = getenv("PFO_GEMM_XCD") ? atoi(getenv("PFO_GEMM_XCD")) : 1;                  // A/B switch
-        const int tmr = (int)pfo_ceil_div(g.M, BM);
-        dim3 grid((unsigned)tmr, tn, 1);
-        if (xcd && tn > 1) { d.xcd_tm = tmr; d.xcd_tn = (int)tn; grid = dim3((unsigned)(pfo_ceil_div(tmr, 8) * 8 * tn), 1, 1); }
-        // (eight single-strip wavefronts from PFO_AREG8 workgroups on: 0 = never; below one workgroup per slot the four-wavefront form's
-        //  fewer barriers win - QX / GRU shapes at 470 workgroups: 32.0 against 35.7 us)
-        // short contraction, many columns, plain stores: the A-stationary form (gemm_bx_astat_kernel)
-        bool as_done = false;
-        static const int astat = getenv("PFO_ASTAT") ? atoi(getenv("PFO_ASTAT")) : PFO_DEFAULT_ASTAT;           // A/B switch
-        if (astat && pfo_bx_fmt() && g.K[1] == 0 && g.K[0] <= AS_TMAX * BK && (g.N % 32) == 0 && g.N >= 352 && (g.ldc % 4) == 0 &&
-            aligned4(g.C) && !g.bias && !g.relu && !g.relu_src && !g.add_src && !g.accumulate && !g.row_scale && !g.row_zero &&
-            !g.gg_gates && g.M >= 128 * 256) {
-          if (g.N <= AS_NMAX) {
-            PFO_KLAUNCH(gemm_bx_astat_kernel, dim3((unsigned)pfo_ceil_div(g.M, 128)), dim3(GEMM_THREADS), 0, stream, d);
-            as_done = true;
-          }
-        }
-        static const int areg8_min = getenv("PFO_AREG8") ? atoi(getenv("PFO_AREG8")) : PFO_DEFAULT_AREG8;      // A/B switch
-        const bool areg8 = areg8_min > 0 && big_tiles >= areg8_min;
-        if (as_done) { }
-        else if (pfo_bx_fmt() && areg8) PFO_KLAUNCH(gemm_bx_areg8_kernel<1>, grid, dim3(512), 0, stream, d);
-        else if (pfo_bx_fmt()) PFO_KLAUNCH(gemm_bx_areg_kernel<1>, grid, dim3(GEMM_THREADS), 0, stream, d);
-        else PFO_KLAUNCH(gemm_bx_areg_kernel<0>, grid, dim3(GEMM_THREADS), 0, stream, d);
-      }
-      else {
-        PFO_REQUIRE(!pfo_bx_fmt(), "the fp16x2 images are read by the row-major-A kernels only (batch 1)");
-        PFO_KLAUNCH(gemm_bf16x3_kernel<true>, dim3((unsigned)pfo_ceil_div(g.M, BM), tn, 1), dim3(GEMM_THREADS), 0,
-                           stream, d);
-      }
+      const int tmr = (int)pfo_ceil_div(g.M, BM);
+      dim3 grid_x((unsigned)tmr, tn, 1);
+      if (tn > 1) { d.xcd_tm = tmr; d.xcd_tn = (int)tn; grid_x = dim3((unsigned)(pfo_ceil_div(tmr, 8) * 8 * tn), 1, 1); }
+      // short contraction, many columns, plain stores: the A-stationary form (gemm_bx_astat_kernel)
+      const bool astat = g.K[1] == 0 && g.K[0] <= AS_TMAX * BK && (g.N % 32) == 0 && g.N >= 352 && g.N <= AS_NMAX && (g.ldc % 4) == 0 &&
+                         aligned4(g.C) && !g.bias && !g.relu && !g.relu_src && !g.add_src && !g.accumulate && !g.row_scale && !g.row_zero &&
+                         g.M >= 128 * 256;
+      // (eight single-strip wavefronts from BX_AREG8_MIN workgroups on; below one workgroup per slot the four-wavefront form's
+      //  fewer barriers win - QX / GRU shapes at 470 workgroups: 32.0 against 35.7 us)
+      if (astat) PFO_KLAUNCH(gemm_bx_astat_kernel, dim3((unsigned)pfo_ceil_div(g.M, 128)), dim3(GEMM_THREADS), 0, stream, d);
+      else if (big_tiles >= BX_AREG8_MIN) PFO_KLAUNCH(gemm_bx_areg8_kernel<1>, grid_x, dim3(512), 0, stream, d);
+      else PFO_KLAUNCH(gemm_bx_areg_kernel<1>, grid_x, dim3(GEMM_THREADS), 0, stream, d);
     } else if (g.K[1] > 0 && g.b_img2) {
       // the caller fused two sources whose float B operands may differ in layout: only the image kernels can take that
       pfo_set_error("pfo_gemm_launch: a two-source launch with weight images needs 16-byte aligned row-major A operands");
       return PFO_ERR_INVALID;
-    } else if (bx >= 2 && !g.b_kmajor && tile == 0 && vec) {
-      kind = PFO_PROF_GEMM_BX;
-      PFO_KLAUNCH(gemm_bf16x3_kernel<false>, grid, dim3(GEMM_THREADS), 0, stream, d);
     } else if (g.b_kmajor) {
       if (tile == 1) GEMM_GO(false, true, 1, grid); else GEMM_GO(false, true, 0, grid);
     } else {
@@ -3129,22 +2413,14 @@ int pfo_gemm_multi_launch(const PfoGemm* list, int n, hipStream_t stream) {
     memset(&g, 0, sizeof(g));
     bool vec = true;
     int tiles = 0;
-    // the direct form (gemm_multi_direct_kernel): plain problems of one source - everything these launches are used for
-    static const int direct_env = getenv("PFO_MULTI_DIRECT") ? atoi(getenv("PFO_MULTI_DIRECT")) : 0;      // A/B switch (off: 1.223-1.239 against 1.216-1.220 ms per step, profiles/r6_experiments.txt 17)
-    bool direct = direct_env != 0;
-    for (int i = 0; i < cnt; ++i) {
-      const PfoGemm& s = list[base + i];
-      direct = direct && s.K[1] == 0 && !s.a_idx[0] && !s.b_idx && !s.relu && !s.relu_src && !s.row_scale && !s.row_zero && !s.add_src &&
-               !s.b_img && !s.gg_gates;
-    }
     for (int i = 0; i < cnt; ++i) {
       const PfoGemm& s = list[base + i];
       PFO_REQUIRE(s.M > 0 && s.N > 0 && s.K[0] > 0 && s.A[0] && s.B[0] && s.C, "bad problem");
       PFO_REQUIRE(!s.m_dev && !s.slabs, "multi launch takes plain problems only");
       to_dev(s, g.p[i]);
       g.layout[i] = (s.a_kmajor ? 2 : 0) + (s.b_kmajor ? 1 : 0);
-      g.tm[i] = (int)pfo_ceil_div(s.M, direct ? 16 : 32);
-      g.tn[i] = (int)pfo_ceil_div(s.N, 64);            // gemm_tile's TINY shape: 32 x 64; the direct form: 16 x 64 (four 16 x 16 tiles)
+      g.tm[i] = (int)pfo_ceil_div(s.M, 32);
+      g.tn[i] = (int)pfo_ceil_div(s.N, 64);            // gemm_tile's TINY shape: 32 x 64
       g.tile_begin[i] = tiles;
       tiles += g.tm[i] * g.tn[i] * s.batch;
       vec = vec && gemm_vec_ok(s);
@@ -3153,11 +2429,7 @@ int pfo_gemm_multi_launch(const PfoGemm* list, int n, hipStream_t stream) {
     double mflops = 0;
     for (int i = 0; i < cnt; ++i) mflops += 2.0 * list[base + i].M * list[base + i].N * (double)list[base + i].K[0] * list[base + i].batch;
     pfo_prof_begin(stream);
-    static const int abl_multi = getenv("PFO_ABL_MULTI") ? atoi(getenv("PFO_ABL_MULTI")) : 0;   // timing-only ablation (wrong results): 1 = a single tile per launch
-    if (abl_multi) tiles = 1;
-    if (direct && vec) PFO_KLAUNCH(gemm_multi_direct_kernel<true>, dim3(tiles), dim3(GEMM_THREADS), 0, stream, g);
-    else if (direct) PFO_KLAUNCH(gemm_multi_direct_kernel<false>, dim3(tiles), dim3(GEMM_THREADS), 0, stream, g);
-    else if (vec) PFO_KLAUNCH(gemm_multi_kernel<true>, dim3(tiles), dim3(GEMM_THREADS), 0, stream, g);
+    if (vec) PFO_KLAUNCH(gemm_multi_kernel<true>, dim3(tiles), dim3(GEMM_THREADS), 0, stream, g);
     else PFO_KLAUNCH(gemm_multi_kernel<false>, dim3(tiles), dim3(GEMM_THREADS), 0, stream, g);
     PFO_LAUNCH_CHECK();
     pfo_prof_end(PFO_PROF_GEMM_MULTI, mflops, stream);

@@ -486,8 +486,7 @@ int pfo_segsum_launch(const float* src0, int W0, const float* src1, int W1, cons
   PFO_REQUIRE(src0 && src1 && seg_ptr && members && n_rows && out && W0 > 0 && W1 > 0, "bad arguments");
   PFO_REQUIRE(!src0_live || src0_by_position, "row flags go with rows stored by position");
   const bool vec = ((W0 | W1) & 3) == 0 && ((((uintptr_t)src0) | ((uintptr_t)src1) | ((uintptr_t)out)) & 15) == 0;
-  static const int chunked = getenv("PFO_SEGSUM_CHUNKED") ? atoi(getenv("PFO_SEGSUM_CHUNKED")) : 1;   // A/B switch
-  if (vec && seg_of && cap_members > 0 && chunked) {
+  if (vec && seg_of && cap_members > 0) {
     const int nbm = (int)pfo_ceil_div(cap_members, SEGSUM_CHUNK);
     pfo_prof_begin(stream);
     PFO_KLAUNCH(segsum_chunk_kernel, dim3(nbm), dim3(256), 0, stream, src0, W0, src1, W1, seg_ptr, members, seg_of, n_rows,
@@ -502,19 +501,6 @@ int pfo_segsum_launch(const float* src0, int W0, const float* src1, int W1, cons
                               src0_by_position, src0_live, out);
   else PFO_KLAUNCH(segsum_kernel, dim3(nb), dim3(256), 0, stream, src0, W0, src1, W1, seg_ptr, members, n_rows,
                           src0_by_position, src0_live, out);
-  PFO_LAUNCH_CHECK();
-  return PFO_OK;
-}
-
-// One source, the sums written as a column block of wider rows: out[s * out_ld + 0 .. W) = sum of src[members of s] (layer-1
-// backward: the d h1 half of Dq, taken beside the attention backward whose float atomics fill the d qk' half - attn.hpp dq_rows)
-int pfo_segsum_cols_launch(const float* src, int W, const int32_t* seg_ptr, const int32_t* members, const int32_t* seg_of,
-                           int64_t cap_members, const int32_t* n_rows, float* out, int64_t out_ld, hipStream_t stream) {
-  PFO_REQUIRE(src && seg_ptr && members && seg_of && n_rows && out && W > 0 && cap_members > 0, "bad arguments");
-  PFO_REQUIRE((W & 3) == 0 && (out_ld & 3) == 0 && ((((uintptr_t)src) | ((uintptr_t)out)) & 15) == 0, "rows must be float4-aligned");
-  const int nbm = (int)pfo_ceil_div(cap_members, SEGSUM_CHUNK);
-  PFO_KLAUNCH(segsum_chunk_kernel, dim3(nbm), dim3(256), 0, stream, src, W, (const float*)nullptr, 0, seg_ptr, members, seg_of, n_rows,
-              0, (const uint8_t*)nullptr, out, out_ld);
   PFO_LAUNCH_CHECK();
   return PFO_OK;
 }

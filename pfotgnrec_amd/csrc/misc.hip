@@ -98,11 +98,10 @@ extern "C" int pfo_prof_collect(double* ms, double* work, int64_t* count) {
 namespace {
 thread_local hipEvent_t g_stop_event = nullptr;
 thread_local int g_stop_skip = 0;
-const bool g_stop_enabled = !(getenv("PFO_STOP_EVENTS") && getenv("PFO_STOP_EVENTS")[0] == '0');   // A/B switch
 }  // namespace
 void pfo_stop_event_arm(hipEvent_t e, int skip) { g_stop_event = e; g_stop_skip = skip; }
 bool pfo_stop_event_take(hipEvent_t* e) {
-  if (!g_stop_event || !g_stop_enabled) return false;
+  if (!g_stop_event) return false;
   if (g_stop_skip > 0) { --g_stop_skip; return false; }
   *e = g_stop_event;
   g_stop_event = nullptr;

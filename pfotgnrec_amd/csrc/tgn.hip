@@ -339,7 +339,7 @@ struct Side {
   // Buckets of a side-stream optimizer step in order of FIRST USE (pfo_tgn_adam_side_bucket): early_done fires behind the
   // kernel that finishes the parameters the next forward reads on the caller's stream (time encoder, GRU, layer 1's biases);
   // it stands for the whole side stream as long as nothing but later buckets of the same step was queued behind it.
-  hipEvent_t early_done = nullptr, late_done = nullptr;
+  hipEvent_t early_done = nullptr;
   uint64_t early_gen = 0;
   bool early_ok = false;
   struct Joined { hipStream_t s; uint64_t gen; } joined[8] = {};
@@ -355,7 +355,7 @@ struct Side {
     for (int i = 1; i < 8; ++i) joined[i - 1] = joined[i];       // more streams than slots: the oldest entry goes (it will wait again)
     joined[7].s = s; joined[7].gen = side_gen;
   }
-  hipEvent_t fork = nullptr, done = nullptr, seg_done = nullptr, tn_a = nullptr, tn_b = nullptr, fold_done = nullptr, dh1_sum = nullptr;
+  hipEvent_t fork = nullptr, done = nullptr, seg_done = nullptr, tn_a = nullptr, tn_b = nullptr, fold_done = nullptr;
   hipEvent_t layer[PFO_MAX_LAYERS + 1] = {};
   bool ok = false;
 };
@@ -370,12 +370,11 @@ Side& side() {
     // GPU_MAX_HW_QUEUES hardware queues (default 4) PER PRIORITY CLASS, and once a process holds more streams than that (a
     // process group: RCCL, c10d) a normal-priority side stream shares a hardware queue with the caller's stream - every
     // "beside" of this file silently becomes "behind" (rank path at world 1 on RCCL: 1.65 ms per step against 1.39).  In
-    // classes of their own they cannot.  (Dispatch priority itself changes nothing measurable: round 3.)  PFO_SIDE_PRIO=0: A/B.
-    static const int prio = getenv("PFO_SIDE_PRIO") ? atoi(getenv("PFO_SIDE_PRIO")) : 1;
+    // classes of their own they cannot.  (Dispatch priority itself changes nothing measurable: round 3.)
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);           // lo = least (numerically largest), hi = greatest
-    bool good = (prio ? hipStreamCreateWithPriority(&sd.s, hipStreamNonBlocking, hi) : hipStreamCreateWithFlags(&sd.s, hipStreamNonBlocking)) == hipSuccess;
-    good = good && (prio ? hipStreamCreateWithPriority(&sd.s2, hipStreamNonBlocking, lo) : hipStreamCreateWithFlags(&sd.s2, hipStreamNonBlocking)) == hipSuccess;
+    bool good = hipStreamCreateWithPriority(&sd.s, hipStreamNonBlocking, hi) == hipSuccess;
+    good = good && hipStreamCreateWithPriority(&sd.s2, hipStreamNonBlocking, lo) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.tn_a_done, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.done2, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) == hipSuccess;
@@ -384,7 +383,6 @@ Side& side() {
     good = good && hipEventCreateWithFlags(&sd.tn_a, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.tn_b, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.fold_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.dh1_sum, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.gru_done, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.comp_done, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.pc_a, hipEventDisableTiming) == hipSuccess;
@@ -392,7 +390,6 @@ Side& side() {
     good = good && hipEventCreateWithFlags(&sd.main_done, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.side_done, hipEventDisableTiming) == hipSuccess;
     good = good && hipEventCreateWithFlags(&sd.early_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.late_done, hipEventDisableTiming) == hipSuccess;
     for (int l = 0; l <= PFO_MAX_LAYERS; ++l) good = good && hipEventCreateWithFlags(&sd.layer[l], hipEventDisableTiming) == hipSuccess;
     sd.ok = good;
   }
@@ -509,17 +506,6 @@ static int grad_replicas(const pfo_tgn_config* c, const pfo_tgn_batch* b) {
   const int det = b->deterministic ? 1 : 0;
   return (det || (c->use_memory && !b->uniform && pfo_attn_bwd_runs_possible(b->K, c->D, c->n_heads))) ? 1 : PFO_GRAD_REPLICAS;
 }
-// Layer-1 backward, run-merged attention kernel, non-deterministic calls (PFO_DQ_ATOMIC=1): the attention kernel adds the
-// query-side gradient rows straight into the per-table-row sums Dq[:, :H Cp] (float atomics, attn.hpp dq_rows) and the d h1
-// half Dq[:, H Cp:] is summed on the side stream beside it - no segment-sum pass on the serial tail.  OFF by default: measured
-// at C2 (round 5, one box, interleaved) 1.382 / 1.392 ms per step against 1.302 / 1.303 - the ~20 k extra rows of atomics
-// cost the attention kernel 36 us (270 -> 306 alone), and the table-row contraction that now follows it directly runs
-// beside the tail of the instance weight-gradient launch (114 us instead of 49) where the HBM-bound segment sum used to
-// overlap with it for free: this phase is bound by the chip's total work, not by the order of its launches.
-static bool dq_atomic_mode(const pfo_tgn_config* c, const pfo_tgn_batch* b) {
-  static const int on = getenv("PFO_DQ_ATOMIC") ? atoi(getenv("PFO_DQ_ATOMIC")) : 0;          // A/B switch
-  return on && c->use_memory && !b->uniform && !b->deterministic && pfo_attn_bwd_runs_possible(b->K, c->D, c->n_heads);
-}
 // What the backward's layer-1 kernels need and that depends on the sampled levels alone: the cleared level-0 gradient rows and
 // the layer-1 instances grouped by the touched-table row they sit on.  Queued by the backward on its side stream - or, for
 // calls with pfo_tgn_batch.seg_in_forward, by the forward on ITS side stream (beside layer 1, joined by the event layer 2 waits
@@ -530,7 +516,6 @@ static int seg_prologue(const pfo_tgn_config* c, const pfo_tgn_batch* b, const W
   const int64_t rep_stride = (int64_t)d.capP * d.D;
   // (deterministic: the table holds int64 fixed-point sums - rows of 2 D floats' worth)
   if (c->use_memory) RUN(pfo_zero_rows_launch(w.d_h0, w.n_core, capP, det ? 2 * d.D : d.D, grad_replicas(c, b), rep_stride, ss));
-  if (dq_atomic_mode(c, b)) RUN(pfo_zero_rows_launch(w.Dq, w.n_core, capP, d.H * d.Cp + d.D, 1, 0, ss));   // the row sums the attention backward adds into
   RUN(pfo_seg_build_launch(w.idx0, w.nodes[0], (int)n[1], capP, b->uniform ? nullptr : w.cnt1, w.seg_ptr, w.seg_cur,
                            w.seg_tmp, w.seg_mem, w.seg_of, w.seg_scratch, ss));
   return PFO_OK;
@@ -713,12 +698,7 @@ static int build_stage_b(const Dims& d, const Ws& w, const Params& P, hipStream_
     const LayerWs& lw = w.layer[l];
     const float* A = P.l[l - 1].w2;
     const float* bv = P.l[l - 1].b2;
-    static const int grouped_copy = getenv("PFO_GROUPED_COPY") ? atoi(getenv("PFO_GROUPED_COPY")) : 1;      // A/B switch
-    if (!grouped_copy) {
-      HIPOK(hipMemcpyAsync(lw.W1ovT_f, lw.W1ovT, HCpD * sizeof(float), hipMemcpyDeviceToDevice, ss), "copy failed");
-      HIPOK(hipMemcpyAsync(lw.Wqk_f, lw.T1, HCpD * sizeof(float), hipMemcpyDeviceToDevice, ss), "copy failed");   // edge | time rows stay
-      HIPOK(hipMemcpyAsync(lw.cqk_f, lw.tq, (size_t)HCp * sizeof(float), hipMemcpyDeviceToDevice, ss), "copy failed");
-    } else {
+    {
       // the rows the fold does not touch (edge | time, the two bias rows) come over as they are - ONE grouped launch instead of
       // three runtime blits (each a launch of its own in this chain of small dependent launches)
       PfoSumSlabs cp[3];
@@ -856,24 +836,11 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
   PFO_MARK("fwd.begin", s);
   // (with a deferred backward end in flight the side stream already waits for the caller's stream's last launch of that
   //  backward, and everything this call gives it either reads parameters only or sits behind an event of this call: no fork)
-  static const int skip_fork = getenv("PFO_SKIP_FORK") ? atoi(getenv("PFO_SKIP_FORK")) : 1;      // A/B switch
   // (only for the stream that queued the deferred backward: the side stream waits for THAT stream's last launch; a writer of
   //  the parameters on any other stream - a native optimizer step there, a graph replay - is ordered by the fork below)
-  if (!(skip_fork && sd.pending_for(s) && sd.deferred_from == s && bind_events)) {
+  if (!(sd.pending_for(s) && sd.deferred_from == s && bind_events)) {
     HIPOK(hipEventRecord(sd.fork, s), "event record failed");
     HIPOK(hipStreamWaitEvent(ss, sd.fork, 0), "event wait failed");
-  }
-  // The GRU's two weight images depend on the parameters alone.  With a deferred backward end + optimizer step in flight on
-  // the side stream they are made THERE, right behind that step's kernel (this call is queued while the device still runs the
-  // backward) - the join below covers them - instead of on the caller's stream between the join and the lazy GRU (6 us + a
-  // launch gap of the step's serial head).  PFO_GRU_IMG_SIDE=1: A/B (off: +6 us, as round 4 found for the refresh path).
-  static const int early_join = getenv("PFO_EARLY_JOIN") ? atoi(getenv("PFO_EARLY_JOIN")) : 1;      // A/B switch
-  static const int gru_img_side = getenv("PFO_GRU_IMG_SIDE") ? atoi(getenv("PFO_GRU_IMG_SIDE")) : 0;   // (measured: 1.2238 with, 1.2173 without - off)
-  const bool early_path = early_join != 0 && c->n_layers >= 2 && sd.early_ok && sd.early_gen == sd.side_gen;
-  bool gru_img_done = false;
-  if (gru_img_side && c->use_memory && build && bind_events && sd.pending_for(s) && sd.deferred_from == s && !early_path) {
-    RUN(build_gru_images(c, d, w, P, ss));
-    gru_img_done = true;
   }
   if (!b->prepared) RUN(prepare_sample(c, st, b, w, n, s));
   PFO_MARK("fwd.sampled", s);
@@ -881,15 +848,13 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
   // reads neither its buffers nor the parameters; everything below does (compaction counts, the GRU's weights ...)
   // (early: needs the fused state update's ordering - persist / message store run on the side stream behind every bucket -
   //  and layers >= 2 wait for fold_done, recorded there too; the top layer's raw b2 is the only late-bucket value this stream reads)
-  RUN(side_join(sd, s, early_join != 0 && c->n_layers >= 2));
+  RUN(side_join(sd, s, c->n_layers >= 2));
   PFO_MARK("fwd.side_joined", s);
   const bool fused_state = b->upd_src != nullptr && c->use_memory && L >= 2;
-  static const int side_late_env = getenv("PFO_FWD_SIDE_LATE") ? atoi(getenv("PFO_FWD_SIDE_LATE")) : 0;   // EXPERIMENT switch
-  const bool side_late = side_late_env != 0 && bind_events;
   PFO_REQUIRE(!fused_state || (b->upd_dst && b->upd_ts && b->upd_eidx && b->upd_B >= 1), "bad state-update arguments");
 
   // the GRU contractions come first on the main stream: their two weight images are made there too (one 4 us launch)
-  if (c->use_memory && build && !gru_img_done) RUN(build_gru_images(c, d, w, P, s));
+  if (c->use_memory && build) RUN(build_gru_images(c, d, w, P, s));
   bool composites_awaited = false;
 
   // ---- the nodes this step reads, compacted, and their level-0 rows packed (prepare_compact_pack; a prepared batch has them)
@@ -898,8 +863,7 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
   // With memory the row pack leaves the caller's stream: the fused GRU gathers its rows straight from the per-node tables, and
   // the packed copies (for the backward, which runs after the state update has overwritten the tables) + the level-0 remap
   // (first used by layer 1's attention) are made on the side stream, in front of the event layer 1 waits for anyway.
-  static const int pack_side_env = getenv("PFO_PACK_SIDE") ? atoi(getenv("PFO_PACK_SIDE")) : 1;      // A/B switch
-  const bool pack_side = pack_side_env && c->use_memory && !b->prepared;
+  const bool pack_side = c->use_memory && !b->prepared;
   if (!b->prepared) {
     if (pack_side) {
       // (comp_done rides on the completion of the compaction's LAST launch - its only one, or the third when the caller's extra
@@ -949,7 +913,7 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
     if (L >= 2) {
       if (build) RUN(build_stage_b(d, w, P, ss));
       else if (!capturing) HIPOK(hipStreamWaitEvent(ss, sd.pc_b, 0), "event wait failed");
-      if (fused_state && !side_late) {
+      if (fused_state) {
         // the batch's state update, here: behind the lazy GRU (whose rows it persists), beside layer 1, in front of the event
         // layer 2 waits for - persist + message store leave the critical path and are joined at no extra wait
         HIPOK(hipStreamWaitEvent(ss, sd.gru_done, 0), "event wait failed");
@@ -1028,35 +992,18 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
     PFO_MARK(mk_qk[l], s);
     RUN(pfo_attn_fwd_launch(a, s));
     PFO_MARK(mk_at[l], s);
-    if (l == 1 && fused_state && side_late) {
-      // EXPERIMENT (PFO_FWD_SIDE_LATE=1): the state update and the instance groups behind layer 1's attention kernel instead of
-      // beside it (they are ~12 small launches that share the chip with the step's second-longest kernel)
-      HIPOK(hipEventRecord(sd.layer[1], s), "event record failed");
-      HIPOK(hipStreamWaitEvent(ss, sd.layer[1], 0), "event wait failed");
-      RUN(state_update(c, st, w, b->upd_src, b->upd_dst, b->upd_ts, b->upd_eidx, b->upd_B, ss));
-      if (b->seg_in_forward) RUN(seg_prologue(c, b, w, d, n, ss));
-      HIPOK(hipEventRecord(sd.late_done, ss), "event record failed");
-    }
     // ---- h1 = relu(ctx' W1ovT + x W1[:, E:]^T + b1)   (MergeLayer fc1 with out_proj and the value projection folded in)
     if (l == 1) {
       // the x term was projected with the table: it arrives as a row-gathered addend of the epilogue
-      PFO_REQUIRE(pfo_gemm_takes_bx(N, D), "the touched-table layer needs the bf16x3 image kernels");
       PfoGemm g = g_nn(lw.ctx, HCp, lw.W1ovT, D, lw.h1, D, N, D, HCp);
       g.bias = p.b1; g.relu = 1; g.b_img = lw.iW1ov;
       g.add_src = w.QX + HCp; g.add_ld = WQ; g.add_idx = idx0;
       RUN(pfo_gemm_launch(g, s));
-    } else if (pfo_gemm_takes_bx(N, D)) {
+    } else {
       // both K-concatenated sources ([ctx' | x] against [W1ov | W1[:, E:]]) in one launch: h1 is written once
       PfoGemm g = g_nn(lw.ctx, HCp, W1ovT_l, D, lw.h1, D, N, D, HCp);
       g.A[1] = xA; g.lda[1] = D; g.a_idx[1] = x_idx; g.B[1] = W1b_l; g.ldb[1] = W1b_ld; g.K[1] = D;
       g.bias = b1_l; g.relu = 1; g.b_img = lw.iW1ov; g.b_img2 = lw.iW1b;
-      RUN(pfo_gemm_launch(g, s));
-    } else {
-      PfoGemm g = g_nn(lw.ctx, HCp, W1ovT_l, D, lw.h1, D, N, D, HCp);
-      g.b_img = lw.iW1ov;
-      RUN(pfo_gemm_launch(g, s));
-      g = g_nt(xA, D, x_idx, W1b_l, W1b_ld, lw.h1, D, N, D, D, b1_l);
-      g.accumulate = 1; g.relu = 1; g.b_img = lw.iW1b;
       RUN(pfo_gemm_launch(g, s));
     }
     PFO_MARK(mk_h1[l], s);
@@ -1068,7 +1015,6 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
       RUN(pfo_gemm_launch(g, s));
     }
   }
-  if (fused_state && side_late) HIPOK(hipStreamWaitEvent(s, sd.late_done, 0), "event wait failed");
   PFO_MARK("fwd.end", s);
   return PFO_OK;
 }
@@ -1153,7 +1099,6 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
     HIPOK(hipEventRecord(sd.seg_done, ss), "event record failed");
   }
   std::function<int()> deferred_chain;                       // a layer's chain-back launches, issued one layer later (below)
-  bool gates_fused = false;                                  // the GRU gate backward ran as the epilogue of layer 1's dx_tab launch
   static const char* const bwd_names[PFO_MAX_LAYERS + 1] = {"", "backward layer 1", "backward layer 2", "backward layer 3", "backward layer 4"};
   static const char* const mk_dh1[PFO_MAX_LAYERS + 1] = {"", "bwd.L1.dh1", "bwd.L2.dh1", "bwd.L3.dh1", "bwd.L4.dh1"};
   static const char* const mk_dctx[PFO_MAX_LAYERS + 1] = {"", "bwd.L1.dctx", "bwd.L2.dctx", "bwd.L3.dctx", "bwd.L4.dctx"};
@@ -1212,35 +1157,12 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
     // better than next to the attention backward alone, whose single-wavefront workgroups starved a 74 KB-LDS kernel of slots);
     // the fp16 tile (49 KB, half the matrix work) does better behind d ctx', beside the attention backward: 1.4495 against
     // 1.4532 ms over four interleaved pairs.  (Behind the attention backward, beside the serial tail: +2 % per step.)
-    static const int tna_mode = getenv("PFO_TNA_MODE") ? atoi(getenv("PFO_TNA_MODE")) : 0;
-    const int tna_mode_g = tna_mode;   // A/B: 0 fork behind the d ctx' contraction (beside the attention backward), 2 beside d ctx', 1 main stream
-    bool tn_a_bound = false;                                   // tn_a already rides on the d ctx' launch
-    const bool dq_atomic = l == 1 && dq_atomic_mode(c, b);
-    bool dh1_summed = false;
-    auto tn_a_side = [&]() -> int {
-      if (!tn_a_bound) HIPOK(hipEventRecord(sd.tn_a, s), "event record failed");
-      HIPOK(hipStreamWaitEvent(ss, sd.tn_a, 0), "event wait failed");
-      RUN(side_mean_once());
-      if (dq_atomic && l == 1) {
-        // the d h1 half of the per-row sums, here beside the attention backward (whose atomics fill the other half)
-        RUN(pfo_segsum_cols_launch(dh1, D, w.seg_ptr, w.seg_mem, w.seg_of, n[1], w.n_core, w.Dq + HCp, WQ, ss));
-        HIPOK(hipEventRecord(sd.dh1_sum, ss), "event record failed");
-        dh1_summed = true;
-      }
-      PFO_MARK("@side1.tn_a.begin", ss);
-      RUN(pfo_gemm_tn_group_launch(tn, n_tn_a, N, nullptr, w.slabs2, w.slab_floats, ss));
-      PFO_MARK("@side1.tn_a.end", ss);
-      HIPOK(hipEventRecord(sd.tn_a_done, ss), "event record failed");
-      return PFO_OK;
-    };
-    if (l == 1 && tna_mode == 2 && !pfo_prof_on()) RUN(tn_a_side());
     // merged fc1: d ctx' = dh1 W1ovT^T (dx = dh1 W1[:, E:] is taken together with the query/key part below)
     {
       PfoGemm q = g_nt(dh1, D, nullptr, W1ovT_l, D, w.dctx, HCp, N, HCp, D, nullptr);
       q.b_img = lw.iW1ovT;
-      const bool bind_tn_a = bind_events && l == 1 && tna_mode == 0 && !pfo_prof_on();
+      const bool bind_tn_a = bind_events && l == 1 && !pfo_prof_on();
       PFO_RUN_BOUND(bind_tn_a, sd.tn_a, 0, s, pfo_gemm_launch(q, s));
-      if (bind_tn_a) tn_a_bound = true;
       PFO_MARK(mk_dctx[l], s);
       if (l == 1 && b->mid_event && !b->mid_event_late) HIPOK(hipEventRecord((hipEvent_t)b->mid_event, s), "event record failed");
     }
@@ -1250,11 +1172,17 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
       ++ntn;
     }
     if (l == 1) {
-      if (pfo_prof_on() || tna_mode == 1) {        // event-bracketed step (bench.py's roofline sample): serial, so the bracket times the kernel alone
+      if (pfo_prof_on()) {        // event-bracketed step (bench.py's roofline sample): serial, so the bracket times the kernel alone
         RUN(pfo_gemm_tn_group_launch(tn, n_tn_a, N, nullptr, w.slabs, w.slab_floats, s));
         HIPOK(hipEventRecord(sd.tn_a_done, s), "event record failed");
-      } else if (tna_mode == 0) {
-        RUN(tn_a_side());
+      } else {
+        if (!bind_events) HIPOK(hipEventRecord(sd.tn_a, s), "event record failed");     // (bound: tn_a rides on the d ctx' launch)
+        HIPOK(hipStreamWaitEvent(ss, sd.tn_a, 0), "event wait failed");
+        RUN(side_mean_once());
+        PFO_MARK("@side1.tn_a.begin", ss);
+        RUN(pfo_gemm_tn_group_launch(tn, n_tn_a, N, nullptr, w.slabs2, w.slab_floats, ss));
+        PFO_MARK("@side1.tn_a.end", ss);
+        HIPOK(hipEventRecord(sd.tn_a_done, ss), "event record failed");
       }
     }
     // attention core
@@ -1283,16 +1211,8 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
       // key-side gradients of instances with identical neighbour lists leave as one set of atomics (attn.hip)
       a.members = w.seg_mem; a.seg_ptr = w.seg_ptr; a.n_rows = w.n_core; a.run_cnt = w.cnt1; a.dqk_live = w.dqk_live;
     }
-    if (dq_atomic) { a.dq_rows = w.Dq; a.dq_ld = WQ; }
     const int dqk_by_member = pfo_attn_bwd_uses_runs(a) ? 1 : 0;
-    const bool dq_added = dq_atomic && dqk_by_member;         // (the alignment test of pfo_attn_bwd_uses_runs may still say no)
-    if (dq_added && !dh1_summed) {
-      // serial forms (bracketed steps, PFO_TNA_MODE): the d h1 half on this stream, in front of the attention backward
-      // (the groups exist: seg_done was awaited above, or the forward built them)
-      RUN(pfo_segsum_cols_launch(dh1, D, w.seg_ptr, w.seg_mem, w.seg_of, n[1], w.n_core, w.Dq + HCp, WQ, s));
-    }
-    PFO_RUN_BOUND(dq_added && bind_events, sd.tn_b, 0, s, pfo_attn_bwd_launch(a, &n_parts, s));   // (atomic row sums: tn_b rides on the attention launch, no segment sum behind it)
-    if (l == 1 && tna_mode == 3 && !pfo_prof_on()) RUN(tn_a_side());     // A/B: the instance weight gradients BEHIND the attention backward, beside the serial tail
+    RUN(pfo_attn_bwd_launch(a, &n_parts, s));
     PFO_MARK(mk_battn[l], s);
     if (l == 1 && b->mid_event && b->mid_event_late) HIPOK(hipEventRecord((hipEvent_t)b->mid_event, s), "event record failed");
     if (det) det_rows += n_parts;
@@ -1305,17 +1225,11 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
       // weight gradients against x - is taken AFTER summing those gradients per table row: contractions over the
       // ~11 k touched rows instead of the ~54 k instances.
       if (!c->use_memory) HIPOK(hipStreamWaitEvent(s, sd.seg_done, 0), "event wait failed");   // (with memory: awaited before the attention backward)
-      if (dq_added) {
-        // Dq is complete when the attention launch and the side stream's d h1 sum are (the latter fired long ago)
-        if (!bind_events) HIPOK(hipEventRecord(sd.tn_b, s), "event record failed");
-        if (dh1_summed) HIPOK(hipStreamWaitEvent(s, sd.dh1_sum, 0), "event wait failed");
-      } else {
       PFO_RUN_BOUND(bind_events, sd.tn_b, 0, s,
                     pfo_segsum_launch(dqk_l, HCp, dh1, D, w.seg_ptr, w.seg_mem, w.seg_of, n[1], w.n_core, capP, dqk_by_member,
                                       dqk_by_member ? w.dqk_live : nullptr, w.Dq, s));   // Dq = [sum dqk' | sum dh1]
       // the weight gradients over the table rows go to the side stream too (beside d h0 / the GRU backward on this one)
       if (!bind_events) HIPOK(hipEventRecord(sd.tn_b, s), "event record failed");
-      }
       PFO_MARK("bwd.L1.segsum", s);
       HIPOK(hipStreamWaitEvent(ss, sd.tn_b, 0), "event wait failed");
       RUN(side_mean_once());
@@ -1332,20 +1246,12 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
         PfoGemm q = g_nn(w.Dq, WQ, lw.Wqk, D, w.dx_tab, D, capP, D, HCp);
         q.A[1] = w.Dq + HCp; q.lda[1] = WQ; q.B[1] = p.w1 + E; q.ldb[1] = E + D; q.K[1] = D;
         q.b_img = lw.iWqkT; q.b_img2 = lw.iW1bT; q.m_dev = w.n_core;
-        // The GRU's gate backward rides in this launch's epilogue when it takes the 32-row kernel (one table, float rows):
-        // d h0 = key side (scattered by the attention backward) + this contraction's query side never goes to HBM as dx_tab,
-        // and the separate gate launch (26 us + a launch gap on the serial tail at C2) disappears
-        const int fuse_env = getenv("PFO_FUSE_GATES") ? atoi(getenv("PFO_FUSE_GATES")) : 0;   // (read per call: a test flips it)         // A/B switch (measured: 1.458-1.461 ms with, 1.453 without - the epilogue runs on the ~375 live workgroups of a 32-row launch, the separate kernel on the whole chip; off)
-        if (fuse_env && n_rep == 1 && !det && pfo_gemm_takes_skinny(capP, D) && (D % 4) == 0) {
-          q.gg_gates = w.gates; q.gg_h = w.h_rows; q.gg_hm = w.hm; q.gg_dh0 = w.d_h0; q.gg_dgi = w.gi; q.gg_dgh = w.gh;
-          gates_fused = true;
-        }
         RUN(pfo_gemm_launch(q, s));
         PFO_MARK(mk_dx[l], s);
       }
     } else {
       // d h1 of the layer below, self rows [0, N): [dqk' | dh1] [Q_f ; W1b_f], masked by that layer's ReLU
-      if (pfo_gemm_takes_bx(N, D)) {
+      {
         // both sources in one launch, dx written once
         PfoGemm q = g_nn(dqk_l, HCp, Wqk_l, D, dx, D, N, D, HCp);
         q.A[1] = dh1; q.lda[1] = D; q.B[1] = W1b_l; q.ldb[1] = W1b_ld; q.K[1] = D;
@@ -1353,14 +1259,6 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
         q.relu_src = xA; q.relu_ld = D;
         PFO_RUN_BOUND(bind_events, sd.layer[l], 0, s, pfo_gemm_launch(q, s));     // (layer[l], recorded below, rides on this launch)
         if (bind_events) layer_event_bound = true;
-      } else {
-        PfoGemm q = g_nn(dh1, D, W1b_l, W1b_ld, dx, D, N, D, D);
-        q.b_img = lw.iW1bT;
-        RUN(pfo_gemm_launch(q, s));
-        q = g_nn(dqk_l, HCp, Wqk_l, D, dx, D, N, D, HCp);
-        q.accumulate = 1; q.b_img = lw.iWqkT;
-        q.relu_src = xA; q.relu_ld = D;
-        RUN(pfo_gemm_launch(q, s));
       }
       PFO_MARK(mk_dx[l], s);
       set_tn(tn[ntn], dqk_l, HCp, xA, D, x_idx, HCp, D, dWqk_l, D, gqk_l);
@@ -1392,10 +1290,6 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
       // (on the second side stream: the first one must stay free for layer 1's weight gradients over the instances)
       hipStream_t sf = sd.s2;
       HIPOK(hipStreamWaitEvent(sf, sd.layer[l], 0), "event wait failed");
-      // (A/B, PFO_L2_CHAIN_LATE=1: layer 2's weight gradients and chain wait for layer 1's d ctx' contraction too - they then
-      //  run beside the attention backward instead of taking workgroup slots from the contraction the caller's stream waits for)
-      static const int chain_late = getenv("PFO_L2_CHAIN_LATE") ? atoi(getenv("PFO_L2_CHAIN_LATE")) : 0;
-      if (chain_late && l == 2 && !pfo_prof_on() && tna_mode_g == 0) HIPOK(hipStreamWaitEvent(sf, sd.tn_a, 0), "event wait failed");
       if (pfo_prof_on()) {
         // event-bracketed step (bench.py's roofline sample): on the caller's stream, so that the bracket times the kernel alone
         RUN(pfo_gemm_tn_group_launch(tn, ntn, N, nullptr, w.slabs, w.slab_floats, s));
@@ -1404,12 +1298,7 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
       } else {
         RUN(pfo_gemm_tn_group_launch(tn, ntn, N, nullptr, w.slabs3, w.slab_floats, sf));
       }
-      static const int grouped_copy_b = getenv("PFO_GROUPED_COPY") ? atoi(getenv("PFO_GROUPED_COPY")) : 1;      // A/B switch
-      if (!grouped_copy_b) {
-        HIPOK(hipMemcpyAsync(lw.dT1, lw.dWqk_f, HCpD * sizeof(float), hipMemcpyDeviceToDevice, sf), "copy failed");
-        HIPOK(hipMemcpyAsync(lw.gqk, lw.gqk_f, (size_t)HCp * sizeof(float), hipMemcpyDeviceToDevice, sf), "copy failed");
-        HIPOK(hipMemcpyAsync(lw.dW1ovT, lw.dW1ovT_f, HCpD * sizeof(float), hipMemcpyDeviceToDevice, sf), "copy failed");
-      } else {
+      {
         PfoSumSlabs cp[3];                        // (one grouped launch instead of three runtime blits, as in build_stage_b)
         cp[0].dst = lw.dT1;    cp[0].src = lw.dWqk_f;   cp[0].count = HCpD;
         cp[1].dst = lw.gqk;    cp[1].src = lw.gqk_f;    cp[1].count = HCp;
@@ -1538,8 +1427,7 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
     }
       return PFO_OK;
     };
-    static const int defer = getenv("PFO_DEFER_CHAIN") ? atoi(getenv("PFO_DEFER_CHAIN")) : 1;      // A/B switch
-    if (l > 1 && defer && !pfo_prof_on()) deferred_chain = chain_back;
+    if (l > 1 && !pfo_prof_on()) deferred_chain = chain_back;
     else RUN(chain_back());
   }
   if (deferred_chain) { RUN(deferred_chain()); deferred_chain = nullptr; }
@@ -1549,9 +1437,8 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
   if (c->use_memory) {
     PfoRange range_gru("backward GRU");
     // (the GRU's backward covers the rows the layers read: rows only the extra list names carry no gradient)
-    if (!gates_fused)
-      RUN(pfo_gru_gates_bwd_launch(w.gates, w.gi, w.gh, w.h_rows, w.hm, w.n_core, capP, D, w.d_h0, n_rep, rep_stride,
-                                   w.dx_tab, det, s));
+    RUN(pfo_gru_gates_bwd_launch(w.gates, w.gi, w.gh, w.h_rows, w.hm, w.n_core, capP, D, w.d_h0, n_rep, rep_stride,
+                                 w.dx_tab, det, s));
     PFO_MARK("bwd.gru.gates", s);
     {
       PfoTnProblem gp[2];

@@ -257,8 +257,7 @@ def test_gemm_split_contraction_row_scales(M):
     A[1::7] *= ramp[::-1]                                   # ... and one that shrinks
     A[2::7, K // 2:] = 0                                    # zeros behind a live half
     A[3::7] = 0                                             # rows of zeros
-    if os.environ.get("PFO_BX_FMT") != "0":                 # (the bf16x3 path feeds denormal pieces to the matrix cores, which flush them)
-        A[4::7] = 1e-42                                     # fp32 denormals
+    A[4::7] = 1e-42                                         # fp32 denormals
     W[5::11] = 0
     W[6::11] *= ramp[::-1]
     A = A.astype(np.float32); W = W.astype(np.float32)

@@ -314,43 +314,6 @@ def test_backward_after_a_parameter_update_is_refused():
         P.bpr_loss(emb, B, 3).backward()
 
 
-def test_gru_gate_backward_as_gemm_epilogue_equals_the_separate_kernel():
-    """PFO_FUSE_GATES=1: the GRU's gate backward runs as the epilogue of layer 1's dx_tab contraction (32-row image kernel)
-    instead of its own launch.  Same arithmetic per element on the same inputs: gradients of a step are identical up to the
-    summation order of nothing - bitwise in deterministic mode... the fused form is taken only for the float table (one
-    replica, not the deterministic int64 one), so the comparison is at fp32 rounding of the atomics: 1e-5 relative."""
-    from pfotgnrec_amd.synthetic import SyntheticConfig, make_graph
-    cfg = SyntheticConfig("fg", 300, 25, 6000, 64, 2, 8, 2)
-    g = make_graph(cfg, with_prices=False)
-    d = g.data
-    B, K = 64, 8
-    s = 3000
-    neg = np.random.RandomState(3).randint(cfg.n_users + 1, cfg.n_users + cfg.n_items + 1, size=B * 3)
-
-    def grads(fuse):
-        os.environ["PFO_FUSE_GATES"] = "1" if fuse else "0"
-        try:
-            torch.manual_seed(5)
-            tgn = P.TGN(P.get_neighbor_finder(d, False), g.node_features, g.edge_features, DEV, n_layers=2, n_heads=2, dropout=0.0,
-                        use_memory=True, memory_dimension=64, message_function="identity", n_neighbors=K)
-            tgn.train()
-            for s0 in (s - 2 * B, s - B):                     # populate memory and pending messages
-                with torch.no_grad():
-                    tgn.compute_temporal_embeddings(d.sources[s0:s0 + B], d.destinations[s0:s0 + B], neg, d.timestamps[s0:s0 + B],
-                                                    d.edge_idxs[s0:s0 + B], K)
-            emb = torch.cat(tgn.compute_temporal_embeddings(d.sources[s:s + B], d.destinations[s:s + B], neg, d.timestamps[s:s + B],
-                                                            d.edge_idxs[s:s + B], K))
-            P.bpr_loss(emb, B, 3).backward()
-            torch.cuda.synchronize()
-            return tgn.flat_grad.clone()
-        finally:
-            os.environ.pop("PFO_FUSE_GATES", None)
-    g0, g1 = grads(False), grads(True)
-    gru = slice(2 * 64, 2 * 64 + 3 * 64 * (3 * 64 + 4) + 3 * 64 * 64 + 6 * 64)      # the GRU block of the flat layout
-    assert g0[gru].abs().max().item() > 0
-    assert (g0 - g1).abs().max().item() <= 1e-5 * g0.abs().max().item()
-
-
 @pytest.mark.parametrize("use_memory", [True, False])
 def test_fused_backward_and_optimizer_step_on_the_side_stream_equals_the_serial_order(use_memory):
     """``bpr_step(..., optimizer=opt)``: the end of the backward and the Adam kernel stay on the library's side stream while

@@ -1,4 +1,4 @@
-"""Round-6 GPU tests: the three forms of the attention forward (register form, LDS key ring, instance pipeline) against each
+"""Round-6 GPU tests: the two forms of the attention forward (register form, LDS key ring) against each
 other and the oracle at ragged shapes, the optimizer step that clears the gradients it read, the shader-clock stamps."""
 import os
 import subprocess
@@ -58,13 +58,13 @@ np.savez(sys.argv[1], **out)
 @pytest.mark.parametrize("D,H,K,L,B", [(172, 2, 20, 2, 96), (64, 4, 7, 2, 40), (32, 1, 10, 1, 64), (172, 4, 20, 2, 24), (256, 2, 5, 1, 16)])
 def test_attention_forward_forms_agree(tmp_path, D, H, K, L, B):
     """The LDS key-ring forward (default; one LDS-DMA per key, [node | edge] columns as one vector, scores in log2 units with
-    the scale folded into the query), the round-5 register form (PFO_ATTN_FWD_RING=0) and the instance pipeline
-    (PFO_ATTN_FWD_PIPE=1 with its launch threshold at 0) on the same two steps: embeddings within 1e-6 of each other (the
+    the scale folded into the query) and the round-5 register form (PFO_ATTN_FWD_RING=0) on the same two steps: embeddings
+    within 1e-6 of each other (the
     forms differ only in rounding: pre-scaled query, exp2), gradients within 1e-5 (the backward reads ctx' / weights the
     forward wrote).  Shapes: C2's, four heads (NR H = 12: four wavefronts per SIMD), one column group, D = 256 (four groups),
     K < and > the ring; batches early in the timeline hold instances with 0 .. K neighbours (odd counts: the pair tail)."""
     res = {}
-    for name, env in (("ring", {}), ("reg", {"PFO_ATTN_FWD_RING": "0"}), ("pipe", {"PFO_ATTN_FWD_PIPE": "1", "PFO_ATTN_FWD_PIPE_MIN": "0"})):
+    for name, env in (("ring", {}), ("reg", {"PFO_ATTN_FWD_RING": "0"})):
         path = str(tmp_path / (name + ".npz"))
         r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", _FWD_CHILD, path, REPO, str(D), str(H), str(K), str(L), str(B), "4"],
                            env=dict(os.environ, **env), capture_output=True)
@@ -73,7 +73,6 @@ def test_attention_forward_forms_agree(tmp_path, D, H, K, L, B):
     for k in res["reg"].files:
         tol = 1e-6 if k.startswith("emb") else 2e-5
         assert relerr(res["ring"][k], res["reg"][k]) < tol, ("ring", k, relerr(res["ring"][k], res["reg"][k]))
-        assert relerr(res["pipe"][k], res["reg"][k]) < tol, ("pipe", k, relerr(res["pipe"][k], res["reg"][k]))
     assert np.abs(res["ring"]["emb0"]).max() > 0 and np.isfinite(res["ring"]["grad1"]).all()
 
 
