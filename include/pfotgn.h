@@ -193,6 +193,32 @@ int pfo_rank_metrics(const float* emb, int64_t B, int32_t D, int32_t n_items, in
                      float* ndcg_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The whole per-interaction part of eval_recommendation (evaluation.py:114-207) in one launch: a superset of
+ * pfo_rank_metrics that also ranks the head of the candidate list and evaluates the investment metrics.
+ *   emb f32[B*(2+n_neg), D] = [src B | dst B | neg B*n_neg], 16-byte aligned, D a multiple of 4, D <= 256; read once.
+ *   cand i32[B, 1+n_neg]: item node ids of the candidates, column 0 the destination (evaluation.py:176-178).
+ *   day_idx i32[B]; port_idx i32[B, port_stride] stock indices, port_len i32[B] (0: the reference's `'' in portfolio`
+ *   branch, evaluation.py:153-157); ret_past / ret_future f64[n_days, n_stocks, n_ret]: log-returns of
+ *   time_feature_past / time_feature_future, np.log(p[1:] / p[:-1]) per stock (evaluation.py:31); a candidate's stock
+ *   index is its node id - upper_u - 1.  A day or a stock outside the tables turns that row's figures into NaN.
+ * Rows [out_row0, out_row0 + B) of buffers that hold out_rows rows are written (a whole evaluation pass accumulates in
+ * one set of buffers and is read back once); any output pointer may be NULL:
+ *   rank_out i32, hits_out f32[.,3], ndcg_out f32[.,3]: as pfo_rank_metrics.
+ *   top5_pos i32[.,5]: positions into the 1+n_neg row of the five best candidates in the canonical order (stable
+ *   ascending argsort reversed, SURVEY App. A-9: score descending, the larger position first among equal scores, so the
+ *   positive comes last among its ties); top5_item i32[.,5]: their node ids; -1 where fewer than five candidates exist.
+ *   invest_out f64[.,12] = (return@1,3,5 | sharpe@1,3,5) in-sample, then the same six out-of-sample: the change
+ *   of mean(daily) * 251 and of mean(daily) * 251 / (std(daily, ddof=0) * sqrt(251)) when the top-k stocks' rows join the
+ *   portfolio's (duplicates counted as often as they occur), daily = the mean log-return over the rows
+ *   (return_sharpe_at_k, evaluation.py:23-36).  fp64 in numpy's order of operations; no guards (zero deviation: inf / nan).
+ */
+int pfo_eval_metrics(const float* emb, int64_t B, int32_t D, int32_t n_neg, const int32_t* cand, const int32_t* day_idx,
+                     const int32_t* port_idx, const int32_t* port_len, int32_t port_stride, const double* ret_past,
+                     const double* ret_future, int32_t n_days, int32_t n_stocks, int32_t n_ret, int32_t upper_u,
+                     int64_t out_row0, int64_t out_rows, int32_t* rank_out, float* hits_out, float* ndcg_out,
+                     int32_t* top5_pos, int32_t* top5_item, double* invest_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Time-sorted adjacency built on the device: replaces get_neighbor_finder / NeighborFinder.__init__ (utils/utils.py:117-148).
  * Every edge e contributes (dst, eidx, ts) to row src[e] and (src, eidx, ts) to row dst[e]; rows are sorted by timestamp,
  * ties in edge order (Python's stable sorted(key=ts), utils.py:139).  A stable LSD radix sort of the 2E entries; the eight

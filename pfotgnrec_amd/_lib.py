@@ -81,6 +81,8 @@ PROTOTYPES = {
     "pfo_bpr_loss_parts": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_float, _VP,
                                      _VP, _VP]),
     "pfo_rank_metrics": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
+    "pfo_eval_metrics": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_adam_step": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                 _VP]),
     "pfo_csr_build_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),

@@ -267,6 +267,26 @@ __device__ __forceinline__ float pfo_wave_max(float v) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// numpy's pairwise summation order for 8 <= n <= 128 (np.mean / np.std of a contiguous fp64 vector, main.py:243,
+// evaluation.py:33-35): eight interleaved partial sums, combined as a balanced tree, then the tail.
+__device__ __forceinline__ double pfo_np_sum(const double* a, int n) {
+  if (n < 8) {
+    double r = 0.0;
+    for (int i = 0; i < n; ++i) r += a[i];
+    return r;
+  }
+  double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
+  int i = 8;
+  for (; i < n - (n % 8); i += 8) {
+    r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
+    r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
+  }
+  double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
+  for (; i < n; ++i) res += a[i];
+  return res;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Shader clock as the product kernels see it (include/pfotgn.h pfo_shader_clock): the first wavefront of workgroup 0 of a few
 // large kernels reads the shader cycle counter (s_memtime) and the constant 100 MHz counter (s_memrealtime) at its start and its
 // end and adds both differences to a per-kernel pair - two scalar reads and two atomics per LAUNCH.  cycles / (ticks * 10 ns)

@@ -275,25 +275,7 @@ extern "C" int pfo_neg_draw_dev(const uint8_t* item_avail, int32_t n_items, cons
 
 // ---------------------------------------------------------------------------------------------
 // K2: main.py:209-304.  One wavefront per interaction, one lane per candidate, fp64 throughout.
-// numpy's pairwise summation order for 8 <= n <= 128 (used by np.mean, main.py:243): eight
-// interleaved partial sums, combined as a balanced tree, then the tail.
-__device__ __forceinline__ double np_sum(const double* a, int n) {
-  if (n < 8) {
-    double r = 0.0;
-    for (int i = 0; i < n; ++i) r += a[i];
-    return r;
-  }
-  double r0 = a[0], r1 = a[1], r2 = a[2], r3 = a[3], r4 = a[4], r5 = a[5], r6 = a[6], r7 = a[7];
-  int i = 8;
-  for (; i < n - (n % 8); i += 8) {
-    r0 += a[i]; r1 += a[i + 1]; r2 += a[i + 2]; r3 += a[i + 3];
-    r4 += a[i + 4]; r5 += a[i + 5]; r6 += a[i + 6]; r7 += a[i + 7];
-  }
-  double res = ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
-  for (; i < n; ++i) res += a[i];
-  return res;
-}
-
+// (np.mean's summation order: pfo_np_sum, common.hpp)
 #define PFO_MV_MAX_RET 128
 
 __global__ __launch_bounds__(64) void mv_select_kernel(const double* __restrict__ returns, int n_items, int n_ret,
@@ -314,7 +296,7 @@ __global__ __launch_bounds__(64) void mv_select_kernel(const double* __restrict_
   double y = 0.0;
   if (have) {
     const double* ri = day + (int64_t)item * n_ret;
-    const double mu = np_sum(ri, n_ret) / (double)n_ret;                  // main.py:243
+    const double mu = pfo_np_sum(ri, n_ret) / (double)n_ret;                  // main.py:243
     const double inv = 1.0 / (double)(n_ret - 1);                         // np.cov: c *= 1/(N - ddof)
     double var = 0.0;
     for (int t = 0; t < n_ret; ++t) var += (ri[t] - mu) * (ri[t] - mu);
@@ -325,7 +307,7 @@ __global__ __launch_bounds__(64) void mv_select_kernel(const double* __restrict_
       double ssum = 0.0;
       for (int p = 0; p < plen; ++p) {
         const double* rp = day + (int64_t)port_idx[b * port_stride + p] * n_ret;
-        const double mp = np_sum(rp, n_ret) / (double)n_ret;
+        const double mp = pfo_np_sum(rp, n_ret) / (double)n_ret;
         double cv = 0.0;
         for (int t = 0; t < n_ret; ++t) cv += (ri[t] - mu) * (rp[t] - mp);
         ssum += cv * inv;                                                 // np.sum(sigma_ij), main.py:268

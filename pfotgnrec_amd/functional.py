@@ -191,3 +191,41 @@ def rank_metrics(emb, batch, n_items):
     _lib.call("pfo_rank_metrics", emb.data_ptr(), batch, D, n_items, rank.data_ptr(), hits.data_ptr(), ndcg.data_ptr(),
               _lib.stream_ptr())
     return rank, hits, ndcg
+
+
+def eval_buffers(rows, device):
+    """Preallocated outputs of ``eval_metrics`` for ``rows`` interactions: (rank i32[rows], recall f32[rows,3],
+    ndcg f32[rows,3], top5_pos i32[rows,5], top5_item i32[rows,5], invest f64[rows,12])."""
+    _lib.require_gpu(device)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+    return (e(rows, torch.int32), e((rows, 3), torch.float32), e((rows, 3), torch.float32), e((rows, 5), torch.int32),
+            e((rows, 5), torch.int32), e((rows, 12), torch.float64))
+
+
+def eval_metrics(emb, batch, n_neg, cand, day_idx, port_idx, port_len, ret_past, ret_future, upper_u, out=None, out_row0=0):
+    """The per-interaction part of evaluation.py:114-207 in one launch (``pfo_eval_metrics``): emb [R,D] = [src B | dst B |
+    neg B*n_neg]; cand i32[B,1+n_neg] item node ids, column 0 the destination; day_idx i32[B]; port_idx i32[B,W] stock
+    indices and port_len i32[B] (0 for the reference's ``'' in portfolio`` rows); ret_past / ret_future f64[n_days, n_stocks,
+    n_ret] log-return tables (``InvestTables``); all on the device.
+
+    Returns (rank i32[B], recall f32[B,3], ndcg f32[B,3], top5_pos i32[B,5], top5_item i32[B,5], invest f64[B,12]): rank,
+    recall and NDCG as ``rank_metrics``; the five best candidates in the canonical order (score descending, the larger
+    position first among equal scores) as positions into the 1+n_neg row and as node ids; invest =
+    (return@1,3,5 | sharpe@1,3,5) in-sample, then out-of-sample (``return_sharpe_at_k``, evaluation.py:23-36).
+    ``out`` (``eval_buffers``) and ``out_row0``: write rows [out_row0, out_row0 + B) of preallocated buffers - an evaluation
+    pass accumulates on the device and is read back once; the returned tensors are those rows."""
+    _lib.require_gpu(emb.device)
+    emb = emb.contiguous()
+    D = emb.shape[1]
+    if out is None:
+        out, out_row0 = eval_buffers(batch, emb.device), 0
+    W = port_idx.shape[1] if port_idx is not None and port_idx.dim() == 2 else 0
+    n_days, n_stocks, n_ret = ret_past.shape
+    if tuple(ret_future.shape) != (n_days, n_stocks, n_ret):
+        raise ValueError("ret_past and ret_future differ in shape")
+    if emb.shape[0] != batch * (2 + n_neg) or tuple(cand.shape) != (batch, 1 + n_neg):
+        raise ValueError("emb must hold batch * (2 + n_neg) rows and cand batch x (1 + n_neg) ids")
+    _lib.call("pfo_eval_metrics", emb.data_ptr(), batch, D, n_neg, _lib.ptr(cand.contiguous()), _lib.ptr(day_idx.contiguous()),
+              _lib.ptr(port_idx.contiguous() if W else None), _lib.ptr(port_len.contiguous()), W, _lib.ptr(ret_past), _lib.ptr(ret_future),
+              n_days, n_stocks, n_ret, int(upper_u), int(out_row0), out[0].shape[0], *[o.data_ptr() for o in out], _lib.stream_ptr())
+    return tuple(o[out_row0:out_row0 + batch] for o in out)

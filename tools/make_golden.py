@@ -7,7 +7,7 @@ reference's outputs.  The fixtures are data only - no reference source text is
 stored.  The inline MV block of main.py (not importable: wandb/CUDA/data files)
 is executed in place from the reference tree, as SURVEY.md App. E describes.
 
-Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8]      (default: all)
+Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8 g9a g9b]      (default: all)
 Library versions used are recorded in each fixture (``versions``).
 """
 import os
@@ -575,10 +575,332 @@ def g8():
     save("g8_dropout", **out)
 
 
+# ------------------------------------------------------------------ G9: evaluation loop with the investment metrics
+def _finance_ref():
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import finance_ref
+    return finance_ref
+
+
+def _baseline_block():
+    """evaluation.py's lines from ``if '' in portfolio:`` to the out-of-sample baseline (:153-172), compiled in place."""
+    lines = open(os.path.join(REF, "evaluation.py")).read().split("\n")
+    a = next(i for i, l in enumerate(lines) if l.strip().startswith("if '' in portfolio"))
+    b = next(i for i, l in enumerate(lines) if "Sort the pos and neg items" in l)
+    return compile(textwrap.dedent("\n".join(lines[a:b])), "<reference evaluation.py:153-172>", "exec")
+
+
+def _ref_invest(ev, block, ts_key, portfolio, items, tf_past, tf_future, period=30):
+    """One interaction of evaluation.py:146-190 through the reference's own code; ``items`` = stock codes in ranked order."""
+    ns = dict(np=np, portfolio=portfolio, ts=ts_key, time_feature_past=tf_past, time_feature_future=tf_future, period=period)
+    exec(block, ns)
+    out = np.zeros(12)
+    for t, (pf, r, s, tf) in enumerate(((ns["port_feature"], ns["return_"], ns["sharpe"], tf_past),
+                                        (ns["port_feature_"], ns["return__"], ns["sharpe_"], tf_future))):
+        for i, k in enumerate((1, 3, 5)):
+            dr, ds = ev.return_sharpe_at_k(ts_key, pf, r, s, tf, items, k)
+            out[t * 6 + i], out[t * 6 + 3 + i] = dr, ds
+    return out
+
+
+def _exact_invest(F, ret_past_day, ret_future_day, portfolio, map_item_id, top_idx):
+    port = [] if "" in portfolio else [map_item_id[c] for c in portfolio]
+    x, scale = F.invest_metrics(ret_past_day, ret_future_day, port, top_idx, dtype=np.longdouble, parts=True)
+    hi = x.astype(np.float64)
+    return hi, (x - hi).astype(np.float64), scale.astype(np.float64)
+
+
+def _check_signs(F, ref, hi, lo, scale):
+    """No golden value within the test's bar of zero except exact zeros: the '>0' shares then compare exactly."""
+    e_ref = np.abs((ref - hi) - lo)
+    bar = F.invest_bar(e_ref.max(), scale)
+    near = (np.abs(ref) <= bar) & (ref != 0)
+    assert not near.any(), (ref[near], bar[near])
+    return e_ref
+
+
+def g9a():
+    """pfo_eval_metrics, kernel level: score rows [positive | 25 negatives] as g6's, scores multiples of 1/64 (any f32
+    summation order reproduces them from the embeddings the test builds), candidate ids, portfolios, past / future prices;
+    expected values from the reference's return_sharpe_at_k and baseline lines fed the canonical ranking."""
+    import evaluation as ev
+    from pfotgnrec_amd.mv_sampler import log_returns
+    F = _finance_ref()
+    block = _baseline_block()
+    rs = np.random.RandomState(29)
+    B, N, U, I, n_days, W = 120, 25, 50, 40, 4, 7
+    codes = ["%06d" % (i + 1) for i in range(I)]
+    map_item_id = {c: i for i, c in enumerate(codes)}
+    days = ["2020010%d" % (d + 1) for d in range(n_days)]
+    past = 100.0 * np.exp(np.cumsum(rs.randn(n_days, I, 30) * 0.02, axis=2))
+    future = 100.0 * np.exp(np.cumsum(rs.randn(n_days, I, 30) * 0.02 + 0.001, axis=2))
+    tf_past = {d: {c: past[k, j] for j, c in enumerate(codes)} for k, d in enumerate(days)}
+    tf_future = {d: {c: future[k, j] for j, c in enumerate(codes)} for k, d in enumerate(days)}
+    ret_past, ret_future = log_returns(past), log_returns(future)
+    day_idx = rs.randint(0, n_days, B)
+    ts = np.array([float(days[d]) * 1e6 + rs.randint(0, 235959) for d in day_idx])          # YYYYMMDDhhmmss
+    assert all(str(t)[:8] == days[d] for t, d in zip(ts, day_idx))
+    scores = np.zeros((B, 1 + N), np.float32)
+    cand = np.zeros((B, 1 + N), np.int64)
+    kind = np.zeros(B, np.int64)
+    for b in range(B):
+        k = kind[b] = b % 10
+        scores[b] = rs.choice(np.arange(-400, 400), 1 + N, replace=False) / 64.0            # distinct, |s| < 8
+        cand[b] = U + 1 + rs.choice(I, 1 + N, replace=False)
+        order = np.argsort(scores[b, 1:])[::-1] + 1                                          # negatives, best first
+        if k == 4:                                           # the destination among its own negatives (utils.py:96): an exact tie
+            j = 1 + rs.randint(N); cand[b, j] = cand[b, 0]; scores[b, j] = scores[b, 0]
+        elif k == 5:                                         # several negatives tie with the positive
+            scores[b, 1 + rs.choice(N, 3, replace=False)] = scores[b, 0]
+        elif k == 6:                                         # ties among negatives that straddle the top-1 / 3 / 5 boundary
+            kk = (1, 3, 5)[(b // 10) % 3]
+            scores[b, 0] = scores[b].min() - 1.0
+            scores[b, order[kk]] = scores[b, order[kk - 1]]
+            if (b // 10) % 2:                                # ... a group of three across it
+                scores[b, order[kk + 1]] = scores[b, order[kk - 1]]
+        elif k == 7:                                         # everything equal
+            scores[b, :] = 0.25
+        elif k == 8:                                         # one stock drawn twice (with replacement) inside the top 5
+            i0, i1 = order[(b // 10) % 3], order[3]
+            cand[b, i1] = cand[b, i0]; scores[b, i1] = scores[b, i0]
+        elif k == 9:                                         # the positive on top / at the bottom
+            scores[b, 0] = scores[b].max() + 1.0 if (b // 10) % 2 else scores[b].min() - 1.0
+    assert np.all(np.abs(scores) < 8) and np.array_equal(scores * 64, np.round(scores * 64))
+    canon = np.stack([F.canonical_order(scores[b]) for b in range(B)])
+    refrank = np.stack([np.argsort(scores[b])[::-1] for b in range(B)])                      # evaluation.py:122
+    tie_free = np.array([[F.tie_free(scores[b], k) for k in (1, 3, 5)] for b in range(B)])
+    portfolios = []
+    for b in range(B):
+        k = b % 9
+        top1 = codes[cand[b, canon[b, 0]] - U - 1]
+        if k == 0:
+            pf = [""]
+        elif k == 1:
+            pf = [top1]                                      # the recommended stock is the whole portfolio: delta = 0 exactly
+        elif k == 2:
+            pf = ["", codes[rs.randint(I)], codes[rs.randint(I)]]   # '' mixed in: the whole list counts as empty (:153)
+        elif k == 3:
+            pf = [codes[j] for j in rs.choice(I, W, replace=False)]  # the packed width
+        else:
+            pf = [codes[j] for j in rs.choice(I, rs.randint(1, W), replace=False)]
+        portfolios.append(pf)
+    width = max(len(p) for p in portfolios)
+    port_codes = np.full((B, width), "", dtype="U6")
+    port_n = np.array([len(p) for p in portfolios])
+    for b, p in enumerate(portfolios):
+        port_codes[b, :len(p)] = p
+    invest = np.zeros((B, 12)); invest_refrank = np.zeros((B, 12))
+    hi = np.zeros((B, 12)); lo = np.zeros((B, 12)); scale = np.zeros((B, 12))
+    inv_code = {v: k for k, v in map_item_id.items()}
+    for b in range(B):
+        key = str(ts[b])[:8]
+        items = np.array([inv_code[i] for i in cand[b] - (U + 1)])                           # evaluation.py:131-134
+        invest[b] = _ref_invest(ev, block, key, portfolios[b], items[canon[b]], tf_past, tf_future)
+        invest_refrank[b] = _ref_invest(ev, block, key, portfolios[b], items[refrank[b]], tf_past, tf_future)
+        hi[b], lo[b], scale[b] = _exact_invest(F, ret_past[day_idx[b]], ret_future[day_idx[b]], portfolios[b], map_item_id,
+                                               (cand[b] - U - 1)[canon[b]][:5])
+    free_all = tie_free.all(1)
+    assert free_all.sum() * 2 >= B, free_all.sum()
+    assert np.array_equal(invest[free_all], invest_refrank[free_all])        # the reference's own ranking: identical metrics there
+    e_ref = _check_signs(F, invest, hi, lo, scale)
+    assert np.all(invest[np.arange(B) % 9 == 1][:, [0, 3, 6, 9]] == 0)       # portfolio == [top-1]: delta@1 is exactly 0
+    n_greater = (scores[:, 1:] > scores[:, :1]).sum(1); n_equal = (scores[:, 1:] == scores[:, :1]).sum(1)
+    print("g9a: %d / %d rows tie-free for all k; max e_ref %.3g" % (free_all.sum(), B, e_ref.max()))
+    save("g9a_invest_metrics", scores=scores, cand=cand, kind=kind, ts=ts, day_idx=day_idx, days=np.array(days), codes=np.array(codes),
+         upper_u=np.array(U), prices_past=past, prices_future=future, port_codes=port_codes, port_n=port_n,
+         canonical=canon, ref_ranking=refrank, tie_free=tie_free, n_greater=n_greater, n_equal=n_equal,
+         invest=invest, invest_ref_ranking=invest_refrank, invest_exact_hi=hi, invest_exact_lo=lo, invest_scale=scale)
+
+
+def _g9b_try(seed, L):
+    import contextlib, io, pickle, tempfile
+    import evaluation as ev
+    from pfotgnrec_amd.mv_sampler import log_returns
+    F = _finance_ref()
+    R = ref_modules()
+    torch.manual_seed(seed); np.random.seed(seed)
+    rs = np.random.RandomState(seed)
+    U, I, E, D, Ef, K, H, B = 30, 12, 400, 8, 4, 5, 2, 12
+    M = 3 * D + Ef
+    n = U + I + 1
+    src = rs.randint(1, U + 1, E); dst = rs.randint(U + 1, U + I + 1, E)
+    day_vals = np.sort(rs.choice(np.arange(10_000_000, 16_000_000), 40, replace=False))      # 8 digits: str(ts)[:8] is the value
+    ts = np.sort(day_vals[rs.randint(0, 40, E)]).astype(np.float64)
+    eidx = np.arange(1, E + 1)
+    node_feat = rs.randn(n, D); edge_feat = rs.randn(E + 1, Ef); edge_feat[0] = 0
+    codes = ["%06d" % (i + 1) for i in range(I)]
+    map_item_id = {c: i for i, c in enumerate(codes)}
+    portfolios = np.empty(E, dtype=object)
+    for e in range(E):
+        k = rs.randint(0, 6)
+        pf = [codes[j] for j in rs.choice(I, k, replace=False)] if k else [""]
+        if k and rs.rand() < 0.1:
+            pf = pf + [""]                                                                    # '' mixed into a non-empty list
+        portfolios[e] = pf
+    days = [str(float(v))[:8] for v in day_vals]
+    past = 100.0 * np.exp(np.cumsum(rs.randn(40, I, 30) * 0.02, axis=2))
+    future = 100.0 * np.exp(np.cumsum(rs.randn(40, I, 30) * 0.02 + 0.001, axis=2))
+    tf_past = {d: {c: past[k, j] for j, c in enumerate(codes)} for k, d in enumerate(days)}
+    tf_future = {d: {c: future[k, j] for j, c in enumerate(codes)} for k, d in enumerate(days)}
+    full = R.Data(src, dst, ts, eidx, np.zeros(E, np.int64), portfolios)
+    nf = R.get_neighbor_finder(full, uniform=False)
+    tgn = R.TGN(neighbor_finder=nf, node_features=node_feat, edge_features=edge_feat.copy(), device=torch.device("cpu"),
+                n_layers=L, n_heads=H, dropout=0.1, use_memory=True, message_dimension=100, memory_dimension=D,
+                memory_update_at_start=True, embedding_module_type="graph_attention", message_function="identity",
+                aggregator_type="last", memory_updater_type="gru", n_neighbors=K)
+    with torch.no_grad():
+        tgn.time_encoder.w.bias.copy_(torch.randn(D) * 0.3)
+        tgn.eval()
+        for w in (200, 212, 224, 236):                                                                 # memory and pending messages to start from
+            sl = slice(w, w + B)
+            tgn.compute_temporal_embeddings(src[sl], dst[sl], dst[sl].repeat(2), ts[sl], eidx[sl], K)
+    n_run = 5
+    first, n_eval = 248, n_run * B + 7                                                       # 6 batches: 5 run, the short last one is skipped
+    sl = slice(first, first + n_eval)
+    data = R.Data(src[sl], dst[sl], ts[sl], eidx[sl], np.zeros(n_eval, np.int64), portfolios[sl])
+    sd = {k: v.detach().numpy().copy() for k, v in tgn.state_dict().items()
+          if not (k.startswith("memory_updater.memory.") or k.startswith("embedding_module.memory.")
+                  or k.startswith("embedding_module.time_encoder."))}
+    tab, mt, cnt = dense_messages(tgn, n, M)
+    out = dict(L=np.array(L), H=np.array(H), K=np.array(K), batch=np.array(B), upper_u=np.array(U), seed=np.array(seed),
+               src_all=src, dst_all=dst, ts_all=ts, eidx_all=eidx, node_features=node_feat, edge_features=edge_feat,
+               eval_first=np.array(first), eval_n=np.array(n_eval), codes=np.array(codes), days=np.array(days),
+               prices_past=past, prices_future=future, msg_tab=tab, msg_t=mt, msg_cnt=cnt,
+               memory0=tgn.memory.memory.detach().numpy().copy(), last_update0=tgn.memory.last_update.detach().numpy().copy())
+    width = max(len(p) for p in portfolios)
+    pc = np.full((E, width), "", dtype="U6")
+    for e, p in enumerate(portfolios):
+        pc[e, :len(p)] = p
+    out.update(port_codes=pc, port_n=np.array([len(p) for p in portfolios]))
+    for k, v in sd.items():
+        out["sd_" + k] = v
+    neg_log, emb_log = [], []
+
+    class RecSampler(R.RandEdgeSampler):                     # records the draw, changes nothing
+        def sample(self, size):
+            r = super().sample(size); neg_log.append(r.copy()); return r
+    orig_cte = tgn.compute_temporal_embeddings
+
+    def rec_cte(*a, **k):
+        r = orig_cte(*a, **k); emb_log.append([t.detach().numpy().copy() for t in r]); return r
+    tgn.compute_temporal_embeddings = rec_cte
+    cwd, keep = os.getcwd(), ev.RandEdgeSampler
+    with tempfile.TemporaryDirectory() as tmp:
+        os.makedirs(os.path.join(tmp, "data", "period_30"))
+        for name, obj in (("time_feature_past_30.pkl", tf_past), ("time_feature_future_30.pkl", tf_future), ("map_item_id.pkl", map_item_id)):
+            with open(os.path.join(tmp, "data", "period_30", name), "wb") as f:
+                pickle.dump(obj, f)
+        os.chdir(tmp)
+        ev.RandEdgeSampler = RecSampler
+        try:
+            with contextlib.redirect_stderr(io.StringIO()):
+                result = ev.eval_recommendation(tgn, data, full, B, K, U, 30, False, "val")
+        finally:
+            os.chdir(cwd); ev.RandEdgeSampler = keep
+            del tgn.compute_temporal_embeddings
+    assert len(neg_log) == n_run and len(emb_log) == n_run
+    # per-interaction lists recomputed from the recorded scores with the reference's functions, under the canonical ranking
+    block = _baseline_block()
+    inv_code = {v: k for k, v in map_item_id.items()}
+    ret_past, ret_future = log_returns(past), log_returns(future)
+    day_of = {d: i for i, d in enumerate(days)}
+    n_rows = n_run * B
+    scores = np.zeros((n_rows, 1 + I), np.float32); canon = np.zeros((n_rows, 1 + I), np.int64); rank = np.zeros(n_rows, np.int64)
+    recall_ref = np.zeros((n_rows, 3)); ndcg_ref = np.zeros((n_rows, 3)); self_tie = np.zeros(n_rows, bool)
+    recall = np.zeros((n_rows, 3)); ndcg = np.zeros((n_rows, 3)); invest = np.zeros((n_rows, 12))
+    hi = np.zeros((n_rows, 12)); lo = np.zeros((n_rows, 12)); scale = np.zeros((n_rows, 12))
+    top5_item = np.zeros((n_rows, 5), np.int64)
+    worst_gap = np.inf
+    for bi in range(n_run):
+        se, de, ne = (torch.from_numpy(x) for x in emb_log[bi])
+        pos = torch.sum(se.view(B, 1, -1) * de.view(B, 1, -1), dim=2).numpy()               # evaluation.py:114-115
+        negs = torch.sum(se.view(B, 1, -1) * ne.view(B, I, -1), dim=2).numpy()
+        for i in range(B):
+            r = bi * B + i
+            e = first + r
+            s = scores[r] = np.concatenate((pos[i], negs[i]))
+            ids = np.concatenate(([dst[e]], neg_log[bi][i]))
+            order = canon[r] = F.canonical_order(s)
+            refo = np.argsort(s)[::-1]
+            rank[r] = int(np.where(order == 0)[0][0])
+            # the gap condition: adjacent scores among the six best and around the positive differ by > 1e-3 of max |score|,
+            # except exact ties between two draws of ONE stock (either order selects the same stock)
+            sorted_s, sorted_id = s[order], ids[order]
+            for j in sorted(set(range(0, 6)) | {rank[r] - 1, rank[r]}):
+                if j < 0 or j + 1 > I:
+                    continue
+                gap = float(sorted_s[j]) - float(sorted_s[j + 1])
+                if gap == 0 and sorted_id[j] == sorted_id[j + 1]:
+                    continue
+                worst_gap = min(worst_gap, gap / float(np.abs(s).max()))
+            assert np.array_equal(ids[order][:5], ids[refo][:5])                              # the reference's own order: same stocks
+            recall[r] = [ev.recall_at_k(order, [0], k) for k in (1, 3, 5)]
+            ndcg[r] = [ev.ndcg_at_k(order, [0], k) for k in (1, 3, 5)]
+            # the reference's own np.argsort is not stable (evaluation.py:122): where the destination is among its own negatives
+            # (utils.py:96; every empty-portfolio row) it places the positive anywhere among those exact ties, the canonical order
+            # last.  Nowhere else may the two differ.
+            recall_ref[r] = [ev.recall_at_k(refo, [0], k) for k in (1, 3, 5)]
+            ndcg_ref[r] = [ev.ndcg_at_k(refo, [0], k) for k in (1, 3, 5)]
+            self_tie[r] = bool(np.any((ids[1:] == ids[0]) & (s[1:] == s[0])))
+            rank_ref = int(np.where(refo == 0)[0][0])
+            assert rank_ref == rank[r] or (self_tie[r] and rank[r] - int(((ids[1:] == ids[0]) & (s[1:] == s[0])).sum()) <= rank_ref < rank[r])
+            items = np.array([inv_code[x] for x in ids - (U + 1)])
+            invest[r] = _ref_invest(ev, block, str(ts[e])[:8], portfolios[e], items[order], tf_past, tf_future)
+            d = day_of[str(ts[e])[:8]]
+            top5_item[r] = ids[order][:5]
+            hi[r], lo[r], scale[r] = _exact_invest(F, ret_past[d], ret_future[d], portfolios[e], map_item_id, (ids - U - 1)[order][:5])
+    if not worst_gap > 1e-3:
+        return None, worst_gap
+    # the reference's dict is what these lists average to: its own ranking picked the same stocks, and the same rank of the
+    # positive except among exact ties with its own duplicate (recall / NDCG under its ranking: *_ref; under the canonical: the
+    # six 'canonical' values the native path has to give)
+    mine, canonical = {}, {}
+    for name, a, c in (("recall", recall_ref, recall), ("ndcg", ndcg_ref, ndcg)):
+        for j, k in enumerate((1, 3, 5)):
+            mine["val_%s_avg_%d" % (name, k)] = np.mean([a[i][j] for i in range(n_rows)])
+            canonical["val_%s_avg_%d" % (name, k)] = np.mean([c[i][j] for i in range(n_rows)])
+    for t, suf in ((0, ""), (1, "_")):
+        for m, name in ((0, "return"), (1, "sharpe")):
+            for j, k in enumerate((1, 3, 5)):
+                col = [invest[i][t * 6 + m * 3 + j] for i in range(n_rows)]
+                mine["val_%s_avg_%d%s" % (name, k, suf)] = np.mean(col)
+                mine["val_%s_percent_%d%s" % (name, k, suf)] = len([x for x in col if x > 0]) / n_rows
+    assert set(mine) == set(result) and len(result) == 30
+    for k in result:
+        assert mine[k] == result[k], (k, mine[k], result[k])
+    e_ref = _check_signs(F, invest, hi, lo, scale)
+    tab, mt, cnt = dense_messages(tgn, n, M)
+    out.update(negatives=np.stack(neg_log), scores=scores, canonical=canon, rank=rank, recall=recall, ndcg=ndcg, invest=invest,
+               top5_item=top5_item, invest_exact_hi=hi, invest_exact_lo=lo, invest_scale=scale,
+               result_keys=np.array(list(result)), result_values=np.array([result[k] for k in result], np.float64),
+               canonical_values=np.array([canonical.get(k, result[k]) for k in result], np.float64), self_tie=self_tie,
+               recall_ref_ranking=recall_ref, ndcg_ref_ranking=ndcg_ref,
+               after_memory=tgn.memory.memory.detach().numpy().copy(), after_last_update=tgn.memory.last_update.detach().numpy().copy(),
+               after_msg_tab=tab, after_msg_t=mt, after_msg_cnt=cnt, worst_gap=np.array(worst_gap))
+    print("g9b L%d seed %d: worst relative gap %.3g, max e_ref %.3g" % (L, seed, worst_gap, e_ref.max()))
+    return out, worst_gap
+
+
+def g9b():
+    """eval_recommendation end to end: the reference's own loop (evaluation.py:39-264) on a tiny bipartite graph with the
+    reference TGN on the CPU (memory, GRU, L in {1, 2}), synthetic data/period_30/*.pkl in a temporary directory; its
+    RandEdgeSampler and compute_temporal_embeddings are wrapped only to RECORD.  The seed is the first for which every
+    interaction meets the score-gap condition (see _g9b_try): a native embedding within the project's 1e-4 bar cannot reorder
+    the candidates that matter."""
+    for L in (1, 2):
+        for seed in range(100, 400):
+            out, gap = _g9b_try(seed, L)
+            if out is not None:
+                save("g9b_eval_loop_L%d" % L, **out)
+                break
+            print("g9b L%d seed %d: worst relative gap %.3g - next seed" % (L, seed, gap))
+        else:
+            raise SystemExit("g9b: no seed met the gap condition")
+
 
 if __name__ == "__main__":
     import warnings
     warnings.filterwarnings("ignore")
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9a", "g9b"]
     for w in which:
         globals()[w]()
