@@ -83,7 +83,8 @@ class OracleNeighborFinder:
     def gather_uniform(self, source_nodes, timestamps, sampled_idx, n_neighbors):
         """Uniform mode with INJECTED draws and the canonical (stable) time re-sort.
 
-        ``sampled_idx`` is i64[N, K]; rows of queries without history are ignored.
+        ``sampled_idx`` is i64[N, K]; rows of queries without history are ignored, a draw outside its row's history
+        raises ValueError naming the row.
         """
         N = len(source_nodes)
         neighbors = np.zeros((N, n_neighbors), np.int32)
@@ -92,7 +93,10 @@ class OracleNeighborFinder:
         for i, (node, t) in enumerate(zip(source_nodes, timestamps)):
             s_nbr, s_eidx, s_ts = self.find_before(int(node), t)
             if len(s_nbr) > 0:
-                sel = sampled_idx[i]
+                sel = np.asarray(sampled_idx[i])
+                if ((sel < 0) | (sel >= len(s_nbr))).any():      # a mis-addressed fixture: say so, do not index out of bounds
+                    raise ValueError("gather_uniform: row %d (node %d, t = %r) has %d entries before t, injected draws %s"
+                                     % (i, int(node), float(t), len(s_nbr), sel.tolist()))
                 et = s_ts[sel].astype(np.float32)
                 pos = np.argsort(et, kind="stable")
                 neighbors[i] = s_nbr[sel][pos]

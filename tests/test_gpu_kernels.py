@@ -101,6 +101,76 @@ def test_sampler_large_rows_and_frontier_expansion():
     assert np.array_equal(nts.cpu().numpy(), np.concatenate([qt, np.repeat(qt, K)]))
 
 
+# ------------------------------------------------------------------ K1 on yyyymmddHHMMSS timestamps (fixture g10)
+def _raw_sample(nf, q, qt, K, mode=0, draws=None):
+    """pfo_tnbr_sample through the C ABI with every output: (nbr, eidx, et, dt, next_nodes, next_ts)."""
+    indptr, anbr, aeidx, ats = nf.device_arrays(DEV)
+    N = len(q)
+    qn, qts = t(np.asarray(q).astype(np.int32)), t(np.asarray(qt, np.float64))
+    dd = None if draws is None else t(np.asarray(draws, np.int64))
+    nb = torch.empty((N, K), dtype=torch.int32, device=DEV)
+    ei = torch.empty((N, K), dtype=torch.int32, device=DEV)
+    et = torch.empty((N, K), dtype=torch.float32, device=DEV)
+    dt = torch.empty((N, K), dtype=torch.float32, device=DEV)
+    nxt = torch.empty(N * (K + 1), dtype=torch.int32, device=DEV)
+    nts = torch.empty(N * (K + 1), dtype=torch.float64, device=DEV)
+    _lib.call("pfo_tnbr_sample", indptr.data_ptr(), anbr.data_ptr(), aeidx.data_ptr(), ats.data_ptr(), nf.n_nodes,
+              qn.data_ptr(), qts.data_ptr(), N, K, mode, _lib.ptr(dd), 0, 0, nb.data_ptr(), ei.data_ptr(), et.data_ptr(),
+              dt.data_ptr(), nxt.data_ptr(), nts.data_ptr(), _lib.stream_ptr())
+    torch.cuda.synchronize()
+    return tuple(a.cpu().numpy() for a in (nb, ei, et, dt, nxt, nts))
+
+
+def _g10_finders(g, uniform=False):
+    top = int(g["q_nodes"].max())
+    nf = P.NeighborFinder.from_arrays(g["src"], g["dst"], g["eidx"], g["ts"], uniform=uniform, max_node_idx=top)
+    onf = OracleNeighborFinder(*build_adjacency(g["src"], g["dst"], g["eidx"], g["ts"], top), uniform=uniform)
+    return nf, onf
+
+
+@pytest.mark.parametrize("K", [10, 3])
+def test_sampler_real_timestamps_recent(K):
+    """Near 2.02e13 one f32 step is 2**21 (two calendar days): the search runs on the f64 times (an f32 query moves a tenth of
+    these rows, tests/test_oracle_golden.py), the edge times come out f32 (utils.py:179-180), and dt = f64 query - f32 edge
+    time, then f32 (embedding_module.py:133-135) - NEGATIVE where the edge time rounds up past the query."""
+    g = load_golden("g10_realts_sampler")
+    nf, _ = _g10_finders(g)
+    q, qt = g["q_nodes"], g["q_ts"]
+    nb, ei, et = nf.get_temporal_neighbor(q, qt, K)
+    assert nb.dtype == np.int32 and et.dtype == np.float32
+    assert np.array_equal(nb, g["K%d_nbr" % K]) and np.array_equal(ei, g["K%d_eidx" % K]) and np.array_equal(et, g["K%d_et" % K])
+    nb, ei, et, dt, nxt, nts = _raw_sample(nf, q, qt, K)
+    assert np.array_equal(nb, g["K%d_nbr" % K]) and np.array_equal(ei, g["K%d_eidx" % K]) and np.array_equal(et, g["K%d_et" % K])
+    assert np.array_equal(dt, g["K%d_dt" % K])
+    if K == 10:
+        assert int((dt < 0).sum()) == int(g["n_negative_dt"]) > 0
+    assert np.array_equal(nxt, np.concatenate([q.astype(np.int32), g["K%d_nbr" % K].flatten()]))
+    assert nts.dtype == np.float64 and np.array_equal(nts, np.concatenate([qt, np.repeat(qt, K)]))    # f64-exact frontier times
+    assert (nts.astype(np.float32).astype(np.float64) != nts).any()                                    # (an f32 detour would show)
+
+
+def test_sampler_real_timestamps_uniform_injected_draws():
+    """Ties between DIFFERENT edges on most rows (uni_n_tie_rows): the reference's slot order inside a tie group is its
+    platform's, the kernel's is the stable one (App. A-9) - equal to the oracle's exactly, to the reference's up to permutation
+    inside tie groups, times and deltas bit for bit."""
+    g = load_golden("g10_realts_sampler")
+    assert int(g["uni_n_tie_rows"]) > 0
+    nf, onf = _g10_finders(g, uniform=True)
+    q, qt, K = g["q_nodes"], g["q_ts"], 5
+    rn, re, rt = onf.gather_uniform(q, qt, g["uni_draws"], K)
+    for nb, ei, et, dt, nxt, nts in (nf.get_temporal_neighbor(q, qt, K, draws=g["uni_draws"]) + (None, None, None),
+                                     _raw_sample(nf, q, qt, K, mode=1, draws=g["uni_draws"])):
+        assert np.array_equal(nb, rn) and np.array_equal(ei, re) and np.array_equal(et, rt)          # canonical stable order
+        assert np.array_equal(et, g["uni_et"])
+        for i in range(len(nb)):
+            for tt in np.unique(et[i]):
+                m = et[i] == tt
+                assert sorted(zip(nb[i][m], ei[i][m])) == sorted(zip(g["uni_nbr"][i][m], g["uni_eidx"][i][m]))
+    assert np.array_equal(dt, g["uni_dt"]) and (dt < 0).any()
+    assert np.array_equal(nxt, np.concatenate([q.astype(np.int32), rn.flatten()]))
+    assert np.array_equal(nts, np.concatenate([qt, np.repeat(qt, K)]))
+
+
 # ------------------------------------------------------------------ candidate draw
 @pytest.mark.parametrize("size", [3, 20, 30])
 def test_candidate_draw_semantics(size):

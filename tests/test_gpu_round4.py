@@ -182,6 +182,7 @@ def test_step_against_reference_golden_at_dropout_01():
     (pfo_tgn_batch.dropout_keep, the dropout counterpart of the uniform sampler's injected draws) and must land on the
     reference's embeddings (1e-4), loss, every parameter gradient (5e-4; time encoder 3e-3) and memory state."""
     from conftest import load_golden
+    from parity import row_relerr, ROW_RTOL
     from test_gpu_tgn_step import inject
     g = load_golden("g8_dropout")
     L, H, K = int(g["step_L"]), int(g["step_H"]), int(g["step_K"])
@@ -198,6 +199,8 @@ def test_step_against_reference_golden_at_dropout_01():
     for got, key in ((se, "emb_src"), (de, "emb_dst"), (ne, "emb_neg")):
         e = relerr(got.detach().cpu().numpy(), g["s_" + key])
         assert e < RTOL_EMB, (key, e)
+        er = row_relerr(got.detach().cpu().numpy(), g["s_" + key])
+        assert er < ROW_RTOL, (key, er)
     emb = torch.cat([se, de, ne])
     loss = P.bpr_loss(emb, B, 3)
     assert abs(float(loss) - float(g["s_loss"])) < 1e-5 * max(1.0, abs(float(g["s_loss"])))
@@ -220,10 +223,12 @@ def test_step_against_reference_golden_at_dropout_01():
         n_checked += 1
     assert n_checked >= 20
     assert relerr(tgn.memory.memory.cpu().numpy(), g["s_after_memory"]) < RTOL_EMB
+    assert row_relerr(tgn.memory.memory.cpu().numpy(), g["s_after_memory"]) < ROW_RTOL
     assert np.array_equal(tgn.memory.last_update.cpu().numpy(), g["s_after_last_update"])
     has = g["s_after_msg_cnt"] > 0
     assert np.array_equal(tgn.memory.has_msg.cpu().numpy() > 0, has)
     assert relerr(tgn.memory.msg_table.cpu().numpy()[has], g["s_after_msg_tab"][has]) < RTOL_EMB
+    assert row_relerr(tgn.memory.msg_table.cpu().numpy()[has], g["s_after_msg_tab"][has]) < ROW_RTOL
     # the injected decisions are what ran: without them (the step's own Philox masks) the embeddings are far off
     inject(tgn, g, "s_")
     with torch.no_grad():

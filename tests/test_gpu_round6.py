@@ -329,3 +329,89 @@ def test_ours_branch_with_native_bpr_blocks_and_backward_overlap():
     # four Adam steps of lr 1e-3 from rounding-level different gradients: a parameter whose gradient is noise moves +-lr per
     # step either way (SURVEY 7 hard part 5) - the bound is the optimizer's reach, not a parity bar
     assert np.abs(p1 - p0).max() <= 4 * 2 * 1e-3 * 1.01 and np.isfinite(p1).all()
+
+
+# ------------------------------------------------------------------ eval dedup on yyyymmddHHMMSS timestamps
+def _real_timestamps(n, rs, n_days=60, n_dup=0):
+    """Sorted f64 ``yyyymmddHHMMSS`` timestamps (the recipe of the g10 fixtures, restated): 2023-12-01 onwards, 09:00:00 to
+    15:30:00, ``n_dup`` exact duplicates.  Near 2.02e13 one f32 step is 2**21 - about two calendar days."""
+    import datetime
+    d0 = datetime.date(2023, 12, 1)
+    days = np.array([int((d0 + datetime.timedelta(int(k))).strftime("%Y%m%d")) for k in range(n_days)], np.int64)
+    sec = rs.randint(9 * 3600, 15 * 3600 + 30 * 60 + 1, n)
+    hms = (sec // 3600) * 10000 + (sec // 60 % 60) * 100 + sec % 60
+    ts = (days[rs.randint(0, n_days, n)] * 1_000_000 + hms).astype(np.float64)
+    dup = rs.choice(n, n_dup, replace=False)
+    ts[dup] = ts[rs.randint(0, n, n_dup)]
+    return np.sort(ts)
+
+
+def test_eval_dedup_keeps_roots_apart_that_differ_in_f64_and_collapse_in_f32():
+    """The forward-only dedup (R >= 4096) embeds each distinct (node, time) root once.  With real timestamps most roots of
+    one item fall into one f32 step while their f64 times - and the histories in front of them - differ: the grid must be
+    built from the f64 times.  One evaluation batch of 180 interactions x all 25 items against the oracle, every row."""
+    from oracle import tgn_oracle as T
+    from oracle.neighbor_finder import OracleNeighborFinder, build_adjacency
+    from parity import row_relerr, ROW_RTOL
+    torch.manual_seed(5)
+    rs = np.random.RandomState(21)
+    U, I, E, D, K, L, H, B = 300, 25, 5000, 32, 6, 2, 2, 180
+    src, dst = rs.randint(1, U + 1, E), rs.randint(U + 1, U + I + 1, E)
+    ts = _real_timestamps(E, rs, n_dup=E // 3)
+    eidx = np.arange(1, E + 1)
+    node_feat, edge_feat = rs.rand(U + I + 1, D), rs.randn(E + 1, 4)
+    edge_feat[0] = 0
+    nf = P.NeighborFinder.from_arrays(src, dst, eidx, ts, max_node_idx=U + I)
+    tgn = P.TGN(nf, node_feat, edge_feat, DEV, n_layers=L, n_heads=H, dropout=0.2, use_memory=True, memory_dimension=D,
+                message_function="identity", n_neighbors=K)
+    with torch.no_grad():
+        tgn.time_encoder.w.bias.normal_(0, 0.3)
+    onf = OracleNeighborFinder(*build_adjacency(src, dst, eidx, ts, max_node_idx=U + I))
+    names = [k for k in tgn.state_dict() if "layer_norm" not in k and not k.startswith("memory.")]
+    ref = T.OracleTGN(onf, node_feat, edge_feat, {k: tgn.state_dict()[k].cpu().numpy() for k in names}, L, H, True)
+    sl = slice(3000, 3000 + B)
+    items = np.arange(U + 1, U + I + 1)
+    neg = np.tile(items, B)                                                 # R = 180 * 27 = 4860 roots
+    taken = []
+    dedup = tgn._dedup_roots
+
+    def spy(*a, **k):
+        r = dedup(*a, **k)
+        taken.append((r[2] is not None, int(r[0].shape[0])))
+        return r
+    tgn._dedup_roots = spy
+    tgn.eval()
+    res = []
+    for flag in (True, False):
+        tgn.eval_dedup = flag
+        tgn.memory.__init_memory__()
+        with torch.no_grad():
+            for warm in (2800, 2900):
+                w = slice(warm, warm + 100)
+                tgn.compute_temporal_embeddings(src[w], dst[w], dst[w].repeat(3), ts[w], eidx[w], K)
+            res.append(torch.cat(tgn.compute_temporal_embeddings(src[sl], dst[sl], neg, ts[sl], eidx[sl], K)).cpu().numpy())
+    assert taken == [(True, taken[0][1])] and taken[0][1] < B * (2 + I)    # the dedup ran once, on the big batch, and saved roots
+    assert res[0].shape[0] == B * (2 + I) >= 4096 and np.array_equal(res[0], res[1])
+    for warm in (2800, 2900):
+        w = slice(warm, warm + 100)
+        ref.compute_temporal_embeddings(src[w], dst[w], dst[w].repeat(3), ts[w], eidx[w], K)
+    remb = np.concatenate(ref.compute_temporal_embeddings(src[sl], dst[sl], neg, ts[sl], eidx[sl], K))
+    # pairs of roots on ONE item whose times differ in f64 and are equal in f32 - and whose embeddings differ by far more than
+    # the bar (an edge of the item lies between the two times): a grid keyed on f32 times would hand both the same row
+    tb = ts[sl]
+    t32 = tb.astype(np.float32)
+    n_pairs = n_apart = 0
+    for a in range(B - 1):
+        b = a + 1
+        if tb[a] != tb[b] and t32[a] == t32[b]:
+            ra, rb = remb[2 * B + a * I:2 * B + (a + 1) * I], remb[2 * B + b * I:2 * B + (b + 1) * I]
+            n_pairs += I
+            n_apart += int((np.abs(ra - rb).max(1) > 100 * RTOL_EMB * np.abs(remb).max()).sum())
+    assert n_pairs >= 25 * 50 and n_apart >= 50, (n_pairs, n_apart)
+    e, er = relerr(res[0], remb), row_relerr(res[0], remb)
+    print("FIGURES eval dedup on real timestamps: relerr %.3g row_relerr %.3g, %d f32-collapsing pairs, %d apart" % (e, er, n_pairs, n_apart))
+    assert e < RTOL_EMB, e
+    assert er < ROW_RTOL, er
+    assert relerr(tgn.memory.memory.cpu().numpy(), ref.memory) < RTOL_EMB
+    assert row_relerr(tgn.memory.memory.cpu().numpy(), ref.memory) < ROW_RTOL
+    assert np.array_equal(tgn.memory.last_update.cpu().numpy(), ref.last_update)

@@ -12,6 +12,7 @@ import pfotgnrec_amd as P
 from pfotgnrec_amd.synthetic import SyntheticConfig, make_graph
 from oracle import tgn_oracle as T
 from oracle.neighbor_finder import OracleNeighborFinder, build_adjacency
+from parity import row_relerr, ROW_RTOL
 
 DEV = "cuda:0"
 RTOL_EMB = 1e-4      # BASELINE.json north_star: embeddings within 1e-4 relative
@@ -49,7 +50,27 @@ def inject(tgn, g, pre):
 
 @pytest.mark.parametrize("tag", ["L1_mem", "L2_mem", "L2_nomem_uniform", "L1_mem_p"])
 def test_step_against_reference_golden(tag):
-    g = load_golden("g5_step_" + tag)
+    _step_against_golden("g5_step_" + tag, "draws")
+
+
+@pytest.mark.parametrize("tag", ["L1_mem", "L2_mem", "L2_nomem_uniform", "L1_mem_p"])
+def test_step_against_reference_golden_real_timestamps(tag):
+    """g10: the same step of the reference on yyyymmddHHMMSS timestamps (~2.02e13: one f32 step is 2**21, about two days).
+    Message times and last_update are f32 in the reference (tgn.py:359,367, memory_updater.py:25) and compared bit for bit;
+    the deltas reach 1e10 and are NEGATIVE where an f32 edge time rounds up past the f64 query; in the uniform case ties
+    between different edges are the rule, and the draws are injected addressed to the canonical (stable) slot order.
+    Same constants as g5."""
+    _step_against_golden("g10_realts_step_" + tag, "cdraws")
+
+
+def _step_against_golden(fixture, draws_key):
+    g = load_golden(fixture)
+    tag = fixture
+    worst = {}
+
+    def note(key, e):
+        worst[key] = max(worst.get(key, 0.0), float(e))
+        return e
     L, H, K = int(g["L"]), int(g["H"]), int(g["K"])
     use_mem, uniform, path = bool(g["use_memory"]), bool(g["uniform"]), str(g["path"])
     nf = P.NeighborFinder.from_arrays(g["src_all"], g["dst_all"], g["eidx_all"], g["ts_all"], uniform=uniform)
@@ -64,7 +85,8 @@ def test_step_against_reference_golden(tag):
         B = len(sb)
         draws = None
         if uniform:   # reference call order: layer-1(roots) = draws0, layer-2(roots) = draws1, layer-1(neighbours) = draws2
-            draws = [g[pre + "draws1"], np.concatenate([g[pre + "draws0"], g[pre + "draws2"]])] if L == 2 else [g[pre + "draws0"]]
+            dr = [g[pre + draws_key + "%d" % j] for j in range(3 if L == 2 else 1)]
+            draws = [dr[1], np.concatenate([dr[0], dr[2]])] if L == 2 else [dr[0]]
         tgn.train()
         opt.zero_grad()
         if path == "p":
@@ -75,8 +97,10 @@ def test_step_against_reference_golden(tag):
             pe = de
             emb = torch.cat([se, de, ne]); pos_block = 1
         for got, key in ((se, "emb_src"), (de, "emb_dst"), (pe, "emb_pos"), (ne, "emb_neg")):
-            e = relerr(got.detach().cpu().numpy(), g[pre + key])
+            e = note("emb relerr", relerr(got.detach().cpu().numpy(), g[pre + key]))
+            er = note("emb row_relerr", row_relerr(got.detach().cpu().numpy(), g[pre + key]))
             assert e < RTOL_EMB, (tag, step, key, e)
+            assert er < ROW_RTOL, (tag, step, key, er)
         loss = P.bpr_loss(emb, B, 3, pos_block=pos_block)
         assert abs(float(loss) - float(g[pre + "loss"])) < 1e-5 * max(1.0, abs(float(g[pre + "loss"])))
         loss.backward()
@@ -92,14 +116,18 @@ def test_step_against_reference_golden(tag):
             if scale < 1e-7:           # e.g. the key bias: its gradient cancels exactly in the softmax
                 assert np.abs(got).max() < 1e-6, name
                 continue
-            e = relerr(got, ref)
+            e = note("time grad relerr" if name.startswith("time_encoder") else "grad relerr", relerr(got, ref))
             assert e < (RTOL_GRAD_TIME if name.startswith("time_encoder") else RTOL_GRAD), (tag, step, name, e)
         if use_mem:
-            assert relerr(tgn.memory.memory.cpu().numpy(), g[pre + "after_memory"]) < RTOL_EMB
+            mem = tgn.memory.memory.cpu().numpy()
+            assert note("memory relerr", relerr(mem, g[pre + "after_memory"])) < RTOL_EMB
+            assert note("memory row_relerr", row_relerr(mem, g[pre + "after_memory"])) < ROW_RTOL
             assert np.array_equal(tgn.memory.last_update.cpu().numpy(), g[pre + "after_last_update"])
             assert np.array_equal(tgn.memory.has_msg.cpu().numpy() > 0, g[pre + "after_msg_cnt"] > 0)
             has = g[pre + "after_msg_cnt"] > 0
-            assert relerr(tgn.memory.msg_table.cpu().numpy()[has], g[pre + "after_msg_tab"][has]) < RTOL_EMB
+            tab = tgn.memory.msg_table.cpu().numpy()[has]
+            assert note("msg relerr", relerr(tab, g[pre + "after_msg_tab"][has])) < RTOL_EMB
+            assert note("msg row_relerr", row_relerr(tab, g[pre + "after_msg_tab"][has])) < ROW_RTOL
             assert np.array_equal(tgn.memory.msg_time.cpu().numpy()[has], g[pre + "after_msg_t"][has])
         # optimizer step (Adam, main.py:123,389) with the reference optimizer's moments injected: post-step parameters
         # against the reference's `after_*`.  Adam divides by sqrt(v): where an element's gradient history is tiny the
@@ -139,6 +167,7 @@ def test_step_against_reference_golden(tag):
             v_mine = b2 * g[pre + "adam_v_" + name].astype(np.float64) + (1 - b2) * gn * gn
             want = g[pre + "sd_" + name].astype(np.float64) - lr / bc1 * m_new / (np.sqrt(v_mine / bc2) + eps)
             assert np.abs(got_after - want).max() <= 4e-7 * max(1.0, np.abs(want).max()) + 1e-3 * lr, (tag, step, name)
+    print("FIGURES %s: %s" % (fixture, ", ".join("%s %.3g" % kv for kv in sorted(worst.items()))))
 
 
 @pytest.mark.parametrize("D,H,L,K,use_mem,uniform", [(32, 2, 1, 10, True, False), (172, 2, 2, 8, True, False),

@@ -8,12 +8,10 @@ from conftest import load_golden
 from oracle import tgn_oracle as T
 from oracle.neighbor_finder import OracleNeighborFinder, build_adjacency
 
+from parity import relerr, row_relerr, ROW_RTOL
+
 RTOL = 1e-4     # north_star bar; observed restatement error is 1e-7..1e-6
-
-
-def relerr(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return np.abs(a - b).max() / (np.abs(b).max() + 1e-12)
+FIGURES = {}    # (fixture, quantity) -> worst error seen (printed by the g10 tests: run with -s to read them)
 
 
 def test_g4_time_encode_bit_exact_argument():
@@ -92,9 +90,40 @@ def _load_state(g, pre, tgn, use_mem):
             tgn.messages[int(nid)] = [(tab[nid], mt[nid])]
 
 
+def _note(fixture, key, value):
+    FIGURES[(fixture, key)] = max(FIGURES.get((fixture, key), 0.0), float(value))
+    return value
+
+
 @pytest.mark.parametrize("tag", ["L1_mem", "L2_mem", "L2_nomem_uniform", "L1_mem_p"])
 def test_g5_full_step(tag):
-    g = load_golden("g5_step_" + tag)
+    _full_step("g5_step_" + tag, "draws")
+
+
+@pytest.mark.parametrize("tag", ["L1_mem", "L2_mem", "L2_nomem_uniform", "L1_mem_p"])
+def test_g10_full_step_real_timestamps(tag):
+    """The g5 step on yyyymmddHHMMSS timestamps (f32 step 2**21): f32 message times and last_update bit-exact, deltas up to
+    ~1e10 through the time encoder, and - uniform, two layers - sampled rows where ties between different edges are the rule:
+    the draws of the call on the neighbours are injected re-addressed to the canonical (stable) slot order."""
+    _full_step("g10_realts_step_" + tag, "cdraws")
+    print({k[1]: "%.3g" % v for k, v in FIGURES.items() if k[0] == "g10_realts_step_" + tag})
+
+
+def test_g10_uniform_raw_draws_are_misaddressed():
+    """The reference logs the neighbour call's draws in ITS slot order (default argsort on f32 times, utils.py:201); injected
+    as they are, rows land on other nodes than they were drawn for: the oracle refuses them or the embeddings miss the bar."""
+    g = load_golden("g10_realts_step_L2_nomem_uniform")
+    assert sum(int(g["s%d_n_readdressed_roots" % s]) for s in g["recorded_steps"]) > 0
+    assert any(not np.array_equal(g["s%d_draws2" % s], g["s%d_cdraws2" % s]) for s in g["recorded_steps"])
+    for s in g["recorded_steps"]:                                  # the calls on the roots need no re-addressing
+        assert np.array_equal(g["s%d_draws0" % s], g["s%d_cdraws0" % s]) and np.array_equal(g["s%d_draws1" % s], g["s%d_cdraws1" % s])
+    with pytest.raises((ValueError, AssertionError)):
+        _full_step("g10_realts_step_L2_nomem_uniform", "draws")
+
+
+def _full_step(fixture, draws_key):
+    g = load_golden(fixture)
+    tag = fixture
     L, H, K = int(g["L"]), int(g["H"]), int(g["K"])
     use_mem, uniform, path = bool(g["use_memory"]), bool(g["uniform"]), str(g["path"])
     nf = OracleNeighborFinder(*build_adjacency(g["src_all"], g["dst_all"], g["eidx_all"], g["ts_all"]), uniform=uniform)
@@ -104,7 +133,7 @@ def test_g5_full_step(tag):
         _load_state(g, pre, tgn, use_mem)                           # re-inject reference state at every step
         draws = None
         if uniform:
-            draws = [g[pre + "draws%d" % j] for j in range(3 if L == 2 else 1)]
+            draws = [g[pre + draws_key + "%d" % j] for j in range(3 if L == 2 else 1)]
         sb, db, tb, eb, neg = g[pre + "src"], g[pre + "dst"], g[pre + "ts"], g[pre + "eidx"], g[pre + "neg"]
         B = len(sb)
         if path == "p":
@@ -113,7 +142,8 @@ def test_g5_full_step(tag):
             se, de, ne = tgn.compute_temporal_embeddings(sb, db, neg.flatten(), tb, eb, K, draws=draws)
             pe = de
         for got, key in ((se, "emb_src"), (de, "emb_dst"), (pe, "emb_pos"), (ne, "emb_neg")):
-            assert relerr(got, g[pre + key]) < RTOL, (tag, step, key, relerr(got, g[pre + key]))
+            assert _note(fixture, "emb relerr", relerr(got, g[pre + key])) < RTOL, (tag, step, key, relerr(got, g[pre + key]))
+            assert _note(fixture, "emb row_relerr", row_relerr(got, g[pre + key])) < ROW_RTOL, (tag, step, key, row_relerr(got, g[pre + key]))
         loss, cache = T.bpr_loss(se, pe.reshape(B, 1, -1), ne.reshape(B, 3, -1))
         assert abs(loss - g[pre + "loss"]) < 1e-5 * max(1.0, abs(g[pre + "loss"]))
         d_src, d_pos, d_neg = T.bpr_loss_backward(cache)
@@ -137,13 +167,16 @@ def test_g5_full_step(tag):
                     continue
                 e = relerr(got, ref)
                 worst = max(worst, e)
+                _note(fixture, "time grad relerr" if name.startswith("time_encoder") else "grad relerr", e)
                 assert e < 5e-4, (tag, step, name, e)
         if use_mem:
-            assert relerr(tgn.memory, g[pre + "after_memory"]) < RTOL
+            assert _note(fixture, "memory relerr", relerr(tgn.memory, g[pre + "after_memory"])) < RTOL
+            assert _note(fixture, "memory row_relerr", row_relerr(tgn.memory, g[pre + "after_memory"])) < ROW_RTOL
             assert np.array_equal(tgn.last_update, g[pre + "after_last_update"])
             tab, mt, has = tgn.pending_table()
             assert np.array_equal(has, g[pre + "after_msg_cnt"] > 0)
-            assert relerr(tab, g[pre + "after_msg_tab"]) < RTOL
+            assert _note(fixture, "msg relerr", relerr(tab, g[pre + "after_msg_tab"])) < RTOL
+            assert _note(fixture, "msg row_relerr", row_relerr(tab, g[pre + "after_msg_tab"])) < ROW_RTOL
             assert np.array_equal(mt, g[pre + "after_msg_t"])
             # per-node list lengths (all messages of a node come from one batch)
             cnt = np.array([len(tgn.messages.get(i, [])) for i in range(tgn.n_nodes)])
@@ -196,6 +229,7 @@ def test_g8_full_step_with_dropout():
     se, de, ne = tgn.compute_temporal_embeddings(sb, db, neg.flatten(), tb, eb, K)
     for got, key in ((se, "emb_src"), (de, "emb_dst"), (ne, "emb_neg")):
         assert relerr(got, g["s_" + key]) < RTOL, (key, relerr(got, g["s_" + key]))
+        assert _note("g8_dropout", "emb row_relerr", row_relerr(got, g["s_" + key])) < ROW_RTOL, (key, row_relerr(got, g["s_" + key]))
     loss, cache = T.bpr_loss(se, de.reshape(B, 1, -1), ne.reshape(B, 3, -1))
     assert abs(loss - g["s_loss"]) < 1e-5 * max(1.0, abs(g["s_loss"]))
     d_src, d_pos, d_neg = T.bpr_loss_backward(cache)
@@ -213,9 +247,11 @@ def test_g8_full_step_with_dropout():
             n_checked += 1
     assert n_checked >= 20
     assert relerr(tgn.memory, g["s_after_memory"]) < RTOL
+    assert _note("g8_dropout", "memory row_relerr", row_relerr(tgn.memory, g["s_after_memory"])) < ROW_RTOL
     assert np.array_equal(tgn.last_update, g["s_after_last_update"])
     tab, mt, has = tgn.pending_table()
     assert np.array_equal(has, g["s_after_msg_cnt"] > 0) and relerr(tab, g["s_after_msg_tab"]) < RTOL
+    assert _note("g8_dropout", "msg row_relerr", row_relerr(tab, g["s_after_msg_tab"])) < ROW_RTOL
     # without the masks the embeddings are off by far more than the bar: the fixture does pin the dropout algebra
     _load_state(g, "s_", tgn, True)
     tgn.dropout_masks = None

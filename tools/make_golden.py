@@ -7,7 +7,8 @@ reference's outputs.  The fixtures are data only - no reference source text is
 stored.  The inline MV block of main.py (not importable: wandb/CUDA/data files)
 is executed in place from the reference tree, as SURVEY.md App. E describes.
 
-Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8 g9a g9b]      (default: all)
+Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8 g9a g9b g10]  (default: all)
+g10 = the g1 / g5 recipes on ``yyyymmddHHMMSS`` timestamps (~2.02e13: one f32 step is 2**21, about two calendar days).
 Library versions used are recorded in each fixture (``versions``).
 """
 import os
@@ -276,17 +277,26 @@ def dense_messages(tgn, n_nodes, M):
 
 
 def g5():
+    step_fixtures("g5_step_", 16)
+
+
+def step_fixtures(prefix, dim, timestamps=None):
     # Note: every recorded step stores its own inputs (state_dict, memory, pending messages, batch, draws) next to its
     # outputs, so a fixture is self-contained.  The 5-step trajectory itself is not bit-reproducible across runs of this
     # script for the 2-layer memory case (multi-threaded CPU reductions in the reference's torch ops); regenerating
     # replaces that fixture with an equally valid one.
+    # ``timestamps`` (g10): f64[E] sorted, replace the synthetic graph's; the uniform case then also records every sampler
+    # call's output in the reference's own slot order and the draws re-addressed to the canonical order (readdress_draws).
     R = ref_modules()
     for tag, L, use_mem, uniform, H, path in (("L1_mem", 1, True, False, 2, "base"), ("L2_mem", 2, True, False, 2, "base"),
                                                ("L2_nomem_uniform", 2, False, True, 4, "base"), ("L1_mem_p", 1, True, False, 2, "p")):
         torch.manual_seed(1); np.random.seed(1)
-        cfg = SyntheticConfig("g5", 120, 20, 1500, 16, L, 5, H)
+        cfg = SyntheticConfig("g5", 120, 20, 1500, dim, L, 5, H)
         g = make_graph(cfg, with_prices=False)
         d = g.data
+        if timestamps is not None:
+            assert len(timestamps) == cfg.n_edges and np.all(np.diff(timestamps) >= 0)
+            d.timestamps = np.asarray(timestamps, np.float64).copy()
         D, Ef, K, B, n = cfg.dim, cfg.edge_dim, cfg.n_neighbors, 24, g.n_nodes
         M = 3 * D + Ef
         rdata = R.Data(d.sources, d.destinations, d.timestamps, d.edge_idxs, d.labels, d.portfolios)
@@ -330,6 +340,7 @@ def g5():
                     out[pre + "adam_t_" + k] = np.array(int(st_["step"]))      # per tensor: the GRU's lag one step (None grad in step 0)
             # uniform mode: log the draws in call order
             draws, orig = [], np.random.randint
+            calls = []                                   # uniform: (nodes, ts, nbr, eidx, et) of every sampler call, in call order
             if uniform:
                 cur = []
 
@@ -350,6 +361,7 @@ def g5():
                         if len(nf.find_before(a, b)[0]) > 0:
                             dense[i] = next(it)
                     draws.append(dense)
+                    calls.append((np.asarray(nodes).copy(), np.asarray(ts, np.float64).copy()) + tuple(np.array(a) for a in res))
                     return res
                 nf.get_temporal_neighbor = gtn
             tgn.train(); opt.zero_grad()
@@ -379,6 +391,8 @@ def g5():
                         out[pre + "grad_" + k] = (v.grad.numpy().copy() if v.grad is not None else np.zeros(v.shape, np.float32))
                 for j, dr in enumerate(draws):
                     out[pre + "draws%d" % j] = dr
+                if uniform and timestamps is not None:
+                    out.update({pre + k: v for k, v in readdress_draws(nf, calls, draws, K, L).items()})
             opt.step()
             if use_mem:
                 tgn.memory.detach_memory()
@@ -392,7 +406,11 @@ def g5():
                                 pre + "after_last_update": tgn.memory.last_update.detach().numpy().copy(),
                                 pre + "after_msg_tab": tab, pre + "after_msg_t": mt, pre + "after_msg_cnt": cnt})
         out["recorded_steps"] = np.array([2, 3, 4])
-        save("g5_step_" + tag, **out)
+        if uniform and timestamps is not None:
+            n_moved = sum(int(out["s%d_n_readdressed_roots" % s_]) for s_ in (2, 3, 4))
+            assert n_moved > 0, "no root whose reference slot order differs from the stable one: the fixture would not pin the tie policy"
+            print("%s%s: %d roots re-addressed over the recorded steps" % (prefix, tag, n_moved))
+        save(prefix + tag, **out)
 
 
 def g6():
@@ -898,9 +916,153 @@ def g9b():
             raise SystemExit("g9b: no seed met the gap condition")
 
 
+# ------------------------------------------------------------------ G10: yyyymmddHHMMSS timestamps (f32 step = 2**21 ~ two days)
+def real_timestamps(n, rs, first_day=(2023, 12, 1), n_days=60, n_dup=None, n_edge_of_day=8):
+    """Sorted f64[n] ``yyyymmddHHMMSS`` timestamps, the format of the reference's data (main.py:212 takes ``str(ts)[:8]``):
+    ``n_days`` calendar days from ``first_day`` (the default spans the 2023-12-31 -> 2024-01-01 boundary, a gap of ~8.87e9),
+    several edges per day at 09:00:00-15:30:00, ``n_edge_of_day`` of them moved to 00:00:00 / 23:59:59 and ``n_dup``
+    (default n // 12) exact f64 duplicates of other entries.  Near 2.02e13 one f32 step is 2**21: about two days."""
+    import datetime
+    d0 = datetime.date(*first_day)
+    days = np.array([int((d0 + datetime.timedelta(int(k))).strftime("%Y%m%d")) for k in range(n_days)], np.int64)
+    day = rs.randint(0, n_days, n)
+    sec = rs.randint(9 * 3600, 15 * 3600 + 30 * 60 + 1, n)
+    edge = rs.choice(n, n_edge_of_day, replace=False)
+    sec[edge[:n_edge_of_day // 2]] = 0
+    sec[edge[n_edge_of_day // 2:]] = 86399
+    hms = (sec // 3600) * 10000 + (sec // 60 % 60) * 100 + sec % 60
+    ts = (days[day] * 1_000_000 + hms).astype(np.float64)            # < 2**53: exact
+    dup = rs.choice(n, n // 12 if n_dup is None else n_dup, replace=False)
+    ts[dup] = ts[rs.randint(0, n, len(dup))]
+    return np.sort(ts)
+
+
+def _stable_rows(nf, nodes, ts, draws, K):
+    """The canonical output of one uniform sampler call (App. A-9): the drawn entries stable-sorted by their f32 time."""
+    N = len(nodes)
+    nbr = np.zeros((N, K), np.int32); eidx = np.zeros((N, K), np.int32); et = np.zeros((N, K), np.float32)
+    for i, (a, b) in enumerate(zip(nodes, ts)):
+        h_n, h_e, h_t = nf.find_before(a, b)
+        if len(h_n) > 0:
+            sel = draws[i]
+            t32 = h_t[sel].astype(np.float32)
+            pos = np.argsort(t32, kind="stable")
+            nbr[i], eidx[i], et[i] = h_n[sel][pos], h_e[sel][pos], t32[pos]
+    return nbr, eidx, et
+
+
+def readdress_draws(nf, calls, draws, K, L):
+    """The reference logs the draws of the call on the NEIGHBOURS in the slot order its own (non-stable) argsort gave the call
+    above; the canonical order is the stable one.  Per root of that call: a bijection reference slot -> canonical slot that
+    preserves the edge (duplicate draws of one edge are interchangeable: the layer above sums over the slots), and the rows of
+    the neighbour call's draws moved along it.  Returns the reference's rows per call (ref_nbr/eidx/et<j>), the canonical
+    draws (cdraws<j>) and how many roots were moved."""
+    assert len(calls) == len(draws) == (3 if L == 2 else 1)
+    out = {}
+    for j, (_, _, nb, ei, et) in enumerate(calls):
+        out["ref_nbr%d" % j], out["ref_eidx%d" % j], out["ref_et%d" % j] = nb, ei, et
+    cdraws = [dr.copy() for dr in draws]
+    moved = 0
+    if L == 2:
+        # call order (embedding_module.py:115,125,141): layer 1 on the roots, layer 2 on the roots, layer 1 on call 1's neighbours
+        nodes, ts, r_nb, r_ei, r_et = calls[1]
+        c_nb, c_ei, c_et = _stable_rows(nf, nodes, ts, draws[1], K)
+        assert np.array_equal(c_et, r_et)                         # the times are sorted either way
+        N = len(nodes)
+        assert np.array_equal(calls[2][0], r_nb.flatten()) and np.array_equal(calls[2][1], np.repeat(ts, K))
+        for i in range(N):
+            free = list(range(K))
+            perm = np.zeros(K, np.int64)
+            for s in range(K):
+                c = next(c for c in free if c_ei[i, c] == r_ei[i, s] and c_et[i, c] == r_et[i, s])
+                free.remove(c)
+                perm[s] = c
+                assert c_nb[i, c] == r_nb[i, s]
+            moved += int(not np.array_equal(perm, np.arange(K)))
+            cdraws[2][i * K + perm] = draws[2][i * K:(i + 1) * K]
+        # every re-addressed draw is a position in ITS node's history
+        for r, (a, b) in enumerate(zip(c_nb.flatten(), np.repeat(ts, K))):
+            cnt = len(nf.find_before(a, b)[0])
+            row = cdraws[2][r]
+            assert (cnt == 0 and np.all(row == -1)) or (cnt > 0 and np.all((row >= 0) & (row < cnt))), (r, a, b, cnt, row)
+    for j, dr in enumerate(cdraws):
+        out["cdraws%d" % j] = dr
+    out["n_readdressed_roots"] = np.array(moved)
+    return out
+
+
+def g10():
+    """(a) g10_realts_sampler: the g1 recipe on a small bipartite graph with real timestamps: most-recent K in {10, 3},
+    uniform K = 5 with the draws logged, ``dt`` by the reference's expression (embedding_module.py:133-135: f64 query time
+    minus f32 edge time, then .float()), the counts the sensitivity tests rely on, and the day key of every interaction.
+    (b) g10_realts_step_*: the g5 recipe (narrower features: the files stay below the size of g5's) on the same timestamps."""
+    R = ref_modules()
+    rs = np.random.RandomState(10)
+    U, I, E = 60, 12, 1200
+    src = rs.randint(1, U - 2, size=E)                            # users U-2..U never interact
+    dst = rs.randint(U + 1, U + I + 1, size=E)
+    ts = real_timestamps(E, rs)
+    eidx = np.arange(1, E + 1)
+    t32 = ts.astype(np.float32)
+    print("g10: %d distinct f64 timestamps, %d distinct f32" % (len(np.unique(ts)), len(np.unique(t32))))
+    assert len(np.unique(ts)) < E and len(np.unique(t32)) * 10 < len(np.unique(ts))
+    keys = np.array([str(t)[:8] for t in ts])                     # main.py:212, per interaction
+    assert len(set(k[:4] for k in keys)) == 2 and any(str(t)[8:14] == "000000" for t in ts) and any(str(t)[8:14] == "235959" for t in ts)
+    D = R.Data(src, dst, ts, eidx, np.zeros(E), None)
+    nf = R.get_neighbor_finder(D, uniform=False)
+    sl = slice(500, 756)
+    extra = real_timestamps(192, rs, n_dup=0)                     # cut times that are (mostly) no edge's time
+    q_nodes = np.concatenate([src[sl], dst[sl], rs.randint(0, U + I + 1, len(extra)), np.arange(0, U + I + 1)])
+    q_ts = np.concatenate([ts[sl], ts[sl], extra, np.full(U + I + 1, ts[E // 2] + 1.0)])
+    out = dict(src=src, dst=dst, ts=ts, eidx=eidx, q_nodes=q_nodes, q_ts=q_ts, day_keys=keys)
+
+    def deltas(et):                                               # embedding_module.py:133-135
+        return torch.from_numpy(q_ts[:, np.newaxis] - et).float().numpy()
+    for K in (10, 3):
+        nb, ei, et = nf.get_temporal_neighbor(q_nodes, q_ts, K)
+        out["K%d_nbr" % K], out["K%d_eidx" % K], out["K%d_et" % K], out["K%d_dt" % K] = nb, ei, et, deltas(et)
+    n_neg = int((out["K10_dt"] < 0).sum())
+    newest = out["K10_et"][:, -1]
+    has = out["K10_nbr"][:, -1] != 0
+    n_same_step = int((has & (q_ts.astype(np.float32) == newest)).sum())
+    n_rounded_past = int((has & (newest.astype(np.float64) > q_ts)).sum())
+    # a query time cast to f32 in front of find_before selects another history on these rows
+    n_f32_query = sum(int(len(nf.find_before(a, b)[0]) != len(nf.find_before(a, np.float32(b))[0])) for a, b in zip(q_nodes, q_ts))
+    assert n_neg > 0 and n_same_step > 0 and n_rounded_past > 0 and n_f32_query > 0
+    nfu = R.get_neighbor_finder(D, uniform=True)
+    log, orig = [], np.random.randint
+
+    def rec(lo, hi, n):
+        r = orig(lo, hi, n); log.append(r.copy()); return r
+    np.random.seed(12)
+    np.random.randint = rec
+    try:
+        nb, ei, et = nfu.get_temporal_neighbor(q_nodes, q_ts, 5)
+    finally:
+        np.random.randint = orig
+    draws = np.full((len(q_nodes), 5), -1, np.int64)
+    it = iter(log)
+    for i, (a, b) in enumerate(zip(q_nodes, q_ts)):
+        if len(nf.find_before(a, b)[0]) > 0:
+            draws[i] = next(it)
+    n_tie = sum(int(any(et[i, a] == et[i, b] and ei[i, a] != ei[i, b] for a in range(5) for b in range(a))) for i in range(len(et))
+                if nb[i].any())
+    c_nb, c_ei, c_et = _stable_rows(nf, q_nodes, q_ts, draws, 5)
+    n_unstable = int(((c_ei != ei).any(1)).sum())
+    assert n_tie > 0 and np.array_equal(c_et, et)
+    print("g10 sampler: %d negative dt, %d rows in the newest edge's f32 step, %d with f32(t_e) > t, %d rows move under an f32 "
+          "query; uniform: %d rows tie between different edges, %d not in stable order" %
+          (n_neg, n_same_step, n_rounded_past, n_f32_query, n_tie, n_unstable))
+    out.update(uni_nbr=nb, uni_eidx=ei, uni_et=et, uni_dt=deltas(et), uni_draws=draws, uni_seed=np.array(12),
+               n_negative_dt=np.array(n_neg), n_same_step_rows=np.array(n_same_step), n_rounded_past_rows=np.array(n_rounded_past),
+               n_f32_query_rows=np.array(n_f32_query), uni_n_tie_rows=np.array(n_tie), uni_n_unstable_rows=np.array(n_unstable))
+    save("g10_realts_sampler", **out)
+    step_fixtures("g10_realts_step_", 12, real_timestamps(1500, np.random.RandomState(10)))
+
+
 if __name__ == "__main__":
     import warnings
     warnings.filterwarnings("ignore")
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9a", "g9b"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9a", "g9b", "g10"]
     for w in which:
         globals()[w]()
