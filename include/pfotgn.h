@@ -219,6 +219,29 @@ int pfo_eval_metrics(const float* emb, int64_t B, int32_t D, int32_t n_neg, cons
                      int32_t* top5_pos, int32_t* top5_item, double* invest_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Read-only top-k recommendation: scores a tile of users against ONE shared candidate matrix and keeps the k best per user
+ * (one launch; the U x I score matrix never reaches memory).
+ *   user_emb f32[U,D]; item_emb f32[n_t*I, D]: n_t blocks of the same I candidates embedded at n_t times;
+ *   user_block i32[U] in [0,n_t) (NULL: all 0): the block user u is scored against (a value outside the range is clamped
+ *   into it).  Both matrices 16-byte aligned.
+ *   score(u,i) = user_emb[u] . item_emb[user_block[u]*I + i] in fp32 on the fp32 matrix core (v_mfma_f32_16x16x4_f32: exact
+ *   products, fp32 accumulation - within the fp32 dot-product error bound, NOT the split 16-bit contraction).
+ *   Candidate i is skipped for user u when item_ok != NULL && item_ok[i] == 0, or when i occurs in
+ *   excl_pos[u, 0:excl_len[u]] (candidate POSITIONS, rows of excl_stride entries; entries < 0 or >= I are ignored, duplicates
+ *   allowed, excl_len is clamped to [0, excl_stride]).
+ *   Order: score descending; among equal scores (-0 == +0) the LARGER position first - the canonical order of
+ *   SURVEY App. A-9 that pfo_eval_metrics uses.  A NaN score is outside the contract.
+ *   top_pos i32[U,k], top_score f32[U,k] (a zero score is returned as +0); slots beyond the number of admissible candidates
+ *   hold -1 / -inf; n_valid i32[U] (optional) = min(k, #admissible).
+ *   D % 4 == 0, D <= 256, 1 <= k <= 64, 1 <= I <= PFO_RECOMMEND_MAX_ITEMS.  The candidates pass through LDS 512 at a time with
+ *   the best k so far carried along, so LDS bounds nothing; the constant bounds the time of one workgroup.
+ */
+#define PFO_RECOMMEND_MAX_ITEMS 65536
+int pfo_recommend_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                       int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                       const uint8_t* item_ok, int32_t k, int32_t* top_pos, float* top_score, int32_t* n_valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Time-sorted adjacency built on the device: replaces get_neighbor_finder / NeighborFinder.__init__ (utils/utils.py:117-148).
  * Every edge e contributes (dst, eidx, ts) to row src[e] and (src, eidx, ts) to row dst[e]; rows are sorted by timestamp,
  * ties in edge order (Python's stable sorted(key=ts), utils.py:139).  A stable LSD radix sort of the 2E entries; the eight

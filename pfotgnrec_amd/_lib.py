@@ -13,6 +13,7 @@ c_i32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 _VP = C.c_void_p
 
 MAX_LAYERS = 4
+RECOMMEND_MAX_ITEMS = 65536     # PFO_RECOMMEND_MAX_ITEMS
 
 
 class TgnConfig(C.Structure):
@@ -83,6 +84,8 @@ PROTOTYPES = {
     "pfo_rank_metrics": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "pfo_eval_metrics": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32,
+                                     _VP, _VP, _VP, _VP]),
     "pfo_adam_step": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                 _VP]),
     "pfo_csr_build_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),

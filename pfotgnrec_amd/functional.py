@@ -229,3 +229,78 @@ def eval_metrics(emb, batch, n_neg, cand, day_idx, port_idx, port_len, ret_past,
               _lib.ptr(port_idx.contiguous() if W else None), _lib.ptr(port_len.contiguous()), W, _lib.ptr(ret_past), _lib.ptr(ret_future),
               n_days, n_stocks, n_ret, int(upper_u), int(out_row0), out[0].shape[0], *[o.data_ptr() for o in out], _lib.stream_ptr())
     return tuple(o[out_row0:out_row0 + batch] for o in out)
+
+
+def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_len=None, item_ok=None, n_blocks=None):
+    """The k best candidates per user in one launch (``pfo_recommend_topk``); nothing but its outputs is written.
+
+    user_emb f32[U,D]; item_emb f32[n_t*I,D]: n_t blocks of the same I candidates (embedded at n_t times); user_block
+    i32[U] in [0,n_t): the block each user is scored against (None: one block).  ``n_blocks`` = n_t; when None it is 1 without
+    ``user_block`` and rows / len(item_ok) with ``item_ok`` - with ``user_block`` alone it must be given.  score(u,i) =
+    user_emb[u] . item_emb[user_block[u]*I + i] in fp32.  Candidate i is skipped for user u when ``item_ok[i] == 0`` (u8 / bool
+    [I]) or when i occurs in ``excl_pos[u, :excl_len[u]]`` (i32[U,W] candidate POSITIONS, entries outside [0,I) ignored;
+    excl_len i32[U], None: the whole row).
+
+    Returns (top_pos i32[U,k], top_score f32[U,k], n_valid i32[U]): score descending, the larger position first among equal
+    scores (the order of ``eval_metrics``); slots beyond the admissible candidates hold -1 / -inf."""
+    import operator
+    for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError("%s must be a 2-D float32 tensor" % name)
+    U, D = user_emb.shape
+    if item_emb.shape[1] != D:
+        raise ValueError("user_emb has %d columns, item_emb %d" % (D, item_emb.shape[1]))
+    if D == 0 or D % 4 != 0 or D > 256:
+        raise ValueError("D must be a positive multiple of 4, at most 256 (got %d)" % D)
+    try:
+        k = operator.index(k)
+    except TypeError:
+        raise ValueError("k must be an integer") from None
+    if not 1 <= k <= 64:
+        raise ValueError("k must be in [1, 64] (got %d)" % k)
+    rows = item_emb.shape[0]
+    if n_blocks is None:
+        if item_ok is not None and item_ok.dim() == 1 and item_ok.shape[0] > 0 and rows % item_ok.shape[0] == 0:
+            n_blocks = rows // item_ok.shape[0]
+        elif user_block is None:
+            n_blocks = 1
+        else:
+            raise ValueError("user_block without item_ok needs n_blocks")
+    n_t = int(n_blocks)
+    if n_t < 1 or rows % n_t != 0 or rows == 0:
+        raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of at least one candidate" % (rows, n_t))
+    I = rows // n_t
+    if I > _lib.RECOMMEND_MAX_ITEMS:
+        raise ValueError("%d candidates, at most %d" % (I, _lib.RECOMMEND_MAX_ITEMS))
+    if user_block is not None and (user_block.dim() != 1 or user_block.shape[0] != U or user_block.dtype != torch.int32):
+        raise ValueError("user_block must be int32 [U]")
+    if item_ok is not None:
+        if item_ok.dim() != 1 or item_ok.shape[0] != I or item_ok.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("item_ok must be uint8 or bool [I]")
+    W = 0
+    if excl_pos is not None:
+        if excl_pos.dim() != 2 or excl_pos.shape[0] != U or excl_pos.dtype != torch.int32:
+            raise ValueError("excl_pos must be int32 [U, W]")
+        W = int(excl_pos.shape[1])
+        if excl_len is not None and (excl_len.dim() != 1 or excl_len.shape[0] != U or excl_len.dtype != torch.int32):
+            raise ValueError("excl_len must be int32 [U]")
+    elif excl_len is not None:
+        raise ValueError("excl_len without excl_pos")
+    dev = user_emb.device
+    _lib.require_gpu(dev)
+    for t in (item_emb, user_block, excl_pos, excl_len, item_ok):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    user_emb, item_emb = user_emb.contiguous(), item_emb.contiguous()
+    if W and excl_len is None:
+        excl_len = torch.full((U,), W, dtype=torch.int32, device=dev)
+    if item_ok is not None:
+        item_ok = item_ok.contiguous().view(torch.uint8) if item_ok.dtype == torch.bool else item_ok.contiguous()
+    top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
+    top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
+    n_valid = torch.empty(U, dtype=torch.int32, device=dev)
+    _lib.call("pfo_recommend_topk", user_emb.data_ptr(), item_emb.data_ptr(),
+              _lib.ptr(user_block.contiguous() if user_block is not None else None), U, I, n_t, D,
+              _lib.ptr(excl_pos.contiguous() if W else None), _lib.ptr(excl_len.contiguous() if W else None), W, _lib.ptr(item_ok), k,
+              top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
+    return top_pos, top_score, n_valid

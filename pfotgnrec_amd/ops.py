@@ -9,11 +9,14 @@ inference and - for the BPR loss - an autograd formula:
     torch.ops.pfotgn.time_encode(t, weight, bias)                              model/time_encoding.py:17-25
     torch.ops.pfotgn.bpr_loss(emb, batch, n_neg, pos_block, grad_scale)        main.py:321-337 / 364-381
     torch.ops.pfotgn.rank_metrics(emb, batch, n_items)                         evaluation.py:114-145
+    torch.ops.pfotgn.recommend_topk(user_emb, item_emb, k, n_blocks, ...)      the k best candidates per user (no reference form)
 
 Only a HIP implementation is registered ("cuda" dispatch key = ROCm here): on any other device the dispatcher raises,
 there is no CPU fallback.  The TGN step itself keeps its ``autograd.Function`` (``tgn._EmbedFn``): it owns state (memory,
 message tables, a workspace per outstanding call) that a functional op schema cannot express.
 """
+from typing import Optional
+
 import torch
 
 from . import _lib, functional
@@ -95,3 +98,18 @@ def rank_metrics(emb: torch.Tensor, batch: int, n_items: int) -> tuple[torch.Ten
 def _(emb, batch, n_items):
     return (emb.new_empty((batch,), dtype=torch.int32), emb.new_empty((batch, 3), dtype=torch.float32),
             emb.new_empty((batch, 3), dtype=torch.float32))
+
+
+@torch.library.custom_op(_LIB_NS + "::recommend_topk", mutates_args=(), device_types="cuda")
+def recommend_topk(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int, n_blocks: int = 1,
+                   user_block: Optional[torch.Tensor] = None, excl_pos: Optional[torch.Tensor] = None,
+                   excl_len: Optional[torch.Tensor] = None,
+                   item_ok: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return functional.recommend_topk(user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, n_blocks=n_blocks)
+
+
+@recommend_topk.register_fake
+def _(user_emb, item_emb, k, n_blocks=1, user_block=None, excl_pos=None, excl_len=None, item_ok=None):
+    U = user_emb.shape[0]
+    return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
+            user_emb.new_empty((U,), dtype=torch.int32))
