@@ -257,3 +257,69 @@ def test_g8_full_step_with_dropout():
     tgn.dropout_masks = None
     se0, _, _ = tgn.compute_temporal_embeddings(sb, db, neg.flatten(), tb, eb, K)
     assert relerr(se0, g["s_emb_src"]) > 1e-3
+
+
+# ------------------------------------------------------------------ the attention layer at widths no fixture has
+@pytest.mark.parametrize("D,Ef,H,K", [(8, 0, 1, 3), (12, 8, 2, 4), (32, 4, 2, 64), (16, 64, 2, 5)])
+def test_attention_layer_against_torch_at_other_widths(D, Ef, H, K):
+    """The fixtures pin the oracle to the reference at ONE edge-feature width.  Here the layer is restated from its public parts -
+    torch.nn.MultiheadAttention(embed_dim=2D, kdim=vdim=2D+Ef) + the two-layer merger (temporal_attention.py:22-32,
+    utils.py:5-20), float64, same weights - at no edge columns, Ef close to D, Ef far wider than D and a full 64 keys, with the
+    rule for rows that are all padding (first slot unmasked, output zeroed, :60-84).  Forward and every gradient (torch.autograd)
+    at the bars of test_g4_attention_forward_backward."""
+    import torch
+    rs = np.random.RandomState(100 * D + Ef)
+    N, E, C = 37, 2 * D, 2 * D + Ef
+    P = T.init_params(D, Ef, 1, seed=D + K, use_memory=False)
+    p = T.layer_params(P, 0)
+    x, tq = rs.randn(N, D).astype(np.float32), rs.randn(N, D).astype(np.float32)
+    nb, te = rs.randn(N, K, D).astype(np.float32), rs.randn(N, K, D).astype(np.float32)
+    ef = rs.randn(N, K, Ef).astype(np.float32)
+    n_valid = rs.randint(0, K + 1, N)                                  # most-recent layout: padding in front
+    n_valid[:4] = (0, 0, K, 1)
+    mask = np.arange(K)[None, :] < (K - n_valid)[:, None]
+    assert mask.all(1).sum() >= 2 and (~mask).all(1).any()
+    go = rs.randn(N, D).astype(np.float32)
+    out, c = T.attention_forward(p, x, tq, nb, ef, te, mask, H)
+    grads, dx, dtq, dnb, dte = T.attention_backward(p, c, go, H, D)
+
+    t = lambda a, grad=False: torch.tensor(np.asarray(a, np.float64), requires_grad=grad)
+    mha = torch.nn.MultiheadAttention(embed_dim=E, kdim=C, vdim=C, num_heads=H).double()
+    fc1, fc2 = torch.nn.Linear(E + D, D).double(), torch.nn.Linear(D, D).double()
+    packed = mha.q_proj_weight is None          # Ef = 0: kdim == embed_dim and torch keeps ONE in_proj_weight = [Wq ; Wk ; Wv]
+    assert packed == (Ef == 0)
+    with torch.no_grad():
+        if packed:
+            mha.in_proj_weight.copy_(t(np.concatenate([p["Wq"], p["Wk"], p["Wv"]])))
+        else:
+            for dst, src in ((mha.q_proj_weight, "Wq"), (mha.k_proj_weight, "Wk"), (mha.v_proj_weight, "Wv")):
+                dst.copy_(t(p[src]))
+        for dst, src in ((mha.in_proj_bias, "b_in"), (mha.out_proj.weight, "Wo"), (mha.out_proj.bias, "bo"), (fc1.weight, "W1"),
+                         (fc1.bias, "b1"), (fc2.weight, "W2"), (fc2.bias, "b2")):
+            dst.copy_(t(p[src]))
+    tx, ttq, tnb, tte = t(x, True), t(tq, True), t(nb, True), t(te, True)
+    query = torch.cat([tx, ttq], 1).unsqueeze(0)                                    # [1, N, E]
+    key = torch.cat([tnb, t(ef), tte], 2).permute(1, 0, 2)                          # [K, N, C]
+    inv = torch.from_numpy(mask.all(1))
+    pad = torch.from_numpy(mask.copy())
+    pad[inv, 0] = False
+    attn, _ = mha(query=query, key=key, value=key, key_padding_mask=pad)
+    attn = attn.squeeze(0).masked_fill(inv[:, None], 0.0)
+    want = fc2(torch.relu(fc1(torch.cat([attn, tx], 1))))
+    want.backward(t(go))
+    assert relerr(out, want.detach().numpy()) < 1e-5
+    assert row_relerr(out, want.detach().numpy()) < ROW_RTOL
+    assert relerr(dx, tx.grad.numpy()) < 1e-5 and relerr(dnb, tnb.grad.numpy()) < 1e-5
+    assert relerr(dte, tte.grad.numpy()) < 1e-5 and relerr(dtq, ttq.grad.numpy()) < 1e-5
+    if packed:
+        tg = dict(zip(("Wq", "Wk", "Wv"), mha.in_proj_weight.grad.numpy().reshape(3, E, E)))
+    else:
+        tg = dict(Wq=mha.q_proj_weight.grad.numpy(), Wk=mha.k_proj_weight.grad.numpy(), Wv=mha.v_proj_weight.grad.numpy())
+    tg.update({k: w.grad.numpy() for k, w in dict(b_in=mha.in_proj_bias, Wo=mha.out_proj.weight, bo=mha.out_proj.bias, W1=fc1.weight,
+                                                  b1=fc1.bias, W2=fc2.weight, b2=fc2.bias).items()})
+    assert set(tg) == set(T._LAYER_KEYS)
+    E3 = slice(E, 2 * E)                                               # the key bias: its gradient cancels in the softmax
+    for k, ref in tg.items():
+        if k == "b_in":
+            assert np.abs(grads[k][E3]).max() < 1e-5 * np.abs(ref).max() and np.abs(ref[E3]).max() < 1e-12
+        assert relerr(grads[k], ref) < 1e-5, k
