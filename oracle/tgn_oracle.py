@@ -1,4 +1,4 @@
-"""Oracle: TGN forward/backward + memory state machine in numpy fp32.  Test infrastructure only.
+"""Oracle: TGN forward/backward + memory state machine in numpy fp32 (or float64, below).  Test infrastructure only.
 
 Restates, in the reference's own operation order (un-folded K/V projections,
 materialised key tensor, recursive embedding), what these reference files
@@ -18,6 +18,14 @@ that golden fixtures captured from the reference inject directly.  Dropout is
 not modelled (parity is defined at p=0 / eval mode).
 Backward is hand-derived; it is pinned against the reference's autograd by the
 golden fixtures (tests/test_oracle_golden.py).
+
+Working dtype.  Every function takes ``dtype`` (default fp32: the path the fixtures pin, bit for bit what it was before the
+argument existed, since a cast of an fp32 array to fp32 changes nothing).  ``dtype=np.float64`` evaluates the SAME function
+in float64: parameters, features and state are the fp32 values promoted exactly, and the roundings that belong to the
+function and not to its evaluation stay fp32 in both modes - f32 edge times, ``dt = f32(q_ts - f64(f32(t_e)))``, f32
+``last_update`` and message times, and the time-encoder argument as one fp32 FMA (its cosine / sine are then taken in float64
+of that fp32 argument).  The distance of the fp32 evaluation from the float64 one is the evaluation noise of one fp32
+run, which is what tests/parity.py sets the gradient bar from.
 """
 from collections import defaultdict
 import numpy as np
@@ -67,10 +75,13 @@ def _clib():
     return _CLIB or None
 
 
-def time_encode(t, w, b):
-    """cos(fma(t, w_d, b_d)); t f32[...]; w [D] (or [D,1]); returns f32[..., D]  (time_encoding.py:17-25)."""
+def time_encode(t, w, b, dtype=f32):
+    """cos(fma(t, w_d, b_d)); t f32[...]; w [D] (or [D,1]); returns dtype[..., D]  (time_encoding.py:17-25).  The argument is
+    one fp32 FMA in either mode (w and b hold fp32 values: the casts below are exact)."""
     lib = _clib()
     w1, b1 = np.ascontiguousarray(w, f32).reshape(-1), np.ascontiguousarray(b, f32)
+    if dtype != f32:
+        return np.cos(fmaf(np.asarray(t, f32)[..., None], w1, b1).astype(dtype))
     if lib is not None and len(w1) <= 512:
         tt = np.ascontiguousarray(t, f32)
         out = np.empty(tt.shape + (len(w1),), f32)
@@ -80,10 +91,15 @@ def time_encode(t, w, b):
     return np.cos(fmaf(t, w1, b1)).astype(f32)
 
 
-def time_encode_backward(t, w, b, g):
+def time_encode_backward(t, w, b, g, dtype=f32):
     """Grads of sum(g * cos(t*w+b)) w.r.t. w [D] and b [D]."""
     lib = _clib()
     w1, b1 = np.ascontiguousarray(w, f32).reshape(-1), np.ascontiguousarray(b, f32)
+    if dtype != f32:
+        t = np.asarray(t, f32)[..., None]
+        s = -np.sin(fmaf(t, w1, b1).astype(dtype)) * g
+        D = s.shape[-1]
+        return (s * t.astype(dtype)).reshape(-1, D).sum(0), s.reshape(-1, D).sum(0)
     if lib is not None and len(w1) <= 512:
         tt, gg = np.ascontiguousarray(t, f32), np.ascontiguousarray(g, f32)
         dw, db = np.empty(len(w1), np.float64), np.empty(len(w1), np.float64)
@@ -96,24 +112,24 @@ def time_encode_backward(t, w, b, g):
     return (s * t).reshape(-1, D).sum(0, dtype=np.float64).astype(f32), s.reshape(-1, D).sum(0, dtype=np.float64).astype(f32)
 
 
-def sigmoid(x):
-    return (1.0 / (1.0 + np.exp(-x.astype(np.float64)))).astype(f32)
+def sigmoid(x, dtype=f32):
+    return (1.0 / (1.0 + np.exp(-x.astype(np.float64)))).astype(dtype)
 
 
 # ----------------------------------------------------------------------------- GRU cell
-def gru_cell(x, h, W_ih, W_hh, b_ih, b_hh):
+def gru_cell(x, h, W_ih, W_hh, b_ih, b_hh, dtype=f32):
     """torch.nn.GRUCell (memory_updater.py:60): gates ordered (r, z, n)."""
     D = h.shape[1]
     gi = x @ W_ih.T + b_ih
     gh = h @ W_hh.T + b_hh
-    r = sigmoid(gi[:, :D] + gh[:, :D])
-    z = sigmoid(gi[:, D:2 * D] + gh[:, D:2 * D])
-    n = np.tanh(gi[:, 2 * D:] + r * gh[:, 2 * D:]).astype(f32)
-    hn = ((1 - z) * n + z * h).astype(f32)
+    r = sigmoid(gi[:, :D] + gh[:, :D], dtype)
+    z = sigmoid(gi[:, D:2 * D] + gh[:, D:2 * D], dtype)
+    n = np.tanh(gi[:, 2 * D:] + r * gh[:, 2 * D:]).astype(dtype)
+    hn = ((1 - z) * n + z * h).astype(dtype)
     return hn, (x, h, r, z, n, gh[:, 2 * D:])
 
 
-def gru_cell_backward(cache, d_hn, W_ih, W_hh):
+def gru_cell_backward(cache, d_hn, W_ih, W_hh, dtype=f32):
     """Parameter grads only: x (stored message) and h (detached memory) are constants."""
     x, h, r, z, n, ghn = cache
     dn = d_hn * (1 - z)
@@ -122,13 +138,13 @@ def gru_cell_backward(cache, d_hn, W_ih, W_hh):
     dr = dpre_n * ghn
     dpre_r = dr * r * (1 - r)
     dpre_z = dz * z * (1 - z)
-    dgi = np.concatenate([dpre_r, dpre_z, dpre_n], 1).astype(f32)
-    dgh = np.concatenate([dpre_r, dpre_z, dpre_n * r], 1).astype(f32)
+    dgi = np.concatenate([dpre_r, dpre_z, dpre_n], 1).astype(dtype)
+    dgh = np.concatenate([dpre_r, dpre_z, dpre_n * r], 1).astype(dtype)
     return {"weight_ih": dgi.T @ x, "weight_hh": dgh.T @ h, "bias_ih": dgi.sum(0), "bias_hh": dgh.sum(0)}
 
 
 # ----------------------------------------------------------------------------- temporal attention layer
-def attention_forward(p, x, tq, nbr_feat, ef, te, mask, n_head, drop=None):
+def attention_forward(p, x, tq, nbr_feat, ef, te, mask, n_head, drop=None, dtype=f32):
     """TemporalAttentionLayer.forward (temporal_attention.py:34-90).
 
     p: dict with Wq [E,E], Wk [E,C], Wv [E,C], b_in [3E], Wo [E,E], bo [E], W1 [D,E+D], b1, W2 [D,D], b2
@@ -151,24 +167,25 @@ def attention_forward(p, x, tq, nbr_feat, ef, te, mask, n_head, drop=None):
     Kp = (key2 @ p["Wk"].T + bk).reshape(N, K, E)                      # [N,K,E]
     Vp = (key2 @ p["Wv"].T + bv).reshape(N, K, E)
     dh = E // n_head
-    scale = f32(1.0 / np.sqrt(dh))
+    scale = np.dtype(dtype).type(1.0 / np.sqrt(dh))
     Qh = (Qp * scale).reshape(N, n_head, dh)
     Kh = Kp.reshape(N, K, n_head, dh)
     Vh = Vp.reshape(N, K, n_head, dh)
     scores = np.matmul(Kh.transpose(0, 2, 1, 3), Qh[:, :, :, None])[..., 0]          # [N,H,K] (batched BLAS)
-    scores = np.where(mask[:, None, :], -np.inf, scores).astype(f32)
+    scores = np.where(mask[:, None, :], -np.inf, scores).astype(dtype)
     m = scores.max(-1, keepdims=True)
     e = np.exp(scores - m)
-    a = (e / e.sum(-1, keepdims=True)).astype(f32)                     # [N,H,K]
-    ad = a if drop is None else (a * drop).astype(f32)                 # F.dropout on the attention weights (train mode)
+    a = (e / e.sum(-1, keepdims=True)).astype(dtype)                   # [N,H,K]
+    ad = a if drop is None else (a * drop).astype(dtype)               # F.dropout on the attention weights (train mode)
     Oh = np.matmul(ad[:, :, None, :], Vh.transpose(0, 2, 1, 3))[:, :, 0, :].reshape(N, E)
     attn = Oh @ p["Wo"].T + p["bo"]
     attn[inv] = 0                                                      # :84
     cat = np.concatenate([attn, x], 1)                                 # :88 / utils.py:15
     z1 = cat @ p["W1"].T + p["b1"]
     h1 = np.maximum(z1, 0)
-    out = (h1 @ p["W2"].T + p["b2"]).astype(f32)
-    cache = dict(q_in=q_in, key=key, inv=inv, Qh=Qh, Kh=Kh, Vh=Vh, a=a, ad=ad, drop=drop, Oh=Oh, cat=cat, z1=z1, h1=h1, scale=scale)
+    out = (h1 @ p["W2"].T + p["b2"]).astype(dtype)
+    cache = dict(q_in=q_in, key=key, inv=inv, Qh=Qh, Kh=Kh, Vh=Vh, a=a, ad=ad, drop=drop, Oh=Oh, cat=cat, z1=z1, h1=h1, scale=scale,
+                 dtype=dtype)
     return out, cache
 
 
@@ -176,6 +193,7 @@ def attention_backward(p, c, d_out, n_head, D):
     """Returns (param grads, d_x [N,D], d_tq [N,D], d_nbr_feat [N,K,D], d_te [N,K,D])."""
     N, K = c["a"].shape[0], c["a"].shape[2]
     E = c["q_in"].shape[1]
+    dtype = c["dtype"]                                                  # the forward's working dtype
     g = {}
     g["W2"] = d_out.T @ c["h1"]; g["b2"] = d_out.sum(0)
     dh1 = d_out @ p["W2"]
@@ -208,8 +226,8 @@ def attention_backward(p, c, d_out, n_head, D):
     d_x += dq_in[:, :D]
     d_tq = dq_in[:, D:]
     Ef = dkey.shape[2] - 2 * D
-    return ({k: v.astype(f32) for k, v in g.items()}, d_x.astype(f32), d_tq.astype(f32),
-            dkey[:, :, :D].astype(f32), dkey[:, :, D + Ef:].astype(f32))
+    return ({k: v.astype(dtype) for k, v in g.items()}, d_x.astype(dtype), d_tq.astype(dtype),
+            dkey[:, :, :D].astype(dtype), dkey[:, :, D + Ef:].astype(dtype))
 
 
 # ----------------------------------------------------------------------------- the same two functions over row chunks, threaded
@@ -249,15 +267,15 @@ class _one_blas_thread:
             self._ctx.__exit__(*a)
 
 
-def attention_forward_mt(p, x, tq, nbr_feat, ef, te, mask, n_head, drop=None):
+def attention_forward_mt(p, x, tq, nbr_feat, ef, te, mask, n_head, drop=None, dtype=f32):
     N = mask.shape[0]
     if N < MT_MIN_ROWS:
-        return attention_forward(p, x, tq, nbr_feat, ef, te, mask, n_head, drop)
+        return attention_forward(p, x, tq, nbr_feat, ef, te, mask, n_head, drop, dtype)
     bounds = [(i, min(N, i + MT_CHUNK)) for i in range(0, N, MT_CHUNK)]
     with _one_blas_thread():
         res = list(_pool().map(lambda b: attention_forward(p, x[b[0]:b[1]], tq[b[0]:b[1]], nbr_feat[b[0]:b[1]], ef[b[0]:b[1]],
                                                            te[b[0]:b[1]], mask[b[0]:b[1]], n_head,
-                                                           None if drop is None else drop[b[0]:b[1]]), bounds))
+                                                           None if drop is None else drop[b[0]:b[1]], dtype), bounds))
     out = np.concatenate([r[0] for r in res])
     cache = dict(chunks=[r[1] for r in res], bounds=bounds, z1=np.concatenate([r[1]["z1"] for r in res]))
     return out, cache
@@ -276,19 +294,19 @@ def attention_backward_mt(p, c, d_out, n_head, D):
 
 
 # ----------------------------------------------------------------------------- BPR (main.py:321-337)
-def bpr_loss(src, pos, neg):
+def bpr_loss(src, pos, neg, dtype=f32):
     """src [B,D]; pos [B,p,D]; neg [B,q,D].  sigma of the MEAN difference."""
     pos_s = np.einsum("bd,bpd->bp", src, pos)                          # [B,p]  (p == 1 in the reference)
     neg_s = np.einsum("bd,bqd->bq", src, neg)
     diff = pos_s - neg_s                                               # broadcast [B,1]-[B,q]
     dm = diff.mean(1)
-    sg = sigmoid(dm)
+    sg = sigmoid(dm, dtype)
     loss = -np.mean(np.log(sg))
-    return f32(loss), (src, pos, neg, sg, diff.shape[1])
+    return np.dtype(dtype).type(loss), (src, pos, neg, sg, diff.shape[1], dtype)
 
 
 def bpr_loss_backward(cache):
-    src, pos, neg, sg, q = cache
+    src, pos, neg, sg, q, dtype = cache
     B = src.shape[0]
     ddm = -(1 - sg) / B                                                # d loss / d dm
     ddiff = np.repeat((ddm / q)[:, None], q, 1)                        # [B,q]
@@ -297,7 +315,7 @@ def bpr_loss_backward(cache):
     d_src = np.einsum("bp,bpd->bd", dpos_s, pos) + np.einsum("bq,bqd->bd", dneg_s, neg)
     d_pos = dpos_s[:, :, None] * src[:, None, :]
     d_neg = dneg_s[:, :, None] * src[:, None, :]
-    return d_src.astype(f32), d_pos.astype(f32), d_neg.astype(f32)
+    return d_src.astype(dtype), d_pos.astype(dtype), d_neg.astype(dtype)
 
 
 # ----------------------------------------------------------------------------- the model
@@ -339,11 +357,12 @@ def _scatter_add_rows(dst, idx, rows):
 class OracleTGN:
     """State + step semantics of model/tgn.py (graph_attention + identity message + last aggregator + GRU)."""
 
-    def __init__(self, neighbor_finder, node_features, edge_features, params, n_layers, n_heads, use_memory=True):
+    def __init__(self, neighbor_finder, node_features, edge_features, params, n_layers, n_heads, use_memory=True, dtype=f32):
         self.neighbor_finder = neighbor_finder
-        self.node_features = np.asarray(node_features).astype(f32)                 # tgn.py:35
-        self.edge_features = normalise_edge_features(edge_features)                 # tgn.py:38-41
-        self.P = {k: np.asarray(v, f32) for k, v in params.items()}
+        self.dtype = np.dtype(dtype).type                                           # working dtype (module docstring)
+        self.node_features = np.asarray(node_features).astype(f32).astype(self.dtype)            # tgn.py:35
+        self.edge_features = normalise_edge_features(edge_features).astype(self.dtype)           # tgn.py:38-41 (fp32, promoted)
+        self.P = {k: np.asarray(v, f32).astype(self.dtype) for k, v in params.items()}
         self.n_layers, self.n_heads, self.use_memory = n_layers, n_heads, use_memory
         self.n_nodes, self.D = self.node_features.shape
         # train-mode attention dropout, injected: {layer l (1-based): f32 [n_l, H, K]} multipliers for the n_l instances of
@@ -354,9 +373,24 @@ class OracleTGN:
 
     # -- modules/memory.py:23-33
     def init_memory(self):
-        self.memory = np.zeros((self.n_nodes, self.D), f32)
+        self.memory = np.zeros((self.n_nodes, self.D), self.dtype)
         self.last_update = np.zeros(self.n_nodes, f32)
         self.messages = defaultdict(list)
+
+    def load_state(self, other):
+        """Parameters, memory, last_update, pending messages and injected dropout masks of ``other`` (an fp32 instance on the
+        same graph), promoted exactly to this instance's dtype: both then evaluate the same function at the same point.  A
+        float64 instance is loaded before EVERY step and never carries the state it computed itself into the next one."""
+        assert other.dtype is f32 and other.n_nodes == self.n_nodes and other.use_memory == self.use_memory
+        dt = self.dtype
+        self.P = {k: np.asarray(v, f32).astype(dt) for k, v in other.P.items()}
+        self.memory = other.memory.astype(dt)
+        self.last_update = other.last_update.astype(f32)
+        self.messages = defaultdict(list)
+        for nid, lst in other.messages.items():
+            if len(lst) > 0:
+                self.messages[nid] = [(np.asarray(m, f32).astype(dt), f32(t)) for m, t in lst]
+        self.dropout_masks = other.dropout_masks
 
     def _w(self):
         return self.P["time_encoder.w.weight"].reshape(-1), self.P["time_encoder.w.bias"]
@@ -373,8 +407,8 @@ class OracleTGN:
             if len(lst) > 0:
                 ids.append(int(nid)); msgs.append(lst[-1][0]); ts.append(lst[-1][1])
         if ids:
-            return np.array(ids, np.int64), np.stack(msgs).astype(f32), np.array(ts, f32)
-        return np.zeros(0, np.int64), np.zeros((0, 0), f32), np.zeros(0, f32)
+            return np.array(ids, np.int64), np.stack(msgs).astype(self.dtype), np.array(ts, f32)
+        return np.zeros(0, np.int64), np.zeros((0, 0), self.dtype), np.zeros(0, f32)
 
     # -- memory_updater.py:35-53
     def _get_updated_memory(self):
@@ -383,7 +417,7 @@ class OracleTGN:
         cache = None
         if len(ids) > 0:
             assert (self.last_update[ids] <= ts).all(), "Trying to update memory to time in the past"
-            hn, cache = gru_cell(msgs, mem[ids], *self._gru())
+            hn, cache = gru_cell(msgs, mem[ids], *self._gru(), dtype=self.dtype)
             mem[ids] = hn
             lu[ids] = ts
         return mem, lu, (ids, cache)
@@ -396,15 +430,15 @@ class OracleTGN:
         assert (self.last_update[ids] <= ts).all(), "Trying to update memory to time in the past"
         h = self.memory[ids]
         self.last_update[ids] = ts
-        self.memory[ids], _ = gru_cell(msgs, h, *self._gru())
+        self.memory[ids], _ = gru_cell(msgs, h, *self._gru(), dtype=self.dtype)
 
     # -- tgn.py:357-378
     def _get_raw_messages(self, src, dst, edge_times, edge_idxs):
         et = np.asarray(edge_times).astype(f32)                                    # :359
         ef = self.edge_features[edge_idxs]
         delta = et - self.last_update[src]                                          # :367 fp32
-        enc = time_encode(delta, *self._w())
-        msg = np.concatenate([self.memory[src], self.memory[dst], ef, enc], 1).astype(f32)   # :371
+        enc = time_encode(delta, *self._w(), dtype=self.dtype)
+        msg = np.concatenate([self.memory[src], self.memory[dst], ef, enc], 1).astype(self.dtype)   # :371
         for i in range(len(src)):
             self.messages[int(src[i])].append((msg[i], et[i]))                      # :375-376 (store_raw_messages extends)
 
@@ -419,7 +453,7 @@ class OracleTGN:
             feat = self.node_features[nodes]
             if self.use_memory:
                 feat = memory[nodes] + feat                                         # :98
-            return feat.astype(f32), ("leaf", nodes)
+            return feat.astype(self.dtype), ("leaf", nodes)
         w, b = self._w()
         Kc = K if K > 0 else 1
         n_below = n_l * (1 + Kc)
@@ -431,15 +465,15 @@ class OracleTGN:
         deltas = (ts[:, None] - et).astype(f32)                                     # :133-135 (f64 - f32 -> f32)
         nb, c_nb = self._embed(memory, nbr.flatten(), np.repeat(ts, K), l - 1, K, draws, n_l + base * Kc, n_below)   # :141
         nb = nb.reshape(len(nodes), Kc, -1)
-        te = time_encode(deltas, w, b)                                              # :150
-        tq = np.broadcast_to(time_encode(np.zeros(1, f32), w, b), (len(nodes), self.D)).astype(f32)   # :92
+        te = time_encode(deltas, w, b, self.dtype)                                  # :150
+        tq = np.broadcast_to(time_encode(np.zeros(1, f32), w, b, self.dtype), (len(nodes), self.D)).astype(self.dtype)   # :92
         ef = self.edge_features[eidx]                                               # :152
         mask = nbr == 0                                                             # :154
         drop = None
         if self.dropout_masks is not None:
             drop = self.dropout_masks[l][base:base + len(nodes)]
             assert drop.shape == (len(nodes), self.n_heads, Kc), (drop.shape, len(nodes), self.n_heads, Kc)
-        out, c = attention_forward_mt(layer_params(self.P, l - 1), x, tq, nb, ef, te, mask, self.n_heads, drop)
+        out, c = attention_forward_mt(layer_params(self.P, l - 1), x, tq, nb, ef, te, mask, self.n_heads, drop, self.dtype)
         return out, ("layer", l, c_x, c_nb, c, deltas, (nbr, eidx, et))
 
     def _embed_backward(self, ctx, d_out, grads, d_mem):
@@ -453,8 +487,8 @@ class OracleTGN:
         pre = "embedding_module.attention_models.%d." % (l - 1)
         for k, v in g.items():
             grads[pre + _LAYER_KEYS[k]] += v
-        gw, gb = time_encode_backward(deltas, w, b, d_te)
-        gw0, gb0 = time_encode_backward(np.zeros(d_tq.shape[0], f32), w, b, d_tq)
+        gw, gb = time_encode_backward(deltas, w, b, d_te, self.dtype)
+        gw0, gb0 = time_encode_backward(np.zeros(d_tq.shape[0], f32), w, b, d_tq, self.dtype)
         grads["time_encoder.w.weight"] += (gw + gw0).reshape(-1, 1)
         grads["time_encoder.w.bias"] += gb + gb0
         self._embed_backward(c_x, d_x, grads, d_mem)
@@ -496,20 +530,20 @@ class OracleTGN:
     def backward(self, d_emb):
         """d_emb [R,D] for the concatenated roots of the last step -> dict of parameter grads."""
         grads = {k: np.zeros_like(v) for k, v in self.P.items()}
-        d_mem = np.zeros((self.n_nodes, self.D), f32)
-        self._embed_backward(self._ctx, np.asarray(d_emb, f32), grads, d_mem)
+        d_mem = np.zeros((self.n_nodes, self.D), self.dtype)
+        self._embed_backward(self._ctx, np.asarray(d_emb, self.dtype), grads, d_mem)
         if self.use_memory and self._gru_ctx is not None and self._gru_ctx[1] is not None:
             ids, cache = self._gru_ctx
             W_ih, W_hh, _, _ = self._gru()
-            g = gru_cell_backward(cache, d_mem[ids], W_ih, W_hh)
+            g = gru_cell_backward(cache, d_mem[ids], W_ih, W_hh, self.dtype)
             for k, v in g.items():
-                grads["memory_updater.memory_updater." + k] += v.astype(f32)
+                grads["memory_updater.memory_updater." + k] += v.astype(self.dtype)
         return grads
 
     # dense view of the pending-message table (last message per node) for comparisons with the device layout
     def pending_table(self):
         M = 3 * self.D + self.edge_features.shape[1]
-        tab = np.zeros((self.n_nodes, M), f32); t = np.zeros(self.n_nodes, f32); has = np.zeros(self.n_nodes, bool)
+        tab = np.zeros((self.n_nodes, M), self.dtype); t = np.zeros(self.n_nodes, f32); has = np.zeros(self.n_nodes, bool)
         for nid, lst in self.messages.items():
             if len(lst) > 0:
                 tab[nid], t[nid], has[nid] = lst[-1][0], lst[-1][1], True

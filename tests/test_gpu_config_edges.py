@@ -16,7 +16,8 @@ from pfotgnrec_amd.synthetic import SyntheticConfig, make_graph
 from oracle import tgn_oracle as T
 from oracle.neighbor_finder import OracleNeighborFinder, build_adjacency
 from parity import (relerr, row_relerr, ROW_RTOL, RTOL_EMB, RTOL_GRAD_TIME, RTOL_GRAD_ORACLE_L2, _near_kink_roots,
-                    _masked_bpr_backward, _legal_draws)
+                    _masked_bpr_backward, _legal_draws, GRAD_MARGIN, grad_blocks, grad_block_bar, check_grad_blocks,
+                    fmt_worst_block, f64_twin, _f64_backward)
 
 DEV = "cuda:0"
 N_NEG = 3
@@ -61,6 +62,7 @@ CASES = {
     "p": (16, 4, 2, 4, 2, True, False, WIDE, 8, (2500, 2508, 2516), 1, True),
 }
 DEEP_CASES = ("i", "j", "k", "l")
+F64_LAST_STEP_ONLY = ("i", "j")   # float64 walk of 5 200 instances x 63 / 64 keys: ~2.5 s per step on the host, so the last step only
 
 
 class _Inputs:
@@ -123,6 +125,12 @@ class _Inputs:
             assert shifted > 0
 
 
+def _f64_on_step(cid, step, n_steps):
+    """Whether the float64 oracle walks this step.  Every step of every case, unless a case's float64 walk is too slow for the
+    suite (then its last step only; see F64_LAST_STEP_ONLY)."""
+    return cid not in F64_LAST_STEP_ONLY or step == n_steps - 1
+
+
 def _kink_fraction(ref, R, K):
     return float(_near_kink_roots(ref._ctx, R, K).mean())
 
@@ -139,22 +147,45 @@ def _numpy_adam(P_, grads, m, v, t, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
 def test_case_batches_cover_what_the_case_is_for(cid):
     """Without a device: the oracle alone walks the case's three steps (its own gradients through Adam in numpy stand in for the
     product's optimizer) - at every step it leaves out at most 10 % of the roots as near a ReLU kink, and the deep-history cases
-    hold the empty, partial, full and shifted histories they exist for."""
+    hold the empty, partial, full and shifted histories they exist for.  Beside it the float64 oracle evaluates every step from
+    the fp32 state: its ReLU decisions on the roots the mask keeps are the fp32 run's, and the block bar of the GPU test
+    (GRAD_MARGIN x e32 per tensor, parity.py) is finite, positive and below the per-tensor bar it stands beside."""
     c = _Inputs(cid)
     if cid in DEEP_CASES:
         c.assert_history_coverage()
     ref = c.oracle()
+    ref64 = f64_twin(ref)
     m, v = {}, {}
     B, R = c.B, (2 + N_NEG) * c.B
     for step, (sb, db, tb, eb, neg, _) in enumerate(c.steps):
         _, odraws = c.draws(step)
+        f64_here = _f64_on_step(cid, step, len(c.steps))
+        if f64_here:
+            ref64.load_state(ref)
+            e64 = ref64.compute_temporal_embeddings(sb, db, neg, tb, eb, c.K, draws=None if odraws is None else list(odraws))
         rse, rde, rne = ref.compute_temporal_embeddings(sb, db, neg, tb, eb, c.K, draws=odraws)
         frac = _kink_fraction(ref, R, c.K)
         assert frac <= MAX_KINK_FRACTION, (cid, step, frac)
         assert np.isfinite(np.concatenate([rse, rde, rne])).all()
         _, cache = T.bpr_loss(rse, rde.reshape(B, 1, -1), rne.reshape(B, N_NEG, -1))
         ds, dp, dn = T.bpr_loss_backward(cache)
-        grads = ref.backward(np.concatenate([ds, dp.reshape(B, -1), dn.reshape(N_NEG * B, -1)]))
+        W = np.concatenate([ds, dp.reshape(B, -1), dn.reshape(N_NEG * B, -1)])
+        grads = ref.backward(W)
+        if f64_here:
+            assert relerr(np.concatenate(e64), np.concatenate([rse, rde, rne])) < 1e-5     # the same function at the same point
+            g64 = _f64_backward(ref64, ref, e64, B, c.K, n_neg=N_NEG)                       # asserts the ReLU decisions agree
+            W[_near_kink_roots(ref._ctx, R, c.K)] = 0
+            g32 = ref.backward(W)
+            n_checked = 0
+            for name in sorted(g32):
+                if np.abs(g32[name]).max() < 1e-7:                                           # (what _run_case leaves out)
+                    continue
+                e32, bar = grad_block_bar(g32[name], g64[name], grad_blocks(name, g64[name].shape, c.D, c.Ef, c.H))
+                assert np.isfinite(e32) and e32 > 0, (cid, step, name, e32)
+                old = RTOL_GRAD_TIME if name.startswith("time_encoder") else RTOL_GRAD_ORACLE_L2
+                assert GRAD_MARGIN * e32 < old and bar < old, (cid, step, name, e32)
+                n_checked += 1
+            assert n_checked >= 2 + 8 * c.L, (cid, step, n_checked)
         _numpy_adam(ref.P, grads, m, v, step + 1)
 
 
@@ -177,7 +208,8 @@ def _run_case(cid, deterministic=False):
             sd[k].copy_(torch.from_numpy(c.params[k]))
     opt = P.FusedAdam(tgn, lr=1e-3)
     ref = c.oracle()
-    worst = {}
+    ref64 = f64_twin(ref)
+    worst, worst_block = {}, (0.0, None, None, 0.0, 0.0)
 
     def note(key, e):
         worst[key] = max(worst.get(key, 0.0), float(e))
@@ -189,6 +221,10 @@ def _run_case(cid, deterministic=False):
         draws, odraws = c.draws(step)
         tgn.train(); opt.zero_grad()
         se, de, ne = tgn.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=draws)
+        f64_here = _f64_on_step(cid, step, len(c.steps))
+        if f64_here:                                # float64 from the fp32 state BEFORE the fp32 step moves it on
+            ref64.load_state(ref)
+            e64 = ref64.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=None if odraws is None else list(odraws))
         rse, rde, rne = ref.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=odraws)
         emb = torch.cat([se, de, ne])
         got, remb = emb.detach().cpu().numpy(), np.concatenate([rse, rde, rne])
@@ -211,6 +247,7 @@ def _run_case(cid, deterministic=False):
         if last:
             launches = {k: v["count"] for k, v in _lib.prof_collect().items()}
         n_checked = 0
+        mine = {}
         for name, p in tgn.named_parameters():
             if name not in rgrads:
                 continue
@@ -220,11 +257,19 @@ def _run_case(cid, deterministic=False):
                 continue
             g_ = p.grad.cpu().numpy().astype(np.float64)
             assert np.isfinite(g_).all(), (cid, step, name)
+            mine[name] = g_
             time = name.startswith("time_encoder")
             e = note("time grad L2" if time else "grad L2", np.linalg.norm(g_ - r) / (np.linalg.norm(r) + 1e-30))
             assert e < (RTOL_GRAD_TIME if time else RTOL_GRAD_ORACLE_L2), (cid, step, name, e)
             n_checked += 1
         assert n_checked >= 2 + 8 * L, (cid, step, n_checked)
+        if f64_here:                               # beside the per-tensor bars: every block against float64, at the fp32 oracle's bar
+            g64 = _f64_backward(ref64, ref, e64, B, K, n_neg=N_NEG)
+            wb, over = check_grad_blocks(mine, rgrads, g64, D, c.Ef, c.H)
+            worst_block = max(worst_block, wb, key=lambda w: w[0])
+            if over:
+                print("BLOCKS OVER THE BAR edge %s step %d: %s" % (cid, step, "; ".join("%s[%s] %.3g e32 %.3g bar %.3g" % o for o in over)))
+            assert not over, (cid, step, over)
         if c.use_mem:
             mem = tgn.memory.memory.cpu().numpy()
             assert np.isfinite(mem).all()
@@ -240,8 +285,9 @@ def _run_case(cid, deterministic=False):
             assert np.array_equal(tgn.memory.msg_time.cpu().numpy()[has], mt[has])
         opt.step()
     tag = cid + ("-det" if deterministic else "")
-    print("FIGURES edge %s (D %d Ef %d H %d L %d K %d): %s, attn_bwd_runs %d attn_bwd %d" % (
-        tag, D, c.Ef, c.H, L, K, ", ".join("%s %.3g" % kv for kv in sorted(worst.items())), launches["attn_bwd_runs"], launches["attn_bwd"]))
+    print("FIGURES edge %s (D %d Ef %d H %d L %d K %d): %s, %s, attn_bwd_runs %d attn_bwd %d" % (
+        tag, D, c.Ef, c.H, L, K, ", ".join("%s %.3g" % kv for kv in sorted(worst.items())), fmt_worst_block(worst_block),
+        launches["attn_bwd_runs"], launches["attn_bwd"]))
     if c.run_merged:
         assert launches["attn_bwd_runs"] == 1 and launches["attn_bwd"] == L - 1, launches      # layer 1 run-merged, one launch per layer above
     else:

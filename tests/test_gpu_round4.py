@@ -128,6 +128,9 @@ def test_step_with_dropout_against_oracle(D, H, L, K, use_mem, uniform, pdrop):
             att.multi_head_target.out_proj.bias.normal_(0, 0.1)
     opt = P.FusedAdam(tgn, lr=1e-3)
     onf, names, ref = _oracle_for(tgn, g, d, L, H, use_mem, uniform)
+    from parity import check_grad_blocks, fmt_worst_block, f64_twin, _f64_backward
+    ref64 = f64_twin(ref)
+    worst_block = (0.0, None, None, 0.0, 0.0)
     rs = np.random.RandomState(6)
     B = 40
     for step in range(4):
@@ -144,12 +147,15 @@ def test_step_with_dropout_against_oracle(D, H, L, K, use_mem, uniform, pdrop):
         se, de, ne = tgn.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=draws)
         ref.dropout_masks = tgn.debug_dropout_masks()
         assert ref.dropout_masks is not None and (ref.dropout_masks[L] == 0).any()
+        ref64.load_state(ref)                       # float64 from the fp32 state and the same injected masks, before the fp32 step
+        e64 = ref64.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=None if odraws is None else list(odraws))
         rse, rde, rne = ref.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=None if odraws is None else list(odraws))
         emb = torch.cat([se, de, ne])
         remb = np.concatenate([rse, rde, rne])
         e = relerr(emb.detach().cpu().numpy(), remb)
         assert e < RTOL_EMB, (step, e)
         rgrads = _masked_bpr_backward(tgn, ref, emb, rse, rde, rne, B, K)
+        mine = {}
         for name, p in tgn.named_parameters():
             if name not in rgrads:
                 continue
@@ -160,6 +166,14 @@ def test_step_with_dropout_against_oracle(D, H, L, K, use_mem, uniform, pdrop):
             got = p.grad.cpu().numpy().astype(np.float64)
             err = np.linalg.norm(got - r) / (np.linalg.norm(r) + 1e-30)
             assert err < (RTOL_GRAD_TIME if name.startswith("time_encoder") else RTOL_GRAD_L2), (step, name, err)
+            mine[name] = got
+        # beside the per-tensor bars: every block against the float64 oracle, at the bar the fp32 oracle sets (parity.py)
+        g64 = _f64_backward(ref64, ref, e64, B, K)
+        wb, over = check_grad_blocks(mine, rgrads, g64, D, g.edge_features.shape[1], H)
+        worst_block = max(worst_block, wb, key=lambda w: w[0])
+        if over:
+            print("BLOCKS OVER THE BAR step %d: %s" % (step, "; ".join("%s[%s] %.3g e32 %.3g bar %.3g" % o for o in over)))
+        assert not over, (step, over)
         if use_mem:
             assert relerr(tgn.memory.memory.cpu().numpy(), ref.memory) < RTOL_EMB
             assert np.array_equal(tgn.memory.last_update.cpu().numpy(), ref.last_update)
@@ -167,6 +181,8 @@ def test_step_with_dropout_against_oracle(D, H, L, K, use_mem, uniform, pdrop):
             assert np.array_equal(tgn.memory.has_msg.cpu().numpy() > 0, has)
             assert relerr(tgn.memory.msg_table.cpu().numpy()[has], tab[has]) < RTOL_EMB
         opt.step()
+    print("FIGURES step_with_dropout (D %d H %d L %d K %d mem %d uniform %d p %.1f): %s" % (D, H, L, K, use_mem, uniform, pdrop,
+                                                                                          fmt_worst_block(worst_block)))
     # the masks matter: the same step replayed WITHOUT them is far outside the bar (the test would notice a no-op dropout)
     ref.dropout_masks = None
     ref.P = {k: tgn.state_dict()[k].detach().cpu().numpy().copy() for k in names}

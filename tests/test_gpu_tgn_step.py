@@ -13,7 +13,8 @@ from pfotgnrec_amd.synthetic import SyntheticConfig, make_graph
 from oracle import tgn_oracle as T
 from oracle.neighbor_finder import OracleNeighborFinder, build_adjacency
 from parity import (relerr, row_relerr, ROW_RTOL, RTOL_EMB, RTOL_GRAD_TIME, RTOL_GRAD_ORACLE_L2, KINK_THR,
-                    _near_kink_roots, _masked_bpr_backward, _legal_draws)
+                    _near_kink_roots, _masked_bpr_backward, _legal_draws, check_grad_blocks, fmt_worst_block, f64_twin,
+                    _f64_backward)
 
 DEV = "cuda:0"
 RTOL_GRAD = 5e-4     # parameter gradients (atomic accumulation order + folded projections)
@@ -195,6 +196,8 @@ def test_step_against_oracle(D, H, L, K, use_mem, uniform):
     onf = OracleNeighborFinder(*build_adjacency(d.sources, d.destinations, d.edge_idxs, d.timestamps), uniform=uniform)
     names = [k for k in tgn.state_dict() if "layer_norm" not in k and not k.startswith("memory.")]
     ref = T.OracleTGN(onf, g.node_features, g.edge_features, {k: tgn.state_dict()[k].cpu().numpy() for k in names}, L, H, use_mem)
+    ref64 = f64_twin(ref)
+    worst_block = (0.0, None, None, 0.0, 0.0)
     rs = np.random.RandomState(5)
     B = 40
     for step in range(4):
@@ -213,12 +216,15 @@ def test_step_against_oracle(D, H, L, K, use_mem, uniform):
             # positions must be < history length: reduce modulo the count on both sides via a shared helper
             draws, odraws = _legal_draws(onf, np.concatenate([sb, db, neg]), np.concatenate([tb, tb, np.repeat(tb, 3)]), K, L, draws)
         se, de, ne = tgn.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=draws)
+        ref64.load_state(ref)                       # float64 from the fp32 state BEFORE the fp32 step moves it on
+        e64 = ref64.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=None if odraws is None else list(odraws))
         rse, rde, rne = ref.compute_temporal_embeddings(sb, db, neg, tb, eb, K, draws=odraws)
         emb = torch.cat([se, de, ne])
         remb = np.concatenate([rse, rde, rne])
         assert relerr(emb.detach().cpu().numpy(), remb) < RTOL_EMB, (step, relerr(emb.detach().cpu().numpy(), remb))
         rgrads = _masked_bpr_backward(tgn, ref, emb, rse, rde, rne, B, K)
         tol, tol_time = RTOL_GRAD_ORACLE_L2, RTOL_GRAD_TIME
+        mine = {}
         for name, p in tgn.named_parameters():
             if name not in rgrads:
                 continue
@@ -229,6 +235,14 @@ def test_step_against_oracle(D, H, L, K, use_mem, uniform):
             got = p.grad.cpu().numpy().astype(np.float64)
             e = np.linalg.norm(got - r) / (np.linalg.norm(r) + 1e-30)
             assert e < (tol_time if name.startswith("time_encoder") else tol), (step, name, e)
+            mine[name] = got
+        # beside the per-tensor bars: every block against the float64 oracle, at the bar the fp32 oracle sets (parity.py)
+        g64 = _f64_backward(ref64, ref, e64, B, K)
+        wb, over = check_grad_blocks(mine, rgrads, g64, D, g.edge_features.shape[1], H)
+        worst_block = max(worst_block, wb, key=lambda w: w[0])
+        if over:
+            print("BLOCKS OVER THE BAR step %d: %s" % (step, "; ".join("%s[%s] %.3g e32 %.3g bar %.3g" % o for o in over)))
+        assert not over, (step, over)
         if use_mem:
             assert relerr(tgn.memory.memory.cpu().numpy(), ref.memory) < RTOL_EMB
             assert np.array_equal(tgn.memory.last_update.cpu().numpy(), ref.last_update)
@@ -238,6 +252,8 @@ def test_step_against_oracle(D, H, L, K, use_mem, uniform):
             assert np.array_equal(tgn.memory.msg_time.cpu().numpy()[has], mt[has])
             # layer-0 table of the touched nodes = lazily updated memory + node features (embedding_module.py:98)
         opt.step()
+    print("FIGURES step_against_oracle (D %d H %d L %d K %d mem %d %s): %s" % (
+        D, H, L, K, use_mem, "scaled" if scaled else "uniform" if uniform else "recent", fmt_worst_block(worst_block)))
 
 
 def test_eval_mode_no_grad_and_state_progression():

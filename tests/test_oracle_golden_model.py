@@ -323,3 +323,263 @@ def test_attention_layer_against_torch_at_other_widths(D, Ef, H, K):
         if k == "b_in":
             assert np.abs(grads[k][E3]).max() < 1e-5 * np.abs(ref).max() and np.abs(ref[E3]).max() < 1e-12
         assert relerr(grads[k], ref) < 1e-5, k
+
+
+# ------------------------------------------------------------------ the float64 mode of the oracle, on its own
+# tests/parity.py takes the bar for the product's gradients from the fp32 oracle's distance to the float64 oracle, so the
+# float64 mode is validated here without leaning on the fp32 one: against float64 torch autograd on the same inputs, at 1e-11.
+F64_RTOL = 1e-11
+
+
+def _t64(a, grad=False):
+    import torch
+    return torch.tensor(np.asarray(a, np.float64), requires_grad=grad)
+
+
+def _torch_attention_layer(p, x, tq, nb, ef, te, mask, H, drop):
+    """TemporalAttentionLayer from plain float64 torch ops (temporal_attention.py:34-90 with nn.MultiheadAttention written
+    out, so that a dropout multiplier can be put on the softmax weights); returns (out, leaves, parameters)."""
+    import torch
+    N, K = mask.shape
+    E = 2 * x.shape[1]
+    dh = E // H
+    w = {k: _t64(v, True) for k, v in p.items()}
+    tx, ttq, tnb, tte = _t64(x, True), _t64(tq, True), _t64(nb, True), _t64(te, True)
+    q_in = torch.cat([tx, ttq], 1)
+    key = torch.cat([tnb, _t64(ef), tte], 2)
+    inv = torch.from_numpy(mask.all(1))
+    pad = torch.from_numpy(mask.copy())
+    pad[inv, 0] = False
+    bq, bk, bv = w["b_in"][:E], w["b_in"][E:2 * E], w["b_in"][2 * E:]
+    Q = (q_in @ w["Wq"].T + bq).reshape(N, H, dh) / np.sqrt(dh)
+    Kp = (key @ w["Wk"].T + bk).reshape(N, K, H, dh)
+    Vp = (key @ w["Wv"].T + bv).reshape(N, K, H, dh)
+    s = torch.einsum("nhd,nkhd->nhk", Q, Kp).masked_fill(pad[:, None, :], float("-inf"))
+    a = torch.softmax(s, -1)
+    if drop is not None:
+        a = a * _t64(drop)
+    o = torch.einsum("nhk,nkhd->nhd", a, Vp).reshape(N, E)
+    attn = (o @ w["Wo"].T + w["bo"]).masked_fill(inv[:, None], 0.0)
+    h1 = torch.relu(torch.cat([attn, tx], 1) @ w["W1"].T + w["b1"])
+    return h1 @ w["W2"].T + w["b2"], (tx, ttq, tnb, tte), w
+
+
+def _l2rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64).reshape(np.shape(a))
+    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
+
+
+@pytest.mark.parametrize("D,Ef,H,K,pdrop", [(4, 0, 1, 3, 0.0), (4, 4, 4, 5, 0.5), (32, 4, 2, 64, 0.1), (32, 64, 1, 5, 0.0),
+                                            (172, 64, 2, 8, 0.0), (172, 4, 4, 7, 0.3), (256, 0, 4, 6, 0.1), (256, 4, 2, 6, 0.0)])
+def test_float64_attention_layer_against_torch_autograd(D, Ef, H, K, pdrop):
+    """oracle attention_forward / attention_backward with dtype=float64 against float64 torch autograd: forward, the four input
+    gradients and every parameter gradient within 1e-11, with rows that are all padding, partially masked rows, full rows, and
+    (pdrop > 0) a dropout multiplier on the softmax weights.  Without dropout the torch side is nn.MultiheadAttention itself."""
+    import torch
+    rs = np.random.RandomState(7 * D + Ef + H)
+    N, E, C = 29, 2 * D, 2 * D + Ef
+    p = {k: v.astype(np.float64) for k, v in T.layer_params(T.init_params(D, Ef, 1, seed=D + K, use_memory=False), 0).items()}
+    x, tq, go = rs.randn(N, D), rs.randn(N, D), rs.randn(N, D)
+    nb, te, ef = rs.randn(N, K, D), rs.randn(N, K, D), rs.randn(N, K, Ef)
+    n_valid = rs.randint(0, K + 1, N)
+    n_valid[:4] = (0, 0, K, 1)
+    mask = np.arange(K)[None, :] < (K - n_valid)[:, None]
+    assert mask.all(1).sum() >= 2 and (~mask).all(1).any() and (mask.any(1) & ~mask.all(1)).any()
+    drop = None
+    if pdrop > 0:
+        drop = ((rs.rand(N, H, K) >= pdrop) / (1 - pdrop)).astype(np.float32)
+        assert (drop == 0).any() and (drop > 0).any()
+    out, c = T.attention_forward(p, x, tq, nb, ef, te, mask, H, drop, dtype=np.float64)
+    assert out.dtype == np.float64 and c["z1"].dtype == np.float64
+    grads, dx, dtq, dnb, dte = T.attention_backward(p, c, go, H, D)
+    assert all(v.dtype == np.float64 for v in grads.values()) and dx.dtype == np.float64
+    want, (tx, ttq, tnb, tte), w = _torch_attention_layer(p, x, tq, nb, ef, te, mask, H, drop)
+    want.backward(_t64(go))
+    assert relerr(out, want.detach().numpy()) < F64_RTOL and row_relerr(out, want.detach().numpy()) < F64_RTOL
+    for mine, theirs, what in ((dx, tx, "dx"), (dtq, ttq, "dtq"), (dnb, tnb, "dnb"), (dte, tte, "dte")):
+        assert relerr(mine, theirs.grad.numpy()) < F64_RTOL and _l2rel(mine, theirs.grad.numpy()) < F64_RTOL, what
+    E3 = slice(E, 2 * E)                                               # the key bias: its gradient cancels in the softmax
+    for k in T._LAYER_KEYS:
+        ref = w[k].grad.numpy()
+        if k == "b_in":
+            assert np.abs(grads[k][E3]).max() < F64_RTOL * np.abs(ref).max()
+            ref = ref.copy(); ref[E3] = grads[k][E3]
+        assert relerr(grads[k], ref) < F64_RTOL and _l2rel(grads[k], ref) < F64_RTOL, k
+    if drop is None:                                                   # and the written-out torch layer is nn.MultiheadAttention's
+        mha = torch.nn.MultiheadAttention(embed_dim=E, kdim=C, vdim=C, num_heads=H).double()
+        with torch.no_grad():
+            if mha.q_proj_weight is None:
+                mha.in_proj_weight.copy_(_t64(np.concatenate([p["Wq"], p["Wk"], p["Wv"]])))
+            else:
+                for dst, src in ((mha.q_proj_weight, "Wq"), (mha.k_proj_weight, "Wk"), (mha.v_proj_weight, "Wv")):
+                    dst.copy_(_t64(p[src]))
+            for dst, src in ((mha.in_proj_bias, "b_in"), (mha.out_proj.weight, "Wo"), (mha.out_proj.bias, "bo")):
+                dst.copy_(_t64(p[src]))
+        inv = torch.from_numpy(mask.all(1))
+        pad = torch.from_numpy(mask.copy())
+        pad[inv, 0] = False
+        attn, _ = mha(query=torch.cat([_t64(x), _t64(tq)], 1).unsqueeze(0), key=torch.cat([_t64(nb), _t64(ef), _t64(te)], 2).permute(1, 0, 2),
+                      value=torch.cat([_t64(nb), _t64(ef), _t64(te)], 2).permute(1, 0, 2), key_padding_mask=pad)
+        attn = attn.squeeze(0).masked_fill(inv[:, None], 0.0)
+        h1 = torch.relu(torch.cat([attn, _t64(x)], 1) @ _t64(p["W1"]).T + _t64(p["b1"]))
+        assert relerr(out, (h1 @ _t64(p["W2"]).T + _t64(p["b2"])).detach().numpy()) < F64_RTOL
+
+
+@pytest.mark.parametrize("D,Ef", [(4, 0), (32, 4), (172, 64), (256, 4), (256, 0)])
+def test_float64_gru_cell_against_torch_autograd(D, Ef):
+    """oracle gru_cell / gru_cell_backward with dtype=float64 against torch.nn.GRUCell in float64: new memory and the four
+    parameter gradients within 1e-11 (message row 3 D + Ef wide)."""
+    import torch
+    rs = np.random.RandomState(D + Ef)
+    n, M = 23, 3 * D + Ef
+    P = T.init_params(D, Ef, 1, seed=D, use_memory=True)
+    pre = "memory_updater.memory_updater."
+    W = [P[pre + k].astype(np.float64) for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    x, h, ghn = rs.randn(n, M), rs.randn(n, D), rs.randn(n, D)
+    hn, cache = T.gru_cell(x, h, *W, dtype=np.float64)
+    assert hn.dtype == np.float64
+    g = T.gru_cell_backward(cache, ghn, W[0], W[1], dtype=np.float64)
+    cell = torch.nn.GRUCell(M, D).double()
+    with torch.no_grad():
+        for dst, src in zip((cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh), W):
+            dst.copy_(_t64(src))
+    want = cell(_t64(x), _t64(h))
+    want.backward(_t64(ghn))
+    assert relerr(hn, want.detach().numpy()) < F64_RTOL and row_relerr(hn, want.detach().numpy()) < F64_RTOL
+    for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+        ref = getattr(cell, k).grad.numpy()
+        assert g[k].dtype == np.float64 and relerr(g[k], ref) < F64_RTOL and _l2rel(g[k], ref) < F64_RTOL, k
+
+
+@pytest.mark.parametrize("D,q", [(4, 1), (32, 3), (172, 3), (256, 5)])
+def test_float64_bpr_against_torch_autograd(D, q):
+    """oracle bpr_loss / bpr_loss_backward with dtype=float64 against float64 torch autograd of main.py:321-337 (sigma of the
+    MEAN score difference): loss and the three embedding gradients within 1e-11."""
+    import torch
+    rs = np.random.RandomState(D + q)
+    B = 17
+    src, pos, neg = rs.randn(B, D) * 0.3, rs.randn(B, 1, D) * 0.3, rs.randn(B, q, D) * 0.3
+    loss, cache = T.bpr_loss(src, pos, neg, dtype=np.float64)
+    ds, dp, dn = T.bpr_loss_backward(cache)
+    assert type(loss) is np.float64 and ds.dtype == np.float64
+    ts, tp, tn = _t64(src, True), _t64(pos, True), _t64(neg, True)
+    diff = torch.einsum("bd,bpd->bp", ts, tp) - torch.einsum("bd,bqd->bq", ts, tn)
+    want = -torch.log(torch.sigmoid(diff.mean(1))).mean()
+    want.backward()
+    assert abs(loss - want.item()) < F64_RTOL * abs(want.item())
+    for mine, theirs, what in ((ds, ts, "src"), (dp, tp, "pos"), (dn, tn, "neg")):
+        assert relerr(mine, theirs.grad.numpy()) < F64_RTOL and _l2rel(mine, theirs.grad.numpy()) < F64_RTOL, what
+
+
+def test_float64_time_encoder_keeps_the_fp32_argument():
+    """The time-encoder argument is one fp32 FMA in both modes (a contract rounding, not evaluation noise): the float64 mode is
+    the float64 cosine / sine of exactly that fp32 argument, and its gradients are float64 sums of float64 terms."""
+    rs = np.random.RandomState(3)
+    D = 32
+    t = (rs.rand(200) * 1e7).astype(np.float32)
+    w = (1 / 10 ** np.linspace(0, 9, D)).astype(np.float32)
+    b = (rs.randn(D) * 0.3).astype(np.float32)
+    arg = T.fmaf(t[:, None], w, b)
+    assert arg.dtype == np.float32
+    y = T.time_encode(t, w, b, dtype=np.float64)
+    assert y.dtype == np.float64 and np.array_equal(y, np.cos(arg.astype(np.float64)))
+    assert np.abs(y - T.time_encode(t, w, b)).max() < 5e-7            # the fp32 mode: cosf of the same argument
+    g = rs.randn(200, D)
+    gw, gb = T.time_encode_backward(t, w, b, g, dtype=np.float64)
+    s = -np.sin(arg.astype(np.float64)) * g
+    assert gw.dtype == np.float64 and np.allclose(gw, (s * t[:, None].astype(np.float64)).sum(0), rtol=1e-13, atol=0)
+    assert np.allclose(gb, s.sum(0), rtol=1e-13, atol=1e-300)
+
+
+# ------------------------------------------------------------------ what the per-tensor bar lets through and the block bar does not
+_SENS = {}
+
+
+def _sensitivity_grads(which):
+    """(fp32 oracle gradients, float64 oracle gradients, D, Ef, H) of one training step with the near-kink roots left out on
+    both sides, computed once per session.  "f": the last step of case f of test_gpu_config_edges (D 172, Ef 64, H 2).
+    "scaled": the shape and graph of the "scaled" row of test_step_against_oracle (D 172, H 2, L 2, K 8, memory) on the oracle's
+    own initialiser, with the weight blocks moved 2^9-2^10 apart by that row's factors; third step, so the GRU has messages."""
+    if which in _SENS:
+        return _SENS[which]
+    from parity import _near_kink_roots, f64_twin, _f64_backward
+    if which == "f":
+        import test_gpu_config_edges as CE
+        c = CE._Inputs("f")
+        ref, D, Ef, H, K, B, n_neg = c.oracle(), c.D, c.Ef, c.H, c.K, c.B, CE.N_NEG
+        steps = [(sb, db, tb, eb, neg) for sb, db, tb, eb, neg, _ in c.steps]
+    else:
+        from pfotgnrec_amd.synthetic import SyntheticConfig, make_graph
+        D, Ef, H, L, K, B, n_neg = 172, 4, 2, 2, 8, 40, 3
+        cfg = SyntheticConfig("t", 300, 25, 5000, D, L, K, H)
+        g = make_graph(cfg, with_prices=False)
+        d = g.data
+        P = T.init_params(D, Ef, L, seed=3)
+        P["memory_updater.memory_updater.weight_ih"] *= np.float32(2.0 ** 3)
+        P["memory_updater.memory_updater.weight_hh"] *= np.float32(2.0 ** -6)
+        for l in range(L):
+            pre = "embedding_module.attention_models.%d." % l
+            P[pre + "merger.fc1.weight"][:, :2 * D] *= np.float32(2.0 ** 2)
+            P[pre + "merger.fc1.weight"][:, 2 * D:] *= np.float32(2.0 ** -8)
+            P[pre + "merger.fc2.weight"] *= np.float32(2.0 ** -4)
+            P[pre + "multi_head_target.q_proj_weight"] *= np.float32(2.0 ** 2)
+        onf = OracleNeighborFinder(*build_adjacency(d.sources, d.destinations, d.edge_idxs, d.timestamps))
+        ref = T.OracleTGN(onf, g.node_features, g.edge_features, P, L, H, True)
+        rs = np.random.RandomState(5)
+        steps = []
+        for s in (2500, 2540, 2580):
+            steps.append((d.sources[s:s + B], d.destinations[s:s + B], d.timestamps[s:s + B], d.edge_idxs[s:s + B],
+                          rs.randint(cfg.n_users + 1, cfg.n_users + cfg.n_items + 1, size=B * n_neg)))
+    ref64 = f64_twin(ref)
+    for i, (sb, db, tb, eb, neg) in enumerate(steps):
+        if i == len(steps) - 1:
+            ref64.load_state(ref)
+            e64 = ref64.compute_temporal_embeddings(sb, db, neg, tb, eb, K)
+        rse, rde, rne = ref.compute_temporal_embeddings(sb, db, neg, tb, eb, K)
+    _, cache = T.bpr_loss(rse, rde.reshape(B, 1, -1), rne.reshape(B, n_neg, -1))
+    W = np.concatenate([a.reshape(-1, D) for a in T.bpr_loss_backward(cache)])
+    bad = _near_kink_roots(ref._ctx, len(W), K)
+    assert bad.mean() <= 0.10
+    W[bad] = 0
+    g32 = ref.backward(W)
+    g64 = _f64_backward(ref64, ref, e64, B, K, n_neg=n_neg)
+    _SENS[which] = (g32, g64, D, Ef, H)
+    return _SENS[which]
+
+
+# which step, tensor, and what is done to that tensor's fp32-oracle gradient.  Each stands for one way a block goes wrong: a
+# block a fraction of a per cent off, a small block entirely wrong, a gate block off by a quarter.  (Zeroing fc1's node half
+# and swapping b_hh's r and z rows were tried first: they move the whole tensor by 0.19 and 0.64 and the per-tensor bar
+# catches them, so they show nothing about it.  The blocks below are the small ones of their tensors: W_ih's r-gate edge
+# columns hold 0.0017 of its gradient norm in the "scaled" step and b_hh's r third 0.0115.)
+CORRUPTIONS = {
+    # (half a per cent: at Ef = 64 the edge columns hold 0.72 of Wk's gradient norm, and a whole per cent on them is 7.2e-3 of the tensor)
+    "Wk Ef columns x 1.005": ("f", "embedding_module.attention_models.1.multi_head_target.k_proj_weight",
+                              lambda g, D, Ef: g.__setitem__((slice(None), slice(D, D + Ef)), g[:, D:D + Ef] * np.float32(1.005))),
+    "W_ih r-gate Ef block zeroed (scaled)": ("scaled", "memory_updater.memory_updater.weight_ih",
+                                             lambda g, D, Ef: g.__setitem__((slice(0, D), slice(2 * D, 2 * D + Ef)), 0)),
+    "b_hh r third x 1.25 (scaled)": ("scaled", "memory_updater.memory_updater.bias_hh",
+                                     lambda g, D, Ef: g.__setitem__(slice(0, D), g[:D] * np.float32(1.25))),
+}
+
+
+@pytest.mark.parametrize("what", sorted(CORRUPTIONS))
+def test_block_bar_catches_what_the_tensor_bar_lets_through(what):
+    """One block of the fp32 oracle's own gradient is corrupted; every other element keeps the oracle's value.  The per-tensor
+    relative L2 against the float64 oracle stays under 5e-3 (the old measure passes the corrupted tensor), the block measure
+    puts that block over GRAD_MARGIN x e32 - and the uncorrupted tensor passes both."""
+    from parity import RTOL_GRAD_ORACLE_L2, check_grad_blocks
+    which, name, corrupt = CORRUPTIONS[what]
+    g32, g64, D, Ef, H = _sensitivity_grads(which)
+    clean = {name: g32[name].astype(np.float64)}
+    _, over = check_grad_blocks(clean, g32, g64, D, Ef, H)
+    assert not over, over
+    g = g32[name].copy()
+    corrupt(g, D, Ef)
+    assert not np.array_equal(g, g32[name])
+    tensor_err = np.linalg.norm(g.astype(np.float64) - g64[name]) / np.linalg.norm(g64[name])
+    assert tensor_err < RTOL_GRAD_ORACLE_L2, (what, tensor_err)           # the old per-tensor bar lets it through
+    worst, over = check_grad_blocks({name: g.astype(np.float64)}, g32, g64, D, Ef, H)
+    assert over and worst[0] > 1, (what, worst)                            # the block bar does not
+    print("%s: tensor L2 %.3g (bar %.3g); %d block(s) over, worst %s[%s] %.3g = %.3g x its bar" % (
+        what, tensor_err, RTOL_GRAD_ORACLE_L2, len(over), worst[1], worst[2], worst[3], worst[0]))
