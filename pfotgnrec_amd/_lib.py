@@ -206,6 +206,15 @@ def call(name, *args):
         raise PfoError("%s failed (%d): %s" % (name, rc, lib.pfo_last_error().decode()))
 
 
+def byte_count(name, *args):
+    """A ``*_bytes`` query of the library: the count it returns, or ``PfoError`` with its message when that is negative."""
+    lib = load()
+    n = getattr(lib, name)(*args)
+    if n < 0:
+        raise PfoError("%s: %s" % (name, lib.pfo_last_error().decode()))
+    return n
+
+
 _GPU_SEEN = [False]
 
 

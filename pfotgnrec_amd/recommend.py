@@ -1,0 +1,162 @@
+"""Read-only top-k recommendation behind ``TGN.recommend``: ``validate`` checks the arguments on the host alone (no device is
+asked for), ``assemble`` embeds users and candidates on the device and lets ``pfo_recommend_topk`` score and select."""
+import collections
+import operator
+
+import numpy as np
+import torch
+
+from . import _lib
+
+Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len")
+
+
+def _host(a):
+    return None if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _int_vector(a, what, n_nodes):
+    h = _host(a)
+    t = a if h is None else h
+    if t.ndim != 1 or (h is not None and h.size and h.dtype.kind not in "iu") or (
+            h is None and (t.dtype.is_floating_point or t.dtype == torch.bool)):
+        raise ValueError("%s must be a 1-D array of integer node ids" % what)
+    if h is not None and h.size and (int(h.min()) < 0 or int(h.max()) >= n_nodes):
+        raise ValueError("%s holds node ids outside [0, %d)" % (what, n_nodes))
+    return h
+
+
+def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors):
+    """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
+    not read back, except ``items`` once."""
+    try:
+        k = operator.index(k)
+    except TypeError:
+        raise ValueError("k must be an integer") from None
+    if not 1 <= k <= 64:
+        raise ValueError("k must be in [1, 64] (got %d)" % k)
+    users_h = _int_vector(users, "users", n_nodes)
+    U = int(users.shape[0]) if users_h is None else int(users_h.shape[0])
+    items_h = _int_vector(items.detach().cpu().numpy() if isinstance(items, torch.Tensor) else items, "items", n_nodes)
+    I = int(items_h.shape[0])
+    if I < 1 or I > _lib.RECOMMEND_MAX_ITEMS:
+        raise ValueError("items must hold between 1 and %d candidates (got %d)" % (_lib.RECOMMEND_MAX_ITEMS, I))
+    if (items_h == 0).any():
+        raise ValueError("items holds node 0 (the padding node)")
+    if np.unique(items_h).shape[0] != I:
+        raise ValueError("items holds duplicates")
+    ts_h = _host(timestamps)
+    ts_any = timestamps if ts_h is None else ts_h
+    scalar_ts = ts_any.ndim == 0
+    if not scalar_ts and tuple(ts_any.shape) != (U,):
+        raise ValueError("timestamps must be a scalar or hold one value per user (%d), got shape %s" % (U, tuple(ts_any.shape)))
+    if ts_h is not None and ts_h.dtype.kind not in "fiu":
+        raise ValueError("timestamps must be numbers")
+    ok_h = None
+    if item_ok is not None:
+        ok_any = item_ok if isinstance(item_ok, torch.Tensor) else np.asarray(item_ok)
+        if tuple(ok_any.shape) != (I,):
+            raise ValueError("item_ok must hold one flag per candidate (%d), got shape %s" % (I, tuple(ok_any.shape)))
+        ok_h = _host(item_ok)
+    ex_ids = ex_len = None
+    if exclude is not None:
+        packed = (isinstance(exclude, (tuple, list)) and len(exclude) == 2
+                  and isinstance(exclude[0], (torch.Tensor, np.ndarray)) and exclude[0].ndim == 2)
+        if packed:
+            ex_ids, ex_len = exclude
+            if not isinstance(ex_len, (torch.Tensor, np.ndarray)):
+                ex_len = np.asarray(ex_len)
+            if ex_ids.shape[0] != U or tuple(ex_len.shape) != (U,):
+                raise ValueError("packed exclude must be (ids [U,W], lens [U]) with U = %d" % U)
+            for t, what in ((ex_ids, "ids"), (ex_len, "lens")):
+                kind_ok = (t.dtype.kind in "iu") if isinstance(t, np.ndarray) else not (t.dtype.is_floating_point or t.dtype == torch.bool)
+                if not kind_ok:
+                    raise ValueError("packed exclude %s must be integers" % what)
+        else:
+            try:
+                rows = [np.asarray(list(r), np.int64).reshape(-1) for r in exclude]
+            except (TypeError, ValueError):
+                raise ValueError("exclude must be None, a list of per-user lists of item ids or a packed (ids, lens) pair") from None
+            if len(rows) != U:
+                raise ValueError("exclude lists %d users, users holds %d" % (len(rows), U))
+            W = max([len(r) for r in rows], default=0)
+            ex_ids = np.full((U, W), -1, np.int32)
+            ex_len = np.zeros(U, np.int32)
+            for i, r in enumerate(rows):
+                if r.size and (int(r.min()) < -(1 << 31) or int(r.max()) >= (1 << 31)):
+                    raise ValueError("exclude holds ids that do not fit 32 bits")
+                ex_ids[i, :len(r)] = r
+                ex_len[i] = len(r)
+    if n_neighbors is None:
+        n_neighbors = 20 if default_neighbors is None else default_neighbors
+    return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len)
+
+
+def assemble(tgn, q, return_embeddings=False):
+    """The device side of ``TGN.recommend`` for a validated query: every (item, distinct timestamp) pair is embedded once (the
+    grid of ``TGN._dedup_roots``), users and grid go through ``TGN._embed_readonly``, ``recommend_topk`` scores and selects."""
+    from .functional import recommend_topk
+    dev, k, U, I = tgn.device, q.k, q.U, q.I
+
+    def to_dev(a, dtype):
+        if isinstance(a, torch.Tensor):
+            return a.to(device=dev, dtype=dtype).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a).astype(str(dtype).replace("torch.", ""), copy=False)).to(dev)
+
+    with torch.no_grad():
+        users_d = to_dev(q.users if q.users_h is None else q.users_h, torch.int32)
+        items_d = to_dev(q.items_h, torch.int32)
+        user_block = None
+        if q.scalar_ts:
+            grid_t = to_dev(q.timestamps.reshape(1), torch.float64)
+            user_ts = grid_t.expand(U)
+        elif q.ts_h is not None:
+            uniq, inv = np.unique(q.ts_h.astype(np.float64), return_inverse=True)
+            grid_t, user_ts = to_dev(uniq, torch.float64), to_dev(q.ts_h, torch.float64)
+            user_block = to_dev(inv.reshape(-1), torch.int32)
+        else:
+            user_ts = to_dev(q.timestamps, torch.float64)
+            grid_t, inv = torch.unique(user_ts, return_inverse=True)
+            user_block = inv.to(torch.int32)
+        n_t = max(1, int(grid_t.shape[0]))
+        if U == 0:
+            grid_t, n_t = grid_t[:0], 1
+        roots = torch.cat([users_d, items_d.repeat(int(grid_t.shape[0]))]).contiguous()
+        root_ts = torch.cat([user_ts, grid_t.repeat_interleave(I)]).contiguous()
+        emb = tgn._embed_readonly(roots, root_ts, q.K) if roots.shape[0] else torch.empty((0, tgn.n_node_features), dtype=torch.float32, device=dev)
+        user_emb, item_emb = emb[:U], emb[U:]
+        if U == 0:
+            empty = lambda dt: torch.empty((0, k), dtype=dt, device=dev)
+            out = (empty(torch.int32), empty(torch.float32), torch.empty(0, dtype=torch.int32, device=dev))
+            if return_embeddings:
+                out += (user_emb, item_emb, torch.empty(0, dtype=torch.int32, device=dev))
+            return out
+        excl_pos = excl_len = None
+        if q.ex_ids is not None and q.ex_ids.shape[1] > 0:
+            # node id -> position in ``items`` through a table over the node ids (-1: not a candidate)
+            pos_of = torch.full((tgn.n_nodes,), -1, dtype=torch.int32, device=dev)
+            pos_of[items_d.long()] = torch.arange(I, dtype=torch.int32, device=dev)
+            ids = to_dev(q.ex_ids, torch.int64)
+            inside = (ids >= 0) & (ids < tgn.n_nodes)
+            excl_pos = torch.where(inside, pos_of[ids.clamp(0, tgn.n_nodes - 1)], torch.full_like(ids, -1, dtype=torch.int32))
+            excl_pos = excl_pos.contiguous()
+            excl_len = to_dev(q.ex_len, torch.int32)
+        ok_d = None
+        if q.item_ok is not None:
+            ok_d = (to_dev(q.item_ok if q.ok_h is None else q.ok_h, torch.int64) != 0).to(torch.uint8)
+        if user_block is not None and n_t > 1:
+            # users of one block side by side: the kernel serves a tile of 16 users in one pass per distinct block
+            order = torch.argsort(user_block, stable=True)
+            sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
+            res = recommend_topk(sel(user_emb), item_emb, k, sel(user_block), sel(excl_pos), sel(excl_len), ok_d, n_blocks=n_t)
+            res = tuple(torch.empty_like(t).index_copy_(0, order, t) for t in res)
+        else:
+            res = recommend_topk(user_emb, item_emb, k, user_block if n_t > 1 else None, excl_pos, excl_len, ok_d, n_blocks=n_t)
+        top_pos, top_score, n_valid = res
+        item_ids = torch.where(top_pos >= 0, items_d[top_pos.clamp(min=0).long()], torch.full_like(top_pos, -1))
+        out = (item_ids, top_score, n_valid)
+        if return_embeddings:
+            if user_block is None:
+                user_block = torch.zeros(U, dtype=torch.int32, device=dev)
+            out += (user_emb, item_emb, user_block)
+        return out

@@ -12,6 +12,7 @@ Supported (what the training path of main.py:106-121 selects): ``embedding_modul
 ``memory_updater_type = "gru"``, ``use_memory`` True (TGN / ours) or False (TGAT, main.py:70-74).
 Other enum values raise ``ValueError`` like the reference's factories do for unknown names.
 """
+import contextlib
 import ctypes
 import os
 import math
@@ -41,11 +42,20 @@ class _Call:
     __slots__ = ("roots", "root_ts", "R", "K", "mode", "draws", "draw_ptrs", "keep_ptrs", "seed", "offset", "dropout_p", "training",
                  "extra", "batch_struct", "ws", "ws_caps", "cfg", "pool", "gru_applied", "ready", "keep", "pkey", "__weakref__")
 
+    def __init__(self):
+        self.roots = self.root_ts = self.draws = self.draw_ptrs = self.keep_ptrs = self.extra = None
+        self.R = self.K = self.mode = self.seed = self.offset = self.training = 0
+        self.dropout_p = 0.0
+        self.batch_struct = self.ws = self.ws_caps = self.cfg = self.pool = None
+        self.gru_applied = True
+        self.ready = None         # event behind ``pfo_tgn_prepare`` (a call prepared ahead of time)
+        self.pkey = None          # ``_param_key`` of the forward, when it read the parameter cache
+        self.keep = []            # whatever the native calls read by address and nothing else holds
+
     def release(self):
         """Hands the call's workspace back to its TGN's pool (after the backward, or when the graph is dropped)."""
-        ws, pool = getattr(self, "ws", None), getattr(self, "pool", None)
-        if ws is not None and pool is not None:
-            pool.append((self.ws_caps, ws))
+        if self.ws is not None and self.pool is not None:
+            self.pool.append((self.ws_caps, self.ws))
         self.ws = None
 
     def __del__(self):
@@ -147,15 +157,11 @@ class TGN(nn.Module):
         self._layout = _lib.TgnLayout()
         _lib.call("pfo_tgn_param_layout", ctypes.byref(self._cfg), ctypes.byref(self._layout))
         self._flat = torch.zeros(self._layout.total, dtype=torch.float32, device=self.device)
-        self._flat_grad = None
         self._views = []          # (parameter, offset, numel, shape)
-        self._adj_cache = None
+        self._module_list = None  # train(): the submodules, walked once
         self.dp_grad_scale = 1.0
-        self._ws_pool = []        # free workspaces: [(caps, tensor)]
-        self._side_stream = None
-        self._prefetched, self._pre_stream, self._pre_main = None, None, None
-        self.fuse_state_update = os.environ.get("PFO_FUSE_STATE", "1") != "0"      # training calls: persist + message store inside the native forward, on its side stream
         self._ws_caps = (0, 0, 0)
+        self._reset_device_state()
         # Parameter cache (pfo_tgn_state.pcache): composite weights + fp16 weight images, rebuilt only when the parameters
         # changed.  "Changed" = the torch version counters of the flat buffer AND of every nn.Parameter (in-place ops of any
         # torch optimizer, load_state_dict, copy_ ... bump them; after a real device move the parameters keep counters of their
@@ -166,27 +172,22 @@ class TGN(nn.Module):
         # the next forward.  Off by default: measured at C2, 1.461 ms per step with, 1.454 without - the ~15 launches are hidden
         # beside the sampling / GRU phase either way, and the refresh adds two event waits and moves the GRU's image launch
         self.refresh_after_step = os.environ.get("PFO_PCACHE_REFRESH", "0") != "0"
-        self._pcache, self._pcache_key, self._param_epoch = None, None, 0
-        self._last_ws = None      # (config, workspace) of the newest forward (debug_touched)
+        self._param_epoch = 0
         self._step = 0
         self.seed = 0
         self.dp_rank, self.dp_world = 0, 1
         self.deterministic = False        # bitwise run-to-run reproducible backward (pfo_tgn_batch.deterministic), ~4 % slower
         self.dp_bucketed = False          # ask the backward for the "top layer's gradients are final" event (two-bucket all-reduce)
         self.dp_ordered = False           # fused step: reduce + optimizer step per bucket, first-use bucket first (distributed.allreduce_flat_grad_ordered)
-        self._comm_pending = None         # the communication stream the top block's all-reduce of this step is in flight on
-        self._bucket_event, self._bucket_event_fresh, self._grad_split = None, False, None
-        self._mid_event, self._mid_event_fresh = None, False   # recorded by the native backward in front of layer 1's attention backward
-        self.seg_in_forward_dp = os.environ.get("PFO_SEG_FWD_DP", "1") != "0"   # ... also on a data-parallel rank (A/B switch; emulated rank 0 of 8: 1.4465 -> 1.439 ms)
-        self.seg_in_forward = os.environ.get("PFO_SEG_FWD", "1") != "0"      # the backward's instance groups are built beside the forward's layer 1
-        self.record_mid_event = False     # ... only on request: an event record on the caller's stream costs the step a launch gap
+        self._grad_split = None
+        self.record_mid_event = False     # (the mid event) only on request: an event record on the caller's stream costs the step a launch gap
         self.mid_event_late = False       # record it behind the attention backward instead of in front of it
         self._zero_next = False
         self._grad_zeroed = False         # the optimizer's kernel cleared the flat gradient buffer (FusedAdam(zero_grads_in_step=True))
         # FusedAdam(tgn, overlap_backward=True): loss.backward() leaves the native backward - and optimizer.step() its kernel - on
         # a stream of their own, so that the loop's per-batch ``loss.item()`` (main.py:390) waits for the forward only
         self.overlap_backward = False
-        self._bwd_stream, self._bwd_event, self._bwd_hold, self._bwd_joined, self._bwd_home = None, None, [], set(), None
+        self._bwd_event, self._bwd_hold, self._bwd_joined, self._bwd_home = None, [], set(), None
         self.eval_chunk_roots = 16384     # roots per forward-only pass (evaluation.py scores B*(2+N_ITEMS) roots per batch)
         self.eval_dedup = True            # forward-only passes embed every distinct (node, time) root once
         # memory_updater.py:25,41 assert that no pending message is older than its node's last update; the check reads
@@ -241,6 +242,23 @@ class TGN(nn.Module):
             self.embedding_module.attention_models.append(att)
         self.reset_parameters()
 
+    def _reset_device_state(self):
+        """Everything that belongs to one device and one flat buffer, at its initial value: ``__init__`` starts from it and
+        ``_apply`` (a device move / cast) returns to it, so that nothing of the old buffer outlives the move."""
+        self._flat_grad = None
+        self._grad_views = None           # (flat gradient buffer, its per-parameter views): made once per buffer
+        self._seen_versions = None        # ``_torch_versions`` at the newest native forward
+        self._adj_cache, self._keepalive = None, None     # the device CSR / the arrays the newest state struct points into
+        self._ws_pool = []                # free workspaces: [(caps, tensor)]
+        self._last_ws, self._last_call = None, None       # newest forward: (config, workspace) / (seed, offset, R, K, p, offset on device)
+        self._pcache, self._pcache_key = None, None
+        self._prefetched = None           # (batch key, dropout_p, call) of ``prefetch``
+        self._stage_ring, self._stage_next = [None, None], -1     # ``_batch_to_dev``: (pinned buffer, its numpy view, event) twice
+        self._side_stream, self._pre_stream, self._pre_main, self._bwd_stream = None, None, None, None
+        self._comm_pending = None         # the communication stream the top block's all-reduce of this step is in flight on
+        self._bucket_event, self._bucket_event_fresh = None, False
+        self._mid_event, self._mid_event_fresh = None, False   # recorded by the native backward in front of layer 1's attention backward
+
     # ------------------------------------------------------------------ parameters
     def _register(self, module, name, offset, shape):
         n = int(np.prod(shape))
@@ -289,8 +307,6 @@ class TGN(nn.Module):
         if new_flat.dtype != torch.float32:
             raise TypeError("the native path is fp32 only (1e-4 parity bar)")
         self._flat = new_flat.contiguous()
-        self._flat_grad = None
-        self._side_stream = None
         for p, off, n, shape in self._views:
             p.data = self._flat[off:off + n].view(shape)
             p.grad = None
@@ -307,9 +323,7 @@ class TGN(nn.Module):
         self.device = self._flat.device
         if self._prefetched is not None and self._prefetched[2].ws is not None and self._prefetched[2].ws.is_cuda:
             torch.cuda.current_stream(self._prefetched[2].ws.device).wait_event(self._prefetched[2].ready)
-        self._ws_pool, self._last_ws, self._adj_cache = [], None, None
-        self._prefetched = None
-        self._pcache, self._pcache_key = None, None
+        self._reset_device_state()
         return self
 
     # ------------------------------------------------------------------ neighbour finder plumbing
@@ -351,19 +365,19 @@ class TGN(nn.Module):
             self._ws_pool[:] = [e for e in self._ws_pool if e[0] == caps]   # smaller buffers are not worth keeping (in place:
                                                                             # outstanding calls hand theirs back to this list)
             cfg = self._cfg_for(caps)
-            nbytes = _lib.load().pfo_tgn_workspace_bytes(ctypes.byref(cfg))
-            if nbytes < 0:
-                raise _lib.PfoError("pfo_tgn_workspace_bytes: %s" % _lib.load().pfo_last_error().decode())
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            ws = torch.empty(_lib.byte_count("pfo_tgn_workspace_bytes", ctypes.byref(cfg)), dtype=torch.uint8, device=self.device)
         return caps, self._cfg_for(caps), ws
 
     def _cfg_for(self, caps):
         c = self._cfg
         return _lib.TgnConfig(c.n_nodes, c.n_edges_p1, c.D, c.Ef, c.n_layers, c.n_heads, c.use_memory, caps[0], caps[1], caps[2])
 
-    def _param_key(self):
+    def _torch_versions(self):
         # every parameter's own counter too: after .to(device) / .float() they no longer share the flat buffer's
-        return (self._flat._version, sum(v[0]._version for v in self._views), self._param_epoch, self._flat.data_ptr())
+        return (self._flat._version, sum(v[0]._version for v in self._views))
+
+    def _param_key(self):
+        return self._torch_versions() + (self._param_epoch, self._flat.data_ptr())
 
     def parameters_changed(self, refresh=False):
         """Tells the model that something outside torch's view wrote the parameters (a native optimizer kernel, a graph replay,
@@ -388,9 +402,7 @@ class TGN(nn.Module):
         pc, valid = None, 0
         if self.param_cache and self._flat.is_cuda:
             if self._pcache is None:
-                nbytes = _lib.load().pfo_tgn_pcache_bytes(ctypes.byref(self._cfg))
-                if nbytes < 0:
-                    raise _lib.PfoError("pfo_tgn_pcache_bytes: %s" % _lib.load().pfo_last_error().decode())
+                nbytes = _lib.byte_count("pfo_tgn_pcache_bytes", ctypes.byref(self._cfg))
                 self._pcache, self._pcache_key = torch.zeros(nbytes, dtype=torch.uint8, device=self.device), None   # (zeroed ONCE: include/pfotgn.h)
             pc = self._pcache.data_ptr()
             # (a step being captured into a HIP graph always builds: its replays run with whatever the parameters are then)
@@ -441,7 +453,6 @@ class TGN(nn.Module):
         uniform = bool(getattr(self.neighbor_finder, "uniform", False))
         c.mode = 0 if not uniform else (1 if draws is not None else 2)
         c.draws = draws
-        c.draw_ptrs = None
         if draws is not None:
             if len(draws) != self.n_layers:
                 raise ValueError("uniform mode with injected draws needs one index tensor per layer")
@@ -462,7 +473,6 @@ class TGN(nn.Module):
                                        int(extra.shape[0]) if extra is not None else 0,
                                        offset_dev.data_ptr() if offset_dev is not None else None,
                                        1 if self.deterministic else 0)
-        c.keep_ptrs = None
         if dropout_keep is not None:
             # injected dropout decisions (parity tests): one u8 [n_l, K] tensor per layer, the roots' level first (like draws)
             if len(dropout_keep) != self.n_layers:
@@ -472,16 +482,13 @@ class TGN(nn.Module):
                 if t.dtype != torch.uint8 or tuple(t.shape) != (n, c.K) or not t.is_contiguous():
                     raise ValueError("dropout_keep tensors must be contiguous uint8 [n_l, K] in level order (roots first)")
                 n *= 1 + c.K
-            c.keep = (getattr(c, "keep", None), dropout_keep)
+            c.keep.append(dropout_keep)
             c.keep_ptrs = (ctypes.c_void_p * self.n_layers)(*[t.data_ptr() for t in dropout_keep])
             c.batch_struct.dropout_keep = ctypes.cast(c.keep_ptrs, ctypes.POINTER(ctypes.c_void_p))
         c.pool = self._ws_pool
         c.ws_caps, c.cfg, c.ws = self._acquire_workspace(c.R, c.K, B)
         c.gru_applied = self._gru_applied_now
         return c
-
-    def _torch_versions(self):
-        return (self._flat._version, sum(v[0]._version for v in self._views))
 
     def _native_forward(self, call, out=None):
         _lib.require_gpu(self.device)
@@ -490,7 +497,7 @@ class TGN(nn.Module):
         # that write is ordered against nothing the library left on its side stream, and the forward would not fork from
         # the caller's stream while a deferred step is pending there - join first (a no-op when nothing is pending)
         tv = self._torch_versions()
-        if tv != getattr(self, "_seen_versions", None):
+        if tv != self._seen_versions:
             self._seen_versions = tv
             if not torch.cuda.is_current_stream_capturing():
                 self.join()
@@ -504,8 +511,6 @@ class TGN(nn.Module):
             elif not st.pcache_valid:
                 self._pcache_key = self._param_key()               # this call built the cache for the current parameters
             call.pkey = self._param_key()
-        else:
-            call.pkey = None
         self._last_ws = (call.cfg, call.ws)
         self._last_call = (int(call.seed), int(call.batch_struct.offset), int(call.R), int(call.K), float(call.dropout_p),
                            call.batch_struct.offset_dev is not None)
@@ -521,11 +526,11 @@ class TGN(nn.Module):
         backward (which does it on its side stream, off the critical path)."""
         if self._flat_grad is None:
             self._flat_grad = torch.zeros_like(self._flat)
-        gv = self.__dict__.get("_grad_views")
+        gv = self._grad_views
         if gv is None or gv[0] is not self._flat_grad:
             # the views are made once per buffer: main.py's optimizer.zero_grad() drops every .grad in front of every batch, and
             # slicing + reshaping ~50 views again was 70 us of host time per batch in front of the native backward
-            gv = self.__dict__["_grad_views"] = (self._flat_grad, [self._flat_grad[off:off + n].view(shape) for _, off, n, shape in self._views])
+            gv = self._grad_views = (self._flat_grad, [self._flat_grad[off:off + n].view(shape) for _, off, n, shape in self._views])
         missing = [i for i, v in enumerate(self._views) if v[0].grad is None]
         deferred = False
         if len(missing) == len(self._views):
@@ -605,7 +610,7 @@ class TGN(nn.Module):
             self._native_backward(call, d_emb)
             ev = torch.cuda.Event()
             ev.record(side)
-        self._bwd_hold.append((d_emb, call.roots, call.root_ts, call.extra, getattr(call, "keep", None), call.draws))
+        self._bwd_hold.append((d_emb, call.roots, call.root_ts, call.extra, call.keep, call.draws))
         self._bwd_home = cur.cuda_stream
         self._set_backward_event(ev)
 
@@ -630,7 +635,7 @@ class TGN(nn.Module):
             zero_first = False
         self._grad_zeroed = False         # this backward accumulates into it
         st = self._state_struct()
-        pkey = getattr(call, "pkey", None)
+        pkey = call.pkey
         if pkey is not None and not torch.cuda.is_current_stream_capturing() and pkey != self._param_key():
             # the composites the backward reads (parameter cache) belong to the parameters of the forward
             raise RuntimeError("the parameters were modified between a TGN forward and its backward "
@@ -638,15 +643,11 @@ class TGN(nn.Module):
         ev = None
         if self.dp_bucketed and self.grad_split < self._layout.total:
             # the top layer's gradient block is final when this event fires (distributed.allreduce_flat_grad_buckets)
-            if self._bucket_event is None:
-                self._bucket_event = torch.cuda.Event()
-                self._bucket_event.record()                       # materialises the underlying hipEvent_t
+            self._bucket_event = self._bucket_event or self._recorded_event()
             ev = self._bucket_event.cuda_event
             self._bucket_event_fresh = True
         if self.record_mid_event and not torch.cuda.is_current_stream_capturing():
-            if self._mid_event is None:
-                self._mid_event = torch.cuda.Event()
-                self._mid_event.record()                          # materialises the underlying hipEvent_t
+            self._mid_event = self._mid_event or self._recorded_event()
             call.batch_struct.mid_event = self._mid_event.cuda_event
             call.batch_struct.mid_event_late = 1 if self.mid_event_late else 0
             self._mid_event_fresh = True
@@ -655,6 +656,12 @@ class TGN(nn.Module):
                   call.ws.data_ptr(), d_emb.data_ptr(), self._flat_grad.data_ptr(), 1 if zero_first else 0, ev,
                   mean[0].data_ptr() if mean else None, int(mean[0].shape[0]) if mean else 0,
                   mean[1].data_ptr() if mean else None, _lib.stream_ptr())
+
+    @staticmethod
+    def _recorded_event():
+        ev = torch.cuda.Event()
+        ev.record()                                               # on the current stream (materialises the underlying hipEvent_t)
+        return ev
 
     def request_zero_grad(self):
         """``optimizer.zero_grad()`` without a launch of its own: the NEXT native backward clears the flat gradient buffer
@@ -695,14 +702,36 @@ class TGN(nn.Module):
                   roots.data_ptr(), root_ts.data_ptr(), _lib.stream_ptr())
         return roots, root_ts
 
+    def _batch_plan(self, src, dst, extra_roots, extra_repeat, with_extra=True):
+        """What ``prefetch`` and ``embed_device`` must agree on for one batch: ``(B, lo, hi, b, groups, R, extra, dropout_p)``.
+
+        This rank embeds interactions [lo, hi) = [rank*B//world, (rank+1)*B//world) of the B given (b of them, 0 when B < world).
+        roots = [src | dst | extra groups] (tgn.py:123-124 / 238-239): ``groups`` = [(nodes, repeat)] without the groups of zero
+        nodes per interaction (e.g. no negatives), R = b * (2 + repeats).  ``extra``: the whole batch's nodes on a data-parallel
+        rank with memory; ``with_extra=False`` leaves that concatenation out.  Dropout follows train()/eval(), not autograd."""
+        B = int(src.shape[0])
+        lo, hi = 0, B
+        if self.dp_world > 1:
+            lo, hi = self.dp_rank * B // self.dp_world, (self.dp_rank + 1) * B // self.dp_world
+        b = hi - lo
+        groups = [(t.contiguous(), int(r)) for t, r in zip(extra_roots, extra_repeat) if int(r) > 0]
+        R = b * (2 + sum(r for _, r in groups))
+        extra = torch.cat([src, dst]).contiguous() if (with_extra and self.use_memory and self.dp_world > 1) else None
+        return B, lo, hi, b, groups, R, extra, (self.dropout if self.training else 0.0)
+
+    @staticmethod
+    def _no_neighbours(K, root_ts):      # utils.py:175: K <= 0 samples a single all-padding column - one slot, every root at time -1
+        return (K, root_ts) if K > 0 else (1, torch.full_like(root_ts, -1.0))
+
     # ------------------------------------------------------------------ next batch's neighbourhood beside this batch's backward
-    def _batch_key(self, src, dst, groups, edge_times, K):
+    def _batch_key(self, src, dst, edge_times, K, B, groups):
         nf = self.neighbor_finder
-        return (src.data_ptr(), dst.data_ptr(), edge_times.data_ptr(), int(src.shape[0]), int(K),
+        return (src.data_ptr(), dst.data_ptr(), edge_times.data_ptr(), B, int(K),
                 tuple((t.data_ptr(), int(t.shape[0]), r) for t, r in groups),
                 self.memory._state_version if self.use_memory else 0, id(nf), getattr(nf, "_version", 0),
                 self.dp_rank, self.dp_world)
 
+    @contextlib.contextmanager
     def prefetching(self, beside_attention_backward=False):
         """Context manager: work issued inside runs on this model's prefetch stream, ordered behind everything the caller's
         stream holds at entry.  A training loop draws the NEXT batch's negatives and calls ``prefetch`` inside it, right after
@@ -713,23 +742,17 @@ class TGN(nn.Module):
         the event that backward recorded in front of its layer-1 attention kernel (``pfo_tgn_batch.mid_event``) instead of for
         the whole backward: the preparation's small latency-bound launches run beside the longest kernel of the step, the one
         phase that hides them (beside the layer-2 backward - equally small launches - they cost as much as they save)."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def ctx():
-            if self._pre_stream is None:
-                self._pre_stream = torch.cuda.Stream(device=self.device)
-            if beside_attention_backward and self._mid_event_fresh:
-                ev = self._mid_event                              # (behind the forward's state update too: same stream, earlier)
-                self._mid_event_fresh = False
-            else:
-                ev = torch.cuda.Event()
-                ev.record()                                       # after the caller's forward (whose state update the pack reads)
-            self._pre_main = torch.cuda.current_stream()
-            self._pre_stream.wait_event(ev)
-            with torch.cuda.stream(self._pre_stream):
-                yield
-        return ctx()
+        if self._pre_stream is None:
+            self._pre_stream = torch.cuda.Stream(device=self.device)
+        if beside_attention_backward and self._mid_event_fresh:
+            ev = self._mid_event                                  # (behind the forward's state update too: same stream, earlier)
+            self._mid_event_fresh = False
+        else:
+            ev = self._recorded_event()                           # after the caller's forward (whose state update the pack reads)
+        self._pre_main = torch.cuda.current_stream()
+        self._pre_stream.wait_event(ev)
+        with torch.cuda.stream(self._pre_stream):
+            yield
 
     def prefetch(self, src, dst, extra_roots, extra_repeat, edge_times, edge_idxs, n_neighbors):
         """Everything of the next training ``embed_device`` / ``compute_temporal_embeddings[_p]`` call (SAME tensors, passed
@@ -742,18 +765,11 @@ class TGN(nn.Module):
             return False
         self._join_backward()             # (overlap_backward: the workspace this call takes may be the one that backward reads)
         self._drop_prefetched()
-        B, K = int(src.shape[0]), int(n_neighbors)
-        lo, hi = 0, B
-        if self.dp_world > 1:
-            lo, hi = self.dp_rank * B // self.dp_world, (self.dp_rank + 1) * B // self.dp_world
-        b = hi - lo
+        K = int(n_neighbors)
+        B, lo, hi, b, groups, R, extra, dropout_p = self._batch_plan(src, dst, extra_roots, extra_repeat)
         if b == 0 or K <= 0:
             return False
-        groups = [(t.contiguous(), int(r)) for t, r in zip(extra_roots, extra_repeat) if int(r) > 0]
-        R = b * (2 + sum(r for _, r in groups))
-        extra = torch.cat([src, dst]).contiguous() if (self.use_memory and self.dp_world > 1) else None
         roots, root_ts = self._assemble_roots(src, dst, edge_times, groups, lo, hi, R)
-        dropout_p = self.dropout if self.training else 0.0
         main = self._pre_main if self._pre_main is not None else torch.cuda.default_stream(self.device)
         with torch.cuda.stream(main):
             # a NEW workspace (pool miss) must belong to the caller's stream's allocator pool: the forward / backward that use
@@ -763,43 +779,33 @@ class TGN(nn.Module):
         st = self._state_struct()
         _lib.call("pfo_tgn_prepare", ctypes.byref(call.cfg), ctypes.byref(st), ctypes.byref(call.batch_struct),
                   call.ws.data_ptr(), _lib.stream_ptr())
-        call.ready = torch.cuda.Event()
-        call.ready.record()
-        call.keep = (src, dst, edge_times, groups)                 # the key's addresses stay theirs until the call is used
+        call.ready = self._recorded_event()
+        call.keep += (src, dst, edge_times, groups)                # the key's addresses stay theirs until the call is used
         for t in (roots, root_ts, extra) + tuple(g for g, _ in groups):
             if t is not None:
                 t.record_stream(main)                             # allocated on the prefetch stream, read on the caller's
-        self._prefetched = (self._batch_key(src, dst, groups, edge_times, K), dropout_p, call)
+        self._prefetched = (self._batch_key(src, dst, edge_times, K, B, groups), dropout_p, call)
         return True
 
-    def _discard_call(self, call):
+    def _drop_prefetched(self):
         """Hands a prepared-but-unused call's workspace back.  ``pfo_tgn_prepare`` may still be running on the prefetch
         stream: whoever pops that workspace from the pool next works on the CALLER's stream, so that stream is made to
         wait for the preparation first (stream-ordered, no host sync)."""
-        ready = getattr(call, "ready", None)
-        if ready is not None:
-            torch.cuda.current_stream(self.device).wait_event(ready)
-        call.release()
-
-    def _drop_prefetched(self):
         if self._prefetched is not None:
-            self._discard_call(self._prefetched[2])
-            self._prefetched = None
+            call, self._prefetched = self._prefetched[2], None
+            torch.cuda.current_stream(self.device).wait_event(call.ready)
+            call.release()
 
-    def _take_prefetched(self, src, dst, groups, edge_times, K, draws, offset_dev, grad_mode, dropout_p):
-        if self._prefetched is None:
-            return None
+    def _take_prefetched(self, src, dst, edge_times, K, B, groups, draws, offset_dev, grad_mode, dropout_p):
         key, p_drop, call = self._prefetched
-        self._prefetched = None
-        if (grad_mode and draws is None and offset_dev is None and p_drop == dropout_p
-                and key == self._batch_key(src, dst, groups, edge_times, K)
+        if not (grad_mode and draws is None and offset_dev is None and p_drop == dropout_p
+                and key == self._batch_key(src, dst, edge_times, K, B, groups)
                 and bool(self.deterministic) == bool(call.batch_struct.deterministic)):
-            self._step += 1                                       # its position in the random streams (dropout masks): now
-            call.offset = self._step << 36
-            call.batch_struct.offset = call.offset
-            return call
-        self._discard_call(call)
-        return None
+            return self._drop_prefetched()
+        self._prefetched = None
+        self._step += 1                                           # its position in the random streams (dropout masks): now
+        call.offset = call.batch_struct.offset = self._step << 36
+        return call
 
     def embed_device(self, src, dst, extra_roots, extra_repeat, edge_times, edge_idxs, n_neighbors, draws=None, offset_dev=None,
                      dropout_keep=None, split_blocks=None):
@@ -818,7 +824,6 @@ class TGN(nn.Module):
         blocks instead of the matrix - under autograd as separate outputs of one node (see _EmbedFn.forward).
         """
         _lib.require_gpu(self.device)
-        B = int(src.shape[0])
         K = int(n_neighbors)
         if self.debug_checks and self.use_memory:
             m = self.memory
@@ -829,33 +834,26 @@ class TGN(nn.Module):
         if self.use_memory and not self.memory._any_msg:
             self._gru_applied_now = bool(self.memory.has_msg.any())
             self.memory._any_msg = self._gru_applied_now
-        lo, hi = 0, B
-        if self.dp_world > 1:
-            lo, hi = self.dp_rank * B // self.dp_world, (self.dp_rank + 1) * B // self.dp_world
-        b = hi - lo
-        self.dp_grad_scale = (b / float(B)) if B > 0 else 0.0
-        # roots = [src | dst | extra groups], root_ts = the interaction's edge time per root (tgn.py:123-124 / 238-239);
-        # a group with zero nodes per interaction (e.g. no negatives) contributes nothing
-        groups = [(t.contiguous(), int(r)) for t, r in zip(extra_roots, extra_repeat) if int(r) > 0]
-        R = b * (2 + sum(r for _, r in groups))
-        D = self.n_node_features
         grad_mode = torch.is_grad_enabled()
-        dropout_p = self.dropout if self.training else 0.0       # dropout follows train()/eval(), not the autograd mode
         if dropout_keep is not None:
             self._drop_prefetched()
-        pre = self._take_prefetched(src, dst, groups, edge_times, K, draws, offset_dev, grad_mode, dropout_p)
+        # (a call prepared ahead of time brings its ``extra``; one prepared for another batch is dropped and the plan made in full)
+        pending = self._prefetched is not None
+        B, lo, hi, b, groups, R, extra, dropout_p = self._batch_plan(src, dst, extra_roots, extra_repeat, with_extra=not pending)
+        pre = self._take_prefetched(src, dst, edge_times, K, B, groups, draws, offset_dev, grad_mode, dropout_p) if pending else None
+        if pending and pre is None:
+            B, lo, hi, b, groups, R, extra, dropout_p = self._batch_plan(src, dst, extra_roots, extra_repeat)
+        self.dp_grad_scale = (b / float(B)) if B > 0 else 0.0
+        D = self.n_node_features
         if pre is not None:
             roots, root_ts, extra = pre.roots, pre.root_ts, pre.extra
         else:
-            extra = torch.cat([src, dst]).contiguous() if (self.use_memory and self.dp_world > 1) else None
             roots, root_ts = self._assemble_roots(src, dst, edge_times, groups, lo, hi, R)
         no_neighbours = K <= 0
-        if no_neighbours:                # utils.py:175: a single all-padding column
-            K, root_ts = 1, torch.full_like(root_ts, -1.0)
-        post = None
-        if self.use_memory:
-            post = lambda call: self._native_update_state(call, src, dst, edge_times, edge_idxs)
-        fuse_state = self.use_memory and self.n_layers >= 2 and b > 0 and grad_mode and self.fuse_state_update
+        K, root_ts = self._no_neighbours(K, root_ts)
+        post = (lambda call: self._native_update_state(call, src, dst, edge_times, edge_idxs)) if self.use_memory else None
+        # training calls: persist + message store inside the native forward, on its side stream
+        fuse_state = self.use_memory and self.n_layers >= 2 and b > 0 and grad_mode
         if b == 0:
             call = self._make_call(roots, root_ts, K, None, 0.0, extra, B)
             self._native_forward(call)
@@ -888,11 +886,8 @@ class TGN(nn.Module):
                 bs = call.batch_struct
                 bs.upd_src, bs.upd_dst, bs.upd_ts, bs.upd_eidx, bs.upd_B = (src.data_ptr(), dst.data_ptr(), edge_times.data_ptr(),
                                                                            edge_idxs.data_ptr(), B)
-                # (one rank only: a data-parallel rank's forward-side stream already carries the GLOBAL batch's state update -
-                #  8x the work at 8 ranks - and the event layer 2 waits for would move behind it: emulated 8-rank step 1.547 ms
-                #  with, 1.537 without)
-                bs.seg_in_forward = 1 if (self.seg_in_forward and (self.dp_world == 1 or self.seg_in_forward_dp)) else 0
-                call.keep = (getattr(call, "keep", None), src, dst, edge_times, edge_idxs)
+                bs.seg_in_forward = 1     # ... and builds the backward's instance groups there too, on a data-parallel rank as well
+                call.keep += (src, dst, edge_times, edge_idxs)
                 self.memory._any_msg = True
                 post = None
             # (ONE parameter that requires a gradient ties the node into the graph: the native backward accumulates every
@@ -911,23 +906,15 @@ class TGN(nn.Module):
             roots, root_ts, inverse = self._dedup_roots(src[lo:hi], dst[lo:hi], edge_times[lo:hi], groups, lo, hi, B, roots, root_ts)
             R = int(roots.shape[0])
         cap = int(self.eval_chunk_roots)
-        if dropout_keep is not None and (inverse is not None or R > int(self.eval_chunk_roots)):
+        if dropout_keep is not None and (inverse is not None or R > cap):
             raise ValueError("injected dropout decisions address the roots as given: not with the forward-only dedup / chunk walk")
         if R <= cap or draws is not None:
             call = self._make_call(roots, root_ts, K, draws, dropout_p, extra, B, dropout_keep=dropout_keep)
             emb = self._native_forward(call)
         else:
-            emb = torch.empty((R, D), dtype=torch.float32, device=self.device)
-            pos = torch.cat([src, dst]).contiguous() if self.use_memory else None
-            order = list(range(cap, R, cap)) + [0]                # chunk 0 (holds src|dst) last: its touched set feeds the persist
-            call = None
-            for c0 in order:
-                c1 = min(R, c0 + cap)
-                ex = extra if c0 != 0 or pos is None else (pos if extra is None else extra)
-                if call is not None:
-                    call.release()
-                call = self._make_call(roots[c0:c1], root_ts[c0:c1], K, None, dropout_p, ex, B)
-                self._native_forward(call, out=emb[c0:c1])
+            # chunk 0 (holds src|dst) last: its touched set feeds the persist, so its ``extra`` names the whole batch's positives
+            first = extra if (extra is not None or not self.use_memory) else torch.cat([src, dst]).contiguous()
+            emb, call = self._forward_chunks(roots, root_ts, K, dropout_p, B, [(c0, extra) for c0 in range(cap, R, cap)] + [(0, first)])
         if post is not None:
             post(call)
         call.release()
@@ -936,6 +923,22 @@ class TGN(nn.Module):
         if split is not None:
             emb = tuple(emb[r0:r1] for r0, r1 in split)
         return emb, b
+
+    def _forward_chunks(self, roots, root_ts, K, dropout_p, B, chunks):
+        """Forward-only passes over ``(roots, root_ts)`` in chunks of ``eval_chunk_roots`` rows into one embedding matrix.
+        ``chunks`` = [(first row, that pass's ``extra``)] in the order the passes run (each takes its place in the Philox
+        streams as it is made).  Every call hands its workspace back before the next takes one; the last is returned with
+        its workspace, for a state update from its touched set - the caller releases it."""
+        R, cap = int(roots.shape[0]), max(1, int(self.eval_chunk_roots))
+        emb = torch.empty((R, self.n_node_features), dtype=torch.float32, device=self.device)
+        call = None
+        for c0, extra in chunks:
+            c1 = min(R, c0 + cap)
+            if call is not None:
+                call.release()
+            call = self._make_call(roots[c0:c1], root_ts[c0:c1], K, None, dropout_p, extra, B)
+            self._native_forward(call, out=emb[c0:c1])
+        return emb, call
 
     def _dedup_roots(self, src, dst, ts, groups, lo, hi, B, roots, root_ts):
         """An embedding is a function of (node, time) only, and an evaluation batch scores the same few hundred items for
@@ -977,13 +980,13 @@ class TGN(nn.Module):
         if self.training == mode:
             # (the module LIST is kept: walking named_modules() is 25 us per batch; a module attached to this model later
             #  drops it - __setattr__ / add_module below - and a tree edited underneath a child is caught by the count)
-            mods = self.__dict__.get("_module_list")
+            mods = self._module_list
             if mods is None or len(mods[0]._modules) != mods[1]:
                 ms = list(self.modules())
-                mods = self.__dict__["_module_list"] = (self, len(self._modules), ms, sum(len(m._modules) for m in ms))
+                mods = self._module_list = (self, len(self._modules), ms, sum(len(m._modules) for m in ms))
             if all(m.training == mode for m in mods[2]) and sum(len(m._modules) for m in mods[2]) == mods[3]:
                 return self
-            self.__dict__["_module_list"] = None
+            self._module_list = None
         return super().train(mode)
 
     def __setattr__(self, name, value):
@@ -1014,56 +1017,36 @@ class TGN(nn.Module):
         for n in sizes:
             offs.append(total)
             total += (n + 7) & ~7
-        ring = self.__dict__.setdefault("_stage_ring", [])
-        slot = self.__dict__["_stage_next"] = (self.__dict__.get("_stage_next", -1) + 1) % 2
-        if len(ring) <= slot or ring[slot][0].numel() < total:
+        slot = self._stage_next = (self._stage_next + 1) % 2
+        entry = self._stage_ring[slot]
+        if entry is not None:
+            entry[2].synchronize()                            # (its last copy: two batches ago - normally long done)
+        if entry is None or entry[0].numel() < total:
             host = torch.empty(max(total, 1 << 16), dtype=torch.uint8, pin_memory=True)
-            entry = (host, host.numpy(), torch.cuda.Event())
-            if len(ring) <= slot:
-                ring.append(entry)
-            else:
-                ring[slot][2].synchronize()
-                ring[slot] = entry
-        else:
-            ring[slot][2].synchronize()                       # (its last copy: two batches ago - normally long done)
-        host, view, ev = ring[slot]
+            entry = self._stage_ring[slot] = (host, host.numpy(), torch.cuda.Event())
+        host, view, ev = entry
         for a, dt, o, n in zip(arrs, dts, offs, sizes):
             view[o:o + n].view(dt)[...] = a.reshape(-1)       # converts while it copies
         dev = host[:total].to(self.device, non_blocking=True)
         ev.record()
-        out = []
-        for a, dt, o, n in zip(arrs, dts, offs, sizes):
-            out.append(dev[o:o + n].view(_TORCH_OF[dt.name]).view(a.shape))
-        return out
+        return [dev[o:o + n].view(_TORCH_OF[dt.name]).view(a.shape) for a, dt, o, n in zip(arrs, dts, offs, sizes)]
+
+    @staticmethod
+    def _check_range(a, n, what):
+        # ids outside [0, n) raise IndexError like the reference's table lookups would (the native kernels index unchecked)
+        a = np.asarray(a)
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= n):
+            raise IndexError("%s outside [0, %d)" % (what, n))
+        return a
 
     def _check_nodes(self, a, what):
-        a = np.asarray(a)
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= self.n_nodes):
-            raise IndexError("%s holds node ids outside [0, %d)" % (what, self.n_nodes))
-        return a
+        return self._check_range(a, self.n_nodes, what + " holds node ids")
 
     def _check_edges(self, a):
-        a = np.asarray(a)
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= self.edge_raw_features.shape[0]):
-            raise IndexError("edge_idxs outside [0, %d)" % self.edge_raw_features.shape[0])
-        return a
+        return self._check_range(a, self.edge_raw_features.shape[0], "edge_idxs")
 
     def _to_dev(self, a, dtype):
         return torch.from_numpy(np.ascontiguousarray(np.asarray(a), dtype=dtype)).to(self.device)
-
-    def _nodes_to_dev(self, a, what):
-        """Host node ids -> i32 device tensor; ids outside [0, n_nodes) raise IndexError like the reference's table
-        lookups would (the native kernels index feature / memory / adjacency tables with them unchecked)."""
-        a = np.asarray(a)
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= self.n_nodes):
-            raise IndexError("%s holds node ids outside [0, %d)" % (what, self.n_nodes))
-        return self._to_dev(a, np.int32)
-
-    def _edges_to_dev(self, a):
-        a = np.asarray(a)
-        if a.size and (int(a.min()) < 0 or int(a.max()) >= self.edge_raw_features.shape[0]):
-            raise IndexError("edge_idxs outside [0, %d)" % self.edge_raw_features.shape[0])
-        return self._to_dev(a, np.int32)
 
     def compute_temporal_embeddings(self, source_nodes, destination_nodes, p_neg_nodes, edge_times, edge_idxs,
                                     n_neighbors=20, draws=None, dropout_keep=None):
@@ -1101,23 +1084,15 @@ class TGN(nn.Module):
         through the forward-only passes in chunks of ``eval_chunk_roots``.  The host-side step counter (position of the Philox
         streams: uniform sampling draws from it) and the "a GRU took part" flag are put back, so the next training step is the
         one it would have been."""
-        R, D = int(roots.shape[0]), self.n_node_features
-        K = int(K)
-        if K <= 0:                       # utils.py:175: a single all-padding column
-            K, root_ts = 1, torch.full_like(root_ts, -1.0)
+        K, root_ts = self._no_neighbours(int(K), root_ts)
         saved = (self._step, self._gru_applied_now)
         self._drop_prefetched()          # (a batch prepared ahead of time is simply prepared again by its own call)
-        emb = torch.empty((R, D), dtype=torch.float32, device=self.device)
-        cap = max(1, int(self.eval_chunk_roots))
         try:
             with torch.no_grad():
-                for c0 in range(0, R, cap):
-                    c1 = min(R, c0 + cap)
-                    call = self._make_call(roots[c0:c1], root_ts[c0:c1], K, None, 0.0, None, max(1, self._ws_caps[2]))
-                    try:
-                        self._native_forward(call, out=emb[c0:c1])
-                    finally:
-                        call.release()
+                emb, call = self._forward_chunks(roots, root_ts, K, 0.0, max(1, self._ws_caps[2]),
+                                                 [(c0, None) for c0 in range(0, int(roots.shape[0]), max(1, int(self.eval_chunk_roots)))])
+                if call is not None:
+                    call.release()
         finally:
             self._step, self._gru_applied_now = saved
         return emb
@@ -1141,154 +1116,10 @@ class TGN(nn.Module):
 
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` are not (it would cost a
         read-back).  ``items`` is read back once when it is a device tensor."""
-        import operator
-        from .functional import recommend_topk
-
-        def host(a):
-            return None if isinstance(a, torch.Tensor) else np.asarray(a)
-
-        def int_vector(a, what):
-            h = host(a)
-            t = a if h is None else h
-            if t.ndim != 1 or (h is not None and h.size and h.dtype.kind not in "iu") or (
-                    h is None and (t.dtype.is_floating_point or t.dtype == torch.bool)):
-                raise ValueError("%s must be a 1-D array of integer node ids" % what)
-            if h is not None and h.size and (int(h.min()) < 0 or int(h.max()) >= self.n_nodes):
-                raise ValueError("%s holds node ids outside [0, %d)" % (what, self.n_nodes))
-            return h
-
-        # ---- validation, on the host alone
-        try:
-            k = operator.index(k)
-        except TypeError:
-            raise ValueError("k must be an integer") from None
-        if not 1 <= k <= 64:
-            raise ValueError("k must be in [1, 64] (got %d)" % k)
-        users_h = int_vector(users, "users")
-        U = int(users.shape[0]) if users_h is None else int(users_h.shape[0])
-        items_h = int_vector(items.detach().cpu().numpy() if isinstance(items, torch.Tensor) else items, "items")
-        I = int(items_h.shape[0])
-        if I < 1 or I > _lib.RECOMMEND_MAX_ITEMS:
-            raise ValueError("items must hold between 1 and %d candidates (got %d)" % (_lib.RECOMMEND_MAX_ITEMS, I))
-        if (items_h == 0).any():
-            raise ValueError("items holds node 0 (the padding node)")
-        if np.unique(items_h).shape[0] != I:
-            raise ValueError("items holds duplicates")
-        ts_h = host(timestamps)
-        ts_any = timestamps if ts_h is None else ts_h
-        scalar_ts = ts_any.ndim == 0
-        if not scalar_ts and tuple(ts_any.shape) != (U,):
-            raise ValueError("timestamps must be a scalar or hold one value per user (%d), got shape %s" % (U, tuple(ts_any.shape)))
-        if ts_h is not None and ts_h.dtype.kind not in "fiu":
-            raise ValueError("timestamps must be numbers")
-        ok_h = None
-        if item_ok is not None:
-            ok_any = item_ok if isinstance(item_ok, torch.Tensor) else np.asarray(item_ok)
-            if tuple(ok_any.shape) != (I,):
-                raise ValueError("item_ok must hold one flag per candidate (%d), got shape %s" % (I, tuple(ok_any.shape)))
-            ok_h = host(item_ok)
-        ex_ids = ex_len = None
-        if exclude is not None:
-            packed = (isinstance(exclude, (tuple, list)) and len(exclude) == 2
-                      and isinstance(exclude[0], (torch.Tensor, np.ndarray)) and exclude[0].ndim == 2)
-            if packed:
-                ex_ids, ex_len = exclude
-                if not isinstance(ex_len, (torch.Tensor, np.ndarray)):
-                    ex_len = np.asarray(ex_len)
-                if ex_ids.shape[0] != U or tuple(ex_len.shape) != (U,):
-                    raise ValueError("packed exclude must be (ids [U,W], lens [U]) with U = %d" % U)
-                for t, what in ((ex_ids, "ids"), (ex_len, "lens")):
-                    kind_ok = (t.dtype.kind in "iu") if isinstance(t, np.ndarray) else not (t.dtype.is_floating_point or t.dtype == torch.bool)
-                    if not kind_ok:
-                        raise ValueError("packed exclude %s must be integers" % what)
-            else:
-                try:
-                    rows = [np.asarray(list(r), np.int64).reshape(-1) for r in exclude]
-                except (TypeError, ValueError):
-                    raise ValueError("exclude must be None, a list of per-user lists of item ids or a packed (ids, lens) pair") from None
-                if len(rows) != U:
-                    raise ValueError("exclude lists %d users, users holds %d" % (len(rows), U))
-                W = max([len(r) for r in rows], default=0)
-                ex_ids = np.full((U, W), -1, np.int32)
-                ex_len = np.zeros(U, np.int32)
-                for i, r in enumerate(rows):
-                    if r.size and (int(r.min()) < -(1 << 31) or int(r.max()) >= (1 << 31)):
-                        raise ValueError("exclude holds ids that do not fit 32 bits")
-                    ex_ids[i, :len(r)] = r
-                    ex_len[i] = len(r)
-        if n_neighbors is None:
-            n_neighbors = 20 if self.n_neighbors is None else self.n_neighbors
-        K = int(n_neighbors)
-
-        # ---- the device from here on
+        from . import recommend as R
+        query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors)
         _lib.require_gpu(self.device)
-        dev = self.device
-
-        def to_dev(a, dtype):
-            if isinstance(a, torch.Tensor):
-                return a.to(device=dev, dtype=dtype).contiguous()
-            return torch.from_numpy(np.ascontiguousarray(a).astype(str(dtype).replace("torch.", ""), copy=False)).to(dev)
-
-        with torch.no_grad():
-            users_d = to_dev(users if users_h is None else users_h, torch.int32)
-            items_d = to_dev(items_h, torch.int32)
-            user_block = None
-            if scalar_ts:
-                grid_t = to_dev(ts_any.reshape(1), torch.float64)
-                user_ts = grid_t.expand(U)
-            elif ts_h is not None:
-                uniq, inv = np.unique(ts_h.astype(np.float64), return_inverse=True)
-                grid_t, user_ts = to_dev(uniq, torch.float64), to_dev(ts_h, torch.float64)
-                user_block = to_dev(inv.reshape(-1), torch.int32)
-            else:
-                user_ts = to_dev(timestamps, torch.float64)
-                grid_t, inv = torch.unique(user_ts, return_inverse=True)
-                user_block = inv.to(torch.int32)
-            n_t = max(1, int(grid_t.shape[0]))
-            if U == 0:
-                grid_t = grid_t[:0]
-                n_t = 1
-            roots = torch.cat([users_d, items_d.repeat(int(grid_t.shape[0]))]).contiguous()
-            root_ts = torch.cat([user_ts, grid_t.repeat_interleave(I)]).contiguous()
-            D = self.n_node_features
-            emb = self._embed_readonly(roots, root_ts, K) if roots.shape[0] else torch.empty((0, D), dtype=torch.float32, device=dev)
-            user_emb, item_emb = emb[:U], emb[U:]
-            if U == 0:
-                empty = lambda dt: torch.empty((0, k), dtype=dt, device=dev)
-                out = (empty(torch.int32), empty(torch.float32), torch.empty(0, dtype=torch.int32, device=dev))
-                if return_embeddings:
-                    out += (user_emb, item_emb, torch.empty(0, dtype=torch.int32, device=dev))
-                return out
-            excl_pos = excl_len = None
-            if ex_ids is not None and ex_ids.shape[1] > 0:
-                # node id -> position in ``items`` through a table over the node ids (-1: not a candidate)
-                pos_of = torch.full((self.n_nodes,), -1, dtype=torch.int32, device=dev)
-                pos_of[items_d.long()] = torch.arange(I, dtype=torch.int32, device=dev)
-                ids = to_dev(ex_ids, torch.int64)
-                inside = (ids >= 0) & (ids < self.n_nodes)
-                excl_pos = torch.where(inside, pos_of[ids.clamp(0, self.n_nodes - 1)], torch.full_like(ids, -1, dtype=torch.int32))
-                excl_pos = excl_pos.contiguous()
-                excl_len = to_dev(ex_len, torch.int32)
-            ok_d = None
-            if item_ok is not None:
-                ok_d = (to_dev(item_ok if ok_h is None else ok_h, torch.int64) != 0).to(torch.uint8)
-            order = None
-            if user_block is not None and n_t > 1:
-                # users of one block side by side: the kernel serves a tile of 16 users in one pass per distinct block
-                order = torch.argsort(user_block, stable=True)
-                sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
-                res = recommend_topk(sel(user_emb), item_emb, k, sel(user_block), sel(excl_pos), sel(excl_len), ok_d, n_blocks=n_t)
-                res = tuple(torch.empty_like(t).index_copy_(0, order, t) for t in res)
-            else:
-                res = recommend_topk(user_emb, item_emb, k, user_block if n_t > 1 else None, excl_pos, excl_len, ok_d, n_blocks=n_t)
-            top_pos, top_score, n_valid = res
-            item_ids = torch.where(top_pos >= 0, items_d[top_pos.clamp(min=0).long()], torch.full_like(top_pos, -1))
-            out = (item_ids, top_score, n_valid)
-            if return_embeddings:
-                if user_block is None:
-                    user_block = torch.zeros(U, dtype=torch.int32, device=dev)
-                out += (user_emb, item_emb, user_block)
-            return out
+        return R.assemble(self, query, return_embeddings)
 
     def _dev_keep(self, masks):
         """Injected dropout decisions for a parity test: ``{l: multipliers or booleans [n_l, H, K]}`` (level order, the layout
@@ -1306,9 +1137,7 @@ class TGN(nn.Module):
         return out
 
     def _dev_draws(self, draws):
-        if draws is None:
-            return None
-        return [self._to_dev(d, np.int64) for d in draws]
+        return None if draws is None else [self._to_dev(d, np.int64) for d in draws]
 
     # ------------------------------------------------------------------ introspection for tests
     def debug_dropout_masks(self):
@@ -1329,12 +1158,9 @@ class TGN(nn.Module):
             n *= 1 + K
         return out
 
-    def debug_weight_gradient_operands(self):
-        """fp32 operands and results of the two largest weight-gradient contractions of the LAST backward (before the next
-        forward reuses the workspace): ``dict(ctx [n_1, H*Cp], dh1 [n_1, D], dW1ovT [H*Cp, D], dgi [n_core, 3D],
-        msg_rows [n_core, 3D+Ef])`` as numpy arrays (tests re-contract them in fp64)."""
+    def _debug_views(self):
+        """(the native library's map of the LAST forward's workspace, ``view(ptr, count, dtype)`` of one of its entries)."""
         cfg, ws = self._last_ws
-        seed, offset, R, K, p, _ = self._last_call
         dbg = _lib.TgnDebug()
         _lib.call("pfo_tgn_debug_views", ctypes.byref(cfg), ws.data_ptr(), ctypes.byref(dbg))
         base = ws.data_ptr()
@@ -1342,6 +1168,14 @@ class TGN(nn.Module):
         def view(ptr, count, dtype=torch.float32):
             off = ptr - base
             return ws[off:off + count * torch.empty((), dtype=dtype).element_size()].view(dtype)
+        return dbg, view
+
+    def debug_weight_gradient_operands(self):
+        """fp32 operands and results of the two largest weight-gradient contractions of the LAST backward (before the next
+        forward reuses the workspace): ``dict(ctx [n_1, H*Cp], dh1 [n_1, D], dW1ovT [H*Cp, D], dgi [n_core, 3D],
+        msg_rows [n_core, 3D+Ef])`` as numpy arrays (tests re-contract them in fp64)."""
+        seed, offset, R, K, p, _ = self._last_call
+        dbg, view = self._debug_views()
         D, H, Cp = self.n_node_features, self.n_heads, int(dbg.Cp)
         n1 = R * (1 + K) ** (self.n_layers - 1)
         out = dict(ctx=view(dbg.l1_ctx, n1 * H * Cp).view(n1, H * Cp).cpu().numpy(),
@@ -1356,14 +1190,7 @@ class TGN(nn.Module):
 
     def debug_touched(self):
         """(touched node ids, layer-0 feature table rows) of the last forward (use_memory only)."""
-        cfg, ws = self._last_ws
-        dbg = _lib.TgnDebug()
-        _lib.call("pfo_tgn_debug_views", ctypes.byref(cfg), ws.data_ptr(), ctypes.byref(dbg))
-        base = ws.data_ptr()
-
-        def view(ptr, count, dtype):
-            off = ptr - base
-            return ws[off:off + count * torch.empty((), dtype=dtype).element_size()].view(dtype)
+        dbg, view = self._debug_views()
         n = int(view(dbg.n_touched, 1, torch.int32).item())
         ids = view(dbg.touched_ids, n, torch.int32).clone()
         h0 = view(dbg.h0_table, n * self.n_node_features, torch.float32).view(n, -1).clone()

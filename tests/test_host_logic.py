@@ -83,6 +83,72 @@ def test_neighbor_finder_attribute_paths():
     assert tgn.neighbor_finder is a
 
 
+def _cpu_model(use_memory=True):
+    g = make_graph(SyntheticConfig("t", 30, 8, 300, 16, 2, 4, 2), with_prices=False)
+    kw = dict(use_memory=True, memory_dimension=16, message_function="identity") if use_memory else dict(use_memory=False)
+    return P.TGN(P.get_neighbor_finder(g.data, False), g.node_features, g.edge_features, "cpu", n_layers=2, n_heads=2, **kw)
+
+
+@pytest.mark.parametrize("use_memory", [True, False])
+def test_batch_plan_shards_groups_and_extra(use_memory):
+    """TGN._batch_plan, the one place the data-parallel shard, the surviving extra groups, R, ``extra`` and the dropout rate of
+    a batch are decided: shard [rank*B//world, (rank+1)*B//world), groups with repeat 0 dropped, R = b * (2 + repeats),
+    ``extra`` = cat(src, dst) exactly for a memory model on more than one rank, dropout only in train()."""
+    import torch
+    tgn = _cpu_model(use_memory)
+    i32 = lambda n, base=1: torch.arange(base, base + n, dtype=torch.int32)
+
+    def plan(B, rank, world, reps, **kw):
+        tgn.set_data_parallel(rank, world)
+        src, dst = i32(B), i32(B, 31)
+        extras = [i32(B * r, 31) for r in reps]
+        out = tgn._batch_plan(src, dst, extras, reps, **kw)
+        assert len(out) == 8 and out[0] == B
+        extra = out[6]
+        assert (extra is not None) == (use_memory and world > 1 and kw.get("with_extra", True))
+        if extra is not None:
+            assert torch.equal(extra, torch.cat([src, dst]))
+        return out, extras
+
+    for rank, (lo, hi) in enumerate([(0, 1), (1, 3), (3, 5)]):                 # B = 5 over 3 ranks: shards of 1, 2, 2
+        (B, plo, phi, b, groups, R, extra, p), extras = plan(5, rank, 3, [3])
+        assert (plo, phi, b) == (lo, hi, hi - lo) and R == b * 5
+        assert len(groups) == 1 and groups[0][0].data_ptr() == extras[0].data_ptr() and groups[0][1] == 3
+    (B, lo, hi, b, groups, R, extra, p), _ = plan(2, 0, 3, [3])                # B < world: rank 0's shard is empty
+    assert (lo, hi, b, R) == (0, 0, 0, 0) and len(groups) == 1
+    (B, lo, hi, b, groups, R, extra, p), extras = plan(4, 0, 1, [2, 0])        # a group of zero nodes per interaction is dropped
+    assert (lo, hi, b, R) == (0, 4, 4, 16) and [(t.data_ptr(), r) for t, r in groups] == [(extras[0].data_ptr(), 2)]
+    plan(5, 1, 3, [3], with_extra=False)                                       # (a prepared call brings its own)
+    tgn.train()
+    assert plan(4, 0, 1, [1])[0][7] == tgn.dropout > 0
+    tgn.eval()
+    assert plan(4, 0, 1, [1])[0][7] == 0.0
+
+
+def test_call_and_model_state_is_explicit():
+    """Every slot of a fresh ``_Call`` holds a value, and a device move / cast (``nn.Module._apply``) returns every cache bound
+    to the old flat buffer to its initial value."""
+    import torch
+    from pfotgnrec_amd.tgn import _Call
+    c = _Call()
+    assert all(hasattr(c, s) for s in _Call.__slots__ if s != "__weakref__")
+    assert c.keep == [] and c.ready is None and c.pkey is None and c.ws is None and c.pool is None
+    c.release()                                                                # (nothing to hand back: no error)
+    tgn = _cpu_model()
+    initial = lambda t: (t._grad_views, t._seen_versions, t._stage_ring, t._stage_next, t._pcache, t._pcache_key, t._prefetched,
+                         t._flat_grad, t._ws_pool, t._last_ws, t._last_call, t._adj_cache, t._side_stream, t._bucket_event)
+    fresh = initial(tgn)
+    assert fresh == (None, None, [None, None], -1, None, None, None, None, [], None, None, None, None, None)
+    for move in (lambda t: t.float(), lambda t: t.to("cpu")):
+        tgn._attach_grads()
+        assert tgn._grad_views is not None and tgn.hot_parameters()[0].grad is not None
+        tgn._seen_versions, tgn._stage_ring, tgn._pcache, tgn._last_call = (1, 2), [("host", "view", "event"), None], "cache", (0,) * 6
+        flat = tgn.flat_parameters.clone()
+        assert move(tgn) is tgn and initial(tgn) == fresh
+        assert torch.equal(tgn.flat_parameters, flat) and all(p.grad is None for p in tgn.hot_parameters())
+        assert tgn._param_key() == tgn._torch_versions() + (tgn._param_epoch, tgn.flat_parameters.data_ptr())
+
+
 def test_time_statistics_match_reference_loop():
     g = make_graph(SyntheticConfig("t", 30, 8, 500, 8, 1, 4, 2), with_prices=False)
     d = g.data
