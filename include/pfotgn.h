@@ -430,6 +430,30 @@ int pfo_tgn_grad_split(const pfo_tgn_config* cfg, int64_t* split);
 int pfo_tgn_update_state(const pfo_tgn_config* cfg, const pfo_tgn_state* st, const int32_t* src, const int32_t* dst,
                          const double* ts, const int32_t* eidx, int32_t B, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Serving write path: advance memory, last_update and the pending-message tables over a chronological log WITHOUT
+ * embedding anything - the write-only counterpart of pfo_recommend_topk.  The log src/dst i32[N], ts f64[N], eidx i32[N]
+ * (device pointers; node ids in [0, n_nodes), eidx rows of edge_feat) is walked in ceil(N / B) batches of B interactions,
+ * the last one shorter, queued back to back from the host side of this call.  Per batch (positives P = src u dst):
+ *   1. every X in P with has_msg[X]:  memory[X] = GRUCell(msg_table[X], memory[X]),  last_update[X] = msg_time[X]
+ *      (tgn.py:295, memory_updater.py:18-33); other positives keep both bit for bit; a node named twice is updated once
+ *   2. pfo_tgn_update_state's message store: event e = side * B + i ascending, the last event per node wins; both memory
+ *      reads see the state after step 1 for the whole batch (tgn.py:302-317, 357-378)
+ * Batch k+1 sees the state batch k left: batch boundaries are part of the semantics, B is not a tuning knob.
+ * Nothing else is written (parameters, gradients, optimizer state).  Launches per batch: 4 - row selection (the distinct
+ * positives that hold a message, compacted), the step's fused GRU launch in its gather form over exactly those rows, persist,
+ * message store - and 5 when 2 B > 16384 (the store's winner pass).  Per call in front of them: one clear of the row
+ * selection's stamp table and, when st->pcache_valid is not set, ONE launch that builds the GRU's two weight images into the
+ * workspace (with a valid parameter cache they are taken from st->pcache).
+ * Everything runs on `stream` (the call first joins work pfo_tgn_adam_side left on the library's side stream): capturable.
+ * The CSR pointers of `st` are not read and may be NULL.  N == 0 queues nothing.  PFO_ERR_INVALID: cfg->use_memory == 0,
+ * B < 1 (or >= 2^30), N < 0, workspace_bytes < pfo_tgn_observe_workspace_bytes(cfg, B) (which returns -1 for a bad cfg / B).
+ */
+int64_t pfo_tgn_observe_workspace_bytes(const pfo_tgn_config* cfg, int32_t B);
+int pfo_tgn_observe(const pfo_tgn_config* cfg, const pfo_tgn_state* st, const int32_t* src, const int32_t* dst,
+                    const double* ts, const int32_t* eidx, int64_t N, int32_t B, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+
 /* diagnostics for tests: copies of internals of the last forward (device pointers into the workspace) */
 typedef struct pfo_tgn_debug {
   const int32_t* n_touched;  /* [1] */

@@ -3,6 +3,7 @@
 Public surface mirrors the reference's: ``TGN`` (model/tgn.py), ``NeighborFinder`` /
 ``get_neighbor_finder`` / ``RandEdgeSampler`` (utils/utils.py), ``Data`` (utils/data.py), ``Memory``
 (modules/memory.py), ``eval_recommendation`` (evaluation.py), plus the MV sampler that main.py keeps inline (``MVSampler``).
+Beyond the reference, on ``TGN``: ``recommend`` (read-only top-k query) and ``observe`` (write-only state advance over a log).
 """
 __version__ = "0.1.0"
 

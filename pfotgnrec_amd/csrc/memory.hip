@@ -764,6 +764,62 @@ int pfo_msg_store_launch(const int32_t* src, const int32_t* dst, const double* t
   return PFO_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Row selection of the serving write path (pfo_tgn_observe): the DISTINCT positives of one batch that hold a pending message,
+// compacted - the only rows that batch's GRU has to run over (the training step compacts its whole sampled frontier instead).
+// One workgroup, one launch, no clear per batch:
+//   1. every event e = side * B + i stamps its node: atomicMax(rep[X], base + e + 1).  `base` grows by 2B from batch to
+//      batch, so stamps of earlier batches are smaller than every stamp of this one and rep[] is cleared once per CALL;
+//      the event that finds its own stamp again is the last one that names X - one representative per distinct node.
+//   2. the representatives whose node has a message are compacted in event order: a wave ballot gives the position inside
+//      the wavefront, the 16 wave counts go through LDS, the running total stays in a register - rows come out in the same
+//      order on every run.  touched[pos] = X, slot[X] = pos (what persist_kernel reads), *n_out = the number of rows.
+// The stamps are read back by the workgroup that wrote them: atomics and atomic loads both work at L2, the fence + barrier
+// in between orders them.  A batch of B <= 512 is one sweep of each loop; very large batches walk 1024 events per sweep.
+__global__ __launch_bounds__(SCAN_BLOCK) void observe_select_kernel(const int32_t* __restrict__ src, const int32_t* __restrict__ dst,
+                                                                    int B, const uint8_t* __restrict__ has_msg, int32_t* rep, int base,
+                                                                    int32_t* __restrict__ slot, int32_t* __restrict__ touched,
+                                                                    int32_t* __restrict__ n_out) {
+  __shared__ int s_cnt[SCAN_BLOCK / 64];
+  const int n = 2 * B;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int e = threadIdx.x; e < n; e += SCAN_BLOCK) atomicMax(&rep[e < B ? src[e] : dst[e - B]], base + e + 1);
+  __threadfence();
+  __syncthreads();
+  int carry = 0;
+  for (int e0 = 0; e0 < n; e0 += SCAN_BLOCK) {
+    const int e = e0 + threadIdx.x;
+    int X = 0;
+    bool f = false;
+    if (e < n) {
+      X = e < B ? src[e] : dst[e - B];
+      f = has_msg[X] != 0 && __hip_atomic_load(&rep[X], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == base + e + 1;
+    }
+    const unsigned long long bal = __ballot(f);
+    if (lane == 0) s_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int cnt = 0, woff = 0;
+    for (int w = 0; w < SCAN_BLOCK / 64; ++w) { if (w == wave) woff = cnt; cnt += s_cnt[w]; }
+    if (f) {
+      const int pos = carry + woff + __popcll(bal & ((1ull << lane) - 1ull));
+      slot[X] = pos;
+      touched[pos] = X;
+    }
+    carry += cnt;
+    __syncthreads();                                     // (s_cnt is written again by the next sweep)
+  }
+  if (threadIdx.x == 0) *n_out = carry;
+}
+
+int pfo_observe_select_launch(const int32_t* src, const int32_t* dst, int B, const uint8_t* has_msg, int32_t* rep, int base,
+                              int32_t* slot, int32_t* touched, int32_t* n_out, hipStream_t stream) {
+  PFO_REQUIRE(src && dst && has_msg && rep && slot && touched && n_out, "null argument");
+  PFO_REQUIRE(B >= 1 && B < (1 << 30) && base >= 0 && (int64_t)base + 2 * (int64_t)B < 0x7fffffffll, "bad batch size or stamp base");
+  PFO_KLAUNCH(observe_select_kernel, dim3(1), dim3(SCAN_BLOCK), 0, stream, src, dst, B, has_msg, rep, base, slot, touched, n_out);
+  PFO_LAUNCH_CHECK();
+  return PFO_OK;
+}
+
 // zeroes rows [0, *n_rows) of n_rep replicas (each rep_stride floats apart): the touched part of the gradient table
 __global__ __launch_bounds__(256) void zero_rows_kernel(float* __restrict__ dst, const int32_t* __restrict__ n_rows, int D,
                                                         int n_rep, int64_t rep_stride) {

@@ -60,6 +60,11 @@ int pfo_msg_store_launch(const int32_t* src, const int32_t* dst, const double* t
                          const float* tb, int D, int Ef, float* msg_table, float* msg_time, uint8_t* has_msg,
                          int32_t* winner, hipStream_t stream);
 
+// --- serving write path (pfo_tgn_observe): touched[0, *n_out) = the distinct nodes of [src | dst] that hold a pending message,
+// slot[X] = the row of X.  rep i32[n_nodes]: stamp table, zero before the first batch of a call; base = 2 B (batches so far)
+int pfo_observe_select_launch(const int32_t* src, const int32_t* dst, int B, const uint8_t* has_msg, int32_t* rep, int base,
+                              int32_t* slot, int32_t* touched, int32_t* n_out, hipStream_t stream);
+
 // --- small ops (misc.hip)
 // out[0] = mean(src[0 .. n)), one wavefront, fixed order
 int pfo_mean_launch(const float* src, int64_t n, float* out, hipStream_t stream);

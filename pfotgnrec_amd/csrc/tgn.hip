@@ -1559,3 +1559,105 @@ extern "C" int pfo_tgn_update_state(const pfo_tgn_config* c, const pfo_tgn_state
   RUN(side_join(side(), (hipStream_t)stream));
   return state_update(c, st, w, src, dst, ts, eidx, B, (hipStream_t)stream);
 }
+
+// =============================================================================================
+// The serving write path: a chronological log walked in batches of B, the model state left where the step would leave it -
+// without sampling, attention or embeddings (tgn.py:295-317 alone).  Per batch four launches on the caller's stream
+// (five beyond MSG_INLINE_MAX events): row selection (memory.hip observe_select_kernel) -> the step's own fused GRU in its
+// gather form over exactly those rows -> persist -> [winner pass] -> message store; the last three are state_update().
+// The GRU result goes through the packed buffer + persist_kernel, not an in-place epilogue: gru_fused_kernel and
+// state_update() are then the training step's, launched unchanged - the parity with the step is shared code.
+namespace {
+struct ObsWs {
+  int32_t *rep, *slot, *touched, *n_rows, *winner;
+  float *upd_mem, *h0_tab, *gates;
+  void *iWih, *iWhh;
+  int64_t cap, bytes;
+};
+ObsWs carve_observe(const pfo_tgn_config* c, int32_t B, void* base) {
+  const Dims d = dims_of(c);
+  ObsWs o;
+  memset(&o, 0, sizeof(o));
+  char* p = reinterpret_cast<char*>(base);
+  o.cap = std::min<int64_t>(c->n_nodes, 2 * (int64_t)B);          // distinct positives of one batch
+  o.rep = take<int32_t>(p, c->n_nodes);
+  o.slot = take<int32_t>(p, c->n_nodes);
+  o.touched = take<int32_t>(p, o.cap);
+  o.n_rows = take<int32_t>(p, 64);
+  if (pfo_msg_store_needs_winner(B)) o.winner = take<int32_t>(p, c->n_nodes);
+  o.upd_mem = take<float>(p, o.cap * d.D);
+  o.h0_tab = take<float>(p, o.cap * d.D);                         // (by-products of the fused launch, not read here)
+  o.gates = take<float>(p, o.cap * 4 * d.D);
+  o.iWih = take<char>(p, pfo_gru_img_bytes(d.D, d.M));            // (used when the state carries no valid parameter cache)
+  o.iWhh = take<char>(p, pfo_gru_img_bytes(d.D, d.D));
+  o.bytes = p - reinterpret_cast<char*>(base);
+  return o;
+}
+int check_observe(const pfo_tgn_config* c, int32_t B) {
+  if (int rc = check_cfg(c)) return rc;
+  PFO_REQUIRE(c->use_memory != 0, "a model without memory has no state to advance");
+  PFO_REQUIRE(B >= 1 && B < (1 << 30), "B must be in [1, 2^30)");
+  return PFO_OK;
+}
+}  // namespace
+
+extern "C" int64_t pfo_tgn_observe_workspace_bytes(const pfo_tgn_config* c, int32_t B) {
+  if (check_observe(c, B) != PFO_OK) return -1;
+  return carve_observe(c, B, nullptr).bytes + 256;
+}
+
+extern "C" int pfo_tgn_observe(const pfo_tgn_config* c, const pfo_tgn_state* st, const int32_t* src, const int32_t* dst,
+                               const double* ts, const int32_t* eidx, int64_t N, int32_t B, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  if (int rc = check_observe(c, B)) return rc;
+  PFO_REQUIRE(N >= 0, "N must not be negative");
+  if (N == 0) return PFO_OK;
+  PFO_REQUIRE(workspace_bytes >= carve_observe(c, B, nullptr).bytes + 256, "workspace too small (pfo_tgn_observe_workspace_bytes)");
+  PFO_REQUIRE(st && workspace && src && dst && ts && eidx, "null argument");
+  PFO_REQUIRE(st->node_feat && st->params && st->memory && st->last_update && st->msg_table && st->msg_time && st->has_msg, "null state");
+  PFO_REQUIRE(c->Ef == 0 || st->edge_feat, "null edge features");
+  const Dims d = dims_of(c);
+  const ObsWs o = carve_observe(c, B, reinterpret_cast<void*>(pfo_align_up((int64_t)(uintptr_t)workspace, 256)));
+  hipStream_t s = (hipStream_t)stream;
+  pfo_tgn_layout lay;
+  RUN(pfo_tgn_param_layout(c, &lay));
+  Params P;
+  bind(lay, st->params, P, d.L, true);
+  PfoRange range("pfo_tgn_observe");
+  RUN(side_join(side(), s));                                      // (a deferred optimizer step may still be writing the parameters)
+  // GRU weight images: the parameter cache's when it is valid, else built here, once - parameters cannot change inside a call
+  const void *iWih = o.iWih, *iWhh = o.iWhh;
+  if (st->pcache && st->pcache_valid) {
+    Ws pw;
+    memset(&pw, 0, sizeof(pw));
+    pcache_bind(c, st->pcache, pw);
+    iWih = pw.iWih; iWhh = pw.iWhh;
+  } else {
+    Ws bw;
+    memset(&bw, 0, sizeof(bw));
+    bw.iWih = o.iWih; bw.iWhh = o.iWhh;
+    RUN(build_gru_images(c, d, bw, P, s));
+  }
+  HIPOK(hipMemsetAsync(o.rep, 0, (size_t)c->n_nodes * sizeof(int32_t), s), "memset failed");
+  Ws w;                                                           // what state_update() reads of a step's workspace
+  memset(&w, 0, sizeof(w));
+  w.slot = o.slot; w.upd_mem = o.upd_mem; w.winner = o.winner;
+  int64_t base = 0;
+  for (int64_t k0 = 0; k0 < N; k0 += B) {
+    const int32_t b = (int32_t)std::min<int64_t>(B, N - k0);
+    if (base + 2 * (int64_t)b >= 0x7fffffffll) {                  // the stamps would leave int32: start over on a cleared table
+      HIPOK(hipMemsetAsync(o.rep, 0, (size_t)c->n_nodes * sizeof(int32_t), s), "memset failed");
+      base = 0;
+    }
+    RUN(pfo_observe_select_launch(src + k0, dst + k0, b, st->has_msg, o.rep, (int)base, o.slot, o.touched, o.n_rows, s));
+    base += 2 * (int64_t)b;
+    PfoGruFused f;
+    f.gather = 1; f.msg_rows = st->msg_table; f.K_msg = d.M; f.h_rows = st->memory; f.hm = st->has_msg;
+    f.img_ih = iWih; f.img_hh = iWhh; f.b_ih = P.b_ih; f.b_hh = P.b_hh; f.touched = o.touched; f.node_feat = st->node_feat;
+    f.upd_mem = o.upd_mem; f.h0_tab = o.h0_tab; f.gates = o.gates; f.D = d.D;
+    f.cap_rows = (int)std::min<int64_t>(c->n_nodes, 2 * (int64_t)b); f.n_rows = o.n_rows;
+    RUN(pfo_gru_fused_launch(f, s));
+    RUN(state_update(c, st, w, src + k0, dst + k0, ts + k0, eidx + k0, b, s));
+  }
+  return PFO_OK;
+}

@@ -1121,6 +1121,79 @@ class TGN(nn.Module):
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
+    # ------------------------------------------------------------------ serving: write-only state advance
+    def _observe_workspace(self, B):
+        """A workspace of ``pfo_tgn_observe`` from the pool (its entries carry the capacities (0, 0, 0): no forward takes them,
+        and they go with the other undersized buffers when the step's workspace grows)."""
+        need = _lib.byte_count("pfo_tgn_observe_workspace_bytes", ctypes.byref(self._cfg), B)
+        for i, (caps, ws) in enumerate(self._ws_pool):
+            if caps == (0, 0, 0) and ws.numel() >= need:
+                return self._ws_pool.pop(i)[1]
+        return torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def observe(self, sources, destinations, edge_times, edge_idxs, batch_size=None, append=False):
+        """Takes in interactions WITHOUT embedding anything - the write-only counterpart of ``recommend``: a chronological log
+        is walked on the device in batches of ``batch_size`` and ``memory``, ``last_update`` and the pending-message tables
+        end exactly where ``compute_temporal_embeddings[_p]`` would leave them batch by batch (tgn.py:295-317: the GRU on the
+        batch's own positives that hold a message, the persist, the raw-message store) - no negatives, no sampling, no
+        attention.  One native call (``pfo_tgn_observe``), no Python work per batch.  Nothing else is written: parameters,
+        gradients, optimizer state, the step counter and the random streams stay as they are; no gradient is recorded
+        whatever ``train()`` says.  Returns the number of interactions consumed.
+
+        sources / destinations / edge_times / edge_idxs: numpy i64 / i64 / f64 / i64 like the entry points (range-checked:
+        IndexError), or device tensors i32 / i32 / f64 / i32 (not checked: it would cost a read-back).  ``edge_idxs`` must
+        address EXISTING rows of the edge-feature table: growing that table (or the node table) is out of scope.
+        ``batch_size``: interactions per batch, None = the whole input is one batch.  Batch boundaries are part of the
+        semantics (messages are built from the memory as of their batch's persist): replay a log with the batch size it
+        was - or would have been - trained with.  Chronological order is the caller's contract (``debug_checks`` asserts, like
+        ``embed_device``, that no pending message is older than its node's last update).
+        ``append``: the edges also go into the model's neighbour finder (``NeighborFinder.append``) behind the state update, so
+        that a later ``recommend`` sees them; a ``GraphedTrainStep`` captured over the finder goes stale.  Off by default:
+        a replay over a finder that already holds the log must not duplicate its edges.
+        The data-parallel sharding is ignored (every rank observes the whole input: the state is replicated).
+        Without memory there is no state: only the optional append happens."""
+        on_dev = torch.is_tensor(sources)
+        N = int(sources.shape[0]) if on_dev else len(sources)
+        if any(len(a) != N for a in (destinations, edge_times, edge_idxs)):
+            raise ValueError("sources, destinations, edge_times and edge_idxs must have the same length")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be at least 1")
+        if on_dev:
+            want = (torch.int32, torch.int32, torch.float64, torch.int32)
+            if any((not torch.is_tensor(a)) or a.dtype != dt or a.dim() != 1 for a, dt in zip((sources, destinations, edge_times, edge_idxs), want)):
+                raise ValueError("device inputs must be 1-d tensors i32 / i32 / f64 / i32")
+        else:
+            sources, destinations = self._check_nodes(sources, "sources"), self._check_nodes(destinations, "destinations")
+            edge_idxs = self._check_edges(edge_idxs)
+        if self.use_memory and N > 0:
+            _lib.require_gpu(self.device)
+            with torch.no_grad():
+                self.join()                   # a side-stream optimizer step / a backward beside the host loop may still be running
+                self._drop_prefetched()       # (its packed memory / message rows would be stale)
+                if on_dev:
+                    src, dst, ts, eidx = (a.contiguous() for a in (sources, destinations, edge_times, edge_idxs))
+                else:
+                    ts, src, dst, eidx = self._batch_to_dev([(edge_times, np.float64), (sources, np.int32), (destinations, np.int32),
+                                                             (edge_idxs, np.int32)])
+                if self.debug_checks:
+                    m = self.memory
+                    late = (m.has_msg > 0) & (m.last_update > m.msg_time)
+                    assert not bool(late.any()), "Trying to update memory to time in the past"      # memory_updater.py:25,41
+                B = N if batch_size is None else min(int(batch_size), N)
+                ws = self._observe_workspace(B)
+                st = self._state_struct(adjacency=False)
+                try:
+                    _lib.call("pfo_tgn_observe", ctypes.byref(self._cfg), ctypes.byref(st), src.data_ptr(), dst.data_ptr(),
+                              ts.data_ptr(), eidx.data_ptr(), N, B, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+                finally:
+                    self._ws_pool.append(((0, 0, 0), ws))
+                self.memory._any_msg = True
+                self.memory._state_version += 1
+        if append and N > 0:
+            host = (lambda a: a.cpu().numpy()) if on_dev else np.asarray
+            self.neighbor_finder.append(host(sources), host(destinations), host(edge_idxs), host(edge_times))
+        return N
+
     def _dev_keep(self, masks):
         """Injected dropout decisions for a parity test: ``{l: multipliers or booleans [n_l, H, K]}`` (level order, the layout
         of ``debug_dropout_masks`` and of the oracle's ``dropout_masks``) -> per layer, roots' level first, u8 [n_l, K] with bit
