@@ -242,6 +242,39 @@ int pfo_recommend_topk(const float* user_emb, const float* item_emb, const int32
                        const uint8_t* item_ok, int32_t k, int32_t* top_pos, float* top_score, int32_t* n_valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Portfolio-aware top-k: pfo_recommend_topk with the mean-variance rank fusion of main.py:243-289 applied to the whole candidate
+ * list of every user, in one launch; nothing of size U x I reaches memory unless a diagnostic array is asked for.
+ *   The first eleven arguments are pfo_recommend_topk's, and score(u,i) is its score to the bit (same matrix-core path, same
+ *   accumulation order).
+ *   cand_stock i32[I]: row of candidate i in `returns`; returns f64[n_days, n_stocks, n_ret]: log-returns, np.log(p[1:] / p[:-1])
+ *   per stock (MVSampler.returns); day_idx i32[U]; port_idx i32[U, port_stride], port_len i32[U] (clamped to [0, port_stride]):
+ *   the portfolio of u is the entries in [0, n_stocks) among the first port_len[u], duplicates counted as often as they occur;
+ *   none left (or port_idx NULL): the empty-portfolio branch, main.py:254.
+ *   y(u,i) = y_mv of main.py:243-271 in fp64, numpy's order of operations, no contraction - the arithmetic of pfo_mv_select
+ *   (from eight holdings on, np.sum adds the covariances pairwise and the last bits may differ from this sequential sum).
+ *   Admissible set A(u): the rules of pfo_recommend_topk (item_ok, excl_pos), minus candidates with cand_stock outside
+ *   [0, n_stocks), minus candidates whose y is NaN (a constant price series: 0 / 0); +-inf are ordinary values.  A user whose
+ *   day_idx is outside [0, n_days) has an empty A(u) and nothing is read for it.
+ *   Over A(u) alone, n = |A(u)|: invest_rank = average-tie rank of y (scipy rankdata, main.py:282); tgn_rank = average-tie rank
+ *   of the fp32 score, -0 == +0 (it stands in for the positional n..1 of main.py:283, "the model's order");
+ *   fused = lambda_mv * invest_rank + (1 - lambda_mv) * tgn_rank (main.py:286).
+ *   Order: stable ascending argsort of fused, reversed: fused descending, the LARGER position first among equal
+ *   values.  top_pos i32[U,k], top_score f32[U,k] (a zero score as +0), top_fused f64[U,k]: the first min(k, n) of that order,
+ *   the other slots -1 / -inf / -inf; n_valid i32[U] (optional) = min(k, n).
+ *   Diagnostics, each optional: score_out f32[U,I] (every i), y_out / fused_out f64[U,I] (NaN outside A(u)).
+ *   D % 4 == 0, D <= 256, 1 <= k <= 64, 1 <= I <= PFO_RECOMMEND_MV_MAX_ITEMS (scores, y and ranks of a user live in LDS),
+ *   2 <= n_ret <= 128, 1 <= n_t.
+ */
+#define PFO_RECOMMEND_MV_MAX_ITEMS 2048
+int pfo_recommend_mv_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                          int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                          const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                          int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                          const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                          int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                          double* y_out, double* fused_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Time-sorted adjacency built on the device: replaces get_neighbor_finder / NeighborFinder.__init__ (utils/utils.py:117-148).
  * Every edge e contributes (dst, eidx, ts) to row src[e] and (src, eidx, ts) to row dst[e]; rows are sorted by timestamp,
  * ties in edge order (Python's stable sorted(key=ts), utils.py:139).  A stable LSD radix sort of the 2E entries; the eight

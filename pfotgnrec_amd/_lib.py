@@ -14,6 +14,7 @@ _VP = C.c_void_p
 
 MAX_LAYERS = 4
 RECOMMEND_MAX_ITEMS = 65536     # PFO_RECOMMEND_MAX_ITEMS
+RECOMMEND_MV_MAX_ITEMS = 2048   # PFO_RECOMMEND_MV_MAX_ITEMS
 
 
 class TgnConfig(C.Structure):
@@ -86,6 +87,9 @@ PROTOTYPES = {
                                    C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_recommend_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32,
                                      _VP, _VP, _VP, _VP]),
+    "pfo_recommend_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                        _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
+                                        C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_adam_step": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                 _VP]),
     "pfo_csr_build_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),

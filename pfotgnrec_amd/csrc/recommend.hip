@@ -17,6 +17,7 @@
 // Users of one tile that sit in different blocks are served block by block (a pass per distinct block of the tile; callers
 // that sort their users by block get one pass).
 #include "common.hpp"
+#include "mv_value.hpp"
 
 #define PFO_REC_THREADS 256
 #define PFO_REC_TILE 16                       // users per workgroup = rows of the MFMA tile
@@ -37,6 +38,28 @@ __device__ __forceinline__ float rec_unordered(uint32_t o) {
   return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
 }
 __device__ __forceinline__ unsigned long long rec_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+// One 16 x 16 tile of scores: acc[i] = user row 4 q + i . candidate row `item` (this lane's column), uf the lane's pieces of its
+// user row.  The ONE place the accumulation order of a score is written down: both kernels below call it, so they agree to the bit.
+template <int NJ>
+__device__ __forceinline__ rec_f32x4 rec_score_tile(const float4 (&uf)[NJ], const float* __restrict__ items, int item, int D, int q) {
+  const float4* ip = reinterpret_cast<const float4*>(items + (int64_t)item * D);
+  float4 v[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int d = 16 * j + 4 * q;
+    v[j] = d < D ? ip[d >> 2] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  rec_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].x, v[j].x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].y, v[j].y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].z, v[j].z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].w, v[j].w, acc, 0, 0, 0);
+  }
+  return acc;
+}
 
 // NJ 16-byte pieces per lane cover a row of D <= 16 * NJ floats
 template <int NJ>
@@ -89,22 +112,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(
       // ---- A: scores of candidates [c0, c0 + n)
       const int n_tile = (n + 15) >> 4;
       for (int t = wave; t < n_tile; t += 4) {
-        const int item = min(c0 + 16 * t + r, I - 1);                // (a column beyond I repeats the last row; never read back)
-        const float4* ip = reinterpret_cast<const float4*>(items + (int64_t)item * D);
-        float4 v[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int d = 16 * j + 4 * q;
-          v[j] = d < D ? ip[d >> 2] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        rec_f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].x, v[j].x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].y, v[j].y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].z, v[j].z, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_16x16x4f32(uf[j].w, v[j].w, acc, 0, 0, 0);
-        }
+        const rec_f32x4 acc = rec_score_tile<NJ>(uf, items, min(c0 + 16 * t + r, I - 1), D, q);   // (a column beyond I repeats the last row; never read back)
         // acc[i] = score(user 4 q + i, candidate 16 t + r)
 #pragma unroll
         for (int i = 0; i < 4; ++i) sc[(4 * q + i) * ICS + 16 * t + r] = acc[i];
@@ -199,6 +207,175 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Portfolio-aware top-k: the rank fusion of main.py:243-289 over the WHOLE candidate list of a user, in the same launch shape.
+//   A  scores of the tile's 16 users against ALL I <= 2048 candidates of a block, as above (rec_score_tile), into LDS [16][I].
+//   Then the users of the pass one at a time, all four wavefronts on one user:
+//   B  y_mv of every candidate in fp64 (pfo_mv_value, the arithmetic mv_select_kernel runs) into LDS y[I]; a candidate that is
+//      not admissible - item_ok, cand_stock or the day outside the tables, a NaN y, then the exclusion list - is a NaN there:
+//      every comparison with it is false, so it takes part in no count below.
+//   C  average-tie ranks of y and of the fp32 score by counting over LDS (scipy's rankdata is less + (equal + 1) / 2), blended
+//      into `fused` in registers (a thread owns candidates tid, tid + 256, ...: eight at most); after a barrier fused replaces y.
+//   D  the place of a candidate in the canonical order (fused descending, the larger position first among equal values) is
+//      the number of candidates before it, by counting again; places below k write the output row.
+// LDS: 8 I (y / fused) + 16 (I + 4) 4 (scores) bytes, 144 KB at I = 2048 of the 160 KB a workgroup may take - one workgroup per
+// CU there, four at I = 500.  About 3 I^2 comparisons per user.
+#define PFO_RMV_PER_THREAD (PFO_RECOMMEND_MV_MAX_ITEMS / PFO_REC_THREADS)
+
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(
+    const float* __restrict__ user_emb, const float* __restrict__ item_emb, const int32_t* __restrict__ user_block, int64_t U,
+    int I, int n_t, int D, const int32_t* __restrict__ excl_pos, const int32_t* __restrict__ excl_len, int excl_stride,
+    const uint8_t* __restrict__ item_ok, const int32_t* __restrict__ cand_stock, const double* __restrict__ returns, int n_days,
+    int n_stocks, int n_ret, const int32_t* __restrict__ day_idx, const int32_t* __restrict__ port_idx,
+    const int32_t* __restrict__ port_len, int port_stride, double gamma, double lam, int k, int32_t* __restrict__ top_pos,
+    float* __restrict__ top_score, double* __restrict__ top_fused, int32_t* __restrict__ n_valid, float* __restrict__ score_out,
+    double* __restrict__ y_out, double* __restrict__ fused_out, int IC) {
+  const int ICS = IC + 4;
+  extern __shared__ double lds_mv[];
+  double* yv = lds_mv;                                               // [IC]: y, then fused, of the user being ranked
+  float* sc = reinterpret_cast<float*>(yv + IC);                     // [16][ICS]
+  __shared__ int ub[PFO_REC_TILE];
+  __shared__ int n_adm;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+  const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
+  const double nan = __builtin_nan("");
+
+  if (tid < PFO_REC_TILE) {
+    const int64_t u = u0 + tid;
+    int b = -1;
+    if (u < U) b = user_block ? min(max(user_block[u], 0), n_t - 1) : 0;
+    ub[tid] = b;
+  }
+  float4 uf[NJ];
+  {
+    const float4* up = reinterpret_cast<const float4*>(user_emb + min(u0 + r, U - 1) * D);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int d = 16 * j + 4 * q;
+      uf[j] = d < D ? up[d >> 2] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __syncthreads();
+  unsigned pending = 0;
+#pragma unroll
+  for (int i = 0; i < PFO_REC_TILE; ++i) pending |= (ub[i] >= 0 ? 1u : 0u) << i;
+
+  while (pending) {                                                  // one pass per distinct block of the tile
+    const int b = ub[__ffs(pending) - 1];
+    unsigned members = 0;
+#pragma unroll
+    for (int i = 0; i < PFO_REC_TILE; ++i) members |= (((pending >> i) & 1u) && ub[i] == b ? 1u : 0u) << i;
+    pending &= ~members;
+    const float* items = item_emb + (int64_t)b * I * D;
+
+    // ---- A: scores of all candidates (the previous pass ended on a barrier)
+    const int n_tile = (I + 15) >> 4;
+    for (int t = wave; t < n_tile; t += 4) {
+      const rec_f32x4 acc = rec_score_tile<NJ>(uf, items, min(16 * t + r, I - 1), D, q);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) sc[(4 * q + i) * ICS + 16 * t + r] = acc[i];
+    }
+    __syncthreads();
+
+    for (int us = 0; us < PFO_REC_TILE; ++us) {
+      if (!((members >> us) & 1u)) continue;                         // (the same for every thread)
+      const int64_t u = u0 + us;
+      const float* su = sc + us * ICS;
+      if (tid == 0) n_adm = 0;
+      // ---- B: y_mv, NaN where the candidate is not admissible
+      const int day = day_idx[u];
+      const bool day_ok = day >= 0 && day < n_days;                  // no day: nothing of this user's is read
+      const int plen = (day_ok && port_idx && port_stride > 0) ? min(max(port_len[u], 0), port_stride) : 0;
+      const double* dayp = returns + (int64_t)(day_ok ? day : 0) * n_stocks * n_ret;
+      for (int c = tid; c < I; c += PFO_REC_THREADS) {
+        if (score_out) score_out[u * I + c] = su[c];
+        double y = nan;
+        if (day_ok && (!item_ok || item_ok[c])) {
+          const int stock = cand_stock[c];
+          if (stock >= 0 && stock < n_stocks)
+            y = pfo_mv_value<true>(dayp, stock, n_stocks, n_ret, port_idx + u * port_stride, plen, gamma);
+        }
+        yv[c] = y;
+      }
+      __syncthreads();
+      {
+        const int len = (excl_pos && excl_stride > 0) ? min(max(excl_len[u], 0), excl_stride) : 0;
+        for (int e = tid; e < len; e += PFO_REC_THREADS) {
+          const int p = excl_pos[u * excl_stride + e];
+          if (p >= 0 && p < I) yv[p] = nan;                          // (duplicates store the same value)
+        }
+      }
+      __syncthreads();
+      // ---- C: ranks over the admissible candidates, blended
+      double fused[PFO_RMV_PER_THREAD];
+      int mine = 0;
+#pragma unroll
+      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) fused[m] = nan;
+#pragma unroll
+      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
+        const int c = tid + PFO_REC_THREADS * m;
+        if (PFO_REC_THREADS * m >= I) break;
+        if (c >= I) continue;
+        const double yi = yv[c];
+        if (y_out) y_out[u * I + c] = yi;
+        if (!(yi == yi)) continue;
+        const float si = su[c];
+        int ly = 0, ey = 0, ls = 0, es = 0;
+        for (int j = 0; j < I; ++j) {
+          const double yj = yv[j];
+          const float sj = su[j];
+          const bool aj = yj == yj;
+          ly += (yj < yi);
+          ey += (yj == yi);
+          ls += (aj && sj < si);
+          es += (aj && sj == si);                                    // (-0 == +0)
+        }
+        fused[m] = pfo_mv_blend(pfo_mv_avg_rank(ly, ey), pfo_mv_avg_rank(ls, es), lam);   // main.py:282-286
+        ++mine;
+      }
+      __syncthreads();                                               // every y has been read
+#pragma unroll
+      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
+        const int c = tid + PFO_REC_THREADS * m;
+        if (c < I) {
+          yv[c] = fused[m];
+          if (fused_out) fused_out[u * I + c] = fused[m];
+        }
+      }
+      if (mine) atomicAdd(&n_adm, mine);
+      __syncthreads();
+      // ---- D: the first k of the canonical order
+#pragma unroll
+      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
+        const int c = tid + PFO_REC_THREADS * m;
+        if (PFO_REC_THREADS * m >= I) break;
+        const double fi = fused[m];
+        if (c >= I || !(fi == fi)) continue;
+        int before = 0;
+        for (int j = 0; j < I; ++j) {
+          const double fj = yv[j];
+          before += (fj > fi) || (fj == fi && j > c);
+        }
+        if (before < k) {
+          const float s = su[c];
+          top_pos[u * k + before] = c;
+          top_score[u * k + before] = s == 0.f ? 0.f : s;            // a zero score is handed out as +0
+          top_fused[u * k + before] = fi;
+        }
+      }
+      const int n = min(k, n_adm);
+      if (tid >= n && tid < k) {
+        top_pos[u * k + tid] = -1;
+        top_score[u * k + tid] = -__builtin_inff();
+        top_fused[u * k + tid] = -__builtin_inf();
+      }
+      if (tid == 0 && n_valid) n_valid[u] = n;
+      __syncthreads();                                               // n_adm and y are free for the next user
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int pfo_recommend_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
@@ -230,6 +407,59 @@ extern "C" int pfo_recommend_topk(const float* user_emb, const float* item_emb, 
   else if (nj <= 11) PFO_REC_LAUNCH(11);
   else PFO_REC_LAUNCH(16);
 #undef PFO_REC_LAUNCH
+  PFO_LAUNCH_CHECK();
+  return PFO_OK;
+}
+
+extern "C" int pfo_recommend_mv_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                     int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                     const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                     int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                     const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                     int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                     double* y_out, double* fused_out, void* stream) {
+  PFO_REQUIRE(U >= 0 && U <= (int64_t)PFO_REC_TILE * 0x7fffffff, "U out of range");
+  PFO_REQUIRE(D > 0 && D % 4 == 0, "D must be a positive multiple of 4");
+  PFO_REQUIRE(D <= 256, "D must be at most 256");
+  PFO_REQUIRE(k >= 1 && k <= 64, "k must be in [1, 64]");
+  PFO_REQUIRE(I >= 1 && I <= PFO_RECOMMEND_MV_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MV_MAX_ITEMS]");
+  PFO_REQUIRE(n_t >= 1 && (int64_t)n_t * I <= 0x7fffffff, "n_t must be at least 1 and n_t * I fit 31 bits");
+  PFO_REQUIRE(excl_stride >= 0 && port_stride >= 0, "excl_stride and port_stride must not be negative");
+  PFO_REQUIRE(n_ret >= 2 && n_ret <= 128, "n_ret must be in [2, 128]");
+  PFO_REQUIRE(n_days > 0 && n_stocks > 0, "n_days and n_stocks must be positive");
+  if (U == 0) return PFO_OK;
+  PFO_REQUIRE(user_emb && item_emb && top_pos && top_score && top_fused, "null input or output");
+  PFO_REQUIRE(cand_stock && returns && day_idx, "null mean-variance input");
+  PFO_REQUIRE(!excl_pos || excl_stride == 0 || excl_len, "excl_pos without excl_len");
+  PFO_REQUIRE(!port_idx || port_stride == 0 || port_len, "port_idx without port_len");
+  PFO_REQUIRE((((uintptr_t)user_emb | (uintptr_t)item_emb) & 15) == 0, "user_emb and item_emb must be 16-byte aligned");
+  const int IC = (int)pfo_align_up(I, 16);
+  const size_t shmem = (size_t)IC * sizeof(double) + (size_t)PFO_REC_TILE * (IC + 4) * sizeof(float);
+  const dim3 grid((unsigned)pfo_ceil_div(U, PFO_REC_TILE)), block(PFO_REC_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  // (more than 64 KB of dynamic LDS has to be asked for, per kernel)
+#define PFO_RMV_LAUNCH(NJ)                                                                                                   \
+  do {                                                                                                                       \
+    if (shmem > 65536) {                                                                                                     \
+      const hipError_t ea__ = hipFuncSetAttribute(reinterpret_cast<const void*>(&recommend_mv_topk_kernel<NJ>),              \
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                   \
+      if (ea__ != hipSuccess) {                                                                                              \
+        pfo_set_error("%s: %zu bytes of LDS refused: %s", __func__, shmem, hipGetErrorString(ea__));                         \
+        return PFO_ERR_HIP;                                                                                                  \
+      }                                                                                                                      \
+    }                                                                                                                        \
+    PFO_KLAUNCH(recommend_mv_topk_kernel<NJ>, grid, block, shmem, s, user_emb, item_emb, user_block, U, (int)I, (int)n_t,    \
+                (int)D, excl_pos, excl_len, (int)excl_stride, item_ok, cand_stock, returns, (int)n_days, (int)n_stocks,      \
+                (int)n_ret, day_idx, port_idx, port_len, (int)port_stride, gamma, lambda_mv, (int)k, top_pos, top_score,     \
+                top_fused, n_valid, score_out, y_out, fused_out, IC);                                                        \
+  } while (0)
+  const int nj = (D + 15) / 16;
+  if (nj <= 2) PFO_RMV_LAUNCH(2);
+  else if (nj <= 4) PFO_RMV_LAUNCH(4);
+  else if (nj <= 8) PFO_RMV_LAUNCH(8);
+  else if (nj <= 11) PFO_RMV_LAUNCH(11);
+  else PFO_RMV_LAUNCH(16);
+#undef PFO_RMV_LAUNCH
   PFO_LAUNCH_CHECK();
   return PFO_OK;
 }

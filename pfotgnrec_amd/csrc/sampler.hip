@@ -5,6 +5,7 @@
 // coalesced row-tail copies.  One query per 16-lane group so a wave runs four binary searches
 // in lock-step, each search 16-ary (4 dependent loads for a 20k-entry row instead of 15).
 #include "common.hpp"
+#include "mv_value.hpp"
 
 #pragma clang fp contract(off)   // fp64 rank arithmetic must round exactly like numpy/python
 
@@ -275,7 +276,7 @@ extern "C" int pfo_neg_draw_dev(const uint8_t* item_avail, int32_t n_items, cons
 
 // ---------------------------------------------------------------------------------------------
 // K2: main.py:209-304.  One wavefront per interaction, one lane per candidate, fp64 throughout.
-// (np.mean's summation order: pfo_np_sum, common.hpp)
+// (the arithmetic of one candidate: mv_value.hpp, shared with the serving kernel of recommend.hip)
 #define PFO_MV_MAX_RET 128
 
 __global__ __launch_bounds__(64) void mv_select_kernel(const double* __restrict__ returns, int n_items, int n_ret,
@@ -294,28 +295,7 @@ __global__ __launch_bounds__(64) void mv_select_kernel(const double* __restrict_
   const double* day = returns + (int64_t)day_idx[b] * n_items * n_ret;
   const int plen = min(port_len[b], port_stride);
   double y = 0.0;
-  if (have) {
-    const double* ri = day + (int64_t)item * n_ret;
-    const double mu = pfo_np_sum(ri, n_ret) / (double)n_ret;                  // main.py:243
-    const double inv = 1.0 / (double)(n_ret - 1);                         // np.cov: c *= 1/(N - ddof)
-    double var = 0.0;
-    for (int t = 0; t < n_ret; ++t) var += (ri[t] - mu) * (ri[t] - mu);
-    var *= inv;
-    if (plen == 0) {
-      y = (mu / gamma) / var;                                             // main.py:254
-    } else {
-      double ssum = 0.0;
-      for (int p = 0; p < plen; ++p) {
-        const double* rp = day + (int64_t)port_idx[b * port_stride + p] * n_ret;
-        const double mp = pfo_np_sum(rp, n_ret) / (double)n_ret;
-        double cv = 0.0;
-        for (int t = 0; t < n_ret; ++t) cv += (ri[t] - mu) * (rp[t] - mp);
-        ssum += cv * inv;                                                 // np.sum(sigma_ij), main.py:268
-      }
-      const double sum_sigma = (1.0 / (double)plen) * ssum;               // y_uj/n_holding * sum
-      y = (mu / gamma - 0.5 * sum_sigma) / var;                           // main.py:271
-    }
-  }
+  if (have) y = pfo_mv_value<false>(day, item, n_items, n_ret, port_idx + b * port_stride, plen, gamma);   // main.py:243-271
   // invest_rank: scipy.stats.rankdata average ties (main.py:282); tgn_rank = n..1 (main.py:283)
   int less = 0, eq = 0;
   for (int j = 0; j < n_cand; ++j) {
@@ -323,9 +303,9 @@ __global__ __launch_bounds__(64) void mv_select_kernel(const double* __restrict_
     less += (yj < y);
     eq += (yj == y);
   }
-  const double invest = (double)less + ((double)eq + 1.0) * 0.5;
+  const double invest = pfo_mv_avg_rank(less, eq);
   const double tgn = (double)(n_cand - lane);
-  const double nr = invest * lam + tgn * (1.0 - lam);                     // main.py:286
+  const double nr = pfo_mv_blend(invest, tgn, lam);                       // main.py:286
   // order = stable ascending argsort, reversed (main.py:289 + tie policy)
   int pos = 0;
   for (int j = 0; j < n_cand; ++j) {

@@ -304,3 +304,101 @@ def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_l
               _lib.ptr(excl_pos.contiguous() if W else None), _lib.ptr(excl_len.contiguous() if W else None), W, _lib.ptr(item_ok), k,
               top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
     return top_pos, top_score, n_valid
+
+
+def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
+                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False):
+    """``recommend_topk`` with the mean-variance rank fusion of main.py:243-289 over every user's whole candidate list, in one
+    launch (``pfo_recommend_mv_topk``).
+
+    The arguments of ``recommend_topk`` mean what they mean there and the score is that kernel's to the bit.  cand_stock
+    i32[I]: row of candidate i in ``returns`` f64[n_days,n_stocks,n_ret] (``MVSampler.returns``); day_idx i32[U]; port_idx
+    i32[U,W], port_len i32[U] (None: whole rows): the stock rows user u holds, entries outside [0,n_stocks) ignored,
+    duplicates counted.  Over the admissible candidates of a user (the rules of ``recommend_topk``, minus cand_stock outside the
+    table, minus a NaN y; none for a day outside the table): fused = lambda_mv * rank(y_mv) + (1 - lambda_mv) * rank(score), both
+    average-tie ranks (``scipy.stats.rankdata``).
+
+    Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]): fused descending, the larger position
+    first among equal values; empty slots -1 / -inf / -inf.  ``want_all`` adds (score f32[U,I], y f64[U,I],
+    fused f64[U,I]), NaN in the last two where a candidate is not admissible."""
+    import operator
+    for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError("%s must be a 2-D float32 tensor" % name)
+    U, D = user_emb.shape
+    if item_emb.shape[1] != D:
+        raise ValueError("user_emb has %d columns, item_emb %d" % (D, item_emb.shape[1]))
+    if D == 0 or D % 4 != 0 or D > 256:
+        raise ValueError("D must be a positive multiple of 4, at most 256 (got %d)" % D)
+    try:
+        k = operator.index(k)
+    except TypeError:
+        raise ValueError("k must be an integer") from None
+    if not 1 <= k <= 64:
+        raise ValueError("k must be in [1, 64] (got %d)" % k)
+    if not isinstance(cand_stock, torch.Tensor) or cand_stock.dim() != 1 or cand_stock.dtype != torch.int32 or cand_stock.shape[0] < 1:
+        raise ValueError("cand_stock must be int32 [I]")
+    I = int(cand_stock.shape[0])
+    if I > _lib.RECOMMEND_MV_MAX_ITEMS:
+        raise ValueError("%d candidates, at most %d with the mean-variance rank" % (I, _lib.RECOMMEND_MV_MAX_ITEMS))
+    n_t = 1 if n_blocks is None else int(n_blocks)
+    if n_t < 1 or item_emb.shape[0] != n_t * I:
+        raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of %d candidates" % (item_emb.shape[0], n_t, I))
+    if user_block is not None and (user_block.dim() != 1 or user_block.shape[0] != U or user_block.dtype != torch.int32):
+        raise ValueError("user_block must be int32 [U]")
+    if not isinstance(returns, torch.Tensor) or returns.dim() != 3 or returns.dtype != torch.float64 or 0 in returns.shape:
+        raise ValueError("returns must be a float64 tensor [n_days, n_stocks, n_ret]")
+    n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
+    if not 2 <= n_ret <= 128:
+        raise ValueError("n_ret must be in [2, 128] (got %d)" % n_ret)
+    if not isinstance(day_idx, torch.Tensor) or tuple(day_idx.shape) != (U,) or day_idx.dtype != torch.int32:
+        raise ValueError("day_idx must be int32 [U]")
+    Wp = 0
+    if port_idx is not None:
+        if port_idx.dim() != 2 or port_idx.shape[0] != U or port_idx.dtype != torch.int32:
+            raise ValueError("port_idx must be int32 [U, W]")
+        Wp = int(port_idx.shape[1])
+        if port_len is not None and (tuple(port_len.shape) != (U,) or port_len.dtype != torch.int32):
+            raise ValueError("port_len must be int32 [U]")
+    elif port_len is not None:
+        raise ValueError("port_len without port_idx")
+    if item_ok is not None:
+        if item_ok.dim() != 1 or item_ok.shape[0] != I or item_ok.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("item_ok must be uint8 or bool [I]")
+    W = 0
+    if excl_pos is not None:
+        if excl_pos.dim() != 2 or excl_pos.shape[0] != U or excl_pos.dtype != torch.int32:
+            raise ValueError("excl_pos must be int32 [U, W]")
+        W = int(excl_pos.shape[1])
+        if excl_len is not None and (excl_len.dim() != 1 or excl_len.shape[0] != U or excl_len.dtype != torch.int32):
+            raise ValueError("excl_len must be int32 [U]")
+    elif excl_len is not None:
+        raise ValueError("excl_len without excl_pos")
+    dev = user_emb.device
+    _lib.require_gpu(dev)
+    for t in (item_emb, user_block, excl_pos, excl_len, item_ok, cand_stock, returns, day_idx, port_idx, port_len):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    user_emb, item_emb, returns = user_emb.contiguous(), item_emb.contiguous(), returns.contiguous()
+    if W and excl_len is None:
+        excl_len = torch.full((U,), W, dtype=torch.int32, device=dev)
+    if Wp and port_len is None:
+        port_len = torch.full((U,), Wp, dtype=torch.int32, device=dev)
+    if item_ok is not None:
+        item_ok = item_ok.contiguous().view(torch.uint8) if item_ok.dtype == torch.bool else item_ok.contiguous()
+    top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
+    top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
+    top_fused = torch.empty((U, k), dtype=torch.float64, device=dev)
+    n_valid = torch.empty(U, dtype=torch.int32, device=dev)
+    score = torch.empty((U, I), dtype=torch.float32, device=dev) if want_all else None
+    y = torch.empty((U, I), dtype=torch.float64, device=dev) if want_all else None
+    fused = torch.empty((U, I), dtype=torch.float64, device=dev) if want_all else None
+    _lib.call("pfo_recommend_mv_topk", user_emb.data_ptr(), item_emb.data_ptr(),
+              _lib.ptr(user_block.contiguous() if user_block is not None else None), U, I, n_t, D,
+              _lib.ptr(excl_pos.contiguous() if W else None), _lib.ptr(excl_len.contiguous() if W else None), W, _lib.ptr(item_ok),
+              _lib.ptr(cand_stock.contiguous()), returns.data_ptr(), n_days, n_stocks, n_ret, _lib.ptr(day_idx.contiguous()),
+              _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None), Wp,
+              float(gamma), float(lambda_mv), k, top_pos.data_ptr(), top_score.data_ptr(), top_fused.data_ptr(), n_valid.data_ptr(),
+              _lib.ptr(score), _lib.ptr(y), _lib.ptr(fused), _lib.stream_ptr())
+    out = (top_pos, top_score, top_fused, n_valid)
+    return out + (score, y, fused) if want_all else out

@@ -1,5 +1,6 @@
 """Read-only top-k recommendation behind ``TGN.recommend``: ``validate`` checks the arguments on the host alone (no device is
-asked for), ``assemble`` embeds users and candidates on the device and lets ``pfo_recommend_topk`` score and select."""
+asked for), ``assemble`` embeds users and candidates on the device and lets ``pfo_recommend_topk`` score and select - or, with
+a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` score, rank twice, blend and select."""
 import collections
 import operator
 
@@ -8,7 +9,10 @@ import torch
 
 from . import _lib
 
-Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len")
+Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv",
+                               defaults=(None,))
+# the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
+MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
 
 
 def _host(a):
@@ -26,7 +30,77 @@ def _int_vector(a, what, n_nodes):
     return h
 
 
-def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors):
+def _is_int_array(t):
+    return (t.dtype.kind in "iu") if isinstance(t, np.ndarray) else not (t.dtype.is_floating_point or t.dtype == torch.bool)
+
+
+def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts):
+    """The mean-variance keywords of ``TGN.recommend`` checked on the host (ValueError) -> ``MVQuery``, or None without any."""
+    if mv is None:
+        if portfolios is not None or day_idx is not None:
+            raise ValueError("portfolios / day_idx need mv (an MVSampler): without it the portfolio can only be excluded")
+        return None
+    for name in ("returns", "upper_u", "gamma", "lambda_mv", "day_of"):
+        if not hasattr(mv, name):
+            raise ValueError("mv must carry returns, upper_u, gamma, lambda_mv and day_of (an MVSampler); %s is missing" % name)
+    if portfolios is None:
+        raise ValueError("mv needs portfolios: packed (port_idx [U,W], port_len [U]) or one list of stock indices per user")
+    if len(mv.returns.shape) != 3:
+        raise ValueError("mv.returns must be [n_days, n_stocks, n_ret]")
+    if I > _lib.RECOMMEND_MV_MAX_ITEMS:
+        raise ValueError("with mv, items may hold at most %d candidates (got %d)" % (_lib.RECOMMEND_MV_MAX_ITEMS, I))
+    n_days = int(mv.returns.shape[0])
+    packed = (isinstance(portfolios, (tuple, list)) and len(portfolios) == 2
+              and isinstance(portfolios[0], (torch.Tensor, np.ndarray)) and portfolios[0].ndim == 2)
+    if packed:
+        port_idx, port_len = portfolios
+        if not isinstance(port_len, (torch.Tensor, np.ndarray)):
+            port_len = np.asarray(port_len)
+        if port_idx.shape[0] != U or tuple(port_len.shape) != (U,):
+            raise ValueError("packed portfolios must be (port_idx [U,W], port_len [U]) with U = %d" % U)
+        for t, what in ((port_idx, "port_idx"), (port_len, "port_len")):
+            if not _is_int_array(t):
+                raise ValueError("packed portfolios: %s must be integers" % what)
+    else:
+        try:
+            rows = [np.asarray(list(r)).reshape(-1) for r in portfolios]
+            if any(r.size and r.dtype.kind not in "iu" for r in rows):
+                raise TypeError
+            rows = [r.astype(np.int64) for r in rows]
+        except (TypeError, ValueError):
+            raise ValueError("portfolios must be a packed (port_idx, port_len) pair or one list of integer stock indices per user") from None
+        if len(rows) != U:
+            raise ValueError("portfolios lists %d users, users holds %d" % (len(rows), U))
+        W = max([len(r) for r in rows], default=0)
+        port_idx = np.full((U, W), -1, np.int32)
+        port_len = np.zeros(U, np.int32)
+        for i, r in enumerate(rows):
+            if r.size and (int(r.min()) < -(1 << 31) or int(r.max()) >= (1 << 31)):
+                raise ValueError("portfolios holds indices that do not fit 32 bits")
+            port_idx[i, :len(r)] = r
+            port_len[i] = len(r)
+    if day_idx is None:
+        if ts_h is None:
+            raise ValueError("day_idx=None takes the day from mv.day_of(timestamps): that needs timestamps on the host")
+        day = np.asarray(mv.day_of(ts_h.reshape(-1)))
+        day = np.broadcast_to(day.reshape(-1), (U,)) if scalar_ts else day
+    elif isinstance(day_idx, torch.Tensor):
+        day = day_idx
+    else:
+        day = np.asarray(day_idx)
+    if not _is_int_array(day):
+        raise ValueError("day_idx must be integers")
+    if day.ndim == 0:
+        day = day.reshape(1).expand(U) if isinstance(day, torch.Tensor) else np.broadcast_to(day.reshape(1), (U,))
+    if tuple(day.shape) != (U,):
+        raise ValueError("day_idx must be an integer or hold one value per user (%d), got shape %s" % (U, tuple(day.shape)))
+    if isinstance(day, np.ndarray) and day.size and (int(day.min()) < 0 or int(day.max()) >= n_days):
+        raise ValueError("day_idx holds days outside [0, %d)" % n_days)
+    return MVQuery(mv, port_idx, port_len, day)
+
+
+def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
+             day_idx=None):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
     try:
@@ -89,7 +163,8 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
                 ex_len[i] = len(r)
     if n_neighbors is None:
         n_neighbors = 20 if default_neighbors is None else default_neighbors
-    return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len)
+    mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts)
+    return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq)
 
 
 def assemble(tgn, q, return_embeddings=False):
@@ -128,6 +203,8 @@ def assemble(tgn, q, return_embeddings=False):
         if U == 0:
             empty = lambda dt: torch.empty((0, k), dtype=dt, device=dev)
             out = (empty(torch.int32), empty(torch.float32), torch.empty(0, dtype=torch.int32, device=dev))
+            if q.mv is not None:
+                out += (empty(torch.float64),)
             if return_embeddings:
                 out += (user_emb, item_emb, torch.empty(0, dtype=torch.int32, device=dev))
             return out
@@ -144,6 +221,8 @@ def assemble(tgn, q, return_embeddings=False):
         ok_d = None
         if q.item_ok is not None:
             ok_d = (to_dev(q.item_ok if q.ok_h is None else q.ok_h, torch.int64) != 0).to(torch.uint8)
+        if q.mv is not None:
+            return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings)
         if user_block is not None and n_t > 1:
             # users of one block side by side: the kernel serves a tile of 16 users in one pass per distinct block
             order = torch.argsort(user_block, stable=True)
@@ -160,3 +239,36 @@ def assemble(tgn, q, return_embeddings=False):
                 user_block = torch.zeros(U, dtype=torch.int32, device=dev)
             out += (user_emb, item_emb, user_block)
         return out
+
+
+def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings):
+    """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
+    portfolio rows following the users through the block sort."""
+    from .functional import recommend_mv_topk
+    dev, k, U, mv = tgn.device, q.k, q.U, q.mv.src
+    returns = mv.returns
+    if not isinstance(returns, torch.Tensor):
+        returns = torch.from_numpy(np.ascontiguousarray(returns, dtype=np.float64))
+    returns = returns.to(device=dev, dtype=torch.float64)
+    cand_stock = (items_d - (int(mv.upper_u) + 1)).contiguous()
+    day = to_dev(q.mv.day_idx, torch.int32)
+    port_idx = to_dev(q.mv.port_idx, torch.int32) if q.mv.port_idx.shape[1] > 0 else None
+    port_len = to_dev(q.mv.port_len, torch.int32) if port_idx is not None else None
+    args = (float(mv.gamma), float(mv.lambda_mv))
+    if user_block is not None and n_t > 1:
+        order = torch.argsort(user_block, stable=True)
+        sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
+        res = recommend_mv_topk(sel(user_emb), item_emb, k, cand_stock, returns, sel(day), sel(port_idx), sel(port_len), *args,
+                                sel(user_block), sel(excl_pos), sel(excl_len), ok_d, n_blocks=n_t)
+        res = tuple(torch.empty_like(t).index_copy_(0, order, t) for t in res)
+    else:
+        res = recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day, port_idx, port_len, *args,
+                                user_block if n_t > 1 else None, excl_pos, excl_len, ok_d, n_blocks=n_t)
+    top_pos, top_score, top_fused, n_valid = res
+    item_ids = torch.where(top_pos >= 0, items_d[top_pos.clamp(min=0).long()], torch.full_like(top_pos, -1))
+    out = (item_ids, top_score, n_valid, top_fused)
+    if return_embeddings:
+        if user_block is None:
+            user_block = torch.zeros(U, dtype=torch.int32, device=dev)
+        out += (user_emb, item_emb, user_block)
+    return out

@@ -1097,7 +1097,8 @@ class TGN(nn.Module):
             self._step, self._gru_applied_now = saved
         return emb
 
-    def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False):
+    def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
+                  mv=None, portfolios=None, day_idx=None):
         """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
         written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
         is left as found), no gradient is recorded and dropout is off.
@@ -1114,10 +1115,20 @@ class TGN(nn.Module):
         ``return_embeddings`` also (user_emb [U,D], item_emb [n_t*I,D], user_block i32[U]): the block of n_t = number of
         distinct timestamps each user was scored against.
 
+        With ``mv`` (an ``MVSampler``, or any object with ``returns``, ``upper_u``, ``gamma``, ``lambda_mv``, ``day_of``) the
+        order is the mean-variance rank fusion the model is trained towards (main.py:243-289) over the whole candidate list:
+        ``lambda_mv * rank(y_mv) + (1 - lambda_mv) * rank(score)``, one launch of ``pfo_recommend_mv_topk``.  portfolios: the
+        stock indices each user holds, packed (port_idx i32[U,W], port_len i32[U]) on host or device, or a list of per-user
+        lists (entries outside the return table are ignored; they weigh on y_mv, ``exclude`` still decides what is offered);
+        day_idx: an int or one per user, None: ``mv.day_of(timestamps)`` (host timestamps only); a candidate's stock row is
+        ``item - upper_u - 1``; at most 2048 candidates.  Returns (item_ids, scores, n_valid, fused f64[U,k]) - fused
+        descending, -inf in empty slots - then the embeddings as above.
+
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` are not (it would cost a
         read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
-        query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors)
+        query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
+                           portfolios, day_idx)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
