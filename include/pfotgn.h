@@ -487,6 +487,18 @@ int pfo_tgn_observe(const pfo_tgn_config* cfg, const pfo_tgn_state* st, const in
                     const double* ts, const int32_t* eidx, int64_t N, int32_t B, void* workspace, int64_t workspace_bytes,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Serving ingest: rows of RAW edge features, z-scored with the model's FROZEN column statistics, appended to the edge-feature
+ * table (abi 6, additive).  table[row0 + i][j] = (raw[i][j] - mean[j]) / stdv[j] for i < m, j < Ef - numpy's fp32
+ * `ef -= mean; ef /= std`: one correctly rounded subtraction, then one correctly rounded division (no FMA, no reciprocal), so a
+ * zero-variance column yields inf / NaN exactly where numpy does.  raw f32[m, Ef], mean / stdv f32[Ef], table f32[cap, Ef]: device
+ * pointers, rows contiguous; Ef is arbitrary (no alignment is assumed).  One launch on `stream`; rows outside [row0, row0 + m)
+ * are not touched.  m == 0 queues nothing.  PFO_ERR_INVALID - nothing is written: m < 0, Ef < 1, row0 outside [0, cap],
+ * row0 + m > cap, a null pointer with m > 0.
+ */
+int pfo_edge_rows_append(const float* raw, const float* mean, const float* stdv, int64_t m, int32_t Ef, float* table,
+                         int64_t row0, int64_t cap, void* stream);
+
 /* diagnostics for tests: copies of internals of the last forward (device pointers into the workspace) */
 typedef struct pfo_tgn_debug {
   const int32_t* n_touched;  /* [1] */

@@ -120,6 +120,7 @@ PROTOTYPES = {
     "pfo_tgn_observe_workspace_bytes": (C.c_int64, [C.POINTER(TgnConfig), C.c_int32]),
     "pfo_tgn_observe": (C.c_int, [C.POINTER(TgnConfig), C.POINTER(TgnState), _VP, _VP, _VP, _VP, C.c_int64, C.c_int32, _VP,
                                   C.c_int64, _VP]),
+    "pfo_edge_rows_append": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int64, _VP]),
     "pfo_tgn_debug_views": (C.c_int, [C.POINTER(TgnConfig), _VP, C.POINTER(TgnDebug)]),
     "pfo_prof_enable": (C.c_int, [C.c_int32]),
     "pfo_marks_enable": (C.c_int, [C.c_int32]),

@@ -97,7 +97,8 @@ class GraphedTrainStep:
         self._keep = (tgn._last_ws, tgn._adj_cache, tgn._pcache, tgn.flat_parameters, tgn.flat_grad, self.opt._m, self.opt._v,
                       tgn.node_raw_features, tgn.edge_raw_features,
                       None if mem is None else (mem.memory, mem.last_update, mem.msg_table, mem.msg_time, mem.has_msg))
-        self._guard = (nf, getattr(nf, "_version", 0), tgn._ws_caps, tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr())
+        self._guard = (nf, getattr(nf, "_version", 0), tgn._ws_caps, tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(),
+                       tgn._tables_version)
         return self
 
     def _check_guard(self):
@@ -106,10 +107,10 @@ class GraphedTrainStep:
         tgn = self.tgn
         nf = tgn.neighbor_finder
         now = (nf, getattr(nf, "_version", 0), tgn._ws_caps, tgn.flat_parameters.data_ptr(),
-               None if tgn.flat_grad is None else tgn.flat_grad.data_ptr())
+               None if tgn.flat_grad is None else tgn.flat_grad.data_ptr(), tgn._tables_version)
         if now[0] is not self._guard[0] or now[1:] != self._guard[1:]:
             raise RuntimeError("the captured step is stale (neighbour finder changed / appended to, workspace capacities grew, "
-                               "or the parameter buffers moved): capture() again")
+                               "a node / edge table grew or moved, or the parameter buffers moved): capture() again")
 
     def __call__(self, src, dst, ts, eidx, port_idx, port_len, day=None):
         """One training step on the given device-resident batch: six small copies and ONE graph launch."""

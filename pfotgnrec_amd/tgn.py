@@ -29,12 +29,24 @@ class _Holder(nn.Module):
     """Bare container used to reproduce the reference's parameter names."""
 
 
-def _normalise_edge_features(edge_features):
-    # tgn.py:38-41: fp32 z-score per column, the padding row 0 included
+def _normalise_with_stats(edge_features):
+    """tgn.py:38-41: fp32 z-score per column, the padding row 0 included -> (table, mean f32[Ef], std f32[Ef]): the column
+    mean of the table and the column standard deviation of the CENTRED table, the two vectors the reference throws away."""
     ef = np.asarray(edge_features).astype(np.float32)
-    ef -= ef.mean(axis=0)
-    ef /= ef.std(axis=0)
-    return ef.astype(np.float32)
+    mean = ef.mean(axis=0)
+    ef -= mean
+    std = ef.std(axis=0)
+    ef /= std
+    return ef.astype(np.float32), mean, std
+
+
+def _normalise_edge_features(edge_features):
+    return _normalise_with_stats(edge_features)[0]
+
+
+def _grown(capacity, need):
+    # geometric growth: a stream of serving ticks reallocates O(log n) times
+    return max(int(need), int(capacity) + (int(capacity) >> 1) + 16)
 
 
 class _Call:
@@ -143,7 +155,12 @@ class TGN(nn.Module):
         self.mean_time_shift_dst, self.std_time_shift_dst = mean_time_shift_dst, std_time_shift_dst
 
         self.node_raw_features = torch.from_numpy(np.asarray(node_features).astype(np.float32)).to(self.device).contiguous()
-        self.edge_raw_features = torch.from_numpy(_normalise_edge_features(edge_features)).to(self.device).contiguous()
+        ef, ef_mean, ef_std = _normalise_with_stats(edge_features)
+        self.edge_raw_features = torch.from_numpy(ef).to(self.device).contiguous()
+        # capacity storage of the two feature tables (``reserve``): the attributes are its leading rows
+        self._node_store, self._edge_store = self.node_raw_features, self.edge_raw_features
+        self._tables_version = 0          # bumped whenever a table grows or moves (a captured step goes stale)
+        self._set_stats(ef_mean, ef_std)
         self.n_nodes, self.n_node_features = self.node_raw_features.shape
         self.n_edge_features = self.edge_raw_features.shape[1]
         self.embedding_dimension = self.n_node_features
@@ -310,14 +327,16 @@ class TGN(nn.Module):
         for p, off, n, shape in self._views:
             p.data = self._flat[off:off + n].view(shape)
             p.grad = None
-        self.node_raw_features = fn(self.node_raw_features).contiguous()
-        self.edge_raw_features = fn(self.edge_raw_features).contiguous()
+        # the capacity storage moves as a whole; the attributes are re-made as its leading rows
+        self._node_store, self._edge_store = fn(self._node_store).contiguous(), fn(self._edge_store).contiguous()
+        self.node_raw_features = self._node_store[:self.node_raw_features.shape[0]]
+        self.edge_raw_features = self._edge_store[:self.edge_raw_features.shape[0]]
+        self._edge_stats_dev = fn(self._edge_stats_dev).contiguous()
+        self._tables_version += 1
         if self.use_memory:
             mem = self.memory
-            with torch.no_grad():
-                mem.memory.data = fn(mem.memory.data)
-                mem.last_update.data = fn(mem.last_update.data)
-            mem.msg_table, mem.msg_time, mem.has_msg = fn(mem.msg_table), fn(mem.msg_time), mem.has_msg.to(self._flat.device)
+            st = mem._stores()
+            mem._point([fn(st[0]), fn(st[1]), fn(st[2]), fn(st[3]), st[4].to(self._flat.device)], mem.n_nodes)
             mem.device = self._flat.device
             self.memory_updater.layer_norm._apply(fn)
         self.device = self._flat.device
@@ -1153,13 +1172,15 @@ class TGN(nn.Module):
 
         sources / destinations / edge_times / edge_idxs: numpy i64 / i64 / f64 / i64 like the entry points (range-checked:
         IndexError), or device tensors i32 / i32 / f64 / i32 (not checked: it would cost a read-back).  ``edge_idxs`` must
-        address EXISTING rows of the edge-feature table: growing that table (or the node table) is out of scope.
+        address EXISTING rows of the edge-feature table: interactions whose features (or nodes) the model has never seen go
+        through ``ingest``, which grows the tables and then calls this.
         ``batch_size``: interactions per batch, None = the whole input is one batch.  Batch boundaries are part of the
         semantics (messages are built from the memory as of their batch's persist): replay a log with the batch size it
         was - or would have been - trained with.  Chronological order is the caller's contract (``debug_checks`` asserts, like
         ``embed_device``, that no pending message is older than its node's last update).
         ``append``: the edges also go into the model's neighbour finder (``NeighborFinder.append``) behind the state update, so
-        that a later ``recommend`` sees them; a ``GraphedTrainStep`` captured over the finder goes stale.  Off by default:
+        that a later ``recommend`` sees them; a ``GraphedTrainStep`` captured over the finder goes stale - as does one captured
+        before ``reserve`` / ``add_nodes`` / ``add_edge_features`` moved or grew a table it holds the address of.  Off by default:
         a replay over a finder that already holds the log must not duplicate its edges.
         The data-parallel sharding is ignored (every rank observes the whole input: the state is replicated).
         Without memory there is no state: only the optional append happens."""
@@ -1204,6 +1225,217 @@ class TGN(nn.Module):
             host = (lambda a: a.cpu().numpy()) if on_dev else np.asarray
             self.neighbor_finder.append(host(sources), host(destinations), host(edge_idxs), host(edge_times))
         return N
+
+    # ------------------------------------------------------------------ serving: tables that grow
+    @property
+    def edge_feature_stats(self):
+        """``(mean f32[Ef], std f32[Ef])`` on the host: the column statistics the constructor normalised the edge-feature
+        table with - the mean of the table, the standard deviation of the centred table, both fp32 as numpy computed them.
+        FROZEN: rows added later (``add_edge_features``) are scaled with these and never with recomputed ones - the weights
+        were trained against this scaling.  They are NOT part of ``state_dict()`` (existing checkpoints keep loading): a model
+        restored next to a table that has grown since takes them from ``set_edge_feature_stats``."""
+        return self._edge_stats
+
+    def _set_stats(self, mean, std):
+        mean = np.ascontiguousarray(np.asarray(mean), dtype=np.float32).reshape(-1)
+        std = np.ascontiguousarray(np.asarray(std), dtype=np.float32).reshape(-1)
+        self._edge_stats = (mean, std)
+        self._edge_stats_dev = torch.from_numpy(np.stack([mean, std])).to(self.device).contiguous()     # [2, Ef]: mean | std
+
+    def set_edge_feature_stats(self, mean, std):
+        """Replaces the frozen statistics (``edge_feature_stats``), e.g. with those saved beside a checkpoint.  The table is
+        NOT re-normalised: only rows added from now on are scaled with the new vectors."""
+        mean, std = np.asarray(mean), np.asarray(std)
+        if mean.shape != (self.n_edge_features,) or std.shape != (self.n_edge_features,):
+            raise ValueError("mean and std must have shape (%d,)" % self.n_edge_features)
+        self._set_stats(mean, std)
+
+    @property
+    def node_capacity(self):
+        return int(self._node_store.shape[0])
+
+    @property
+    def edge_capacity(self):
+        return int(self._edge_store.shape[0])
+
+    def _quiesce(self):
+        # a side-stream optimizer step / a backward beside the host loop may still read the tables that are about to move
+        if self._flat.is_cuda:
+            self.join()
+            self._drop_prefetched()
+
+    def reserve(self, n_nodes=None, n_edges=None):
+        """Capacity for ``n_nodes`` rows of the node tables (``node_raw_features``, ``memory.memory``, ``memory.last_update``,
+        the pending-message table, its times and flags) and ``n_edges`` rows of the edge-feature table - rows, the padding
+        row 0 included.  Live rows are copied across bit for bit, rows behind them are zero; the attributes stay what they
+        were - contiguous leading-row views of the storage, same dtypes and shapes - but their addresses change when storage
+        is reallocated.  Capacity never shrinks (asking for what is there, or less, does nothing); asking for less than the
+        live rows raises ``ValueError``.  Without ``reserve`` the tables grow geometrically on demand.  Call it between steps
+        (see ``add_nodes``); a ``GraphedTrainStep`` captured before goes stale."""
+        if n_nodes is not None and int(n_nodes) < self.n_nodes:
+            raise ValueError("reserve(n_nodes=%d) is below the %d live rows" % (int(n_nodes), self.n_nodes))
+        if n_edges is not None and int(n_edges) < self.edge_raw_features.shape[0]:
+            raise ValueError("reserve(n_edges=%d) is below the %d live rows" % (int(n_edges), self.edge_raw_features.shape[0]))
+        if n_edges is not None and int(n_edges) > self.edge_capacity:
+            self._quiesce()
+            live = self.edge_raw_features.shape[0]
+            store = torch.zeros((int(n_edges), self.n_edge_features), dtype=torch.float32, device=self.device)
+            store[:live].copy_(self.edge_raw_features)
+            self._edge_store, self.edge_raw_features = store, store[:live]
+            self._tables_version += 1
+        if n_nodes is not None and int(n_nodes) > self.node_capacity:
+            self._quiesce()
+            live = self.n_nodes
+            store = torch.zeros((int(n_nodes), self.n_node_features), dtype=torch.float32, device=self.device)
+            store[:live].copy_(self.node_raw_features)
+            self._node_store, self.node_raw_features = store, store[:live]
+            if self.use_memory:
+                self.memory.resize(live, int(n_nodes))
+            self._tables_version += 1
+        return self
+
+    def add_edge_features(self, raw):
+        """Appends ``raw`` f32[m, Ef] RAW edge-feature rows - a host array (checked: width, finite values; staged through the
+        batch ring) or an fp32 device tensor (shape checked only) - behind the live rows, normalised with the frozen
+        ``edge_feature_stats`` by ONE launch of ``pfo_edge_rows_append`` (numpy's two fp32 operations, bit for bit).  Returns
+        the new rows' edge indices, i64[m]: the old row count onwards.  Nothing else changes; live rows keep every bit (they
+        move only when the capacity is exceeded: ``reserve``)."""
+        Ef = self.n_edge_features
+        if torch.is_tensor(raw):
+            if raw.dim() != 2 or raw.shape[1] != Ef or raw.dtype != torch.float32:
+                raise ValueError("device edge features must be an fp32 tensor [m, %d]" % Ef)
+            dev_rows = raw
+        else:
+            raw = np.asarray(raw)
+            if raw.ndim != 2 or raw.shape[1] != Ef:
+                raise ValueError("edge features must have shape [m, %d], got %s" % (Ef, raw.shape))
+            raw = raw.astype(np.float32, copy=False)
+            if not np.isfinite(raw).all():
+                raise ValueError("edge features must be finite")
+            dev_rows = None
+        m, n0 = int(raw.shape[0]), int(self.edge_raw_features.shape[0])
+        if n0 + m >= 2 ** 31:
+            raise ValueError("edge indices must fit in int32")
+        if m == 0:
+            return np.zeros(0, np.int64)
+        _lib.require_gpu(self.device)
+        if dev_rows is None:
+            dev_rows = self._batch_to_dev([(raw, np.float32)])[0]
+        dev_rows = dev_rows.contiguous()
+        if n0 + m > self.edge_capacity:
+            self.reserve(n_edges=_grown(self.edge_capacity, n0 + m))
+        st = self._edge_stats_dev
+        _lib.call("pfo_edge_rows_append", dev_rows.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), m, Ef, self._edge_store.data_ptr(),
+                  n0, self.edge_capacity, _lib.stream_ptr())
+        self.edge_raw_features = self._edge_store[:n0 + m]
+        self._cfg.n_edges_p1 = n0 + m
+        return np.arange(n0, n0 + m, dtype=np.int64)
+
+    def add_nodes(self, n, node_features=None):
+        """``n`` new nodes behind the last one; returns the first new node id (= the old ``n_nodes``).  Their rows of
+        ``node_raw_features`` are ``node_features`` f32[n, D] or zeros (the reference's node features are all zeros,
+        main.py:87); their memory, last update and pending-message state are the initial ones (zero, none pending).
+        Parameters, their ``.grad`` views, the flat buffers, the optimizer state, the step counter and the parameter cache
+        (its size does not depend on the node count) are untouched.  Invalidated: the workspace pool (workspaces are carved
+        per node count), the padded device adjacency, a batch prepared ahead of time, the ``debug_*`` views of the last
+        forward, and any ``GraphedTrainStep`` captured before.
+
+        Call it BETWEEN steps: a forward whose backward is still pending keeps the workspace and config it ran with, and must
+        have its backward run first."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        D = self.n_node_features
+        rows = None
+        if node_features is not None:
+            rows = node_features if torch.is_tensor(node_features) else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(node_features), dtype=np.float32))
+            if rows.dim() != 2 or tuple(rows.shape) != (n, D):
+                raise ValueError("node_features must have shape [%d, %d], got %s" % (n, D, tuple(rows.shape)))
+        first = self.n_nodes
+        if n == 0:
+            return first
+        if first + n >= 2 ** 31:
+            raise ValueError("node ids must fit in int32")
+        self._quiesce()
+        if first + n > self.node_capacity:
+            self.reserve(n_nodes=_grown(self.node_capacity, first + n))
+        if rows is not None:                                      # (rows behind the live ones are zero already)
+            self._node_store[first:first + n].copy_(rows.to(dtype=torch.float32))
+        self.node_raw_features = self._node_store[:first + n]
+        self.n_nodes = first + n
+        self._cfg.n_nodes = first + n
+        if self.use_memory:
+            self.memory.resize(first + n)                         # (bumps memory._state_version)
+        # outstanding calls hand their - now undersized - workspaces back to the list they took them from, not to the new one
+        self._ws_pool = []
+        self._adj_cache, self._keepalive = None, None             # (the indptr padding depends on n_nodes)
+        self._last_ws, self._last_call = None, None
+        self._tables_version += 1
+        if self._pcache is not None and self._pcache.numel() != _lib.byte_count("pfo_tgn_pcache_bytes", ctypes.byref(self._cfg)):
+            self._pcache, self._pcache_key = None, None           # (parameter-only buffers: today its size ignores the node count)
+        return first
+
+    def ingest(self, sources, destinations, edge_times, edge_features, batch_size=None, node_features=None):
+        """The serving tick: takes in interactions the model has NEVER seen - their feature rows are not in the edge-feature
+        table, their nodes may not exist yet - so that the next ``recommend`` accounts for them.  A thin chain of
+        ``add_nodes`` (when the input names new nodes), ``add_edge_features`` and ``observe(..., append=True)``: the state
+        semantics are ``observe``'s by shared code (batch boundaries included: ``batch_size``), every rank of a data-parallel
+        group ingests the whole input, and nothing else is written.  Per tick: one launch for the feature rows, ONE
+        ``pfo_tgn_observe`` call (4 launches per batch) and the CSR append; no Python work per batch.  Without memory only the
+        tables and the finder grow.  Returns ``(n_consumed, edge_idxs i64[N])`` - the indices the new rows got.
+
+        sources / destinations / edge_times: numpy i64 / i64 / f64 like ``observe``; edge_features: RAW rows f32[N, Ef]
+        (normalised here with the frozen ``edge_feature_stats``).  Node ids >= ``n_nodes`` are allowed only as exactly the
+        next consecutive ids; those nodes are added first, with ``node_features`` f32[n_new, D] as their rows in ascending id
+        order, zeros otherwise.  Host inputs are validated BEFORE anything is written (``ValueError``: lengths, feature width,
+        non-finite features, decreasing ``edge_times``, node ids < 1, ids that skip ahead, ``batch_size`` < 1): a rejected call
+        leaves the model bit for bit as it was.  Device tensors (i32 / i32 / f64 and f32[N, Ef]) are checked for shape and
+        dtype only and must name existing nodes (``add_nodes`` first)."""
+        on_dev = torch.is_tensor(sources)
+        N = int(sources.shape[0]) if on_dev else len(sources)
+        if any(len(a) != N for a in (destinations, edge_times, edge_features)):
+            raise ValueError("sources, destinations, edge_times and edge_features must have the same length")
+        if batch_size is not None and int(batch_size) < 1:
+            raise ValueError("batch_size must be at least 1")
+        Ef, n_new = self.n_edge_features, 0
+        if on_dev:
+            want = (torch.int32, torch.int32, torch.float64)
+            if any((not torch.is_tensor(a)) or a.dtype != dt or a.dim() != 1 for a, dt in zip((sources, destinations, edge_times), want)):
+                raise ValueError("device inputs must be 1-d tensors i32 / i32 / f64")
+            if not torch.is_tensor(edge_features) or edge_features.dim() != 2 or edge_features.shape[1] != Ef or edge_features.dtype != torch.float32:
+                raise ValueError("device edge features must be an fp32 tensor [N, %d]" % Ef)
+            if node_features is not None:
+                raise ValueError("device inputs must name existing nodes: add_nodes first")
+        else:
+            sources, destinations = np.asarray(sources), np.asarray(destinations)
+            edge_times, edge_features = np.asarray(edge_times, np.float64), np.asarray(edge_features)
+            if sources.ndim != 1 or destinations.ndim != 1 or edge_times.ndim != 1:
+                raise ValueError("sources, destinations and edge_times must be 1-d")
+            if edge_features.ndim != 2 or edge_features.shape[1] != Ef:
+                raise ValueError("edge features must have shape [N, %d], got %s" % (Ef, edge_features.shape))
+            if not np.isfinite(edge_features).all():
+                raise ValueError("edge features must be finite")
+            if N and (not np.isfinite(edge_times).all() or (np.diff(edge_times) < 0).any()):
+                raise ValueError("edge_times must be finite and chronological (non-decreasing)")
+            ids = np.concatenate([sources, destinations]).astype(np.int64)
+            if N and int(ids.min()) < 1:
+                raise ValueError("node ids must be >= 1 (node 0 is the padding node)")
+            fresh = np.unique(ids[ids >= self.n_nodes])
+            n_new = int(fresh.shape[0])
+            if n_new and not np.array_equal(fresh, np.arange(self.n_nodes, self.n_nodes + n_new)):
+                raise ValueError("new node ids must be exactly the next consecutive ids %d.. : got %s"
+                                 % (self.n_nodes, fresh[:8].tolist()))
+            if node_features is not None and tuple(np.shape(node_features)) != (n_new, self.n_node_features):
+                raise ValueError("node_features must have shape [%d, %d]: one row per new node" % (n_new, self.n_node_features))
+        if N == 0:
+            return 0, np.zeros(0, np.int64)
+        _lib.require_gpu(self.device)             # (nothing below has a host path: refuse before the first table grows)
+        if n_new:
+            self.add_nodes(n_new, node_features)
+        new_idxs = self.add_edge_features(edge_features)
+        eidx = torch.arange(int(new_idxs[0]), int(new_idxs[0]) + N, dtype=torch.int32, device=self.device) if on_dev else new_idxs
+        return self.observe(sources, destinations, edge_times, eidx, batch_size, append=True), new_idxs
 
     def _dev_keep(self, masks):
         """Injected dropout decisions for a parity test: ``{l: multipliers or booleans [n_l, H, K]}`` (level order, the layout

@@ -1,0 +1,286 @@
+"""CPU side of ``TGN.ingest``: the new symbol and entry points, the frozen edge-feature statistics, host-side validation
+(a rejected call leaves the model bit for bit as it was), and the capacity scheme of the tables on CPU tensors - none of which
+needs a kernel."""
+import numpy as np
+import pytest
+import torch
+
+
+def _host_model(use_memory=True, edge_features=None):
+    import pfotgnrec_amd as P
+    from pfotgnrec_amd.synthetic import SyntheticConfig, make_graph
+    g = make_graph(SyntheticConfig("t", 50, 10, 400, 8, 1, 4, 2), with_prices=False)
+    nf = P.get_neighbor_finder(g.data, False)
+    tgn = P.TGN(nf, g.node_features, g.edge_features if edge_features is None else edge_features, "cpu", n_layers=1, n_heads=2,
+                use_memory=use_memory, memory_dimension=8, message_function="identity")
+    return tgn, g
+
+
+def _snapshot(tgn):
+    """Row counts, addresses and every bit of every table."""
+    m = tgn.memory
+    tabs = [tgn.node_raw_features, tgn.edge_raw_features] + ([m.memory.data, m.last_update.data, m.msg_table, m.msg_time, m.has_msg]
+                                                            if m is not None else [])
+    return (tgn.n_nodes, tgn._cfg.n_nodes, tgn._cfg.n_edges_p1, tgn.neighbor_finder.n_nodes, tgn.neighbor_finder._version,
+            tgn._step, None if m is None else (m.n_nodes, m._state_version),
+            tuple((tuple(t.shape), t.data_ptr(), t.numpy().tobytes()) for t in tabs))
+
+
+def _fill(tgn, seed=0):
+    """Non-trivial content in every state table, so that 'preserved bitwise' says something."""
+    rs = np.random.RandomState(seed)
+    m = tgn.memory
+    with torch.no_grad():
+        for t in (m.memory, m.last_update, m.msg_table, m.msg_time):
+            t.copy_(torch.from_numpy(rs.randn(*t.shape).astype(np.float32)))
+        m.has_msg.copy_(torch.from_numpy((rs.rand(m.n_nodes) < 0.5).astype(np.uint8)))
+
+
+# ---------------------------------------------------------------------------------------------- 1. the new surface
+def test_library_and_model_export_the_ingest_surface():
+    import pfotgnrec_amd as P
+    from pfotgnrec_amd import _lib
+    lib = _lib.load()
+    assert hasattr(lib, "pfo_edge_rows_append") and "pfo_edge_rows_append" in _lib.PROTOTYPES
+    assert lib.pfo_abi_version() == 6
+    for name in ("ingest", "add_edge_features", "add_nodes", "reserve", "edge_feature_stats", "set_edge_feature_stats"):
+        assert hasattr(P.TGN, name), name
+
+
+def test_kernel_entry_rejects_bad_arguments_without_a_device():
+    """The argument checks run in front of the launch: no device is needed to see them refuse."""
+    from pfotgnrec_amd import _lib
+    call = lambda m, Ef, row0, cap: _lib.call("pfo_edge_rows_append", None, None, None, m, Ef, None, row0, cap, None)
+    with pytest.raises(_lib.PfoError, match="do not fit"):
+        call(3, 4, 8, 10)
+    with pytest.raises(_lib.PfoError, match="negative"):
+        call(-1, 4, 0, 10)
+    with pytest.raises(_lib.PfoError, match="Ef must be"):
+        call(1, 0, 0, 10)
+    with pytest.raises(_lib.PfoError, match="row0"):
+        call(1, 4, 11, 10)
+    with pytest.raises(_lib.PfoError, match="null pointer"):
+        call(2, 4, 8, 10)
+    call(0, 4, 10, 10)                                           # m == 0: nothing is queued, nothing is looked at
+
+
+# ---------------------------------------------------------------------------------------------- 2. frozen statistics
+def _numpy_normalisation(raw):
+    ef = np.asarray(raw).astype(np.float32)
+    mean = ef.mean(axis=0)
+    ef -= mean
+    std = ef.std(axis=0)
+    ef /= std
+    return ef, mean, std
+
+
+def test_statistics_of_a_random_9x5_table():
+    """The issue's table is [9, 5].  The model itself takes edge widths that are a multiple of 4 only (the library's config
+    check, unchanged), so a ``TGN`` cannot be built over five columns: the [9, 5] table goes through the function the
+    constructor normalises with, and the constructed model is checked below on the widths it accepts."""
+    from pfotgnrec_amd import tgn as T, _lib
+    raw = np.random.RandomState(7).randn(9, 5) * 3.0 + 1.5
+    want, mean, std = _numpy_normalisation(raw)
+    got, g_mean, g_std = T._normalise_with_stats(raw)
+    assert got.dtype == np.float32 and got.tobytes() == want.tobytes()
+    assert g_mean.dtype == np.float32 and g_mean.tobytes() == mean.tobytes()
+    assert g_std.dtype == np.float32 and g_std.tobytes() == std.tobytes()
+    assert T._normalise_edge_features(raw).tobytes() == want.tobytes()
+    with pytest.raises(_lib.PfoError, match="multiple of 4"):
+        _host_model(edge_features=np.random.RandomState(7).randn(401, 5))
+
+
+@pytest.mark.parametrize("shape", [(9, 4), (9, 8), (401, 4)])
+def test_constructed_model_keeps_the_statistics_and_todays_table(shape):
+    raw = np.random.RandomState(7).randn(*shape) * 3.0 + 1.5
+    tgn, _ = _host_model(edge_features=raw)
+    # the three numpy lines of tgn.py:38-41, as the constructor had them before it kept the statistics
+    ef = raw.astype(np.float32)
+    ef -= ef.mean(axis=0)
+    ef /= ef.std(axis=0)
+    assert tgn.edge_raw_features.numpy().tobytes() == ef.astype(np.float32).tobytes()
+    _, mean, std = _numpy_normalisation(raw)
+    g_mean, g_std = tgn.edge_feature_stats
+    assert g_mean.dtype == np.float32 and g_std.dtype == np.float32
+    assert g_mean.tobytes() == mean.tobytes() and g_std.tobytes() == std.tobytes()
+    dev = tgn._edge_stats_dev.numpy()
+    assert dev.tobytes() == np.stack([mean, std]).tobytes()
+    assert not any("stats" in k for k in tgn.state_dict())       # not part of the checkpoint
+    with pytest.raises(ValueError):
+        tgn.set_edge_feature_stats(mean[:-1], std)
+    tgn.set_edge_feature_stats(mean * 2, std * 3)
+    assert np.array_equal(tgn.edge_feature_stats[0], mean * 2) and np.array_equal(tgn._edge_stats_dev.numpy()[1], std * 3)
+    assert tgn.edge_raw_features.numpy().tobytes() == ef.tobytes()      # the table is not re-normalised
+
+
+# ---------------------------------------------------------------------------------------------- 3. validation
+def _tick(g, n_nodes, n=6):
+    d = g.data
+    return dict(sources=d.sources[:n].copy(), destinations=d.destinations[:n].copy(),
+                edge_times=d.timestamps[-1] + 1.0 + np.arange(n), edge_features=np.random.RandomState(1).randn(n, 4))
+
+
+@pytest.mark.parametrize("case", ["feature_width", "length", "decreasing_times", "skips_ahead", "batch_size_0", "node_zero",
+                                  "nan_feature", "node_features_rows"])
+def test_rejected_call_leaves_the_model_as_it_was(case):
+    tgn, g = _host_model(True)
+    _fill(tgn)
+    kw = _tick(g, tgn.n_nodes)
+    if case == "feature_width":
+        kw["edge_features"] = np.zeros((6, 5))
+    elif case == "length":
+        kw["destinations"] = kw["destinations"][:5]
+    elif case == "decreasing_times":
+        kw["edge_times"] = kw["edge_times"][::-1].copy()
+    elif case == "skips_ahead":
+        kw["destinations"][2] = tgn.n_nodes + 1                  # n_nodes itself is not named
+    elif case == "batch_size_0":
+        kw["batch_size"] = 0
+    elif case == "node_zero":
+        kw["sources"][0] = 0
+    elif case == "nan_feature":
+        kw["edge_features"][3, 1] = np.nan
+    elif case == "node_features_rows":
+        kw["destinations"][2] = tgn.n_nodes
+        kw["node_features"] = np.zeros((2, 8))
+    before = _snapshot(tgn)
+    with pytest.raises(ValueError):
+        tgn.ingest(**kw)
+    assert _snapshot(tgn) == before
+
+
+def test_a_model_on_the_host_refuses_before_it_grows_anything():
+    from pfotgnrec_amd import _lib
+    tgn, g = _host_model(True)                                  # (its tensors live on the host: refused with or without a device)
+    kw = _tick(g, tgn.n_nodes)
+    kw["destinations"][2] = tgn.n_nodes                          # a valid tick with one new node
+    before = _snapshot(tgn)
+    with pytest.raises(_lib.PfoError):
+        tgn.ingest(**kw)
+    assert _snapshot(tgn) == before
+    with pytest.raises(ValueError, match="shape"):
+        tgn.add_edge_features(np.zeros((3, 5)))
+    with pytest.raises(ValueError, match="finite"):
+        tgn.add_edge_features(np.full((3, 4), np.inf))
+    assert tgn.add_edge_features(np.zeros((0, 4))).shape == (0,) and _snapshot(tgn) == before
+    assert tgn.ingest(kw["sources"][:0], kw["destinations"][:0], kw["edge_times"][:0], kw["edge_features"][:0]) [0] == 0
+
+
+# ---------------------------------------------------------------------------------------------- 4. reserve
+def _tables(tgn):
+    m = tgn.memory
+    return dict(node=tgn.node_raw_features, edge=tgn.edge_raw_features, memory=m.memory.data, last_update=m.last_update.data,
+                msg_table=m.msg_table, msg_time=m.msg_time, has_msg=m.has_msg)
+
+
+def test_reserve_keeps_rows_and_attributes():
+    tgn, _ = _host_model(True)
+    _fill(tgn)
+    n, e = tgn.n_nodes, tgn.edge_raw_features.shape[0]
+    with pytest.raises(ValueError, match="below"):
+        tgn.reserve(n_nodes=n - 1)
+    with pytest.raises(ValueError, match="below"):
+        tgn.reserve(n_edges=e - 1)
+    before = {k: (t.numpy().copy(), t.dtype, tuple(t.shape)) for k, t in _tables(tgn).items()}
+    tgn.reserve(n_nodes=n + 7, n_edges=e + 13)
+    assert (tgn.node_capacity, tgn.edge_capacity, tgn.memory.capacity) == (n + 7, e + 13, n + 7)
+    after = _tables(tgn)
+    for k, (vals, dt, shape) in before.items():
+        t = after[k]
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous(), k
+        assert t.numpy().tobytes() == vals.tobytes(), k
+    assert isinstance(tgn.memory.memory, torch.nn.Parameter) and not tgn.memory.memory.requires_grad
+    assert isinstance(tgn.memory.last_update, torch.nn.Parameter) and not tgn.memory.last_update.requires_grad
+    # the attributes are leading-row views of the storage, and the rows behind them are zero
+    stores = [tgn._node_store, tgn._edge_store] + tgn.memory._stores()
+    for t, s, live in zip(after.values(), stores, [n, e, n, n, n, n, n]):
+        assert t.data_ptr() == s.data_ptr() and s.shape[0] == (e + 13 if s is tgn._edge_store else n + 7)
+        assert not s[live:].any()
+    assert (tgn.n_nodes, tgn._cfg.n_nodes, tgn._cfg.n_edges_p1, tgn.memory.n_nodes) == (n, n, e, n)
+    # idempotent: the same request again - or a smaller one that still covers the live rows - moves nothing
+    ptrs = [t.data_ptr() for t in after.values()]
+    tgn.reserve(n_nodes=n + 7, n_edges=e + 13)
+    tgn.reserve(n_nodes=n, n_edges=e)
+    tgn.reserve()
+    assert [t.data_ptr() for t in _tables(tgn).values()] == ptrs
+    assert (tgn.node_capacity, tgn.edge_capacity) == (n + 7, e + 13)
+    assert [k for k in tgn.state_dict() if k.startswith("memory.")] == ["memory.memory", "memory.last_update"]
+    assert tuple(tgn.state_dict()["memory.memory"].shape) == (n, 8)
+
+
+# ---------------------------------------------------------------------------------------------- 5. add_nodes
+@pytest.mark.parametrize("reserved", [False, True])
+def test_add_nodes_grows_every_table_with_zero_rows(reserved):
+    tgn, _ = _host_model(True)
+    _fill(tgn)
+    n = tgn.n_nodes
+    if reserved:
+        tgn.reserve(n_nodes=n + 5)
+    ptr = tgn.node_raw_features.data_ptr()
+    before = {k: t.numpy().copy() for k, t in _tables(tgn).items()}
+    backup = tgn.memory.backup_memory()
+    flat, step, version = tgn.flat_parameters.clone(), tgn._step, tgn.memory._state_version
+    tgn._ws_pool.append(((1, 1, 1), torch.zeros(4, dtype=torch.uint8)))
+    tgn._adj_cache, tgn._last_ws, tgn._last_call = ("x",), ("y",), ("z",)
+    feats = np.random.RandomState(2).rand(3, 8)
+    assert tgn.add_nodes(3, feats) == n
+    assert tgn.add_nodes(2) == n + 3 and tgn.add_nodes(0) == n + 5
+    N = n + 5
+    assert tgn.n_nodes == tgn.memory.n_nodes == tgn._cfg.n_nodes == N
+    assert (tgn.node_raw_features.data_ptr() == ptr) == reserved          # within capacity nothing moves
+    after = _tables(tgn)
+    for k, t in after.items():
+        if k == "edge":
+            assert t.numpy().tobytes() == before[k].tobytes()
+            continue
+        assert t.shape[0] == N and t.is_contiguous() and t.dtype == torch.from_numpy(before[k]).dtype, k
+        assert t[:n].numpy().tobytes() == before[k].tobytes(), k
+        if k == "node":
+            assert np.array_equal(t[n:n + 3].numpy(), feats.astype(np.float32)) and not t[n + 3:].any()
+        else:
+            assert not t[n:].any(), k
+    sd = tgn.state_dict()
+    assert tuple(sd["memory.memory"].shape) == (N, 8) and tuple(sd["memory.last_update"].shape) == (N,)
+    assert tgn._ws_pool == [] and tgn._adj_cache is None and tgn._last_ws is None and tgn._last_call is None
+    assert tgn.memory._state_version > version and tgn._step == step and torch.equal(flat, tgn.flat_parameters)
+    with pytest.raises(ValueError, match="shape"):
+        tgn.add_nodes(2, np.zeros((3, 8)))
+    with pytest.raises(ValueError):
+        tgn.add_nodes(-1)
+    # a backup taken before the growth restores into the leading rows; the nodes added since return to the initial state
+    m = tgn.memory
+    with torch.no_grad():
+        m.memory[n:] = 1.0
+        m.last_update[n:] = 2.0
+        m.msg_table[n:] = 3.0
+        m.msg_time[n:] = 4.0
+        m.has_msg[n:] = 1
+        m.memory[:n] = 9.0
+    m.restore_memory(backup)
+    for k in ("memory", "last_update", "msg_table", "msg_time", "has_msg"):
+        t = _tables(tgn)[k]
+        assert t[:n].numpy().tobytes() == before[k].tobytes() and not t[n:].any(), k
+    # ... one of today's size restores as ever, one with MORE rows than the model is refused
+    now = m.backup_memory()
+    m.restore_memory(now)
+    small, _ = _host_model(True)
+    with pytest.raises(ValueError, match="backup"):
+        small.memory.restore_memory(now)
+
+
+def test_add_nodes_without_memory_and_device_move_keep_the_storage():
+    tgn, _ = _host_model(False)
+    n, e = tgn.n_nodes, tgn.edge_raw_features.shape[0]
+    tgn.reserve(n_nodes=n + 4, n_edges=e + 4)
+    assert tgn.add_nodes(1) == n and tgn.memory is None and tgn.n_nodes == tgn._cfg.n_nodes == n + 1
+    mean, std = tgn.edge_feature_stats
+    tgn.to("cpu")                                               # _apply: the capacity storage and the statistics travel along
+    assert (tgn.node_capacity, tgn.edge_capacity) == (n + 4, e + 4)
+    assert tgn.node_raw_features.data_ptr() == tgn._node_store.data_ptr() and tgn.node_raw_features.shape[0] == n + 1
+    assert tgn.edge_raw_features.data_ptr() == tgn._edge_store.data_ptr() and tgn.edge_raw_features.shape[0] == e
+    assert np.array_equal(tgn._edge_stats_dev.numpy(), np.stack([mean, std]))
+    mem, _ = _host_model(True)
+    mem.reserve(n_nodes=n + 4)
+    mem.float()
+    assert mem.memory.capacity == n + 4 and mem.memory.memory.shape[0] == n and mem.memory.has_msg.dtype == torch.uint8
+    assert mem.memory.memory.data_ptr() == mem.memory._stores()[0].data_ptr()
