@@ -43,7 +43,10 @@ class FusedAdam(torch.optim.Optimizer):
         it there, so that ``loss.item()`` waits for the forward only and the host prepares the next batch (candidate draw,
         uploads, launches) while the device is still differentiating; the next forward - and ``state_dict()``, ``tgn.join()`` -
         wait for the step.  Gradients and parameters are IN FLIGHT after ``backward()`` / ``step()`` until then: read ``.grad`` or
-        a parameter only behind ``tgn.join()``.  One rank, eager mode; anything else takes the serial order.
+        a parameter only behind ``tgn.join()``.  One rank, eager mode; anything else takes the serial order.  ``step()`` goes to
+        that stream if and only if the model's newest native backward ran there and no step has consumed it (``tgn.beside``);
+        a backward on the caller's stream in between (``bpr_step`` without ``optimizer=``) sends it the serial way.  Out of
+        reach: parameter gradients torch autograd itself produces on the caller's stream after the fork.
         ``zero_grads_in_step``: a side-stream step (``step(side=True)``, i.e. ``bpr_step(..., optimizer=)``) also CLEARS the
         gradients it consumed - ``optimizer.zero_grad()`` folded into the optimizer's kernel, for loops that zero the gradients
         right after the step anyway (main.py:388-390 does): the next native backward then clears nothing on its critical path.
@@ -91,17 +94,9 @@ class FusedAdam(torch.optim.Optimizer):
         (``sync_steps`` folds it back into the host counters afterwards).
         ``side``: the kernel goes to the library's side stream, behind a backward that ran with ``defer_join``
         (``functional.bpr_step(..., optimizer=self)``); otherwise anything pending there is joined first."""
-        tgn = self.tgn
-        if (not side and step_dev is None and getattr(tgn, "_bwd_event", None) is not None and tgn._overlap_ok()
-                and _lib.stream_ptr() != tgn._backward_stream().cuda_stream):
-            # behind the backward on ITS stream (overlap_backward); the event the next forward waits for moves behind the step
-            bwd = tgn._backward_stream()
-            with _lib.on_stream(bwd):
-                out = self._step(closure, None, False)
-                ev = torch.cuda.Event()
-                ev.record(bwd)
-            tgn._set_backward_event(ev)
-            return out
+        beside = self.tgn.beside
+        if not side and step_dev is None and beside.takes_step():
+            return beside.step(lambda: self._step(closure, None, False))      # behind the backward on ITS stream (overlap_backward)
         return self._step(closure, step_dev, side)
 
     def _step(self, closure, step_dev, side):
@@ -140,6 +135,8 @@ class FusedAdam(torch.optim.Optimizer):
         # the kernel may clear what it read when the ranges cover the whole flat buffer (every tensor has a gradient)
         covered = bool(lo) and lo[0] == 0 and hi[-1] == tgn.flat_parameters.numel() and all(hi[j] == lo[j + 1] for j in range(len(lo) - 1))
         zero_all = bool(side and self.zero_grads_in_step and step_dev is None and covered and len(lo) <= MAXR)
+        args = (tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr())
+        hyp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
         ordered = side and getattr(tgn, "dp_ordered", False) and step_dev is None and 0 < tgn.grad_split < tgn.flat_parameters.numel()
         if ordered:
             # Two buckets in order of first use: [0, split) = time encoder, GRU, layer 1 - the next forward reads them on the
@@ -154,9 +151,6 @@ class FusedAdam(torch.optim.Optimizer):
                     cut_lo.append(a); cut_hi.append(b); cut_st.append(t)
             first = [j for j in range(len(cut_lo)) if cut_hi[j] <= split]
             later = [j for j in range(len(cut_lo)) if cut_lo[j] >= split]
-            args = (tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr())
-            hyp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
-
             zflag = 4 if zero_all else 0
 
             def run(idx, last_bucket):
@@ -178,29 +172,16 @@ class FusedAdam(torch.optim.Optimizer):
             tgn.wait_comm_stream()
         for i in range(0, len(lo), MAXR):
             k = min(MAXR, len(lo) - i)
+            ranges = (k, (ctypes.c_int64 * k)(*lo[i:i + k]), (ctypes.c_int64 * k)(*hi[i:i + k]), (ctypes.c_int32 * k)(*st[i:i + k]))
             if step_dev is not None:
-                _lib.call("pfo_adam_step_ranges_dev", tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), self._m.data_ptr(),
-                          self._v.data_ptr(), k, (ctypes.c_int64 * k)(*lo[i:i + k]), (ctypes.c_int64 * k)(*hi[i:i + k]),
-                          (ctypes.c_int32 * k)(*st[i:i + k]), step_dev.data_ptr(), float(g["lr"]), float(g["betas"][0]),
-                          float(g["betas"][1]), float(g["eps"]), _lib.stream_ptr())
-                continue
-            if side and zero_all:
-                _lib.call("pfo_tgn_adam_side_bucket", tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), self._m.data_ptr(),
-                          self._v.data_ptr(), k, (ctypes.c_int64 * k)(*lo[i:i + k]), (ctypes.c_int64 * k)(*hi[i:i + k]),
-                          (ctypes.c_int32 * k)(*st[i:i + k]), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                          float(g["eps"]), 4)
+                _lib.call("pfo_adam_step_ranges_dev", *args, *ranges, step_dev.data_ptr(), *hyp, _lib.stream_ptr())
+            elif side and zero_all:
+                _lib.call("pfo_tgn_adam_side_bucket", *args, *ranges, *hyp, 4)
                 tgn._grad_zeroed = True
-                continue
-            if side:
-                _lib.call("pfo_tgn_adam_side", tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), self._m.data_ptr(),
-                          self._v.data_ptr(), k, (ctypes.c_int64 * k)(*lo[i:i + k]), (ctypes.c_int64 * k)(*hi[i:i + k]),
-                          (ctypes.c_int32 * k)(*st[i:i + k]), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                          float(g["eps"]))
-                continue
-            _lib.call("pfo_adam_step_ranges", tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), self._m.data_ptr(),
-                      self._v.data_ptr(), k, (ctypes.c_int64 * k)(*lo[i:i + k]), (ctypes.c_int64 * k)(*hi[i:i + k]),
-                      (ctypes.c_int32 * k)(*st[i:i + k]), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                      float(g["eps"]), _lib.stream_ptr())
+            elif side:
+                _lib.call("pfo_tgn_adam_side", *args, *ranges, *hyp)
+            else:
+                _lib.call("pfo_adam_step_ranges", *args, *ranges, *hyp, _lib.stream_ptr())
         if lo:
             # the kernel above wrote the parameters behind torch's back: the model's parameter cache (composite weights, weight
             # images) is rebuilt right here, on the library's side stream behind this kernel - beside the next batch's sampling
@@ -214,7 +195,9 @@ def overlap_backward(tgn, optimizer):
     ``torch.optim.Adam``): ``loss.backward()`` leaves the native backward on a stream of its own, and ``optimizer.step()`` -
     wrapped here - runs its kernels on that stream behind it, so the loop's ``loss.item()`` (main.py:390) waits for the forward
     only and the host prepares the next batch beside the backward.  The next forward, ``state_dict()`` and ``tgn.join()`` wait
-    for the step; read ``.grad`` or a parameter from torch only behind ``tgn.join()``.  ``optimizer.zero_grad(set_to_none=
+    for the step; read ``.grad`` or a parameter from torch only behind ``tgn.join()``.  As with ``FusedAdam``, ``step()`` goes to
+    that stream only behind a native backward that ran there and that no step has consumed (``tgn.beside``), else the serial way,
+    and parameter gradients torch autograd itself produces after the fork are out of reach.  ``optimizer.zero_grad(set_to_none=
     False)`` joins first (its kernels run on the caller's stream).  Returns the optimizer."""
     tgn.overlap_backward = True
     if isinstance(optimizer, FusedAdam) or getattr(optimizer, "_pfo_overlap", None) is tgn:
@@ -222,16 +205,10 @@ def overlap_backward(tgn, optimizer):
     plain_step, plain_zero = optimizer.step, optimizer.zero_grad
 
     def step(*args, **kwargs):
-        if getattr(tgn, "_bwd_event", None) is None or not tgn._overlap_ok():
-            tgn.join()
-            return plain_step(*args, **kwargs)
-        bwd = tgn._backward_stream()
-        with _lib.on_stream(bwd):
-            out = plain_step(*args, **kwargs)
-            ev = torch.cuda.Event()
-            ev.record(bwd)
-        tgn._set_backward_event(ev)
-        return out
+        if tgn.beside.takes_step():
+            return tgn.beside.step(lambda: plain_step(*args, **kwargs))
+        tgn.join()
+        return plain_step(*args, **kwargs)
 
     def zero_grad(set_to_none=True):
         if not set_to_none:

@@ -77,6 +77,72 @@ class _Call:
             pass
 
 
+class _Beside:
+    """The backward beside the host loop (``tgn.overlap_backward``): ``loss.backward()`` leaves the native backward - and
+    ``optimizer.step()`` its kernel - on ``stream``, and whoever touches parameters, gradients or a workspace next waits for
+    ``event`` (``join``).  Only these methods write the fields.  Invariant: a step goes to ``stream`` if and only if the newest
+    native backward of this model ran there and no step has consumed it yet (``fresh``): ``launch`` sets that, a native backward
+    on any other stream and ``step`` clear it; otherwise ``step()`` takes the serial route (``tgn.join()``, then the caller's
+    stream).  Out of reach: parameter gradients torch autograd itself produces on the caller's stream after the fork."""
+    __slots__ = ("tgn", "stream", "event", "joined", "home", "hold", "fresh")
+
+    def __init__(self, tgn):
+        self.tgn, self.stream = tgn, None         # (the stream is made by the first ``launch``: no device API is touched here)
+        self.event, self.joined = None, set()     # behind the newest backward / step on ``stream``; the streams that wait for it
+        self.home, self.hold = None, []           # the stream the newest backward forked from; what the work in flight reads
+        self.fresh = False
+
+    @property
+    def in_flight(self):
+        """Work on ``stream`` that the stream it forked from does not wait for yet."""
+        return self.event is not None and self.home not in self.joined
+
+    def takes_step(self):
+        return self.fresh and self.tgn._overlap_ok()
+
+    def launch(self, call, d_emb):
+        """``_native_backward`` on ``stream``, behind everything the current stream holds (the gradient rows)."""
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=self.tgn.device)
+        cur, side = _lib.current_stream(), self.stream
+        fork = torch.cuda.Event()
+        fork.record(cur)
+        side.wait_event(fork)
+        with _lib.on_stream(side):
+            self.tgn._native_backward(call, d_emb)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        # (the workspace too: the call hands it back to the pool at once, and the pool may drop it before ``home`` has waited)
+        self.hold.append((d_emb, call.roots, call.root_ts, call.extra, call.keep, call.draws, call.ws))
+        self.home, self.event, self.joined, self.fresh = cur.cuda_stream, ev, set(), True
+
+    def step(self, fn):
+        """``fn()`` - an optimizer step, when ``takes_step()`` - on ``stream`` behind the backward; ``event`` moves behind it."""
+        self.fresh = False
+        with _lib.on_stream(self.stream):
+            out = fn()
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        self.event, self.joined = ev, set()
+        return out
+
+    def join(self, backward=False):
+        """The current stream waits for what is in flight, once per stream and event (never ``stream`` itself: the optimizer's
+        kernel queues behind the backward there).  What that work reads is let go when the stream it was allocated on has
+        waited: the allocator may then hand the memory to that stream again.  ``backward``: a native backward follows."""
+        if self.event is None:                    # (idle - every model without a device: no device API is touched)
+            return
+        key = _lib.stream_ptr()
+        if key == self.stream.cuda_stream:
+            return
+        self.fresh = self.fresh and not backward
+        if key not in self.joined:
+            _lib.current_stream().wait_event(self.event)
+            self.joined.add(key)
+            if key == self.home:
+                self.hold = []
+
+
 _TORCH_OF = {"float64": torch.float64, "float32": torch.float32, "int32": torch.int32, "int64": torch.int64, "uint8": torch.uint8}
 
 
@@ -115,7 +181,7 @@ class _EmbedFn(torch.autograd.Function):
             if d_emb is None:
                 d_emb = torch.cat(d_out)
         if ctx.tgn._overlap_ok():
-            ctx.tgn._backward_beside(ctx.call, d_emb)
+            ctx.tgn.beside.launch(ctx.call, d_emb)
         else:
             ctx.tgn._native_backward(ctx.call, d_emb)
         ctx.call.release()
@@ -202,9 +268,8 @@ class TGN(nn.Module):
         self._zero_next = False
         self._grad_zeroed = False         # the optimizer's kernel cleared the flat gradient buffer (FusedAdam(zero_grads_in_step=True))
         # FusedAdam(tgn, overlap_backward=True): loss.backward() leaves the native backward - and optimizer.step() its kernel - on
-        # a stream of their own, so that the loop's per-batch ``loss.item()`` (main.py:390) waits for the forward only
+        # a stream of their own (``self.beside``), so that the loop's per-batch ``loss.item()`` (main.py:390) waits for the forward only
         self.overlap_backward = False
-        self._bwd_event, self._bwd_hold, self._bwd_joined, self._bwd_home = None, [], set(), None
         self.eval_chunk_roots = 16384     # roots per forward-only pass (evaluation.py scores B*(2+N_ITEMS) roots per batch)
         self.eval_dedup = True            # forward-only passes embed every distinct (node, time) root once
         # memory_updater.py:25,41 assert that no pending message is older than its node's last update; the check reads
@@ -271,7 +336,8 @@ class TGN(nn.Module):
         self._pcache, self._pcache_key = None, None
         self._prefetched = None           # (batch key, dropout_p, call) of ``prefetch``
         self._stage_ring, self._stage_next = [None, None], -1     # ``_batch_to_dev``: (pinned buffer, its numpy view, event) twice
-        self._side_stream, self._pre_stream, self._pre_main, self._bwd_stream = None, None, None, None
+        self._side_stream, self._pre_stream, self._pre_main = None, None, None
+        self.beside = _Beside(self)       # idle (``_apply`` joined the old one first)
         self._comm_pending = None         # the communication stream the top block's all-reduce of this step is in flight on
         self._bucket_event, self._bucket_event_fresh = None, False
         self._mid_event, self._mid_event_fresh = None, False   # recorded by the native backward in front of layer 1's attention backward
@@ -511,7 +577,7 @@ class TGN(nn.Module):
 
     def _native_forward(self, call, out=None):
         _lib.require_gpu(self.device)
-        self._join_backward()
+        self.beside.join()
         # torch wrote the parameters on the caller's stream since the last native forward (p.copy_(), a torch optimizer ...):
         # that write is ordered against nothing the library left on its side stream, and the forward would not fork from
         # the caller's stream while a deferred step is pending there - join first (a no-op when nothing is pending)
@@ -588,50 +654,13 @@ class TGN(nn.Module):
         library's side stream, and for a whole backward + step that ``overlap_backward`` left on theirs (no-op when nothing is
         pending)."""
         if self._flat.is_cuda:
-            self._join_backward()
+            self.beside.join()
             _lib.call("pfo_tgn_join", _lib.stream_ptr())
 
     # ------------------------------------------------------------------ backward beside the host loop (overlap_backward)
     def _overlap_ok(self):
         return (self.overlap_backward and self.dp_world == 1 and self._flat.is_cuda and not self.record_mid_event
                 and not self.dp_bucketed and not torch.cuda.is_current_stream_capturing())
-
-    def _backward_stream(self):
-        if self._bwd_stream is None:
-            self._bwd_stream = torch.cuda.Stream(device=self.device)
-        return self._bwd_stream
-
-    def _join_backward(self):
-        """The current stream waits for what ``overlap_backward`` left in flight (once per stream and event).  The tensors that
-        work reads (gradient rows, the call's roots) are let go when the stream they were allocated on has waited: the
-        allocator may then hand their memory to that stream again."""
-        ev = self._bwd_event
-        if ev is None:
-            return
-        key = _lib.stream_ptr()
-        if key in self._bwd_joined or (self._bwd_stream is not None and key == self._bwd_stream.cuda_stream):
-            return                                                # (the backward stream itself: the optimizer's kernel behind the backward)
-        _lib.current_stream().wait_event(ev)
-        self._bwd_joined.add(key)
-        if key == self._bwd_home:
-            self._bwd_hold = []
-
-    def _set_backward_event(self, ev):
-        self._bwd_event, self._bwd_joined = ev, set()
-
-    def _backward_beside(self, call, d_emb):
-        """``_native_backward`` on the backward stream, behind everything the current stream holds (the gradient rows)."""
-        cur, side = _lib.current_stream(), self._backward_stream()
-        fork = torch.cuda.Event()
-        fork.record(cur)
-        side.wait_event(fork)
-        with _lib.on_stream(side):
-            self._native_backward(call, d_emb)
-            ev = torch.cuda.Event()
-            ev.record(side)
-        self._bwd_hold.append((d_emb, call.roots, call.root_ts, call.extra, call.keep, call.draws))
-        self._bwd_home = cur.cuda_stream
-        self._set_backward_event(ev)
 
     def state_dict(self, *args, **kwargs):
         self.join()
@@ -647,7 +676,7 @@ class TGN(nn.Module):
 
     def _native_backward(self, call, d_emb, mean=None, defer_join=False):
         """``mean`` = (src f32[n], out f32[1]): a mean the backward takes on its side stream (the BPR loss value)."""
-        self._join_backward()             # (a no-op on the backward stream itself and when nothing is in flight)
+        self.beside.join(backward=True)   # (a no-op on the backward stream itself and when nothing is in flight)
         zero_first = self._attach_grads(call.gru_applied, defer_zero=True) or self._zero_next
         self._zero_next = False
         if self._grad_zeroed:             # (the buffer IS clear: the optimizer's side-stream kernel wrote the zeros behind its reads)
@@ -697,7 +726,7 @@ class TGN(nn.Module):
         return self._grad_split
 
     def _native_update_state(self, call, src, dst, ts, eidx):
-        self._join_backward()
+        self.beside.join()
         self.memory._any_msg = True
         st = self._state_struct()
         _lib.call("pfo_tgn_update_state", ctypes.byref(call.cfg), ctypes.byref(st), src.data_ptr(), dst.data_ptr(),
@@ -782,7 +811,7 @@ class TGN(nn.Module):
         _lib.require_gpu(self.device)
         if bool(getattr(self.neighbor_finder, "uniform", False)) or not torch.is_grad_enabled():
             return False
-        self._join_backward()             # (overlap_backward: the workspace this call takes may be the one that backward reads)
+        self.beside.join()               # (overlap_backward: the workspace this call takes may be the one that backward reads)
         self._drop_prefetched()
         K = int(n_neighbors)
         B, lo, hi, b, groups, R, extra, dropout_p = self._batch_plan(src, dst, extra_roots, extra_repeat)

@@ -282,7 +282,7 @@ def test_backward_beside_the_host_loop_equals_the_serial_order(kind):
             loss = -torch.mean(torch.log(torch.sigmoid(torch.mean(pos - ngs, dim=1))))
             loss.backward()
             if overlap and step == 1:
-                assert tgn._bwd_event is not None                    # in flight: nothing on this stream waits for it yet
+                assert tgn.beside.in_flight                          # in flight: nothing on this stream waits for it yet
             opt.step()
             losses.append(loss.item())
             tgn.memory.detach_memory()

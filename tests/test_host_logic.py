@@ -136,15 +136,18 @@ def test_call_and_model_state_is_explicit():
     c.release()                                                                # (nothing to hand back: no error)
     tgn = _cpu_model()
     initial = lambda t: (t._grad_views, t._seen_versions, t._stage_ring, t._stage_next, t._pcache, t._pcache_key, t._prefetched,
-                         t._flat_grad, t._ws_pool, t._last_ws, t._last_call, t._adj_cache, t._side_stream, t._bucket_event)
+                         t._flat_grad, t._ws_pool, t._last_ws, t._last_call, t._adj_cache, t._side_stream, t._bucket_event,
+                         t.beside.event, list(t.beside.hold), t.beside.stream, t.beside.in_flight, t.beside.takes_step())
     fresh = initial(tgn)
-    assert fresh == (None, None, [None, None], -1, None, None, None, None, [], None, None, None, None, None)
+    assert fresh == (None, None, [None, None], -1, None, None, None, None, [], None, None, None, None, None, None, [], None, False, False)
     for move in (lambda t: t.float(), lambda t: t.to("cpu")):
         tgn._attach_grads()
         assert tgn._grad_views is not None and tgn.hot_parameters()[0].grad is not None
         tgn._seen_versions, tgn._stage_ring, tgn._pcache, tgn._last_call = (1, 2), [("host", "view", "event"), None], "cache", (0,) * 6
+        old = tgn.beside
+        old.hold.append(("of the old device",))
         flat = tgn.flat_parameters.clone()
-        assert move(tgn) is tgn and initial(tgn) == fresh
+        assert move(tgn) is tgn and initial(tgn) == fresh and tgn.beside is not old
         assert torch.equal(tgn.flat_parameters, flat) and all(p.grad is None for p in tgn.hot_parameters())
         assert tgn._param_key() == tgn._torch_versions() + (tgn._param_epoch, tgn.flat_parameters.data_ptr())
 
