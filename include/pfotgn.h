@@ -293,6 +293,23 @@ int pfo_csr_append(const int64_t* old_indptr, const int32_t* old_nbr, const int3
                    int64_t n_old_nodes, const int64_t* add_indptr, const int32_t* add_nbr, const int32_t* add_eidx,
                    const double* add_ts, int64_t n_nodes, int64_t* new_indptr, int32_t* new_nbr, int32_t* new_eidx,
                    double* new_ts, void* stream);
+/* Retention (abi 6, additive): every entry with ts < cutoff leaves the adjacency - strict, compared in fp64 on the stored fp64
+ * timestamps.  Rows are time-sorted, so row v keeps the suffix [first_kept[v], indptr[v + 1]); n_nodes is unchanged, rows may
+ * become empty.  The result equals masking the flat arrays with ts >= cutoff and re-accumulating indptr, bit for bit.
+ *   pfo_csr_expire_plan : per-row lower bound -> first_kept i64[n_nodes], kept counts, exclusive scan -> new_indptr
+ *                         i64[n_nodes + 1] (new_indptr[n_nodes] = the surviving total, which the caller reads back to size the
+ *                         output).  Two launches; scratch holds pfo_csr_expire_scratch_bytes(n_nodes) bytes.  ts may be NULL
+ *                         when the adjacency has no entries.
+ *   pfo_csr_expire_copy : the surviving suffixes into new arrays of `total` entries (total = new_indptr[n_nodes]); one launch,
+ *                         one lane per surviving entry.  total == 0 queues nothing.
+ * PFO_ERR_INVALID - nothing is queued: n_nodes < 1, a cutoff that is NaN or infinite, a null pointer, a short scratch.
+ */
+int64_t pfo_csr_expire_scratch_bytes(int64_t n_nodes);
+int pfo_csr_expire_plan(const int64_t* indptr, const double* ts, int64_t n_nodes, double cutoff, int64_t* first_kept,
+                        int64_t* new_indptr, void* scratch, int64_t scratch_bytes, void* stream);
+int pfo_csr_expire_copy(const int64_t* old_indptr, const int32_t* old_nbr, const int32_t* old_eidx, const double* old_ts,
+                        int64_t n_nodes, const int64_t* first_kept, const int64_t* new_indptr, int64_t total, int32_t* new_nbr,
+                        int32_t* new_eidx, double* new_ts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Adam step over a flat parameter buffer (torch.optim.Adam defaults, main.py:123,389).
@@ -498,6 +515,28 @@ int pfo_tgn_observe(const pfo_tgn_config* cfg, const pfo_tgn_state* st, const in
  */
 int pfo_edge_rows_append(const float* raw, const float* mean, const float* stdv, int64_t m, int32_t Ef, float* table,
                          int64_t row0, int64_t cap, void* stream);
+/* Retention of the edge-feature table (abi 6, additive).  The table is shared between finders, so the decision is taken over
+ * all of them: row r >= 1 is RELEASED iff some expired adjacency entry (ts < cutoff) names r and no surviving one does; rows
+ * nobody names stay, row 0 always stays.  Surviving rows keep their order and are renumbered densely.
+ *   pfo_edge_rows_mark    : one call per finder over its adjacency as it was BEFORE the expiry (eidx i32[n], ts f64[n]):
+ *                           flags[eidx[i]] |= (ts[i] < cutoff ? 1 : 2).  flags i32[n_rows], zero before the first call; entries
+ *                           outside [0, n_rows) are ignored.
+ *   pfo_edge_rows_plan    : remap i32[n_rows] = the exclusive scan of the keep flags, -1 for released rows (remap[0] = 0);
+ *                           *n_keep (device) = the new row count.  Two launches; scratch: pfo_edge_rows_plan_scratch_bytes.
+ *   pfo_edge_rows_compact : kept rows move down to remap[r] inside the table's own storage THROUGH tmp f32[n_keep, Ef] (gather
+ *                           into tmp, stream-ordered copy back: no overlapping in-place copy); rows [n_keep, n_rows) are zeroed.
+ *                           n_keep == n_rows queues nothing.
+ *   pfo_eidx_remap        : eidx[i] = remap[eidx[i]] in place, for every finder that took part.
+ * PFO_ERR_INVALID - nothing is queued: bad sizes, a non-finite cutoff, a null pointer, a short scratch.
+ */
+int pfo_edge_rows_mark(const int32_t* eidx, const double* ts, int64_t n, double cutoff, int64_t n_rows, int32_t* flags,
+                       void* stream);
+int64_t pfo_edge_rows_plan_scratch_bytes(int64_t n_rows);
+int pfo_edge_rows_plan(const int32_t* flags, int64_t n_rows, int32_t* remap, int32_t* n_keep, void* scratch,
+                       int64_t scratch_bytes, void* stream);
+int pfo_edge_rows_compact(float* table, int64_t n_rows, int64_t n_keep, int32_t Ef, const int32_t* remap, float* tmp,
+                          void* stream);
+int pfo_eidx_remap(int32_t* eidx, int64_t n, const int32_t* remap, int64_t n_rows, void* stream);
 
 /* diagnostics for tests: copies of internals of the last forward (device pointers into the workspace) */
 typedef struct pfo_tgn_debug {

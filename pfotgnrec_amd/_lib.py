@@ -95,6 +95,9 @@ PROTOTYPES = {
     "pfo_csr_build_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "pfo_csr_build": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "pfo_csr_append": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_csr_expire_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "pfo_csr_expire_plan": (C.c_int, [_VP, _VP, C.c_int64, C.c_double, _VP, _VP, _VP, C.c_int64, _VP]),
+    "pfo_csr_expire_copy": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "pfo_adam_step_ranges": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int32), C.c_float, C.c_float, C.c_float, C.c_float, _VP]),
     "pfo_adam_step_ranges_dev": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
@@ -121,6 +124,11 @@ PROTOTYPES = {
     "pfo_tgn_observe": (C.c_int, [C.POINTER(TgnConfig), C.POINTER(TgnState), _VP, _VP, _VP, _VP, C.c_int64, C.c_int32, _VP,
                                   C.c_int64, _VP]),
     "pfo_edge_rows_append": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int64, _VP]),
+    "pfo_edge_rows_mark": (C.c_int, [_VP, _VP, C.c_int64, C.c_double, C.c_int64, _VP, _VP]),
+    "pfo_edge_rows_plan_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "pfo_edge_rows_plan": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
+    "pfo_edge_rows_compact": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP]),
+    "pfo_eidx_remap": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP]),
     "pfo_tgn_debug_views": (C.c_int, [C.POINTER(TgnConfig), _VP, C.POINTER(TgnDebug)]),
     "pfo_prof_enable": (C.c_int, [C.c_int32]),
     "pfo_marks_enable": (C.c_int, [C.c_int32]),

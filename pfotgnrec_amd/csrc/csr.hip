@@ -10,7 +10,11 @@
 //
 // pfo_csr_append merges a batch of new edges into an existing CSR with the same result as a rebuild over [old ; new]:
 // inside a row a new entry goes behind every old entry with ts <= its own (new edges are later in edge order).
+//
+// pfo_csr_expire_plan / pfo_csr_expire_copy drop every entry with ts < cutoff (the retention window): rows are time-sorted, so a
+// row keeps a suffix - a lower bound per row, an exclusive scan of the kept counts (scan64.hpp), one flat copy.
 #include "memory.hpp"
+#include "scan64.hpp"
 #include <algorithm>
 
 #define RS_TILE 1024        // entries per wavefront tile (16 steps of 64)
@@ -145,6 +149,37 @@ __global__ void csr_merge_kernel(const int64_t* __restrict__ optr, const int32_t
 
 int64_t tiles_of(int64_t n) { return pfo_ceil_div(n, RS_TILE); }
 
+// retention: first_kept[v] = the first position of row v with ts >= cutoff (fp64, strict <: a tie group at the cutoff stays
+// whole); the value scanned is the row's kept count
+struct ExpireCount {
+  const int64_t* indptr; const double* ts; double cutoff; int64_t* first_kept;
+  __device__ int64_t operator()(int64_t v) const {
+    int64_t lo = indptr[v], hi = indptr[v + 1];
+    const int64_t end = hi;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (ts[mid] < cutoff) lo = mid + 1; else hi = mid; }
+    first_kept[v] = lo;
+    return end - lo;
+  }
+};
+struct ExpireStore {
+  int64_t* new_indptr;
+  __device__ void operator()(int64_t i, int64_t x) const { new_indptr[i] = x; }
+};
+// one lane per SURVIVING entry (a row of any length costs what its entries cost: no wavefront is tied to a hub row): the row
+// of output position o is the last v with new_indptr[v] <= o - never an empty row, those share their successor's offset
+__global__ void csr_expire_copy_kernel(const int64_t* __restrict__ optr, const int32_t* __restrict__ onbr, const int32_t* __restrict__ oeid, const double* __restrict__ ots,
+                                       int64_t n_nodes, const int64_t* __restrict__ first_kept, const int64_t* __restrict__ nptr,
+                                       int64_t total, int32_t* __restrict__ nnbr, int32_t* __restrict__ neid, double* __restrict__ nts) {
+  for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
+    int64_t lo = 0, hi = n_nodes;                      // first v in [0, n_nodes] with nptr[v] > o; nptr[n_nodes] = total > o
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (nptr[mid] <= o) lo = mid + 1; else hi = mid; }
+    const int64_t v = lo - 1;
+    const int64_t p = first_kept[v] + (o - nptr[v]);
+    if (p >= optr[v + 1]) continue;                    // (a `total` that is not the plan's: read nothing outside the row)
+    nnbr[o] = onbr[p]; neid[o] = oeid[p]; nts[o] = ots[p];
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t pfo_csr_build_workspace_bytes(int64_t E, int64_t n_nodes) {
@@ -220,6 +255,41 @@ extern "C" int pfo_csr_append(const int64_t* old_indptr, const int32_t* old_nbr,
   PFO_KLAUNCH(csr_merge_kernel, dim3((unsigned)pfo_ceil_div(n_nodes + 1, 4)), dim3(256), 0, (hipStream_t)stream, old_indptr,
                      old_nbr, old_eidx, old_ts, add_indptr, add_nbr, add_eidx, add_ts, n_old_nodes, n_nodes, new_indptr, new_nbr,
                      new_eidx, new_ts);
+  PFO_LAUNCH_CHECK();
+  return PFO_OK;
+}
+
+extern "C" int64_t pfo_csr_expire_scratch_bytes(int64_t n_nodes) {
+  if (n_nodes <= 0) return -1;
+  return pfo_xs_tiles(n_nodes) * 8;
+}
+
+extern "C" int pfo_csr_expire_plan(const int64_t* indptr, const double* ts, int64_t n_nodes, double cutoff, int64_t* first_kept,
+                                   int64_t* new_indptr, void* scratch, int64_t scratch_bytes, void* stream) {
+  PFO_REQUIRE(n_nodes > 0 && n_nodes < ((int64_t)1 << 31), "bad node count");
+  PFO_REQUIRE(cutoff == cutoff && cutoff - cutoff == 0.0, "the cutoff must be finite");
+  PFO_REQUIRE(indptr && first_kept && new_indptr && scratch, "null pointer");      // (ts may be null: an adjacency without entries)
+  PFO_REQUIRE(scratch_bytes >= pfo_csr_expire_scratch_bytes(n_nodes), "short scratch");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nt = (unsigned)pfo_xs_tiles(n_nodes);
+  int64_t* tile_sum = reinterpret_cast<int64_t*>(scratch);
+  PFO_KLAUNCH(xs_tile_kernel<ExpireCount>, dim3(nt), dim3(XS_TILE), 0, s, (ExpireCount{indptr, ts, cutoff, first_kept}), n_nodes,
+              new_indptr, tile_sum);
+  PFO_KLAUNCH(xs_offset_kernel<ExpireStore>, dim3(nt), dim3(XS_TILE), 0, s, (ExpireStore{new_indptr}), n_nodes,
+              (const int64_t*)new_indptr, (const int64_t*)tile_sum);
+  PFO_LAUNCH_CHECK();
+  return PFO_OK;
+}
+
+extern "C" int pfo_csr_expire_copy(const int64_t* old_indptr, const int32_t* old_nbr, const int32_t* old_eidx, const double* old_ts, int64_t n_nodes,
+                                   const int64_t* first_kept, const int64_t* new_indptr, int64_t total, int32_t* new_nbr,
+                                   int32_t* new_eidx, double* new_ts, void* stream) {
+  PFO_REQUIRE(n_nodes > 0 && total >= 0, "bad sizes");
+  if (total == 0) return PFO_OK;
+  PFO_REQUIRE(old_indptr && old_nbr && old_eidx && old_ts && first_kept && new_indptr && new_nbr && new_eidx && new_ts, "null pointer");
+  const int blk = (int)std::min<int64_t>(8192, pfo_ceil_div(total, 256));
+  PFO_KLAUNCH(csr_expire_copy_kernel, dim3(blk), dim3(256), 0, (hipStream_t)stream, old_indptr, old_nbr, old_eidx, old_ts, n_nodes,
+              first_kept, new_indptr, total, new_nbr, new_eidx, new_ts);
   PFO_LAUNCH_CHECK();
   return PFO_OK;
 }

@@ -196,7 +196,7 @@ extern "C" int pfo_shader_clock(double* ghz_out, int32_t reset) {
   for (int i = 0; i < PFO_CLOCK_KERNELS; ++i) ghz_out[i] = ct[2 * i + 1] > 0 ? ct[2 * i] / (ct[2 * i + 1] * 10.0) : 0.0;   // cycles per ns
   return PFO_OK;
 }
-extern "C" int pfo_abi_version(void) { return 6; }   // 3: pfo_tgn_batch.dropout_keep, pfo_attn_dropout_mask, PFO_PROF_GRU_FUSED; 4: pfo_segment_sum, pfo_tgn_side_stream, defer_join / pcache fields; 5: PFO_PROF_KINDS 12 -> 16 (pfo_prof_collect arrays); 6: PFO_PROF_GEMM_TN_BX8 (17 kinds), pfo_shader_clock; still 6: pfo_tgn_observe, pfo_edge_rows_append (new symbols only are additive: no struct or array changed, the number stays)
+extern "C" int pfo_abi_version(void) { return 6; }   // 3: pfo_tgn_batch.dropout_keep, pfo_attn_dropout_mask, PFO_PROF_GRU_FUSED; 4: pfo_segment_sum, pfo_tgn_side_stream, defer_join / pcache fields; 5: PFO_PROF_KINDS 12 -> 16 (pfo_prof_collect arrays); 6: PFO_PROF_GEMM_TN_BX8 (17 kinds), pfo_shader_clock; still 6: pfo_tgn_observe, pfo_edge_rows_append, pfo_csr_expire_*, pfo_edge_rows_mark / _plan / _compact, pfo_eidx_remap (new symbols only are additive: no struct or array changed, the number stays)
 
 // ---------------------------------------------------------------------------------------------
 // roctx ranges (common.hpp)

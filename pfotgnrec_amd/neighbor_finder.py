@@ -222,6 +222,71 @@ class NeighborFinder:
         self._version += 1
         return self
 
+    def expire(self, cutoff, device=None, _row_flags=None):
+        """The retention window: removes every adjacency entry with ``ts < cutoff`` and returns how many went.  The comparison
+        is strict and runs in fp64 on the stored fp64 timestamps (it has nothing to do with the sampler's fp32 casts); rows
+        are time-sorted, so each row keeps a suffix.  ``n_nodes`` is unchanged, rows may become empty.  The result equals
+        boolean-masking the flat ``nbr / eidx / ts`` with ``ts >= cutoff`` and re-accumulating ``indptr``, bit for bit.
+
+        On the device: ``pfo_csr_expire_plan`` (per-row lower bound, kept counts, exclusive scan into the new ``indptr``) and
+        ``pfo_csr_expire_copy`` (the surviving suffixes).  The new total is read back to size the output - ONE
+        synchronisation: this is a maintenance call, not a step.  ``cutoff`` must be finite (``ValueError``, nothing is
+        written).  A cutoff below every timestamp is a no-op that does not bump ``_version``; otherwise the version is
+        bumped (consumers re-fetch the device arrays, a captured step goes stale), the host mirrors go stale and the tracked
+        extrema are unknown again until somebody asks."""
+        import torch
+        cutoff = float(cutoff)
+        if not np.isfinite(cutoff):
+            raise ValueError("the cutoff must be finite, got %r" % cutoff)
+        _lib.require_gpu(device)
+        if device is None:
+            device = next(iter(self._dev)) if self._dev else "cuda"
+        dev = torch.device(device)
+        o_ptr, o_nbr, o_eid, o_ts = self.device_arrays(dev)
+        n, old_total = self.n_nodes, int(o_nbr.shape[0])
+        if _row_flags is not None:             # (TGN.expire: which edge-table rows the expired / the surviving entries name)
+            _lib.call("pfo_edge_rows_mark", _lib.ptr(o_eid), _lib.ptr(o_ts), old_total, cutoff, int(_row_flags.shape[0]),
+                      _lib.ptr(_row_flags), _lib.stream_ptr())
+        if old_total == 0:
+            return 0
+        nbytes = _lib.byte_count("pfo_csr_expire_scratch_bytes", n)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        first = torch.empty(n, dtype=torch.int64, device=dev)
+        n_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        _lib.call("pfo_csr_expire_plan", _lib.ptr(o_ptr), _lib.ptr(o_ts), n, cutoff, _lib.ptr(first), _lib.ptr(n_ptr),
+                  _lib.ptr(scratch), nbytes, _lib.stream_ptr())
+        total = int(n_ptr[n].item())                                 # the one read-back
+        if total == old_total:
+            return 0
+        n_nbr = torch.empty(total, dtype=torch.int32, device=dev)
+        n_eid = torch.empty(total, dtype=torch.int32, device=dev)
+        n_ts = torch.empty(total, dtype=torch.float64, device=dev)
+        _lib.call("pfo_csr_expire_copy", _lib.ptr(o_ptr), _lib.ptr(o_nbr), _lib.ptr(o_eid), _lib.ptr(o_ts), n, _lib.ptr(first),
+                  _lib.ptr(n_ptr), total, _lib.ptr(n_nbr), _lib.ptr(n_eid), _lib.ptr(n_ts), _lib.stream_ptr())
+        self._dev = {_dev_key(dev): (n_ptr, n_nbr, n_eid, n_ts)}
+        self._host = None
+        self._max_nbr, self._max_eidx = None, None
+        self._version += 1
+        return old_total - total
+
+    def remap_edge_idxs(self, remap, device=None):
+        """``eidx[i] = remap[eidx[i]]`` in place on the device (``pfo_eidx_remap``), after the edge-feature table this finder
+        points into has been compacted (``TGN.expire``).  ``remap`` i32[old row count] on the device; no entry of this finder
+        may name a row that ``remap`` sends to -1.  Bumps ``_version``; host mirrors and other devices' copies go stale."""
+        import torch
+        _lib.require_gpu(device)
+        if device is None:
+            device = next(iter(self._dev)) if self._dev else remap.device
+        dev = torch.device(device)
+        arrays = self.device_arrays(dev)
+        _lib.call("pfo_eidx_remap", _lib.ptr(arrays[2]), int(arrays[2].shape[0]), _lib.ptr(remap), int(remap.shape[0]),
+                  _lib.stream_ptr())
+        self._dev = {_dev_key(dev): arrays}
+        self._host = None
+        self._max_eidx = None
+        self._version += 1
+        return self
+
     def next_stream_offset(self):
         self._calls += 1
         return self._calls << 20

@@ -1466,6 +1466,74 @@ class TGN(nn.Module):
         eidx = torch.arange(int(new_idxs[0]), int(new_idxs[0]) + N, dtype=torch.int32, device=self.device) if on_dev else new_idxs
         return self.observe(sources, destinations, edge_times, eidx, batch_size, append=True), new_idxs
 
+    # ------------------------------------------------------------------ serving: the retention window
+    def expire(self, cutoff, compact_edges=True, finders=None):
+        """"Keep the last N days": every adjacency entry with ``ts < cutoff`` (strict, fp64) leaves the neighbour finder
+        (``NeighborFinder.expire``) and, with ``compact_edges``, the rows of the edge-feature table that only expired entries
+        named are released.  Returns ``(n_entries_dropped, remap)``: the entries dropped over all finders taking part, and the
+        DEVICE tensor ``remap`` i32[old row count] - old edge index -> new one, ``remap[0] == 0``, -1 for a released row - or
+        ``None`` when ``compact_edges=False`` or no row was released (edge indices then mean what they meant).
+
+        The table is shared between finders (a train finder and a full finder over one table): ``finders`` names the OTHER
+        ``NeighborFinder``s over this model's table; the model's own finder always takes part.  All are expired with the same
+        cutoff and remapped with the same map.  A row ``r >= 1`` is released iff some expired entry of a finder taking part
+        names it and no surviving entry of any of them does; rows nobody names stay, row 0 always stays.  A finder over this
+        table that is NOT passed keeps its old edge indices and is wrong afterwards.  Surviving rows keep their order and are
+        renumbered densely; they move down inside the unchanged storage through a temporary (``pfo_edge_rows_compact``), the
+        rows behind the new live count are zero again, capacity never shrinks, and the next ``add_edge_features`` / ``ingest``
+        continues from the new row count.
+
+        Order: ``_quiesce()``, the finders, then the table.  Node memory, ``last_update``, the pending messages (they hold the
+        feature VALUES, not edge indices), parameters, gradients, optimizer state, the step counter and the random streams are
+        not touched.  Invalidated after a compaction: the padded device adjacency, the ``debug_*`` views of the last forward,
+        a batch prepared ahead of time and any ``GraphedTrainStep`` captured before (an expiry alone already stales the
+        latter through the finder's version).  Two read-backs (the surviving entry total per finder, the new row count): a
+        maintenance call, not a step.
+
+        Call it BETWEEN steps, like ``add_nodes``: a forward whose backward is still pending must have that backward run
+        first.  On a data-parallel group EVERY rank calls it with the same cutoff: state is replicated, there is no
+        collective.  ``cutoff`` must be finite (``ValueError`` before anything is written); without a device it raises like
+        every compute method."""
+        cutoff = float(cutoff)
+        if not np.isfinite(cutoff):
+            raise ValueError("the cutoff must be finite, got %r" % cutoff)
+        _lib.require_gpu(self.device)
+        taking_part = [self.neighbor_finder]
+        for nf in (finders or ()):
+            if not any(nf is f for f in taking_part):
+                taking_part.append(nf)
+        n_rows, Ef = int(self.edge_raw_features.shape[0]), self.n_edge_features
+        if compact_edges:
+            for nf in taking_part:
+                if nf.max_edge_idx() >= n_rows:
+                    raise ValueError("a neighbour finder references edge index %d but edge features have %d rows"
+                                     % (nf.max_edge_idx(), n_rows))
+        self._quiesce()
+        flags = torch.zeros(n_rows, dtype=torch.int32, device=self.device) if compact_edges else None
+        dropped = sum(nf.expire(cutoff, self.device, _row_flags=flags) for nf in taking_part)
+        if not compact_edges or dropped == 0:                        # (nothing expired: nothing can be released)
+            return dropped, None
+        nbytes = _lib.byte_count("pfo_edge_rows_plan_scratch_bytes", n_rows)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        remap = torch.empty(n_rows, dtype=torch.int32, device=self.device)
+        n_keep_dev = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.call("pfo_edge_rows_plan", flags.data_ptr(), n_rows, remap.data_ptr(), n_keep_dev.data_ptr(), scratch.data_ptr(),
+                  nbytes, _lib.stream_ptr())
+        n_keep = int(n_keep_dev.item())
+        if n_keep == n_rows:
+            return dropped, None
+        tmp = torch.empty((n_keep, Ef), dtype=torch.float32, device=self.device)
+        _lib.call("pfo_edge_rows_compact", self._edge_store.data_ptr(), n_rows, n_keep, Ef, remap.data_ptr(), tmp.data_ptr(),
+                  _lib.stream_ptr())
+        for nf in taking_part:
+            nf.remap_edge_idxs(remap, self.device)
+        self.edge_raw_features = self._edge_store[:n_keep]
+        self._cfg.n_edges_p1 = n_keep
+        self._adj_cache, self._keepalive = None, None
+        self._last_ws, self._last_call = None, None
+        self._tables_version += 1
+        return dropped, remap
+
     def _dev_keep(self, masks):
         """Injected dropout decisions for a parity test: ``{l: multipliers or booleans [n_l, H, K]}`` (level order, the layout
         of ``debug_dropout_masks`` and of the oracle's ``dropout_masks``) -> per layer, roots' level first, u8 [n_l, K] with bit
