@@ -63,6 +63,12 @@ int pfo_tnbr_sample(const int64_t* indptr, const int32_t* adj_nbr, const int32_t
  *   out i32[B,size] = item NODE ids (index + upper_u + 1), drawn without replacement from
  *   avail \ portfolio when that set has >= size members, otherwise with replacement (:99-111).
  *   RNG: Philox(seed, offset + interaction) - semantics-level parity only.
+ *   The draw itself (DESIGN "Random streams"; pinned bit for bit by tests/philox_ref.py): row b's list = the available items
+ *   in ascending index that are not among its first min(port_len, port_stride) portfolio entries (entries outside
+ *   [0, n_items) exclude nothing); slot k reads word k & 3 of the Philox4x32-10 block at counter (b + offset, k >> 2);
+ *   n_avail >= size: step k of a partial Fisher-Yates swaps entry k with entry k + ((word * (n_avail - k)) >> 32) and emits it;
+ *   0 < n_avail < size: list[(word * n_avail) >> 32]; n_avail == 0: the row is all ZEROS (node id 0, the padding node).
+ *   1 <= n_items <= 16384: the list lives in n_items * 4 bytes of dynamic LDS, 64 KiB at the maximum.
  */
 int pfo_neg_draw(const uint8_t* item_avail, int32_t n_items, const int32_t* port_idx, const int32_t* port_len,
                  int32_t port_stride, int64_t B, int32_t size, int32_t upper_u, uint64_t seed, uint64_t offset,

@@ -108,37 +108,52 @@ def packed_portfolios_of(portfolio_list, map_item_id):
                 or not _spot_check(a, idx[start:start + n], lens[start:start + n], map_item_id)):   # the dataset changed under the cache: repack
             _PORT_CACHE[:] = []
             return pack_portfolios(a, map_item_id)
-        _PORT_LAST[:] = [(idx, start, n)]
         return idx[start:start + n], lens[start:start + n]
     except Exception:
         return pack_portfolios(a, map_item_id)
 
 
-_PORT_LAST = []           # [(packed idx of the cached base, start, n)] of the last cache hit: how RandEdgeSampler finds the device copy
-_PORT_DEV = []            # [(packed idx object, device, idx on the device, lens on the device)] - at most one entry
+_PORT_DEV = []            # [(packed idx object, device, idx on the device, lens on the device, packed lens object)] - at most one entry
 _PORT_DEV_MAX_BYTES = 1 << 30
 _AVAIL_DEV = []           # [(availability array object, device, its device copy)] - at most one entry
+
+
+def _rows_of(rows, base):
+    """First row of ``rows`` inside ``base`` when ``rows`` is a run of whole rows of that array (a basic slice of it, same row
+    layout, inside its bounds), else None.  Taken from the slice's OWN data pointer: several slices of one packed base may be
+    held at once (a train and a validation sampler over one array, a prefetched batch), each names its own rows."""
+    if not (isinstance(rows, np.ndarray) and rows.base is base and base.flags.c_contiguous and rows.dtype == base.dtype
+            and rows.ndim == base.ndim and rows.shape[1:] == base.shape[1:] and rows.shape[0] > 0
+            and rows.strides == base.strides and base.strides[0] > 0):
+        return None
+    off = rows.__array_interface__["data"][0] - base.__array_interface__["data"][0]
+    start, rem = divmod(off, base.strides[0])
+    if rem != 0 or start < 0 or start + rows.shape[0] > base.shape[0]:
+        return None
+    return int(start)
 
 
 def _device_rows(idx_rows, lens_rows, device):
     """The packed rows of a batch on the device.  A batch that is a slice of the cached packed base (packed_portfolios_of) is a
     slice of ONE device copy of that base, uploaded when the base was packed (<= 1 GiB; a batch costs no host-to-device copy
     then: two pageable copies were ~50 us of a step whose device sits idle meanwhile, bench.py secondary.drop_in_surface);
-    anything else is uploaded as it is."""
+    anything else is uploaded as it is.  Which rows of the base a batch is comes from the batch's own arrays (_rows_of), never
+    from what was packed last."""
     import torch
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:          # ("cuda" and "cuda:0" are ONE cache entry)
         device = torch.device("cuda", torch.cuda.current_device())
-    last = _PORT_LAST[0] if _PORT_LAST else None
-    if last is not None and isinstance(idx_rows, np.ndarray) and idx_rows.base is last[0] and idx_rows.shape[0] == last[2]:
-        base, start, n = last
+    base = idx_rows.base if isinstance(idx_rows, np.ndarray) else None
+    if isinstance(base, np.ndarray) and base.ndim == 2:
         hit = _PORT_DEV and _PORT_DEV[0][0] is base and _PORT_DEV[0][1] == device
         if not hit and base.nbytes <= _PORT_DEV_MAX_BYTES and _PORT_CACHE and _PORT_CACHE[0][2] is base:
             lens_base = _PORT_CACHE[0][3]
-            _PORT_DEV[:] = [(base, device, torch.from_numpy(base).to(device), torch.from_numpy(lens_base).to(device))]
+            _PORT_DEV[:] = [(base, device, torch.from_numpy(base).to(device), torch.from_numpy(lens_base).to(device), lens_base)]
             hit = True
         if hit:
-            return _PORT_DEV[0][2][start:start + n], _PORT_DEV[0][3][start:start + n]
+            start, n = _rows_of(idx_rows, base), idx_rows.shape[0]
+            if start is not None and _rows_of(lens_rows, _PORT_DEV[0][4]) == start and lens_rows.shape[0] == n:
+                return _PORT_DEV[0][2][start:start + n], _PORT_DEV[0][3][start:start + n]
     return (torch.from_numpy(np.ascontiguousarray(idx_rows)).to(device), torch.from_numpy(np.ascontiguousarray(lens_rows)).to(device))
 
 
