@@ -544,6 +544,37 @@ int pfo_edge_rows_compact(float* table, int64_t n_rows, int64_t n_keep, int32_t 
                           void* stream);
 int pfo_eidx_remap(int32_t* eidx, int64_t n, const int32_t* remap, int64_t n_rows, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Holdings ledger (abi 6, additive): per node row the portfolio its newest interaction record carried.  hold_idx i32[n_nodes, W]
+ * STOCK indices padded with -1 (the packed form of port_idx everywhere else; the item node of stock s is s + upper_u + 1),
+ * hold_len i32[n_nodes] valid leading entries, hold_time f64[n_nodes] the record's time.  All pointers are device pointers.
+ *
+ * pfo_holdings_store: for e = 0..N-1 in input order, u = src[e]: skipped unless 1 <= u < n_nodes; L = clamp(port_len[e], 0,
+ *   min(W, port_stride)); hold_idx[u, :L] = port_idx[e, :L] (row stride port_stride, entries verbatim), hold_idx[u, L:] = -1,
+ *   hold_len[u] = L, hold_time[u] = ts[e].  Per user the LAST event of the call wins, on every run and for every launch
+ *   geometry: a cleared stamp table, atomicMax(stamp[u], e + 1), and the event that finds its own stamp copies the row with one
+ *   lane per element - three stream-ordered nodes (memset, two kernels), no workgroup waits for another.  Rows of nodes the
+ *   call does not name keep every bit.  scratch: pfo_holdings_store_scratch_bytes(n_nodes, N) bytes (-1 for bad sizes), its
+ *   content on entry is irrelevant.  port_idx may be NULL when port_stride == 0.
+ * pfo_holdings_gather: for q < U, u = users[q], ok = 0 <= u < n_nodes: port_idx_out[q, :] = ok ? hold_idx[u, :] : -1,
+ *   port_len_out[q] = ok ? hold_len[u] : 0, and - unless excl_pos_out is NULL - excl_pos_out[q, j] = the position in items
+ *   i32[I] (distinct node ids) of node hold_idx[u, j] + upper_u + 1 if ok, j < hold_len[u] and that node is a candidate, else
+ *   -1 (the stock index is range-checked before the addition).  pos_scratch i32[n_nodes] needs no initialisation and may be
+ *   kept between queries: pos_scratch[items[i]] = i is scattered, and an entry p is trusted only if 0 <= p < I and
+ *   items[p] names the node - another list's positions are never seen.  Two launches (one when excl_pos_out is NULL: items
+ *   and pos_scratch are then not read and may be NULL).  Outputs: i32[U, W], i32[U], i32[U, W].
+ * PFO_ERR_INVALID - checked before anything is read, nothing is written: W outside [1, 256], N outside [0, 2^31), I outside
+ * [1, PFO_RECOMMEND_MAX_ITEMS], n_nodes < 1 (or >= 2^31), port_stride < 0, U < 0; then a null pointer, a short scratch.
+ * N == 0 / U == 0 queue nothing and return PFO_OK.
+ */
+int64_t pfo_holdings_store_scratch_bytes(int64_t n_nodes, int64_t N);
+int pfo_holdings_store(const int32_t* src, const int32_t* port_idx, const int32_t* port_len, int32_t port_stride, const double* ts,
+                       int64_t N, int32_t* hold_idx, int32_t* hold_len, double* hold_time, int64_t n_nodes, int32_t W, void* scratch,
+                       int64_t scratch_bytes, void* stream);
+int pfo_holdings_gather(const int32_t* users, int64_t U, const int32_t* hold_idx, const int32_t* hold_len, int64_t n_nodes, int32_t W,
+                        const int32_t* items, int32_t I, int32_t upper_u, int32_t* pos_scratch, int32_t* port_idx_out,
+                        int32_t* port_len_out, int32_t* excl_pos_out, void* stream);
+
 /* diagnostics for tests: copies of internals of the last forward (device pointers into the workspace) */
 typedef struct pfo_tgn_debug {
   const int32_t* n_touched;  /* [1] */

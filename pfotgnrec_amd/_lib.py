@@ -129,7 +129,12 @@ PROTOTYPES = {
     "pfo_edge_rows_plan": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
     "pfo_edge_rows_compact": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP]),
     "pfo_eidx_remap": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP]),
-    "pfo_tgn_debug_views": (C.c_int, [C.POINTER(TgnConfig), _VP, C.POINTER(TgnDebug)]),
+    "pfo_holdings_store_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "pfo_holdings_store": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int64,
+                                     _VP]),
+    "pfo_holdings_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP,
+                                      _VP]),
+    "pfo_tgn_debug_views": (C.c_int,[C.POINTER(TgnConfig), _VP, C.POINTER(TgnDebug)]),
     "pfo_prof_enable": (C.c_int, [C.c_int32]),
     "pfo_marks_enable": (C.c_int, [C.c_int32]),
     "pfo_mark": (C.c_int, [C.c_char_p, _VP]),

@@ -402,3 +402,68 @@ def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_
               _lib.ptr(score), _lib.ptr(y), _lib.ptr(fused), _lib.stream_ptr())
     out = (top_pos, top_score, top_fused, n_valid)
     return out + (score, y, fused) if want_all else out
+
+
+def holdings_store(src, port_idx, port_len, ts, hold_idx, hold_len, hold_time, scratch=None):
+    """Writes the ledger rows of the events' users in place (``pfo_holdings_store``): for every event in input order, users
+    outside [1, n_nodes) skipped, ``hold_idx[u] = port_idx[e, :L]`` padded with -1, ``hold_len[u] = L`` =
+    clamp(port_len[e], 0, min(W, Wp)), ``hold_time[u] = ts[e]``; per user the last event wins.
+
+    src i32[N], port_idx i32[N, Wp], port_len i32[N], ts f64[N]; hold_idx i32[n_nodes, W], hold_len i32[n_nodes], hold_time
+    f64[n_nodes] contiguous; scratch: a uint8 / int32 tensor of ``pfo_holdings_store_scratch_bytes`` bytes or None (allocated)."""
+    if (hold_idx.dim() != 2 or hold_idx.dtype != torch.int32 or hold_len.dtype != torch.int32 or hold_time.dtype != torch.float64
+            or tuple(hold_len.shape) != (hold_idx.shape[0],) or tuple(hold_time.shape) != (hold_idx.shape[0],)):
+        raise ValueError("the ledger must be (i32 [n_nodes, W], i32 [n_nodes], f64 [n_nodes])")
+    if not (hold_idx.is_contiguous() and hold_len.is_contiguous() and hold_time.is_contiguous()):
+        raise ValueError("the ledger tables must be contiguous")
+    n_nodes, W = (int(v) for v in hold_idx.shape)
+    N = int(src.shape[0]) if src.dim() == 1 else -1
+    if (src.dtype != torch.int32 or N < 0 or port_idx.dim() != 2 or port_idx.dtype != torch.int32 or port_idx.shape[0] != N
+            or port_len.dtype != torch.int32 or tuple(port_len.shape) != (N,) or ts.dtype != torch.float64 or tuple(ts.shape) != (N,)):
+        raise ValueError("events must be src i32[N], port_idx i32[N, Wp], port_len i32[N], ts f64[N]")
+    dev = hold_idx.device
+    _lib.require_gpu(dev)
+    for t in (src, port_idx, port_len, ts, hold_len, hold_time, scratch):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    need = _lib.byte_count("pfo_holdings_store_scratch_bytes", n_nodes, N)
+    if scratch is None or scratch.numel() * scratch.element_size() < need or not scratch.is_contiguous():
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    Wp = int(port_idx.shape[1])
+    _lib.call("pfo_holdings_store", _lib.ptr(src.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None),
+              _lib.ptr(port_len.contiguous()), Wp, _lib.ptr(ts.contiguous()), N, hold_idx.data_ptr(), hold_len.data_ptr(),
+              hold_time.data_ptr(), n_nodes, W, scratch.data_ptr(), scratch.numel() * scratch.element_size(), _lib.stream_ptr())
+
+
+def holdings_gather(users, hold_idx, hold_len, upper_u, items=None, pos_scratch=None):
+    """The ledger rows of ``users`` i32[U] (``pfo_holdings_gather``): (port_idx i32[U, W], port_len i32[U], excl_pos) - users
+    outside [0, n_nodes) give (-1.., 0).  With ``items`` i32[I] (distinct candidate node ids) excl_pos i32[U, W] holds, per
+    valid entry, the position in ``items`` of node ``stock + upper_u + 1`` or -1; without, None.  ``pos_scratch``: i32[>= n_nodes]
+    kept between queries (any content), None: allocated."""
+    if hold_idx.dim() != 2 or hold_idx.dtype != torch.int32 or hold_len.dtype != torch.int32 or tuple(hold_len.shape) != (hold_idx.shape[0],):
+        raise ValueError("the ledger must be (i32 [n_nodes, W], i32 [n_nodes])")
+    if not (hold_idx.is_contiguous() and hold_len.is_contiguous()):
+        raise ValueError("the ledger tables must be contiguous")
+    if users.dim() != 1 or users.dtype != torch.int32:
+        raise ValueError("users must be int32 [U]")
+    n_nodes, W = (int(v) for v in hold_idx.shape)
+    U, I = int(users.shape[0]), 1
+    dev = hold_idx.device
+    if items is not None:
+        if items.dim() != 1 or items.dtype != torch.int32:
+            raise ValueError("items must be int32 [I]")
+        I = int(items.shape[0])
+        if pos_scratch is None or pos_scratch.dtype != torch.int32 or pos_scratch.numel() < n_nodes or not pos_scratch.is_contiguous():
+            pos_scratch = torch.empty(n_nodes, dtype=torch.int32, device=dev)
+    _lib.require_gpu(dev)
+    for t in (users, hold_len, items, pos_scratch if items is not None else None):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    port_idx = torch.empty((U, W), dtype=torch.int32, device=dev)
+    port_len = torch.empty(U, dtype=torch.int32, device=dev)
+    excl_pos = torch.empty((U, W), dtype=torch.int32, device=dev) if items is not None else None
+    _lib.call("pfo_holdings_gather", _lib.ptr(users.contiguous()), U, hold_idx.data_ptr(), hold_len.data_ptr(), n_nodes, W,
+              _lib.ptr(items.contiguous() if items is not None else None), I, int(upper_u),
+              _lib.ptr(pos_scratch if items is not None else None), port_idx.data_ptr(), port_len.data_ptr(), _lib.ptr(excl_pos),
+              _lib.stream_ptr())
+    return port_idx, port_len, excl_pos

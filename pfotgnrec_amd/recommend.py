@@ -9,10 +9,15 @@ import torch
 
 from . import _lib
 
-Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv",
-                               defaults=(None,))
+Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held",
+                               defaults=(None, None))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
+HELD = "held"     # ``exclude`` / ``portfolios``: take the rows of the model's holdings ledger (port_idx is None in the MVQuery then)
+
+
+def _is_held(a):
+    return isinstance(a, str) and a == HELD
 
 
 def _host(a):
@@ -34,8 +39,10 @@ def _is_int_array(t):
     return (t.dtype.kind in "iu") if isinstance(t, np.ndarray) else not (t.dtype.is_floating_point or t.dtype == torch.bool)
 
 
-def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts):
+def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
     """The mean-variance keywords of ``TGN.recommend`` checked on the host (ValueError) -> ``MVQuery``, or None without any."""
+    if _is_held(portfolios) and holdings is None:
+        raise ValueError('portfolios="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
     if mv is None:
         if portfolios is not None or day_idx is not None:
             raise ValueError("portfolios / day_idx need mv (an MVSampler): without it the portfolio can only be excluded")
@@ -44,7 +51,9 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts):
         if not hasattr(mv, name):
             raise ValueError("mv must carry returns, upper_u, gamma, lambda_mv and day_of (an MVSampler); %s is missing" % name)
     if portfolios is None:
-        raise ValueError("mv needs portfolios: packed (port_idx [U,W], port_len [U]) or one list of stock indices per user")
+        raise ValueError("mv needs portfolios: packed (port_idx [U,W], port_len [U]), one list of stock indices per user, or \"held\"")
+    if _is_held(portfolios) and int(mv.upper_u) != holdings.upper_u:
+        raise ValueError("mv.upper_u is %d, the holdings ledger's %d: they number the stocks differently" % (int(mv.upper_u), holdings.upper_u))
     if len(mv.returns.shape) != 3:
         raise ValueError("mv.returns must be [n_days, n_stocks, n_ret]")
     if I > _lib.RECOMMEND_MV_MAX_ITEMS:
@@ -52,7 +61,9 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts):
     n_days = int(mv.returns.shape[0])
     packed = (isinstance(portfolios, (tuple, list)) and len(portfolios) == 2
               and isinstance(portfolios[0], (torch.Tensor, np.ndarray)) and portfolios[0].ndim == 2)
-    if packed:
+    if _is_held(portfolios):
+        port_idx = port_len = None
+    elif packed:
         port_idx, port_len = portfolios
         if not isinstance(port_len, (torch.Tensor, np.ndarray)):
             port_len = np.asarray(port_len)
@@ -100,7 +111,7 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts):
 
 
 def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
-             day_idx=None):
+             day_idx=None, holdings=None):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
     try:
@@ -133,7 +144,10 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
             raise ValueError("item_ok must hold one flag per candidate (%d), got shape %s" % (I, tuple(ok_any.shape)))
         ok_h = _host(item_ok)
     ex_ids = ex_len = None
-    if exclude is not None:
+    if _is_held(exclude):
+        if holdings is None:
+            raise ValueError('exclude="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
+    elif exclude is not None:
         packed = (isinstance(exclude, (tuple, list)) and len(exclude) == 2
                   and isinstance(exclude[0], (torch.Tensor, np.ndarray)) and exclude[0].ndim == 2)
         if packed:
@@ -163,8 +177,10 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
                 ex_len[i] = len(r)
     if n_neighbors is None:
         n_neighbors = 20 if default_neighbors is None else default_neighbors
-    mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts)
-    return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq)
+    mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings)
+    held = (_is_held(exclude), mvq is not None and mvq.port_idx is None)
+    return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
+                 held if any(held) else None)
 
 
 def assemble(tgn, q, return_embeddings=False):
@@ -208,7 +224,14 @@ def assemble(tgn, q, return_embeddings=False):
             if return_embeddings:
                 out += (user_emb, item_emb, torch.empty(0, dtype=torch.int32, device=dev))
             return out
-        excl_pos = excl_len = None
+        excl_pos = excl_len = held_ports = None
+        if q.held is not None:
+            # one gather for whichever of the two asks: the ledger rows of the users, and their stocks as candidate positions
+            h_idx, h_len, h_pos = tgn.holdings.gather(users_d, items_d if q.held[0] else None)
+            if q.held[0]:
+                excl_pos, excl_len = h_pos, h_len
+            if q.held[1]:
+                held_ports = (h_idx, h_len)
         if q.ex_ids is not None and q.ex_ids.shape[1] > 0:
             # node id -> position in ``items`` through a table over the node ids (-1: not a candidate)
             pos_of = torch.full((tgn.n_nodes,), -1, dtype=torch.int32, device=dev)
@@ -222,7 +245,8 @@ def assemble(tgn, q, return_embeddings=False):
         if q.item_ok is not None:
             ok_d = (to_dev(q.item_ok if q.ok_h is None else q.ok_h, torch.int64) != 0).to(torch.uint8)
         if q.mv is not None:
-            return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings)
+            return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
+                                held_ports)
         if user_block is not None and n_t > 1:
             # users of one block side by side: the kernel serves a tile of 16 users in one pass per distinct block
             order = torch.argsort(user_block, stable=True)
@@ -241,9 +265,10 @@ def assemble(tgn, q, return_embeddings=False):
         return out
 
 
-def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings):
+def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
+                 held_ports=None):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
-    portfolio rows following the users through the block sort."""
+    portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held")."""
     from .functional import recommend_mv_topk
     dev, k, U, mv = tgn.device, q.k, q.U, q.mv.src
     returns = mv.returns
@@ -252,8 +277,11 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
     returns = returns.to(device=dev, dtype=torch.float64)
     cand_stock = (items_d - (int(mv.upper_u) + 1)).contiguous()
     day = to_dev(q.mv.day_idx, torch.int32)
-    port_idx = to_dev(q.mv.port_idx, torch.int32) if q.mv.port_idx.shape[1] > 0 else None
-    port_len = to_dev(q.mv.port_len, torch.int32) if port_idx is not None else None
+    if held_ports is not None:
+        port_idx, port_len = held_ports
+    else:
+        port_idx = to_dev(q.mv.port_idx, torch.int32) if q.mv.port_idx.shape[1] > 0 else None
+        port_len = to_dev(q.mv.port_len, torch.int32) if port_idx is not None else None
     args = (float(mv.gamma), float(mv.lambda_mv))
     if user_block is not None and n_t > 1:
         order = torch.argsort(user_block, stable=True)

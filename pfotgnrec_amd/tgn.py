@@ -226,6 +226,7 @@ class TGN(nn.Module):
         # capacity storage of the two feature tables (``reserve``): the attributes are its leading rows
         self._node_store, self._edge_store = self.node_raw_features, self.edge_raw_features
         self._tables_version = 0          # bumped whenever a table grows or moves (a captured step goes stale)
+        self.holdings = None              # the holdings ledger (``track_holdings``): serving state the step never reads
         self._set_stats(ef_mean, ef_std)
         self.n_nodes, self.n_node_features = self.node_raw_features.shape
         self.n_edge_features = self.edge_raw_features.shape[1]
@@ -398,6 +399,8 @@ class TGN(nn.Module):
         self.node_raw_features = self._node_store[:self.node_raw_features.shape[0]]
         self.edge_raw_features = self._edge_store[:self.edge_raw_features.shape[0]]
         self._edge_stats_dev = fn(self._edge_stats_dev).contiguous()
+        if self.holdings is not None:
+            self.holdings.move(self._flat.device)
         self._tables_version += 1
         if self.use_memory:
             mem = self.memory
@@ -1172,11 +1175,15 @@ class TGN(nn.Module):
         ``item - upper_u - 1``; at most 2048 candidates.  Returns (item_ids, scores, n_valid, fused f64[U,k]) - fused
         descending, -inf in empty slots - then the embeddings as above.
 
+        ``exclude="held"`` / ``portfolios="held"`` (either alone, or both): the rows of the holdings ledger
+        (``track_holdings``) in place of the argument - one ``pfo_holdings_gather`` over the users already on the device, no
+        lists packed or uploaded per query; ``portfolios="held"`` still needs ``mv``, whose ``upper_u`` must be the ledger's.
+
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` are not (it would cost a
         read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
         query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
-                           portfolios, day_idx)
+                           portfolios, day_idx, self.holdings)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
@@ -1320,6 +1327,8 @@ class TGN(nn.Module):
             self._node_store, self.node_raw_features = store, store[:live]
             if self.use_memory:
                 self.memory.resize(live, int(n_nodes))
+            if self.holdings is not None:
+                self.holdings.resize(live, int(n_nodes))
             self._tables_version += 1
         return self
 
@@ -1396,6 +1405,8 @@ class TGN(nn.Module):
         self._cfg.n_nodes = first + n
         if self.use_memory:
             self.memory.resize(first + n)                         # (bumps memory._state_version)
+        if self.holdings is not None:
+            self.holdings.resize(first + n)                       # (rows behind the live ones hold the initial values already)
         # outstanding calls hand their - now undersized - workspaces back to the list they took them from, not to the new one
         self._ws_pool = []
         self._adj_cache, self._keepalive = None, None             # (the indptr padding depends on n_nodes)
@@ -1405,7 +1416,7 @@ class TGN(nn.Module):
             self._pcache, self._pcache_key = None, None           # (parameter-only buffers: today its size ignores the node count)
         return first
 
-    def ingest(self, sources, destinations, edge_times, edge_features, batch_size=None, node_features=None):
+    def ingest(self, sources, destinations, edge_times, edge_features, batch_size=None, node_features=None, portfolios=None):
         """The serving tick: takes in interactions the model has NEVER seen - their feature rows are not in the edge-feature
         table, their nodes may not exist yet - so that the next ``recommend`` accounts for them.  A thin chain of
         ``add_nodes`` (when the input names new nodes), ``add_edge_features`` and ``observe(..., append=True)``: the state
@@ -1420,9 +1431,16 @@ class TGN(nn.Module):
         order, zeros otherwise.  Host inputs are validated BEFORE anything is written (``ValueError``: lengths, feature width,
         non-finite features, decreasing ``edge_times``, node ids < 1, ids that skip ahead, ``batch_size`` < 1): a rejected call
         leaves the model bit for bit as it was.  Device tensors (i32 / i32 / f64 and f32[N, Ef]) are checked for shape and
-        dtype only and must name existing nodes (``add_nodes`` first)."""
+        dtype only and must name existing nodes (``add_nodes`` first).
+
+        ``portfolios``: what each record says its user holds at that moment, in a form ``update_holdings`` takes (host forms
+        with host inputs, the device pair with device inputs); needs a ledger (``track_holdings``).  Its checks join the ones
+        above - a rejected call leaves the ledger too - and the ledger is written ONCE per call behind ``add_nodes`` (last
+        record per user over the whole input: batch boundaries do not matter to it).  None: the ledger is not touched."""
         on_dev = torch.is_tensor(sources)
         N = int(sources.shape[0]) if on_dev else len(sources)
+        if portfolios is not None and self.holdings is None:
+            raise ValueError("portfolios need a holdings ledger: call track_holdings(width, upper_u) first")
         if any(len(a) != N for a in (destinations, edge_times, edge_features)):
             raise ValueError("sources, destinations, edge_times and edge_features must have the same length")
         if batch_size is not None and int(batch_size) < 1:
@@ -1457,14 +1475,76 @@ class TGN(nn.Module):
                                  % (self.n_nodes, fresh[:8].tolist()))
             if node_features is not None and tuple(np.shape(node_features)) != (n_new, self.n_node_features):
                 raise ValueError("node_features must have shape [%d, %d]: one row per new node" % (n_new, self.n_node_features))
+        held = None
+        if portfolios is not None:                # (the new nodes are rows of the ledger by the time it is written)
+            from . import holdings as H
+            held = H.validate(self.holdings.width, self.n_nodes + n_new, sources, portfolios, edge_times)
         if N == 0:
             return 0, np.zeros(0, np.int64)
         _lib.require_gpu(self.device)             # (nothing below has a host path: refuse before the first table grows)
         if n_new:
             self.add_nodes(n_new, node_features)
+        if held is not None:
+            self._write_holdings(held)
         new_idxs = self.add_edge_features(edge_features)
         eidx = torch.arange(int(new_idxs[0]), int(new_idxs[0]) + N, dtype=torch.int32, device=self.device) if on_dev else new_idxs
         return self.observe(sources, destinations, edge_times, eidx, batch_size, append=True), new_idxs
+
+    # ------------------------------------------------------------------ serving: the holdings ledger
+    def track_holdings(self, width, upper_u):
+        """Creates the holdings ledger (``self.holdings``, None before): per node row the portfolio its user's newest
+        interaction record carried - ``idx`` i32[n_nodes, width] STOCK indices padded with -1 (the packed form of
+        ``pack_portfolios``; the item node of stock ``s`` is ``s + upper_u + 1``), ``len`` i32[n_nodes], ``time`` f64[n_nodes]
+        (-1 / 0 / -inf until written) - in capacity storage that follows ``node_capacity`` (``reserve`` / ``add_nodes`` keep
+        live rows bit for bit) and the model's device.  ``update_holdings`` and ``ingest(portfolios=)`` write it,
+        ``recommend(exclude="held", portfolios="held")`` and ``holdings.rows(users)`` read it; the training step, ``observe``
+        and ``expire`` do not touch it, and it is not part of ``state_dict()``: persist ``holdings.idx / len / time`` and load
+        them with ``update_holdings``.  Once: a second call with other arguments raises ``ValueError``.  Returns the ledger."""
+        from . import holdings as H
+        try:
+            width, upper_u = int(width), int(upper_u)
+        except (TypeError, ValueError):
+            raise ValueError("width and upper_u must be integers") from None
+        if not 1 <= width <= H.MAX_WIDTH:
+            raise ValueError("width must lie in [1, %d] (got %d)" % (H.MAX_WIDTH, width))
+        if not 0 <= upper_u < 2 ** 31 - 1:
+            raise ValueError("upper_u must be a non-negative int32 (got %d)" % upper_u)
+        if self.holdings is not None:
+            if (self.holdings.width, self.holdings.upper_u) != (width, upper_u):
+                raise ValueError("the model already tracks holdings with width %d, upper_u %d"
+                                 % (self.holdings.width, self.holdings.upper_u))
+            return self.holdings
+        self.holdings = H.Holdings(self.n_nodes, self.node_capacity, width, upper_u, self.device)
+        return self.holdings
+
+    def update_holdings(self, sources, portfolios, edge_times):
+        """The one writer of the ledger: for every event in input order, ``holdings[sources[e]] = (portfolios[e], edge_times[e])``
+        - per user the LAST event of the call wins, an empty portfolio overwrites, entries are stored verbatim, nothing is
+        compared with the stored time (chronological input is the caller's contract, as for ``observe``); node 0 is skipped.
+        One native call (``pfo_holdings_store``: a memset and two launches).  Seeds a served model from the training log and
+        loads a saved ledger (``sources = arange(n_nodes)``, ``portfolios = (idx, len)``, ``edge_times = time``).
+
+        ``portfolios``: a packed pair (idx [N, Wp], len [N]) as numpy, one list of integer stock indices per event, or the pair
+        as i32 device tensors next to i32 / f64 device ``sources`` / ``edge_times``.  Host inputs are validated before anything
+        is written (``ValueError``: lengths, integer dtypes, values beyond int32, len outside [0, Wp], a row longer than the
+        ledger's width, node ids outside [0, n_nodes)) and staged in one copy; device inputs are checked for shape and dtype
+        only - the kernel skips ids outside [1, n_nodes) and clamps lengths to the row.  Returns the number of events."""
+        if self.holdings is None:
+            raise ValueError("no holdings ledger: call track_holdings(width, upper_u) first")
+        from . import holdings as H
+        w = H.validate(self.holdings.width, self.n_nodes, sources, portfolios, edge_times)
+        if w.N:
+            _lib.require_gpu(self.device)
+            self._write_holdings(w)
+        return w.N
+
+    def _write_holdings(self, w):
+        with torch.no_grad():
+            if w.on_dev:
+                src, idx, length, ts = w.src, w.idx, w.len, w.ts
+            else:
+                ts, src, idx, length = self._batch_to_dev([(w.ts, np.float64), (w.src, np.int32), (w.idx, np.int32), (w.len, np.int32)])
+            self.holdings.store(src, idx, length, ts)
 
     # ------------------------------------------------------------------ serving: the retention window
     def expire(self, cutoff, compact_edges=True, finders=None):
