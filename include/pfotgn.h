@@ -281,6 +281,35 @@ int pfo_recommend_mv_topk(const float* user_emb, const float* item_emb, const in
                           double* y_out, double* fused_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Basket top-k (abi 6, additive): the list of pfo_recommend_mv_topk taken one pick at a time, each pick joining the holdings
+ * before the next is ranked, in one launch.  The arguments are pfo_recommend_mv_topk's without the three diagnostic arrays and
+ * mean what they mean there: scores, admissible set A(u), portfolio P (list order, out-of-range entries left out, duplicates
+ * kept), y_mv arithmetic, average-tie ranks, blend and canonical order are that function's.
+ *   For round r = 0 .. k-1 of user u:
+ *     1. P_r = P followed by cand_stock[pick_0 .. pick_{r-1}] in pick order.  y_r[c] = y_mv of candidate c against P_r - fp64,
+ *        no contraction, the covariances summed in that order - for every c of A(u) that has not been picked.  A candidate
+ *        whose y_r is NaN sits out round r only.
+ *     2. invest_rank / tgn_rank: the average-tie ranks of y_r and of the fp32 score over the candidates taking part in round r;
+ *        fused_r = lambda_mv * invest_rank + (1 - lambda_mv) * tgn_rank.
+ *     3. pick_r = the first of the canonical order: fused_r descending, the LARGER position first among equal values.
+ *     4. top_pos[u,r] = pick_r, top_score[u,r] = its score (a zero as +0), top_fused[u,r] = fused_r[pick_r] - the value of
+ *        round r, so top_fused need not descend along a row.
+ *     5. Nobody takes part: the list ends; n_valid[u] (optional) = number of picks, the other slots hold -1 / -inf / -inf.
+ *   Only the picked POSITION leaves the pool: another candidate on the same stock stays (and now carries the covariance with
+ *   itself).  The picked stock joins P_r even if it is held already.  A user whose day_idx is outside [0, n_days) gets an
+ *   empty list.
+ *   Hence: k = 1 is pfo_recommend_mv_topk(k = 1) bit for bit; lambda_mv = 0 gives pfo_recommend_mv_topk's positions for any k;
+ *   any k equals k calls of pfo_recommend_mv_topk(k = 1) with each pick appended to the portfolio row and the exclusion row.
+ *   Bounds as for pfo_recommend_mv_topk.  Work per user: 2 k I^2 comparisons, (|P| + k - 1) I n_ret multiply-adds.
+ */
+int pfo_recommend_basket_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                              int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                              const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                              int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                              const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                              int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Time-sorted adjacency built on the device: replaces get_neighbor_finder / NeighborFinder.__init__ (utils/utils.py:117-148).
  * Every edge e contributes (dst, eidx, ts) to row src[e] and (src, eidx, ts) to row dst[e]; rows are sorted by timestamp,
  * ties in edge order (Python's stable sorted(key=ts), utils.py:139).  A stable LSD radix sort of the 2E entries; the eight

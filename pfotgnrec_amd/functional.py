@@ -306,21 +306,11 @@ def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_l
     return top_pos, top_score, n_valid
 
 
-def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
-                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False):
-    """``recommend_topk`` with the mean-variance rank fusion of main.py:243-289 over every user's whole candidate list, in one
-    launch (``pfo_recommend_mv_topk``).
-
-    The arguments of ``recommend_topk`` mean what they mean there and the score is that kernel's to the bit.  cand_stock
-    i32[I]: row of candidate i in ``returns`` f64[n_days,n_stocks,n_ret] (``MVSampler.returns``); day_idx i32[U]; port_idx
-    i32[U,W], port_len i32[U] (None: whole rows): the stock rows user u holds, entries outside [0,n_stocks) ignored,
-    duplicates counted.  Over the admissible candidates of a user (the rules of ``recommend_topk``, minus cand_stock outside the
-    table, minus a NaN y; none for a day outside the table): fused = lambda_mv * rank(y_mv) + (1 - lambda_mv) * rank(score), both
-    average-tie ranks (``scipy.stats.rankdata``).
-
-    Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]): fused descending, the larger position
-    first among equal values (SURVEY App. A-9); empty slots -1 / -inf / -inf.  ``want_all`` adds (score f32[U,I], y f64[U,I],
-    fused f64[U,I]), NaN in the last two where a candidate is not admissible."""
+def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
+                         user_block, excl_pos, excl_len, item_ok, n_blocks):
+    """The argument checks, output rows and launch that ``recommend_mv_topk`` and ``recommend_basket_topk`` share: ``symbol``
+    takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays (``diagnostics``: allocate them or pass NULL)
+    or without them (None)."""
     import operator
     for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
         if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
@@ -390,18 +380,52 @@ def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_
     top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
     top_fused = torch.empty((U, k), dtype=torch.float64, device=dev)
     n_valid = torch.empty(U, dtype=torch.int32, device=dev)
-    score = torch.empty((U, I), dtype=torch.float32, device=dev) if want_all else None
-    y = torch.empty((U, I), dtype=torch.float64, device=dev) if want_all else None
-    fused = torch.empty((U, I), dtype=torch.float64, device=dev) if want_all else None
-    _lib.call("pfo_recommend_mv_topk", user_emb.data_ptr(), item_emb.data_ptr(),
+    out = (top_pos, top_score, top_fused, n_valid)
+    extra = ()
+    if diagnostics is not None:
+        extra = tuple(torch.empty((U, I), dtype=dt, device=dev) if diagnostics else None
+                      for dt in (torch.float32, torch.float64, torch.float64))
+    _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(),
               _lib.ptr(user_block.contiguous() if user_block is not None else None), U, I, n_t, D,
               _lib.ptr(excl_pos.contiguous() if W else None), _lib.ptr(excl_len.contiguous() if W else None), W, _lib.ptr(item_ok),
               _lib.ptr(cand_stock.contiguous()), returns.data_ptr(), n_days, n_stocks, n_ret, _lib.ptr(day_idx.contiguous()),
               _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None), Wp,
-              float(gamma), float(lambda_mv), k, top_pos.data_ptr(), top_score.data_ptr(), top_fused.data_ptr(), n_valid.data_ptr(),
-              _lib.ptr(score), _lib.ptr(y), _lib.ptr(fused), _lib.stream_ptr())
-    out = (top_pos, top_score, top_fused, n_valid)
-    return out + (score, y, fused) if want_all else out
+              float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), _lib.stream_ptr())
+    return out + extra if diagnostics else out
+
+
+def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
+                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False):
+    """``recommend_topk`` with the mean-variance rank fusion of main.py:243-289 over every user's whole candidate list, in one
+    launch (``pfo_recommend_mv_topk``).
+
+    The arguments of ``recommend_topk`` mean what they mean there and the score is that kernel's to the bit.  cand_stock
+    i32[I]: row of candidate i in ``returns`` f64[n_days,n_stocks,n_ret] (``MVSampler.returns``); day_idx i32[U]; port_idx
+    i32[U,W], port_len i32[U] (None: whole rows): the stock rows user u holds, entries outside [0,n_stocks) ignored,
+    duplicates counted.  Over the admissible candidates of a user (the rules of ``recommend_topk``, minus cand_stock outside the
+    table, minus a NaN y; none for a day outside the table): fused = lambda_mv * rank(y_mv) + (1 - lambda_mv) * rank(score), both
+    average-tie ranks (``scipy.stats.rankdata``).
+
+    Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]): fused descending, the larger position
+    first among equal values (SURVEY App. A-9); empty slots -1 / -inf / -inf.  ``want_all`` adds (score f32[U,I], y f64[U,I],
+    fused f64[U,I]), NaN in the last two where a candidate is not admissible."""
+    return _recommend_mv_launch("pfo_recommend_mv_topk", bool(want_all), user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
+                                port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks)
+
+
+def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
+                          excl_pos=None, excl_len=None, item_ok=None, n_blocks=None):
+    """``recommend_mv_topk`` taken one pick at a time, in one launch (``pfo_recommend_basket_topk``): pick r is the first of the
+    canonical order of round r, in which the stocks of picks 0 .. r-1 count as held behind ``port_idx[u]`` (in pick order) and
+    their positions have left the pool; only the position leaves - another candidate on the same stock stays.  Arguments and
+    their checks are ``recommend_mv_topk``'s.
+
+    Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]): ``top_fused[u, r]`` is the pick's fused
+    value OF ROUND r (a row need not descend); the list ends when no candidate is left, empty slots -1 / -inf / -inf.  k = 1 is
+    ``recommend_mv_topk`` bit for bit; any k equals k calls of it with k = 1, each pick appended to the user's portfolio row and
+    exclusion row."""
+    return _recommend_mv_launch("pfo_recommend_basket_topk", None, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
+                                port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks)
 
 
 def holdings_store(src, port_idx, port_len, ts, hold_idx, hold_len, hold_time, scratch=None):

@@ -1,6 +1,7 @@
 """Read-only top-k recommendation behind ``TGN.recommend``: ``validate`` checks the arguments on the host alone (no device is
 asked for), ``assemble`` embeds users and candidates on the device and lets ``pfo_recommend_topk`` score and select - or, with
-a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` score, rank twice, blend and select."""
+a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` score, rank twice, blend and select; with ``basket`` on top
+of that, ``pfo_recommend_basket_topk`` re-rank after every pick."""
 import collections
 import operator
 
@@ -9,8 +10,8 @@ import torch
 
 from . import _lib
 
-Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held",
-                               defaults=(None, None))
+Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held basket",
+                               defaults=(None, None, False))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
 HELD = "held"     # ``exclude`` / ``portfolios``: take the rows of the model's holdings ledger (port_idx is None in the MVQuery then)
@@ -111,7 +112,7 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
 
 
 def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
-             day_idx=None, holdings=None):
+             day_idx=None, holdings=None, basket=False):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
     try:
@@ -120,6 +121,10 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
         raise ValueError("k must be an integer") from None
     if not 1 <= k <= 64:
         raise ValueError("k must be in [1, 64] (got %d)" % k)
+    if not isinstance(basket, (bool, np.bool_)):
+        raise ValueError("basket must be True or False")
+    if basket and mv is None:
+        raise ValueError("basket=True needs mv (an MVSampler): a pick changes the order only through the mean-variance rank")
     users_h = _int_vector(users, "users", n_nodes)
     U = int(users.shape[0]) if users_h is None else int(users_h.shape[0])
     items_h = _int_vector(items.detach().cpu().numpy() if isinstance(items, torch.Tensor) else items, "items", n_nodes)
@@ -180,7 +185,7 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
     mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings)
     held = (_is_held(exclude), mvq is not None and mvq.port_idx is None)
     return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
-                 held if any(held) else None)
+                 held if any(held) else None, bool(basket))
 
 
 def assemble(tgn, q, return_embeddings=False):
@@ -268,8 +273,10 @@ def assemble(tgn, q, return_embeddings=False):
 def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
                  held_ports=None):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
-    portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held")."""
-    from .functional import recommend_mv_topk
+    portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held").
+    ``q.basket``: ``recommend_basket_topk`` in its place."""
+    from .functional import recommend_basket_topk, recommend_mv_topk
+    topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
     dev, k, U, mv = tgn.device, q.k, q.U, q.mv.src
     returns = mv.returns
     if not isinstance(returns, torch.Tensor):
@@ -286,12 +293,12 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
     if user_block is not None and n_t > 1:
         order = torch.argsort(user_block, stable=True)
         sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
-        res = recommend_mv_topk(sel(user_emb), item_emb, k, cand_stock, returns, sel(day), sel(port_idx), sel(port_len), *args,
-                                sel(user_block), sel(excl_pos), sel(excl_len), ok_d, n_blocks=n_t)
+        res = topk(sel(user_emb), item_emb, k, cand_stock, returns, sel(day), sel(port_idx), sel(port_len), *args,
+                   sel(user_block), sel(excl_pos), sel(excl_len), ok_d, n_blocks=n_t)
         res = tuple(torch.empty_like(t).index_copy_(0, order, t) for t in res)
     else:
-        res = recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day, port_idx, port_len, *args,
-                                user_block if n_t > 1 else None, excl_pos, excl_len, ok_d, n_blocks=n_t)
+        res = topk(user_emb, item_emb, k, cand_stock, returns, day, port_idx, port_len, *args,
+                   user_block if n_t > 1 else None, excl_pos, excl_len, ok_d, n_blocks=n_t)
     top_pos, top_score, top_fused, n_valid = res
     item_ids = torch.where(top_pos >= 0, items_d[top_pos.clamp(min=0).long()], torch.full_like(top_pos, -1))
     out = (item_ids, top_score, n_valid, top_fused)

@@ -1149,7 +1149,7 @@ class TGN(nn.Module):
         return emb
 
     def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
-                  mv=None, portfolios=None, day_idx=None):
+                  mv=None, portfolios=None, day_idx=None, basket=False):
         """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
         written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
         is left as found), no gradient is recorded and dropout is off.
@@ -1175,6 +1175,11 @@ class TGN(nn.Module):
         ``item - upper_u - 1``; at most 2048 candidates.  Returns (item_ids, scores, n_valid, fused f64[U,k]) - fused
         descending, -inf in empty slots - then the embeddings as above.
 
+        ``basket=True`` (needs ``mv``): the list is taken one pick at a time - pick r is ranked with the stocks of picks
+        0 .. r-1 counted as held behind the user's portfolio, so two near-identical stocks no longer both make the list; one
+        launch of ``pfo_recommend_basket_topk`` in place of ``pfo_recommend_mv_topk``, equal to k calls with ``k=1`` and each
+        pick appended to ``portfolios`` and ``exclude``.  The same return tuple; ``fused[u, r]`` is the pick's value in round r.
+
         ``exclude="held"`` / ``portfolios="held"`` (either alone, or both): the rows of the holdings ledger
         (``track_holdings``) in place of the argument - one ``pfo_holdings_gather`` over the users already on the device, no
         lists packed or uploaded per query; ``portfolios="held"`` still needs ``mv``, whose ``upper_u`` must be the ledger's.
@@ -1183,7 +1188,7 @@ class TGN(nn.Module):
         read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
         query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
-                           portfolios, day_idx, self.holdings)
+                           portfolios, day_idx, self.holdings, basket)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
