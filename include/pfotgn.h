@@ -622,6 +622,68 @@ typedef struct pfo_tgn_debug {
 } pfo_tgn_debug;
 int pfo_tgn_debug_views(const pfo_tgn_config* cfg, void* workspace, pfo_tgn_debug* out);
 
+/* debug / test probes of the internal contraction interface (csrc/gemm.hpp).  Every struct mirrors the internal one field
+ * for field and every call forwards to the internal launcher unchanged; the comments of gemm.hpp are the contract.  Not part
+ * of the drop-in surface: the package's own Python never calls them, the kernel tests do. */
+typedef struct pfo_gemm_desc {     /* PfoGemm */
+  const float* A[2]; int64_t lda[2]; const int32_t* a_idx[2];
+  const float* B[2]; int64_t ldb[2]; const int32_t* b_idx;
+  int32_t K[2];
+  float* C; int64_t ldc;
+  const float* bias;
+  const float* row_scale; int64_t rs_ld;
+  const uint8_t* row_zero;
+  const float* relu_src; int64_t relu_ld;
+  const float* add_src; int64_t add_ld; const int32_t* add_idx;
+  int32_t M, N;
+  const int32_t* m_dev;
+  int32_t relu, accumulate, a_kmajor, b_kmajor;
+  int32_t batch;
+  int64_t a_bs[2], b_bs[2], c_bs, bias_bs, rs_bs;
+  float* slabs; int64_t slab_floats;
+  const void* b_img; const void* b_img2;
+  int32_t bx_force;
+} pfo_gemm_desc;
+typedef struct pfo_tn_desc {       /* PfoTnProblem */
+  const float* A; int64_t lda;
+  const float* B; int64_t ldb; const int32_t* b_idx;
+  int32_t M, N;
+  float* C; int64_t ldc; int32_t c_accumulate;
+  float* bias_out; int32_t bias_accumulate;
+} pfo_tn_desc;
+typedef struct pfo_bimg_desc {     /* PfoBimg */
+  const float* src; int64_t ld; int32_t N, K, trans; void* dst;
+  int32_t row0, rows_total, last;
+  int32_t gate, gate_D;
+} pfo_bimg_desc;
+typedef struct pfo_gru_desc {      /* PfoGruFused */
+  const float* msg_rows; int32_t K_msg;
+  const float* h_rows;
+  const void* img_ih; const void* img_hh;
+  const float* b_ih; const float* b_hh;
+  const uint8_t* hm; const int32_t* touched; const float* node_feat;
+  float* upd_mem; float* h0_tab; float* gates;
+  int32_t D, cap_rows; const int32_t* n_rows;
+  int32_t gather;
+} pfo_gru_desc;
+typedef struct pfo_rank1_desc {    /* PfoRank1 */
+  const float* u; int64_t ldu; const float* v; int64_t ldv; int32_t M, N; float* out; int64_t ldo;
+  int32_t reps; int64_t u_rs, v_rs;
+} pfo_rank1_desc;
+typedef struct pfo_sum_slabs_desc { /* PfoSumSlabs */
+  float* dst; const float* src; int64_t stride, count; int32_t n_slabs, accumulate;
+} pfo_sum_slabs_desc;
+int pfo_debug_gemm(const pfo_gemm_desc* g, void* stream);
+int pfo_debug_gemm_multi(const pfo_gemm_desc* list, int32_t n, void* stream);
+int pfo_debug_gemm_tn_group(const pfo_tn_desc* probs, int32_t n, int32_t K, const int32_t* k_dev, float* slabs, int64_t slab_floats,
+                            void* stream);
+int64_t pfo_debug_bimg_bytes(int32_t N, int32_t K);
+int64_t pfo_debug_gru_img_bytes(int32_t D, int32_t K);
+int pfo_debug_bimg(const pfo_bimg_desc* list, int32_t n, void* stream);
+int pfo_debug_gru_fused(const pfo_gru_desc* f, void* stream);
+int pfo_debug_rank1_multi(const pfo_rank1_desc* list, int32_t n, void* stream);
+int pfo_debug_sum_slabs(const pfo_sum_slabs_desc* list, int32_t n, void* stream);
+
 /* Parameter cache (pfo_tgn_state.pcache): its size, and the call that (re)builds it from state->params on the library's
  * side stream, forked from `stream` and NOT joined back - the next pfo_tgn_forward with pcache_valid = 1 queues its own
  * side-stream work behind it, so the caller's stream never waits for the build itself.  Meant to be called right behind the

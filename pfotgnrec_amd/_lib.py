@@ -52,6 +52,46 @@ class TgnDebug(C.Structure):
                                    "gru_dgi", "gru_msg_rows")] + [("Cp", C.c_int32)]
 
 
+# debug / test probes of the internal contraction interface (csrc/gemm.hpp through csrc/probe.hip); the package never calls them
+_FP = C.c_void_p
+
+
+class GemmDesc(C.Structure):
+    _fields_ = [("A", _FP * 2), ("lda", C.c_int64 * 2), ("a_idx", _FP * 2), ("B", _FP * 2), ("ldb", C.c_int64 * 2), ("b_idx", _FP),
+                ("K", C.c_int32 * 2), ("C", _FP), ("ldc", C.c_int64), ("bias", _FP), ("row_scale", _FP), ("rs_ld", C.c_int64),
+                ("row_zero", _FP), ("relu_src", _FP), ("relu_ld", C.c_int64), ("add_src", _FP), ("add_ld", C.c_int64),
+                ("add_idx", _FP), ("M", C.c_int32), ("N", C.c_int32), ("m_dev", _FP), ("relu", C.c_int32),
+                ("accumulate", C.c_int32), ("a_kmajor", C.c_int32), ("b_kmajor", C.c_int32), ("batch", C.c_int32),
+                ("a_bs", C.c_int64 * 2), ("b_bs", C.c_int64 * 2), ("c_bs", C.c_int64), ("bias_bs", C.c_int64), ("rs_bs", C.c_int64),
+                ("slabs", _FP), ("slab_floats", C.c_int64), ("b_img", _FP), ("b_img2", _FP), ("bx_force", C.c_int32)]
+
+
+class TnDesc(C.Structure):
+    _fields_ = [("A", _FP), ("lda", C.c_int64), ("B", _FP), ("ldb", C.c_int64), ("b_idx", _FP), ("M", C.c_int32), ("N", C.c_int32),
+                ("C", _FP), ("ldc", C.c_int64), ("c_accumulate", C.c_int32), ("bias_out", _FP), ("bias_accumulate", C.c_int32)]
+
+
+class BimgDesc(C.Structure):
+    _fields_ = [("src", _FP), ("ld", C.c_int64), ("N", C.c_int32), ("K", C.c_int32), ("trans", C.c_int32), ("dst", _FP),
+                ("row0", C.c_int32), ("rows_total", C.c_int32), ("last", C.c_int32), ("gate", C.c_int32), ("gate_D", C.c_int32)]
+
+
+class GruDesc(C.Structure):
+    _fields_ = [("msg_rows", _FP), ("K_msg", C.c_int32), ("h_rows", _FP), ("img_ih", _FP), ("img_hh", _FP), ("b_ih", _FP),
+                ("b_hh", _FP), ("hm", _FP), ("touched", _FP), ("node_feat", _FP), ("upd_mem", _FP), ("h0_tab", _FP), ("gates", _FP),
+                ("D", C.c_int32), ("cap_rows", C.c_int32), ("n_rows", _FP), ("gather", C.c_int32)]
+
+
+class Rank1Desc(C.Structure):
+    _fields_ = [("u", _FP), ("ldu", C.c_int64), ("v", _FP), ("ldv", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("out", _FP),
+                ("ldo", C.c_int64), ("reps", C.c_int32), ("u_rs", C.c_int64), ("v_rs", C.c_int64)]
+
+
+class SumSlabsDesc(C.Structure):
+    _fields_ = [("dst", _FP), ("src", _FP), ("stride", C.c_int64), ("count", C.c_int64), ("n_slabs", C.c_int32),
+                ("accumulate", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol of include/pfotgn.h
 PROTOTYPES = {
     "pfo_abi_version": (C.c_int, []),
@@ -138,6 +178,15 @@ PROTOTYPES = {
     "pfo_holdings_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP,
                                       _VP]),
     "pfo_tgn_debug_views": (C.c_int,[C.POINTER(TgnConfig), _VP, C.POINTER(TgnDebug)]),
+    "pfo_debug_gemm": (C.c_int, [C.POINTER(GemmDesc), _VP]),
+    "pfo_debug_gemm_multi": (C.c_int, [C.POINTER(GemmDesc), C.c_int32, _VP]),
+    "pfo_debug_gemm_tn_group": (C.c_int, [C.POINTER(TnDesc), C.c_int32, C.c_int32, _VP, _VP, C.c_int64, _VP]),
+    "pfo_debug_bimg_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "pfo_debug_gru_img_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
+    "pfo_debug_bimg": (C.c_int, [C.POINTER(BimgDesc), C.c_int32, _VP]),
+    "pfo_debug_gru_fused": (C.c_int, [C.POINTER(GruDesc), _VP]),
+    "pfo_debug_rank1_multi": (C.c_int, [C.POINTER(Rank1Desc), C.c_int32, _VP]),
+    "pfo_debug_sum_slabs": (C.c_int, [C.POINTER(SumSlabsDesc), C.c_int32, _VP]),
     "pfo_prof_enable": (C.c_int, [C.c_int32]),
     "pfo_marks_enable": (C.c_int, [C.c_int32]),
     "pfo_mark": (C.c_int, [C.c_char_p, _VP]),

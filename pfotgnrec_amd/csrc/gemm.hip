@@ -2313,6 +2313,14 @@ int pfo_gemm_launch(const PfoGemm& g, hipStream_t stream) {
   GemmDev d;
   to_dev(g, d);
   const bool vec = a_vec && b_vec;
+  // the launch takes an image kernel (below) exactly when this holds; what those kernels, or the fp32 one, would not read
+  // is refused, not dropped
+  const bool img_launch = !g.a_kmajor && g.b_img && (g.K[1] == 0 || g.b_img2) && a_vec && g.batch == 1;
+  // b_idx gathers the k rows of a k-major B in the fp32 kernel; a weight image is built from the ungathered operand
+  PFO_REQUIRE(!g.b_idx || (g.b_kmajor && !img_launch), "b_idx needs a k-major B and a launch that takes no weight image");
+  PFO_REQUIRE(!g.a_kmajor || (!g.a_idx[0] && !g.a_idx[1]), "a_idx needs a row-major A");
+  // the row-gathered addend exists in the epilogue of the image kernels only
+  PFO_REQUIRE(!g.add_src || img_launch, "add_src needs a weight-image launch (row-major 16-byte aligned A, b_img, batch 1)");
   const double flops = 2.0 * g.M * g.N * ((double)g.K[0] + g.K[1]) * g.batch;
   int kind = g.m_dev ? PFO_PROF_GEMM_DEVM : (g.a_kmajor ? PFO_PROF_GEMM_TN : (g.b_kmajor ? PFO_PROF_GEMM_NN : PFO_PROF_GEMM_NT));
   pfo_prof_begin(stream);
@@ -2350,8 +2358,7 @@ int pfo_gemm_launch(const PfoGemm& g, hipStream_t stream) {
     const dim3 grid((unsigned)pfo_ceil_div(g.M, rows), tn, g.batch);
     // the split contraction on the caller's pre-split image of B (pfo_bimg_launch): 32-row workgroups for launches of fewer
     // than BX_MIN_TILES 128-row tiles, the 128-row kernels above (bx_force: tests pick one)
-    const bool a_rowvec = a_vec && g.batch == 1;
-    const bool img_ok = g.b_img && (g.K[1] == 0 || g.b_img2) && a_rowvec;
+    const bool img_ok = img_launch;
     if (img_ok && (g.bx_force == 2 || (!g.bx_force && big_tiles < BX_MIN_TILES))) {
       d.b_img = g.b_img; d.b_img_rows = (int)pfo_align_up(g.N, BN); d.b_img2 = g.b_img2;
       kind = PFO_PROF_GEMM_BX_SKINNY;
@@ -2416,7 +2423,8 @@ int pfo_gemm_multi_launch(const PfoGemm* list, int n, hipStream_t stream) {
     for (int i = 0; i < cnt; ++i) {
       const PfoGemm& s = list[base + i];
       PFO_REQUIRE(s.M > 0 && s.N > 0 && s.K[0] > 0 && s.A[0] && s.B[0] && s.C, "bad problem");
-      PFO_REQUIRE(!s.m_dev && !s.slabs, "multi launch takes plain problems only");
+      PFO_REQUIRE(!s.m_dev && !s.slabs && !s.add_src, "multi launch takes plain problems only");
+      PFO_REQUIRE((!s.b_idx || s.b_kmajor) && (!s.a_kmajor || (!s.a_idx[0] && !s.a_idx[1])), "a gather the problem's layout does not read");
       to_dev(s, g.p[i]);
       g.layout[i] = (s.a_kmajor ? 2 : 0) + (s.b_kmajor ? 1 : 0);
       g.tm[i] = (int)pfo_ceil_div(s.M, 32);

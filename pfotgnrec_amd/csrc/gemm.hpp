@@ -3,7 +3,7 @@
 #include "common.hpp"
 
 // C[M,N] = epilogue( sum over up to two K-concatenated sources  A_s[M,K_s] * op(B_s) )
-//   A_s row-major [M,K_s] (a_kmajor=0, optional row gather a_idx) or [K_s,M] (a_kmajor=1)
+//   A_s row-major [M,K_s] (a_kmajor=0, optional row gather a_idx) or [K_s,M] (a_kmajor=1; a_idx is refused)
 //   B_s [N,K_s] (b_kmajor=0, nn.Linear layout) or [K_s,N] (b_kmajor=1, optional k-row gather b_idx)
 // epilogue order: (+= C)  ->  + bias[n]*row_scale[m]  ->  + add_src[add_idx[m]][n]  ->  row_zero  ->  relu  ->  * (relu_src>0)
 struct PfoGemm {
@@ -12,7 +12,7 @@ struct PfoGemm {
   const int32_t* a_idx[2] = {nullptr, nullptr};
   const float* B[2] = {nullptr, nullptr};
   int64_t ldb[2] = {0, 0};
-  const int32_t* b_idx = nullptr;   // k-major B only: gathers the k rows of source 0
+  const int32_t* b_idx = nullptr;   // k-major B only: gathers the k rows of source 0 (refused with a row-major B or in an image launch)
   int K[2] = {0, 0};
   float* C = nullptr;
   int64_t ldc = 0;
@@ -20,7 +20,8 @@ struct PfoGemm {
   const float* row_scale = nullptr; int64_t rs_ld = 1;
   const uint8_t* row_zero = nullptr;
   const float* relu_src = nullptr; int64_t relu_ld = 0;
-  // row-gathered addend (bf16x3 image kernels only): C[m][n] += add_src[add_idx ? add_idx[m] : m][n]
+  // row-gathered addend (bf16x3 image kernels only; a launch that would take another kernel is refused):
+  // C[m][n] += add_src[add_idx ? add_idx[m] : m][n]
   const float* add_src = nullptr; int64_t add_ld = 0; const int32_t* add_idx = nullptr;
   int M = 0, N = 0;
   const int32_t* m_dev = nullptr;   // device-side row count (rows M for row-major A, extent K for k-major A)

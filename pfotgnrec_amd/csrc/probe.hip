@@ -1,0 +1,102 @@
+// Debug / test probes of the internal contraction interface (gemm.hpp): the flat C structs of include/pfotgn.h copied field
+// for field into the internal ones and handed to the internal launchers unchanged.  No logic of their own beyond null and
+// count checks - what a probe computes is what tgn.hip gets from the same launcher.
+#include "gemm.hpp"
+
+static void to_gemm(const pfo_gemm_desc& s, PfoGemm& g) {
+  for (int i = 0; i < 2; ++i) {
+    g.A[i] = s.A[i]; g.lda[i] = s.lda[i]; g.a_idx[i] = s.a_idx[i];
+    g.B[i] = s.B[i]; g.ldb[i] = s.ldb[i]; g.K[i] = s.K[i];
+    g.a_bs[i] = s.a_bs[i]; g.b_bs[i] = s.b_bs[i];
+  }
+  g.b_idx = s.b_idx;
+  g.C = s.C; g.ldc = s.ldc;
+  g.bias = s.bias; g.row_scale = s.row_scale; g.rs_ld = s.rs_ld; g.row_zero = s.row_zero;
+  g.relu_src = s.relu_src; g.relu_ld = s.relu_ld;
+  g.add_src = s.add_src; g.add_ld = s.add_ld; g.add_idx = s.add_idx;
+  g.M = s.M; g.N = s.N; g.m_dev = s.m_dev;
+  g.relu = s.relu; g.accumulate = s.accumulate; g.a_kmajor = s.a_kmajor; g.b_kmajor = s.b_kmajor;
+  g.batch = s.batch; g.c_bs = s.c_bs; g.bias_bs = s.bias_bs; g.rs_bs = s.rs_bs;
+  g.slabs = s.slabs; g.slab_floats = s.slab_floats;
+  g.b_img = s.b_img; g.b_img2 = s.b_img2; g.bx_force = s.bx_force;
+}
+
+extern "C" int pfo_debug_gemm(const pfo_gemm_desc* g, void* stream) {
+  PFO_REQUIRE(g, "null descriptor");
+  PfoGemm q;
+  to_gemm(*g, q);
+  return pfo_gemm_launch(q, (hipStream_t)stream);
+}
+
+#define PROBE_MULTI_MAX 32
+extern "C" int pfo_debug_gemm_multi(const pfo_gemm_desc* list, int32_t n, void* stream) {
+  PFO_REQUIRE(list && n >= 1 && n <= PROBE_MULTI_MAX, "bad problem list");
+  PfoGemm q[PROBE_MULTI_MAX];
+  for (int i = 0; i < n; ++i) to_gemm(list[i], q[i]);
+  return pfo_gemm_multi_launch(q, n, (hipStream_t)stream);
+}
+
+#define PROBE_TN_MAX 16
+extern "C" int pfo_debug_gemm_tn_group(const pfo_tn_desc* probs, int32_t n, int32_t K, const int32_t* k_dev, float* slabs,
+                                       int64_t slab_floats, void* stream) {
+  PFO_REQUIRE(probs && n >= 1 && n <= PROBE_TN_MAX, "bad problem list");
+  PfoTnProblem q[PROBE_TN_MAX];
+  for (int i = 0; i < n; ++i) {
+    const pfo_tn_desc& s = probs[i];
+    q[i].A = s.A; q[i].lda = s.lda; q[i].B = s.B; q[i].ldb = s.ldb; q[i].b_idx = s.b_idx; q[i].M = s.M; q[i].N = s.N;
+    q[i].C = s.C; q[i].ldc = s.ldc; q[i].c_accumulate = s.c_accumulate;
+    q[i].bias_out = s.bias_out; q[i].bias_accumulate = s.bias_accumulate;
+  }
+  return pfo_gemm_tn_group_launch(q, n, K, k_dev, slabs, slab_floats, (hipStream_t)stream);
+}
+
+extern "C" int64_t pfo_debug_bimg_bytes(int32_t N, int32_t K) {
+  if (N <= 0 || K <= 0) { pfo_set_error("%s: bad sizes", __func__); return -1; }
+  return pfo_bimg_bytes(N, K);
+}
+extern "C" int64_t pfo_debug_gru_img_bytes(int32_t D, int32_t K) {
+  if (D <= 0 || K <= 0) { pfo_set_error("%s: bad sizes", __func__); return -1; }
+  return pfo_gru_img_bytes(D, K);
+}
+
+extern "C" int pfo_debug_bimg(const pfo_bimg_desc* list, int32_t n, void* stream) {
+  PFO_REQUIRE(list && n >= 1 && n <= PFO_BIMG_MAX, "bad image list");
+  PfoBimg q[PFO_BIMG_MAX];
+  for (int i = 0; i < n; ++i) {
+    const pfo_bimg_desc& s = list[i];
+    q[i].src = s.src; q[i].ld = s.ld; q[i].N = s.N; q[i].K = s.K; q[i].trans = s.trans; q[i].dst = s.dst;
+    q[i].row0 = s.row0; q[i].rows_total = s.rows_total; q[i].last = s.last; q[i].gate = s.gate; q[i].gate_D = s.gate_D;
+  }
+  return pfo_bimg_launch(q, n, (hipStream_t)stream);
+}
+
+extern "C" int pfo_debug_gru_fused(const pfo_gru_desc* f, void* stream) {
+  PFO_REQUIRE(f, "null descriptor");
+  PfoGruFused q;
+  q.msg_rows = f->msg_rows; q.K_msg = f->K_msg; q.h_rows = f->h_rows; q.img_ih = f->img_ih; q.img_hh = f->img_hh;
+  q.b_ih = f->b_ih; q.b_hh = f->b_hh; q.hm = f->hm; q.touched = f->touched; q.node_feat = f->node_feat;
+  q.upd_mem = f->upd_mem; q.h0_tab = f->h0_tab; q.gates = f->gates; q.D = f->D; q.cap_rows = f->cap_rows; q.n_rows = f->n_rows;
+  q.gather = f->gather;
+  return pfo_gru_fused_launch(q, (hipStream_t)stream);
+}
+
+extern "C" int pfo_debug_rank1_multi(const pfo_rank1_desc* list, int32_t n, void* stream) {
+  PFO_REQUIRE(list && n >= 1 && n <= PFO_RANK1_MAX, "bad rank-1 list");
+  PfoRank1 q[PFO_RANK1_MAX];
+  for (int i = 0; i < n; ++i) {
+    const pfo_rank1_desc& s = list[i];
+    q[i].u = s.u; q[i].ldu = s.ldu; q[i].v = s.v; q[i].ldv = s.ldv; q[i].M = s.M; q[i].N = s.N; q[i].out = s.out; q[i].ldo = s.ldo;
+    q[i].reps = s.reps; q[i].u_rs = s.u_rs; q[i].v_rs = s.v_rs;
+  }
+  return pfo_rank1_multi_launch(q, n, (hipStream_t)stream);
+}
+
+extern "C" int pfo_debug_sum_slabs(const pfo_sum_slabs_desc* list, int32_t n, void* stream) {
+  PFO_REQUIRE(list && n >= 1 && n <= PFO_SUM_SLABS_MAX, "bad slab list");
+  PfoSumSlabs q[PFO_SUM_SLABS_MAX];
+  for (int i = 0; i < n; ++i) {
+    q[i].dst = list[i].dst; q[i].src = list[i].src; q[i].stride = list[i].stride; q[i].count = list[i].count;
+    q[i].n_slabs = list[i].n_slabs; q[i].accumulate = list[i].accumulate;
+  }
+  return pfo_sum_slabs_launch(q, n, (hipStream_t)stream);
+}

@@ -16,6 +16,7 @@ from pfotgnrec_amd.synthetic import SyntheticConfig, make_graph, CONFIGS
 from oracle.neighbor_finder import OracleNeighborFinder, build_adjacency
 from oracle import mv_select as omv
 from oracle import tgn_oracle as T
+from gemm_ref import tn_scale_floor as _tn_scale_floor, wide
 
 DEV = "cuda:0"
 
@@ -295,8 +296,8 @@ def test_gemm_bf16x3_split_contraction_matches_float64(M, N, K):
     """fp32 contraction on the bf16 matrix cores (3-way operand split, 6 piece products): fp32-level accuracy.
     Operands with a wide dynamic range (exponents differ along k) so that dropped low pieces would show."""
     rs = np.random.RandomState(M + N + K)
-    A = (rs.randn(M, K) * np.exp(2 * rs.randn(M, K))).astype(np.float32)
-    W = (rs.randn(N, K) * np.exp(2 * rs.randn(N, K))).astype(np.float32)
+    A = wide(rs, M, K)
+    W = wide(rs, N, K)
     bias = rs.randn(N).astype(np.float32)
     ref = A.astype(np.float64) @ W.astype(np.float64).T
     mag = np.abs(A).astype(np.float64) @ np.abs(W).astype(np.float64).T + 1.0
@@ -382,22 +383,6 @@ def test_gemm_weight_gradient_form_operand_scales(grow):
     got = _gemm(A, B, None, 1, 1)
     assert np.abs(got - ref).max() < 4e-6 * mag.max()
     assert np.array_equal(got, _gemm(A, B, None, 1, 1))
-
-
-def _tn_scale_floor(X, col_block, k_tile=32, floor=2.0 ** -14):
-    """max(|x_kc|, floor * S(k, block(c))) with S = the largest magnitude of the operand's column block over every row up to
-    the end of k's tile: an upper bound of the ONE running scale the weight-gradient tile keeps per operand, workgroup tile
-    (128 columns of A, 176 of B: gemm.hip BM / BN) and K-slab (a slab starts later than row 0, so its running maximum is at
-    most this one).  ``floor``: 2^-16 of the scaled top, which sits up to HX_GROW = 2 binades above the maximum."""
-    K, C = X.shape
-    out = np.abs(X).astype(np.float64)
-    for c0 in range(0, C, col_block):
-        blk = out[:, c0:c0 + col_block]
-        per_tile = blk.reshape(-1, k_tile, blk.shape[1]).max((1, 2)) if K % k_tile == 0 else None
-        assert per_tile is not None, "K must be a multiple of the k-tile in this test"
-        run = np.maximum.accumulate(per_tile)                         # [tiles]
-        out[:, c0:c0 + col_block] = np.maximum(blk, floor * np.repeat(run, k_tile)[:, None])
-    return out
 
 
 @pytest.mark.parametrize("shape", ["ramp_up", "ramp_down", "flat"])
