@@ -604,6 +604,48 @@ int pfo_holdings_gather(const int32_t* users, int64_t U, const int32_t* hold_idx
                         const int32_t* items, int32_t I, int32_t upper_u, int32_t* pos_scratch, int32_t* port_idx_out,
                         int32_t* port_len_out, int32_t* excl_pos_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Price ledger (abi 6, additive): the log-return table of the mean-variance rank kept on the device and grown by the day.
+ * returns f64[day_cap, stock_cap, n_ret]: the day axis is a ring of slots, a slot holds stock_cap rows of n_ret doubles, row s
+ * of a day is the window of stock s's n_ret newest log-returns as of that day, oldest first.  pfo_mv_select,
+ * pfo_recommend_mv_topk and pfo_recommend_basket_topk read the table unchanged with n_days = day_cap, n_stocks = stock_cap and
+ * day_idx = the SLOT.  A row never quoted, and every row at or behind n_stocks, is all zeros: a constant series has y = 0/0, so
+ * by the NaN rule of those kernels such a stock is not admissible until its window holds two different closes.  day_keys
+ * i64[day_cap]: the key of each slot, strictly increasing over the live slots in ring order; last_close f64[stock_cap]: NaN
+ * until a stock is first quoted.  All pointers are device pointers.
+ *
+ * pfo_returns_append_day: writes rows [0, n_stocks) of slot new_slot and day_keys[new_slot] = day_key, one launch, one lane per
+ *   element, nothing else is written (rows [n_stocks, stock_cap) of the slot keep their bits).  For s < n_stocks:
+ *     R[new, s, j] = R[prev, s, j + 1] for j < n_ret - 1, copied bitwise (+0 when prev_slot == -1: the first day);
+ *     c = the close of s: dense (stamp NULL) closes[s] for s < n_closes; sparse closes[stamp[s] - 1] when 1 <= stamp[s] <=
+ *       n_closes (the table pfo_returns_scatter_closes left); otherwise not quoted.  A close that is not positive and finite
+ *       (NaN included) is "not quoted";
+ *     quoted and last_close[s] not NaN: R[new, s, n_ret - 1] = log(c / last_close[s]) - the IEEE fp64 quotient, then log;
+ *       otherwise +0.  Quoted: last_close[s] = c; not quoted: last_close[s] is carried forward.
+ *     quot_out f64[n_stocks] (may be NULL, for tests): the quotient the logarithm was taken of, NaN where none was.
+ *   prev_slot must differ from new_slot (the copy is not in place), so day_cap >= 2.
+ * pfo_returns_scatter_closes: the sparse form (stocks i32[m], closes f64[m]) -> stamp i32[n_stocks]: cleared, then
+ *   atomicMax(stamp[s], p + 1) over the positions p whose index lies in [0, n_stocks) and whose close is positive and finite;
+ *   the others are skipped.  Among repeated indices the LAST valid position wins on every run and for every launch geometry
+ *   (the scheme of pfo_holdings_store).  A memset and one launch; stamp's content on entry is irrelevant, its size is
+ *   pfo_returns_scatter_scratch_bytes(n_stocks) (-1 for bad sizes).
+ * pfo_day_lookup: slot_out[u] = the slot of the live day whose key is (int64) floor(ts[u] / key_divisor), -1 when the ledger
+ *   holds no such day (or ts[u] is not finite): a binary search over the n_days live slots head, head + 1, .. (mod day_cap).
+ *   The query kernels give a user whose day is -1 an empty answer and read nothing for it.  One launch.
+ * PFO_ERR_INVALID - checked before anything is read, nothing is written: day_cap < 2 (lookup: < 1), n_ret outside [2, 128],
+ * stock_cap outside [1, 2^31), n_stocks outside [0, stock_cap], a slot outside the ring, prev_slot == new_slot, m / n_closes
+ * outside [0, 2^31), head / n_days outside the ring, a key_divisor that is not positive and finite; then a null pointer, a
+ * short scratch.  U == 0 queues nothing.
+ */
+int64_t pfo_returns_scatter_scratch_bytes(int64_t n_stocks);
+int pfo_returns_scatter_closes(const int32_t* stocks, const double* closes, int64_t m, int64_t n_stocks, int32_t* stamp,
+                               int64_t stamp_bytes, void* stream);
+int pfo_returns_append_day(double* returns, int32_t day_cap, int64_t stock_cap, int32_t n_ret, int32_t prev_slot, int32_t new_slot,
+                           int64_t n_stocks, const double* closes, int64_t n_closes, const int32_t* stamp, double* last_close,
+                           int64_t* day_keys, int64_t day_key, double* quot_out, void* stream);
+int pfo_day_lookup(const double* ts, int64_t U, const int64_t* day_keys, int32_t day_cap, int32_t head, int32_t n_days,
+                   double key_divisor, int32_t* slot_out, void* stream);
+
 /* diagnostics for tests: copies of internals of the last forward (device pointers into the workspace) */
 typedef struct pfo_tgn_debug {
   const int32_t* n_touched;  /* [1] */

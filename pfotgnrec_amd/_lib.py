@@ -177,6 +177,11 @@ PROTOTYPES = {
                                      _VP]),
     "pfo_holdings_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP,
                                       _VP]),
+    "pfo_returns_scatter_scratch_bytes": (C.c_int64, [C.c_int64]),
+    "pfo_returns_scatter_closes": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP]),
+    "pfo_returns_append_day": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _VP, C.c_int64, _VP, _VP,
+                                         _VP, C.c_int64, _VP, _VP]),
+    "pfo_day_lookup": (C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP]),
     "pfo_tgn_debug_views": (C.c_int,[C.POINTER(TgnConfig), _VP, C.POINTER(TgnDebug)]),
     "pfo_debug_gemm": (C.c_int, [C.POINTER(GemmDesc), _VP]),
     "pfo_debug_gemm_multi": (C.c_int, [C.POINTER(GemmDesc), C.c_int32, _VP]),

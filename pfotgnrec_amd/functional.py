@@ -491,3 +491,76 @@ def holdings_gather(users, hold_idx, hold_len, upper_u, items=None, pos_scratch=
               _lib.ptr(pos_scratch if items is not None else None), port_idx.data_ptr(), port_len.data_ptr(), _lib.ptr(excl_pos),
               _lib.stream_ptr())
     return port_idx, port_len, excl_pos
+
+
+def returns_scatter_closes(stocks, closes, n_stocks, stamp=None):
+    """The sparse form of a day's closes -> the stamp table ``pfo_returns_append_day`` reads (``pfo_returns_scatter_closes``: a
+    memset and one launch).  stocks i32[m], closes f64[m]; positions whose index lies outside [0, n_stocks) or whose close is
+    not positive and finite are skipped, among repeated indices the last valid position wins.  ``stamp``: i32[>= n_stocks]
+    kept between calls (any content), None: allocated.  Returns the stamp tensor."""
+    m = int(stocks.shape[0]) if stocks.dim() == 1 else -1
+    if stocks.dtype != torch.int32 or m < 0 or closes.dtype != torch.float64 or tuple(closes.shape) != (m,):
+        raise ValueError("sparse closes must be stocks i32[m] next to closes f64[m]")
+    dev = closes.device
+    _lib.require_gpu(dev)
+    n_stocks = int(n_stocks)
+    if stamp is None or stamp.dtype != torch.int32 or stamp.numel() < n_stocks or not stamp.is_contiguous():
+        stamp = torch.empty(max(n_stocks, 1), dtype=torch.int32, device=dev)
+    if stocks.device != dev or stamp.device != dev:
+        raise ValueError("all tensors must live on %s" % dev)
+    _lib.call("pfo_returns_scatter_closes", _lib.ptr(stocks.contiguous()), _lib.ptr(closes.contiguous()), m, n_stocks, stamp.data_ptr(),
+              stamp.numel() * 4, _lib.stream_ptr())
+    return stamp
+
+
+def returns_append_day(returns, day_keys, last_close, prev_slot, new_slot, n_stocks, day_key, closes, stamp=None, want_quotients=False):
+    """One trading day appended to a return table in place (``pfo_returns_append_day``, one launch): rows [0, n_stocks) of slot
+    ``new_slot`` of ``returns`` f64[day_cap, stock_cap, n_ret] become the rows of ``prev_slot`` shifted by one with the newest
+    return ``log(close / last_close)`` (+0 for a stock not quoted today or never quoted before) in the last column;
+    ``day_keys[new_slot] = day_key``; ``last_close`` f64[>= n_stocks] takes today's closes where quoted.  ``prev_slot`` -1: the
+    first day, all zeros.  closes f64[n]: dense (entry s is stock s, NaN = not quoted), or with ``stamp`` (the table
+    ``returns_scatter_closes`` made of the sparse form) the closes that table points into.  ``want_quotients``: returns
+    f64[n_stocks], the quotient each logarithm was taken of (NaN where none was) - for tests."""
+    if (not isinstance(returns, torch.Tensor) or returns.dim() != 3 or returns.dtype != torch.float64 or not returns.is_contiguous()
+            or 0 in returns.shape):
+        raise ValueError("returns must be a contiguous float64 tensor [day_cap, stock_cap, n_ret]")
+    day_cap, stock_cap, n_ret = (int(v) for v in returns.shape)
+    if day_keys.dtype != torch.int64 or tuple(day_keys.shape) != (day_cap,) or not day_keys.is_contiguous():
+        raise ValueError("day_keys must be a contiguous int64 tensor [day_cap]")
+    n_stocks = int(n_stocks)
+    if last_close.dtype != torch.float64 or last_close.dim() != 1 or last_close.shape[0] < n_stocks or not last_close.is_contiguous():
+        raise ValueError("last_close must be a contiguous float64 tensor of at least n_stocks entries")
+    if closes.dtype != torch.float64 or closes.dim() != 1:
+        raise ValueError("closes must be float64 [n]")
+    if stamp is not None and (stamp.dtype != torch.int32 or stamp.numel() < n_stocks or not stamp.is_contiguous()):
+        raise ValueError("stamp must be a contiguous int32 tensor of at least n_stocks entries")
+    dev = returns.device
+    _lib.require_gpu(dev)
+    for t in (day_keys, last_close, closes, stamp):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    quot = torch.empty(n_stocks, dtype=torch.float64, device=dev) if want_quotients else None
+    n = int(closes.shape[0])
+    _lib.call("pfo_returns_append_day", returns.data_ptr(), day_cap, stock_cap, n_ret, int(prev_slot), int(new_slot), n_stocks,
+              _lib.ptr(closes.contiguous() if n else None), n, _lib.ptr(stamp), last_close.data_ptr(), day_keys.data_ptr(), int(day_key),
+              _lib.ptr(quot), _lib.stream_ptr())
+    return quot
+
+
+def day_lookup(ts, day_keys, head, n_days, key_divisor):
+    """slot i32[U] of the live day each timestamp falls on (``pfo_day_lookup``, one launch): key = (int64) floor(ts / key_divisor)
+    searched among the ``n_days`` live slots ``head, head + 1, ..`` (mod day_cap) of ``day_keys`` i64[day_cap]; -1 for a day the
+    ring does not hold.  ts f64[U] on the device."""
+    if not isinstance(ts, torch.Tensor) or ts.dtype != torch.float64 or ts.dim() != 1:
+        raise ValueError("ts must be a float64 tensor [U]")
+    if day_keys.dtype != torch.int64 or day_keys.dim() != 1 or not day_keys.is_contiguous():
+        raise ValueError("day_keys must be a contiguous int64 tensor [day_cap]")
+    dev = ts.device
+    _lib.require_gpu(dev)
+    if day_keys.device != dev:
+        raise ValueError("all tensors must live on %s" % dev)
+    U = int(ts.shape[0])
+    slot = torch.empty(U, dtype=torch.int32, device=dev)
+    _lib.call("pfo_day_lookup", _lib.ptr(ts.contiguous()), U, day_keys.data_ptr(), int(day_keys.shape[0]), int(head), int(n_days),
+              float(key_divisor), slot.data_ptr(), _lib.stream_ptr())
+    return slot

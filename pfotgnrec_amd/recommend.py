@@ -9,10 +9,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from .prices import PriceLedger
 
 Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held basket",
                                defaults=(None, None, False))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
+# (with a PriceLedger as the owner: the ORDINAL among its live days, or None - the day is looked up on the device)
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
 HELD = "held"     # ``exclude`` / ``portfolios``: take the rows of the model's holdings ledger (port_idx is None in the MVQuery then)
 
@@ -59,7 +61,8 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
         raise ValueError("mv.returns must be [n_days, n_stocks, n_ret]")
     if I > _lib.RECOMMEND_MV_MAX_ITEMS:
         raise ValueError("with mv, items may hold at most %d candidates (got %d)" % (_lib.RECOMMEND_MV_MAX_ITEMS, I))
-    n_days = int(mv.returns.shape[0])
+    ledger = isinstance(mv, PriceLedger)
+    n_days = mv.n_days if ledger else int(mv.returns.shape[0])   # (a ledger's day_idx counts its LIVE days, 0 = oldest)
     packed = (isinstance(portfolios, (tuple, list)) and len(portfolios) == 2
               and isinstance(portfolios[0], (torch.Tensor, np.ndarray)) and portfolios[0].ndim == 2)
     if _is_held(portfolios):
@@ -93,7 +96,9 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
             port_len[i] = len(r)
     if day_idx is None:
         if ts_h is None:
-            raise ValueError("day_idx=None takes the day from mv.day_of(timestamps): that needs timestamps on the host")
+            if not ledger:
+                raise ValueError("day_idx=None takes the day from mv.day_of(timestamps): that needs timestamps on the host")
+            return MVQuery(mv, port_idx, port_len, None)         # device timestamps: one pfo_day_lookup, no read-back
         day = np.asarray(mv.day_of(ts_h.reshape(-1)))
         day = np.broadcast_to(day.reshape(-1), (U,)) if scalar_ts else day
     elif isinstance(day_idx, torch.Tensor):
@@ -251,7 +256,7 @@ def assemble(tgn, q, return_embeddings=False):
             ok_d = (to_dev(q.item_ok if q.ok_h is None else q.ok_h, torch.int64) != 0).to(torch.uint8)
         if q.mv is not None:
             return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                                held_ports)
+                                held_ports, user_ts)
         if user_block is not None and n_t > 1:
             # users of one block side by side: the kernel serves a tile of 16 users in one pass per distinct block
             order = torch.argsort(user_block, stable=True)
@@ -271,10 +276,11 @@ def assemble(tgn, q, return_embeddings=False):
 
 
 def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                 held_ports=None):
+                 held_ports=None, user_ts=None):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
     portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held").
-    ``q.basket``: ``recommend_basket_topk`` in its place."""
+    ``q.basket``: ``recommend_basket_topk`` in its place.  With a ``PriceLedger`` the kernels index its storage by ring slot:
+    day ordinals become slots, no day index at all is ``pfo_day_lookup`` over ``user_ts`` f64[U] on the device."""
     from .functional import recommend_basket_topk, recommend_mv_topk
     topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
     dev, k, U, mv = tgn.device, q.k, q.U, q.mv.src
@@ -283,7 +289,10 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
         returns = torch.from_numpy(np.ascontiguousarray(returns, dtype=np.float64))
     returns = returns.to(device=dev, dtype=torch.float64)
     cand_stock = (items_d - (int(mv.upper_u) + 1)).contiguous()
-    day = to_dev(q.mv.day_idx, torch.int32)
+    if isinstance(mv, PriceLedger):
+        day = mv.lookup(user_ts.contiguous()) if q.mv.day_idx is None else to_dev(mv.slots_of(q.mv.day_idx), torch.int32)
+    else:
+        day = to_dev(q.mv.day_idx, torch.int32)
     if held_ports is not None:
         port_idx, port_len = held_ports
     else:

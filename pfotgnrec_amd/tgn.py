@@ -1184,6 +1184,11 @@ class TGN(nn.Module):
         (``track_holdings``) in place of the argument - one ``pfo_holdings_gather`` over the users already on the device, no
         lists packed or uploaded per query; ``portfolios="held"`` still needs ``mv``, whose ``upper_u`` must be the ledger's.
 
+        ``mv`` may be a ``PriceLedger`` (prices.py): its return table grows by the day on the device.  ``day_idx`` is then the
+        ordinal among the ledger's live days (0 = oldest); ``day_idx=None`` also takes DEVICE timestamps - one
+        ``pfo_day_lookup``, no read-back - and a user whose day the ledger does not hold gets an empty answer there, where host
+        timestamps raise ``KeyError``.
+
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` are not (it would cost a
         read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
