@@ -16,8 +16,18 @@
 //      list longer than a chunk is a walk over chunks with the list carried along.
 // Users of one tile that sit in different blocks are served block by block (a pass per distinct block of the tile; callers
 // that sort their users by block get one pass).
+//
+// Layout of the file.  Three kernels - plain, mean-variance, basket - over one argument block (RecArgs, with RecMvArgs for the
+// last two), passed by value.  What they share is written once, above them: the opening (rec_user_fragments, rec_block_table,
+// rec_next_pass), stage A (rec_score_tile / rec_score_chunk), the exclusion-length clamp, and for the last two the per-user
+// header (RecMvUser), the two halves of the admissible set and the empty-slot tail (rec_mv_*).  Only the rank loops are each
+// kernel's own (rec_next_pass hands out the members and leaves the `while (pending)` to the kernel: as the loop's condition it
+// cost the plain and the mean-variance kernel 10 to 14 VGPRs and two of them a wave of occupancy).  On the host one
+// check per argument block (rec_check_common, rec_check_mv) and one launcher (rec_launch: the NJ dispatch, the LDS attribute,
+// the launch and its check) serve the three entries.
 #include "common.hpp"
 #include "mv_value.hpp"
+#include <type_traits>
 
 #define PFO_REC_THREADS 256
 #define PFO_REC_TILE 16                       // users per workgroup = rows of the MFMA tile
@@ -27,6 +37,25 @@
 namespace {
 
 typedef float rec_f32x4 __attribute__((ext_vector_type(4)));
+
+// What the three kernels share: the arguments of pfo_recommend_topk (include/pfotgn.h) and IC, the candidates a row of LDS holds.
+struct RecArgs {
+  const float *user_emb, *item_emb;
+  const int32_t *user_block, *excl_pos, *excl_len;
+  const uint8_t* item_ok;
+  int64_t U;
+  int I, n_t, D, excl_stride, k, IC;
+  int32_t *top_pos, *n_valid;
+  float* top_score;
+};
+// The mean-variance side (pfo_recommend_mv_topk) but for its five read-only tables, which the kernels take as __restrict__
+// parameters of their own (PFO_REC_MV_TABLES); the three diagnostic outputs are the mv kernel's alone.
+struct RecMvArgs {
+  int n_days, n_stocks, n_ret, port_stride;
+  double gamma, lam;
+  double *top_fused, *y_out, *fused_out;
+  float* score_out;
+};
 
 // fp32 -> unsigned with the same order; -0 and +0 share a key (they are equal scores)
 __device__ __forceinline__ uint32_t rec_ordered(float s) {
@@ -39,8 +68,50 @@ __device__ __forceinline__ float rec_unordered(uint32_t o) {
 }
 __device__ __forceinline__ unsigned long long rec_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
+// ---- the opening of every kernel: the user fragments, the tile's block table, the passes
+// this lane's pieces of user row r: NJ 16-byte pieces per lane cover a row of D <= 16 * NJ floats (a row beyond U reads the last
+// user's: its scores are never selected from)
+template <int NJ>
+__device__ __forceinline__ void rec_user_fragments(float4 (&uf)[NJ], const float* __restrict__ user_emb, int64_t u0, int64_t U, int D) {
+  const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+  const float4* up = reinterpret_cast<const float4*>(user_emb + min(u0 + r, U - 1) * D);
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int d = 16 * j + 4 * q;
+    uf[j] = d < D ? up[d >> 2] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+// ub[i] = the block user u0 + i is scored against, -1 for a row beyond U: served by no pass.  All threads (a barrier);
+// returns the users still to be served, a bit each.
+__device__ __forceinline__ unsigned rec_block_table(int* ub, const RecArgs& a, int64_t u0) {
+  const int tid = threadIdx.x;
+  if (tid < PFO_REC_TILE) {
+    const int64_t u = u0 + tid;
+    int b = -1;
+    if (u < a.U) b = a.user_block ? min(max(a.user_block[u], 0), a.n_t - 1) : 0;
+    ub[tid] = b;
+  }
+  __syncthreads();
+  unsigned pending = 0;
+#pragma unroll
+  for (int i = 0; i < PFO_REC_TILE; ++i) pending |= (ub[i] >= 0 ? 1u : 0u) << i;
+  return pending;
+}
+// One pass per distinct block of the tile: takes the block b of the first pending user and every pending user of that block
+// (the members, returned) out of `pending`, which is not 0.  The same for every thread.
+__device__ __forceinline__ unsigned rec_next_pass(unsigned& pending, const int* ub, int& b) {
+  b = ub[__ffs(pending) - 1];
+  unsigned members = 0;
+#pragma unroll
+  for (int i = 0; i < PFO_REC_TILE; ++i) members |= (((pending >> i) & 1u) && ub[i] == b ? 1u : 0u) << i;
+  pending &= ~members;
+  return members;
+}
+
+// ---- stage A
 // One 16 x 16 tile of scores: acc[i] = user row 4 q + i . candidate row `item` (this lane's column), uf the lane's pieces of its
-// user row.  The ONE place the accumulation order of a score is written down: both kernels below call it, so they agree to the bit.
+// user row.  The ONE place the accumulation order of a score is written down: every kernel below comes here through
+// rec_score_chunk, so they agree to the bit.
 template <int NJ>
 __device__ __forceinline__ rec_f32x4 rec_score_tile(const float4 (&uf)[NJ], const float* __restrict__ items, int item, int D, int q) {
   const float4* ip = reinterpret_cast<const float4*>(items + (int64_t)item * D);
@@ -61,48 +132,96 @@ __device__ __forceinline__ rec_f32x4 rec_score_tile(const float4 (&uf)[NJ], cons
   return acc;
 }
 
-// NJ 16-byte pieces per lane cover a row of D <= 16 * NJ floats
+// The scores of the tile's users against candidates [c0, c0 + n) of `items` into sc[16][ICS], candidate c0 + c in column c.
+// The caller's barriers stand around it.
 template <int NJ>
-__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(
-    const float* __restrict__ user_emb, const float* __restrict__ item_emb, const int32_t* __restrict__ user_block, int64_t U,
-    int I, int n_t, int D, const int32_t* __restrict__ excl_pos, const int32_t* __restrict__ excl_len, int excl_stride,
-    const uint8_t* __restrict__ item_ok, int k, int32_t* __restrict__ top_pos, float* __restrict__ top_score,
-    int32_t* __restrict__ n_valid, int IC) {
+__device__ __forceinline__ void rec_score_chunk(const float4 (&uf)[NJ], const float* __restrict__ items, int c0, int n, int I, int D,
+                                                float* sc, int ICS) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+  const int n_tile = (n + 15) >> 4;
+  for (int t = wave; t < n_tile; t += 4) {
+    const rec_f32x4 acc = rec_score_tile<NJ>(uf, items, min(c0 + 16 * t + r, I - 1), D, q);   // (a column beyond I repeats the last row; never read back)
+    // acc[i] = score(user 4 q + i, candidate c0 + 16 t + r)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sc[(4 * q + i) * ICS + 16 * t + r] = acc[i];
+  }
+}
+
+// how much of user u's exclusion row counts
+__device__ __forceinline__ int rec_excl_len(const RecArgs& a, int64_t u) {
+  return (a.excl_pos && a.excl_stride > 0) ? min(max(a.excl_len[u], 0), a.excl_stride) : 0;
+}
+
+// ---- what the mean-variance and the basket kernel share per user
+struct RecMvUser {
+  bool day_ok;          // no day: nothing of this user's is read
+  int plen;             // how much of the portfolio row counts
+  const double* dayp;   // the day's [n_stocks][n_ret] returns
+  __device__ __forceinline__ RecMvUser(const RecMvArgs& m, const double* __restrict__ returns, const int32_t* __restrict__ day_idx,
+                                       const int32_t* __restrict__ port_idx, const int32_t* __restrict__ port_len, int64_t u) {
+    const int day = day_idx[u];
+    day_ok = day >= 0 && day < m.n_days;
+    plen = (day_ok && port_idx && m.port_stride > 0) ? min(max(port_len[u], 0), m.port_stride) : 0;
+    dayp = returns + (int64_t)(day_ok ? day : 0) * m.n_stocks * m.n_ret;
+  }
+};
+// The admissible set, first half: the row of candidate c in the day's returns, -1 where c takes no part - item_ok, cand_stock
+// or the day outside the tables.  Such a candidate is a NaN in LDS yv[I]: every comparison with it is false, so it takes part
+// in no count.
+__device__ __forceinline__ int rec_mv_stock(const RecArgs& a, const int32_t* __restrict__ cand_stock, int n_stocks, int c, bool day_ok) {
+  if (!day_ok || (a.item_ok && !a.item_ok[c])) return -1;
+  const int stock = cand_stock[c];
+  return stock >= 0 && stock < n_stocks ? stock : -1;
+}
+// Second half: the exclusion list of user u scattered over yv[I] as NaN.  All threads; a barrier before and after.
+__device__ __forceinline__ void rec_mv_exclude(double* yv, const RecArgs& a, int64_t u) {
+  __syncthreads();
+  const int len = rec_excl_len(a, u);
+  for (int e = threadIdx.x; e < len; e += PFO_REC_THREADS) {
+    const int p = a.excl_pos[u * a.excl_stride + e];
+    if (p >= 0 && p < a.I) yv[p] = __builtin_nan("");                // (duplicates store the same value)
+  }
+  __syncthreads();
+}
+
+// slots n .. k - 1 of user u's output row are empty: -1 / -inf / -inf; n_valid[u] = n
+__device__ __forceinline__ void rec_mv_empty_slots(int32_t* __restrict__ top_pos, float* __restrict__ top_score, double* __restrict__ top_fused,
+                                                   int32_t* __restrict__ n_valid, int64_t u, int k, int n) {
+  const int tid = threadIdx.x;
+  if (tid >= n && tid < k) {                                         // (k <= 64: a thread each)
+    top_pos[u * k + tid] = -1;
+    top_score[u * k + tid] = -__builtin_inff();
+    top_fused[u * k + tid] = -__builtin_inf();
+  }
+  if (tid == 0 && n_valid) n_valid[u] = n;
+}
+
+// the canonical order: is (f, c) before the best so far (bf, bc)?  bc < 0: there is none yet
+__device__ __forceinline__ bool rec_better(double f, int c, double bf, int bc) { return bc < 0 || f > bf || (f == bf && c > bc); }
+
+// ---------------------------------------------------------------------------------------------
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const RecArgs a) {
+  const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
+  const int32_t* __restrict__ excl_pos = a.excl_pos;
+  const uint8_t* __restrict__ item_ok = a.item_ok;
+  int32_t *__restrict__ top_pos = a.top_pos, *__restrict__ n_valid = a.n_valid;
+  float* __restrict__ top_score = a.top_score;
+  const int I = a.I, D = a.D, k = a.k, IC = a.IC, excl_stride = a.excl_stride;
   const int ICS = IC + 4;                                            // row stride: the four user rows a half-wave writes fall on different banks
   extern __shared__ float lds[];
   float* sc = lds;                                                    // [16][ICS]
   uint8_t* ok = reinterpret_cast<uint8_t*>(sc + PFO_REC_TILE * ICS);  // [IC]
   __shared__ int ub[PFO_REC_TILE];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
 
-  if (tid < PFO_REC_TILE) {
-    const int64_t u = u0 + tid;
-    int b = -1;                                                      // a row beyond U: served by no pass
-    if (u < U) b = user_block ? min(max(user_block[u], 0), n_t - 1) : 0;
-    ub[tid] = b;
-  }
-  // this lane's pieces of user row r (a row beyond U reads the last user's: its scores are never selected from)
   float4 uf[NJ];
-  {
-    const float4* up = reinterpret_cast<const float4*>(user_emb + min(u0 + r, U - 1) * D);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int d = 16 * j + 4 * q;
-      uf[j] = d < D ? up[d >> 2] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  __syncthreads();
-  unsigned pending = 0;
-#pragma unroll
-  for (int i = 0; i < PFO_REC_TILE; ++i) pending |= (ub[i] >= 0 ? 1u : 0u) << i;
-
-  while (pending) {                                                  // one pass per distinct block of the tile
-    const int b = ub[__ffs(pending) - 1];
-    unsigned members = 0;
-#pragma unroll
-    for (int i = 0; i < PFO_REC_TILE; ++i) members |= (((pending >> i) & 1u) && ub[i] == b ? 1u : 0u) << i;
-    pending &= ~members;
+  rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  unsigned pending = rec_block_table(ub, a, u0);
+  while (pending) {
+    int b;
+    const unsigned members = rec_next_pass(pending, ub, b);
     const float* items = item_emb + (int64_t)b * I * D;
 
     unsigned long long list[4] = {0ull, 0ull, 0ull, 0ull};           // lane t: rank t of user 4 * wave + i so far
@@ -110,13 +229,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(
       const int n = min(IC, I - c0);
       __syncthreads();                                               // the previous chunk's keys have been taken from LDS
       // ---- A: scores of candidates [c0, c0 + n)
-      const int n_tile = (n + 15) >> 4;
-      for (int t = wave; t < n_tile; t += 4) {
-        const rec_f32x4 acc = rec_score_tile<NJ>(uf, items, min(c0 + 16 * t + r, I - 1), D, q);   // (a column beyond I repeats the last row; never read back)
-        // acc[i] = score(user 4 q + i, candidate 16 t + r)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sc[(4 * q + i) * ICS + 16 * t + r] = acc[i];
-      }
+      rec_score_chunk<NJ>(uf, items, c0, n, I, D, sc, ICS);
       for (int c = tid; c < n; c += PFO_REC_THREADS) ok[c] = item_ok ? item_ok[c0 + c] : (uint8_t)1;
       __syncthreads();
 
@@ -136,7 +249,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(
             if (c < n && ok[c]) adm |= 1u << m;
           }
           const int64_t u = u0 + us;
-          const int len = (excl_pos && excl_stride > 0) ? min(max(excl_len[u], 0), excl_stride) : 0;
+          const int len = rec_excl_len(a, u);
           for (int e0 = 0; e0 < len; e0 += 64) {
             int rel = -1;                                            // position within the chunk, -1: not in it
             if (e0 + lane < len) {
@@ -209,11 +322,11 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(
 
 // ---------------------------------------------------------------------------------------------
 // Portfolio-aware top-k: the rank fusion of main.py:243-289 over the WHOLE candidate list of a user, in the same launch shape.
-//   A  scores of the tile's 16 users against ALL I <= 2048 candidates of a block, as above (rec_score_tile), into LDS [16][I].
+//   A  scores of the tile's 16 users against ALL I <= 2048 candidates of a block, as above (rec_score_chunk), into LDS [16][I].
 //   Then the users of the pass one at a time, all four wavefronts on one user:
 //   B  y_mv of every candidate in fp64 (pfo_mv_value, the arithmetic mv_select_kernel runs) into LDS y[I]; a candidate that is
-//      not admissible - item_ok, cand_stock or the day outside the tables, a NaN y, then the exclusion list - is a NaN there:
-//      every comparison with it is false, so it takes part in no count below.
+//      not admissible - item_ok, cand_stock or the day outside the tables (rec_mv_stock), a NaN y, then the exclusion list
+//      (rec_mv_exclude) - is a NaN there: every comparison with it is false, so it takes part in no count below.
 //   C  average-tie ranks of y and of the fp32 score by counting over LDS (scipy's rankdata is less + (equal + 1) / 2), blended
 //      into `fused` in registers (a thread owns candidates tid, tid + 256, ...: eight at most); after a barrier fused replaces y.
 //   D  the place of a candidate in the canonical order (fused descending, the larger position first among equal values) is
@@ -222,60 +335,38 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(
 // CU there, four at I = 500.  About 3 I^2 comparisons per user.
 #define PFO_RMV_PER_THREAD (PFO_RECOMMEND_MV_MAX_ITEMS / PFO_REC_THREADS)
 
+// cand_stock, returns, day_idx, port_idx and port_len stay __restrict__ kernel parameters: a qualifier on a struct member or
+// a local tells the compiler nothing, and without it what all lanes read alike - the holdings, their return rows, the day -
+// is no longer read with scalar loads (the two kernels then ran 3.4 % and 1.2 % longer).
+#define PFO_REC_MV_TABLES                                                                                     \
+  const int32_t *__restrict__ cand_stock, const double *__restrict__ returns, const int32_t *__restrict__ day_idx, \
+      const int32_t *__restrict__ port_idx, const int32_t *__restrict__ port_len
 template <int NJ>
-__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(
-    const float* __restrict__ user_emb, const float* __restrict__ item_emb, const int32_t* __restrict__ user_block, int64_t U,
-    int I, int n_t, int D, const int32_t* __restrict__ excl_pos, const int32_t* __restrict__ excl_len, int excl_stride,
-    const uint8_t* __restrict__ item_ok, const int32_t* __restrict__ cand_stock, const double* __restrict__ returns, int n_days,
-    int n_stocks, int n_ret, const int32_t* __restrict__ day_idx, const int32_t* __restrict__ port_idx,
-    const int32_t* __restrict__ port_len, int port_stride, double gamma, double lam, int k, int32_t* __restrict__ top_pos,
-    float* __restrict__ top_score, double* __restrict__ top_fused, int32_t* __restrict__ n_valid, float* __restrict__ score_out,
-    double* __restrict__ y_out, double* __restrict__ fused_out, int IC) {
+__device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES) {
+  const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
+  int32_t* __restrict__ top_pos = a.top_pos;
+  float *__restrict__ top_score = a.top_score, *__restrict__ score_out = m.score_out;
+  double *__restrict__ top_fused = m.top_fused, *__restrict__ y_out = m.y_out, *__restrict__ fused_out = m.fused_out;
+  const int I = a.I, D = a.D, k = a.k, IC = a.IC;
+  const double lam = m.lam;
   const int ICS = IC + 4;
   extern __shared__ double lds_mv[];
   double* yv = lds_mv;                                               // [IC]: y, then fused, of the user being ranked
   float* sc = reinterpret_cast<float*>(yv + IC);                     // [16][ICS]
   __shared__ int ub[PFO_REC_TILE];
   __shared__ int n_adm;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+  const int tid = threadIdx.x;
   const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
   const double nan = __builtin_nan("");
 
-  if (tid < PFO_REC_TILE) {
-    const int64_t u = u0 + tid;
-    int b = -1;
-    if (u < U) b = user_block ? min(max(user_block[u], 0), n_t - 1) : 0;
-    ub[tid] = b;
-  }
   float4 uf[NJ];
-  {
-    const float4* up = reinterpret_cast<const float4*>(user_emb + min(u0 + r, U - 1) * D);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int d = 16 * j + 4 * q;
-      uf[j] = d < D ? up[d >> 2] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  __syncthreads();
-  unsigned pending = 0;
-#pragma unroll
-  for (int i = 0; i < PFO_REC_TILE; ++i) pending |= (ub[i] >= 0 ? 1u : 0u) << i;
-
-  while (pending) {                                                  // one pass per distinct block of the tile
-    const int b = ub[__ffs(pending) - 1];
-    unsigned members = 0;
-#pragma unroll
-    for (int i = 0; i < PFO_REC_TILE; ++i) members |= (((pending >> i) & 1u) && ub[i] == b ? 1u : 0u) << i;
-    pending &= ~members;
-    const float* items = item_emb + (int64_t)b * I * D;
-
+  rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  unsigned pending = rec_block_table(ub, a, u0);
+  while (pending) {
+    int b;
+    const unsigned members = rec_next_pass(pending, ub, b);
     // ---- A: scores of all candidates (the previous pass ended on a barrier)
-    const int n_tile = (I + 15) >> 4;
-    for (int t = wave; t < n_tile; t += 4) {
-      const rec_f32x4 acc = rec_score_tile<NJ>(uf, items, min(16 * t + r, I - 1), D, q);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sc[(4 * q + i) * ICS + 16 * t + r] = acc[i];
-    }
+    rec_score_chunk<NJ>(uf, item_emb + (int64_t)b * I * D, 0, I, I, D, sc, ICS);
     __syncthreads();
 
     for (int us = 0; us < PFO_REC_TILE; ++us) {
@@ -284,38 +375,22 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(
       const float* su = sc + us * ICS;
       if (tid == 0) n_adm = 0;
       // ---- B: y_mv, NaN where the candidate is not admissible
-      const int day = day_idx[u];
-      const bool day_ok = day >= 0 && day < n_days;                  // no day: nothing of this user's is read
-      const int plen = (day_ok && port_idx && port_stride > 0) ? min(max(port_len[u], 0), port_stride) : 0;
-      const double* dayp = returns + (int64_t)(day_ok ? day : 0) * n_stocks * n_ret;
+      const RecMvUser h(m, returns, day_idx, port_idx, port_len, u);
       for (int c = tid; c < I; c += PFO_REC_THREADS) {
         if (score_out) score_out[u * I + c] = su[c];
-        double y = nan;
-        if (day_ok && (!item_ok || item_ok[c])) {
-          const int stock = cand_stock[c];
-          if (stock >= 0 && stock < n_stocks)
-            y = pfo_mv_value<true>(dayp, stock, n_stocks, n_ret, port_idx + u * port_stride, plen, gamma);
-        }
-        yv[c] = y;
+        const int stock = rec_mv_stock(a, cand_stock, m.n_stocks, c, h.day_ok);
+        yv[c] = stock < 0 ? nan : pfo_mv_value<true>(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + u * m.port_stride, h.plen, m.gamma);
       }
-      __syncthreads();
-      {
-        const int len = (excl_pos && excl_stride > 0) ? min(max(excl_len[u], 0), excl_stride) : 0;
-        for (int e = tid; e < len; e += PFO_REC_THREADS) {
-          const int p = excl_pos[u * excl_stride + e];
-          if (p >= 0 && p < I) yv[p] = nan;                          // (duplicates store the same value)
-        }
-      }
-      __syncthreads();
+      rec_mv_exclude(yv, a, u);
       // ---- C: ranks over the admissible candidates, blended
       double fused[PFO_RMV_PER_THREAD];
       int mine = 0;
 #pragma unroll
-      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) fused[m] = nan;
+      for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) fused[s] = nan;
 #pragma unroll
-      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
-        const int c = tid + PFO_REC_THREADS * m;
-        if (PFO_REC_THREADS * m >= I) break;
+      for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+        const int c = tid + PFO_REC_THREADS * s;
+        if (PFO_REC_THREADS * s >= I) break;
         if (c >= I) continue;
         const double yi = yv[c];
         if (y_out) y_out[u * I + c] = yi;
@@ -331,26 +406,26 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(
           ls += (aj && sj < si);
           es += (aj && sj == si);                                    // (-0 == +0)
         }
-        fused[m] = pfo_mv_blend(pfo_mv_avg_rank(ly, ey), pfo_mv_avg_rank(ls, es), lam);   // main.py:282-286
+        fused[s] = pfo_mv_blend(pfo_mv_avg_rank(ly, ey), pfo_mv_avg_rank(ls, es), lam);   // main.py:282-286
         ++mine;
       }
       __syncthreads();                                               // every y has been read
 #pragma unroll
-      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
-        const int c = tid + PFO_REC_THREADS * m;
+      for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+        const int c = tid + PFO_REC_THREADS * s;
         if (c < I) {
-          yv[c] = fused[m];
-          if (fused_out) fused_out[u * I + c] = fused[m];
+          yv[c] = fused[s];
+          if (fused_out) fused_out[u * I + c] = fused[s];
         }
       }
       if (mine) atomicAdd(&n_adm, mine);
       __syncthreads();
       // ---- D: the first k of the canonical order
 #pragma unroll
-      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
-        const int c = tid + PFO_REC_THREADS * m;
-        if (PFO_REC_THREADS * m >= I) break;
-        const double fi = fused[m];
+      for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+        const int c = tid + PFO_REC_THREADS * s;
+        if (PFO_REC_THREADS * s >= I) break;
+        const double fi = fused[s];
         if (c >= I || !(fi == fi)) continue;
         int before = 0;
         for (int j = 0; j < I; ++j) {
@@ -358,49 +433,51 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(
           before += (fj > fi) || (fj == fi && j > c);
         }
         if (before < k) {
-          const float s = su[c];
+          const float sv = su[c];
           top_pos[u * k + before] = c;
-          top_score[u * k + before] = s == 0.f ? 0.f : s;            // a zero score is handed out as +0
+          top_score[u * k + before] = sv == 0.f ? 0.f : sv;          // a zero score is handed out as +0
           top_fused[u * k + before] = fi;
         }
       }
-      const int n = min(k, n_adm);
-      if (tid >= n && tid < k) {
-        top_pos[u * k + tid] = -1;
-        top_score[u * k + tid] = -__builtin_inff();
-        top_fused[u * k + tid] = -__builtin_inf();
-      }
-      if (tid == 0 && n_valid) n_valid[u] = n;
+      rec_mv_empty_slots(top_pos, top_score, top_fused, a.n_valid, u, k, min(k, n_adm));
       __syncthreads();                                               // n_adm and y are free for the next user
     }
   }
 }
 
+// (the body inlined into its kernel, not the kernel itself: written as the kernel, the D <= 176 instantiation takes 165 VGPRs
+// instead of 163 and loses its third wave per SIMD)
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES) {
+  recommend_mv_topk_body<NJ>(a, m, cand_stock, returns, day_idx, port_idx, port_len);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Basket top-k: the list of recommend_mv_topk_kernel taken one pick at a time, each pick joining the holdings before the next
 // is ranked (include/pfotgn.h states the rounds).  Same launch shape and the same stage A.  Per user, all four wavefronts:
-//   B  the admissible set once - item_ok, cand_stock and the day, then the exclusion list scattered over LDS y[I] - read back
-//      into a bit per owned candidate (a thread owns candidates tid, tid + 256, ...); mu, var and the covariance sum over the
-//      portfolio of every owned candidate in registers (pfo_mv_mean / pfo_mv_var / pfo_mv_add_cov: pfo_mv_value's pieces).
+//   B  the admissible set once (rec_mv_stock, rec_mv_exclude over LDS y[I]) - read back into a bit per owned candidate (a
+//      thread owns candidates tid, tid + 256, ...); mu, var and the covariance sum over the portfolio of every owned candidate
+//      in registers (pfo_mv_mean / pfo_mv_var / pfo_mv_add_cov: pfo_mv_value's pieces).
 //   k rounds of
 //   C  y of the round from the three registers (pfo_mv_finish) into LDS y[I], NaN where the candidate takes no part, and NaN
 //      over its score in the user's LDS row likewise (the owner keeps the score in a register; the row is this user's alone):
 //      the two rank counts of stage C above then need no mask, and run over four candidates per LDS read (y and the row are
 //      NaN from I up to the next multiple of 16); the blend as above;
-//   P  the pick: the arg-max of (fused, position) over the thread's candidates, the wavefront (shuffles), the workgroup (four
-//      LDS slots).  Its owner writes slot r of the output row, clears its bit and sets y[pick] to NaN; every thread adds the
-//      pick's covariance to its candidates' sums - one n_ret-long pass per candidate and round, nothing else is recomputed.
+//   P  the pick: the arg-max of (fused, position) (rec_better) over the thread's candidates, the wavefront (shuffles), the
+//      workgroup (four LDS slots).  Its owner writes slot r of the output row, clears its bit and sets y[pick] to NaN; every
+//      thread adds the pick's covariance to its candidates' sums - one n_ret-long pass per candidate and round, nothing else
+//      is recomputed.
 // LDS as above (the per-candidate values are registers; the dynamic part starts 16-byte aligned for the wide reads).
 // 2 k I^2 comparisons and (held + k - 1) I n_ret multiply-adds per user.
 // Two barriers per round; every loop bound between them depends on k, I and the pick (the same for all threads) alone.
 template <int NJ>
-__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
-    const float* __restrict__ user_emb, const float* __restrict__ item_emb, const int32_t* __restrict__ user_block, int64_t U,
-    int I, int n_t, int D, const int32_t* __restrict__ excl_pos, const int32_t* __restrict__ excl_len, int excl_stride,
-    const uint8_t* __restrict__ item_ok, const int32_t* __restrict__ cand_stock, const double* __restrict__ returns, int n_days,
-    int n_stocks, int n_ret, const int32_t* __restrict__ day_idx, const int32_t* __restrict__ port_idx,
-    const int32_t* __restrict__ port_len, int port_stride, double gamma, double lam, int k, int32_t* __restrict__ top_pos,
-    float* __restrict__ top_score, double* __restrict__ top_fused, int32_t* __restrict__ n_valid, int IC) {
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES) {
+  const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
+  int32_t* __restrict__ top_pos = a.top_pos;
+  float* __restrict__ top_score = a.top_score;
+  double* __restrict__ top_fused = m.top_fused;
+  const int I = a.I, D = a.D, k = a.k, IC = a.IC, n_stocks = m.n_stocks, n_ret = m.n_ret;
+  const double gamma = m.gamma, lam = m.lam;
   const int ICS = IC + 4;
   extern __shared__ __attribute__((aligned(16))) double lds_basket[];
   double* yv = lds_basket;                                           // [IC]: y of the round, NaN = takes no part
@@ -408,110 +485,65 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
   __shared__ int ub[PFO_REC_TILE];
   __shared__ double wave_f[PFO_REC_THREADS / 64];                    // the best (fused, position) of each wavefront
   __shared__ int wave_c[PFO_REC_THREADS / 64];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, q = lane >> 4;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
   const double nan = __builtin_nan("");
   const double inv = pfo_mv_inv(n_ret);
 
-  if (tid < PFO_REC_TILE) {
-    const int64_t u = u0 + tid;
-    int b = -1;
-    if (u < U) b = user_block ? min(max(user_block[u], 0), n_t - 1) : 0;
-    ub[tid] = b;
-  }
   float4 uf[NJ];
-  {
-    const float4* up = reinterpret_cast<const float4*>(user_emb + min(u0 + r, U - 1) * D);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-      const int d = 16 * j + 4 * q;
-      uf[j] = d < D ? up[d >> 2] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  __syncthreads();
-  unsigned pending = 0;
-#pragma unroll
-  for (int i = 0; i < PFO_REC_TILE; ++i) pending |= (ub[i] >= 0 ? 1u : 0u) << i;
-
-  while (pending) {                                                  // one pass per distinct block of the tile
-    const int b = ub[__ffs(pending) - 1];
-    unsigned members = 0;
-#pragma unroll
-    for (int i = 0; i < PFO_REC_TILE; ++i) members |= (((pending >> i) & 1u) && ub[i] == b ? 1u : 0u) << i;
-    pending &= ~members;
-    const float* items = item_emb + (int64_t)b * I * D;
-
+  rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  unsigned pending = rec_block_table(ub, a, u0);
+  while (pending) {
+    int b;
+    const unsigned members = rec_next_pass(pending, ub, b);
     // ---- A: scores of all candidates (the previous pass ended on a barrier)
-    const int n_tile = (I + 15) >> 4;
-    for (int t = wave; t < n_tile; t += 4) {
-      const rec_f32x4 acc = rec_score_tile<NJ>(uf, items, min(16 * t + r, I - 1), D, q);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sc[(4 * q + i) * ICS + 16 * t + r] = acc[i];
-    }
+    rec_score_chunk<NJ>(uf, item_emb + (int64_t)b * I * D, 0, I, I, D, sc, ICS);
     __syncthreads();
 
     for (int us = 0; us < PFO_REC_TILE; ++us) {
       if (!((members >> us) & 1u)) continue;                         // (the same for every thread)
       const int64_t u = u0 + us;
       float* su = sc + us * ICS;                                     // the user's scores; NaN where the candidate takes no part
-      const int day = day_idx[u];
-      const bool day_ok = day >= 0 && day < n_days;                  // no day: nothing of this user's is read
-      const int plen = (day_ok && port_idx && port_stride > 0) ? min(max(port_len[u], 0), port_stride) : 0;
-      const double* dayp = returns + (int64_t)(day_ok ? day : 0) * n_stocks * n_ret;
+      const RecMvUser h(m, returns, day_idx, port_idx, port_len, u);
+      const double* dayp = h.dayp;
       // ---- B: the admissible set, then mu, var and the covariance sum over the portfolio
-      for (int c = tid; c < I; c += PFO_REC_THREADS) {
-        bool ok = day_ok && (!item_ok || item_ok[c]);
-        if (ok) {
-          const int stock = cand_stock[c];
-          ok = stock >= 0 && stock < n_stocks;
-        }
-        yv[c] = ok ? 0.0 : nan;
-      }
-      for (int c = I + tid; c < IC; c += PFO_REC_THREADS) yv[c] = nan;
-      __syncthreads();
-      {
-        const int len = (excl_pos && excl_stride > 0) ? min(max(excl_len[u], 0), excl_stride) : 0;
-        for (int e = tid; e < len; e += PFO_REC_THREADS) {
-          const int p = excl_pos[u * excl_stride + e];
-          if (p >= 0 && p < I) yv[p] = nan;                          // (duplicates store the same value)
-        }
-      }
-      __syncthreads();
+      for (int c = tid; c < IC; c += PFO_REC_THREADS) yv[c] = c < I && rec_mv_stock(a, cand_stock, m.n_stocks, c, h.day_ok) >= 0 ? 0.0 : nan;
+      rec_mv_exclude(yv, a, u);
       double mu[PFO_RMV_PER_THREAD], var[PFO_RMV_PER_THREAD], ssum[PFO_RMV_PER_THREAD];
       float score[PFO_RMV_PER_THREAD];
-      unsigned alive = 0;                                            // bit m: candidate tid + 256 m is in the pool
+      unsigned alive = 0;                                            // bit s: candidate tid + 256 s is in the pool
 #pragma unroll
-      for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
-        const int c = tid + PFO_REC_THREADS * m;
-        mu[m] = var[m] = ssum[m] = 0.0;
-        score[m] = 0.f;
+      for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+        const int c = tid + PFO_REC_THREADS * s;
+        mu[s] = var[s] = ssum[s] = 0.0;
+        score[s] = 0.f;
         if (c < I && yv[c] == yv[c]) {
-          alive |= 1u << m;
-          score[m] = su[c];
+          alive |= 1u << s;
+          score[s] = su[c];
           const double* ri = dayp + (int64_t)cand_stock[c] * n_ret;
-          mu[m] = pfo_mv_mean(ri, n_ret);
-          var[m] = pfo_mv_var(ri, mu[m], n_ret, inv);
+          mu[s] = pfo_mv_mean(ri, n_ret);
+          var[s] = pfo_mv_var(ri, mu[s], n_ret, inv);
         } else if (c < IC) {
           su[c] = __builtin_nanf("");
         }
       }
-      // one more holding: row s of the day (in range) joins every pooled candidate's sum
-      auto hold = [&](int s) {
-        const double* rp = dayp + (int64_t)s * n_ret;
+      // one more holding: row st of the day (in range) joins every pooled candidate's sum
+      auto hold = [&](int st) {
+        const double* rp = dayp + (int64_t)st * n_ret;
         const double mp = pfo_mv_mean(rp, n_ret);
 #pragma unroll
-        for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
-          if (!((alive >> m) & 1u)) continue;
-          const double* ri = dayp + (int64_t)cand_stock[tid + PFO_REC_THREADS * m] * n_ret;
-          ssum[m] = pfo_mv_add_cov(ssum[m], ri, mu[m], rp, mp, n_ret, inv);
+        for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+          if (!((alive >> s) & 1u)) continue;
+          const double* ri = dayp + (int64_t)cand_stock[tid + PFO_REC_THREADS * s] * n_ret;
+          ssum[s] = pfo_mv_add_cov(ssum[s], ri, mu[s], rp, mp, n_ret, inv);
         }
       };
       int n_hold = 0;
-      for (int p = 0; p < plen; ++p) {
-        const int s = port_idx[u * port_stride + p];
-        if ((unsigned)s >= (unsigned)n_stocks) continue;
+      for (int p = 0; p < h.plen; ++p) {
+        const int st = port_idx[u * m.port_stride + p];
+        if ((unsigned)st >= (unsigned)n_stocks) continue;
         ++n_hold;
-        hold(s);
+        hold(st);
       }
 
       int n_pick = 0;
@@ -519,23 +551,23 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
         // ---- C: y of this round (the slot of a candidate outside the pool is NaN already), ranks, blend
         double yr[PFO_RMV_PER_THREAD];
 #pragma unroll
-        for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
-          yr[m] = nan;
-          if (!((alive >> m) & 1u)) continue;
-          const int c = tid + PFO_REC_THREADS * m;
-          yr[m] = pfo_mv_finish(mu[m], gamma, var[m], ssum[m], n_hold);
-          yv[c] = yr[m];
-          su[c] = yr[m] == yr[m] ? score[m] : __builtin_nanf("");
+        for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+          yr[s] = nan;
+          if (!((alive >> s) & 1u)) continue;
+          const int c = tid + PFO_REC_THREADS * s;
+          yr[s] = pfo_mv_finish(mu[s], gamma, var[s], ssum[s], n_hold);
+          yv[c] = yr[s];
+          su[c] = yr[s] == yr[s] ? score[s] : __builtin_nanf("");
         }
         __syncthreads();
         double bf = 0.0;
         int bc = -1;                                                 // the best (fused, position) so far, -1: none
 #pragma unroll
-        for (int m = 0; m < PFO_RMV_PER_THREAD; ++m) {
-          const int c = tid + PFO_REC_THREADS * m;
-          const double yi = yr[m];
+        for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+          const int c = tid + PFO_REC_THREADS * s;
+          const double yi = yr[s];
           if (!(yi == yi)) continue;                                 // outside the pool, or a NaN y: out of this round only
-          const float si = score[m];
+          const float si = score[s];
           int ly = 0, ey = 0, ls = 0, es = 0;
           const double2* y2 = reinterpret_cast<const double2*>(yv);
           const float4* s4 = reinterpret_cast<const float4*>(su);
@@ -549,7 +581,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
             es += (sj.x == si) + (sj.y == si) + (sj.z == si) + (sj.w == si);   // (-0 == +0)
           }
           const double f = pfo_mv_blend(pfo_mv_avg_rank(ly, ey), pfo_mv_avg_rank(ls, es), lam);   // main.py:282-286
-          if (f == f && (bc < 0 || f > bf || (f == bf && c > bc))) {
+          if (f == f && rec_better(f, c, bf, bc)) {
             bf = f;
             bc = c;
           }
@@ -559,7 +591,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
         for (int off = 32; off >= 1; off >>= 1) {
           const double of = __shfl_xor(bf, off, 64);
           const int oc = __shfl_xor(bc, off, 64);
-          if (oc >= 0 && (bc < 0 || of > bf || (of == bf && oc > bc))) {
+          if (oc >= 0 && rec_better(of, oc, bf, bc)) {
             bf = of;
             bc = oc;
           }
@@ -575,7 +607,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
         for (int w = 1; w < PFO_REC_THREADS / 64; ++w) {
           const double of = wave_f[w];
           const int oc = wave_c[w];
-          if (oc >= 0 && (bc < 0 || of > bf || (of == bf && oc > bc))) {
+          if (oc >= 0 && rec_better(of, oc, bf, bc)) {
             bf = of;
             bc = oc;
           }
@@ -584,10 +616,10 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
         if (tid == (bc & (PFO_REC_THREADS - 1))) {
           alive &= ~(1u << (bc / PFO_REC_THREADS));
           yv[bc] = nan;
-          const float s = su[bc];
+          const float sv = su[bc];
           su[bc] = __builtin_nanf("");
           top_pos[u * k + rd] = bc;
-          top_score[u * k + rd] = s == 0.f ? 0.f : s;                // a zero score is handed out as +0
+          top_score[u * k + rd] = sv == 0.f ? 0.f : sv;              // a zero score is handed out as +0
           top_fused[u * k + rd] = bf;
         }
         ++n_pick;
@@ -596,50 +628,104 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
           hold(cand_stock[bc]);                                      // (in range: the pick was in the pool)
         }
       }
-      for (int t = n_pick + tid; t < k; t += PFO_REC_THREADS) {
-        top_pos[u * k + t] = -1;
-        top_score[u * k + t] = -__builtin_inff();
-        top_fused[u * k + t] = -__builtin_inf();
-      }
-      if (tid == 0 && n_valid) n_valid[u] = n_pick;
+      rec_mv_empty_slots(top_pos, top_score, top_fused, a.n_valid, u, k, n_pick);
       __syncthreads();                                               // y and the wavefront slots are free for the next user
     }
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side.  The checks speak in the name of the entry that called them (`who`), as PFO_REQUIRE does with __func__.
+#define PFO_REC_REQUIRE(cond, msg) \
+  do { if (!(cond)) { pfo_set_error("%s: %s", who, msg); return PFO_ERR_INVALID; } } while (0)
+
+// `items_msg` names the bound `max_items` on I, `stride_msg` the strides the entry has; rec_check_mv runs it first
+int rec_check_common(const char* who, const RecArgs& a, int max_items, const char* items_msg, const char* stride_msg) {
+  PFO_REC_REQUIRE(a.U >= 0 && a.U <= (int64_t)PFO_REC_TILE * 0x7fffffff, "U out of range");
+  PFO_REC_REQUIRE(a.D > 0 && a.D % 4 == 0, "D must be a positive multiple of 4");
+  PFO_REC_REQUIRE(a.D <= 256, "D must be at most 256");
+  PFO_REC_REQUIRE(a.k >= 1 && a.k <= 64, "k must be in [1, 64]");
+  PFO_REC_REQUIRE(a.I >= 1 && a.I <= max_items, items_msg);
+  PFO_REC_REQUIRE(a.n_t >= 1 && (int64_t)a.n_t * a.I <= 0x7fffffff, "n_t must be at least 1 and n_t * I fit 31 bits");
+  PFO_REC_REQUIRE(a.excl_stride >= 0, stride_msg);
+  if (a.U == 0) return PFO_OK;                                       // (nothing is read or written: no pointer is looked at)
+  PFO_REC_REQUIRE(a.user_emb && a.item_emb && a.top_pos && a.top_score, "null input or output");
+  PFO_REC_REQUIRE(!a.excl_pos || a.excl_stride == 0 || a.excl_len, "excl_pos without excl_len");
+  PFO_REC_REQUIRE((((uintptr_t)a.user_emb | (uintptr_t)a.item_emb) & 15) == 0, "user_emb and item_emb must be 16-byte aligned");
+  return PFO_OK;
+}
+
+int rec_check_mv(const char* who, const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES) {
+  const char* stride_msg = "excl_stride and port_stride must not be negative";
+  const int rc = rec_check_common(who, a, PFO_RECOMMEND_MV_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MV_MAX_ITEMS]", stride_msg);
+  if (rc != PFO_OK) return rc;
+  PFO_REC_REQUIRE(m.port_stride >= 0, stride_msg);
+  PFO_REC_REQUIRE(m.n_ret >= 2 && m.n_ret <= 128, "n_ret must be in [2, 128]");
+  PFO_REC_REQUIRE(m.n_days > 0 && m.n_stocks > 0, "n_days and n_stocks must be positive");
+  if (a.U == 0) return PFO_OK;
+  PFO_REC_REQUIRE(m.top_fused, "null input or output");
+  PFO_REC_REQUIRE(cand_stock && returns && day_idx, "null mean-variance input");
+  PFO_REC_REQUIRE(!port_idx || m.port_stride == 0 || port_len, "port_idx without port_len");
+  return PFO_OK;
+}
+#undef PFO_REC_REQUIRE
+
+constexpr size_t rec_score_bytes(int IC) { return (size_t)PFO_REC_TILE * (IC + 4) * sizeof(float); }   // sc[16][IC + 4]
+// the mean-variance kernels hold every candidate of a block at once, and y[IC] in fp64 before the scores
+inline int rec_mv_ic(int I) { return (int)pfo_align_up(I, 16); }
+constexpr size_t rec_mv_bytes(int IC) { return (size_t)IC * sizeof(double) + rec_score_bytes(IC); }
+
+// One workgroup per 16 users of a kernel template, in the instantiation that covers a row of a.D floats, with `shmem` bytes of
+// LDS.  `kernel_of` (PFO_REC_KERNEL) names the template: it maps std::integral_constant<int, NJ> to the instantiation.
+#define PFO_REC_KERNEL(name) [](auto nj) { return &name<decltype(nj)::value>; }
+template <class KernelOf, class... Args>
+int rec_launch(const char* who, KernelOf kernel_of, size_t shmem, void* stream, const RecArgs& a, const Args&... more) {
+  auto launch = [&](auto nj) -> int {
+    const auto kernel = kernel_of(nj);
+    if (shmem > 65536) {                                             // (more than 64 KB of dynamic LDS has to be asked for, per kernel)
+      const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+      if (ea != hipSuccess) {
+        pfo_set_error("%s: %zu bytes of LDS refused: %s", who, shmem, hipGetErrorString(ea));
+        return PFO_ERR_HIP;
+      }
+    }
+    const dim3 grid((unsigned)pfo_ceil_div(a.U, PFO_REC_TILE)), block(PFO_REC_THREADS);
+    PFO_KLAUNCH(kernel, grid, block, shmem, (hipStream_t)stream, a, more...);
+    const hipError_t e = hipGetLastError();                          // (PFO_LAUNCH_CHECK, in the entry's name)
+    if (e != hipSuccess) {
+      pfo_set_error("%s: launch failed: %s", who, hipGetErrorString(e));
+      return PFO_ERR_HIP;
+    }
+    return PFO_OK;
+  };
+  const int nj = (a.D + 15) / 16;
+  if (nj <= 2) return launch(std::integral_constant<int, 2>());
+  else if (nj <= 4) return launch(std::integral_constant<int, 4>());
+  else if (nj <= 8) return launch(std::integral_constant<int, 8>());
+  else if (nj <= 11) return launch(std::integral_constant<int, 11>());
+  else return launch(std::integral_constant<int, 16>());
+}
+
 }  // namespace
+
+// The argument blocks of an entry, field by name from its parameters (every entry spells them as include/pfotgn.h does).
+#define PFO_REC_ARGS(ic)                                                                                                  \
+  {.user_emb = user_emb, .item_emb = item_emb, .user_block = user_block, .excl_pos = excl_pos, .excl_len = excl_len,      \
+   .item_ok = item_ok, .U = U, .I = I, .n_t = n_t, .D = D, .excl_stride = excl_stride, .k = k, .IC = (ic), .top_pos = top_pos, \
+   .n_valid = n_valid, .top_score = top_score}
+#define PFO_REC_MV_ARGS(score, y, fused)                                                                                  \
+  {.n_days = n_days, .n_stocks = n_stocks, .n_ret = n_ret, .port_stride = port_stride, .gamma = gamma, .lam = lambda_mv,  \
+   .top_fused = top_fused, .y_out = (y), .fused_out = (fused), .score_out = (score)}
 
 extern "C" int pfo_recommend_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
                                   int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
                                   const uint8_t* item_ok, int32_t k, int32_t* top_pos, float* top_score, int32_t* n_valid,
                                   void* stream) {
-  PFO_REQUIRE(U >= 0 && U <= (int64_t)PFO_REC_TILE * 0x7fffffff, "U out of range");
-  PFO_REQUIRE(D > 0 && D % 4 == 0, "D must be a positive multiple of 4");
-  PFO_REQUIRE(D <= 256, "D must be at most 256");
-  PFO_REQUIRE(k >= 1 && k <= 64, "k must be in [1, 64]");
-  PFO_REQUIRE(I >= 1 && I <= PFO_RECOMMEND_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MAX_ITEMS]");
-  PFO_REQUIRE(n_t >= 1 && (int64_t)n_t * I <= 0x7fffffff, "n_t must be at least 1 and n_t * I fit 31 bits");
-  PFO_REQUIRE(excl_stride >= 0, "excl_stride must not be negative");
-  if (U == 0) return PFO_OK;
-  PFO_REQUIRE(user_emb && item_emb && top_pos && top_score, "null input or output");
-  PFO_REQUIRE(!excl_pos || excl_stride == 0 || excl_len, "excl_pos without excl_len");
-  PFO_REQUIRE((((uintptr_t)user_emb | (uintptr_t)item_emb) & 15) == 0, "user_emb and item_emb must be 16-byte aligned");
-  const int IC = (int)pfo_align_up(I < PFO_REC_CHUNK ? I : PFO_REC_CHUNK, 16);
-  const size_t shmem = (size_t)PFO_REC_TILE * (IC + 4) * sizeof(float) + (size_t)IC;
-  const dim3 grid((unsigned)pfo_ceil_div(U, PFO_REC_TILE)), block(PFO_REC_THREADS);
-  hipStream_t s = (hipStream_t)stream;
-#define PFO_REC_LAUNCH(NJ)                                                                                              \
-  PFO_KLAUNCH(recommend_topk_kernel<NJ>, grid, block, shmem, s, user_emb, item_emb, user_block, U, (int)I, (int)n_t, (int)D, \
-              excl_pos, excl_len, (int)excl_stride, item_ok, (int)k, top_pos, top_score, n_valid, IC)
-  const int nj = (D + 15) / 16;
-  if (nj <= 2) PFO_REC_LAUNCH(2);
-  else if (nj <= 4) PFO_REC_LAUNCH(4);
-  else if (nj <= 8) PFO_REC_LAUNCH(8);
-  else if (nj <= 11) PFO_REC_LAUNCH(11);
-  else PFO_REC_LAUNCH(16);
-#undef PFO_REC_LAUNCH
-  PFO_LAUNCH_CHECK();
-  return PFO_OK;
+  const RecArgs a = PFO_REC_ARGS((int)pfo_align_up(I < PFO_REC_CHUNK ? I : PFO_REC_CHUNK, 16));
+  const int rc = rec_check_common(__func__, a, PFO_RECOMMEND_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MAX_ITEMS]",
+                                  "excl_stride must not be negative");
+  if (rc != PFO_OK || U == 0) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL(recommend_topk_kernel), rec_score_bytes(a.IC) + (size_t)a.IC, stream, a);   // (+ ok[IC])
 }
 
 extern "C" int pfo_recommend_mv_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
@@ -649,50 +735,12 @@ extern "C" int pfo_recommend_mv_topk(const float* user_emb, const float* item_em
                                      const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
                                      int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
                                      double* y_out, double* fused_out, void* stream) {
-  PFO_REQUIRE(U >= 0 && U <= (int64_t)PFO_REC_TILE * 0x7fffffff, "U out of range");
-  PFO_REQUIRE(D > 0 && D % 4 == 0, "D must be a positive multiple of 4");
-  PFO_REQUIRE(D <= 256, "D must be at most 256");
-  PFO_REQUIRE(k >= 1 && k <= 64, "k must be in [1, 64]");
-  PFO_REQUIRE(I >= 1 && I <= PFO_RECOMMEND_MV_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MV_MAX_ITEMS]");
-  PFO_REQUIRE(n_t >= 1 && (int64_t)n_t * I <= 0x7fffffff, "n_t must be at least 1 and n_t * I fit 31 bits");
-  PFO_REQUIRE(excl_stride >= 0 && port_stride >= 0, "excl_stride and port_stride must not be negative");
-  PFO_REQUIRE(n_ret >= 2 && n_ret <= 128, "n_ret must be in [2, 128]");
-  PFO_REQUIRE(n_days > 0 && n_stocks > 0, "n_days and n_stocks must be positive");
-  if (U == 0) return PFO_OK;
-  PFO_REQUIRE(user_emb && item_emb && top_pos && top_score && top_fused, "null input or output");
-  PFO_REQUIRE(cand_stock && returns && day_idx, "null mean-variance input");
-  PFO_REQUIRE(!excl_pos || excl_stride == 0 || excl_len, "excl_pos without excl_len");
-  PFO_REQUIRE(!port_idx || port_stride == 0 || port_len, "port_idx without port_len");
-  PFO_REQUIRE((((uintptr_t)user_emb | (uintptr_t)item_emb) & 15) == 0, "user_emb and item_emb must be 16-byte aligned");
-  const int IC = (int)pfo_align_up(I, 16);
-  const size_t shmem = (size_t)IC * sizeof(double) + (size_t)PFO_REC_TILE * (IC + 4) * sizeof(float);
-  const dim3 grid((unsigned)pfo_ceil_div(U, PFO_REC_TILE)), block(PFO_REC_THREADS);
-  hipStream_t s = (hipStream_t)stream;
-  // (more than 64 KB of dynamic LDS has to be asked for, per kernel)
-#define PFO_RMV_LAUNCH(NJ)                                                                                                   \
-  do {                                                                                                                       \
-    if (shmem > 65536) {                                                                                                     \
-      const hipError_t ea__ = hipFuncSetAttribute(reinterpret_cast<const void*>(&recommend_mv_topk_kernel<NJ>),              \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                   \
-      if (ea__ != hipSuccess) {                                                                                              \
-        pfo_set_error("%s: %zu bytes of LDS refused: %s", __func__, shmem, hipGetErrorString(ea__));                         \
-        return PFO_ERR_HIP;                                                                                                  \
-      }                                                                                                                      \
-    }                                                                                                                        \
-    PFO_KLAUNCH(recommend_mv_topk_kernel<NJ>, grid, block, shmem, s, user_emb, item_emb, user_block, U, (int)I, (int)n_t,    \
-                (int)D, excl_pos, excl_len, (int)excl_stride, item_ok, cand_stock, returns, (int)n_days, (int)n_stocks,      \
-                (int)n_ret, day_idx, port_idx, port_len, (int)port_stride, gamma, lambda_mv, (int)k, top_pos, top_score,     \
-                top_fused, n_valid, score_out, y_out, fused_out, IC);                                                        \
-  } while (0)
-  const int nj = (D + 15) / 16;
-  if (nj <= 2) PFO_RMV_LAUNCH(2);
-  else if (nj <= 4) PFO_RMV_LAUNCH(4);
-  else if (nj <= 8) PFO_RMV_LAUNCH(8);
-  else if (nj <= 11) PFO_RMV_LAUNCH(11);
-  else PFO_RMV_LAUNCH(16);
-#undef PFO_RMV_LAUNCH
-  PFO_LAUNCH_CHECK();
-  return PFO_OK;
+  const RecArgs a = PFO_REC_ARGS(rec_mv_ic(I));
+  const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
+  const int rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  if (rc != PFO_OK || U == 0) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL(recommend_mv_topk_kernel), rec_mv_bytes(a.IC), stream, a, m, cand_stock, returns, day_idx, port_idx,
+                    port_len);
 }
 
 extern "C" int pfo_recommend_basket_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U,
@@ -702,48 +750,10 @@ extern "C" int pfo_recommend_basket_topk(const float* user_emb, const float* ite
                                          const int32_t* day_idx, const int32_t* port_idx, const int32_t* port_len,
                                          int32_t port_stride, double gamma, double lambda_mv, int32_t k, int32_t* top_pos,
                                          float* top_score, double* top_fused, int32_t* n_valid, void* stream) {
-  PFO_REQUIRE(U >= 0 && U <= (int64_t)PFO_REC_TILE * 0x7fffffff, "U out of range");
-  PFO_REQUIRE(D > 0 && D % 4 == 0, "D must be a positive multiple of 4");
-  PFO_REQUIRE(D <= 256, "D must be at most 256");
-  PFO_REQUIRE(k >= 1 && k <= 64, "k must be in [1, 64]");
-  PFO_REQUIRE(I >= 1 && I <= PFO_RECOMMEND_MV_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MV_MAX_ITEMS]");
-  PFO_REQUIRE(n_t >= 1 && (int64_t)n_t * I <= 0x7fffffff, "n_t must be at least 1 and n_t * I fit 31 bits");
-  PFO_REQUIRE(excl_stride >= 0 && port_stride >= 0, "excl_stride and port_stride must not be negative");
-  PFO_REQUIRE(n_ret >= 2 && n_ret <= 128, "n_ret must be in [2, 128]");
-  PFO_REQUIRE(n_days > 0 && n_stocks > 0, "n_days and n_stocks must be positive");
-  if (U == 0) return PFO_OK;
-  PFO_REQUIRE(user_emb && item_emb && top_pos && top_score && top_fused, "null input or output");
-  PFO_REQUIRE(cand_stock && returns && day_idx, "null mean-variance input");
-  PFO_REQUIRE(!excl_pos || excl_stride == 0 || excl_len, "excl_pos without excl_len");
-  PFO_REQUIRE(!port_idx || port_stride == 0 || port_len, "port_idx without port_len");
-  PFO_REQUIRE((((uintptr_t)user_emb | (uintptr_t)item_emb) & 15) == 0, "user_emb and item_emb must be 16-byte aligned");
-  const int IC = (int)pfo_align_up(I, 16);
-  const size_t shmem = (size_t)IC * sizeof(double) + (size_t)PFO_REC_TILE * (IC + 4) * sizeof(float);
-  const dim3 grid((unsigned)pfo_ceil_div(U, PFO_REC_TILE)), block(PFO_REC_THREADS);
-  hipStream_t s = (hipStream_t)stream;
-  // (more than 64 KB of dynamic LDS has to be asked for, per kernel)
-#define PFO_RBK_LAUNCH(NJ)                                                                                                   \
-  do {                                                                                                                       \
-    if (shmem > 65536) {                                                                                                     \
-      const hipError_t ea__ = hipFuncSetAttribute(reinterpret_cast<const void*>(&recommend_basket_topk_kernel<NJ>),          \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);                   \
-      if (ea__ != hipSuccess) {                                                                                              \
-        pfo_set_error("%s: %zu bytes of LDS refused: %s", __func__, shmem, hipGetErrorString(ea__));                         \
-        return PFO_ERR_HIP;                                                                                                  \
-      }                                                                                                                      \
-    }                                                                                                                        \
-    PFO_KLAUNCH(recommend_basket_topk_kernel<NJ>, grid, block, shmem, s, user_emb, item_emb, user_block, U, (int)I,          \
-                (int)n_t, (int)D, excl_pos, excl_len, (int)excl_stride, item_ok, cand_stock, returns, (int)n_days,           \
-                (int)n_stocks, (int)n_ret, day_idx, port_idx, port_len, (int)port_stride, gamma, lambda_mv, (int)k, top_pos, \
-                top_score, top_fused, n_valid, IC);                                                                          \
-  } while (0)
-  const int nj = (D + 15) / 16;
-  if (nj <= 2) PFO_RBK_LAUNCH(2);
-  else if (nj <= 4) PFO_RBK_LAUNCH(4);
-  else if (nj <= 8) PFO_RBK_LAUNCH(8);
-  else if (nj <= 11) PFO_RBK_LAUNCH(11);
-  else PFO_RBK_LAUNCH(16);
-#undef PFO_RBK_LAUNCH
-  PFO_LAUNCH_CHECK();
-  return PFO_OK;
+  const RecArgs a = PFO_REC_ARGS(rec_mv_ic(I));
+  const RecMvArgs m = PFO_REC_MV_ARGS(nullptr, nullptr, nullptr);
+  const int rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  if (rc != PFO_OK || U == 0) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL(recommend_basket_topk_kernel), rec_mv_bytes(a.IC), stream, a, m, cand_stock, returns, day_idx,
+                    port_idx, port_len);
 }

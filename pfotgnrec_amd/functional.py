@@ -231,6 +231,53 @@ def eval_metrics(emb, batch, n_neg, cand, day_idx, port_idx, port_len, ret_past,
     return tuple(o[out_row0:out_row0 + batch] for o in out)
 
 
+def _recommend_check(user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, also=()):
+    """The argument checks the three top-k forms share.  ``dims(U, rows)`` is the caller's part: it checks what only that form
+    takes and returns ``(I, n_t)``; ``also``: its tensors, for the device check.  Returns the tensors as the library takes them
+    (contiguous; the exclusion pair None without columns, its lengths defaulted; item_ok as u8) and ``U, D, k, I, n_t, W``."""
+    import operator
+    for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+            raise ValueError("%s must be a 2-D float32 tensor" % name)
+    U, D = user_emb.shape
+    if item_emb.shape[1] != D:
+        raise ValueError("user_emb has %d columns, item_emb %d" % (D, item_emb.shape[1]))
+    if D == 0 or D % 4 != 0 or D > 256:
+        raise ValueError("D must be a positive multiple of 4, at most 256 (got %d)" % D)
+    try:
+        k = operator.index(k)
+    except TypeError:
+        raise ValueError("k must be an integer") from None
+    if not 1 <= k <= 64:
+        raise ValueError("k must be in [1, 64] (got %d)" % k)
+    I, n_t = dims(U, item_emb.shape[0])
+    if user_block is not None and (user_block.dim() != 1 or user_block.shape[0] != U or user_block.dtype != torch.int32):
+        raise ValueError("user_block must be int32 [U]")
+    if item_ok is not None:
+        if item_ok.dim() != 1 or item_ok.shape[0] != I or item_ok.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("item_ok must be uint8 or bool [I]")
+    W = 0
+    if excl_pos is not None:
+        if excl_pos.dim() != 2 or excl_pos.shape[0] != U or excl_pos.dtype != torch.int32:
+            raise ValueError("excl_pos must be int32 [U, W]")
+        W = int(excl_pos.shape[1])
+        if excl_len is not None and (excl_len.dim() != 1 or excl_len.shape[0] != U or excl_len.dtype != torch.int32):
+            raise ValueError("excl_len must be int32 [U]")
+    elif excl_len is not None:
+        raise ValueError("excl_len without excl_pos")
+    dev = user_emb.device
+    _lib.require_gpu(dev)
+    for t in (item_emb, user_block, excl_pos, excl_len, item_ok) + tuple(also):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    if W and excl_len is None:
+        excl_len = torch.full((U,), W, dtype=torch.int32, device=dev)
+    if item_ok is not None:
+        item_ok = item_ok.contiguous().view(torch.uint8) if item_ok.dtype == torch.bool else item_ok.contiguous()
+    return (user_emb.contiguous(), item_emb.contiguous(), user_block.contiguous() if user_block is not None else None,
+            excl_pos.contiguous() if W else None, excl_len.contiguous() if W else None, item_ok, U, D, k, I, n_t, W)
+
+
 def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_len=None, item_ok=None, n_blocks=None):
     """The k best candidates per user in one launch (``pfo_recommend_topk``); nothing but its outputs is written.
 
@@ -243,66 +290,30 @@ def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_l
 
     Returns (top_pos i32[U,k], top_score f32[U,k], n_valid i32[U]): score descending, the larger position first among equal
     scores (the order of ``eval_metrics``); slots beyond the admissible candidates hold -1 / -inf."""
-    import operator
-    for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
-            raise ValueError("%s must be a 2-D float32 tensor" % name)
-    U, D = user_emb.shape
-    if item_emb.shape[1] != D:
-        raise ValueError("user_emb has %d columns, item_emb %d" % (D, item_emb.shape[1]))
-    if D == 0 or D % 4 != 0 or D > 256:
-        raise ValueError("D must be a positive multiple of 4, at most 256 (got %d)" % D)
-    try:
-        k = operator.index(k)
-    except TypeError:
-        raise ValueError("k must be an integer") from None
-    if not 1 <= k <= 64:
-        raise ValueError("k must be in [1, 64] (got %d)" % k)
-    rows = item_emb.shape[0]
-    if n_blocks is None:
-        if item_ok is not None and item_ok.dim() == 1 and item_ok.shape[0] > 0 and rows % item_ok.shape[0] == 0:
-            n_blocks = rows // item_ok.shape[0]
-        elif user_block is None:
-            n_blocks = 1
-        else:
-            raise ValueError("user_block without item_ok needs n_blocks")
-    n_t = int(n_blocks)
-    if n_t < 1 or rows % n_t != 0 or rows == 0:
-        raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of at least one candidate" % (rows, n_t))
-    I = rows // n_t
-    if I > _lib.RECOMMEND_MAX_ITEMS:
-        raise ValueError("%d candidates, at most %d" % (I, _lib.RECOMMEND_MAX_ITEMS))
-    if user_block is not None and (user_block.dim() != 1 or user_block.shape[0] != U or user_block.dtype != torch.int32):
-        raise ValueError("user_block must be int32 [U]")
-    if item_ok is not None:
-        if item_ok.dim() != 1 or item_ok.shape[0] != I or item_ok.dtype not in (torch.uint8, torch.bool):
-            raise ValueError("item_ok must be uint8 or bool [I]")
-    W = 0
-    if excl_pos is not None:
-        if excl_pos.dim() != 2 or excl_pos.shape[0] != U or excl_pos.dtype != torch.int32:
-            raise ValueError("excl_pos must be int32 [U, W]")
-        W = int(excl_pos.shape[1])
-        if excl_len is not None and (excl_len.dim() != 1 or excl_len.shape[0] != U or excl_len.dtype != torch.int32):
-            raise ValueError("excl_len must be int32 [U]")
-    elif excl_len is not None:
-        raise ValueError("excl_len without excl_pos")
+    def dims(U, rows):
+        n_t = n_blocks
+        if n_t is None:
+            if item_ok is not None and item_ok.dim() == 1 and item_ok.shape[0] > 0 and rows % item_ok.shape[0] == 0:
+                n_t = rows // item_ok.shape[0]
+            elif user_block is None:
+                n_t = 1
+            else:
+                raise ValueError("user_block without item_ok needs n_blocks")
+        n_t = int(n_t)
+        if n_t < 1 or rows % n_t != 0 or rows == 0:
+            raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of at least one candidate" % (rows, n_t))
+        if rows // n_t > _lib.RECOMMEND_MAX_ITEMS:
+            raise ValueError("%d candidates, at most %d" % (rows // n_t, _lib.RECOMMEND_MAX_ITEMS))
+        return rows // n_t, n_t
+
+    user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
+        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims)
     dev = user_emb.device
-    _lib.require_gpu(dev)
-    for t in (item_emb, user_block, excl_pos, excl_len, item_ok):
-        if t is not None and t.device != dev:
-            raise ValueError("all tensors must live on %s" % dev)
-    user_emb, item_emb = user_emb.contiguous(), item_emb.contiguous()
-    if W and excl_len is None:
-        excl_len = torch.full((U,), W, dtype=torch.int32, device=dev)
-    if item_ok is not None:
-        item_ok = item_ok.contiguous().view(torch.uint8) if item_ok.dtype == torch.bool else item_ok.contiguous()
     top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
     top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
     n_valid = torch.empty(U, dtype=torch.int32, device=dev)
-    _lib.call("pfo_recommend_topk", user_emb.data_ptr(), item_emb.data_ptr(),
-              _lib.ptr(user_block.contiguous() if user_block is not None else None), U, I, n_t, D,
-              _lib.ptr(excl_pos.contiguous() if W else None), _lib.ptr(excl_len.contiguous() if W else None), W, _lib.ptr(item_ok), k,
-              top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
+    _lib.call("pfo_recommend_topk", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos),
+              _lib.ptr(excl_len), W, _lib.ptr(item_ok), k, top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
     return top_pos, top_score, n_valid
 
 
@@ -311,71 +322,37 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
     """The argument checks, output rows and launch that ``recommend_mv_topk`` and ``recommend_basket_topk`` share: ``symbol``
     takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays (``diagnostics``: allocate them or pass NULL)
     or without them (None)."""
-    import operator
-    for name, t in (("user_emb", user_emb), ("item_emb", item_emb)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
-            raise ValueError("%s must be a 2-D float32 tensor" % name)
-    U, D = user_emb.shape
-    if item_emb.shape[1] != D:
-        raise ValueError("user_emb has %d columns, item_emb %d" % (D, item_emb.shape[1]))
-    if D == 0 or D % 4 != 0 or D > 256:
-        raise ValueError("D must be a positive multiple of 4, at most 256 (got %d)" % D)
-    try:
-        k = operator.index(k)
-    except TypeError:
-        raise ValueError("k must be an integer") from None
-    if not 1 <= k <= 64:
-        raise ValueError("k must be in [1, 64] (got %d)" % k)
-    if not isinstance(cand_stock, torch.Tensor) or cand_stock.dim() != 1 or cand_stock.dtype != torch.int32 or cand_stock.shape[0] < 1:
-        raise ValueError("cand_stock must be int32 [I]")
-    I = int(cand_stock.shape[0])
-    if I > _lib.RECOMMEND_MV_MAX_ITEMS:
-        raise ValueError("%d candidates, at most %d with the mean-variance rank" % (I, _lib.RECOMMEND_MV_MAX_ITEMS))
-    n_t = 1 if n_blocks is None else int(n_blocks)
-    if n_t < 1 or item_emb.shape[0] != n_t * I:
-        raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of %d candidates" % (item_emb.shape[0], n_t, I))
-    if user_block is not None and (user_block.dim() != 1 or user_block.shape[0] != U or user_block.dtype != torch.int32):
-        raise ValueError("user_block must be int32 [U]")
-    if not isinstance(returns, torch.Tensor) or returns.dim() != 3 or returns.dtype != torch.float64 or 0 in returns.shape:
-        raise ValueError("returns must be a float64 tensor [n_days, n_stocks, n_ret]")
-    n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
-    if not 2 <= n_ret <= 128:
-        raise ValueError("n_ret must be in [2, 128] (got %d)" % n_ret)
-    if not isinstance(day_idx, torch.Tensor) or tuple(day_idx.shape) != (U,) or day_idx.dtype != torch.int32:
-        raise ValueError("day_idx must be int32 [U]")
-    Wp = 0
-    if port_idx is not None:
-        if port_idx.dim() != 2 or port_idx.shape[0] != U or port_idx.dtype != torch.int32:
-            raise ValueError("port_idx must be int32 [U, W]")
-        Wp = int(port_idx.shape[1])
-        if port_len is not None and (tuple(port_len.shape) != (U,) or port_len.dtype != torch.int32):
-            raise ValueError("port_len must be int32 [U]")
-    elif port_len is not None:
-        raise ValueError("port_len without port_idx")
-    if item_ok is not None:
-        if item_ok.dim() != 1 or item_ok.shape[0] != I or item_ok.dtype not in (torch.uint8, torch.bool):
-            raise ValueError("item_ok must be uint8 or bool [I]")
-    W = 0
-    if excl_pos is not None:
-        if excl_pos.dim() != 2 or excl_pos.shape[0] != U or excl_pos.dtype != torch.int32:
-            raise ValueError("excl_pos must be int32 [U, W]")
-        W = int(excl_pos.shape[1])
-        if excl_len is not None and (excl_len.dim() != 1 or excl_len.shape[0] != U or excl_len.dtype != torch.int32):
-            raise ValueError("excl_len must be int32 [U]")
-    elif excl_len is not None:
-        raise ValueError("excl_len without excl_pos")
+    def dims(U, rows):
+        if not isinstance(cand_stock, torch.Tensor) or cand_stock.dim() != 1 or cand_stock.dtype != torch.int32 or cand_stock.shape[0] < 1:
+            raise ValueError("cand_stock must be int32 [I]")
+        I = int(cand_stock.shape[0])
+        if I > _lib.RECOMMEND_MV_MAX_ITEMS:
+            raise ValueError("%d candidates, at most %d with the mean-variance rank" % (I, _lib.RECOMMEND_MV_MAX_ITEMS))
+        n_t = 1 if n_blocks is None else int(n_blocks)
+        if n_t < 1 or rows != n_t * I:
+            raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of %d candidates" % (rows, n_t, I))
+        if not isinstance(returns, torch.Tensor) or returns.dim() != 3 or returns.dtype != torch.float64 or 0 in returns.shape:
+            raise ValueError("returns must be a float64 tensor [n_days, n_stocks, n_ret]")
+        if not 2 <= returns.shape[2] <= 128:
+            raise ValueError("n_ret must be in [2, 128] (got %d)" % returns.shape[2])
+        if not isinstance(day_idx, torch.Tensor) or tuple(day_idx.shape) != (U,) or day_idx.dtype != torch.int32:
+            raise ValueError("day_idx must be int32 [U]")
+        if port_idx is not None:
+            if port_idx.dim() != 2 or port_idx.shape[0] != U or port_idx.dtype != torch.int32:
+                raise ValueError("port_idx must be int32 [U, W]")
+            if port_len is not None and (tuple(port_len.shape) != (U,) or port_len.dtype != torch.int32):
+                raise ValueError("port_len must be int32 [U]")
+        elif port_len is not None:
+            raise ValueError("port_len without port_idx")
+        return I, n_t
+
+    user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
+        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, (cand_stock, returns, day_idx, port_idx, port_len))
     dev = user_emb.device
-    _lib.require_gpu(dev)
-    for t in (item_emb, user_block, excl_pos, excl_len, item_ok, cand_stock, returns, day_idx, port_idx, port_len):
-        if t is not None and t.device != dev:
-            raise ValueError("all tensors must live on %s" % dev)
-    user_emb, item_emb, returns = user_emb.contiguous(), item_emb.contiguous(), returns.contiguous()
-    if W and excl_len is None:
-        excl_len = torch.full((U,), W, dtype=torch.int32, device=dev)
+    n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
+    Wp = int(port_idx.shape[1]) if port_idx is not None else 0
     if Wp and port_len is None:
         port_len = torch.full((U,), Wp, dtype=torch.int32, device=dev)
-    if item_ok is not None:
-        item_ok = item_ok.contiguous().view(torch.uint8) if item_ok.dtype == torch.bool else item_ok.contiguous()
     top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
     top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
     top_fused = torch.empty((U, k), dtype=torch.float64, device=dev)
@@ -385,12 +362,10 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
     if diagnostics is not None:
         extra = tuple(torch.empty((U, I), dtype=dt, device=dev) if diagnostics else None
                       for dt in (torch.float32, torch.float64, torch.float64))
-    _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(),
-              _lib.ptr(user_block.contiguous() if user_block is not None else None), U, I, n_t, D,
-              _lib.ptr(excl_pos.contiguous() if W else None), _lib.ptr(excl_len.contiguous() if W else None), W, _lib.ptr(item_ok),
-              _lib.ptr(cand_stock.contiguous()), returns.data_ptr(), n_days, n_stocks, n_ret, _lib.ptr(day_idx.contiguous()),
-              _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None), Wp,
-              float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), _lib.stream_ptr())
+    _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos), _lib.ptr(excl_len),
+              W, _lib.ptr(item_ok), _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks, n_ret,
+              _lib.ptr(day_idx.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None),
+              Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), _lib.stream_ptr())
     return out + extra if diagnostics else out
 
 

@@ -42,6 +42,39 @@ def _is_int_array(t):
     return (t.dtype.kind in "iu") if isinstance(t, np.ndarray) else not (t.dtype.is_floating_point or t.dtype == torch.bool)
 
 
+def _pack_rows(arg, U, strict, pair_msg, int_msg, names, rows_msg, count_msg, bits_msg):
+    """``exclude`` / ``portfolios`` -> (rows i32[U, W] padded with -1, lengths [U]): a packed pair goes through checked (host or
+    device), one list per user is packed on the host.  ``strict``: a row of anything but integers is refused, not converted.
+    The messages are the caller's (``int_msg`` takes one of ``names``, ``count_msg`` the two user counts)."""
+    if (isinstance(arg, (tuple, list)) and len(arg) == 2 and isinstance(arg[0], (torch.Tensor, np.ndarray)) and arg[0].ndim == 2):
+        rows, lens = arg
+        if not isinstance(lens, (torch.Tensor, np.ndarray)):
+            lens = np.asarray(lens)
+        if rows.shape[0] != U or tuple(lens.shape) != (U,):
+            raise ValueError(pair_msg % U)
+        for t, what in zip((rows, lens), names):
+            if not _is_int_array(t):
+                raise ValueError(int_msg % what)
+        return rows, lens
+    try:
+        lists = [np.asarray(list(r)).reshape(-1) for r in arg]
+        if strict and any(r.size and r.dtype.kind not in "iu" for r in lists):
+            raise TypeError
+        lists = [r.astype(np.int64) for r in lists]
+    except (TypeError, ValueError):
+        raise ValueError(rows_msg) from None
+    if len(lists) != U:
+        raise ValueError(count_msg % (len(lists), U))
+    rows = np.full((U, max([len(r) for r in lists], default=0)), -1, np.int32)
+    lens = np.zeros(U, np.int32)
+    for i, r in enumerate(lists):
+        if r.size and (int(r.min()) < -(1 << 31) or int(r.max()) >= (1 << 31)):
+            raise ValueError(bits_msg)
+        rows[i, :len(r)] = r
+        lens[i] = len(r)
+    return rows, lens
+
+
 def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
     """The mean-variance keywords of ``TGN.recommend`` checked on the host (ValueError) -> ``MVQuery``, or None without any."""
     if _is_held(portfolios) and holdings is None:
@@ -63,37 +96,14 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
         raise ValueError("with mv, items may hold at most %d candidates (got %d)" % (_lib.RECOMMEND_MV_MAX_ITEMS, I))
     ledger = isinstance(mv, PriceLedger)
     n_days = mv.n_days if ledger else int(mv.returns.shape[0])   # (a ledger's day_idx counts its LIVE days, 0 = oldest)
-    packed = (isinstance(portfolios, (tuple, list)) and len(portfolios) == 2
-              and isinstance(portfolios[0], (torch.Tensor, np.ndarray)) and portfolios[0].ndim == 2)
     if _is_held(portfolios):
         port_idx = port_len = None
-    elif packed:
-        port_idx, port_len = portfolios
-        if not isinstance(port_len, (torch.Tensor, np.ndarray)):
-            port_len = np.asarray(port_len)
-        if port_idx.shape[0] != U or tuple(port_len.shape) != (U,):
-            raise ValueError("packed portfolios must be (port_idx [U,W], port_len [U]) with U = %d" % U)
-        for t, what in ((port_idx, "port_idx"), (port_len, "port_len")):
-            if not _is_int_array(t):
-                raise ValueError("packed portfolios: %s must be integers" % what)
     else:
-        try:
-            rows = [np.asarray(list(r)).reshape(-1) for r in portfolios]
-            if any(r.size and r.dtype.kind not in "iu" for r in rows):
-                raise TypeError
-            rows = [r.astype(np.int64) for r in rows]
-        except (TypeError, ValueError):
-            raise ValueError("portfolios must be a packed (port_idx, port_len) pair or one list of integer stock indices per user") from None
-        if len(rows) != U:
-            raise ValueError("portfolios lists %d users, users holds %d" % (len(rows), U))
-        W = max([len(r) for r in rows], default=0)
-        port_idx = np.full((U, W), -1, np.int32)
-        port_len = np.zeros(U, np.int32)
-        for i, r in enumerate(rows):
-            if r.size and (int(r.min()) < -(1 << 31) or int(r.max()) >= (1 << 31)):
-                raise ValueError("portfolios holds indices that do not fit 32 bits")
-            port_idx[i, :len(r)] = r
-            port_len[i] = len(r)
+        port_idx, port_len = _pack_rows(
+            portfolios, U, True, "packed portfolios must be (port_idx [U,W], port_len [U]) with U = %d",
+            "packed portfolios: %s must be integers", ("port_idx", "port_len"),
+            "portfolios must be a packed (port_idx, port_len) pair or one list of integer stock indices per user",
+            "portfolios lists %d users, users holds %d", "portfolios holds indices that do not fit 32 bits")
     if day_idx is None:
         if ts_h is None:
             if not ledger:
@@ -158,33 +168,10 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
         if holdings is None:
             raise ValueError('exclude="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
     elif exclude is not None:
-        packed = (isinstance(exclude, (tuple, list)) and len(exclude) == 2
-                  and isinstance(exclude[0], (torch.Tensor, np.ndarray)) and exclude[0].ndim == 2)
-        if packed:
-            ex_ids, ex_len = exclude
-            if not isinstance(ex_len, (torch.Tensor, np.ndarray)):
-                ex_len = np.asarray(ex_len)
-            if ex_ids.shape[0] != U or tuple(ex_len.shape) != (U,):
-                raise ValueError("packed exclude must be (ids [U,W], lens [U]) with U = %d" % U)
-            for t, what in ((ex_ids, "ids"), (ex_len, "lens")):
-                kind_ok = (t.dtype.kind in "iu") if isinstance(t, np.ndarray) else not (t.dtype.is_floating_point or t.dtype == torch.bool)
-                if not kind_ok:
-                    raise ValueError("packed exclude %s must be integers" % what)
-        else:
-            try:
-                rows = [np.asarray(list(r), np.int64).reshape(-1) for r in exclude]
-            except (TypeError, ValueError):
-                raise ValueError("exclude must be None, a list of per-user lists of item ids or a packed (ids, lens) pair") from None
-            if len(rows) != U:
-                raise ValueError("exclude lists %d users, users holds %d" % (len(rows), U))
-            W = max([len(r) for r in rows], default=0)
-            ex_ids = np.full((U, W), -1, np.int32)
-            ex_len = np.zeros(U, np.int32)
-            for i, r in enumerate(rows):
-                if r.size and (int(r.min()) < -(1 << 31) or int(r.max()) >= (1 << 31)):
-                    raise ValueError("exclude holds ids that do not fit 32 bits")
-                ex_ids[i, :len(r)] = r
-                ex_len[i] = len(r)
+        ex_ids, ex_len = _pack_rows(
+            exclude, U, False, "packed exclude must be (ids [U,W], lens [U]) with U = %d", "packed exclude %s must be integers",
+            ("ids", "lens"), "exclude must be None, a list of per-user lists of item ids or a packed (ids, lens) pair",
+            "exclude lists %d users, users holds %d", "exclude holds ids that do not fit 32 bits")
     if n_neighbors is None:
         n_neighbors = 20 if default_neighbors is None else default_neighbors
     mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings)
@@ -257,22 +244,29 @@ def assemble(tgn, q, return_embeddings=False):
         if q.mv is not None:
             return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
                                 held_ports, user_ts)
-        if user_block is not None and n_t > 1:
-            # users of one block side by side: the kernel serves a tile of 16 users in one pass per distinct block
-            order = torch.argsort(user_block, stable=True)
-            sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
-            res = recommend_topk(sel(user_emb), item_emb, k, sel(user_block), sel(excl_pos), sel(excl_len), ok_d, n_blocks=n_t)
-            res = tuple(torch.empty_like(t).index_copy_(0, order, t) for t in res)
-        else:
-            res = recommend_topk(user_emb, item_emb, k, user_block if n_t > 1 else None, excl_pos, excl_len, ok_d, n_blocks=n_t)
-        top_pos, top_score, n_valid = res
-        item_ids = torch.where(top_pos >= 0, items_d[top_pos.clamp(min=0).long()], torch.full_like(top_pos, -1))
-        out = (item_ids, top_score, n_valid)
-        if return_embeddings:
-            if user_block is None:
-                user_block = torch.zeros(U, dtype=torch.int32, device=dev)
-            out += (user_emb, item_emb, user_block)
-        return out
+        launch = lambda ub, ue, pos, ln: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t)
+        return _select(launch, (user_emb, excl_pos, excl_len), user_block, n_t, items_d, item_emb, return_embeddings)
+
+
+def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddings):
+    """The tail of ``assemble``: ``launch(user_block, *per_user)`` -> (top_pos, ...) with the users of one block side by side
+    (the kernels serve a tile of 16 users in one pass per distinct block), so ``per_user`` - the user embeddings first - follows
+    the stable sort by block and the results are put back; positions become item ids."""
+    if user_block is not None and n_t > 1:
+        order = torch.argsort(user_block, stable=True)
+        sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
+        res = launch(sel(user_block), *(sel(t) for t in per_user))
+        res = tuple(torch.empty_like(t).index_copy_(0, order, t) for t in res)
+    else:
+        res = launch(None, *per_user)
+    top_pos = res[0]
+    out = (torch.where(top_pos >= 0, items_d[top_pos.clamp(min=0).long()], torch.full_like(top_pos, -1)),) + res[1:]
+    if return_embeddings:
+        user_emb = per_user[0]
+        if user_block is None:
+            user_block = torch.zeros(user_emb.shape[0], dtype=torch.int32, device=user_emb.device)
+        out += (user_emb, item_emb, user_block)
+    return out
 
 
 def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
@@ -283,7 +277,7 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
     day ordinals become slots, no day index at all is ``pfo_day_lookup`` over ``user_ts`` f64[U] on the device."""
     from .functional import recommend_basket_topk, recommend_mv_topk
     topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
-    dev, k, U, mv = tgn.device, q.k, q.U, q.mv.src
+    dev, mv = tgn.device, q.mv.src
     returns = mv.returns
     if not isinstance(returns, torch.Tensor):
         returns = torch.from_numpy(np.ascontiguousarray(returns, dtype=np.float64))
@@ -298,21 +292,9 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
     else:
         port_idx = to_dev(q.mv.port_idx, torch.int32) if q.mv.port_idx.shape[1] > 0 else None
         port_len = to_dev(q.mv.port_len, torch.int32) if port_idx is not None else None
-    args = (float(mv.gamma), float(mv.lambda_mv))
-    if user_block is not None and n_t > 1:
-        order = torch.argsort(user_block, stable=True)
-        sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
-        res = topk(sel(user_emb), item_emb, k, cand_stock, returns, sel(day), sel(port_idx), sel(port_len), *args,
-                   sel(user_block), sel(excl_pos), sel(excl_len), ok_d, n_blocks=n_t)
-        res = tuple(torch.empty_like(t).index_copy_(0, order, t) for t in res)
-    else:
-        res = topk(user_emb, item_emb, k, cand_stock, returns, day, port_idx, port_len, *args,
-                   user_block if n_t > 1 else None, excl_pos, excl_len, ok_d, n_blocks=n_t)
-    top_pos, top_score, top_fused, n_valid = res
-    item_ids = torch.where(top_pos >= 0, items_d[top_pos.clamp(min=0).long()], torch.full_like(top_pos, -1))
-    out = (item_ids, top_score, n_valid, top_fused)
-    if return_embeddings:
-        if user_block is None:
-            user_block = torch.zeros(U, dtype=torch.int32, device=dev)
-        out += (user_emb, item_emb, user_block)
-    return out
+
+    def launch(ub, ue, pos, ln, day, port_idx, port_len):
+        top_pos, top_score, top_fused, n_valid = topk(ue, item_emb, q.k, cand_stock, returns, day, port_idx, port_len, float(mv.gamma),
+                                                      float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t)
+        return top_pos, top_score, n_valid, top_fused
+    return _select(launch, (user_emb, excl_pos, excl_len, day, port_idx, port_len), user_block, n_t, items_d, item_emb, return_embeddings)

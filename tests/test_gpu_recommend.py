@@ -59,6 +59,22 @@ def test_exact_arithmetic_bit_exact_order(D):
     assert full > 500, "full rows must be the rule"
 
 
+@pytest.mark.parametrize("D", [48, 64, 112, 128])
+def test_exact_arithmetic_at_the_middle_row_widths(D):
+    """The kernel is built for rows of up to 32, 64, 128, 176 and 256 floats; the D of the test above reach the first and the
+    last two.  These reach the other two, at both ends of each: 17 users (two tiles), 65 candidates, three blocks in shuffled
+    order, exact arithmetic, everything equal to the reference to the bit."""
+    U, I, k, n_t = 17, 65, 5, 3
+    c = R.exact_case(9000 + D, U, I, D, k, n_t)
+    s = R.scores64(c["user_emb"], c["item_emb"], c["user_block"], I)
+    want_pos, want_score, want_n = R.topk(s, R.admissible(U, I, c["excl_pos"], c["excl_len"], c["item_ok"]), k)
+    assert (want_n < k).any() and (want_n == k).any()
+    pos, score, n = _kernel(c, k, n_t)
+    assert np.array_equal(n, want_n), D
+    assert np.array_equal(pos, want_pos), D
+    assert np.array_equal(score.view(np.int32), want_score.view(np.int32)), D
+
+
 def test_exact_arithmetic_across_the_chunk_walk():
     """More candidates than one pass of the kernel's LDS walk holds (512), not a multiple of it, with ties across the chunk
     boundary (duplicated rows) and k = 64: the list carried from chunk to chunk must come out in the canonical order."""

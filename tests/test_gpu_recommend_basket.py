@@ -64,6 +64,16 @@ def test_kernel_equals_the_reference(spec):
         assert (got["n_valid"] < k).all()
 
 
+@pytest.mark.parametrize("D", [48, 64, 112, 128])
+def test_kernel_equals_the_reference_at_the_middle_row_widths(D):
+    """``B.CASES`` reach the instantiations for rows of up to 32, 176 and 256 floats; these reach the ones for 64 and 128, at
+    both ends of each, on the exact case of the mean-variance kernel's test of the same name."""
+    c = M.exact_case(9000 + D, 17, 65, D, 5, 2, 29)
+    ref = B.reference(c, 0.5, 5)
+    assert (ref["n_valid"] == 0).any() and (ref["n_valid"] == 5).any()
+    assert B.same(_basket(c, 0.5, 5, 2), ref), D
+
+
 @pytest.mark.parametrize("I", [1, 2, 15, 16, 17, 255, 256, 257, 2048])
 def test_one_pick_is_the_mean_variance_kernel(I):
     """k = 1 against ``pfo_recommend_mv_topk``: all four outputs equal, at the edges of the 16-wide score tile, of the 256

@@ -83,6 +83,19 @@ def test_exact_arithmetic_bit_exact_everything(I):
     assert I < 63 or full > 100, "full rows must be the rule"
 
 
+@pytest.mark.parametrize("D", [48, 64, 112, 128])
+def test_exact_arithmetic_at_the_middle_row_widths(D):
+    """The row widths the test above does not reach (the kernel is built for rows of up to 32, 64, 128, 176 and 256 floats): the
+    instantiations for 64 and 128, at both ends of each.  Exact arithmetic, everything equal to the reference to the bit."""
+    U, I, k, n_t, lam = 17, 65, 5, 2, 0.5
+    c = M.exact_case(9000 + D, U, I, D, k, n_t, 29)
+    s64 = R.scores64(c["user_emb"], c["item_emb"], c["user_block"], I)
+    ref, got = M.reference(c, lam, k), _kernel(c, lam, k, n_t)
+    assert (ref["n_valid"] == 0).any() and (ref["n_valid"] == k).any()
+    assert np.array_equal(got["score"].astype(np.float64), s64), D
+    _assert_equals_reference(got, ref, D)
+
+
 @pytest.mark.parametrize("seed,U,I,D,k,n_t", [(11, 37, 500, 172, 10, 1), (12, 5, 130, 32, 5, 1), (13, 21, 70, 32, 5, 3)])
 def test_lambda_zero_is_the_plain_kernel(seed, U, I, D, k, n_t):
     """With lambda = 0 fused is the average-tie rank of the score, whose canonical order is the canonical order of the score:
