@@ -726,6 +726,49 @@ int pfo_debug_gru_fused(const pfo_gru_desc* f, void* stream);
 int pfo_debug_rank1_multi(const pfo_rank1_desc* list, int32_t n, void* stream);
 int pfo_debug_sum_slabs(const pfo_sum_slabs_desc* list, int32_t n, void* stream);
 
+/* debug / test probes of the internal attention interface (csrc/attn.hpp) and of the grouping its run-merged backward
+ * consumes (csrc/memory.hpp pfo_seg_build_launch).  As above: the struct mirrors PfoAttn field for field, every call forwards
+ * to the internal launcher unchanged, the comments of attn.hpp are the contract, and none of it is part of the drop-in
+ * surface (additive: the abi version stays).
+ *   pfo_debug_attn_form: the kernel the launcher would take for `desc` - pure host code, the launchers dispatch on the same
+ *     function; -1 (with a message) when the descriptor does not pass the launchers' common checks.
+ *   pfo_debug_attn_det_parts: slab rows a deterministic backward over N instances writes.
+ *   pfo_debug_seg_build: seg_ptr i32[cap_rows + 1], members i32[N], seg_of i32[pfo_debug_seg_of_ints(N)] (optional), scratch
+ *     of pfo_debug_seg_scratch_ints(cap_rows) + 2 (cap_rows + 1) + N int32 (the launcher's scan scratch, cursor and unsorted
+ *     member list, in this order). */
+#define PFO_ATTN_FORM_FWD_RING 0
+#define PFO_ATTN_FORM_FWD_REG 1
+#define PFO_ATTN_FORM_BWD_RUNS 2
+#define PFO_ATTN_FORM_BWD_RING_NONE 3
+#define PFO_ATTN_FORM_BWD_RING_DIRECT 4
+#define PFO_ATTN_FORM_BWD_NONE 5
+#define PFO_ATTN_FORM_BWD_ATOMIC 6
+#define PFO_ATTN_FORM_BWD_DET 7
+#define PFO_ATTN_FORM_BWD_DIRECT 8
+typedef struct pfo_attn_desc {     /* PfoAttn */
+  int32_t N, K, D, Ef, H, Cp;
+  const float* QK; const int32_t* qk_row; int64_t qk_ld;
+  const float* nbr_tab; int64_t nbr_ld; const int32_t* nbr_row; int64_t nbr_row_base;
+  int64_t nbr_rows, edge_rows;
+  int32_t nbr_relu;
+  const int32_t* nbr_ids; const float* edge_feat; const int32_t* eidx; const float* dt; const float* tw; const float* tb;
+  float scale, dropout_p;
+  uint64_t seed, offset; const uint64_t* offset_dev; const uint8_t* keep_inject;
+  float* ctx; float* attw; uint8_t* inv;
+  const float* dctx; float* dQK; float* d_nbr; int64_t d_nbr_ld, d_nbr_rep; int32_t d_nbr_nrep;
+  double* dtime_part;
+  int32_t det; double* dtime_slab; uint8_t* dqk_live;
+  const int32_t* members; const int32_t* seg_ptr; const int32_t* n_rows; const int32_t* run_cnt;
+} pfo_attn_desc;
+int pfo_debug_attn_fwd(const pfo_attn_desc* desc, void* stream);
+int pfo_debug_attn_bwd(const pfo_attn_desc* desc, int32_t* n_parts /* HOST, may be NULL */, void* stream);
+int64_t pfo_debug_attn_det_parts(int64_t N);
+int32_t pfo_debug_attn_form(const pfo_attn_desc* desc, int32_t backward);
+int64_t pfo_debug_seg_scratch_ints(int32_t cap_rows);
+int64_t pfo_debug_seg_of_ints(int64_t n_members);
+int pfo_debug_seg_build(const int32_t* idx, const int32_t* nodes, int32_t N, int32_t cap_rows, const int32_t* key_src,
+                        int32_t* seg_ptr, int32_t* members, int32_t* seg_of, int32_t* scratch, int64_t scratch_ints, void* stream);
+
 /* Parameter cache (pfo_tgn_state.pcache): its size, and the call that (re)builds it from state->params on the library's
  * side stream, forked from `stream` and NOT joined back - the next pfo_tgn_forward with pcache_valid = 1 queues its own
  * side-stream work behind it, so the caller's stream never waits for the build itself.  Meant to be called right behind the

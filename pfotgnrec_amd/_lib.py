@@ -92,6 +92,23 @@ class SumSlabsDesc(C.Structure):
                 ("accumulate", C.c_int32)]
 
 
+# ... and of the internal attention interface (csrc/attn.hpp)
+class AttnDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("K", C.c_int32), ("D", C.c_int32), ("Ef", C.c_int32), ("H", C.c_int32), ("Cp", C.c_int32),
+                ("QK", _FP), ("qk_row", _FP), ("qk_ld", C.c_int64),
+                ("nbr_tab", _FP), ("nbr_ld", C.c_int64), ("nbr_row", _FP), ("nbr_row_base", C.c_int64),
+                ("nbr_rows", C.c_int64), ("edge_rows", C.c_int64), ("nbr_relu", C.c_int32),
+                ("nbr_ids", _FP), ("edge_feat", _FP), ("eidx", _FP), ("dt", _FP), ("tw", _FP), ("tb", _FP),
+                ("scale", C.c_float), ("dropout_p", C.c_float), ("seed", C.c_uint64), ("offset", C.c_uint64), ("offset_dev", _FP),
+                ("keep_inject", _FP), ("ctx", _FP), ("attw", _FP), ("inv", _FP),
+                ("dctx", _FP), ("dQK", _FP), ("d_nbr", _FP), ("d_nbr_ld", C.c_int64), ("d_nbr_rep", C.c_int64),
+                ("d_nbr_nrep", C.c_int32), ("dtime_part", _FP), ("det", C.c_int32), ("dtime_slab", _FP), ("dqk_live", _FP),
+                ("members", _FP), ("seg_ptr", _FP), ("n_rows", _FP), ("run_cnt", _FP)]
+
+
+ATTN_FORMS = ["fwd_ring", "fwd_reg", "bwd_runs", "bwd_ring_none", "bwd_ring_direct", "bwd_none", "bwd_atomic", "bwd_det", "bwd_direct"]
+
+
 # name -> (restype, argtypes); every symbol of include/pfotgn.h
 PROTOTYPES = {
     "pfo_abi_version": (C.c_int, []),
@@ -192,6 +209,13 @@ PROTOTYPES = {
     "pfo_debug_gru_fused": (C.c_int, [C.POINTER(GruDesc), _VP]),
     "pfo_debug_rank1_multi": (C.c_int, [C.POINTER(Rank1Desc), C.c_int32, _VP]),
     "pfo_debug_sum_slabs": (C.c_int, [C.POINTER(SumSlabsDesc), C.c_int32, _VP]),
+    "pfo_debug_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), _VP]),
+    "pfo_debug_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), C.POINTER(C.c_int32), _VP]),
+    "pfo_debug_attn_det_parts": (C.c_int64, [C.c_int64]),
+    "pfo_debug_attn_form": (C.c_int32, [C.POINTER(AttnDesc), C.c_int32]),
+    "pfo_debug_seg_scratch_ints": (C.c_int64, [C.c_int32]),
+    "pfo_debug_seg_of_ints": (C.c_int64, [C.c_int64]),
+    "pfo_debug_seg_build": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "pfo_prof_enable": (C.c_int, [C.c_int32]),
     "pfo_marks_enable": (C.c_int, [C.c_int32]),
     "pfo_mark": (C.c_int, [C.c_char_p, _VP]),

@@ -1571,6 +1571,7 @@ template <int NR, int H> __global__ __launch_bounds__(256, BWD_WAVES(NR, H, 0)) 
 template <int NR, int H> __global__ __launch_bounds__(256, BWD_WAVES(NR, H, 1)) void attn_bwd_kernel(const AttnDev a) { attn_bwd_body<NR, H, 1>(a); }
 template <int NR, int H> __global__ __launch_bounds__(256, BWD_WAVES(NR, H, 2)) void attn_bwd_kernel_direct(const AttnDev a) { attn_bwd_body<NR, H, 2>(a); }
 template <int NR, int H> __global__ __launch_bounds__(256, BWD_WAVES(NR, H, 1)) void attn_bwd_kernel_det(const AttnDev a) { attn_bwd_body<NR, H, 3>(a); }
+static int attn_fwd_form(const PfoAttn& a) { return attn_fwd_ring_ok(a) ? PFO_ATTN_FORM_FWD_RING : PFO_ATTN_FORM_FWD_REG; }
 int pfo_attn_fwd_launch(const PfoAttn& a, hipStream_t stream) {
   if (int rc = check_common(a)) return rc;
   AttnDev d;
@@ -1579,7 +1580,7 @@ int pfo_attn_fwd_launch(const PfoAttn& a, hipStream_t stream) {
   const double C = 2.0 * a.D + a.Ef;
   const double bytes = (double)a.N * (a.K * (4.0 * a.D + 4.0 * a.Ef + 12.0) + 2.0 * a.H * C * 4.0 + 4.0 * a.H * a.K);
   pfo_prof_begin(stream);
-  if (attn_fwd_ring_ok(a)) {
+  if (attn_fwd_form(a) == PFO_ATTN_FORM_FWD_RING) {
     const dim3 g((unsigned)pfo_ceil_div(a.N, 4)), b(256);
     switch (((a.D + 63) / 64) * 8 + a.H) {
       case 1 * 8 + 1: PFO_KLAUNCH((attn_fwd_ring_kernel<1, 1>), g, b, 0, stream, d); break;
@@ -1642,20 +1643,35 @@ bool pfo_attn_bwd_uses_runs(const PfoAttn& a) {
          a.dqk_live && aligned;
 }
 
+// what happens to the neighbour-row gradients (DMODE of the kernels): 0 none, 1 added into the rows nbr_row names, 2 plain stores
+static int attn_bwd_dmode(const PfoAttn& a) { return !a.d_nbr ? 0 : (a.nbr_row ? 1 : 2); }
+static int attn_bwd_form(const PfoAttn& a) {
+  const int dmode = attn_bwd_dmode(a);
+  if (pfo_attn_bwd_uses_runs(a)) return PFO_ATTN_FORM_BWD_RUNS;
+  if (attn_bwd_ring_ok(a, dmode)) return dmode == 0 ? PFO_ATTN_FORM_BWD_RING_NONE : PFO_ATTN_FORM_BWD_RING_DIRECT;
+  if (dmode == 0) return PFO_ATTN_FORM_BWD_NONE;
+  if (dmode == 1) return a.det ? PFO_ATTN_FORM_BWD_DET : PFO_ATTN_FORM_BWD_ATOMIC;
+  return PFO_ATTN_FORM_BWD_DIRECT;
+}
+int pfo_attn_form(const PfoAttn& a, bool backward) {
+  if (check_common(a)) return -1;
+  return backward ? attn_bwd_form(a) : attn_fwd_form(a);
+}
+
 int pfo_attn_bwd_launch(const PfoAttn& a, int* n_parts, hipStream_t stream) {
   if (int rc = check_common(a)) return rc;
   PFO_REQUIRE(a.dctx && a.dQK && a.dtime_part, "null backward buffers");
   PFO_REQUIRE(!a.det || a.dtime_slab, "deterministic mode needs the slab");
+  const int form = attn_bwd_form(a);
   AttnDev d;
   to_dev(a, d);
   const int grid = (int)std::min<int64_t>(ATTN_BWD_MAX_BLOCKS, pfo_ceil_div(a.N, 4));   // (deterministic: the slab's row count is fixed)
   // rows read again + their gradient rows written/added, qk + dctx + ctx in, dqk out
   const double C = 2.0 * a.D + a.Ef;
   const double bytes = (double)a.N * (a.K * (8.0 * a.D + 4.0 * a.Ef + 12.0) + 4.0 * a.H * C * 4.0 + 4.0 * a.H * a.K);
-  const int dmode = !a.d_nbr ? 0 : (a.nbr_row ? 1 : 2);
   // the run-merged kernel's staging image: three rows of H Cp floats + (4 + H) metadata arrays of K words (attn_bwd_runs_kernel)
   const size_t run_lds = 3 * (size_t)a.H * a.Cp * 4 + (size_t)(4 + a.H) * a.K * 4 + (size_t)pfo_align_up(4 * a.K, 16);   // (+ K injected keep bytes, one dword each)
-  if (pfo_attn_bwd_uses_runs(a)) {
+  if (form == PFO_ATTN_FORM_BWD_RUNS) {
     // run-merged form: single-wavefront workgroups, one unit of chunks each (the grid covers every possible unit, so the
     // kernel's grid-stride loop runs once)
     // (16 chunks per XCD turn: FETCH 625 -> 487 MB per launch, 512 at 4; the launch time does not move)
@@ -1685,11 +1701,11 @@ int pfo_attn_bwd_launch(const PfoAttn& a, int* n_parts, hipStream_t stream) {
     return PFO_OK;
   }
   pfo_prof_begin(stream);
-  if (attn_bwd_ring_ok(a, dmode) && dmode == 0) { ATTN_DISPATCH_RING(attn_bwd_ring_kernel_none, grid); }
-  else if (attn_bwd_ring_ok(a, dmode)) { ATTN_DISPATCH_RING(attn_bwd_ring_kernel_direct, grid); }
-  else if (dmode == 0) { ATTN_DISPATCH(attn_bwd_kernel_none, grid); }
-  else if (dmode == 1 && a.det) { ATTN_DISPATCH(attn_bwd_kernel_det, grid); }
-  else if (dmode == 1) { ATTN_DISPATCH(attn_bwd_kernel, grid); }
+  if (form == PFO_ATTN_FORM_BWD_RING_NONE) { ATTN_DISPATCH_RING(attn_bwd_ring_kernel_none, grid); }
+  else if (form == PFO_ATTN_FORM_BWD_RING_DIRECT) { ATTN_DISPATCH_RING(attn_bwd_ring_kernel_direct, grid); }
+  else if (form == PFO_ATTN_FORM_BWD_NONE) { ATTN_DISPATCH(attn_bwd_kernel_none, grid); }
+  else if (form == PFO_ATTN_FORM_BWD_DET) { ATTN_DISPATCH(attn_bwd_kernel_det, grid); }
+  else if (form == PFO_ATTN_FORM_BWD_ATOMIC) { ATTN_DISPATCH(attn_bwd_kernel, grid); }
   else { ATTN_DISPATCH(attn_bwd_kernel_direct, grid); }
   PFO_LAUNCH_CHECK();
   pfo_prof_end(PFO_PROF_ATTN_BWD, bytes, stream);

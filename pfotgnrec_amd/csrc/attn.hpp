@@ -79,3 +79,6 @@ int64_t pfo_attn_bwd_det_parts(int64_t N);   // slab rows a deterministic backwa
 // (a.members[m]), not to instance m
 bool pfo_attn_bwd_uses_runs(const PfoAttn& a);
 bool pfo_attn_bwd_runs_possible(int K, int D, int H);   // the switch and the shape limits alone (known before the launch is described)
+// the kernel a launcher takes for `a` (values: include/pfotgn.h PFO_ATTN_FORM_*; -1 with a message when `a` fails the common
+// checks): the launchers dispatch on the same two static functions
+int pfo_attn_form(const PfoAttn& a, bool backward);

@@ -1,7 +1,10 @@
-// Debug / test probes of the internal contraction interface (gemm.hpp): the flat C structs of include/pfotgn.h copied field
+// Debug / test probes of the internal contraction interface (gemm.hpp), of the attention interface (attn.hpp) and of the
+// grouping the run-merged attention backward consumes (memory.hpp): the flat C structs of include/pfotgn.h copied field
 // for field into the internal ones and handed to the internal launchers unchanged.  No logic of their own beyond null and
 // count checks - what a probe computes is what tgn.hip gets from the same launcher.
 #include "gemm.hpp"
+#include "attn.hpp"
+#include "memory.hpp"
 
 static void to_gemm(const pfo_gemm_desc& s, PfoGemm& g) {
   for (int i = 0; i < 2; ++i) {
@@ -99,4 +102,64 @@ extern "C" int pfo_debug_sum_slabs(const pfo_sum_slabs_desc* list, int32_t n, vo
     q[i].n_slabs = list[i].n_slabs; q[i].accumulate = list[i].accumulate;
   }
   return pfo_sum_slabs_launch(q, n, (hipStream_t)stream);
+}
+
+// ---- the internal attention interface (attn.hpp) and the grouping its run-merged backward consumes (memory.hpp)
+static void to_attn(const pfo_attn_desc& s, PfoAttn& a) {
+  a.N = s.N; a.K = s.K; a.D = s.D; a.Ef = s.Ef; a.H = s.H; a.Cp = s.Cp;
+  a.QK = s.QK; a.qk_row = s.qk_row; a.qk_ld = s.qk_ld;
+  a.nbr_tab = s.nbr_tab; a.nbr_ld = s.nbr_ld; a.nbr_row = s.nbr_row; a.nbr_row_base = s.nbr_row_base;
+  a.nbr_rows = s.nbr_rows; a.edge_rows = s.edge_rows; a.nbr_relu = s.nbr_relu;
+  a.nbr_ids = s.nbr_ids; a.edge_feat = s.edge_feat; a.eidx = s.eidx; a.dt = s.dt; a.tw = s.tw; a.tb = s.tb;
+  a.scale = s.scale; a.dropout_p = s.dropout_p; a.seed = s.seed; a.offset = s.offset; a.offset_dev = s.offset_dev;
+  a.keep_inject = s.keep_inject;
+  a.ctx = s.ctx; a.attw = s.attw; a.inv = s.inv;
+  a.dctx = s.dctx; a.dQK = s.dQK; a.d_nbr = s.d_nbr; a.d_nbr_ld = s.d_nbr_ld; a.d_nbr_rep = s.d_nbr_rep; a.d_nbr_nrep = s.d_nbr_nrep;
+  a.dtime_part = s.dtime_part; a.det = s.det; a.dtime_slab = s.dtime_slab; a.dqk_live = s.dqk_live;
+  a.members = s.members; a.seg_ptr = s.seg_ptr; a.n_rows = s.n_rows; a.run_cnt = s.run_cnt;
+}
+
+extern "C" int pfo_debug_attn_fwd(const pfo_attn_desc* desc, void* stream) {
+  PFO_REQUIRE(desc, "null descriptor");
+  PfoAttn a;
+  to_attn(*desc, a);
+  return pfo_attn_fwd_launch(a, (hipStream_t)stream);
+}
+extern "C" int pfo_debug_attn_bwd(const pfo_attn_desc* desc, int32_t* n_parts, void* stream) {
+  PFO_REQUIRE(desc, "null descriptor");
+  PfoAttn a;
+  to_attn(*desc, a);
+  int parts = 0;
+  const int rc = pfo_attn_bwd_launch(a, &parts, (hipStream_t)stream);
+  if (n_parts) *n_parts = parts;
+  return rc;
+}
+extern "C" int64_t pfo_debug_attn_det_parts(int64_t N) {
+  if (N <= 0) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_attn_bwd_det_parts(N);
+}
+extern "C" int32_t pfo_debug_attn_form(const pfo_attn_desc* desc, int32_t backward) {
+  if (!desc) { pfo_set_error("%s: null descriptor", __func__); return -1; }
+  PfoAttn a;
+  to_attn(*desc, a);
+  return pfo_attn_form(a, backward != 0);
+}
+
+extern "C" int64_t pfo_debug_seg_scratch_ints(int32_t cap_rows) {
+  if (cap_rows <= 0) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_seg_scratch_ints(cap_rows);
+}
+extern "C" int64_t pfo_debug_seg_of_ints(int64_t n_members) {
+  if (n_members <= 0) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_seg_of_ints(n_members);
+}
+extern "C" int pfo_debug_seg_build(const int32_t* idx, const int32_t* nodes, int32_t N, int32_t cap_rows, const int32_t* key_src,
+                                   int32_t* seg_ptr, int32_t* members, int32_t* seg_of, int32_t* scratch, int64_t scratch_ints,
+                                   void* stream) {
+  PFO_REQUIRE(N > 0 && cap_rows > 0 && scratch, "bad arguments");
+  const int64_t scan = pfo_seg_scratch_ints(cap_rows);
+  PFO_REQUIRE(scratch_ints >= scan + 2 * ((int64_t)cap_rows + 1) + N, "short scratch");
+  int32_t* cursor = scratch + scan;
+  int32_t* tmp = cursor + 2 * ((int64_t)cap_rows + 1);
+  return pfo_seg_build_launch(idx, nodes, N, cap_rows, key_src, seg_ptr, cursor, tmp, members, seg_of, scratch, (hipStream_t)stream);
 }

@@ -25,6 +25,51 @@ def test_library_exports_every_declared_symbol():
     assert lib.pfo_abi_version() == 6
 
 
+def test_attention_form_query_follows_the_shape_table():
+    """pfo_debug_attn_form is pure host code over the descriptor (pointers are only tested for null and alignment, never
+    followed): every shape of tests/attn_ref.py reports the kernel DESIGN.md's table names for it, a descriptor the common
+    checks refuse reports -1 with the message, and the size queries answer."""
+    import ctypes
+    from pfotgnrec_amd import _lib
+    import attn_ref as R
+    lib = _lib.load()
+    P = 1 << 12                                                           # any 16-byte aligned non-null address
+
+    def desc(D, Ef, H, K=7, N=13, table=False, d_nbr=False, det=0, members=False, qk=P, nbr_ld=None):
+        d = _lib.AttnDesc(N=N, K=K, D=D, Ef=Ef, H=H, Cp=R.cp_of(D, Ef), nbr_ld=nbr_ld or D, nbr_rows=N * K + 8, edge_rows=18, det=det)
+        for f in ("nbr_tab", "nbr_ids", "eidx", "dt", "tw", "tb", "ctx", "attw", "inv", "edge_feat", "dctx", "dQK"):
+            setattr(d, f, P)
+        d.QK = qk
+        if table:
+            d.nbr_row = P
+        if d_nbr:
+            d.d_nbr = P
+        if members:
+            for f in ("members", "seg_ptr", "n_rows", "run_cnt", "dqk_live", "qk_row"):
+                setattr(d, f, P)
+        return d
+
+    def form(d, backward):
+        return _lib.ATTN_FORMS[lib.pfo_debug_attn_form(ctypes.byref(d), backward)]
+    for ring, shapes in ((True, R.RING_SHAPES), (False, R.REG_SHAPES + [R.ODD_SHAPE])):
+        for D, Ef, H in shapes:
+            assert form(desc(D, Ef, H), 0) == ("fwd_ring" if ring else "fwd_reg"), (D, Ef, H)
+            assert form(desc(D, Ef, H), 1) == ("bwd_ring_none" if ring else "bwd_none")
+            assert form(desc(D, Ef, H, d_nbr=True), 1) == ("bwd_ring_direct" if ring else "bwd_direct")
+            assert form(desc(D, Ef, H, table=True, d_nbr=True), 1) == "bwd_atomic"
+            assert form(desc(D, Ef, H, table=True, d_nbr=True, det=1), 1) == "bwd_det"
+            runs = not (D > 192 and H == 4)
+            assert form(desc(D, Ef, H, table=True, d_nbr=True, members=True), 1) == ("bwd_runs" if runs else "bwd_atomic")
+            assert form(desc(D, Ef, H, table=True, d_nbr=True, det=1, members=True), 1) == ("bwd_runs" if runs else "bwd_det")
+    assert form(desc(32, 4, 2, qk=P + 4), 0) == "fwd_reg" and form(desc(32, 4, 2, nbr_ld=33), 0) == "fwd_reg"
+    assert form(desc(32, 4, 2, qk=P + 4), 1) == "bwd_ring_none" and form(desc(32, 4, 2, nbr_ld=33, d_nbr=True), 1) == "bwd_direct"
+    assert form(desc(32, 4, 2, table=True, d_nbr=True, members=True, qk=P + 4), 1) == "bwd_atomic"     # (staging moves 16 bytes)
+    assert lib.pfo_debug_attn_form(ctypes.byref(desc(32, 4, 3)), 1) == -1 and b"n_heads" in lib.pfo_last_error()
+    assert lib.pfo_debug_attn_form(None, 0) == -1
+    assert lib.pfo_debug_attn_det_parts(13) == 4 and lib.pfo_debug_attn_det_parts(0) == -1
+    assert lib.pfo_debug_seg_scratch_ints(20) > 0 and lib.pfo_debug_seg_of_ints(33) >= 33 and lib.pfo_debug_seg_scratch_ints(0) == -1
+
+
 def test_param_layout_matches_reference_inventory():
     """1.551 M trainable fp32 at C2 (D=172, Ef=4, L=2), 34 304 at C1 incl. the dead layer_norm."""
     import ctypes
