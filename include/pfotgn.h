@@ -769,6 +769,51 @@ int64_t pfo_debug_seg_of_ints(int64_t n_members);
 int pfo_debug_seg_build(const int32_t* idx, const int32_t* nodes, int32_t N, int32_t cap_rows, const int32_t* key_src,
                         int32_t* seg_ptr, int32_t* members, int32_t* seg_of, int32_t* scratch, int64_t scratch_ints, void* stream);
 
+/* debug / test probes of the memory-side interface (csrc/memory.hpp): one call per internal launcher, the arguments handed on
+ * unchanged behind null, count and scratch-size checks.  The comments of memory.hpp are the contract; none of this is part
+ * of the drop-in surface (additive: the abi version stays).  Path queries (pure host code, -1 with a message on a bad size):
+ *   pfo_debug_msg_store_needs_winner: 1 when a batch of B events takes the atomicMax winner table, 0 for the inline scan.
+ *   pfo_debug_gru_gates_bwd_vec: 1 when the launcher takes the float4 kernel for these operands, 0 for the scalar one.
+ *   pfo_debug_scan_sweeps: sweeps of 1024 block totals the middle kernel of an n-entry scan takes (2 and more above 2^20).
+ *   pfo_debug_fold_parts_rows_in_flight: 8 once a thread of the fold has eight part rows to read at a time, else 1.
+ * Sizes: scratch of pfo_debug_touch_compact = pfo_debug_compact_scratch_ints(n_nodes) int32 (its first 2 ceil(n_nodes / 1024)
+ * zero when marks_are_zero), of pfo_debug_iscan = n / 1024 + 16 int32, of pfo_debug_fold_parts =
+ * pfo_debug_fold_parts_scratch_doubles(n) doubles with 64 int32 tickets (zero before the first use).  pfo_debug_cq_backward takes
+ * HOST arrays of n_layers (<= PFO_MAX_LAYERS) device pointers. */
+int64_t pfo_debug_compact_scratch_ints(int32_t n_nodes);
+int pfo_debug_touch_compact(const int32_t* nodes0, int64_t n0, const int32_t* extra, int64_t n_extra, int32_t n_nodes,
+                            int32_t* mark, int32_t* slot, int32_t* touched_ids, int32_t* n_counts, int32_t* scratch,
+                            int64_t scratch_ints, int32_t marks_are_zero, int32_t marked, void* stream);
+int pfo_debug_pack_remap(const float* msg_table, int32_t M, const float* memory, int32_t D, const uint8_t* has_msg,
+                         const int32_t* touched_ids, const int32_t* n_touched, int32_t cap, float* msg_rows, float* h_rows,
+                         uint8_t* hm, const int32_t* nodes0, int64_t n0, const int32_t* slot, int32_t* idx0, void* stream);
+int32_t pfo_debug_gru_gates_bwd_vec(const float* gates, const float* dgi, const float* dgh, const float* h_rows, int32_t D,
+                                    const float* d_h0, int64_t rep_stride, const float* d_extra);
+int pfo_debug_gru_gates_bwd(const float* gates, float* dgi, float* dgh, const float* h_rows, const uint8_t* hm,
+                            const int32_t* n_touched, int32_t cap, int32_t D, const float* d_h0, int32_t n_rep, int64_t rep_stride,
+                            const float* d_extra, int32_t det, void* stream);
+int pfo_debug_zero_rows(float* dst, const int32_t* n_rows, int32_t cap_rows, int32_t D, int32_t n_rep, int64_t rep_stride,
+                        void* stream);
+int pfo_debug_persist(const int32_t* src, const int32_t* dst, int32_t B, const int32_t* slot, const float* upd_mem,
+                      const uint8_t* has_msg, const float* msg_time, float* memory, float* last_update, int32_t D,
+                      int32_t* winner, void* stream);
+int32_t pfo_debug_msg_store_needs_winner(int32_t B);
+int pfo_debug_msg_store(const int32_t* src, const int32_t* dst, const double* ts, const int32_t* eidx, int32_t B,
+                        const float* memory, const float* last_update, const float* edge_feat, const float* tw, const float* tb,
+                        int32_t D, int32_t Ef, float* msg_table, float* msg_time, uint8_t* has_msg, int32_t* winner, void* stream);
+int pfo_debug_observe_select(const int32_t* src, const int32_t* dst, int32_t B, const uint8_t* has_msg, int32_t* rep, int32_t base,
+                             int32_t* slot, int32_t* touched, int32_t* n_out, void* stream);
+int32_t pfo_debug_scan_sweeps(int64_t n);
+int pfo_debug_iscan(const int32_t* in, int64_t n, int32_t* out, int32_t* scratch, int64_t scratch_ints, void* stream);
+int pfo_debug_mean(const float* src, int64_t n, float* out, void* stream);
+int pfo_debug_cq_backward(const float* const* gq, const float* const* Wq, int32_t n_layers, const float* tb, int32_t D,
+                          float* const* d_bq, float* const* d_Wq, float* d_tb, float* tb_part, const float* tb_add,
+                          const double* dtime, int32_t n_bins, float* d_tw, void* stream);
+int64_t pfo_debug_fold_parts_scratch_doubles(int32_t n);
+int32_t pfo_debug_fold_parts_rows_in_flight(int32_t n_parts);
+int pfo_debug_fold_parts(const double* parts, int32_t n_parts, int32_t n, float* out, int32_t accumulate, double* scratch,
+                         int64_t scratch_doubles, int32_t* tickets, double* out64, void* stream);
+
 /* Parameter cache (pfo_tgn_state.pcache): its size, and the call that (re)builds it from state->params on the library's
  * side stream, forked from `stream` and NOT joined back - the next pfo_tgn_forward with pcache_valid = 1 queues its own
  * side-stream work behind it, so the caller's stream never waits for the build itself.  Meant to be called right behind the

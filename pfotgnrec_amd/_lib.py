@@ -216,6 +216,29 @@ PROTOTYPES = {
     "pfo_debug_seg_scratch_ints": (C.c_int64, [C.c_int32]),
     "pfo_debug_seg_of_ints": (C.c_int64, [C.c_int64]),
     "pfo_debug_seg_build": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    # ... and of the memory-side interface (csrc/memory.hpp), one per launcher
+    "pfo_debug_compact_scratch_ints": (C.c_int64, [C.c_int32]),
+    "pfo_debug_touch_compact": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
+                                          C.c_int32, _VP]),
+    "pfo_debug_pack_remap": (C.c_int, [_VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, C.c_int64, _VP,
+                                       _VP, _VP]),
+    "pfo_debug_gru_gates_bwd_vec": (C.c_int32, [_VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int64, _VP]),
+    "pfo_debug_gru_gates_bwd": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_int64, _VP,
+                                          C.c_int32, _VP]),
+    "pfo_debug_zero_rows": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _VP]),
+    "pfo_debug_persist": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    "pfo_debug_msg_store_needs_winner": (C.c_int32, [C.c_int32]),
+    "pfo_debug_msg_store": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP,
+                                      _VP, _VP]),
+    "pfo_debug_observe_select": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP]),
+    "pfo_debug_scan_sweeps": (C.c_int32, [C.c_int64]),
+    "pfo_debug_iscan": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP]),
+    "pfo_debug_mean": (C.c_int, [_VP, C.c_int64, _VP, _VP]),
+    "pfo_debug_cq_backward": (C.c_int, [C.POINTER(_VP), C.POINTER(_VP), C.c_int32, _VP, C.c_int32, C.POINTER(_VP), C.POINTER(_VP),
+                                        _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP]),
+    "pfo_debug_fold_parts_scratch_doubles": (C.c_int64, [C.c_int32]),
+    "pfo_debug_fold_parts_rows_in_flight": (C.c_int32, [C.c_int32]),
+    "pfo_debug_fold_parts": (C.c_int, [_VP, C.c_int32, C.c_int32, _VP, C.c_int32, _VP, C.c_int64, _VP, _VP, _VP]),
     "pfo_prof_enable": (C.c_int, [C.c_int32]),
     "pfo_marks_enable": (C.c_int, [C.c_int32]),
     "pfo_mark": (C.c_int, [C.c_char_p, _VP]),

@@ -28,7 +28,7 @@ __global__ __launch_bounds__(1024) void scan_blocks_kernel(int32_t* __restrict__
   if (threadIdx.x == 0) s_carry = 0;
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int base = 0; base < n_blocks; base += 1024) {
+  for (int base = 0; base < n_blocks; base += 1024) {        // (pfo_scan_sweeps states this trip count for pfo_iscan_launch: keep them together)
     const int i = base + threadIdx.x;
     const int v = i < n_blocks ? block_counts[i] : 0;
     int incl = v;
@@ -136,39 +136,6 @@ int pfo_touch_compact_launch(const int32_t* nodes0, int64_t n0, const int32_t* e
   return PFO_OK;
 }
 
-__global__ void remap_kernel(const int32_t* __restrict__ nodes0, int64_t n0, const int32_t* __restrict__ slot,
-                             int32_t* __restrict__ idx0) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n0; i += (int64_t)gridDim.x * blockDim.x)
-    idx0[i] = slot[nodes0[i]];
-}
-
-int pfo_remap_launch(const int32_t* nodes0, int64_t n0, const int32_t* slot, int32_t* idx0, hipStream_t stream) {
-  const int mb = (int)std::min<int64_t>(2048, pfo_ceil_div(n0, 256));
-  PFO_KLAUNCH(remap_kernel, dim3(mb), dim3(256), 0, stream, nodes0, n0, slot, idx0);
-  PFO_LAUNCH_CHECK();
-  return PFO_OK;
-}
-
-// rows of the touched nodes from a full table: dst[s] = src[touched_ids[s]]   (no-memory models: level 0 = node features)
-__global__ void gather_rows_kernel(const float* __restrict__ src, int D, const int32_t* __restrict__ touched_ids,
-                                   const int32_t* __restrict__ n_touched, float* __restrict__ dst) {
-  const int lane = threadIdx.x & 63;
-  const int nt = *n_touched;
-  for (int s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; s < nt; s += (gridDim.x * blockDim.x) >> 6) {
-    const float4* a = reinterpret_cast<const float4*>(src + (int64_t)touched_ids[s] * D);
-    float4* d = reinterpret_cast<float4*>(dst + (int64_t)s * D);
-    for (int c = lane; c < D / 4; c += 64) d[c] = a[c];
-  }
-}
-int pfo_gather_rows_launch(const float* src, int D, const int32_t* touched_ids, const int32_t* n_touched, int cap, float* dst,
-                           hipStream_t stream) {
-  PFO_REQUIRE((D % 4) == 0, "row length must be a multiple of 4");
-  const int nb = (int)std::min<int64_t>(4096, std::max<int64_t>(1, pfo_ceil_div(cap, 4)));
-  PFO_KLAUNCH(gather_rows_kernel, dim3(nb), dim3(256), 0, stream, src, D, touched_ids, n_touched, dst);
-  PFO_LAUNCH_CHECK();
-  return PFO_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Instances grouped by the touched-table row they read (layer 1: instance n reads row idx[n]).  The backward sums
 // per-instance gradients over each group BEFORE the contractions that only depend on the row, so those contractions run
@@ -237,6 +204,8 @@ __global__ void seg_sort_kernel(const int32_t* __restrict__ seg_ptr, int n_seg, 
     }
   }
 }
+// sweeps of scan_blocks_kernel's loop over the n / SCAN_BLOCK block totals of pfo_iscan_launch (a restatement of that loop's bound)
+int pfo_scan_sweeps(int64_t n) { return (int)pfo_ceil_div(pfo_ceil_div(n, SCAN_BLOCK), 1024); }
 int pfo_iscan_launch(const int32_t* in, int64_t n, int32_t* out, int32_t* scratch, hipStream_t stream) {
   PFO_REQUIRE(in && out && scratch && n > 0 && n < ((int64_t)1 << 31), "bad arguments");
   const int nb = (int)pfo_ceil_div(n, SCAN_BLOCK);
@@ -650,11 +619,15 @@ __global__ void gru_gates_bwd_vec_kernel(const float* __restrict__ gates, float*
   }
 }
 
+bool pfo_gru_gates_bwd_vec(const float* gates, const float* dgi, const float* dgh, const float* h_rows, int D, const float* d_h0,
+                           int64_t rep_stride, const float* d_extra) {
+  return (D & 3) == 0 && (rep_stride & 3) == 0 &&
+         ((((uintptr_t)gates) | ((uintptr_t)dgi) | ((uintptr_t)dgh) | ((uintptr_t)h_rows) | ((uintptr_t)d_h0) | ((uintptr_t)d_extra)) & 15) == 0;
+}
 int pfo_gru_gates_bwd_launch(const float* gates, float* dgi, float* dgh, const float* h_rows, const uint8_t* hm,
                              const int32_t* n_touched, int cap, int D, const float* d_h0, int n_rep, int64_t rep_stride,
                              const float* d_extra, int det, hipStream_t stream) {
-  const bool vec = (D & 3) == 0 && (rep_stride & 3) == 0 &&
-                   ((((uintptr_t)gates) | ((uintptr_t)dgi) | ((uintptr_t)dgh) | ((uintptr_t)h_rows) | ((uintptr_t)d_h0) | ((uintptr_t)d_extra)) & 15) == 0;
+  const bool vec = pfo_gru_gates_bwd_vec(gates, dgi, dgh, h_rows, D, d_h0, rep_stride, d_extra);
   pfo_prof_begin(stream);
   if (vec) {
     const int nb = (int)std::min<int64_t>(4096, pfo_ceil_div((int64_t)cap * (D / 4), 256));

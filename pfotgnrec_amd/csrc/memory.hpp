@@ -11,10 +11,11 @@ int64_t pfo_compact_scratch_ints(int n_nodes);
 int pfo_touch_compact_launch(const int32_t* nodes0, int64_t n0, const int32_t* extra, int64_t n_extra, int n_nodes, int32_t* mark,
                              int32_t* slot, int32_t* touched_ids, int32_t* n_counts, int32_t* scratch, bool marks_are_zero,
                              bool marked, hipStream_t stream);
-// packs the rows backward still needs after the state update overwrites them (pfo_pack_remap_launch):
-//   msg_rows[s] = msg_table[id], h_rows[s] = memory[id], hm[s] = has_msg[id]   (id = touched_ids[s])
-int pfo_remap_launch(const int32_t* nodes0, int64_t n0, const int32_t* slot, int32_t* idx0, hipStream_t stream);
-// both in one launch (msg_table == null: only `memory` rows are copied, e.g. node features of a no-memory model)
+// packs the rows backward still needs after the state update overwrites them, and translates the level-0 node list into
+// table rows, in one launch:
+//   msg_rows[s] = msg_table[id], h_rows[s] = memory[id], hm[s] = has_msg[id]   (id = touched_ids[s], s < *n_touched)
+//   idx0[i] = slot[nodes0[i]], i < n0
+// (msg_table == null: only `memory` rows are copied, e.g. node features of a no-memory model)
 int pfo_pack_remap_launch(const float* msg_table, int M, const float* memory, int D, const uint8_t* has_msg,
                           const int32_t* touched_ids, const int32_t* n_touched, int cap, float* msg_rows, float* h_rows,
                           uint8_t* hm, const int32_t* nodes0, int64_t n0, const int32_t* slot, int32_t* idx0, hipStream_t stream);
@@ -26,11 +27,14 @@ int pfo_pack_remap_launch(const float* msg_table, int M, const float* memory, in
 int pfo_gru_gates_bwd_launch(const float* gates, float* dgi, float* dgh, const float* h_rows, const uint8_t* hm,
                              const int32_t* n_touched, int cap, int D, const float* d_h0, int n_rep, int64_t rep_stride,
                              const float* d_extra, int det, hipStream_t stream);
-// dst[s] = src[touched_ids[s]], s < *n_touched
-int pfo_gather_rows_launch(const float* src, int D, const int32_t* touched_ids, const int32_t* n_touched, int cap, float* dst,
-                           hipStream_t stream);
+// (the float4 kernel is taken when D and rep_stride are multiples of 4 and every float operand is 16-byte aligned: the
+//  launcher dispatches on this function)
+bool pfo_gru_gates_bwd_vec(const float* gates, const float* dgi, const float* dgh, const float* h_rows, int D, const float* d_h0,
+                           int64_t rep_stride, const float* d_extra);
 // exclusive scan of n ints (n < 2^31; scratch: n / 1024 + 16 ints); in == out is allowed
 int pfo_iscan_launch(const int32_t* in, int64_t n, int32_t* out, int32_t* scratch, hipStream_t stream);
+// (sweeps of 1024 block totals the middle kernel of that scan takes: 2 and more above 2^20 scanned entries)
+int pfo_scan_sweeps(int64_t n);
 // --- instances grouped by the touched-table row they read: seg_ptr[cap_rows + 1], members[N] (ascending inside a group)
 int64_t pfo_seg_scratch_ints(int cap_rows);
 // inside a group the members are ordered by (key_src[instance], instance): key = the number of row entries before the
@@ -78,6 +82,8 @@ int pfo_cq_backward_launch(const float* const* gq, const float* const* Wq, int n
                            float* d_tw, hipStream_t stream);
 // scratch: pfo_fold_parts_scratch_doubles(n) doubles; tickets: 64 ints, zero before the first use (self-resetting)
 int64_t pfo_fold_parts_scratch_doubles(int n);
+// (part rows a thread keeps in flight: 8 once some thread of the launch has eight rows to read, else 1)
+int pfo_fold_parts_rows_in_flight(int n_parts);
 int pfo_fold_parts_launch(const double* parts, int n_parts, int n, float* out, int accumulate, double* scratch, int* tickets,
                           hipStream_t stream, double* out64 = nullptr);
 // (out64 != null: the sums are stored there as doubles instead of being cast into `out`)

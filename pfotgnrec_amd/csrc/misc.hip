@@ -617,7 +617,8 @@ __global__ __launch_bounds__(256) void fold_parts_kernel(const double* __restric
   double s = 0.0;
   if (col < n) {
     // eight part rows in flight per thread (they lie 4 * FOLD_SLICES rows apart: one at a time, every load is a full
-    // memory round trip); fixed order -> reproducible
+    // memory round trip); fixed order -> reproducible.  (pfo_fold_parts_rows_in_flight restates the bound of the first
+    // loop - whether ANY thread enters it - for the tests: keep them together)
     int p = blockIdx.y * 4 + pl;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (; p + 7 * 4 * FOLD_SLICES < n_parts; p += 8 * 4 * FOLD_SLICES) {
@@ -652,6 +653,7 @@ __global__ __launch_bounds__(256) void fold_parts_kernel(const double* __restric
   }
   if (threadIdx.x == 0) tickets[blockIdx.x] = 0;
 }
+int pfo_fold_parts_rows_in_flight(int n_parts) { return n_parts > 7 * 4 * FOLD_SLICES ? 8 : 1; }
 int64_t pfo_fold_parts_scratch_doubles(int n) { return (int64_t)FOLD_SLICES * n; }
 int pfo_fold_parts_launch(const double* parts, int n_parts, int n, float* out, int accumulate, double* scratch, int* tickets,
                           hipStream_t stream, double* out64) {

@@ -1,5 +1,6 @@
 // Debug / test probes of the internal contraction interface (gemm.hpp), of the attention interface (attn.hpp) and of the
-// grouping the run-merged attention backward consumes (memory.hpp): the flat C structs of include/pfotgn.h copied field
+// memory-side interface (memory.hpp: the grouping the run-merged attention backward consumes, and one probe per launcher of
+// the compaction, state-update and small-op kernels): the flat C structs of include/pfotgn.h copied field
 // for field into the internal ones and handed to the internal launchers unchanged.  No logic of their own beyond null and
 // count checks - what a probe computes is what tgn.hip gets from the same launcher.
 #include "gemm.hpp"
@@ -162,4 +163,108 @@ extern "C" int pfo_debug_seg_build(const int32_t* idx, const int32_t* nodes, int
   int32_t* cursor = scratch + scan;
   int32_t* tmp = cursor + 2 * ((int64_t)cap_rows + 1);
   return pfo_seg_build_launch(idx, nodes, N, cap_rows, key_src, seg_ptr, cursor, tmp, members, seg_of, scratch, (hipStream_t)stream);
+}
+
+// ---- the memory-side interface (memory.hpp): one probe per launcher, the arguments handed on unchanged.  The path queries
+// answer from the functions the launchers (or the kernels' loop bounds) are written with.
+extern "C" int64_t pfo_debug_compact_scratch_ints(int32_t n_nodes) {
+  if (n_nodes <= 0) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_compact_scratch_ints(n_nodes);
+}
+extern "C" int pfo_debug_touch_compact(const int32_t* nodes0, int64_t n0, const int32_t* extra, int64_t n_extra, int32_t n_nodes,
+                                       int32_t* mark, int32_t* slot, int32_t* touched_ids, int32_t* n_counts, int32_t* scratch,
+                                       int64_t scratch_ints, int32_t marks_are_zero, int32_t marked, void* stream) {
+  PFO_REQUIRE(n_nodes > 0 && n0 >= 0 && n_extra >= 0 && (n_extra == 0 || extra), "bad arguments");
+  PFO_REQUIRE(scratch && scratch_ints >= pfo_compact_scratch_ints(n_nodes), "short scratch");
+  return pfo_touch_compact_launch(nodes0, n0, extra, n_extra, n_nodes, mark, slot, touched_ids, n_counts, scratch,
+                                  marks_are_zero != 0, marked != 0, (hipStream_t)stream);
+}
+extern "C" int pfo_debug_pack_remap(const float* msg_table, int32_t M, const float* memory, int32_t D, const uint8_t* has_msg,
+                                    const int32_t* touched_ids, const int32_t* n_touched, int32_t cap, float* msg_rows,
+                                    float* h_rows, uint8_t* hm, const int32_t* nodes0, int64_t n0, const int32_t* slot,
+                                    int32_t* idx0, void* stream) {
+  PFO_REQUIRE(cap > 0 && D > 0 && M >= 0, "bad sizes");
+  return pfo_pack_remap_launch(msg_table, M, memory, D, has_msg, touched_ids, n_touched, cap, msg_rows, h_rows, hm, nodes0, n0,
+                               slot, idx0, (hipStream_t)stream);
+}
+extern "C" int32_t pfo_debug_gru_gates_bwd_vec(const float* gates, const float* dgi, const float* dgh, const float* h_rows,
+                                               int32_t D, const float* d_h0, int64_t rep_stride, const float* d_extra) {
+  return pfo_gru_gates_bwd_vec(gates, dgi, dgh, h_rows, D, d_h0, rep_stride, d_extra) ? 1 : 0;
+}
+extern "C" int pfo_debug_gru_gates_bwd(const float* gates, float* dgi, float* dgh, const float* h_rows, const uint8_t* hm,
+                                       const int32_t* n_touched, int32_t cap, int32_t D, const float* d_h0, int32_t n_rep,
+                                       int64_t rep_stride, const float* d_extra, int32_t det, void* stream) {
+  PFO_REQUIRE(gates && dgi && dgh && h_rows && hm && n_touched && d_h0, "null argument");
+  PFO_REQUIRE(cap > 0 && D > 0 && n_rep >= 1 && rep_stride >= 0, "bad sizes");
+  return pfo_gru_gates_bwd_launch(gates, dgi, dgh, h_rows, hm, n_touched, cap, D, d_h0, n_rep, rep_stride, d_extra, det,
+                                  (hipStream_t)stream);
+}
+extern "C" int pfo_debug_zero_rows(float* dst, const int32_t* n_rows, int32_t cap_rows, int32_t D, int32_t n_rep, int64_t rep_stride,
+                                   void* stream) {
+  PFO_REQUIRE(dst && n_rows, "null argument");
+  PFO_REQUIRE(cap_rows > 0 && D > 0 && n_rep >= 1 && rep_stride >= 0, "bad sizes");
+  return pfo_zero_rows_launch(dst, n_rows, cap_rows, D, n_rep, rep_stride, (hipStream_t)stream);
+}
+extern "C" int pfo_debug_persist(const int32_t* src, const int32_t* dst, int32_t B, const int32_t* slot, const float* upd_mem,
+                                 const uint8_t* has_msg, const float* msg_time, float* memory, float* last_update, int32_t D,
+                                 int32_t* winner, void* stream) {
+  PFO_REQUIRE(src && dst && slot && upd_mem && has_msg && msg_time && memory && last_update, "null argument");
+  PFO_REQUIRE(B > 0 && D > 0, "bad sizes");
+  return pfo_persist_launch(src, dst, B, slot, upd_mem, has_msg, msg_time, memory, last_update, D, winner, (hipStream_t)stream);
+}
+extern "C" int32_t pfo_debug_msg_store_needs_winner(int32_t B) {
+  if (B <= 0) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_msg_store_needs_winner(B) ? 1 : 0;
+}
+extern "C" int pfo_debug_msg_store(const int32_t* src, const int32_t* dst, const double* ts, const int32_t* eidx, int32_t B,
+                                   const float* memory, const float* last_update, const float* edge_feat, const float* tw,
+                                   const float* tb, int32_t D, int32_t Ef, float* msg_table, float* msg_time, uint8_t* has_msg,
+                                   int32_t* winner, void* stream) {
+  PFO_REQUIRE(src && dst && ts && eidx && memory && last_update && tw && tb && msg_table && msg_time && has_msg, "null argument");
+  PFO_REQUIRE(B > 0 && D > 0 && Ef >= 0 && (Ef == 0 || edge_feat), "bad sizes");
+  return pfo_msg_store_launch(src, dst, ts, eidx, B, memory, last_update, edge_feat, tw, tb, D, Ef, msg_table, msg_time, has_msg,
+                              winner, (hipStream_t)stream);
+}
+extern "C" int pfo_debug_observe_select(const int32_t* src, const int32_t* dst, int32_t B, const uint8_t* has_msg, int32_t* rep,
+                                        int32_t base, int32_t* slot, int32_t* touched, int32_t* n_out, void* stream) {
+  return pfo_observe_select_launch(src, dst, B, has_msg, rep, base, slot, touched, n_out, (hipStream_t)stream);
+}
+extern "C" int32_t pfo_debug_scan_sweeps(int64_t n) {
+  if (n <= 0 || n >= ((int64_t)1 << 31)) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_scan_sweeps(n);
+}
+extern "C" int pfo_debug_iscan(const int32_t* in, int64_t n, int32_t* out, int32_t* scratch, int64_t scratch_ints, void* stream) {
+  PFO_REQUIRE(n > 0, "bad size");
+  PFO_REQUIRE(scratch && scratch_ints >= n / 1024 + 16, "short scratch");
+  return pfo_iscan_launch(in, n, out, scratch, (hipStream_t)stream);
+}
+extern "C" int pfo_debug_mean(const float* src, int64_t n, float* out, void* stream) {
+  PFO_REQUIRE(src && out && n > 0, "bad arguments");
+  return pfo_mean_launch(src, n, out, (hipStream_t)stream);
+}
+extern "C" int pfo_debug_cq_backward(const float* const* gq, const float* const* Wq, int32_t n_layers, const float* tb, int32_t D,
+                                     float* const* d_bq, float* const* d_Wq, float* d_tb, float* tb_part, const float* tb_add,
+                                     const double* dtime, int32_t n_bins, float* d_tw, void* stream) {
+  PFO_REQUIRE(gq && Wq && d_bq && d_Wq && tb, "null argument");
+  PFO_REQUIRE(D > 0, "bad size");
+  PFO_REQUIRE(n_layers >= 1 && n_layers <= PFO_MAX_LAYERS, "bad layer count");
+  for (int l = 0; l < n_layers; ++l) PFO_REQUIRE(gq[l] && Wq[l] && d_bq[l] && d_Wq[l], "null layer pointer");
+  PFO_REQUIRE(tb_part || d_tb, "no place for the time-bias term");
+  PFO_REQUIRE(!dtime || n_bins >= 1, "bad bin count");
+  return pfo_cq_backward_launch(gq, Wq, n_layers, tb, D, d_bq, d_Wq, d_tb, tb_part, tb_add, dtime, n_bins, d_tw, (hipStream_t)stream);
+}
+extern "C" int64_t pfo_debug_fold_parts_scratch_doubles(int32_t n) {
+  if (n <= 0) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_fold_parts_scratch_doubles(n);
+}
+extern "C" int32_t pfo_debug_fold_parts_rows_in_flight(int32_t n_parts) {
+  if (n_parts <= 0) { pfo_set_error("%s: bad size", __func__); return -1; }
+  return pfo_fold_parts_rows_in_flight(n_parts);
+}
+extern "C" int pfo_debug_fold_parts(const double* parts, int32_t n_parts, int32_t n, float* out, int32_t accumulate, double* scratch,
+                                    int64_t scratch_doubles, int32_t* tickets, double* out64, void* stream) {
+  PFO_REQUIRE(parts && tickets && (out || out64), "null argument");
+  PFO_REQUIRE(n_parts > 0 && n > 0, "bad sizes");
+  PFO_REQUIRE(scratch && scratch_doubles >= pfo_fold_parts_scratch_doubles(n), "short scratch");
+  return pfo_fold_parts_launch(parts, n_parts, n, out, accumulate, scratch, tickets, (hipStream_t)stream, out64);
 }
