@@ -281,6 +281,37 @@ int pfo_recommend_mv_topk(const float* user_emb, const float* item_emb, const in
                           double* y_out, double* fused_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The wide form of the portfolio-aware top-k (abi 6, additive): pfo_recommend_mv_topk for candidate lists LDS cannot hold.
+ *   The first 30 arguments are pfo_recommend_mv_topk's and the contract is that function's, word for word - scores, A(u), the
+ *   portfolio rules, the y arithmetic, average-tie ranks (-0 == +0 for both keys, +-inf ordinary values, a NaN y outside A(u)),
+ *   blend, canonical order, empty slots, n_valid, a zero score as +0, the three optional diagnostic arrays - with ONE difference:
+ *   1 <= I <= PFO_RECOMMEND_MV_WIDE_MAX_ITEMS.  For I <= PFO_RECOMMEND_MV_MAX_ITEMS every output equals pfo_recommend_mv_topk's
+ *   bit for bit: scores, y, ranks and blend come from the same device functions, and a rank is an exact (half-)integer however
+ *   it is found.
+ *   The state of a user lives in `workspace` (device memory, 16-byte aligned), and the ranks are found by sorting: per user an
+ *   LSD radix sort of the admissible candidates' y keys (8 passes) and score keys (4 passes), two binary searches per candidate
+ *   and key, k reads of the fused row for the selection - O(I log I) per user, nothing counts pairs.
+ *   Workspace layout: with IP = I rounded up to 16 and R = 16 * (tiles of the slab) user rows, six arrays one after another:
+ *     y / fused f64[R, IP] (8 bytes per user and candidate), y keys u64[R, IP] twice (8 + 8), score f32[R, IP] (4),
+ *     score keys u32[R, IP] twice (4 + 4): 36 bytes per user and candidate.
+ *   pfo_recommend_mv_wide_workspace_bytes(U, I) = 36 * 16 * ceil(U / 16) * IP (host arithmetic, no device; U < 1 and I < 1 count
+ *   as 1) serves all U users in one slab.  The entry accepts any workspace_bytes >= ..._bytes(min(U, 16), I) and serves the users in
+ *   slabs of as many 16-user tiles as fit, queued in order on `stream` (two launches per slab, whatever the data); the result
+ *   does not depend on the slab size.  No allocation, no host synchronisation, no read-back.
+ *   Errors (PFO_ERR_INVALID, nothing queued): those of pfo_recommend_mv_topk; I outside the bound above; with U > 0 a null,
+ *   short or misaligned workspace.  U == 0: PFO_OK, no pointer is looked at.
+ */
+#define PFO_RECOMMEND_MV_WIDE_MAX_ITEMS PFO_RECOMMEND_MAX_ITEMS
+int64_t pfo_recommend_mv_wide_workspace_bytes(int64_t U, int32_t I);
+int pfo_recommend_mv_topk_wide(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                               int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                               const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                               int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                               const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                               int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                               double* y_out, double* fused_out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Basket top-k (abi 6, additive): the list of pfo_recommend_mv_topk taken one pick at a time, each pick joining the holdings
  * before the next is ranked, in one launch.  The arguments are pfo_recommend_mv_topk's without the three diagnostic arrays and
  * mean what they mean there: scores, admissible set A(u), portfolio P (list order, out-of-range entries left out, duplicates

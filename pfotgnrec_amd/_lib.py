@@ -15,6 +15,7 @@ _VP = C.c_void_p
 MAX_LAYERS = 4
 RECOMMEND_MAX_ITEMS = 65536     # PFO_RECOMMEND_MAX_ITEMS
 RECOMMEND_MV_MAX_ITEMS = 2048   # PFO_RECOMMEND_MV_MAX_ITEMS
+RECOMMEND_MV_WIDE_MAX_ITEMS = 65536   # PFO_RECOMMEND_MV_WIDE_MAX_ITEMS
 
 
 class TgnConfig(C.Structure):
@@ -147,6 +148,10 @@ PROTOTYPES = {
     "pfo_recommend_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                         _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
                                         C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_mv_wide_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "pfo_recommend_mv_topk_wide": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                             _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
+                                             C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "pfo_recommend_basket_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                             _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double,
                                             C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP]),

@@ -24,9 +24,12 @@
 // kernel's own (rec_next_pass hands out the members and leaves the `while (pending)` to the kernel: as the loop's condition it
 // cost the plain and the mean-variance kernel 10 to 14 VGPRs and two of them a wave of occupancy).  On the host one
 // check per argument block (rec_check_common, rec_check_mv) and one launcher (rec_launch: the NJ dispatch, the LDS attribute,
-// the launch and its check) serve the three entries.
+// the launch and its check) serve the three entries.  Behind the three kernels stands the wide form of the mean-variance one
+// (two kernels over a workspace, ranks by sorting: its own comment), which shares the opening, stage A, RecMvUser, the rec_mv_*
+// pieces and the host checks with them.
 #include "common.hpp"
 #include "mv_value.hpp"
+#include <algorithm>
 #include <type_traits>
 
 #define PFO_REC_THREADS 256
@@ -635,6 +638,283 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
+// The wide form of the portfolio-aware top-k: recommend_mv_topk_kernel's contract for lists LDS cannot hold (I up to
+// PFO_RECOMMEND_MV_WIDE_MAX_ITEMS), its state in a caller-owned workspace and its ranks found by sorting.  Two launches per slab of
+// users (the host cuts U into slabs of whole 16-user tiles that fit the workspace and hands each slab over as a call of its
+// own: every per-user pointer advanced to the slab's first user, so the kernels know nothing of slabs):
+//   recommend_mv_wide_score_kernel  grid (16-user tile, chunk of PFO_REC_CHUNK candidates).  The opening and stage A of the
+//      kernels above (rec_score_chunk: the same bits), the chunk's scores to the workspace row of every user, and y of every
+//      (user, candidate) as stage B above has it (RecMvUser, rec_mv_stock, pfo_mv_value<true>), NaN where the candidate takes no
+//      part.  The exclusion list is NOT applied here: another chunk's workgroup may still be writing the y it would hit.
+//   recommend_mv_wide_rank_kernel   one workgroup per user, after the kernel boundary.
+//      1  the exclusion list over the user's y row as NaN (rec_mv_exclude);
+//      2  the admissible candidates' keys compacted into two arrays (any order): y as an order-preserving 64-bit key with
+//         -0 folded onto +0 (rec_ordered64), the score as rec_ordered; n = |A(u)|;
+//      3  each array sorted by an LSD radix sort, 8 bits a pass (8 + 4 passes), over ping-pong buffers of the workspace: a
+//         256-bin LDS histogram, its scan, and a stable scatter 256 keys at a time - match-any by eight ballots within a
+//         wavefront (as rs_scatter_kernel, csr.hip), the wavefronts' digit counts side by side in LDS;
+//      4  per admissible candidate two binary searches in each sorted array: `less` = where its run of equal keys starts,
+//         `equal` = the run's length - exact integers however found, so pfo_mv_avg_rank / pfo_mv_blend give the bounded
+//         kernel's fused to the bit; fused replaces y in the row;
+//      5  the first k of the canonical order in k rounds: the best candidate (rec_better) that comes after the previous pick.
+//   Work per user: 12 passes over <= I keys, 4 log2 n search steps per candidate, k reads of the fused row.  Nothing counts pairs.
+// Workspace, per user of a slab and per candidate of I rounded up to 16 (PFO_RMW_BYTES: 36): y / fused f64 (8), two y-key
+// buffers u64 (8 + 8), score f32 (4), two score-key buffers u32 (4 + 4); array by array, rows of a slab side by side.
+#define PFO_RMW_BYTES 36
+
+struct RecWideWs {
+  double* y;              // [users][IP]: y, then fused
+  uint64_t* yk[2];        // [users][IP] each
+  float* sc;              // [users][IP]
+  uint32_t* sk[2];        // [users][IP] each
+  int64_t IP;             // row stride: I rounded up to 16
+};
+
+// the workspace that serves `tiles` 16-user tiles in one slab
+inline int64_t rec_wide_bytes(int64_t tiles, int I) { return tiles * PFO_REC_TILE * PFO_RMW_BYTES * pfo_align_up(I, 16); }
+
+// fp64 -> unsigned with the same order (sortable_f64 of csr.hip); -0 and +0 share a key, as == has it
+__device__ __forceinline__ uint64_t rec_ordered64(double y) {
+  uint64_t b = (uint64_t)__double_as_longlong(y);
+  if (b == 0x8000000000000000ull) b = 0ull;
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_wide_score_kernel(const RecArgs a, const RecMvArgs m, const RecWideWs w,
+                                                                                  PFO_REC_MV_TABLES) {
+  const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
+  float* __restrict__ score_out = m.score_out;
+  const int I = a.I, D = a.D;
+  constexpr int ICS = PFO_REC_CHUNK + 4;
+  __shared__ float sc[PFO_REC_TILE * ICS];                           // 33 KB
+  __shared__ int ub[PFO_REC_TILE];
+  const int tid = threadIdx.x;
+  const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
+  const int c0 = (int)blockIdx.y * PFO_REC_CHUNK, n = min(PFO_REC_CHUNK, I - c0);   // (the grid has ceil(I / chunk) chunks: n >= 1)
+  const double nan = __builtin_nan("");
+
+  float4 uf[NJ];
+  rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  unsigned pending = rec_block_table(ub, a, u0);
+  while (pending) {
+    int b;
+    const unsigned members = rec_next_pass(pending, ub, b);
+    __syncthreads();                                                 // the previous pass's scores have been read
+    rec_score_chunk<NJ>(uf, item_emb + (int64_t)b * I * D, c0, n, I, D, sc, ICS);
+    __syncthreads();
+    for (int us = 0; us < PFO_REC_TILE; ++us) {
+      if (!((members >> us) & 1u)) continue;                         // (the same for every thread; a row beyond U is no member)
+      const int64_t u = u0 + us;
+      const float* su = sc + us * ICS;
+      const RecMvUser h(m, returns, day_idx, port_idx, port_len, u);
+      for (int c = tid; c < n; c += PFO_REC_THREADS) {
+        const int g = c0 + c;
+        const float s = su[c];
+        w.sc[u * w.IP + g] = s;
+        if (score_out) score_out[u * I + g] = s;
+        const int stock = rec_mv_stock(a, cand_stock, m.n_stocks, g, h.day_ok);
+        w.y[u * w.IP + g] = stock < 0 ? nan : pfo_mv_value<true>(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + u * m.port_stride, h.plen, m.gamma);
+      }
+    }
+  }
+}
+
+// the first position of sorted key[0, n) that holds a key >= v (UPPER: > v)
+template <bool UPPER, class K>
+__device__ __forceinline__ int rec_wide_bound(const K* key, int n, K v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const K kv = key[mid];
+    if (UPPER ? kv <= v : kv < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// key[0, n) of buf[0] sorted ascending in place, buf[1] the other half of the ping-pong (BYTES passes, an even number).  All
+// threads of the workgroup; starts and ends on a barrier.  base[256], cnt[2][4][256]: LDS.
+template <int BYTES, class K>
+__device__ __forceinline__ void rec_wide_sort(K* const (&buf)[2], int n, int* base, int (*cnt)[PFO_REC_THREADS / 64][256], int* wave_tot) {
+  static_assert(BYTES % 2 == 0, "the sorted keys must end in buf[0]");
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int pass = 0; pass < BYTES; ++pass) {
+    const K* in = buf[pass & 1];
+    K* out = buf[(pass & 1) ^ 1];
+    const int shift = 8 * pass;
+    // ---- histogram of the digit (a thread is a bin from here on: 256 of each)
+    base[tid] = 0;
+#pragma unroll
+    for (int wv = 0; wv < PFO_REC_THREADS / 64; ++wv) cnt[0][wv][tid] = cnt[1][wv][tid] = 0;
+    __syncthreads();                                                 // (and the previous pass's keys are all in `in`)
+    for (int i = tid; i < n; i += PFO_REC_THREADS) atomicAdd(&base[(int)((in[i] >> shift) & 255)], 1);
+    __syncthreads();
+    // ---- exclusive scan of the 256 bins
+    const int mine = base[tid];
+    int incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int v = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += v;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int before = 0;
+#pragma unroll
+    for (int wv = 0; wv < PFO_REC_THREADS / 64; ++wv) before += wv < wave ? wave_tot[wv] : 0;
+    base[tid] = before + incl - mine;
+    __syncthreads();
+    // ---- stable scatter, 256 keys at a time: a key goes to base[digit] + the earlier keys of the step with its digit
+    K next = tid < n ? in[tid] : (K)0;
+    for (int t0 = 0, step = 0; t0 < n; t0 += PFO_REC_THREADS, ++step) {
+      const int i = t0 + tid;
+      const bool live = i < n;
+      const K key = next;
+      if (i + PFO_REC_THREADS < n) next = in[i + PFO_REC_THREADS];  // (the next step's key is under way across the barriers)
+      const int d = live ? (int)((key >> shift) & 255) : 0;
+      unsigned long long same = __ballot(live);
+#pragma unroll
+      for (int bit = 0; bit < 8; ++bit) {
+        const unsigned long long bal = __ballot(live && ((d >> bit) & 1));
+        same &= ((d >> bit) & 1) ? bal : ~bal;
+      }
+      const int rank = __popcll(same & ((1ull << lane) - 1ull));
+      int (*c)[256] = cnt[step & 1];                                 // (zero: cleared two steps ago, or above)
+      if (live && rank == 0) c[wave][d] = __popcll(same);
+      __syncthreads();                                               // and base has taken the previous step's counts
+      if (live) {
+        int off = base[d] + rank;
+#pragma unroll
+        for (int wv = 0; wv < PFO_REC_THREADS / 64; ++wv) off += wv < wave ? c[wv][d] : 0;
+        out[off] = key;
+      }
+      __syncthreads();
+      int total = 0;                                                 // bin tid moves on; nobody reads c again before it is written two steps on
+#pragma unroll
+      for (int wv = 0; wv < PFO_REC_THREADS / 64; ++wv) {
+        total += c[wv][tid];
+        c[wv][tid] = 0;
+      }
+      base[tid] += total;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_wide_rank_kernel(const RecArgs a, const RecMvArgs m, const RecWideWs w) {
+  int32_t* __restrict__ top_pos = a.top_pos;
+  float* __restrict__ top_score = a.top_score;
+  double *__restrict__ top_fused = m.top_fused, *__restrict__ y_out = m.y_out, *__restrict__ fused_out = m.fused_out;
+  const int I = a.I, k = a.k;
+  const double lam = m.lam;
+  __shared__ int base[256];
+  __shared__ int cnt[2][PFO_REC_THREADS / 64][256];
+  __shared__ int wave_tot[PFO_REC_THREADS / 64];
+  __shared__ int n_adm;
+  __shared__ double wave_f[2][PFO_REC_THREADS / 64];                 // the best (fused, position) of each wavefront, by round parity
+  __shared__ int wave_c[2][PFO_REC_THREADS / 64];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t u = blockIdx.x;                                      // (the grid is the slab's users)
+  double* yv = w.y + u * w.IP;                                       // the rows are this workgroup's alone
+  const float* su = w.sc + u * w.IP;
+  uint64_t* const yk[2] = {w.yk[0] + u * w.IP, w.yk[1] + u * w.IP};
+  uint32_t* const sk[2] = {w.sk[0] + u * w.IP, w.sk[1] + u * w.IP};
+  const double nan = __builtin_nan("");
+
+  // ---- 1: the exclusion list (every y of the row was written by the kernel before this one)
+  if (tid == 0) n_adm = 0;
+  rec_mv_exclude(yv, a, u);
+  // ---- 2: the keys of the admissible candidates, compacted
+  for (int c0 = 0; c0 < I; c0 += PFO_REC_THREADS) {
+    const int c = c0 + tid;
+    const double y = c < I ? yv[c] : nan;
+    if (c < I && y_out) y_out[u * I + c] = y;
+    const bool adm = y == y;
+    const unsigned long long bal = __ballot(adm);
+    int at = 0;
+    if (lane == 0 && bal) at = atomicAdd(&n_adm, __popcll(bal));
+    at = __shfl(at, 0, 64) + __popcll(bal & ((1ull << lane) - 1ull));
+    if (adm) {
+      yk[0][at] = rec_ordered64(y);
+      sk[0][at] = rec_ordered(su[c]);
+    }
+  }
+  __syncthreads();
+  const int n = n_adm;
+  // ---- 3: both sorted
+  rec_wide_sort<8>(yk, n, base, cnt, wave_tot);
+  rec_wide_sort<4>(sk, n, base, cnt, wave_tot);
+  // ---- 4: ranks by position in the sorted rows, blended; fused replaces y (a thread reads and writes its own candidates)
+  for (int c = tid; c < I; c += PFO_REC_THREADS) {
+    const double y = yv[c];
+    double f = nan;
+    if (y == y) {
+      const uint64_t ky = rec_ordered64(y);
+      const uint32_t ks = rec_ordered(su[c]);
+      const int ly = rec_wide_bound<false>(yk[0], n, ky), ey = rec_wide_bound<true>(yk[0], n, ky) - ly;
+      const int ls = rec_wide_bound<false>(sk[0], n, ks), es = rec_wide_bound<true>(sk[0], n, ks) - ls;
+      f = pfo_mv_blend(pfo_mv_avg_rank(ly, ey), pfo_mv_avg_rank(ls, es), lam);   // main.py:282-286
+    }
+    yv[c] = f;
+    if (fused_out) fused_out[u * I + c] = f;
+  }
+  __syncthreads();
+  // ---- 5: the first k of the canonical order, one a round: the best of those that come after the previous pick
+  double pf = 0.0;
+  int pc = -1, n_pick = 0;
+  const int rounds = min(k, n);
+  for (int rd = 0; rd < rounds; ++rd) {
+    double bf = 0.0;
+    int bc = -1;
+    for (int c = tid; c < I; c += PFO_REC_THREADS) {
+      const double f = yv[c];
+      if (!(f == f) || (pc >= 0 && !rec_better(pf, pc, f, c))) continue;
+      if (rec_better(f, c, bf, bc)) {
+        bf = f;
+        bc = c;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const double of = __shfl_xor(bf, off, 64);
+      const int oc = __shfl_xor(bc, off, 64);
+      if (oc >= 0 && rec_better(of, oc, bf, bc)) {
+        bf = of;
+        bc = oc;
+      }
+    }
+    if (lane == 0) {
+      wave_f[rd & 1][wave] = bf;
+      wave_c[rd & 1][wave] = bc;
+    }
+    __syncthreads();                                                 // (the slots of this parity are written again two rounds on)
+    bf = wave_f[rd & 1][0];
+    bc = wave_c[rd & 1][0];
+#pragma unroll
+    for (int wv = 1; wv < PFO_REC_THREADS / 64; ++wv) {
+      const double of = wave_f[rd & 1][wv];
+      const int oc = wave_c[rd & 1][wv];
+      if (oc >= 0 && rec_better(of, oc, bf, bc)) {
+        bf = of;
+        bc = oc;
+      }
+    }
+    if (bc < 0) break;                                               // nobody is left (the same for every thread)
+    if (tid == 0) {
+      const float sv = su[bc];
+      top_pos[u * k + rd] = bc;
+      top_score[u * k + rd] = sv == 0.f ? 0.f : sv;                  // a zero score is handed out as +0
+      top_fused[u * k + rd] = bf;
+    }
+    pf = bf;
+    pc = bc;
+    ++n_pick;
+  }
+  rec_mv_empty_slots(top_pos, top_score, top_fused, a.n_valid, u, k, n_pick);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host side.  The checks speak in the name of the entry that called them (`who`), as PFO_REQUIRE does with __func__.
 #define PFO_REC_REQUIRE(cond, msg) \
   do { if (!(cond)) { pfo_set_error("%s: %s", who, msg); return PFO_ERR_INVALID; } } while (0)
@@ -655,9 +935,11 @@ int rec_check_common(const char* who, const RecArgs& a, int max_items, const cha
   return PFO_OK;
 }
 
-int rec_check_mv(const char* who, const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES) {
+// (`max_items` / `items_msg`: the bounded kernels' bound unless the entry names its own)
+int rec_check_mv(const char* who, const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES, int max_items = PFO_RECOMMEND_MV_MAX_ITEMS,
+                 const char* items_msg = "I must be in [1, PFO_RECOMMEND_MV_MAX_ITEMS]") {
   const char* stride_msg = "excl_stride and port_stride must not be negative";
-  const int rc = rec_check_common(who, a, PFO_RECOMMEND_MV_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MV_MAX_ITEMS]", stride_msg);
+  const int rc = rec_check_common(who, a, max_items, items_msg, stride_msg);
   if (rc != PFO_OK) return rc;
   PFO_REC_REQUIRE(m.port_stride >= 0, stride_msg);
   PFO_REC_REQUIRE(m.n_ret >= 2 && m.n_ret <= 128, "n_ret must be in [2, 128]");
@@ -668,6 +950,14 @@ int rec_check_mv(const char* who, const RecArgs& a, const RecMvArgs& m, PFO_REC_
   PFO_REC_REQUIRE(!port_idx || m.port_stride == 0 || port_len, "port_idx without port_len");
   return PFO_OK;
 }
+
+// the wide form's workspace (U > 0): at least one tile's worth, aligned for its fp64 rows
+int rec_check_wide(const char* who, const RecArgs& a, const void* workspace, int64_t workspace_bytes) {
+  PFO_REC_REQUIRE(workspace, "null workspace");
+  PFO_REC_REQUIRE(workspace_bytes >= rec_wide_bytes(1, a.I), "workspace shorter than pfo_recommend_mv_wide_workspace_bytes(min(U, 16), I)");
+  PFO_REC_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  return PFO_OK;
+}
 #undef PFO_REC_REQUIRE
 
 constexpr size_t rec_score_bytes(int IC) { return (size_t)PFO_REC_TILE * (IC + 4) * sizeof(float); }   // sc[16][IC + 4]
@@ -675,11 +965,12 @@ constexpr size_t rec_score_bytes(int IC) { return (size_t)PFO_REC_TILE * (IC + 4
 inline int rec_mv_ic(int I) { return (int)pfo_align_up(I, 16); }
 constexpr size_t rec_mv_bytes(int IC) { return (size_t)IC * sizeof(double) + rec_score_bytes(IC); }
 
-// One workgroup per 16 users of a kernel template, in the instantiation that covers a row of a.D floats, with `shmem` bytes of
-// LDS.  `kernel_of` (PFO_REC_KERNEL) names the template: it maps std::integral_constant<int, NJ> to the instantiation.
+// One workgroup per 16 users of a kernel template (times `grid_y`: the wide form's candidate chunks), in the instantiation that
+// covers a row of a.D floats, with `shmem` bytes of LDS.  `kernel_of` (PFO_REC_KERNEL) names the template: it maps
+// std::integral_constant<int, NJ> to the instantiation.
 #define PFO_REC_KERNEL(name) [](auto nj) { return &name<decltype(nj)::value>; }
 template <class KernelOf, class... Args>
-int rec_launch(const char* who, KernelOf kernel_of, size_t shmem, void* stream, const RecArgs& a, const Args&... more) {
+int rec_launch_grid(const char* who, KernelOf kernel_of, size_t shmem, unsigned grid_y, void* stream, const RecArgs& a, const Args&... more) {
   auto launch = [&](auto nj) -> int {
     const auto kernel = kernel_of(nj);
     if (shmem > 65536) {                                             // (more than 64 KB of dynamic LDS has to be asked for, per kernel)
@@ -689,7 +980,7 @@ int rec_launch(const char* who, KernelOf kernel_of, size_t shmem, void* stream, 
         return PFO_ERR_HIP;
       }
     }
-    const dim3 grid((unsigned)pfo_ceil_div(a.U, PFO_REC_TILE)), block(PFO_REC_THREADS);
+    const dim3 grid((unsigned)pfo_ceil_div(a.U, PFO_REC_TILE), grid_y), block(PFO_REC_THREADS);
     PFO_KLAUNCH(kernel, grid, block, shmem, (hipStream_t)stream, a, more...);
     const hipError_t e = hipGetLastError();                          // (PFO_LAUNCH_CHECK, in the entry's name)
     if (e != hipSuccess) {
@@ -704,6 +995,10 @@ int rec_launch(const char* who, KernelOf kernel_of, size_t shmem, void* stream, 
   else if (nj <= 8) return launch(std::integral_constant<int, 8>());
   else if (nj <= 11) return launch(std::integral_constant<int, 11>());
   else return launch(std::integral_constant<int, 16>());
+}
+template <class KernelOf, class... Args>
+int rec_launch(const char* who, KernelOf kernel_of, size_t shmem, void* stream, const RecArgs& a, const Args&... more) {
+  return rec_launch_grid(who, kernel_of, shmem, 1u, stream, a, more...);
 }
 
 }  // namespace
@@ -756,4 +1051,64 @@ extern "C" int pfo_recommend_basket_topk(const float* user_emb, const float* ite
   if (rc != PFO_OK || U == 0) return rc;
   return rec_launch(__func__, PFO_REC_KERNEL(recommend_basket_topk_kernel), rec_mv_bytes(a.IC), stream, a, m, cand_stock, returns, day_idx,
                     port_idx, port_len);
+}
+
+extern "C" int64_t pfo_recommend_mv_wide_workspace_bytes(int64_t U, int32_t I) {
+  return rec_wide_bytes(U > 0 ? pfo_ceil_div(U, PFO_REC_TILE) : 1, I > 0 ? I : 1);
+}
+
+extern "C" int pfo_recommend_mv_topk_wide(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                          int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                          const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                          int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                          const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                          int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                          double* y_out, double* fused_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  const RecArgs a = PFO_REC_ARGS(PFO_REC_CHUNK);
+  const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
+  int rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len, PFO_RECOMMEND_MV_WIDE_MAX_ITEMS,
+                        "I must be in [1, PFO_RECOMMEND_MV_WIDE_MAX_ITEMS]");
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_wide(__func__, a, workspace, workspace_bytes);
+  if (rc != PFO_OK) return rc;
+  // slabs of as many whole tiles as the workspace holds, in stream order (which is what makes its reuse safe)
+  const int64_t tiles = pfo_ceil_div(U, PFO_REC_TILE), slab_tiles = std::min(workspace_bytes / rec_wide_bytes(1, I), tiles);
+  const int64_t IP = pfo_align_up(I, 16), rows = slab_tiles * PFO_REC_TILE * IP;
+  RecWideWs w;
+  w.IP = IP;
+  w.y = static_cast<double*>(workspace);
+  w.yk[0] = reinterpret_cast<uint64_t*>(w.y + rows);
+  w.yk[1] = w.yk[0] + rows;
+  w.sc = reinterpret_cast<float*>(w.yk[1] + rows);
+  w.sk[0] = reinterpret_cast<uint32_t*>(w.sc + rows);
+  w.sk[1] = w.sk[0] + rows;
+  for (int64_t t0 = 0; t0 < tiles; t0 += slab_tiles) {
+    const int64_t s = t0 * PFO_REC_TILE, Us = std::min(slab_tiles * PFO_REC_TILE, U - s);   // the slab: users [s, s + Us)
+    RecArgs as = a;
+    RecMvArgs ms = m;
+    as.U = Us;
+    as.user_emb += s * D;
+    if (as.user_block) as.user_block += s;
+    if (as.excl_pos) as.excl_pos += s * excl_stride;
+    if (as.excl_len) as.excl_len += s;
+    as.top_pos += s * k;
+    as.top_score += s * k;
+    if (as.n_valid) as.n_valid += s;
+    ms.top_fused += s * k;
+    if (ms.score_out) ms.score_out += s * I;
+    if (ms.y_out) ms.y_out += s * I;
+    if (ms.fused_out) ms.fused_out += s * I;
+    const int32_t* port_s = port_idx ? port_idx + s * port_stride : nullptr;
+    const int32_t* plen_s = port_len ? port_len + s : nullptr;
+    rc = rec_launch_grid(__func__, PFO_REC_KERNEL(recommend_mv_wide_score_kernel), 0, (unsigned)pfo_ceil_div(I, PFO_REC_CHUNK), stream, as,
+                         ms, w, cand_stock, returns, day_idx + s, port_s, plen_s);
+    if (rc != PFO_OK) return rc;
+    PFO_KLAUNCH(recommend_mv_wide_rank_kernel, dim3((unsigned)Us), dim3(PFO_REC_THREADS), 0, (hipStream_t)stream, as, ms, w);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+      pfo_set_error("%s: launch failed: %s", __func__, hipGetErrorString(e));
+      return PFO_ERR_HIP;
+    }
+  }
+  return PFO_OK;
 }

@@ -317,17 +317,31 @@ def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_l
     return top_pos, top_score, n_valid
 
 
+_NO_WORKSPACE = object()     # ``_recommend_mv_launch``: the symbol takes no workspace (None: it does, allocate one)
+_WIDE_WORKSPACE_CAP = 256 << 20
+
+
 def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
-                         user_block, excl_pos, excl_len, item_ok, n_blocks):
-    """The argument checks, output rows and launch that ``recommend_mv_topk`` and ``recommend_basket_topk`` share: ``symbol``
-    takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays (``diagnostics``: allocate them or pass NULL)
-    or without them (None)."""
+                         user_block, excl_pos, excl_len, item_ok, n_blocks, max_items=_lib.RECOMMEND_MV_MAX_ITEMS, workspace=_NO_WORKSPACE):
+    """The argument checks, output rows and launch that ``recommend_mv_topk``, ``recommend_mv_topk_wide`` and
+    ``recommend_basket_topk`` share: ``symbol`` takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays
+    (``diagnostics``: allocate them or pass NULL) or without them (None).  ``max_items``: the symbol's bound on I.
+    ``workspace``: for a symbol that takes (workspace, workspace_bytes) before the stream - a uint8 tensor, or None: allocated
+    (what serves all users at once, 256 MiB at the most, the minimum at the least)."""
     def dims(U, rows):
         if not isinstance(cand_stock, torch.Tensor) or cand_stock.dim() != 1 or cand_stock.dtype != torch.int32 or cand_stock.shape[0] < 1:
             raise ValueError("cand_stock must be int32 [I]")
         I = int(cand_stock.shape[0])
-        if I > _lib.RECOMMEND_MV_MAX_ITEMS:
-            raise ValueError("%d candidates, at most %d with the mean-variance rank" % (I, _lib.RECOMMEND_MV_MAX_ITEMS))
+        if I > max_items:
+            raise ValueError("%d candidates, at most %d with the mean-variance rank" % (I, max_items))
+        if workspace is not _NO_WORKSPACE and workspace is not None:
+            if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+                raise ValueError("workspace must be a contiguous uint8 tensor")
+            if workspace.device != user_emb.device:
+                raise ValueError("workspace lives on %s, the embeddings on %s" % (workspace.device, user_emb.device))
+            need = _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", min(U, 16), I)
+            if U and workspace.numel() < need:
+                raise ValueError("workspace holds %d bytes, %d users of %d candidates need at least %d" % (workspace.numel(), U, I, need))
         n_t = 1 if n_blocks is None else int(n_blocks)
         if n_t < 1 or rows != n_t * I:
             raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of %d candidates" % (rows, n_t, I))
@@ -362,10 +376,17 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
     if diagnostics is not None:
         extra = tuple(torch.empty((U, I), dtype=dt, device=dev) if diagnostics else None
                       for dt in (torch.float32, torch.float64, torch.float64))
+    ws = ()
+    if workspace is not _NO_WORKSPACE:
+        if workspace is None:
+            size = _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", U, I)
+            size = max(min(size, _WIDE_WORKSPACE_CAP), _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", min(U, 16), I))
+            workspace = torch.empty(size, dtype=torch.uint8, device=dev)
+        ws = (workspace.data_ptr(), workspace.numel())
     _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos), _lib.ptr(excl_len),
               W, _lib.ptr(item_ok), _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks, n_ret,
               _lib.ptr(day_idx.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None),
-              Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), _lib.stream_ptr())
+              Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), *ws, _lib.stream_ptr())
     return out + extra if diagnostics else out
 
 
@@ -386,6 +407,21 @@ def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_
     fused f64[U,I]), NaN in the last two where a candidate is not admissible."""
     return _recommend_mv_launch("pfo_recommend_mv_topk", bool(want_all), user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
                                 port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks)
+
+
+def recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
+                           excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, workspace=None, want_all=False):
+    """``recommend_mv_topk`` for candidate lists beyond its 2048 (``pfo_recommend_mv_topk_wide``, up to 65536): the same
+    arguments, checks and return tuple, the same results to the bit where both apply.  The state of a user lives in
+    ``workspace`` and the ranks are found by sorting, O(I log I) per user.
+
+    ``workspace``: a contiguous uint8 tensor on the embeddings' device of at least
+    ``pfo_recommend_mv_wide_workspace_bytes(min(U, 16), I)`` bytes (36 bytes per user and candidate, users in tiles of 16,
+    candidates rounded up to 16); the users are served in slabs of as many tiles as it holds, and the result does not depend on
+    its size.  None: allocated - what serves all users at once, 256 MiB at the most."""
+    return _recommend_mv_launch("pfo_recommend_mv_topk_wide", bool(want_all), user_emb, item_emb, k, cand_stock, returns, day_idx,
+                                port_idx, port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks,
+                                _lib.RECOMMEND_MV_WIDE_MAX_ITEMS, workspace)
 
 
 def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,

@@ -1,6 +1,7 @@
 """Read-only top-k recommendation behind ``TGN.recommend``: ``validate`` checks the arguments on the host alone (no device is
 asked for), ``assemble`` embeds users and candidates on the device and lets ``pfo_recommend_topk`` score and select - or, with
-a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` score, rank twice, blend and select; with ``basket`` on top
+a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` (beyond 2048 candidates ``pfo_recommend_mv_topk_wide``) score,
+rank twice, blend and select; with ``basket`` on top
 of that, ``pfo_recommend_basket_topk`` re-rank after every pick."""
 import collections
 import operator
@@ -75,8 +76,9 @@ def _pack_rows(arg, U, strict, pair_msg, int_msg, names, rows_msg, count_msg, bi
     return rows, lens
 
 
-def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
-    """The mean-variance keywords of ``TGN.recommend`` checked on the host (ValueError) -> ``MVQuery``, or None without any."""
+def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None, *, max_items=_lib.RECOMMEND_MV_MAX_ITEMS):
+    """The mean-variance keywords of ``TGN.recommend`` checked on the host (ValueError) -> ``MVQuery``, or None without any.
+    ``max_items``: the bound on I of the kernel the query will take."""
     if _is_held(portfolios) and holdings is None:
         raise ValueError('portfolios="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
     if mv is None:
@@ -92,8 +94,8 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None):
         raise ValueError("mv.upper_u is %d, the holdings ledger's %d: they number the stocks differently" % (int(mv.upper_u), holdings.upper_u))
     if len(mv.returns.shape) != 3:
         raise ValueError("mv.returns must be [n_days, n_stocks, n_ret]")
-    if I > _lib.RECOMMEND_MV_MAX_ITEMS:
-        raise ValueError("with mv, items may hold at most %d candidates (got %d)" % (_lib.RECOMMEND_MV_MAX_ITEMS, I))
+    if I > max_items:
+        raise ValueError("with mv, items may hold at most %d candidates (got %d)" % (max_items, I))
     ledger = isinstance(mv, PriceLedger)
     n_days = mv.n_days if ledger else int(mv.returns.shape[0])   # (a ledger's day_idx counts its LIVE days, 0 = oldest)
     if _is_held(portfolios):
@@ -174,7 +176,11 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
             "exclude lists %d users, users holds %d", "exclude holds ids that do not fit 32 bits")
     if n_neighbors is None:
         n_neighbors = 20 if default_neighbors is None else default_neighbors
-    mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings)
+    if basket and I > _lib.RECOMMEND_MV_MAX_ITEMS:
+        raise ValueError("with basket=True, items may hold at most %d candidates (got %d): only the plain mean-variance order has "
+                         "a form for longer lists" % (_lib.RECOMMEND_MV_MAX_ITEMS, I))
+    mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings,
+                      max_items=_lib.RECOMMEND_MV_MAX_ITEMS if basket else _lib.RECOMMEND_MV_WIDE_MAX_ITEMS)
     held = (_is_held(exclude), mvq is not None and mvq.port_idx is None)
     return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
                  held if any(held) else None, bool(basket))
@@ -273,10 +279,12 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
                  held_ports=None, user_ts=None):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
     portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held").
-    ``q.basket``: ``recommend_basket_topk`` in its place.  With a ``PriceLedger`` the kernels index its storage by ring slot:
+    ``q.basket``: ``recommend_basket_topk`` in its place; more than 2048 candidates: ``recommend_mv_topk_wide``.  With a ``PriceLedger`` the kernels index its storage by ring slot:
     day ordinals become slots, no day index at all is ``pfo_day_lookup`` over ``user_ts`` f64[U] on the device."""
-    from .functional import recommend_basket_topk, recommend_mv_topk
+    from .functional import recommend_basket_topk, recommend_mv_topk, recommend_mv_topk_wide
     topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
+    if q.I > _lib.RECOMMEND_MV_MAX_ITEMS:                             # (never the basket: validate refuses it)
+        topk = recommend_mv_topk_wide
     dev, mv = tgn.device, q.mv.src
     returns = mv.returns
     if not isinstance(returns, torch.Tensor):

@@ -1172,13 +1172,16 @@ class TGN(nn.Module):
         stock indices each user holds, packed (port_idx i32[U,W], port_len i32[U]) on host or device, or a list of per-user
         lists (entries outside the return table are ignored; they weigh on y_mv, ``exclude`` still decides what is offered);
         day_idx: an int or one per user, None: ``mv.day_of(timestamps)`` (host timestamps only); a candidate's stock row is
-        ``item - upper_u - 1``; at most 2048 candidates.  Returns (item_ids, scores, n_valid, fused f64[U,k]) - fused
+        ``item - upper_u - 1``.  Up to 2048 candidates that is the one launch; beyond, up to 65536, the same list comes from
+        ``pfo_recommend_mv_topk_wide``: ranks by sorting in a workspace of 36 bytes per user and candidate (256 MiB at the
+        most, the users served in slabs), two launches a slab.  Returns (item_ids, scores, n_valid, fused f64[U,k]) - fused
         descending, -inf in empty slots - then the embeddings as above.
 
         ``basket=True`` (needs ``mv``): the list is taken one pick at a time - pick r is ranked with the stocks of picks
         0 .. r-1 counted as held behind the user's portfolio, so two near-identical stocks no longer both make the list; one
         launch of ``pfo_recommend_basket_topk`` in place of ``pfo_recommend_mv_topk``, equal to k calls with ``k=1`` and each
         pick appended to ``portfolios`` and ``exclude``.  The same return tuple; ``fused[u, r]`` is the pick's value in round r.
+        The basket has no wide form: at most 2048 candidates.
 
         ``exclude="held"`` / ``portfolios="held"`` (either alone, or both): the rows of the holdings ledger
         (``track_holdings``) in place of the argument - one ``pfo_holdings_gather`` over the users already on the device, no
