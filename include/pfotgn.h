@@ -225,6 +225,52 @@ int pfo_eval_metrics(const float* emb, int64_t B, int32_t D, int32_t n_neg, cons
                      int32_t* top5_pos, int32_t* top5_item, double* invest_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * pfo_eval_metrics with the row ranked in a SERVED order (abi 6, additive): the mean-variance rank fusion that
+ * pfo_recommend_mv_topk serves (mode 0) or the basket rounds of pfo_recommend_basket_topk with k = 5 (mode 1), in one launch, one
+ * workgroup per interaction.  The first 23 arguments are pfo_eval_metrics's, in its order and with its meaning; then
+ *   ret_mv f64[mv_days, mv_stocks, mv_ret]: the table the ORDER is computed from (MVSampler.returns; it need not be ret_past or
+ *   ret_future, and it numbers its own days: mv_day_idx i32[B]); gamma, lambda_mv; mode: 0 the fused list, 1 the basket;
+ *   optional outputs, rows [out_row0, out_row0 + B) like the others: top5_fused f64[.,5], n_adm i32[.];
+ *   optional diagnostics for the B rows of THIS call: score_out f32[B, 1+n_neg] (every candidate), y_out f64[B, 1+n_neg] and
+ *   fused_out f64[B, 1+n_neg] (NaN outside A(b); in mode 1 fused_out is round 0's).
+ * Score: score(b,c) is pfo_eval_metrics's to the bit (the same device function), not the matrix-core path of pfo_recommend_*.
+ * Stock of candidate c: cand[b,c] - upper_u - 1.
+ * Portfolio for y: the first min(port_len[b], port_stride) entries of port_idx[b] under pfo_recommend_mv_topk's rules - the
+ *   length clamped to [0, port_stride], entries outside [0, mv_stocks) left out, duplicates kept, none left: the branch of
+ *   main.py:254.  y(b,c) = y_mv of main.py:243-271 on ret_mv[mv_day_idx[b]] in fp64, numpy's order of operations, no
+ *   contraction: the operations of pfo_recommend_mv_topk's y in its order.
+ * Admissible set A(b): the candidates whose stock lies in [0, mv_stocks) and whose y is no NaN; +-inf are ordinary values.
+ *   mv_day_idx[b] outside [0, mv_days): A(b) is empty and nothing of ret_mv is read.  n_adm = |A(b)|.
+ * Mode 0: over A(b) the average-tie ranks (scipy rankdata) of y and of the fp32 score (-0 == +0),
+ *   fused = lambda_mv * rank(y) + (1 - lambda_mv) * rank(score) (main.py:282-286); canonical order: fused descending, the LARGER
+ *   position first among equal values.  top5_pos / top5_item / top5_fused: the first min(5, n_adm) of that order, the other slots
+ *   -1 / -1 / -inf.  rank = the number of candidates in front of the positive (column 0) in that order.
+ * Mode 1: rounds r = 0 .. 4 as pfo_recommend_basket_topk states them (steps 1-5, k = 5): the pick of round r is top5_pos[r],
+ *   top5_fused[r] its fused value OF ROUND r (a row need not descend); only the picked position leaves the pool, the picked
+ *   stock joins the holdings; a NaN y sits out its round only; the list ends when nobody takes part.  n_adm is round 0's |A(b)|.
+ *   rank = the round in which the positive was picked.
+ * The positive not ranked - it is not in A(b) (both modes), or no round picked it (mode 1): rank = PFO_EVAL_RANK_NONE, all three
+ *   hits and NDCG values 0.  In mode 1 rank is therefore CENSORED at 5: it tells the place of a positive inside the basket and
+ *   nothing about one outside it; recall / NDCG@{1,3,5} need no more.
+ * hits_out / ndcg_out follow from rank as in pfo_eval_metrics.  invest_out: that function's investment stage - the same
+ *   operations in the same order - fed with this top-5 and reading ret_past / ret_future by day_idx; a row with fewer than five
+ *   picks adds what there is.
+ * Bounds: 1 <= n_neg and 1 + n_neg <= PFO_RECOMMEND_MV_MAX_ITEMS (score, y, the three pieces of y and fused of a row live in
+ *   LDS, 44 bytes per candidate, and the ranks are found by counting: about 3 (1+n_neg)^2 comparisons per row in mode 0, 10 in
+ *   mode 1); 2 <= mv_ret <= 128; mode in {0, 1}; mv_days, mv_stocks > 0; everything pfo_eval_metrics checks.
+ * Errors: all bounds are checked before any pointer is looked at (PFO_ERR_INVALID, nothing queued).  B == 0: PFO_OK.
+ */
+#define PFO_EVAL_RANK_NONE 2147483647
+int pfo_eval_metrics_mv(const float* emb, int64_t B, int32_t D, int32_t n_neg, const int32_t* cand, const int32_t* day_idx,
+                        const int32_t* port_idx, const int32_t* port_len, int32_t port_stride, const double* ret_past,
+                        const double* ret_future, int32_t n_days, int32_t n_stocks, int32_t n_ret, int32_t upper_u,
+                        int64_t out_row0, int64_t out_rows, int32_t* rank_out, float* hits_out, float* ndcg_out,
+                        int32_t* top5_pos, int32_t* top5_item, double* invest_out, const double* ret_mv, int32_t mv_days,
+                        int32_t mv_stocks, int32_t mv_ret, const int32_t* mv_day_idx, double gamma, double lambda_mv,
+                        int32_t mode, double* top5_fused, int32_t* n_adm, float* score_out, double* y_out, double* fused_out,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Read-only top-k recommendation: scores a tile of users against ONE shared candidate matrix and keeps the k best per user
  * (one launch; the U x I score matrix never reaches memory).
  *   user_emb f32[U,D]; item_emb f32[n_t*I, D]: n_t blocks of the same I candidates embedded at n_t times;

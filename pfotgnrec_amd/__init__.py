@@ -39,7 +39,7 @@ from .prices import PriceLedger  # noqa: F401
 from .memory import Memory  # noqa: F401
 from .tgn import TGN  # noqa: F401
 from .optim import FusedAdam, overlap_backward  # noqa: F401
-from .functional import bpr_loss, bpr_loss_blocks, bpr_step, time_encode, rank_metrics, eval_metrics, eval_buffers, recommend_topk, recommend_mv_topk, recommend_mv_topk_wide, recommend_basket_topk, holdings_store, holdings_gather, returns_append_day, returns_scatter_closes, day_lookup  # noqa: F401
+from .functional import bpr_loss, bpr_loss_blocks, bpr_step, time_encode, rank_metrics, eval_metrics, eval_buffers, eval_metrics_mv, eval_buffers_mv, recommend_topk, recommend_mv_topk, recommend_mv_topk_wide, recommend_basket_topk, holdings_store, holdings_gather, returns_append_day, returns_scatter_closes, day_lookup  # noqa: F401
 from .evaluation import eval_recommendation, InvestTables  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401,E402
 from . import ops  # noqa: F401,E402  (registers torch.ops.pfotgn.*)

@@ -16,6 +16,7 @@ MAX_LAYERS = 4
 RECOMMEND_MAX_ITEMS = 65536     # PFO_RECOMMEND_MAX_ITEMS
 RECOMMEND_MV_MAX_ITEMS = 2048   # PFO_RECOMMEND_MV_MAX_ITEMS
 RECOMMEND_MV_WIDE_MAX_ITEMS = 65536   # PFO_RECOMMEND_MV_WIDE_MAX_ITEMS
+EVAL_RANK_NONE = (1 << 31) - 1  # PFO_EVAL_RANK_NONE: the positive is not ranked
 
 
 class TgnConfig(C.Structure):
@@ -143,6 +144,10 @@ PROTOTYPES = {
     "pfo_rank_metrics": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "pfo_eval_metrics": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_eval_metrics_mv": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP,
+                                      _VP, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_double, C.c_double, C.c_int32, _VP, _VP, _VP, _VP,
+                                      _VP, _VP]),
     "pfo_recommend_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32,
                                      _VP, _VP, _VP, _VP]),
     "pfo_recommend_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,

@@ -17,6 +17,7 @@ from .mv_sampler import day_indices, log_returns, prices_from_time_feature
 from .rand_edge_sampler import DeviceNegativeSampler, item_availability, pack_portfolios
 
 TOPK = (1, 3, 5)
+ORDER_MODES = {"mv": 0, "basket": 1}     # ``order=`` -> ``mode`` of ``pfo_eval_metrics_mv``; "score" is ``pfo_eval_metrics``
 
 
 class InvestTables:
@@ -130,16 +131,39 @@ def _injected(negatives, k, sources, portfolios, n, n_items):
     return neg
 
 
+def check_order(order, mv, upper_u, n_items):
+    """The ``order`` / ``mv`` keywords of ``eval_recommendation`` checked on the host (ValueError), before any device work."""
+    if not isinstance(order, str) or (order != "score" and order not in ORDER_MODES):
+        raise ValueError('order must be "score", "mv" or "basket" (got %r)' % (order,))
+    if order == "score":
+        return
+    if mv is None:
+        raise ValueError('order="%s" needs mv (an MVSampler or a PriceLedger): it supplies the return table, gamma and lambda_mv' % order)
+    for name in ("returns", "upper_u", "gamma", "lambda_mv", "day_of"):
+        if not hasattr(mv, name):
+            raise ValueError("mv must carry returns, upper_u, gamma, lambda_mv and day_of (an MVSampler); %s is missing" % name)
+    if int(mv.upper_u) != int(upper_u):
+        raise ValueError("mv.upper_u is %d, upper_u %d: they number the stocks differently" % (int(mv.upper_u), int(upper_u)))
+    if 1 + n_items > _lib.RECOMMEND_MV_MAX_ITEMS:
+        raise ValueError('order="%s" ranks at most %d candidates per interaction (N_ITEMS = %d)'
+                         % (order, _lib.RECOMMEND_MV_MAX_ITEMS - 1, n_items))
+
+
 def eval_recommendation_rows(tgn, data, full_data, batch_size, n_neighbors, upper_u, period, is_test_run, *, root="./data",
-                             tables=None, map_item_id=None, negatives=None):
+                             tables=None, map_item_id=None, negatives=None, order="score", mv=None):
     """The pass of ``eval_recommendation``; returns its per-interaction rows as host arrays after ONE read-back:
-    dict(rank i32[n], recall f32[n,3], ndcg f32[n,3], top5_pos i32[n,5], top5_item i32[n,5], invest f64[n,12])."""
+    dict(rank i32[n], recall f32[n,3], ndcg f32[n,3], top5_pos i32[n,5], top5_item i32[n,5], invest f64[n,12]); under
+    ``order="mv"`` / ``"basket"`` also top5_fused f64[n,5] and n_adm i32[n], and rank is ``_lib.EVAL_RANK_NONE`` where the
+    positive is not ranked (``eval_metrics_mv``)."""
     import torch
-    from .functional import eval_buffers, eval_metrics
+    from .functional import eval_buffers, eval_buffers_mv, eval_metrics, eval_metrics_mv
+    from .recommend import mv_device_side
+    upper_u = int(upper_u)
+    N_ITEMS = len(np.unique(full_data.destinations))                               # evaluation.py:84-85
+    check_order(order, mv, upper_u, N_ITEMS)
     _lib.require_gpu(tgn.device)
     if tgn.dp_world != 1:
         raise _lib.PfoError("eval_recommendation runs on one rank (evaluation.py has no data-parallel form)")
-    upper_u = int(upper_u)
     if tables is None:
         tables = InvestTables.from_files(period, root, upper_u)
     if map_item_id is None:
@@ -148,7 +172,6 @@ def eval_recommendation_rows(tgn, data, full_data, batch_size, n_neighbors, uppe
     ret_past, ret_future = tables.device_tables(dev)
     batches = eval_batches(len(data.sources), batch_size, is_test_run)
     n_rows = batches[-1][1] if batches else 0
-    N_ITEMS = len(np.unique(full_data.destinations))                               # evaluation.py:84-85
     # whole-pass host work, once: day rows and packed portfolios (no per-interaction work inside the batch loop)
     day = torch.from_numpy(tables.day_indices(data.timestamps[:n_rows])).to(dev)
     p_idx, p_len_draw, p_len_invest = eval_portfolios(data.portfolios[:n_rows], map_item_id)
@@ -162,7 +185,11 @@ def eval_recommendation_rows(tgn, data, full_data, batch_size, n_neighbors, uppe
         # a fresh seed-2024 stream per batch (evaluation.py:88 -> utils.py:82-84), the set semantics of utils.py:96-111
         sampler = DeviceNegativeSampler(item_availability(full_data.destinations, upper_u, n_map), upper_u, dev, seed=2024)
         port_len_draw = torch.from_numpy(p_len_draw).to(dev)
-    out = eval_buffers(max(n_rows, 1), dev)
+    served = order != "score"
+    if served:
+        # the day of every interaction in mv's own numbering, once per pass on the host (a ledger's ordinals become ring slots)
+        ret_mv, mv_day = mv_device_side(mv, dev, np.asarray(mv.day_of(data.timestamps[:n_rows])).reshape(-1))
+    out = eval_buffers_mv(max(n_rows, 1), dev) if served else eval_buffers(max(n_rows, 1), dev)
     with torch.no_grad():
         tgn.eval()
         for k, (s, e) in enumerate(batches):
@@ -179,9 +206,13 @@ def eval_recommendation_rows(tgn, data, full_data, batch_size, n_neighbors, uppe
                 neg = sampler.sample(port_idx[s:e], port_len_draw[s:e], N_ITEMS, 0)
             emb, _ = tgn.embed_device(src, dst, [neg.reshape(-1)], [N_ITEMS], ts, eidx, n_neighbors)
             cand = torch.cat([dst.view(B, 1), neg.view(B, N_ITEMS)], 1)                # evaluation.py:176-178
-            eval_metrics(emb, B, N_ITEMS, cand, day[s:e], port_idx[s:e], port_len[s:e], ret_past, ret_future, upper_u,
-                         out=out, out_row0=s)
-    names = ("rank", "recall", "ndcg", "top5_pos", "top5_item", "invest")
+            if served:
+                eval_metrics_mv(emb, B, N_ITEMS, cand, day[s:e], port_idx[s:e], port_len[s:e], ret_past, ret_future, upper_u, ret_mv,
+                                mv_day[s:e], float(mv.gamma), float(mv.lambda_mv), ORDER_MODES[order], out=out, out_row0=s)
+            else:
+                eval_metrics(emb, B, N_ITEMS, cand, day[s:e], port_idx[s:e], port_len[s:e], ret_past, ret_future, upper_u,
+                             out=out, out_row0=s)
+    names = ("rank", "recall", "ndcg", "top5_pos", "top5_item", "invest", "top5_fused", "n_adm")[:len(out)]
     # one read-back: every buffer's rows as bytes of one device tensor, one copy
     flat = torch.cat([o[:n_rows].reshape(-1).view(torch.uint8) for o in out]).cpu().numpy()
     rows, off = {}, 0
@@ -194,7 +225,7 @@ def eval_recommendation_rows(tgn, data, full_data, batch_size, n_neighbors, uppe
 
 
 def eval_recommendation(tgn, data, full_data, batch_size, n_neighbors, upper_u, period, is_test_run, EVAL, *, root="./data",
-                        tables=None, map_item_id=None, negatives=None):
+                        tables=None, map_item_id=None, negatives=None, order="score", mv=None):
     """Drop-in for the reference's ``eval_recommendation`` (evaluation.py:39; the first nine arguments are its own): the
     same 30-key dict ``{EVAL}_recall_avg_1`` ... ``{EVAL}_sharpe_percent_5_``.
 
@@ -209,7 +240,22 @@ def eval_recommendation(tgn, data, full_data, batch_size, n_neighbors, upper_u, 
     ``(batch_index, sources, portfolios) -> i64[B, N_ITEMS]``, or a sequence of such arrays indexed by batch: the draw is
     injected (parity runs inject the reference's).
     Ranking ties follow the canonical order (score descending, the larger candidate position first, the
-    positive last among its ties) where the reference's ``np.argsort(scores)[::-1]`` is platform-dependent."""
+    positive last among its ties) where the reference's ``np.argsort(scores)[::-1]`` is platform-dependent.
+
+    ``order``: which order of an interaction's candidates is evaluated.  "score" (default): the dot-product score alone, the
+    reference's - today's path, call for call.  "mv": the order ``TGN.recommend(mv=...)`` serves, the rank fusion of
+    main.py:243-289; "basket": the order ``TGN.recommend(mv=..., basket=True)`` serves, re-ranked after each of five picks.  Both
+    need ``mv`` - an ``MVSampler``, an object that carries its attributes, or a ``PriceLedger``: it supplies the return table,
+    ``gamma`` and ``lambda_mv``, its ``day_of(timestamps)`` the day of every interaction (once per pass, on the host), and its
+    ``upper_u`` must be this call's.  The portfolio the order is computed against is the one the investment metrics use, so a
+    portfolio with a '' counts as empty on both sides.  A positive that the order does not rank - its stock outside mv's table,
+    a constant price series, no day, or under "basket" not among the five picks - is a miss at every k; the same 30 keys.
+    Which table ``mv`` was built from is the caller's choice and decides what the out-of-sample columns mean: main.py:88 trains
+    with a sampler built from ``time_feature_future``, and an order computed from that table has already seen the window the
+    ``_``-suffixed (out-of-sample) keys are measured on - they are then in-sample figures of the ranking, whatever their name.
+    Build ``mv`` from ``time_feature_past`` for an out-of-sample reading.
+    ValueError before any device work: an unknown ``order``, "mv" / "basket" without ``mv``, ``mv.upper_u != upper_u``, more
+    than 2047 candidates (``N_ITEMS``) under "mv" / "basket"."""
     rows = eval_recommendation_rows(tgn, data, full_data, batch_size, n_neighbors, upper_u, period, is_test_run, root=root,
-                                    tables=tables, map_item_id=map_item_id, negatives=negatives)
+                                    tables=tables, map_item_id=map_item_id, negatives=negatives, order=order, mv=mv)
     return eval_result_dict(EVAL, rows["rank"], rows["invest"])

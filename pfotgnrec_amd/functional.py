@@ -231,6 +231,72 @@ def eval_metrics(emb, batch, n_neg, cand, day_idx, port_idx, port_len, ret_past,
     return tuple(o[out_row0:out_row0 + batch] for o in out)
 
 
+def eval_buffers_mv(rows, device):
+    """Preallocated outputs of ``eval_metrics_mv`` for ``rows`` interactions: the six of ``eval_buffers`` followed by
+    (top5_fused f64[rows,5], n_adm i32[rows])."""
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+    return eval_buffers(rows, device) + (e((rows, 5), torch.float64), e(rows, torch.int32))
+
+
+def eval_metrics_mv(emb, batch, n_neg, cand, day_idx, port_idx, port_len, ret_past, ret_future, upper_u, returns_mv, mv_day_idx, gamma,
+                    lambda_mv, mode, out=None, out_row0=0, want_all=False):
+    """``eval_metrics`` with the row ranked in a served order, in one launch (``pfo_eval_metrics_mv``): ``mode`` 0 the
+    mean-variance rank fusion ``recommend_mv_topk`` serves, 1 the basket rounds of ``recommend_basket_topk`` with k = 5.
+
+    The first ten arguments are ``eval_metrics``'s and the score is that kernel's to the bit.  returns_mv f64[mv_days, mv_stocks,
+    mv_ret] (``MVSampler.returns``): the table the ORDER is computed from, with its own day numbering mv_day_idx i32[B]; the
+    portfolio rows and the candidates' stocks (node id - upper_u - 1) are the ones the investment stage uses.  Over the admissible
+    candidates (stock inside the table, y no NaN; none for a day outside it): fused = lambda_mv * rank(y_mv) + (1 - lambda_mv) *
+    rank(score), average-tie ranks; fused descending, the larger position first among equal values.
+
+    Returns the six rows of ``eval_metrics`` - with top5 and invest of THIS order, and rank = the positive's place in it, or
+    ``_lib.EVAL_RANK_NONE`` when it is not admissible or (mode 1) not among the five picks: recall and NDCG are 0 then - followed by
+    (top5_fused f64[B,5], n_adm i32[B]); empty slots -1 / -1 / -inf.  ``out``: ``eval_buffers_mv``.  ``want_all`` adds (score
+    f32[B,1+n_neg], y f64[B,1+n_neg], fused f64[B,1+n_neg]), NaN in the last two where a candidate is not admissible (mode 1:
+    round 0's)."""
+    import operator
+    if not isinstance(emb, torch.Tensor) or emb.dim() != 2:
+        raise ValueError("emb must be a 2-D tensor")
+    try:
+        batch, n_neg, mode = operator.index(batch), operator.index(n_neg), operator.index(mode)
+    except TypeError:
+        raise ValueError("batch, n_neg and mode must be integers") from None
+    if mode not in (0, 1):
+        raise ValueError("mode must be 0 (the fused list) or 1 (the basket), got %d" % mode)
+    if n_neg < 1 or 1 + n_neg > _lib.RECOMMEND_MV_MAX_ITEMS:
+        raise ValueError("1 + n_neg must be in [2, %d] under a mean-variance order (got %d)" % (_lib.RECOMMEND_MV_MAX_ITEMS, 1 + n_neg))
+    if not isinstance(returns_mv, torch.Tensor) or returns_mv.dim() != 3 or returns_mv.dtype != torch.float64 or 0 in returns_mv.shape:
+        raise ValueError("returns_mv must be a float64 tensor [mv_days, mv_stocks, mv_ret]")
+    if not 2 <= returns_mv.shape[2] <= 128:
+        raise ValueError("mv_ret must be in [2, 128] (got %d)" % returns_mv.shape[2])
+    if not isinstance(mv_day_idx, torch.Tensor) or tuple(mv_day_idx.shape) != (batch,) or mv_day_idx.dtype != torch.int32:
+        raise ValueError("mv_day_idx must be int32 [B]")
+    n_days, n_stocks, n_ret = ret_past.shape
+    if tuple(ret_future.shape) != (n_days, n_stocks, n_ret):
+        raise ValueError("ret_past and ret_future differ in shape")
+    if emb.shape[0] != batch * (2 + n_neg) or tuple(cand.shape) != (batch, 1 + n_neg):
+        raise ValueError("emb must hold batch * (2 + n_neg) rows and cand batch x (1 + n_neg) ids")
+    _lib.require_gpu(emb.device)
+    for t in (returns_mv, mv_day_idx):
+        if t.device != emb.device:
+            raise ValueError("all tensors must live on %s" % emb.device)
+    emb = emb.contiguous()
+    D = emb.shape[1]
+    if out is None:
+        out, out_row0 = eval_buffers_mv(batch, emb.device), 0
+    W = port_idx.shape[1] if port_idx is not None and port_idx.dim() == 2 else 0
+    extra = tuple(torch.empty((batch, 1 + n_neg), dtype=dt, device=emb.device) if want_all else None
+                  for dt in (torch.float32, torch.float64, torch.float64))
+    mv_days, mv_stocks, mv_ret = (int(v) for v in returns_mv.shape)
+    _lib.call("pfo_eval_metrics_mv", emb.data_ptr(), batch, D, n_neg, _lib.ptr(cand.contiguous()), _lib.ptr(day_idx.contiguous()),
+              _lib.ptr(port_idx.contiguous() if W else None), _lib.ptr(port_len.contiguous()), W, _lib.ptr(ret_past), _lib.ptr(ret_future),
+              n_days, n_stocks, n_ret, int(upper_u), int(out_row0), out[0].shape[0], *[o.data_ptr() for o in out[:6]],
+              returns_mv.contiguous().data_ptr(), mv_days, mv_stocks, mv_ret, _lib.ptr(mv_day_idx.contiguous()), float(gamma),
+              float(lambda_mv), mode, out[6].data_ptr(), out[7].data_ptr(), *(_lib.ptr(t) for t in extra), _lib.stream_ptr())
+    rows = tuple(o[out_row0:out_row0 + batch] for o in out)
+    return rows + extra if want_all else rows
+
+
 def _recommend_check(user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, also=()):
     """The argument checks the three top-k forms share.  ``dims(U, rows)`` is the caller's part: it checks what only that form
     takes and returns ``(I, n_t)``; ``also``: its tensors, for the device check.  Returns the tensors as the library takes them

@@ -186,16 +186,36 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
                  held if any(held) else None, bool(basket))
 
 
+def _to_dev(dev, a, dtype):
+    if isinstance(a, torch.Tensor):
+        return a.to(device=dev, dtype=dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(a).astype(str(dtype).replace("torch.", ""), copy=False)).to(dev)
+
+
+def mv_device_side(mv, dev, day_idx, user_ts=None):
+    """What the kernels read of a mean-variance side ``mv`` (an ``MVSampler``, an object that carries its attributes, or a
+    ``PriceLedger``) on ``dev``: (returns f64[n_days, n_stocks, n_ret], day i32[n]).  ``day_idx``: what ``mv.day_of`` returns
+    (host array or tensor).  A ledger's kernels index its whole storage - ``day_cap`` x ``stock_cap`` - by ring slot: its day
+    ordinals become slots, and with ``day_idx`` None the day is ``pfo_day_lookup`` over ``user_ts`` f64[n] on the device.
+    The one place this conversion is written: ``TGN.recommend`` and ``eval_recommendation`` both come here."""
+    returns = mv.returns
+    if not isinstance(returns, torch.Tensor):
+        returns = torch.from_numpy(np.ascontiguousarray(returns, dtype=np.float64))
+    returns = returns.to(device=dev, dtype=torch.float64)
+    if isinstance(mv, PriceLedger):
+        day = mv.lookup(user_ts.contiguous()) if day_idx is None else _to_dev(dev, mv.slots_of(day_idx), torch.int32)
+    else:
+        day = _to_dev(dev, day_idx, torch.int32)
+    return returns, day
+
+
 def assemble(tgn, q, return_embeddings=False):
     """The device side of ``TGN.recommend`` for a validated query: every (item, distinct timestamp) pair is embedded once (the
     grid of ``TGN._dedup_roots``), users and grid go through ``TGN._embed_readonly``, ``recommend_topk`` scores and selects."""
     from .functional import recommend_topk
     dev, k, U, I = tgn.device, q.k, q.U, q.I
 
-    def to_dev(a, dtype):
-        if isinstance(a, torch.Tensor):
-            return a.to(device=dev, dtype=dtype).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a).astype(str(dtype).replace("torch.", ""), copy=False)).to(dev)
+    to_dev = lambda a, dtype: _to_dev(dev, a, dtype)
 
     with torch.no_grad():
         users_d = to_dev(q.users if q.users_h is None else q.users_h, torch.int32)
@@ -286,15 +306,8 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
     if q.I > _lib.RECOMMEND_MV_MAX_ITEMS:                             # (never the basket: validate refuses it)
         topk = recommend_mv_topk_wide
     dev, mv = tgn.device, q.mv.src
-    returns = mv.returns
-    if not isinstance(returns, torch.Tensor):
-        returns = torch.from_numpy(np.ascontiguousarray(returns, dtype=np.float64))
-    returns = returns.to(device=dev, dtype=torch.float64)
+    returns, day = mv_device_side(mv, dev, q.mv.day_idx, user_ts)
     cand_stock = (items_d - (int(mv.upper_u) + 1)).contiguous()
-    if isinstance(mv, PriceLedger):
-        day = mv.lookup(user_ts.contiguous()) if q.mv.day_idx is None else to_dev(mv.slots_of(q.mv.day_idx), torch.int32)
-    else:
-        day = to_dev(q.mv.day_idx, torch.int32)
     if held_ports is not None:
         port_idx, port_len = held_ports
     else:
