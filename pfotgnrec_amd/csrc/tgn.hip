@@ -12,7 +12,6 @@
 #include "attn.hpp"
 #include "memory.hpp"
 #include <algorithm>
-#include <functional>
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -67,7 +66,7 @@ struct Ws {
   size_t zero_bytes, mark_bytes;
   float* pz; size_t pz_bytes;
   bool pz_in_cache;            // pz lives in the caller's parameter cache, which the caller zeroed once (no per-build memset)
-  int64_t bytes;
+  int64_t bytes, cache_bytes;   // of the workspace / of the parameter cache (carve)
 };
 
 struct Dims {
@@ -96,169 +95,136 @@ T* take(char*& p, int64_t count) {
   return r;
 }
 
-Ws carve(const pfo_tgn_config* c, void* base) {
+// Two cursors: the workspace, and the parameter cache (pfo_tgn_state.pcache).  Every buffer that depends on the parameters alone
+// (par) is taken from the cache when there is one - same sizes as in the workspace, which keeps its own, then unused, copies.
+struct Carver {
+  char *p, *q;
+  bool cached;
+  template <typename T> T* ws(int64_t count) { return take<T>(p, count); }
+  template <typename T> T* par(int64_t count) { T* r = take<T>(p, count); return cached ? take<T>(q, count) : r; }
+};
+
+// layer l's part of the workspace (and of the parameter cache)
+void carve_layer(Carver& k, const Dims& d, int l, int64_t Km, Ws& w) {
+  const int64_t N = d.ncap[l], HCp = (int64_t)d.H * d.Cp, HCpD = HCp * d.D, DD = (int64_t)d.D * d.D, ED = (int64_t)d.E * d.D;
+  LayerWs& lw = w.layer[l];
+  lw.cq = k.par<float>(d.E);     lw.W1oT = k.par<float>(ED);
+  lw.dWqk = k.ws<float>(HCpD);   lw.gqk = k.ws<float>(HCp);
+  lw.dW1ovT = k.ws<float>(HCpD); lw.dW1oT = k.ws<float>(ED);    lw.gq = k.ws<float>(d.E);
+  lw.iWqk = k.par<char>(pfo_bimg_bytes(HCp, d.D));   lw.iWqkT = k.par<char>(pfo_bimg_bytes(d.D, HCp));
+  lw.iW1ovT = k.par<char>(pfo_bimg_bytes(HCp, d.D)); lw.iW1ov = k.par<char>(pfo_bimg_bytes(d.D, HCp));
+  lw.iW1b = k.par<char>(pfo_bimg_bytes(d.D, d.D));   lw.iW1bT = k.par<char>(pfo_bimg_bytes(d.D, d.D));
+  lw.iW2 = k.par<char>(pfo_bimg_bytes(d.D, d.D));    lw.iW2T = k.par<char>(pfo_bimg_bytes(d.D, d.D));
+  lw.QK = l > 1 ? k.ws<float>(N * HCp) : nullptr;      // layer 1 reads its rows from the touched-node table QX
+  lw.attw = k.ws<float>(N * d.H * Km);
+  lw.inv = k.ws<uint8_t>(N);
+  lw.ctx = k.ws<float>(N * HCp);
+  lw.h1 = k.ws<float>(N * d.D);
+  if (l < d.L) w.dH[l] = k.ws<float>(N * d.D);
+  if (l < 2) return;
+  lw.dQK = k.ws<float>(N * HCp);
+  lw.T1 = k.par<float>(HCpD);      lw.tq = k.par<float>(HCp);
+  lw.Wqk_f = k.par<float>(HCpD);   lw.cqk_f = k.par<float>(HCp);
+  lw.W1ovT_f = k.par<float>(HCpD); lw.W1b_f = k.par<float>(DD);   lw.b1_f = k.par<float>(d.D);
+  lw.dT1 = k.ws<float>(HCpD);
+  lw.dWqk_f = k.ws<float>(HCpD);   lw.gqk_f = k.ws<float>(HCp);
+  lw.dW1ovT_f = k.ws<float>(HCpD); lw.dW1b_f = k.ws<float>(DD);   lw.db1_f = k.ws<float>(d.D);
+  lw.fold_slabs = k.ws<float>((2 * d.H + 2) * DD);
+  lw.fold_vslabs = k.ws<float>((int64_t)(d.H + 2) * d.D);
+}
+
+// (`cached` and not `cache != nullptr`: the size queries carve from null bases)
+Ws carve(const pfo_tgn_config* c, void* base, void* cache = nullptr, bool cached = false) {
   const Dims d = dims_of(c);
   Ws w;
   memset(&w, 0, sizeof(w));
-  char* p = reinterpret_cast<char*>(base);
+  Carver k = {reinterpret_cast<char*>(base), reinterpret_cast<char*>(cache), cached};
+  char*& p = k.p;
   const int64_t Km = c->max_neighbors;
   for (int l = 0; l <= d.L; ++l) {
-    w.nodes[l] = take<int32_t>(p, d.ncap[l]);
+    w.nodes[l] = k.ws<int32_t>(d.ncap[l]);
     if (l >= 1) {
-      w.ts[l] = take<double>(p, d.ncap[l]);
-      w.eidx[l] = take<int32_t>(p, d.ncap[l] * Km);
-      w.dt[l] = take<float>(p, d.ncap[l] * Km);
+      w.ts[l] = k.ws<double>(d.ncap[l]);
+      w.eidx[l] = k.ws<int32_t>(d.ncap[l] * Km);
+      w.dt[l] = k.ws<float>(d.ncap[l] * Km);
     }
   }
   // one memset per step clears [zero | tickets | dtime]; a composite build clears pz = [64 floats | Wqk, W1ovT, cqk of every
-  // layer] (padding rows / columns of the composites must be zero; with a parameter cache pz lives there: pcache_bind)
-  w.zero = take<float>(p, 64);
-  w.tickets = take<int32_t>(p, 64);
-  w.dtime = take<double>(p, (int64_t)pfo_attn_bwd_max_parts() * 2 * d.D);      // time-encoder gradient bins, also cleared per step
+  // layer] (padding rows / columns of the composites must be zero; with a parameter cache pz lives there)
+  w.zero = k.ws<float>(64);
+  w.tickets = k.ws<int32_t>(64);
+  w.dtime = k.ws<double>((int64_t)pfo_attn_bwd_max_parts() * 2 * d.D);      // time-encoder gradient bins, also cleared per step
   w.zero_bytes = (size_t)(p - reinterpret_cast<char*>(w.zero));
-  w.pz = take<float>(p, 64);
+  w.pz = k.par<float>(64);
   for (int l = 1; l <= d.L; ++l) {
     LayerWs& lw = w.layer[l];
-    lw.Wqk = take<float>(p, (int64_t)d.H * d.Cp * d.D);
-    lw.W1ovT = take<float>(p, (int64_t)d.H * d.Cp * d.D);
+    lw.Wqk = k.par<float>((int64_t)d.H * d.Cp * d.D);
+    lw.W1ovT = k.par<float>((int64_t)d.H * d.Cp * d.D);
     // layer 1: cqk is the head of the bias of the stacked [Wqk ; W1[:, E:]] projection; its tail (D floats) stays zero
-    lw.cqk = take<float>(p, (int64_t)d.H * d.Cp + (l == 1 ? d.D : 0));
+    lw.cqk = k.par<float>((int64_t)d.H * d.Cp + (l == 1 ? d.D : 0));
   }
   w.l1_bias = w.layer[1].cqk;
-  w.pz_bytes = (size_t)(p - reinterpret_cast<char*>(w.pz));
-  w.cosb = take<float>(p, d.D);
-  w.tb_part = take<float>(p, d.D);
+  w.pz_bytes = (size_t)((cached ? k.q : p) - reinterpret_cast<char*>(w.pz));
+  w.pz_in_cache = cached;
+  w.cosb = k.par<float>(d.D);
+  w.tb_part = k.ws<float>(d.D);
   {
     const int WQ = d.H * d.Cp + d.D;
     // one memset per step clears [touched-node flags | block flags of the one-pass compaction]
-    w.mark = take<int32_t>(p, c->n_nodes);
-    w.scan = take<int32_t>(p, pfo_compact_scratch_ints(c->n_nodes));
+    w.mark = k.ws<int32_t>(c->n_nodes);
+    w.scan = k.ws<int32_t>(pfo_compact_scratch_ints(c->n_nodes));
     w.mark_bytes = (size_t)(p - reinterpret_cast<char*>(w.mark));
-    w.slot = take<int32_t>(p, c->n_nodes);
-    w.touched = take<int32_t>(p, d.capP);
-    w.n_touched = take<int32_t>(p, 64);
+    w.slot = k.ws<int32_t>(c->n_nodes);
+    w.touched = k.ws<int32_t>(d.capP);
+    w.n_touched = k.ws<int32_t>(64);
     w.n_core = w.n_touched + 1;
-    w.idx0 = take<int32_t>(p, d.ncap[0]);
-    w.h0_tab = take<float>(p, d.capP * d.D);
-    w.QX = take<float>(p, d.capP * WQ);
-    w.Dq = take<float>(p, d.capP * WQ);
-    w.dx_tab = take<float>(p, d.capP * d.D);
-    w.iQX = take<char>(p, pfo_bimg_bytes(WQ, d.D));
-    w.seg_ptr = take<int32_t>(p, d.capP + 1);
-    w.seg_cur = take<int32_t>(p, d.capP + 1);
-    w.seg_tmp = take<int32_t>(p, d.ncap[1]);
-    w.seg_mem = take<int32_t>(p, d.ncap[1]);
-    w.seg_of = take<int32_t>(p, pfo_seg_of_ints(d.ncap[1]));
-    w.seg_scratch = take<int32_t>(p, pfo_seg_scratch_ints((int)d.capP));
-    w.cnt1 = take<int32_t>(p, d.ncap[1]);
-    w.dqk_live = take<uint8_t>(p, d.ncap[1]);
+    w.idx0 = k.ws<int32_t>(d.ncap[0]);
+    w.h0_tab = k.ws<float>(d.capP * d.D);
+    w.QX = k.ws<float>(d.capP * WQ);
+    w.Dq = k.ws<float>(d.capP * WQ);
+    w.dx_tab = k.ws<float>(d.capP * d.D);
+    w.iQX = k.par<char>(pfo_bimg_bytes(WQ, d.D));
+    w.seg_ptr = k.ws<int32_t>(d.capP + 1);
+    w.seg_cur = k.ws<int32_t>(d.capP + 1);
+    w.seg_tmp = k.ws<int32_t>(d.ncap[1]);
+    w.seg_mem = k.ws<int32_t>(d.ncap[1]);
+    w.seg_of = k.ws<int32_t>(pfo_seg_of_ints(d.ncap[1]));
+    w.seg_scratch = k.ws<int32_t>(pfo_seg_scratch_ints((int)d.capP));
+    w.cnt1 = k.ws<int32_t>(d.ncap[1]);
+    w.dqk_live = k.ws<uint8_t>(d.ncap[1]);
   }
   if (c->use_memory) {
-    w.winner = take<int32_t>(p, c->n_nodes);
-    w.gi = take<float>(p, d.capP * 3 * d.D);
-    w.gh = take<float>(p, d.capP * 3 * d.D);
-    w.gates = take<float>(p, d.capP * 4 * d.D);
-    w.upd_mem = take<float>(p, d.capP * d.D);
-    w.d_h0 = take<float>(p, PFO_GRAD_REPLICAS * d.capP * d.D);     // one replica per XCD (attn.hip, DMODE 1)
-    w.msg_rows = take<float>(p, d.capP * d.M);
-    w.h_rows = take<float>(p, d.capP * d.D);
-    w.hm = take<uint8_t>(p, d.capP);
-    w.iWih = take<char>(p, pfo_gru_img_bytes(d.D, d.M));
-    w.iWhh = take<char>(p, pfo_gru_img_bytes(d.D, d.D));
+    w.winner = k.ws<int32_t>(c->n_nodes);
+    w.gi = k.ws<float>(d.capP * 3 * d.D);
+    w.gh = k.ws<float>(d.capP * 3 * d.D);
+    w.gates = k.ws<float>(d.capP * 4 * d.D);
+    w.upd_mem = k.ws<float>(d.capP * d.D);
+    w.d_h0 = k.ws<float>(PFO_GRAD_REPLICAS * d.capP * d.D);     // one replica per XCD (attn.hip, DMODE 1)
+    w.msg_rows = k.ws<float>(d.capP * d.M);
+    w.h_rows = k.ws<float>(d.capP * d.D);
+    w.hm = k.ws<uint8_t>(d.capP);
+    w.iWih = k.par<char>(pfo_gru_img_bytes(d.D, d.M));
+    w.iWhh = k.par<char>(pfo_gru_img_bytes(d.D, d.D));
   }
-  for (int l = 1; l <= d.L; ++l) {
-    const int64_t N = d.ncap[l];
-    LayerWs& lw = w.layer[l];
-    lw.cq = take<float>(p, d.E);
-    lw.W1oT = take<float>(p, (int64_t)d.E * d.D);
-    lw.dWqk = take<float>(p, (int64_t)d.H * d.Cp * d.D);
-    lw.gqk = take<float>(p, (int64_t)d.H * d.Cp);
-    lw.dW1ovT = take<float>(p, (int64_t)d.H * d.Cp * d.D);
-    lw.dW1oT = take<float>(p, (int64_t)d.E * d.D);
-    lw.gq = take<float>(p, d.E);
-    {
-      const int HCp = d.H * d.Cp;
-      lw.iWqk = take<char>(p, pfo_bimg_bytes(HCp, d.D));   lw.iWqkT = take<char>(p, pfo_bimg_bytes(d.D, HCp));
-      lw.iW1ovT = take<char>(p, pfo_bimg_bytes(HCp, d.D)); lw.iW1ov = take<char>(p, pfo_bimg_bytes(d.D, HCp));
-      lw.iW1b = take<char>(p, pfo_bimg_bytes(d.D, d.D));   lw.iW1bT = take<char>(p, pfo_bimg_bytes(d.D, d.D));
-      lw.iW2 = take<char>(p, pfo_bimg_bytes(d.D, d.D));    lw.iW2T = take<char>(p, pfo_bimg_bytes(d.D, d.D));
-    }
-    lw.QK = l > 1 ? take<float>(p, N * d.H * d.Cp) : nullptr;      // layer 1 reads its rows from the touched-node table QX
-    lw.attw = take<float>(p, N * d.H * Km);
-    lw.inv = take<uint8_t>(p, N);
-    lw.ctx = take<float>(p, N * d.H * d.Cp);
-    lw.h1 = take<float>(p, N * d.D);
-    if (l < d.L) w.dH[l] = take<float>(p, N * d.D);
-    if (l >= 2) {
-      lw.dQK = take<float>(p, N * d.H * d.Cp);
-      const int64_t HCpD = (int64_t)d.H * d.Cp * d.D, HCp = (int64_t)d.H * d.Cp, DD = (int64_t)d.D * d.D;
-      lw.T1 = take<float>(p, HCpD);      lw.tq = take<float>(p, HCp);
-      lw.Wqk_f = take<float>(p, HCpD);   lw.cqk_f = take<float>(p, HCp);
-      lw.W1ovT_f = take<float>(p, HCpD); lw.W1b_f = take<float>(p, DD);   lw.b1_f = take<float>(p, d.D);
-      lw.dT1 = take<float>(p, HCpD);
-      lw.dWqk_f = take<float>(p, HCpD);  lw.gqk_f = take<float>(p, HCp);
-      lw.dW1ovT_f = take<float>(p, HCpD); lw.dW1b_f = take<float>(p, DD); lw.db1_f = take<float>(p, d.D);
-      lw.fold_slabs = take<float>(p, (2 * d.H + 2) * DD);
-      lw.fold_vslabs = take<float>(p, (int64_t)(d.H + 2) * d.D);
-    }
-  }
+  for (int l = 1; l <= d.L; ++l) carve_layer(k, d, l, Km, w);
   const int64_t N1 = d.ncap[1];
-  w.dh1 = take<float>(p, N1 * d.D);
-  w.dctx = take<float>(p, N1 * d.H * d.Cp);
-  w.dQK = take<float>(p, N1 * d.H * d.Cp);
+  w.dh1 = k.ws<float>(N1 * d.D);
+  w.dctx = k.ws<float>(N1 * d.H * d.Cp);
+  w.dQK = k.ws<float>(N1 * d.H * d.Cp);
   w.slab_floats = SLAB_FLOATS;
-  w.slabs = take<float>(p, w.slab_floats);
-  w.slabs2 = take<float>(p, w.slab_floats);
-  w.slabs3 = take<float>(p, w.slab_floats);
-  w.fold_scratch = take<double>(p, pfo_fold_parts_scratch_doubles(2 * d.D));
+  w.slabs = k.ws<float>(w.slab_floats);
+  w.slabs2 = k.ws<float>(w.slab_floats);
+  w.slabs3 = k.ws<float>(w.slab_floats);
+  w.fold_scratch = k.ws<double>(pfo_fold_parts_scratch_doubles(2 * d.D));
   {
     // deterministic mode: one slab row of time-encoder partials per attention-backward workgroup, all layers
     int64_t rows = 0;
     for (int l = 1; l <= d.L; ++l) rows += pfo_attn_bwd_det_parts(d.ncap[l]);
-    w.dtime_slab = take<double>(p, rows * 2 * d.D);
+    w.dtime_slab = k.ws<double>(rows * 2 * d.D);
   }
   w.bytes = p - reinterpret_cast<char*>(base);
+  w.cache_bytes = k.q - reinterpret_cast<char*>(cache);
   return w;
-}
-
-// The parameter cache (pfo_tgn_state.pcache): every buffer of `w` that depends on the parameters alone is re-pointed into
-// `base` (same sizes as in the workspace, which keeps its own - then unused - copies).  Returns the cache's size.
-int64_t pcache_bind(const pfo_tgn_config* c, void* base, Ws& w) {
-  const Dims d = dims_of(c);
-  char* p = reinterpret_cast<char*>(base);
-  const int HCp = d.H * d.Cp, WQ = HCp + d.D;
-  const int64_t HCpD = (int64_t)HCp * d.D, DD = (int64_t)d.D * d.D;
-  w.pz = take<float>(p, 64);
-  for (int l = 1; l <= d.L; ++l) {
-    LayerWs& lw = w.layer[l];
-    lw.Wqk = take<float>(p, HCpD);
-    lw.W1ovT = take<float>(p, HCpD);
-    lw.cqk = take<float>(p, (int64_t)HCp + (l == 1 ? d.D : 0));
-  }
-  w.l1_bias = w.layer[1].cqk;
-  w.pz_bytes = (size_t)(p - reinterpret_cast<char*>(w.pz));
-  w.pz_in_cache = true;
-  w.cosb = take<float>(p, d.D);
-  w.iQX = take<char>(p, pfo_bimg_bytes(WQ, d.D));
-  if (c->use_memory) {
-    w.iWih = take<char>(p, pfo_gru_img_bytes(d.D, d.M));
-    w.iWhh = take<char>(p, pfo_gru_img_bytes(d.D, d.D));
-  }
-  for (int l = 1; l <= d.L; ++l) {
-    LayerWs& lw = w.layer[l];
-    lw.cq = take<float>(p, d.E);
-    lw.W1oT = take<float>(p, (int64_t)d.E * d.D);
-    lw.iWqk = take<char>(p, pfo_bimg_bytes(HCp, d.D));   lw.iWqkT = take<char>(p, pfo_bimg_bytes(d.D, HCp));
-    lw.iW1ovT = take<char>(p, pfo_bimg_bytes(HCp, d.D)); lw.iW1ov = take<char>(p, pfo_bimg_bytes(d.D, HCp));
-    lw.iW1b = take<char>(p, pfo_bimg_bytes(d.D, d.D));   lw.iW1bT = take<char>(p, pfo_bimg_bytes(d.D, d.D));
-    lw.iW2 = take<char>(p, pfo_bimg_bytes(d.D, d.D));    lw.iW2T = take<char>(p, pfo_bimg_bytes(d.D, d.D));
-    if (l >= 2) {
-      lw.T1 = take<float>(p, HCpD);      lw.tq = take<float>(p, HCp);
-      lw.Wqk_f = take<float>(p, HCpD);   lw.cqk_f = take<float>(p, HCp);
-      lw.W1ovT_f = take<float>(p, HCpD); lw.W1b_f = take<float>(p, DD);   lw.b1_f = take<float>(p, d.D);
-    }
-  }
-  return (int64_t)(p - reinterpret_cast<char*>(base));
 }
 
 int check_cfg(const pfo_tgn_config* c) {
@@ -313,15 +279,6 @@ PfoGemm g_nn(const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
   g.b_kmajor = 1;
   return g;
 }
-// dW[M,N] += A[K,M]^T * B[K,N]   (rows = K)
-PfoGemm g_tn(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* b_idx, float* C, int64_t ldc, int M,
-             int N, int K, const Ws& w) {
-  PfoGemm g = g_nt(A, lda, nullptr, B, ldb, C, ldc, M, N, K, nullptr);
-  g.a_kmajor = 1; g.b_kmajor = 1; g.b_idx = b_idx; g.accumulate = 1;
-  g.slabs = w.slabs; g.slab_floats = w.slab_floats;
-  return g;
-}
-
 #define PFO_MAX_DEVICES 16
 // Internal side stream: the composite-weight products (forward) and their gradient chain (backward) are tiny
 // dependent launches; they run beside the main stream's work and are joined by events where their results are needed.
@@ -375,21 +332,9 @@ Side& side() {
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);           // lo = least (numerically largest), hi = greatest
     bool good = hipStreamCreateWithPriority(&sd.s, hipStreamNonBlocking, hi) == hipSuccess;
     good = good && hipStreamCreateWithPriority(&sd.s2, hipStreamNonBlocking, lo) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.tn_a_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.done2, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.fork, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.seg_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.tn_a, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.tn_b, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.fold_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.gru_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.comp_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.pc_a, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.pc_b, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.main_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.side_done, hipEventDisableTiming) == hipSuccess;
-    good = good && hipEventCreateWithFlags(&sd.early_done, hipEventDisableTiming) == hipSuccess;
+    hipEvent_t* const evs[] = {&sd.tn_a_done, &sd.done2, &sd.fork, &sd.done, &sd.seg_done, &sd.tn_a, &sd.tn_b, &sd.fold_done,
+                               &sd.gru_done, &sd.comp_done, &sd.pc_a, &sd.pc_b, &sd.main_done, &sd.side_done, &sd.early_done};
+    for (hipEvent_t* e : evs) good = good && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     for (int l = 0; l <= PFO_MAX_LAYERS; ++l) good = good && hipEventCreateWithFlags(&sd.layer[l], hipEventDisableTiming) == hipSuccess;
     sd.ok = good;
   }
@@ -498,6 +443,15 @@ static int level_sizes(const pfo_tgn_config* c, const pfo_tgn_batch* b, int64_t*
   PFO_REQUIRE(n[0] < (int64_t)1 << 31, "too many level-0 references");
   return PFO_OK;
 }
+// the batch arguments pfo_tgn_prepare and pfo_tgn_forward both read
+static int check_batch(const pfo_tgn_config* c, const pfo_tgn_batch* b) {
+  PFO_REQUIRE(b->roots && b->root_ts, "null batch arrays");
+  PFO_REQUIRE(b->uniform >= 0 && b->uniform <= 2, "bad sampling mode");
+  PFO_REQUIRE(b->uniform != 1 || b->draws, "mode 1 needs draws");
+  PFO_REQUIRE(b->n_extra >= 0 && b->n_extra <= 2 * c->max_batch, "n_extra exceeds 2 * max_batch");
+  PFO_REQUIRE(b->n_extra == 0 || b->extra_nodes, "null extra_nodes");
+  return PFO_OK;
+}
 
 // Replicas of the level-0 gradient table the layer-1 attention backward adds into: per-XCD replicas pay off only for the
 // per-instance atomics (uniform sampling: 4 replicas 0.537 -> 0.506 ms); the run-merged kernel issues 2-3x fewer and measures
@@ -506,17 +460,124 @@ static int grad_replicas(const pfo_tgn_config* c, const pfo_tgn_batch* b) {
   const int det = b->deterministic ? 1 : 0;
   return (det || (c->use_memory && !b->uniform && pfo_attn_bwd_runs_possible(b->K, c->D, c->n_heads))) ? 1 : PFO_GRAD_REPLICAS;
 }
+static_assert(PFO_GRAD_REPLICAS >= 2, "the deterministic int64 gradient table needs the room of two float replicas");
+
+// ---- One call's context: everything pfo_tgn_prepare / pfo_tgn_forward / pfo_tgn_backward_ev derive from their arguments
+// before they queue anything (open_step), then what the stages of one call hand to each other.
+namespace {
+struct Step {
+  explicit Step(Side& sd_) : sd(sd_) {}
+  const pfo_tgn_config* c = nullptr; const pfo_tgn_state* st = nullptr; const pfo_tgn_batch* b = nullptr;
+  int64_t n[PFO_MAX_LAYERS + 1] = {};   // rows per level of this batch
+  Dims d;
+  Ws w;                                 // (parameter-only buffers in the state's parameter cache, if it has one)
+  pfo_tgn_layout lay;
+  Params P; Grads G;                    // (G: backward only)
+  Side& sd;
+  hipStream_t s = nullptr, ss = nullptr, s2 = nullptr;   // the caller's stream, the library's two side streams
+  int capP = 0;                         // rows of this batch's touched-node table, at most
+  int det = 0, n_rep = 1;               // deterministic backward; replicas of the level-0 gradient table (grad_replicas)
+  int64_t rep_stride = 0;               // floats between the per-XCD replicas of d_h0
+  float scale = 1.f;
+  // The capture status of the caller's stream, asked ONCE per call (nothing inside a call begins or ends a capture there).
+  // Not capturing: events are bound to launches (common.hpp), pc_a / pc_b are waited for, the backward joins in a chain.
+  bool capturing = false;
+  bool build = false, pack_side = false, fused_state = false;      // forward
+  const float* d_emb = nullptr; void* top_ready_event = nullptr;   // backward, from here on
+  bool seg_fwd = false;                 // the forward queued seg_prologue (pfo_tgn_batch.seg_in_forward)
+  const float* mean_src = nullptr; int64_t mean_n = 0; float* mean_out = nullptr;   // the loss mean the caller left to this call
+  int64_t det_rows = 0;                 // slab rows written so far (deterministic mode)
+};
+}  // namespace
+// (each entry first checks the arguments only it takes; `st` is non-null here)
+static int open_step(Step& S, const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, void* workspace, void* stream) {
+  S.c = c; S.st = st; S.b = b;
+  RUN(level_sizes(c, b, S.n));
+  S.d = dims_of(c);
+  S.w = carve(c, workspace, st->pcache, st->pcache != nullptr);   // parameter-only buffers live in the caller's cache
+  RUN(pfo_tgn_param_layout(c, &S.lay));
+  if (st->params) bind(S.lay, st->params, S.P, S.d.L, c->use_memory != 0);
+  S.s = (hipStream_t)stream; S.ss = S.sd.s; S.s2 = S.sd.s2;
+  S.capP = (int)std::min<int64_t>(c->n_nodes, S.n[0] + b->n_extra);
+  S.det = b->deterministic ? 1 : 0;
+  S.n_rep = grad_replicas(c, b);
+  S.rep_stride = (int64_t)S.d.capP * S.d.D;
+  S.scale = 1.0f / sqrtf((float)S.d.dh);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(S.s, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;
+  S.capturing = cap != hipStreamCaptureStatusNone;
+  return PFO_OK;
+}
+
+// One table for the per-layer names of ranges (rocprofv3 --marker-trace) and marks (pfo_marks_*)
+enum { NM_FWD, NM_QK, NM_AT, NM_H1, NM_BWD, NM_DH1, NM_DCTX, NM_BATTN, NM_DX, NM_KINDS };
+#define PFO_L4(a, z) {"", a "1" z, a "2" z, a "3" z, a "4" z}
+static const char* const LAYER_NAMES[NM_KINDS][PFO_MAX_LAYERS + 1] = {
+    PFO_L4("forward layer ", ""), PFO_L4("fwd.L", ".qk"), PFO_L4("fwd.L", ".attn"), PFO_L4("fwd.L", ".h1"),
+    PFO_L4("backward layer ", ""), PFO_L4("bwd.L", ".dh1"), PFO_L4("bwd.L", ".dctx"), PFO_L4("bwd.L", ".attn"),
+    {"", "bwd.L1.dx_tab", "bwd.L2.dx", "bwd.L3.dx", "bwd.L4.dx"}};
+
+// What layer l reads and writes, forward and backward.  Layer 1 works on rows of the touched-node table; layers >= 2 read the
+// previous layer's h1 rows through their fc2-folded composites (build_stage_b, "fc2 fold"): backward, their weight gradients
+// land in the folded composites' gradient buffers and are unfolded on the side stream (unfold_fc2).
+namespace {
+struct LayerView {
+  int l, N; bool folded; const LayerWs* lw;
+  const float* xA; const int32_t* x_idx;
+  const float *Wqk, *cqk, *W1ovT, *W1b, *b1; int64_t W1b_ld;
+  float *dx, *dqk, *dWqk, *gqk, *dW1ovT;
+};
+}  // namespace
+static LayerView layer_view(const Step& S, int l) {
+  const Ws& w = S.w;
+  const LayerWs& lw = w.layer[l];
+  const int D = S.d.D, E = S.d.E;
+  LayerView v;
+  v.l = l; v.N = (int)S.n[l]; v.folded = l >= 2; v.lw = &lw;
+  v.xA = v.folded ? w.layer[l - 1].h1 : w.h0_tab;
+  v.x_idx = v.folded ? nullptr : w.idx0;
+  v.Wqk = v.folded ? lw.Wqk_f : lw.Wqk;
+  v.cqk = v.folded ? lw.cqk_f : lw.cqk;
+  v.W1ovT = v.folded ? lw.W1ovT_f : lw.W1ovT;
+  v.W1b = v.folded ? lw.W1b_f : S.P.l[l].w1 + E;
+  v.W1b_ld = v.folded ? D : E + D;
+  v.b1 = v.folded ? lw.b1_f : S.P.l[l].b1;
+  v.dx = v.folded ? w.dH[l - 1] : nullptr;                  // rows [0, N) of the previous level's gradient
+  v.dqk = v.folded ? lw.dQK : w.dQK;
+  v.dWqk = v.folded ? lw.dWqk_f : lw.dWqk;
+  v.gqk = v.folded ? lw.gqk_f : lw.gqk;
+  v.dW1ovT = v.folded ? lw.dW1ovT_f : lw.dW1ovT;
+  return v;
+}
+// the attention launch of layer l as forward and backward both describe it (the backward adds its own fields on top)
+static PfoAttn attn_of(const Step& S, const LayerView& v) {
+  const Ws& w = S.w;
+  const pfo_tgn_batch* b = S.b;
+  const int l = v.l, N = v.N, HCp = S.d.H * S.d.Cp;
+  PfoAttn a;
+  a.N = N; a.K = b->K; a.D = S.d.D; a.Ef = S.d.Ef; a.H = S.d.H; a.Cp = S.d.Cp;
+  a.QK = (l == 1) ? w.QX : v.lw->QK; a.qk_row = (l == 1) ? w.idx0 : nullptr; a.qk_ld = (l == 1) ? HCp + S.d.D : HCp;
+  a.nbr_tab = v.xA; a.nbr_ld = S.d.D;
+  a.nbr_rows = (l == 1) ? S.capP : S.n[l - 1]; a.edge_rows = S.c->n_edges_p1;
+  a.nbr_row = (l == 1) ? w.idx0 + N : nullptr;
+  a.nbr_row_base = N;
+  a.nbr_ids = w.nodes[l - 1] + N;
+  a.edge_feat = S.st->edge_feat; a.eidx = w.eidx[l]; a.dt = w.dt[l]; a.tw = S.P.tw; a.tb = S.P.tb;
+  a.scale = S.scale; a.dropout_p = b->dropout_p; a.seed = b->seed; a.offset = b->offset + 0x51ED0000ull + (uint64_t)l; a.offset_dev = b->offset_dev;
+  a.keep_inject = (b->dropout_keep && b->training) ? b->dropout_keep[S.d.L - l] : nullptr;
+  a.ctx = v.lw->ctx; a.attw = v.lw->attw; a.inv = v.lw->inv;
+  return a;
+}
+
 // What the backward's layer-1 kernels need and that depends on the sampled levels alone: the cleared level-0 gradient rows and
 // the layer-1 instances grouped by the touched-table row they sit on.  Queued by the backward on its side stream - or, for
 // calls with pfo_tgn_batch.seg_in_forward, by the forward on ITS side stream (beside layer 1, joined by the event layer 2 waits
 // for anyway), which takes one event record and one wait off the backward's critical path.
-static int seg_prologue(const pfo_tgn_config* c, const pfo_tgn_batch* b, const Ws& w, const Dims& d, const int64_t* n, hipStream_t ss) {
-  const int capP = (int)std::min<int64_t>(c->n_nodes, n[0] + b->n_extra);
-  const int det = b->deterministic ? 1 : 0;
-  const int64_t rep_stride = (int64_t)d.capP * d.D;
+static int seg_prologue(const Step& S, hipStream_t ss) {
+  const Ws& w = S.w;
   // (deterministic: the table holds int64 fixed-point sums - rows of 2 D floats' worth)
-  if (c->use_memory) RUN(pfo_zero_rows_launch(w.d_h0, w.n_core, capP, det ? 2 * d.D : d.D, grad_replicas(c, b), rep_stride, ss));
-  RUN(pfo_seg_build_launch(w.idx0, w.nodes[0], (int)n[1], capP, b->uniform ? nullptr : w.cnt1, w.seg_ptr, w.seg_cur,
+  if (S.c->use_memory) RUN(pfo_zero_rows_launch(w.d_h0, w.n_core, S.capP, S.det ? 2 * S.d.D : S.d.D, S.n_rep, S.rep_stride, ss));
+  RUN(pfo_seg_build_launch(w.idx0, w.nodes[0], (int)S.n[1], S.capP, S.b->uniform ? nullptr : w.cnt1, w.seg_ptr, w.seg_cur,
                            w.seg_tmp, w.seg_mem, w.seg_of, w.seg_scratch, ss));
   return PFO_OK;
 }
@@ -538,8 +599,9 @@ static int state_update(const pfo_tgn_config* c, const pfo_tgn_state* st, const 
 
 // ---- the part of a forward call that depends on neither parameters nor gradients, in two halves (pfo_tgn_forward runs the
 // GRU's weight-image launch between them; pfo_tgn_prepare runs them back to back on any stream, ahead of time)
-static int prepare_sample(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, const Ws& w, const int64_t* n,
-                          hipStream_t s) {
+static int prepare_sample(const Step& S, hipStream_t s) {
+  const pfo_tgn_config* c = S.c; const pfo_tgn_state* st = S.st; const pfo_tgn_batch* b = S.b;
+  const Ws& w = S.w; const int64_t* n = S.n;
   const int L = c->n_layers, K = b->K;
   void* stream = (void*)s;
   // The compaction's flags are cleared on THIS stream (4 us): a wait for a side-stream memset costs the waiting stream 5-17 us
@@ -569,35 +631,27 @@ static int prepare_sample(const pfo_tgn_config* c, const pfo_tgn_state* st, cons
                             l == 1 ? w.cnt1 : nullptr, stream, (clear_in_sampler && l == L) ? w.mark : nullptr,
                             (clear_in_sampler && l == L) ? (int64_t)(w.mark_bytes / 4) : 0));
   }
-
   return PFO_OK;
 }
-static int prepare_compact(const pfo_tgn_config* c, const pfo_tgn_batch* b, const Ws& w, hipStream_t s) {
+static int prepare_compact(const Step& S, hipStream_t s) {
+  const Ws& w = S.w;
   // slot[v] = row of v in the per-step tables (roots and every sampled neighbour, all levels; + the caller's extra nodes)
-  RUN(pfo_touch_compact_launch(nullptr, 0, b->extra_nodes, b->n_extra, c->n_nodes, w.mark, w.slot, w.touched, w.n_touched,
-                               w.scan, true, true, s));
-  return PFO_OK;
+  return pfo_touch_compact_launch(nullptr, 0, S.b->extra_nodes, S.b->n_extra, S.c->n_nodes, w.mark, w.slot, w.touched, w.n_touched,
+                                  w.scan, true, true, s);
 }
-static int prepare_pack(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, const Ws& w, const Dims& d,
-                        const int64_t* n, hipStream_t s) {
-  const int D = d.D;
-  const int capP = (int)std::min<int64_t>(c->n_nodes, n[0] + b->n_extra);
+static int prepare_pack(const Step& S, hipStream_t s) {
+  const pfo_tgn_state* st = S.st;
+  const Ws& w = S.w;
+  const int D = S.d.D;
   // ---- level-0 rows of the touched nodes: memory' + node features (embedding_module.py:93-98), memory' = the lazily
   // updated memory (tgn.py:251; memory_updater.py:35-53).  One launch copies the rows the GRU reads (and the backward reads
   // again after the state update has overwritten the tables) and translates the level-0 list into table rows
   // (idx0[i] = row of the i-th level-0 reference).
-  if (c->use_memory)
-    RUN(pfo_pack_remap_launch(st->msg_table, d.M, st->memory, D, st->has_msg, w.touched, w.n_touched, capP, w.msg_rows,
-                              w.h_rows, w.hm, w.nodes[0], n[0], w.slot, w.idx0, s));
-  else
-    RUN(pfo_pack_remap_launch(nullptr, d.M, st->node_feat, D, nullptr, w.touched, w.n_touched, capP, nullptr, w.h0_tab, nullptr,
-                              w.nodes[0], n[0], w.slot, w.idx0, s));
-  return PFO_OK;
-}
-static int prepare_compact_pack(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, const Ws& w, const Dims& d,
-                                const int64_t* n, hipStream_t s) {
-  RUN(prepare_compact(c, b, w, s));
-  return prepare_pack(c, st, b, w, d, n, s);
+  if (S.c->use_memory)
+    return pfo_pack_remap_launch(st->msg_table, S.d.M, st->memory, D, st->has_msg, w.touched, w.n_touched, S.capP, w.msg_rows,
+                                 w.h_rows, w.hm, w.nodes[0], S.n[0], w.slot, w.idx0, s);
+  return pfo_pack_remap_launch(nullptr, S.d.M, st->node_feat, D, nullptr, w.touched, w.n_touched, S.capP, nullptr, w.h0_tab, nullptr,
+                               w.nodes[0], S.n[0], w.slot, w.idx0, s);
 }
 
 // ---- Everything the step derives from the PARAMETERS alone, in two stages of small dependent launches on one stream
@@ -733,18 +787,14 @@ static int build_stage_b(const Dims& d, const Ws& w, const Params& P, hipStream_
 // =============================================================================================
 extern "C" int64_t pfo_tgn_pcache_bytes(const pfo_tgn_config* c) {
   if (check_cfg(c) != PFO_OK) return -1;
-  Ws w;
-  memset(&w, 0, sizeof(w));
-  return pcache_bind(c, nullptr, w) + 256;
+  return carve(c, nullptr, nullptr, true).cache_bytes + 256;
 }
 
 extern "C" int pfo_tgn_refresh(const pfo_tgn_config* c, const pfo_tgn_state* st, void* stream) {
   if (int rc = check_cfg(c)) return rc;
   PFO_REQUIRE(st && st->params && st->pcache, "pfo_tgn_refresh needs parameters and a parameter cache");
   const Dims d = dims_of(c);
-  Ws w;
-  memset(&w, 0, sizeof(w));
-  pcache_bind(c, st->pcache, w);
+  const Ws w = carve(c, nullptr, st->pcache, true);       // (only the cache's buffers are used)
   pfo_tgn_layout lay;
   RUN(pfo_tgn_param_layout(c, &lay));
   Params P;
@@ -779,23 +829,121 @@ extern "C" int pfo_tgn_prepare(const pfo_tgn_config* c, const pfo_tgn_state* st,
   PFO_REQUIRE(st && workspace && b, "null argument");
   PFO_REQUIRE(st->indptr && st->adj_nbr && st->adj_eidx && st->adj_ts && st->node_feat, "null state");
   PFO_REQUIRE(!c->use_memory || (st->memory && st->msg_table && st->has_msg), "null memory state");
-  int64_t n[PFO_MAX_LAYERS + 1];
-  RUN(level_sizes(c, b, n));
-  PFO_REQUIRE(b->roots && b->root_ts, "null batch arrays");
-  PFO_REQUIRE(b->uniform >= 0 && b->uniform <= 2, "bad sampling mode");
-  PFO_REQUIRE(b->uniform != 1 || b->draws, "mode 1 needs draws");
-  PFO_REQUIRE(b->n_extra >= 0 && b->n_extra <= 2 * c->max_batch, "n_extra exceeds 2 * max_batch");
-  PFO_REQUIRE(b->n_extra == 0 || b->extra_nodes, "null extra_nodes");
-  const Dims d = dims_of(c);
-  const Ws w = carve(c, workspace);
+  Step S(side());
+  RUN(open_step(S, c, st, b, workspace, stream));
+  RUN(check_batch(c, b));
   PfoRange range("pfo_tgn_prepare");
-  RUN(side_join(side(), (hipStream_t)stream));
-  RUN(prepare_sample(c, st, b, w, n, (hipStream_t)stream));
-  RUN(prepare_compact_pack(c, st, b, w, d, n, (hipStream_t)stream));
-  return PFO_OK;
+  RUN(side_join(S.sd, S.s));
+  RUN(prepare_sample(S, S.s));
+  RUN(prepare_compact(S, S.s));
+  return prepare_pack(S, S.s);
 }
 
 // =============================================================================================
+// ---- the forward's side-stream work: composite weights of every layer and their fp16 images (build_stage_a / _b), the
+// step's cleared accumulators, the row pack and the fused state update.  Enqueued after the sampling / compaction / GRU
+// launches of the caller's stream (which need none of it): when the host is the slower side (small batches, profilers) the
+// critical chain is already queued while these ~14 launches are being issued; layer 1 waits for them (forward_layer).  With a
+// valid parameter cache (pfo_tgn_state.pcache_valid) NONE of the builds is launched: the side stream only clears the step's
+// accumulators, packs the rows and runs the state update.
+static int forward_side(const Step& S) {
+  const pfo_tgn_state* st = S.st; const pfo_tgn_batch* b = S.b;
+  const Ws& w = S.w; Side& sd = S.sd;
+  hipStream_t ss = S.ss; const bool build = S.build;
+  PFO_REQUIRE(hipMemsetAsync(w.zero, 0, w.zero_bytes, ss) == hipSuccess, "memset failed");   // w.zero, w.tickets, time-gradient bins
+  // (a pfo_tgn_refresh chain may still be running on the second side stream: a rebuild waits for all of it, a call that uses
+  //  the cache waits for its two stages where their results are first needed - no-ops when no refresh is outstanding)
+  if (build && st->pcache && !S.capturing) HIPOK(hipStreamWaitEvent(ss, sd.pc_b, 0), "event wait failed");
+  if (build) RUN(build_stage_a(S.d, w, S.P, ss));
+  // (in front of the pack, not behind it: a cross-stream wait costs the waiting stream 5-17 us even when the event fired long
+  //  ago, and the record below is what layer 1 waits for - stage A of a refresh is done ~80 us after the optimizer's kernel)
+  if (!build && !S.capturing) HIPOK(hipStreamWaitEvent(ss, sd.pc_a, 0), "event wait failed");
+  if (S.pack_side) {
+    HIPOK(hipStreamWaitEvent(ss, sd.comp_done, 0), "event wait failed");
+    RUN(prepare_pack(S, ss));
+  }
+  HIPOK(hipEventRecord(sd.layer[0], ss), "event record failed");      // layer 1 (and the top layer's fc2) can go
+  if (S.d.L >= 2) {
+    if (build) RUN(build_stage_b(S.d, w, S.P, ss));
+    else if (!S.capturing) HIPOK(hipStreamWaitEvent(ss, sd.pc_b, 0), "event wait failed");
+    if (S.fused_state) {
+      // the batch's state update, here: behind the lazy GRU (whose rows it persists), beside layer 1, in front of the event
+      // layer 2 waits for - persist + message store leave the critical path and are joined at no extra wait
+      HIPOK(hipStreamWaitEvent(ss, sd.gru_done, 0), "event wait failed");
+      RUN(state_update(S.c, st, w, b->upd_src, b->upd_dst, b->upd_ts, b->upd_eidx, b->upd_B, ss));
+      if (b->seg_in_forward) RUN(seg_prologue(S, ss));       // (behind gru_done: the compaction and the row pack are done)
+    }
+    HIPOK(hipEventRecord(sd.fold_done, ss), "event record failed");
+  }
+  return PFO_OK;
+}
+
+// One attention layer = THREE large contractions around the neighbour-tile attention kernel (taken
+// to its end).  With one query per instance every projection that touches only that instance folds into a
+// per-step composite weight:
+//   qk'_h  = Wqk_h x + cqk_h,            Wqk_h  = Wk_h^T Wq_h[:, :D],   cqk_h = Wk_h^T (Wq_h[:, D:] cos(b) + bq_h)
+//   h1     = relu( sum_h W1ov_h ctx'_h + W1[:, E:] x + b1 ),
+//            W1ov_h = W1[:, :E] Wo[:, h] Wv_h   (fc1 . out_proj . value projection),
+//            ctx'_h = [ sum_j a'_jh key_j | sum_j a'_jh | valid ]  - the two extra columns carry the folded value
+//            bias (W1 Wo_h bv_h, scaled by the post-dropout weight sum) and the folded out_proj bias (W1 bo, only
+//            on rows that have a valid neighbour: temporal_attention.py:84 zero-fills the others)
+//   out    = W2 h1 + b2
+// 0.60 MFLOP per instance instead of 1.13 (and 10.3 un-folded); Q, O and attn_out are never formed.
+static int forward_layer(const Step& S, int l, float* emb_out) {
+  PfoRange range_layer(LAYER_NAMES[NM_FWD][l]);
+  const Ws& w = S.w;
+  Side& sd = S.sd;
+  hipStream_t s = S.s;
+  const int D = S.d.D, HCp = S.d.H * S.d.Cp, WQ = HCp + D;
+  const LayerView v = layer_view(S, l);   // layers >= 2 read the previous layer's h1 rows: its fc2 lives in this layer's folded composites
+  const LayerWs& lw = *v.lw;
+  const auto& p = S.P.l[l];
+  const int N = v.N;
+  if (l == 1) HIPOK(hipStreamWaitEvent(s, sd.layer[0], 0), "event wait failed");   // composite weights and layer 1's images are ready
+  // ... and the fc2-folded ones of the layers >= 2.  (Round 3 tried ONE wait for both, on the later event: the side stream's
+  // chain - 14 small dependent launches, ~150 us - then ends about when this stream reaches layer 1, and the touched-table
+  // projection started 25 us late; layer 1 needs only the first ~90 us of that chain.)
+  if (l == 2) HIPOK(hipStreamWaitEvent(s, sd.fold_done, 0), "event wait failed");
+  // ---- qk' = x Wqk^T + cqk.  Layer 1: x is a row of the touched-node table, shared by every instance that sits on
+  // that node (~54 k instances on ~11 k nodes at C2): ONE projection of the table, [qk' | x W1[:, E:]^T] per row
+  if (l == 1) {
+    PfoGemm g = g_nt(w.h0_tab, D, nullptr, lw.Wqk, D, w.QX, WQ, S.capP, WQ, D, w.l1_bias);
+    g.m_dev = w.n_core; g.b_img = w.iQX;                 // (rows only the caller's extra list names are never queried)
+    RUN(pfo_gemm_launch(g, s));
+  } else {
+    PfoGemm g = g_nt(v.xA, D, v.x_idx, v.Wqk, D, lw.QK, HCp, N, HCp, D, v.cqk);
+    g.b_img = lw.iWqk;
+    RUN(pfo_gemm_launch(g, s));
+  }
+  const PfoAttn a = attn_of(S, v);
+  PFO_MARK(LAYER_NAMES[NM_QK][l], s);
+  RUN(pfo_attn_fwd_launch(a, s));
+  PFO_MARK(LAYER_NAMES[NM_AT][l], s);
+  // ---- h1 = relu(ctx' W1ovT + x W1[:, E:]^T + b1)   (MergeLayer fc1 with out_proj and the value projection folded in)
+  if (l == 1) {
+    // the x term was projected with the table: it arrives as a row-gathered addend of the epilogue
+    PfoGemm g = g_nn(lw.ctx, HCp, lw.W1ovT, D, lw.h1, D, N, D, HCp);
+    g.bias = p.b1; g.relu = 1; g.b_img = lw.iW1ov;
+    g.add_src = w.QX + HCp; g.add_ld = WQ; g.add_idx = w.idx0;
+    RUN(pfo_gemm_launch(g, s));
+  } else {
+    // both K-concatenated sources ([ctx' | x] against [W1ov | W1[:, E:]]) in one launch: h1 is written once
+    PfoGemm g = g_nn(lw.ctx, HCp, v.W1ovT, D, lw.h1, D, N, D, HCp);
+    g.A[1] = v.xA; g.lda[1] = D; g.a_idx[1] = v.x_idx; g.B[1] = v.W1b; g.ldb[1] = v.W1b_ld; g.K[1] = D;
+    g.bias = v.b1; g.relu = 1; g.b_img = lw.iW1ov; g.b_img2 = lw.iW1b;
+    RUN(pfo_gemm_launch(g, s));
+  }
+  PFO_MARK(LAYER_NAMES[NM_H1][l], s);
+  if (l == S.d.L) {
+    // out = W2 h1 + b2: only the top layer's rows ARE embeddings (N == R; written in place, no copy) - below it the
+    // contraction is folded into the next layer's composites
+    PfoGemm g = g_nt(lw.h1, D, nullptr, p.w2, D, emb_out, D, N, D, D, p.b2);
+    g.b_img = lw.iW2;
+    RUN(pfo_gemm_launch(g, s));
+  }
+  return PFO_OK;
+}
+
 extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, void* workspace,
                                float* emb_out, void* stream) {
   if (int rc = check_cfg(c)) return rc;
@@ -804,35 +952,20 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
   PFO_REQUIRE(c->Ef == 0 || st->edge_feat, "null edge features");
   PFO_REQUIRE(!c->use_memory || (st->memory && st->last_update && st->msg_table && st->msg_time && st->has_msg),
               "null memory state");
-  int64_t n[PFO_MAX_LAYERS + 1];
-  RUN(level_sizes(c, b, n));
-  PFO_REQUIRE(b->roots && b->root_ts, "null batch arrays");
-  PFO_REQUIRE(b->uniform >= 0 && b->uniform <= 2, "bad sampling mode");
-  PFO_REQUIRE(b->uniform != 1 || b->draws, "mode 1 needs draws");
-  const Dims d = dims_of(c);
-  Ws w_ = carve(c, workspace);
-  if (st->pcache) pcache_bind(c, st->pcache, w_);       // parameter-only buffers live in the caller's cache
-  const Ws& w = w_;
-  const bool build = !st->pcache || !st->pcache_valid;  // composites / images (re)built by this call
-  hipStream_t s = (hipStream_t)stream;
-  pfo_tgn_layout lay;
-  RUN(pfo_tgn_param_layout(c, &lay));
-  Params P;
-  bind(lay, st->params, P, d.L, c->use_memory != 0);
-  const int L = d.L, D = d.D, Ef = d.Ef, H = d.H, E = d.E, C = d.C, dh = d.dh, K = b->K;
-  (void)C; (void)dh; (void)E;
+  Step S(side());
+  RUN(open_step(S, c, st, b, workspace, stream));
+  RUN(check_batch(c, b));
+  S.build = !st->pcache || !st->pcache_valid;            // composites / images (re)built by this call
+  S.fused_state = b->upd_src != nullptr && c->use_memory && S.d.L >= 2;
+  PFO_REQUIRE(!S.fused_state || (b->upd_dst && b->upd_ts && b->upd_eidx && b->upd_B >= 1), "bad state-update arguments");
+  const Ws& w = S.w; Side& sd = S.sd;
+  hipStream_t s = S.s, ss = S.ss;
 
   PfoRange range_call(b->training ? "pfo_tgn_forward (training)" : "pfo_tgn_forward");
-  // ---- composite weights of every layer: on the side stream, beside the sampling / memory phase
-  Side& sd = side();
   PFO_REQUIRE(sd.ok, "could not create the side stream");
-  hipStream_t ss = sd.s;
-  const int Cp = d.Cp, HCp = H * d.Cp;
   // Everything on the side stream depends on the parameters only, so it may start at once (after whatever the main
   // stream did before this call); all layers share each launch.
-  hipStreamCaptureStatus cap_early = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap_early) != hipSuccess) cap_early = hipStreamCaptureStatusActive;
-  const bool bind_events = cap_early == hipStreamCaptureStatusNone;      // events bound to a launch (common.hpp): not under capture
+  const bool bind_events = !S.capturing;                 // events bound to a launch (common.hpp): not under capture
   PFO_MARK("fwd.begin", s);
   // (with a deferred backward end in flight the side stream already waits for the caller's stream's last launch of that
   //  backward, and everything this call gives it either reads parameters only or sits behind an event of this call: no fork)
@@ -842,7 +975,7 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
     HIPOK(hipEventRecord(sd.fork, s), "event record failed");
     HIPOK(hipStreamWaitEvent(ss, sd.fork, 0), "event wait failed");
   }
-  if (!b->prepared) RUN(prepare_sample(c, st, b, w, n, s));
+  if (!b->prepared) RUN(prepare_sample(S, s));
   PFO_MARK("fwd.sampled", s);
   // a deferred backward end + optimizer step of the previous step may still be running on the side stream: the sampling above
   // reads neither its buffers nor the parameters; everything below does (compaction counts, the GRU's weights ...)
@@ -850,171 +983,39 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
   //  and layers >= 2 wait for fold_done, recorded there too; the top layer's raw b2 is the only late-bucket value this stream reads)
   RUN(side_join(sd, s, c->n_layers >= 2));
   PFO_MARK("fwd.side_joined", s);
-  const bool fused_state = b->upd_src != nullptr && c->use_memory && L >= 2;
-  PFO_REQUIRE(!fused_state || (b->upd_dst && b->upd_ts && b->upd_eidx && b->upd_B >= 1), "bad state-update arguments");
 
   // the GRU contractions come first on the main stream: their two weight images are made there too (one 4 us launch)
-  if (c->use_memory && build) RUN(build_gru_images(c, d, w, P, s));
-  bool composites_awaited = false;
+  if (c->use_memory && S.build) RUN(build_gru_images(c, S.d, w, S.P, s));
 
-  // ---- the nodes this step reads, compacted, and their level-0 rows packed (prepare_compact_pack; a prepared batch has them)
-  PFO_REQUIRE(b->n_extra >= 0 && b->n_extra <= 2 * c->max_batch, "n_extra exceeds 2 * max_batch");
-  PFO_REQUIRE(b->n_extra == 0 || b->extra_nodes, "null extra_nodes");
+  // ---- the nodes this step reads, compacted, and their level-0 rows packed (prepare_compact, prepare_pack; a prepared batch has them)
   // With memory the row pack leaves the caller's stream: the fused GRU gathers its rows straight from the per-node tables, and
   // the packed copies (for the backward, which runs after the state update has overwritten the tables) + the level-0 remap
   // (first used by layer 1's attention) are made on the side stream, in front of the event layer 1 waits for anyway.
-  const bool pack_side = c->use_memory && !b->prepared;
-  if (!b->prepared) {
-    if (pack_side) {
-      // (comp_done rides on the completion of the compaction's LAST launch - its only one, or the third when the caller's extra
-      //  list is marked and compacted too (data-parallel ranks: memory.hip pfo_touch_compact_launch): no marker packet)
-      PFO_RUN_BOUND(bind_events, sd.comp_done, b->n_extra > 0 ? 2 : 0, s, prepare_compact(c, b, w, s));
-      if (!bind_events) HIPOK(hipEventRecord(sd.comp_done, s), "event record failed");
-    } else {
-      RUN(prepare_compact_pack(c, st, b, w, d, n, s));
-    }
+  S.pack_side = c->use_memory && !b->prepared;
+  if (S.pack_side) {
+    // (comp_done rides on the completion of the compaction's LAST launch - its only one, or the third when the caller's extra
+    //  list is marked and compacted too (data-parallel ranks: memory.hip pfo_touch_compact_launch): no marker packet)
+    PFO_RUN_BOUND(bind_events, sd.comp_done, b->n_extra > 0 ? 2 : 0, s, prepare_compact(S, s));
+    if (!bind_events) HIPOK(hipEventRecord(sd.comp_done, s), "event record failed");
+  } else if (!b->prepared) {
+    RUN(prepare_compact(S, s));
+    RUN(prepare_pack(S, s));
   }
   PFO_MARK("fwd.compacted", s);
-  const int capP = (int)std::min<int64_t>(c->n_nodes, n[0] + b->n_extra);
   if (c->use_memory) {
     PfoRange range_gru("forward lazy GRU");
     // both GRU contractions and the gate math in ONE launch (gemm.hip gru_fused_kernel): gi / gh never exist in HBM
     PfoGruFused f;
-    f.msg_rows = w.msg_rows; f.K_msg = d.M; f.h_rows = w.h_rows; f.img_ih = w.iWih; f.img_hh = w.iWhh;
-    f.b_ih = P.b_ih; f.b_hh = P.b_hh; f.hm = w.hm; f.touched = w.touched; f.node_feat = st->node_feat;
-    f.upd_mem = w.upd_mem; f.h0_tab = w.h0_tab; f.gates = w.gates; f.D = D; f.cap_rows = capP; f.n_rows = w.n_touched;
-    if (pack_side) { f.gather = 1; f.msg_rows = st->msg_table; f.h_rows = st->memory; f.hm = st->has_msg; }
-    PFO_RUN_BOUND(fused_state && bind_events, sd.gru_done, 0, s, pfo_gru_fused_launch(f, s));
-    if (fused_state && !bind_events) HIPOK(hipEventRecord(sd.gru_done, s), "event record failed");
+    f.msg_rows = w.msg_rows; f.K_msg = S.d.M; f.h_rows = w.h_rows; f.img_ih = w.iWih; f.img_hh = w.iWhh;
+    f.b_ih = S.P.b_ih; f.b_hh = S.P.b_hh; f.hm = w.hm; f.touched = w.touched; f.node_feat = st->node_feat;
+    f.upd_mem = w.upd_mem; f.h0_tab = w.h0_tab; f.gates = w.gates; f.D = S.d.D; f.cap_rows = S.capP; f.n_rows = w.n_touched;
+    if (S.pack_side) { f.gather = 1; f.msg_rows = st->msg_table; f.h_rows = st->memory; f.hm = st->has_msg; }
+    PFO_RUN_BOUND(S.fused_state && bind_events, sd.gru_done, 0, s, pfo_gru_fused_launch(f, s));
+    if (S.fused_state && !bind_events) HIPOK(hipEventRecord(sd.gru_done, s), "event record failed");
     PFO_MARK("fwd.gru", s);
   }
-  // ---- composite weights of every layer and their fp16 images (build_stage_a / _b): side stream.  Enqueued HERE, after the
-  // sampling / compaction / GRU launches of the caller's stream (which need none of it): when the host is the slower side
-  // (small batches, profilers) the critical chain is already queued while these ~14 launches are being issued; layer 1 waits
-  // for them below.  With a valid parameter cache (pfo_tgn_state.pcache_valid) NONE of it is launched: the side stream only
-  // clears the step's accumulators, packs the rows and runs the state update.
-  PFO_REQUIRE(hipMemsetAsync(w.zero, 0, w.zero_bytes, ss) == hipSuccess, "memset failed");   // w.zero, w.tickets, time-gradient bins
-  {
-    // (a pfo_tgn_refresh chain may still be running on the second side stream: a rebuild waits for all of it, a call that uses
-    //  the cache waits for its two stages where their results are first needed - no-ops when no refresh is outstanding)
-    hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap_st) != hipSuccess) cap_st = hipStreamCaptureStatusActive;
-    const bool capturing = cap_st != hipStreamCaptureStatusNone;         // (events recorded outside a capture are not waited for inside one)
-    if (build && st->pcache && !capturing) HIPOK(hipStreamWaitEvent(ss, sd.pc_b, 0), "event wait failed");
-    if (build) RUN(build_stage_a(d, w, P, ss));
-    // (in front of the pack, not behind it: a cross-stream wait costs the waiting stream 5-17 us even when the event fired long
-    //  ago, and the record below is what layer 1 waits for - stage A of a refresh is done ~80 us after the optimizer's kernel)
-    if (!build && !capturing) HIPOK(hipStreamWaitEvent(ss, sd.pc_a, 0), "event wait failed");
-    if (pack_side) {
-      HIPOK(hipStreamWaitEvent(ss, sd.comp_done, 0), "event wait failed");
-      RUN(prepare_pack(c, st, b, w, d, n, ss));
-    }
-    HIPOK(hipEventRecord(sd.layer[0], ss), "event record failed");      // layer 1 (and the top layer's fc2) can go
-    if (L >= 2) {
-      if (build) RUN(build_stage_b(d, w, P, ss));
-      else if (!capturing) HIPOK(hipStreamWaitEvent(ss, sd.pc_b, 0), "event wait failed");
-      if (fused_state) {
-        // the batch's state update, here: behind the lazy GRU (whose rows it persists), beside layer 1, in front of the event
-        // layer 2 waits for - persist + message store leave the critical path and are joined at no extra wait
-        HIPOK(hipStreamWaitEvent(ss, sd.gru_done, 0), "event wait failed");
-        RUN(state_update(c, st, w, b->upd_src, b->upd_dst, b->upd_ts, b->upd_eidx, b->upd_B, ss));
-        if (b->seg_in_forward) RUN(seg_prologue(c, b, w, d, n, ss));       // (behind gru_done: the compaction and the row pack are done)
-      }
-      HIPOK(hipEventRecord(sd.fold_done, ss), "event record failed");
-    }
-  }
-  const float* tab0 = w.h0_tab;
-  const int32_t* idx0 = w.idx0;
-  const int WQ = HCp + D;
-
-  // One attention layer = THREE large contractions around the neighbour-tile attention kernel (taken
-  // to its end).  With one query per instance every projection that touches only that instance folds into a
-  // per-step composite weight:
-  //   qk'_h  = Wqk_h x + cqk_h,            Wqk_h  = Wk_h^T Wq_h[:, :D],   cqk_h = Wk_h^T (Wq_h[:, D:] cos(b) + bq_h)
-  //   h1     = relu( sum_h W1ov_h ctx'_h + W1[:, E:] x + b1 ),
-  //            W1ov_h = W1[:, :E] Wo[:, h] Wv_h   (fc1 . out_proj . value projection),
-  //            ctx'_h = [ sum_j a'_jh key_j | sum_j a'_jh | valid ]  - the two extra columns carry the folded value
-  //            bias (W1 Wo_h bv_h, scaled by the post-dropout weight sum) and the folded out_proj bias (W1 bo, only
-  //            on rows that have a valid neighbour: temporal_attention.py:84 zero-fills the others)
-  //   out    = W2 h1 + b2
-  // 0.60 MFLOP per instance instead of 1.13 (and 10.3 un-folded); Q, O and attn_out are never formed.
-  const float scale = 1.0f / sqrtf((float)dh);
-  static const char* const fwd_names[PFO_MAX_LAYERS + 1] = {"", "forward layer 1", "forward layer 2", "forward layer 3", "forward layer 4"};
-  static const char* const mk_qk[PFO_MAX_LAYERS + 1] = {"", "fwd.L1.qk", "fwd.L2.qk", "fwd.L3.qk", "fwd.L4.qk"};
-  static const char* const mk_at[PFO_MAX_LAYERS + 1] = {"", "fwd.L1.attn", "fwd.L2.attn", "fwd.L3.attn", "fwd.L4.attn"};
-  static const char* const mk_h1[PFO_MAX_LAYERS + 1] = {"", "fwd.L1.h1", "fwd.L2.h1", "fwd.L3.h1", "fwd.L4.h1"};
-  for (int l = 1; l <= L; ++l) {
-    PfoRange range_layer(fwd_names[l]);
-    const int N = (int)n[l];
-    const LayerWs& lw = w.layer[l];
-    const auto& p = P.l[l];
-    // layers >= 2 read the previous layer's h1 rows: its fc2 lives in this layer's folded composites (fc2 fold above)
-    const float* xA = (l == 1) ? tab0 : w.layer[l - 1].h1;
-    const int32_t* x_idx = (l == 1) ? idx0 : nullptr;
-    const float* Wqk_l = (l == 1) ? lw.Wqk : lw.Wqk_f;
-    const float* cqk_l = (l == 1) ? lw.cqk : lw.cqk_f;
-    const float* W1ovT_l = (l == 1) ? lw.W1ovT : lw.W1ovT_f;
-    const float* W1b_l = (l == 1) ? p.w1 + E : lw.W1b_f;
-    const int64_t W1b_ld = (l == 1) ? E + D : D;
-    const float* b1_l = (l == 1) ? p.b1 : lw.b1_f;
-
-    if (!composites_awaited) {
-      HIPOK(hipStreamWaitEvent(s, sd.layer[0], 0), "event wait failed");   // composite weights and layer 1's images are ready
-      composites_awaited = true;
-    }
-    // ... and the fc2-folded ones of the layers >= 2.  (Round 3 tried ONE wait for both, on the later event: the side stream's
-    // chain - 14 small dependent launches, ~150 us - then ends about when this stream reaches layer 1, and the touched-table
-    // projection started 25 us late; layer 1 needs only the first ~90 us of that chain.)
-    if (l == 2) HIPOK(hipStreamWaitEvent(s, sd.fold_done, 0), "event wait failed");
-    // ---- qk' = x Wqk^T + cqk.  Layer 1: x is a row of the touched-node table, shared by every instance that sits on
-    // that node (~54 k instances on ~11 k nodes at C2): ONE projection of the table, [qk' | x W1[:, E:]^T] per row
-    if (l == 1) {
-      PfoGemm g = g_nt(tab0, D, nullptr, lw.Wqk, D, w.QX, WQ, capP, WQ, D, w.l1_bias);
-      g.m_dev = w.n_core; g.b_img = w.iQX;                 // (rows only the caller's extra list names are never queried)
-      RUN(pfo_gemm_launch(g, s));
-    } else {
-      PfoGemm g = g_nt(xA, D, x_idx, Wqk_l, D, lw.QK, HCp, N, HCp, D, cqk_l);
-      g.b_img = lw.iWqk;
-      RUN(pfo_gemm_launch(g, s));
-    }
-    PfoAttn a;
-    a.N = N; a.K = K; a.D = D; a.Ef = Ef; a.H = H; a.Cp = Cp;
-    a.QK = (l == 1) ? w.QX : lw.QK; a.qk_row = (l == 1) ? idx0 : nullptr; a.qk_ld = (l == 1) ? WQ : HCp;
-    a.nbr_tab = xA; a.nbr_ld = D;
-    a.nbr_rows = (l == 1) ? capP : n[l - 1]; a.edge_rows = c->n_edges_p1;
-    a.nbr_row = (l == 1) ? idx0 + N : nullptr;
-    a.nbr_row_base = N;
-    a.nbr_ids = w.nodes[l - 1] + N;
-    a.edge_feat = st->edge_feat; a.eidx = w.eidx[l]; a.dt = w.dt[l]; a.tw = P.tw; a.tb = P.tb;
-    a.scale = scale; a.dropout_p = b->dropout_p; a.seed = b->seed; a.offset = b->offset + 0x51ED0000ull + (uint64_t)l; a.offset_dev = b->offset_dev;
-    a.keep_inject = (b->dropout_keep && b->training) ? b->dropout_keep[L - l] : nullptr;
-    a.ctx = lw.ctx; a.attw = lw.attw; a.inv = lw.inv;
-    PFO_MARK(mk_qk[l], s);
-    RUN(pfo_attn_fwd_launch(a, s));
-    PFO_MARK(mk_at[l], s);
-    // ---- h1 = relu(ctx' W1ovT + x W1[:, E:]^T + b1)   (MergeLayer fc1 with out_proj and the value projection folded in)
-    if (l == 1) {
-      // the x term was projected with the table: it arrives as a row-gathered addend of the epilogue
-      PfoGemm g = g_nn(lw.ctx, HCp, lw.W1ovT, D, lw.h1, D, N, D, HCp);
-      g.bias = p.b1; g.relu = 1; g.b_img = lw.iW1ov;
-      g.add_src = w.QX + HCp; g.add_ld = WQ; g.add_idx = idx0;
-      RUN(pfo_gemm_launch(g, s));
-    } else {
-      // both K-concatenated sources ([ctx' | x] against [W1ov | W1[:, E:]]) in one launch: h1 is written once
-      PfoGemm g = g_nn(lw.ctx, HCp, W1ovT_l, D, lw.h1, D, N, D, HCp);
-      g.A[1] = xA; g.lda[1] = D; g.a_idx[1] = x_idx; g.B[1] = W1b_l; g.ldb[1] = W1b_ld; g.K[1] = D;
-      g.bias = b1_l; g.relu = 1; g.b_img = lw.iW1ov; g.b_img2 = lw.iW1b;
-      RUN(pfo_gemm_launch(g, s));
-    }
-    PFO_MARK(mk_h1[l], s);
-    if (l == L) {
-      // out = W2 h1 + b2: only the top layer's rows ARE embeddings (N == R; written in place, no copy) - below it the
-      // contraction is folded into the next layer's composites
-      PfoGemm g = g_nt(lw.h1, D, nullptr, p.w2, D, emb_out, D, N, D, D, p.b2);
-      g.b_img = lw.iW2;
-      RUN(pfo_gemm_launch(g, s));
-    }
-  }
+  RUN(forward_side(S));
+  for (int l = 1; l <= S.d.L; ++l) RUN(forward_layer(S, l, emb_out));
   PFO_MARK("fwd.end", s);
   return PFO_OK;
 }
@@ -1029,457 +1030,407 @@ extern "C" int pfo_tgn_grad_split(const pfo_tgn_config* c, int64_t* split) {
   return PFO_OK;
 }
 
-extern "C" int pfo_tgn_backward(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, void* workspace,
-                                const float* d_emb, float* grad, void* stream) {
-  return pfo_tgn_backward_ev(c, st, b, workspace, d_emb, grad, 0, nullptr, nullptr, 0, nullptr, stream);
+// ---- The backward, stage by stage; pfo_tgn_backward_ev calls the stages in issue order.  Per layer: data gradients first (a
+// chain of GEMMs + the attention core); every weight / bias gradient of the layer is then taken in ONE grouped split-K launch
+// (bias gradients ride along as an extra column).
+namespace {
+// A layer's chain back to the parameters (unfold_fc2, chain_composites), issued by the host one layer later (pfo_tgn_backward_ev)
+struct Chain { int l = 0; PfoTnProblem tn[4]; int ntn = 0; };
+struct LayerBack {                 // what the stages of one layer hand to each other
+  LayerView v;
+  const float* dh1 = nullptr;      // d loss / d (fc1 pre-activation)
+  Chain ch;                        // the layer's weight gradients over the instances, for its chain
+  int n_tn_a = 0;                  // (the first n_tn_a of them need only d out, h1, ctx' and dh1)
+  int dqk_by_member = 0;           // the attention backward took the run-merged kernel: dQK row m belongs to the m-th member
+};
+}  // namespace
+
+static PfoTnProblem tn_of(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* b_idx, int M_, int N_, float* C_,
+                          int64_t ldc, float* bias_out) {
+  PfoTnProblem q;
+  q.A = A; q.lda = lda; q.B = B; q.ldb = ldb; q.b_idx = b_idx; q.M = M_; q.N = N_; q.C = C_; q.ldc = ldc; q.bias_out = bias_out;
+  return q;
+}
+static int side_mean_once(Step& S) {
+  const float* src = S.mean_src;
+  S.mean_src = nullptr;
+  return src ? pfo_mean_launch(src, S.mean_n, S.mean_out, S.ss) : PFO_OK;
 }
 
-extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, void* workspace,
-                                   const float* d_emb, float* grad, int32_t zero_grad_first, void* top_ready_event,
-                                   const float* mean_src, int64_t mean_n, float* mean_out, void* stream) {
-  if (int rc = check_cfg(c)) return rc;
-  PFO_REQUIRE(st && workspace && d_emb && grad && st->params, "null argument");
-  PFO_REQUIRE(!mean_src || (mean_n > 0 && mean_out), "bad deferred mean");
-  int64_t n[PFO_MAX_LAYERS + 1];
-  RUN(level_sizes(c, b, n));
-  const Dims d = dims_of(c);
-  Ws w_ = carve(c, workspace);
-  if (st->pcache) pcache_bind(c, st->pcache, w_);       // the composites and images the forward used
-  const Ws& w = w_;
-  hipStream_t s = (hipStream_t)stream;
-  pfo_tgn_layout lay;
-  RUN(pfo_tgn_param_layout(c, &lay));
-  Params P;
-  Grads G;
-  bind(lay, st->params, P, d.L, c->use_memory != 0);
-  bind(lay, grad, G, d.L, c->use_memory != 0);
-  const int L = d.L, D = d.D, Ef = d.Ef, H = d.H, E = d.E, C = d.C, dh = d.dh, K = b->K;
-  const float scale = 1.0f / sqrtf((float)dh);
-  const float* tab0 = w.h0_tab;
-  const int32_t* idx0 = w.idx0;
-  const int capP = (int)std::min<int64_t>(c->n_nodes, n[0] + b->n_extra);
-  const int64_t rep_stride = (int64_t)d.capP * D;             // floats between the per-XCD replicas of d_h0
-  // Per-XCD replicas of the level-0 gradient table pay off only for the per-instance atomics (uniform sampling: 4 replicas
-  // 0.537 -> 0.506 ms); the run-merged kernel issues 2-3x fewer and measures best on ONE table (1.656 vs 1.665 ms/step)
-  const int det = b->deterministic ? 1 : 0;
-  const int n_rep = grad_replicas(c, b);
-  static_assert(PFO_GRAD_REPLICAS >= 2, "the deterministic int64 gradient table needs the room of two float replicas");
-  int64_t det_rows = 0;                                        // slab rows written so far (deterministic mode)
+// Stage 1, the side stream's opening work: the loss mean the caller left to this call, the cleared level-0 gradient rows and
+// the layer-1 instance groups (seg_prologue: needed only when the layer-1 gradients are summed per row, late in this call -
+// built beside the layer-L .. 2 work; layer 1's attention backward waits for seg_done).  A call whose forward already queued
+// the last two (pfo_tgn_batch.seg_in_forward) forks nothing here - an event record costs the caller's stream a ~6 us bubble in
+// front of its next kernel - and takes the mean behind the first event the side stream waits for anyway.
+static int backward_open(Step& S) {
+  if (S.seg_fwd) return PFO_OK;
+  HIPOK(hipEventRecord(S.sd.fork, S.s), "event record failed");
+  HIPOK(hipStreamWaitEvent(S.ss, S.sd.fork, 0), "event wait failed");
+  RUN(side_mean_once(S));
+  RUN(seg_prologue(S, S.ss));
+  HIPOK(hipEventRecord(S.sd.seg_done, S.ss), "event record failed");
+  return PFO_OK;
+}
 
-  const int Cp = d.Cp, HCp = H * d.Cp, WQ = HCp + D;
-  PfoRange range_call("pfo_tgn_backward");
-  Side& sd = side();
-  PFO_REQUIRE(sd.ok, "could not create the side stream");
-  hipStream_t ss = sd.s;
-  RUN(side_join(sd, s));
-  // layer-1 instances grouped by the touched-table row they sit on (needed only when the layer-1 gradients are summed
-  // per row, late in this call): built on the side stream, beside the layer-L .. 2 work.  The same stream first clears what
-  // this call accumulates into: the level-0 gradient rows (layer 1's attention backward waits for seg_done)
-  // (the gradient buffer is cleared on the caller's stream, before the fork: every writer on any stream comes after it)
-  hipStreamCaptureStatus cap_early = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap_early) != hipSuccess) cap_early = hipStreamCaptureStatusActive;
-  const bool bind_events = cap_early == hipStreamCaptureStatusNone;      // events bound to a launch (common.hpp): not under capture
-  PFO_MARK("bwd.begin", s);
-  if (zero_grad_first) HIPOK(hipMemsetAsync(grad, 0, (size_t)lay.total * sizeof(float), s), "memset failed");
-  // The side stream's opening work: the loss mean the caller left to this call, the cleared level-0 gradient rows and the
-  // layer-1 instance groups (seg_prologue).  A call whose forward already queued the last two (pfo_tgn_batch.seg_in_forward)
-  // forks nothing here - an event record costs the caller's stream a ~6 us bubble in front of its next kernel - and takes
-  // the mean behind the first event the side stream waits for anyway.
-  const bool seg_fwd = b->seg_in_forward && b->upd_src != nullptr && c->use_memory && L >= 2;
-  bool mean_pending = mean_src != nullptr;
-  auto side_mean_once = [&]() -> int {
-    if (mean_pending) { mean_pending = false; RUN(pfo_mean_launch(mean_src, mean_n, mean_out, ss)); }
+// Stage 2, top layer only: it applies its fc2 (utils.py:17): dW2 / db2 and d h1 = relu'(.) (d out W2).  (Below the top the
+// layer above wrote d h1 directly, ReLU mask applied by its producers - attention backward's key rows, the x-side
+// contraction's epilogue: fc2 is part of that layer's composites.)
+static int backward_top_dh1(const Step& S, LayerBack& lb) {
+  const int D = S.d.D, l = lb.v.l;
+  const LayerWs& lw = *lb.v.lw;
+  lb.ch.tn[lb.ch.ntn++] = tn_of(S.d_emb, D, lw.h1, D, nullptr, D, D, S.G.l[l].w2, D, S.G.l[l].b2);
+  PfoGemm q = g_nn(S.d_emb, D, S.P.l[l].w2, D, S.w.dh1, D, lb.v.N, D, D);
+  q.relu_src = lw.h1; q.relu_ld = D;                     // ReLU backward
+  q.b_img = lw.iW2T;
+  RUN(pfo_gemm_launch(q, S.s));
+  PFO_MARK(LAYER_NAMES[NM_DH1][l], S.s);
+  lb.dh1 = S.w.dh1;
+  return PFO_OK;
+}
+
+// Stage 3: merged fc1, d ctx' = dh1 W1ovT^T (dx = dh1 W1[:, E:] is taken together with the query/key part, stage 5), and at
+// layer 1 the weight gradients over the INSTANCES (dW2 / db2 at the top, dW1ovT).  Those need only d out, h1, ctx' and dh1: they
+// go to the side stream.  With the bf16x3 tile they were best started as soon as dh1 existed, beside the d ctx' contraction
+// (15 us/step better than next to the attention backward alone, whose single-wavefront workgroups starved a 74 KB-LDS kernel of
+// slots); the fp16 tile (49 KB, half the matrix work) does better behind d ctx', beside the attention backward: 1.4495 against
+// 1.4532 ms over four interleaved pairs.  (Behind the attention backward, beside the serial tail: +2 % per step.)
+static int backward_dctx(Step& S, LayerBack& lb) {
+  const Ws& w = S.w; Side& sd = S.sd; const pfo_tgn_batch* b = S.b;
+  hipStream_t s = S.s, ss = S.ss;
+  const LayerView& v = lb.v;
+  const int l = v.l, N = v.N, D = S.d.D, HCp = S.d.H * S.d.Cp;
+  const bool bind_events = !S.capturing;
+  lb.ch.tn[lb.ch.ntn] = tn_of(v.lw->ctx, HCp, lb.dh1, D, nullptr, HCp, D, v.dW1ovT, D, nullptr);       // dW1ovT = ctx'^T dh1
+  lb.ch.tn[lb.ch.ntn++].c_accumulate = 0;
+  lb.n_tn_a = lb.ch.ntn;
+  PfoGemm q = g_nt(lb.dh1, D, nullptr, v.W1ovT, D, w.dctx, HCp, N, HCp, D, nullptr);
+  q.b_img = v.lw->iW1ovT;
+  const bool bind_tn_a = bind_events && l == 1 && !pfo_prof_on();
+  PFO_RUN_BOUND(bind_tn_a, sd.tn_a, 0, s, pfo_gemm_launch(q, s));
+  PFO_MARK(LAYER_NAMES[NM_DCTX][l], s);
+  if (l == 1 && b->mid_event && !b->mid_event_late) HIPOK(hipEventRecord((hipEvent_t)b->mid_event, s), "event record failed");
+  if (l > 1) {
+    lb.ch.tn[lb.ch.ntn] = tn_of(lb.dh1, D, v.xA, D, v.x_idx, D, D, v.lw->dW1b_f, D, v.lw->db1_f);      // d (W1[:, E:] A), d (b1 + W1[:, E:] b)
+    lb.ch.tn[lb.ch.ntn].c_accumulate = 0; lb.ch.tn[lb.ch.ntn++].bias_accumulate = 0;
     return PFO_OK;
-  };
-  if (!seg_fwd) {
-    HIPOK(hipEventRecord(sd.fork, s), "event record failed");
-    HIPOK(hipStreamWaitEvent(ss, sd.fork, 0), "event wait failed");
-    RUN(side_mean_once());
-    RUN(seg_prologue(c, b, w, d, n, ss));
-    HIPOK(hipEventRecord(sd.seg_done, ss), "event record failed");
   }
-  std::function<int()> deferred_chain;                       // a layer's chain-back launches, issued one layer later (below)
-  static const char* const bwd_names[PFO_MAX_LAYERS + 1] = {"", "backward layer 1", "backward layer 2", "backward layer 3", "backward layer 4"};
-  static const char* const mk_dh1[PFO_MAX_LAYERS + 1] = {"", "bwd.L1.dh1", "bwd.L2.dh1", "bwd.L3.dh1", "bwd.L4.dh1"};
-  static const char* const mk_dctx[PFO_MAX_LAYERS + 1] = {"", "bwd.L1.dctx", "bwd.L2.dctx", "bwd.L3.dctx", "bwd.L4.dctx"};
-  static const char* const mk_battn[PFO_MAX_LAYERS + 1] = {"", "bwd.L1.attn", "bwd.L2.attn", "bwd.L3.attn", "bwd.L4.attn"};
-  static const char* const mk_dx[PFO_MAX_LAYERS + 1] = {"", "bwd.L1.dx_tab", "bwd.L2.dx", "bwd.L3.dx", "bwd.L4.dx"};
-  for (int l = L; l >= 1; --l) {
-    PfoRange range_layer(bwd_names[l]);
-    const int N = (int)n[l];
-    const LayerWs& lw = w.layer[l];
-    const auto& p = P.l[l];
-    const auto& g = G.l[l];
-    // layers >= 2 work on the previous layer's h1 rows through their fc2-folded composites (pfo_tgn_forward, "fc2 fold"):
-    // their weight gradients land in the folded composites' gradient buffers and are unfolded on the side stream below
-    const bool folded = l >= 2;
-    const float* xA = (l == 1) ? tab0 : w.layer[l - 1].h1;
-    const int32_t* x_idx = (l == 1) ? idx0 : nullptr;
-    float* dx = (l == 1) ? nullptr : w.dH[l - 1];            // rows [0, N) of the previous level's gradient
-    const float* Wqk_l = folded ? lw.Wqk_f : lw.Wqk;
-    const float* W1ovT_l = folded ? lw.W1ovT_f : lw.W1ovT;
-    const float* W1b_l = folded ? lw.W1b_f : p.w1 + E;
-    const int64_t W1b_ld = folded ? D : E + D;
-    float* dWqk_l = folded ? lw.dWqk_f : lw.dWqk;
-    float* gqk_l = folded ? lw.gqk_f : lw.gqk;
-    float* dW1ovT_l = folded ? lw.dW1ovT_f : lw.dW1ovT;
-
-    // Data gradients first (a chain of GEMMs + the attention core); every weight / bias gradient of the layer is
-    // then taken in ONE grouped split-K launch (bias gradients ride along as an extra column).
-    PfoTnProblem tn[4];
-    int ntn = 0;
-    auto set_tn = [&](PfoTnProblem& q, const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* b_idx, int M_,
-                      int N_, float* C_, int64_t ldc, float* bias_out) {
-      q = PfoTnProblem();
-      q.A = A; q.lda = lda; q.B = B; q.ldb = ldb; q.b_idx = b_idx; q.M = M_; q.N = N_; q.C = C_; q.ldc = ldc; q.bias_out = bias_out;
-    };
-    const float* dh1;                                          // d loss / d (fc1 pre-activation)
-    if (l == L) {
-      // the top layer applies its fc2 (utils.py:17): dW2 / db2 and d h1 = relu'(.) (d out W2)
-      set_tn(tn[ntn++], d_emb, D, lw.h1, D, nullptr, D, D, g.w2, D, g.b2);
-      PfoGemm q = g_nn(d_emb, D, p.w2, D, w.dh1, D, N, D, D);
-      q.relu_src = lw.h1; q.relu_ld = D;                     // ReLU backward
-      q.b_img = lw.iW2T;
-      RUN(pfo_gemm_launch(q, s));
-      PFO_MARK(mk_dh1[l], s);
-      dh1 = w.dh1;
-    } else {
-      // below the top the layer above wrote d h1 directly, ReLU mask applied by its producers (attention backward's key
-      // rows, the x-side contraction's epilogue): fc2 is part of that layer's composites
-      dh1 = w.dH[l];
-    }
-    set_tn(tn[ntn], lw.ctx, HCp, dh1, D, nullptr, HCp, D, dW1ovT_l, D, nullptr);       // dW1ovT = ctx'^T dh1
-    tn[ntn].c_accumulate = 0;
-    ++ntn;
-    const int n_tn_a = ntn;
-    // The weight gradients over the INSTANCES (dW2 / db2 at the top, dW1ovT) need only d out, h1, ctx' and dh1: they go to the side
-    // stream.  With the bf16x3 tile they were best started as soon as dh1 existed, beside the d ctx' contraction (15 us/step
-    // better than next to the attention backward alone, whose single-wavefront workgroups starved a 74 KB-LDS kernel of slots);
-    // the fp16 tile (49 KB, half the matrix work) does better behind d ctx', beside the attention backward: 1.4495 against
-    // 1.4532 ms over four interleaved pairs.  (Behind the attention backward, beside the serial tail: +2 % per step.)
-    // merged fc1: d ctx' = dh1 W1ovT^T (dx = dh1 W1[:, E:] is taken together with the query/key part below)
-    {
-      PfoGemm q = g_nt(dh1, D, nullptr, W1ovT_l, D, w.dctx, HCp, N, HCp, D, nullptr);
-      q.b_img = lw.iW1ovT;
-      const bool bind_tn_a = bind_events && l == 1 && !pfo_prof_on();
-      PFO_RUN_BOUND(bind_tn_a, sd.tn_a, 0, s, pfo_gemm_launch(q, s));
-      PFO_MARK(mk_dctx[l], s);
-      if (l == 1 && b->mid_event && !b->mid_event_late) HIPOK(hipEventRecord((hipEvent_t)b->mid_event, s), "event record failed");
-    }
-    if (l > 1) {
-      set_tn(tn[ntn], dh1, D, xA, D, x_idx, D, D, lw.dW1b_f, D, lw.db1_f);              // d (W1[:, E:] A), d (b1 + W1[:, E:] b)
-      tn[ntn].c_accumulate = 0; tn[ntn].bias_accumulate = 0;
-      ++ntn;
-    }
-    if (l == 1) {
-      if (pfo_prof_on()) {        // event-bracketed step (bench.py's roofline sample): serial, so the bracket times the kernel alone
-        RUN(pfo_gemm_tn_group_launch(tn, n_tn_a, N, nullptr, w.slabs, w.slab_floats, s));
-        HIPOK(hipEventRecord(sd.tn_a_done, s), "event record failed");
-      } else {
-        if (!bind_events) HIPOK(hipEventRecord(sd.tn_a, s), "event record failed");     // (bound: tn_a rides on the d ctx' launch)
-        HIPOK(hipStreamWaitEvent(ss, sd.tn_a, 0), "event wait failed");
-        RUN(side_mean_once());
-        PFO_MARK("@side1.tn_a.begin", ss);
-        RUN(pfo_gemm_tn_group_launch(tn, n_tn_a, N, nullptr, w.slabs2, w.slab_floats, ss));
-        PFO_MARK("@side1.tn_a.end", ss);
-        HIPOK(hipEventRecord(sd.tn_a_done, ss), "event record failed");
-      }
-    }
-    // attention core
-    PfoAttn a;
-    a.N = N; a.K = K; a.D = D; a.Ef = Ef; a.H = H; a.Cp = Cp;
-    a.QK = (l == 1) ? w.QX : lw.QK; a.qk_row = (l == 1) ? idx0 : nullptr; a.qk_ld = (l == 1) ? WQ : HCp;
-    a.nbr_tab = xA; a.nbr_ld = D;
-    a.nbr_rows = (l == 1) ? capP : n[l - 1]; a.edge_rows = c->n_edges_p1;
-    a.nbr_row = (l == 1) ? idx0 + N : nullptr;
-    a.nbr_row_base = N;
-    a.nbr_relu = folded ? 1 : 0;                               // the keys are h1 rows of the layer below: d row *= (row > 0)
-    a.nbr_ids = w.nodes[l - 1] + N;
-    a.edge_feat = st->edge_feat; a.eidx = w.eidx[l]; a.dt = w.dt[l]; a.tw = P.tw; a.tb = P.tb;
-    a.scale = scale; a.dropout_p = b->dropout_p; a.seed = b->seed; a.offset = b->offset + 0x51ED0000ull + (uint64_t)l; a.offset_dev = b->offset_dev;
-    a.keep_inject = (b->dropout_keep && b->training) ? b->dropout_keep[L - l] : nullptr;
-    a.ctx = lw.ctx; a.attw = lw.attw; a.inv = lw.inv;
-    float* const dqk_l = (l == 1) ? w.dQK : lw.dQK;
-    a.dctx = w.dctx; a.dQK = dqk_l;
-    if (l == 1) { a.d_nbr = c->use_memory ? w.d_h0 : nullptr; a.d_nbr_ld = D; a.d_nbr_rep = rep_stride; a.d_nbr_nrep = n_rep; }
-    else        { a.d_nbr = w.dH[l - 1]; a.d_nbr_ld = D; }
-    a.dtime_part = w.dtime;
-    a.det = det; a.dtime_slab = w.dtime_slab + det_rows * 2 * D;
-    int n_parts = 0;
-    if (l == 1 && c->use_memory && !seg_fwd) HIPOK(hipStreamWaitEvent(s, sd.seg_done, 0), "event wait failed");   // d_h0 is clear, the groups exist
-    if (l == 1 && c->use_memory && !b->uniform) {
-      // key-side gradients of instances with identical neighbour lists leave as one set of atomics (attn.hip)
-      a.members = w.seg_mem; a.seg_ptr = w.seg_ptr; a.n_rows = w.n_core; a.run_cnt = w.cnt1; a.dqk_live = w.dqk_live;
-    }
-    const int dqk_by_member = pfo_attn_bwd_uses_runs(a) ? 1 : 0;
-    RUN(pfo_attn_bwd_launch(a, &n_parts, s));
-    PFO_MARK(mk_battn[l], s);
-    if (l == 1 && b->mid_event && b->mid_event_late) HIPOK(hipEventRecord((hipEvent_t)b->mid_event, s), "event record failed");
-    if (det) det_rows += n_parts;
-    if (deferred_chain) { RUN(deferred_chain()); deferred_chain = nullptr; }     // the layer above's chain-back (side streams)
-    bool layer_event_bound = false;
-    // merged query/key projection: dx += dqk' Wqk, dWqk = dqk'^T x, gqk = colsum(dqk')
-    if (l == 1) {
-      // Layer 1: x is a row of the touched-node table shared by all instances on that node, so everything that is linear
-      // in the per-instance gradients (dqk', dh1) and otherwise depends on x only - the data gradient of x and the two
-      // weight gradients against x - is taken AFTER summing those gradients per table row: contractions over the
-      // ~11 k touched rows instead of the ~54 k instances.
-      if (!c->use_memory) HIPOK(hipStreamWaitEvent(s, sd.seg_done, 0), "event wait failed");   // (with memory: awaited before the attention backward)
-      PFO_RUN_BOUND(bind_events, sd.tn_b, 0, s,
-                    pfo_segsum_launch(dqk_l, HCp, dh1, D, w.seg_ptr, w.seg_mem, w.seg_of, n[1], w.n_core, capP, dqk_by_member,
-                                      dqk_by_member ? w.dqk_live : nullptr, w.Dq, s));   // Dq = [sum dqk' | sum dh1]
-      // the weight gradients over the table rows go to the side stream too (beside d h0 / the GRU backward on this one)
-      if (!bind_events) HIPOK(hipEventRecord(sd.tn_b, s), "event record failed");
-      PFO_MARK("bwd.L1.segsum", s);
-      HIPOK(hipStreamWaitEvent(ss, sd.tn_b, 0), "event wait failed");
-      RUN(side_mean_once());
-      PfoTnProblem tb[2];
-      set_tn(tb[0], w.Dq, WQ, tab0, D, nullptr, HCp, D, lw.dWqk, D, lw.gqk);               // dWqk = (sum dqk')^T h0, gqk
-      tb[0].c_accumulate = 0; tb[0].bias_accumulate = 0;
-      set_tn(tb[1], w.Dq + HCp, WQ, tab0, D, nullptr, D, D, g.w1 + E, E + D, g.b1);        // dW1[:, E:], db1
-      // (the layer's chain-back on the side stream needs dWqk / gqk: this launch stays there also while profiling)
-      PFO_MARK("@side1.tn_b.begin", ss);
-      RUN(pfo_gemm_tn_group_launch(tb, 2, capP, w.n_core, w.slabs2, w.slab_floats, ss));
-      PFO_MARK("@side1.tn_b.end", ss);
-      if (c->use_memory) {
-        // d h0_tab (query side) = Dq [Wqk ; W1[:, E:]]; the GRU backward adds it to the key-side rows the attention scattered
-        PfoGemm q = g_nn(w.Dq, WQ, lw.Wqk, D, w.dx_tab, D, capP, D, HCp);
-        q.A[1] = w.Dq + HCp; q.lda[1] = WQ; q.B[1] = p.w1 + E; q.ldb[1] = E + D; q.K[1] = D;
-        q.b_img = lw.iWqkT; q.b_img2 = lw.iW1bT; q.m_dev = w.n_core;
-        RUN(pfo_gemm_launch(q, s));
-        PFO_MARK(mk_dx[l], s);
-      }
-    } else {
-      // d h1 of the layer below, self rows [0, N): [dqk' | dh1] [Q_f ; W1b_f], masked by that layer's ReLU
-      {
-        // both sources in one launch, dx written once
-        PfoGemm q = g_nn(dqk_l, HCp, Wqk_l, D, dx, D, N, D, HCp);
-        q.A[1] = dh1; q.lda[1] = D; q.B[1] = W1b_l; q.ldb[1] = W1b_ld; q.K[1] = D;
-        q.b_img = lw.iWqkT; q.b_img2 = lw.iW1bT;
-        q.relu_src = xA; q.relu_ld = D;
-        PFO_RUN_BOUND(bind_events, sd.layer[l], 0, s, pfo_gemm_launch(q, s));     // (layer[l], recorded below, rides on this launch)
-        if (bind_events) layer_event_bound = true;
-      }
-      PFO_MARK(mk_dx[l], s);
-      set_tn(tn[ntn], dqk_l, HCp, xA, D, x_idx, HCp, D, dWqk_l, D, gqk_l);
-      tn[ntn].c_accumulate = 0; tn[ntn].bias_accumulate = 0;
-      ++ntn;
-      // (launched below, on the second side stream in front of the layer's chain: nothing on this stream needs the weight
-      //  gradients of a layer >= 2 - 36 us of launch-latency-bound work off the critical path at C2)
-    }
-
-    // ---- chain the composite-weight gradients back to the parameters (tiny products, side streams).  ~15 launches that no
-    // launch of the caller's stream waits for: for a layer >= 2 the HOST issues them only after the next layer's data-gradient
-    // launches are queued (r3 timeline: the caller's stream sat idle for ~60 us behind them while the host was the slower side);
-    // the event that releases them on the device stays where it was.
-    if (folded && !layer_event_bound) HIPOK(hipEventRecord(sd.layer[l], s), "event record failed");
-    auto chain_back = [=]() -> int {
-    if (folded) {
-      // First undo the fc2 fold (notation of pfo_tgn_forward: A, b = W2, b2 of layer l-1; Q = Wqk, V = W1ovT, per head):
-      //   dT1_node = A dQ_f,node      dT1_edge|time = dQ_f,edge|time         dt likewise from gqk_f
-      //   dV_node  = A dV_f,node + b (x) dV_f[C]         dV elsewhere = dV_f
-      //   dW1b     = dW1b_f A^T + db1_f (x) b            db1 += db1_f
-      //   dQ       = dT1 A^T + dt (x) b                  d cqk = dt
-      //   dA       = sum_h ( T1_node dQ_f,node^T + t_node (x) gqk_f,node + V_node dV_f,node^T ) + W1b^T dW1b_f + Q^T dT1
-      //   db       = sum_h V_node dV_f[C]^T + W1b^T db1_f + Q^T dt
-      // The dA / db terms are written to slabs (several heads add to one matrix) and summed once.
-      const auto& gp = G.l[l - 1];
-      const float* A = P.l[l - 1].w2;
-      const float* bv = P.l[l - 1].b2;
-      const int64_t HCpD = (int64_t)HCp * D, CpD = (int64_t)Cp * D, DD = (int64_t)D * D;
-      // (on the second side stream: the first one must stay free for layer 1's weight gradients over the instances)
-      hipStream_t sf = sd.s2;
-      HIPOK(hipStreamWaitEvent(sf, sd.layer[l], 0), "event wait failed");
-      if (pfo_prof_on()) {
-        // event-bracketed step (bench.py's roofline sample): on the caller's stream, so that the bracket times the kernel alone
-        RUN(pfo_gemm_tn_group_launch(tn, ntn, N, nullptr, w.slabs, w.slab_floats, s));
-        HIPOK(hipEventRecord(sd.layer[l], s), "event record failed");
-        HIPOK(hipStreamWaitEvent(sf, sd.layer[l], 0), "event wait failed");
-      } else {
-        RUN(pfo_gemm_tn_group_launch(tn, ntn, N, nullptr, w.slabs3, w.slab_floats, sf));
-      }
-      {
-        PfoSumSlabs cp[3];                        // (one grouped launch instead of three runtime blits, as in build_stage_b)
-        cp[0].dst = lw.dT1;    cp[0].src = lw.dWqk_f;   cp[0].count = HCpD;
-        cp[1].dst = lw.gqk;    cp[1].src = lw.gqk_f;    cp[1].count = HCp;
-        cp[2].dst = lw.dW1ovT; cp[2].src = lw.dW1ovT_f; cp[2].count = HCpD;
-        for (int q = 0; q < 3; ++q) { cp[q].n_slabs = 1; cp[q].accumulate = 0; cp[q].stride = 0; }
-        RUN(pfo_sum_slabs_launch(cp, 3, sf));
-      }
-      float* sl = lw.fold_slabs;
-      float* vs = lw.fold_vslabs;
-      {
-        PfoGemm u[9];
-        u[0] = g_nn(A, D, lw.dWqk_f, D, lw.dT1, D, D, D, D);                                  // dT1_node = A dQ_f,node
-        u[0].batch = H; u[0].b_bs[0] = CpD; u[0].c_bs = CpD;
-        u[1] = g_nt(lw.gqk_f, D, nullptr, A, D, lw.gqk, D, 1, D, D, nullptr);                 // dt_node = A gqk_f,node
-        u[1].batch = H; u[1].a_bs[0] = Cp; u[1].c_bs = Cp;
-        u[2] = g_nt(lw.T1, D, nullptr, lw.dWqk_f, D, sl, D, D, D, D, nullptr);                // slab h: T1_node dQ_f,node^T
-        u[2].batch = H; u[2].a_bs[0] = CpD; u[2].b_bs[0] = CpD; u[2].c_bs = DD;
-        u[3] = g_nt(lw.W1ovT, D, nullptr, lw.dW1ovT_f, D, sl + H * DD, D, D, D, D, nullptr);  // slab H+h: V_node dV_f,node^T
-        u[3].batch = H; u[3].a_bs[0] = CpD; u[3].b_bs[0] = CpD; u[3].c_bs = DD;
-        u[4] = g_nn(p.w1 + E, E + D, lw.dW1b_f, D, sl + 2 * H * DD, D, D, D, D);              // slab 2H: W1b^T dW1b_f
-        u[4].a_kmajor = 1;
-        u[5] = g_nn(A, D, lw.dW1ovT_f, D, lw.dW1ovT, D, D, D, D);                             // dV_node = A dV_f,node
-        u[5].batch = H; u[5].b_bs[0] = CpD; u[5].c_bs = CpD;
-        u[6] = g_nt(lw.dW1ovT_f + (int64_t)C * D, D, nullptr, lw.W1ovT, D, vs, D, 1, D, D, nullptr);   // vslab h: V_node dV_f[C]^T
-        u[6].batch = H; u[6].a_bs[0] = CpD; u[6].b_bs[0] = CpD; u[6].c_bs = D;
-        u[7] = g_nn(lw.db1_f, D, p.w1 + E, E + D, vs + H * D, D, 1, D, D);                    // vslab H: W1b^T db1_f
-        u[8] = g_nt(lw.dW1b_f, D, nullptr, A, D, g.w1 + E, E + D, D, D, D, nullptr);          // dW1[:, E:] += dW1b_f A^T
-        u[8].accumulate = 1;
-        RUN(pfo_gemm_multi_launch(u, 9, sf));
-      }
-      {
-        PfoGemm u[3];
-        u[0] = g_nt(lw.dT1, D, nullptr, A, D, lw.dWqk, D, HCp, D, D, nullptr);                // dQ = dT1 A^T
-        u[1] = g_nn(lw.Wqk, D, lw.dT1, D, sl + (2 * H + 1) * DD, D, D, D, HCp);               // slab 2H+1: Q^T dT1 (all heads' rows)
-        u[1].a_kmajor = 1;
-        u[2] = g_nn(lw.gqk, HCp, lw.Wqk, D, vs + (H + 1) * D, D, 1, D, HCp);                  // vslab H+1: Q^T dt
-        RUN(pfo_gemm_multi_launch(u, 3, sf));
-      }
-      {
-        PFO_REQUIRE(H + 3 <= PFO_RANK1_MAX, "too many heads");
-        PfoRank1 r[PFO_RANK1_MAX];
-        int nr = 0;
-        r[nr].u = lw.gqk; r[nr].v = bv; r[nr].M = HCp; r[nr].N = D; r[nr].out = lw.dWqk; r[nr].ldo = D; ++nr;                    // dQ += dt (x) b
-        r[nr].u = lw.db1_f; r[nr].v = bv; r[nr].M = D; r[nr].N = D; r[nr].out = g.w1 + E; r[nr].ldo = E + D; ++nr;               // dW1[:, E:] += db1_f (x) b
-        for (int h = 0; h < H; ++h) {                                                                                             // dV_node += b (x) dV_f[C]
-          r[nr].u = bv; r[nr].v = lw.dW1ovT_f + ((int64_t)h * Cp + C) * D; r[nr].M = D; r[nr].N = D;
-          r[nr].out = lw.dW1ovT + (int64_t)h * CpD; r[nr].ldo = D; ++nr;
-        }
-        RUN(pfo_rank1_multi_launch(r, nr, sf));
-        PfoSumSlabs q[3];
-        q[0].dst = gp.w2; q[0].src = sl; q[0].stride = DD; q[0].count = DD; q[0].n_slabs = 2 * H + 2;                             // dA
-        q[1].dst = gp.b2; q[1].src = vs; q[1].stride = D; q[1].count = D; q[1].n_slabs = H + 2;                                   // db
-        q[2].dst = g.b1; q[2].src = lw.db1_f; q[2].stride = 0; q[2].count = D; q[2].n_slabs = 1;                                  // db1 += db1_f
-        RUN(pfo_sum_slabs_launch(q, 3, sf));
-        PfoRank1 ta;                                                                                                              // dA += sum_h t_node (x) gqk_f,node
-        ta.u = lw.tq; ta.v = lw.gqk_f; ta.M = D; ta.N = D; ta.out = gp.w2; ta.ldo = D; ta.reps = H; ta.u_rs = Cp; ta.v_rs = Cp;
-        RUN(pfo_rank1_multi_launch(&ta, 1, sf));
-      }
-    }
-    // Half A hangs off dW1ovT (the weight gradients over the instances), half B off dWqk / gqk (those over the table rows).
-    // At layer 1 the two sources finish ~100 us apart on the side stream, so half A gets a stream of its own and is done
-    // before half B starts.
-    {
-      PfoGemm ca[3], cb[3], c2[3];
-      ca[0] = g_nn(p.wv, C, lw.dW1ovT, D, lw.dW1oT, D, dh, D, C);                          // dW1oT_h = Wv_h dW1ovT_h
-      ca[0].batch = H; ca[0].a_bs[0] = (int64_t)dh * C; ca[0].b_bs[0] = (int64_t)Cp * D; ca[0].c_bs = (int64_t)dh * D;
-      ca[1] = g_nt(lw.W1oT, D, nullptr, lw.dW1ovT, D, g.wv, C, dh, C, D, nullptr);          // dWv_h += W1oT_h dW1ovT_h^T
-      ca[1].batch = H; ca[1].a_bs[0] = (int64_t)dh * D; ca[1].b_bs[0] = (int64_t)Cp * D; ca[1].c_bs = (int64_t)dh * C;
-      ca[1].accumulate = 1;
-      ca[2] = g_nt(lw.W1oT, D, nullptr, lw.dW1ovT + (int64_t)C * D, D, g.b_in + 2 * E, 1, dh, 1, D, nullptr);   // dbv_h += W1oT_h du_h
-      ca[2].batch = H; ca[2].a_bs[0] = (int64_t)dh * D; ca[2].b_bs[0] = (int64_t)Cp * D; ca[2].c_bs = dh;
-      ca[2].accumulate = 1;
-      cb[0] = g_nt(p.wq, E, nullptr, lw.dWqk, D, g.wk, C, dh, C, D, nullptr);               // dWk_h += Wq_h[:, :D] dWqk_h^T
-      cb[0].batch = H; cb[0].a_bs[0] = (int64_t)dh * E; cb[0].b_bs[0] = (int64_t)Cp * D; cb[0].c_bs = (int64_t)dh * C;
-      cb[0].accumulate = 1;
-      cb[1] = g_nn(p.wk, C, lw.dWqk, D, g.wq, E, dh, D, C);                                 // dWq_h[:, :D] += Wk_h dWqk_h
-      cb[1].batch = H; cb[1].a_bs[0] = (int64_t)dh * C; cb[1].b_bs[0] = (int64_t)Cp * D; cb[1].c_bs = (int64_t)dh * E;
-      cb[1].accumulate = 1;
-      cb[2] = g_nt(p.wk, C, nullptr, lw.gqk, C, lw.gq, 1, dh, 1, C, nullptr);                // d cq_h = Wk_h gqk_h
-      cb[2].batch = H; cb[2].a_bs[0] = (int64_t)dh * C; cb[2].b_bs[0] = Cp; cb[2].c_bs = dh;
-      const float* dc = lw.dW1ovT + (int64_t)(C + 1) * D;                                   // gradient of (W1 bo)^T
-      c2[0] = g_nt(lw.dW1oT, D, nullptr, p.wo, E, g.w1, E + D, D, E, E, nullptr);           // dW1[:, :E] += dW1o Wo^T
-      c2[0].a_kmajor = 1; c2[0].accumulate = 1;
-      c2[1] = g_nt(p.w1, E + D, nullptr, lw.dW1oT, D, g.wo, E, E, E, D, nullptr);           // dWo += W1[:, :E]^T dW1o
-      c2[1].a_kmajor = 1; c2[1].accumulate = 1;
-      c2[2] = g_nt(p.w1, E + D, nullptr, dc, D, g.bo, 1, E, 1, D, nullptr);                // dbo += W1[:, :E]^T dc
-      c2[2].a_kmajor = 1; c2[2].accumulate = 1;
-      // the outer-product halves of the composite gradients, one launch per half (disjoint outputs):
-      //   A: W1ovT row C = bv_h^T W1oT_h (into dW1oT, which c2 reads),  dW1[:, :E] += dc (x) bo     B: cqk_h = Wk_h^T cq_h
-      PFO_REQUIRE(H + 1 <= PFO_RANK1_MAX, "too many heads");
-      PfoRank1 ra[PFO_RANK1_MAX], rb[PFO_RANK1_MAX];
-      for (int h = 0; h < H; ++h) {
-        ra[h].u = p.b_in + 2 * E + h * dh; ra[h].ldu = 1; ra[h].v = lw.dW1ovT + ((int64_t)h * Cp + C) * D; ra[h].ldv = 1;
-        ra[h].M = dh; ra[h].N = D; ra[h].out = lw.dW1oT + (int64_t)h * dh * D; ra[h].ldo = D;
-        rb[h].u = lw.cq + h * dh; rb[h].ldu = 1; rb[h].v = lw.gqk + (int64_t)h * Cp; rb[h].ldv = 1;
-        rb[h].M = dh; rb[h].N = C; rb[h].out = g.wk + (int64_t)h * dh * C; rb[h].ldo = C;
-      }
-      ra[H].u = dc; ra[H].ldu = 1; ra[H].v = p.bo; ra[H].ldv = 1; ra[H].M = D; ra[H].N = E; ra[H].out = g.w1; ra[H].ldo = E + D;
-      hipStream_t sa = sd.s2, sb = sd.s2;
-      if (l == 1) {
-        // both sources were launched on side streams (or, bracketed for profiling, the first on the main stream): no need to
-        // hold the chain behind the main stream's d h0 contraction
-        sb = ss;
-        HIPOK(hipStreamWaitEvent(sa, sd.tn_a_done, 0), "event wait failed");
-      }
-      if (l == 1) PFO_MARK("@side2.L1.chainA.begin", sa);
-      RUN(pfo_gemm_multi_launch(ca, 3, sa));
-      RUN(pfo_rank1_multi_launch(ra, H + 1, sa));
-      RUN(pfo_gemm_multi_launch(c2, 3, sa));
-      if (l == 1) PFO_MARK("@side2.L1.chainA.end", sa);
-      else PFO_MARK("@side2.L2.chainA.end", sa);
-      RUN(pfo_gemm_multi_launch(cb, 3, sb));
-      RUN(pfo_rank1_multi_launch(rb, H, sb));
-      if (l == 1) PFO_MARK("@side1.L1.chainB.end", sb);
-      else PFO_MARK("@side2.L2.chainB.end", sb);
-      if (l == L && L >= 2) {
-        // The top layer's folded query-bias backward runs here, on the stream of its chain, with its time-bias term parked in
-        // tb_part (the final launch adds it): from this point every gradient of the top layer's parameter block
-        // [layer[L-1].wq, total) is FINAL - a data-parallel caller starts all-reducing that block while layers L-1 .. 1 are
-        // still being differentiated (pfo_tgn_grad_split, distributed.py)
-        const float* gq1[1] = {lw.gq}; const float* wq1[1] = {p.wq};
-        float* dbq1[1] = {g.b_in}; float* dwq1[1] = {g.wq};
-        RUN(pfo_cq_backward_launch(gq1, wq1, 1, P.tb, D, dbq1, dwq1, G.tb, w.tb_part, nullptr, nullptr, 0, nullptr, sb));
-        if (top_ready_event) HIPOK(hipEventRecord((hipEvent_t)top_ready_event, sb), "event record failed");
-      }
-    }
-      return PFO_OK;
-    };
-    if (l > 1 && !pfo_prof_on()) deferred_chain = chain_back;
-    else RUN(chain_back());
+  if (pfo_prof_on()) {        // event-bracketed step (bench.py's roofline sample): serial, so the bracket times the kernel alone
+    RUN(pfo_gemm_tn_group_launch(lb.ch.tn, lb.n_tn_a, N, nullptr, w.slabs, w.slab_floats, s));
+    HIPOK(hipEventRecord(sd.tn_a_done, s), "event record failed");
+    return PFO_OK;
   }
-  if (deferred_chain) { RUN(deferred_chain()); deferred_chain = nullptr; }
+  if (!bind_events) HIPOK(hipEventRecord(sd.tn_a, s), "event record failed");     // (bound: tn_a rides on the d ctx' launch)
+  HIPOK(hipStreamWaitEvent(ss, sd.tn_a, 0), "event wait failed");
+  RUN(side_mean_once(S));
+  PFO_MARK("@side1.tn_a.begin", ss);
+  RUN(pfo_gemm_tn_group_launch(lb.ch.tn, lb.n_tn_a, N, nullptr, w.slabs2, w.slab_floats, ss));
+  PFO_MARK("@side1.tn_a.end", ss);
+  HIPOK(hipEventRecord(sd.tn_a_done, ss), "event record failed");
+  return PFO_OK;
+}
 
-  // ---- GRU parameters (messages and stored memory are constants: SURVEY App. A-6)
-  bool main_done_bound = false;
-  if (c->use_memory) {
-    PfoRange range_gru("backward GRU");
-    // (the GRU's backward covers the rows the layers read: rows only the extra list names carry no gradient)
-    RUN(pfo_gru_gates_bwd_launch(w.gates, w.gi, w.gh, w.h_rows, w.hm, w.n_core, capP, D, w.d_h0, n_rep, rep_stride,
-                                 w.dx_tab, det, s));
-    PFO_MARK("bwd.gru.gates", s);
-    {
-      PfoTnProblem gp[2];
-      gp[0].A = w.gi; gp[0].lda = 3 * D; gp[0].B = w.msg_rows; gp[0].ldb = d.M; gp[0].M = 3 * D; gp[0].N = d.M;
-      gp[0].C = G.w_ih; gp[0].ldc = d.M; gp[0].bias_out = G.b_ih;
-      gp[1].A = w.gh; gp[1].lda = 3 * D; gp[1].B = w.h_rows; gp[1].ldb = D; gp[1].M = 3 * D; gp[1].N = D;
-      gp[1].C = G.w_hh; gp[1].ldc = D; gp[1].bias_out = G.b_hh;
-      // (a deferred join's main_done event rides on the slab reduce, the caller's stream's last launch of this call)
-      main_done_bound = b->defer_join && bind_events;
-      PFO_RUN_BOUND(main_done_bound, sd.main_done, 1, s, pfo_gemm_tn_group_launch(gp, 2, capP, w.n_core, w.slabs, w.slab_floats, s));
-      PFO_MARK("bwd.gru.tn", s);
-    }
+// Stage 4: the attention core
+static int backward_attn(Step& S, LayerBack& lb) {
+  const Ws& w = S.w; const pfo_tgn_config* c = S.c; const pfo_tgn_batch* b = S.b;
+  hipStream_t s = S.s;
+  const LayerView& v = lb.v;
+  const int l = v.l, D = S.d.D;
+  PfoAttn a = attn_of(S, v);
+  a.nbr_relu = v.folded ? 1 : 0;                               // the keys are h1 rows of the layer below: d row *= (row > 0)
+  a.dctx = w.dctx; a.dQK = v.dqk;
+  if (l == 1) { a.d_nbr = c->use_memory ? w.d_h0 : nullptr; a.d_nbr_ld = D; a.d_nbr_rep = S.rep_stride; a.d_nbr_nrep = S.n_rep; }
+  else        { a.d_nbr = w.dH[l - 1]; a.d_nbr_ld = D; }
+  a.dtime_part = w.dtime;
+  a.det = S.det; a.dtime_slab = w.dtime_slab + S.det_rows * 2 * D;
+  int n_parts = 0;
+  if (l == 1 && c->use_memory && !S.seg_fwd) HIPOK(hipStreamWaitEvent(s, S.sd.seg_done, 0), "event wait failed");   // d_h0 is clear, the groups exist
+  if (l == 1 && c->use_memory && !b->uniform) {
+    // key-side gradients of instances with identical neighbour lists leave as one set of atomics (attn.hip)
+    a.members = w.seg_mem; a.seg_ptr = w.seg_ptr; a.n_rows = w.n_core; a.run_cnt = w.cnt1; a.dqk_live = w.dqk_live;
   }
-  // ---- the last small launches go to the first side stream, beside the GRU's weight gradients on the caller's stream:
-  // [deterministic mode: the attention backwards' slab rows fold, in row order, into bin 0 of the (otherwise empty) fp64 bins]
-  // then ONE launch finishes the time-encoder gradients: the folded query-bias backward of layers 1 .. L-1 (the top layer's ran
-  // with its chain), + its parked time-bias term, + the fold of the fp64 partial sums into time_w / time_b (fixed order).
-  // That stream has seen every attention backward (it waited for tn_b, recorded behind layer 1's) and runs layer 1's chain.
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;
-  const bool chained = cap == hipStreamCaptureStatusNone;
+  lb.dqk_by_member = pfo_attn_bwd_uses_runs(a) ? 1 : 0;
+  RUN(pfo_attn_bwd_launch(a, &n_parts, s));
+  PFO_MARK(LAYER_NAMES[NM_BATTN][l], s);
+  if (l == 1 && b->mid_event && b->mid_event_late) HIPOK(hipEventRecord((hipEvent_t)b->mid_event, s), "event record failed");
+  if (S.det) S.det_rows += n_parts;
+  return PFO_OK;
+}
+
+// Stage 5, layer 1 - merged query/key projection: dx += dqk' Wqk, dWqk = dqk'^T x, gqk = colsum(dqk').  x is a row of the
+// touched-node table shared by all instances on that node, so everything that is linear in the per-instance gradients (dqk',
+// dh1) and otherwise depends on x only - the data gradient of x and the two weight gradients against x - is taken AFTER summing
+// those gradients per table row: contractions over the ~11 k touched rows instead of the ~54 k instances.
+static int backward_table_side(Step& S, const LayerBack& lb) {
+  const Ws& w = S.w; Side& sd = S.sd;
+  hipStream_t s = S.s, ss = S.ss;
+  const LayerWs& lw = *lb.v.lw;
+  const auto& p = S.P.l[1]; const auto& g = S.G.l[1];
+  const int D = S.d.D, E = S.d.E, HCp = S.d.H * S.d.Cp, WQ = HCp + D, capP = S.capP;
+  const bool bind_events = !S.capturing;
+  if (!S.c->use_memory) HIPOK(hipStreamWaitEvent(s, sd.seg_done, 0), "event wait failed");   // (with memory: awaited before the attention backward)
+  PFO_RUN_BOUND(bind_events, sd.tn_b, 0, s,
+                pfo_segsum_launch(lb.v.dqk, HCp, lb.dh1, D, w.seg_ptr, w.seg_mem, w.seg_of, S.n[1], w.n_core, capP, lb.dqk_by_member,
+                                  lb.dqk_by_member ? w.dqk_live : nullptr, w.Dq, s));   // Dq = [sum dqk' | sum dh1]
+  // the weight gradients over the table rows go to the side stream too (beside d h0 / the GRU backward on this one)
+  if (!bind_events) HIPOK(hipEventRecord(sd.tn_b, s), "event record failed");
+  PFO_MARK("bwd.L1.segsum", s);
+  HIPOK(hipStreamWaitEvent(ss, sd.tn_b, 0), "event wait failed");
+  RUN(side_mean_once(S));
+  PfoTnProblem tb[2];
+  tb[0] = tn_of(w.Dq, WQ, w.h0_tab, D, nullptr, HCp, D, lw.dWqk, D, lw.gqk);               // dWqk = (sum dqk')^T h0, gqk
+  tb[0].c_accumulate = 0; tb[0].bias_accumulate = 0;
+  tb[1] = tn_of(w.Dq + HCp, WQ, w.h0_tab, D, nullptr, D, D, g.w1 + E, E + D, g.b1);        // dW1[:, E:], db1
+  // (the layer's chain-back on the side stream needs dWqk / gqk: this launch stays there also while profiling)
+  PFO_MARK("@side1.tn_b.begin", ss);
+  RUN(pfo_gemm_tn_group_launch(tb, 2, capP, w.n_core, w.slabs2, w.slab_floats, ss));
+  PFO_MARK("@side1.tn_b.end", ss);
+  if (S.c->use_memory) {
+    // d h0_tab (query side) = Dq [Wqk ; W1[:, E:]]; the GRU backward adds it to the key-side rows the attention scattered
+    PfoGemm q = g_nn(w.Dq, WQ, lw.Wqk, D, w.dx_tab, D, capP, D, HCp);
+    q.A[1] = w.Dq + HCp; q.lda[1] = WQ; q.B[1] = p.w1 + E; q.ldb[1] = E + D; q.K[1] = D;
+    q.b_img = lw.iWqkT; q.b_img2 = lw.iW1bT; q.m_dev = w.n_core;
+    RUN(pfo_gemm_launch(q, s));
+    PFO_MARK(LAYER_NAMES[NM_DX][1], s);
+  }
+  return PFO_OK;
+}
+// Stage 5, layers >= 2 - d h1 of the layer below, self rows [0, N): [dqk' | dh1] [Q_f ; W1b_f], masked by that layer's ReLU.
+// Both sources in one launch, dx written once.  The launch carries (or is followed by the record of) layer[l], the event that
+// releases the layer's chain on the device.
+static int backward_x_side(const Step& S, LayerBack& lb) {
+  const LayerView& v = lb.v;
+  const int l = v.l, D = S.d.D, HCp = S.d.H * S.d.Cp;
+  const bool bind_events = !S.capturing;
+  PfoGemm q = g_nn(v.dqk, HCp, v.Wqk, D, v.dx, D, v.N, D, HCp);
+  q.A[1] = lb.dh1; q.lda[1] = D; q.B[1] = v.W1b; q.ldb[1] = v.W1b_ld; q.K[1] = D;
+  q.b_img = v.lw->iWqkT; q.b_img2 = v.lw->iW1bT;
+  q.relu_src = v.xA; q.relu_ld = D;
+  PFO_RUN_BOUND(bind_events, S.sd.layer[l], 0, S.s, pfo_gemm_launch(q, S.s));
+  PFO_MARK(LAYER_NAMES[NM_DX][l], S.s);
+  lb.ch.tn[lb.ch.ntn] = tn_of(v.dqk, HCp, v.xA, D, v.x_idx, HCp, D, v.dWqk, D, v.gqk);
+  lb.ch.tn[lb.ch.ntn].c_accumulate = 0; lb.ch.tn[lb.ch.ntn++].bias_accumulate = 0;
+  // (launched by unfold_fc2, on the second side stream in front of the layer's chain: nothing on this stream needs the weight
+  //  gradients of a layer >= 2 - 36 us of launch-latency-bound work off the critical path at C2)
+  if (!bind_events) HIPOK(hipEventRecord(S.sd.layer[l], S.s), "event record failed");
+  return PFO_OK;
+}
+
+// Stage 6, layers >= 2: their weight gradients, then the fc2 fold undone (notation of build_stage_b: A, b = W2, b2 of layer
+// l-1; Q = Wqk, V = W1ovT, per head):
+//   dT1_node = A dQ_f,node      dT1_edge|time = dQ_f,edge|time         dt likewise from gqk_f
+//   dV_node  = A dV_f,node + b (x) dV_f[C]         dV elsewhere = dV_f
+//   dW1b     = dW1b_f A^T + db1_f (x) b            db1 += db1_f
+//   dQ       = dT1 A^T + dt (x) b                  d cqk = dt
+//   dA       = sum_h ( T1_node dQ_f,node^T + t_node (x) gqk_f,node + V_node dV_f,node^T ) + W1b^T dW1b_f + Q^T dT1
+//   db       = sum_h V_node dV_f[C]^T + W1b^T db1_f + Q^T dt
+// The dA / db terms are written to slabs (several heads add to one matrix) and summed once.
+static int unfold_fc2(const Step& S, const Chain& ch) {
+  const Ws& w = S.w; Side& sd = S.sd;
+  const int l = ch.l, N = (int)S.n[l];
+  const LayerWs& lw = w.layer[l];
+  const auto& p = S.P.l[l];
+  const auto &g = S.G.l[l], &gp = S.G.l[l - 1];
+  const int D = S.d.D, H = S.d.H, E = S.d.E, C = S.d.C, Cp = S.d.Cp, HCp = H * Cp;
+  const float *A = S.P.l[l - 1].w2, *bv = S.P.l[l - 1].b2;
+  const int64_t HCpD = (int64_t)HCp * D, CpD = (int64_t)Cp * D, DD = (int64_t)D * D;
+  // (on the second side stream: the first one must stay free for layer 1's weight gradients over the instances)
+  hipStream_t sf = S.s2;
+  HIPOK(hipStreamWaitEvent(sf, sd.layer[l], 0), "event wait failed");
+  if (pfo_prof_on()) {
+    // event-bracketed step (bench.py's roofline sample): on the caller's stream, so that the bracket times the kernel alone
+    RUN(pfo_gemm_tn_group_launch(ch.tn, ch.ntn, N, nullptr, w.slabs, w.slab_floats, S.s));
+    HIPOK(hipEventRecord(sd.layer[l], S.s), "event record failed");
+    HIPOK(hipStreamWaitEvent(sf, sd.layer[l], 0), "event wait failed");
+  } else {
+    RUN(pfo_gemm_tn_group_launch(ch.tn, ch.ntn, N, nullptr, w.slabs3, w.slab_floats, sf));
+  }
+  {
+    PfoSumSlabs cp[3];                        // (one grouped launch instead of three runtime blits, as in build_stage_b)
+    cp[0].dst = lw.dT1;    cp[0].src = lw.dWqk_f;   cp[0].count = HCpD;
+    cp[1].dst = lw.gqk;    cp[1].src = lw.gqk_f;    cp[1].count = HCp;
+    cp[2].dst = lw.dW1ovT; cp[2].src = lw.dW1ovT_f; cp[2].count = HCpD;
+    for (int q = 0; q < 3; ++q) { cp[q].n_slabs = 1; cp[q].accumulate = 0; cp[q].stride = 0; }
+    RUN(pfo_sum_slabs_launch(cp, 3, sf));
+  }
+  float* sl = lw.fold_slabs;
+  float* vs = lw.fold_vslabs;
+  {
+    PfoGemm u[9];
+    u[0] = g_nn(A, D, lw.dWqk_f, D, lw.dT1, D, D, D, D);                                  // dT1_node = A dQ_f,node
+    u[0].batch = H; u[0].b_bs[0] = CpD; u[0].c_bs = CpD;
+    u[1] = g_nt(lw.gqk_f, D, nullptr, A, D, lw.gqk, D, 1, D, D, nullptr);                 // dt_node = A gqk_f,node
+    u[1].batch = H; u[1].a_bs[0] = Cp; u[1].c_bs = Cp;
+    u[2] = g_nt(lw.T1, D, nullptr, lw.dWqk_f, D, sl, D, D, D, D, nullptr);                // slab h: T1_node dQ_f,node^T
+    u[2].batch = H; u[2].a_bs[0] = CpD; u[2].b_bs[0] = CpD; u[2].c_bs = DD;
+    u[3] = g_nt(lw.W1ovT, D, nullptr, lw.dW1ovT_f, D, sl + H * DD, D, D, D, D, nullptr);  // slab H+h: V_node dV_f,node^T
+    u[3].batch = H; u[3].a_bs[0] = CpD; u[3].b_bs[0] = CpD; u[3].c_bs = DD;
+    u[4] = g_nn(p.w1 + E, E + D, lw.dW1b_f, D, sl + 2 * H * DD, D, D, D, D);              // slab 2H: W1b^T dW1b_f
+    u[4].a_kmajor = 1;
+    u[5] = g_nn(A, D, lw.dW1ovT_f, D, lw.dW1ovT, D, D, D, D);                             // dV_node = A dV_f,node
+    u[5].batch = H; u[5].b_bs[0] = CpD; u[5].c_bs = CpD;
+    u[6] = g_nt(lw.dW1ovT_f + (int64_t)C * D, D, nullptr, lw.W1ovT, D, vs, D, 1, D, D, nullptr);   // vslab h: V_node dV_f[C]^T
+    u[6].batch = H; u[6].a_bs[0] = CpD; u[6].b_bs[0] = CpD; u[6].c_bs = D;
+    u[7] = g_nn(lw.db1_f, D, p.w1 + E, E + D, vs + H * D, D, 1, D, D);                    // vslab H: W1b^T db1_f
+    u[8] = g_nt(lw.dW1b_f, D, nullptr, A, D, g.w1 + E, E + D, D, D, D, nullptr);          // dW1[:, E:] += dW1b_f A^T
+    u[8].accumulate = 1;
+    RUN(pfo_gemm_multi_launch(u, 9, sf));
+  }
+  {
+    PfoGemm u[3];
+    u[0] = g_nt(lw.dT1, D, nullptr, A, D, lw.dWqk, D, HCp, D, D, nullptr);                // dQ = dT1 A^T
+    u[1] = g_nn(lw.Wqk, D, lw.dT1, D, sl + (2 * H + 1) * DD, D, D, D, HCp);               // slab 2H+1: Q^T dT1 (all heads' rows)
+    u[1].a_kmajor = 1;
+    u[2] = g_nn(lw.gqk, HCp, lw.Wqk, D, vs + (H + 1) * D, D, 1, D, HCp);                  // vslab H+1: Q^T dt
+    RUN(pfo_gemm_multi_launch(u, 3, sf));
+  }
+  PFO_REQUIRE(H + 3 <= PFO_RANK1_MAX, "too many heads");
+  PfoRank1 r[PFO_RANK1_MAX];
+  int nr = 0;
+  r[nr].u = lw.gqk; r[nr].v = bv; r[nr].M = HCp; r[nr].N = D; r[nr].out = lw.dWqk; r[nr].ldo = D; ++nr;                    // dQ += dt (x) b
+  r[nr].u = lw.db1_f; r[nr].v = bv; r[nr].M = D; r[nr].N = D; r[nr].out = g.w1 + E; r[nr].ldo = E + D; ++nr;               // dW1[:, E:] += db1_f (x) b
+  for (int h = 0; h < H; ++h) {                                                                                             // dV_node += b (x) dV_f[C]
+    r[nr].u = bv; r[nr].v = lw.dW1ovT_f + ((int64_t)h * Cp + C) * D; r[nr].M = D; r[nr].N = D;
+    r[nr].out = lw.dW1ovT + (int64_t)h * CpD; r[nr].ldo = D; ++nr;
+  }
+  RUN(pfo_rank1_multi_launch(r, nr, sf));
+  PfoSumSlabs q[3];
+  q[0].dst = gp.w2; q[0].src = sl; q[0].stride = DD; q[0].count = DD; q[0].n_slabs = 2 * H + 2;                             // dA
+  q[1].dst = gp.b2; q[1].src = vs; q[1].stride = D; q[1].count = D; q[1].n_slabs = H + 2;                                   // db
+  q[2].dst = g.b1; q[2].src = lw.db1_f; q[2].stride = 0; q[2].count = D; q[2].n_slabs = 1;                                  // db1 += db1_f
+  RUN(pfo_sum_slabs_launch(q, 3, sf));
+  PfoRank1 ta;                                                                                                              // dA += sum_h t_node (x) gqk_f,node
+  ta.u = lw.tq; ta.v = lw.gqk_f; ta.M = D; ta.N = D; ta.out = gp.w2; ta.ldo = D; ta.reps = H; ta.u_rs = Cp; ta.v_rs = Cp;
+  return pfo_rank1_multi_launch(&ta, 1, sf);
+}
+
+// Stage 7: the composite-weight gradients chained back to the parameters (tiny products, side streams).
+// Half A hangs off dW1ovT (the weight gradients over the instances), half B off dWqk / gqk (those over the table rows).
+// At layer 1 the two sources finish ~100 us apart on the side stream, so half A gets a stream of its own and is done
+// before half B starts.
+static int chain_composites(const Step& S, int l) {
+  const Ws& w = S.w; Side& sd = S.sd;
+  const LayerWs& lw = w.layer[l];
+  const auto& p = S.P.l[l];
+  const auto& g = S.G.l[l];
+  const int L = S.d.L, D = S.d.D, H = S.d.H, E = S.d.E, C = S.d.C, Cp = S.d.Cp, dh = S.d.dh;
+  PfoGemm ca[3], cb[3], c2[3];
+  ca[0] = g_nn(p.wv, C, lw.dW1ovT, D, lw.dW1oT, D, dh, D, C);                          // dW1oT_h = Wv_h dW1ovT_h
+  ca[0].batch = H; ca[0].a_bs[0] = (int64_t)dh * C; ca[0].b_bs[0] = (int64_t)Cp * D; ca[0].c_bs = (int64_t)dh * D;
+  ca[1] = g_nt(lw.W1oT, D, nullptr, lw.dW1ovT, D, g.wv, C, dh, C, D, nullptr);          // dWv_h += W1oT_h dW1ovT_h^T
+  ca[1].batch = H; ca[1].a_bs[0] = (int64_t)dh * D; ca[1].b_bs[0] = (int64_t)Cp * D; ca[1].c_bs = (int64_t)dh * C;
+  ca[1].accumulate = 1;
+  ca[2] = g_nt(lw.W1oT, D, nullptr, lw.dW1ovT + (int64_t)C * D, D, g.b_in + 2 * E, 1, dh, 1, D, nullptr);   // dbv_h += W1oT_h du_h
+  ca[2].batch = H; ca[2].a_bs[0] = (int64_t)dh * D; ca[2].b_bs[0] = (int64_t)Cp * D; ca[2].c_bs = dh;
+  ca[2].accumulate = 1;
+  cb[0] = g_nt(p.wq, E, nullptr, lw.dWqk, D, g.wk, C, dh, C, D, nullptr);               // dWk_h += Wq_h[:, :D] dWqk_h^T
+  cb[0].batch = H; cb[0].a_bs[0] = (int64_t)dh * E; cb[0].b_bs[0] = (int64_t)Cp * D; cb[0].c_bs = (int64_t)dh * C;
+  cb[0].accumulate = 1;
+  cb[1] = g_nn(p.wk, C, lw.dWqk, D, g.wq, E, dh, D, C);                                 // dWq_h[:, :D] += Wk_h dWqk_h
+  cb[1].batch = H; cb[1].a_bs[0] = (int64_t)dh * C; cb[1].b_bs[0] = (int64_t)Cp * D; cb[1].c_bs = (int64_t)dh * E;
+  cb[1].accumulate = 1;
+  cb[2] = g_nt(p.wk, C, nullptr, lw.gqk, C, lw.gq, 1, dh, 1, C, nullptr);                // d cq_h = Wk_h gqk_h
+  cb[2].batch = H; cb[2].a_bs[0] = (int64_t)dh * C; cb[2].b_bs[0] = Cp; cb[2].c_bs = dh;
+  const float* dc = lw.dW1ovT + (int64_t)(C + 1) * D;                                   // gradient of (W1 bo)^T
+  c2[0] = g_nt(lw.dW1oT, D, nullptr, p.wo, E, g.w1, E + D, D, E, E, nullptr);           // dW1[:, :E] += dW1o Wo^T
+  c2[0].a_kmajor = 1; c2[0].accumulate = 1;
+  c2[1] = g_nt(p.w1, E + D, nullptr, lw.dW1oT, D, g.wo, E, E, E, D, nullptr);           // dWo += W1[:, :E]^T dW1o
+  c2[1].a_kmajor = 1; c2[1].accumulate = 1;
+  c2[2] = g_nt(p.w1, E + D, nullptr, dc, D, g.bo, 1, E, 1, D, nullptr);                // dbo += W1[:, :E]^T dc
+  c2[2].a_kmajor = 1; c2[2].accumulate = 1;
+  // the outer-product halves of the composite gradients, one launch per half (disjoint outputs):
+  //   A: W1ovT row C = bv_h^T W1oT_h (into dW1oT, which c2 reads),  dW1[:, :E] += dc (x) bo     B: cqk_h = Wk_h^T cq_h
+  PFO_REQUIRE(H + 1 <= PFO_RANK1_MAX, "too many heads");
+  PfoRank1 ra[PFO_RANK1_MAX], rb[PFO_RANK1_MAX];
+  for (int h = 0; h < H; ++h) {
+    ra[h].u = p.b_in + 2 * E + h * dh; ra[h].ldu = 1; ra[h].v = lw.dW1ovT + ((int64_t)h * Cp + C) * D; ra[h].ldv = 1;
+    ra[h].M = dh; ra[h].N = D; ra[h].out = lw.dW1oT + (int64_t)h * dh * D; ra[h].ldo = D;
+    rb[h].u = lw.cq + h * dh; rb[h].ldu = 1; rb[h].v = lw.gqk + (int64_t)h * Cp; rb[h].ldv = 1;
+    rb[h].M = dh; rb[h].N = C; rb[h].out = g.wk + (int64_t)h * dh * C; rb[h].ldo = C;
+  }
+  ra[H].u = dc; ra[H].ldu = 1; ra[H].v = p.bo; ra[H].ldv = 1; ra[H].M = D; ra[H].N = E; ra[H].out = g.w1; ra[H].ldo = E + D;
+  hipStream_t sa = S.s2, sb = S.s2;
+  if (l == 1) {
+    // both sources were launched on side streams (or, bracketed for profiling, the first on the main stream): no need to
+    // hold the chain behind the main stream's d h0 contraction
+    sb = S.ss;
+    HIPOK(hipStreamWaitEvent(sa, sd.tn_a_done, 0), "event wait failed");
+  }
+  if (l == 1) PFO_MARK("@side2.L1.chainA.begin", sa);
+  RUN(pfo_gemm_multi_launch(ca, 3, sa));
+  RUN(pfo_rank1_multi_launch(ra, H + 1, sa));
+  RUN(pfo_gemm_multi_launch(c2, 3, sa));
+  if (l == 1) PFO_MARK("@side2.L1.chainA.end", sa);
+  else PFO_MARK("@side2.L2.chainA.end", sa);
+  RUN(pfo_gemm_multi_launch(cb, 3, sb));
+  RUN(pfo_rank1_multi_launch(rb, H, sb));
+  if (l == 1) PFO_MARK("@side1.L1.chainB.end", sb);
+  else PFO_MARK("@side2.L2.chainB.end", sb);
+  if (l == L && L >= 2) {
+    // The top layer's folded query-bias backward runs here, on the stream of its chain, with its time-bias term parked in
+    // tb_part (the final launch adds it): from this point every gradient of the top layer's parameter block
+    // [layer[L-1].wq, total) is FINAL - a data-parallel caller starts all-reducing that block while layers L-1 .. 1 are
+    // still being differentiated (pfo_tgn_grad_split, distributed.py)
+    const float* gq1[1] = {lw.gq}; const float* wq1[1] = {p.wq};
+    float* dbq1[1] = {g.b_in}; float* dwq1[1] = {g.wq};
+    RUN(pfo_cq_backward_launch(gq1, wq1, 1, S.P.tb, D, dbq1, dwq1, S.G.tb, w.tb_part, nullptr, nullptr, 0, nullptr, sb));
+    if (S.top_ready_event) HIPOK(hipEventRecord((hipEvent_t)S.top_ready_event, sb), "event record failed");
+  }
+  return PFO_OK;
+}
+// ~15 launches that no launch of the caller's stream waits for (stages 6 and 7 of one layer)
+static int chain_back(const Step& S, const Chain& ch) {
+  if (ch.l >= 2) RUN(unfold_fc2(S, ch));
+  return chain_composites(S, ch.l);
+}
+
+// Stage 8: GRU parameters (messages and stored memory are constants: SURVEY App. A-6)
+static int backward_gru(const Step& S, bool* main_done_bound) {
+  PfoRange range_gru("backward GRU");
+  const Ws& w = S.w;
+  const int D = S.d.D, M = S.d.M;
+  // (the GRU's backward covers the rows the layers read: rows only the extra list names carry no gradient)
+  RUN(pfo_gru_gates_bwd_launch(w.gates, w.gi, w.gh, w.h_rows, w.hm, w.n_core, S.capP, D, w.d_h0, S.n_rep, S.rep_stride,
+                               w.dx_tab, S.det, S.s));
+  PFO_MARK("bwd.gru.gates", S.s);
+  PfoTnProblem gp[2];
+  gp[0] = tn_of(w.gi, 3 * D, w.msg_rows, M, nullptr, 3 * D, M, S.G.w_ih, M, S.G.b_ih);
+  gp[1] = tn_of(w.gh, 3 * D, w.h_rows, D, nullptr, 3 * D, D, S.G.w_hh, D, S.G.b_hh);
+  // (a deferred join's main_done event rides on the slab reduce, the caller's stream's last launch of this call)
+  *main_done_bound = S.b->defer_join && !S.capturing;
+  PFO_RUN_BOUND(*main_done_bound, S.sd.main_done, 1, S.s, pfo_gemm_tn_group_launch(gp, 2, S.capP, w.n_core, w.slabs, w.slab_floats, S.s));
+  PFO_MARK("bwd.gru.tn", S.s);
+  return PFO_OK;
+}
+
+// Stage 9: the last small launches go to the first side stream, beside the GRU's weight gradients on the caller's stream:
+// [deterministic mode: the attention backwards' slab rows fold, in row order, into bin 0 of the (otherwise empty) fp64 bins]
+// then ONE launch finishes the time-encoder gradients: the folded query-bias backward of layers 1 .. L-1 (the top layer's ran
+// with its chain), + its parked time-bias term, + the fold of the fp64 partial sums into time_w / time_b (fixed order).
+// That stream has seen every attention backward (it waited for tn_b, recorded behind layer 1's) and runs layer 1's chain.
+// Then the closing join.
+static int backward_close(const Step& S, bool main_done_bound) {
+  const Ws& w = S.w; Side& sd = S.sd;
+  hipStream_t s = S.s, ss = S.ss;
+  const int L = S.d.L, D = S.d.D;
+  const bool chained = !S.capturing;
   // The side streams are joined in a chain - the first waits for the second, the caller's stream for the first: one wait on
   // the critical path instead of two - except while the caller's stream is being captured into a HIP graph, where that
   // topology makes hipStreamEndCapture of ROCm 7.0 segfault: there the caller's stream waits for both itself.
-  HIPOK(hipEventRecord(sd.done2, sd.s2), "event record failed");
+  HIPOK(hipEventRecord(sd.done2, S.s2), "event record failed");
   HIPOK(hipStreamWaitEvent(chained ? ss : s, sd.done2, 0), "event wait failed");
   if (!chained) {                                             // (the launches below read the second side stream's results)
     HIPOK(hipEventRecord(sd.tn_a, s), "event record failed");
     HIPOK(hipStreamWaitEvent(ss, sd.tn_a, 0), "event wait failed");
   }
-  if (det) RUN(pfo_fold_parts_launch(w.dtime_slab, (int)det_rows, 2 * D, nullptr, 0, w.fold_scratch, w.tickets, ss, w.dtime));
-  {
-    const float *gq[PFO_MAX_LAYERS], *wq[PFO_MAX_LAYERS];
-    float *dbq[PFO_MAX_LAYERS], *dwq[PFO_MAX_LAYERS];
-    const int nl = L >= 2 ? L - 1 : L;
-    for (int l = 1; l <= nl; ++l) { gq[l - 1] = w.layer[l].gq; wq[l - 1] = P.l[l].wq; dbq[l - 1] = G.l[l].b_in; dwq[l - 1] = G.l[l].wq; }
-    RUN(pfo_cq_backward_launch(gq, wq, nl, P.tb, D, dbq, dwq, G.tb, nullptr, L >= 2 ? w.tb_part : nullptr, w.dtime,
-                               pfo_attn_bwd_max_parts(), G.tw, ss));                  // cq = Wq[:, D:] cos(b) + bq
-  }
+  if (S.det) RUN(pfo_fold_parts_launch(w.dtime_slab, (int)S.det_rows, 2 * D, nullptr, 0, w.fold_scratch, w.tickets, ss, w.dtime));
+  const float *gq[PFO_MAX_LAYERS], *wq[PFO_MAX_LAYERS];
+  float *dbq[PFO_MAX_LAYERS], *dwq[PFO_MAX_LAYERS];
+  const int nl = L >= 2 ? L - 1 : L;
+  for (int l = 1; l <= nl; ++l) { gq[l - 1] = w.layer[l].gq; wq[l - 1] = S.P.l[l].wq; dbq[l - 1] = S.G.l[l].b_in; dwq[l - 1] = S.G.l[l].wq; }
+  RUN(pfo_cq_backward_launch(gq, wq, nl, S.P.tb, D, dbq, dwq, S.G.tb, nullptr, L >= 2 ? w.tb_part : nullptr, w.dtime,
+                             pfo_attn_bwd_max_parts(), S.G.tw, ss));                  // cq = Wq[:, D:] cos(b) + bq
   PFO_MARK("@side1.cq.end", ss);
-  if (b->defer_join && chained && bind_events) {               // (bind_events: not under capture - side_join)
+  if (S.b->defer_join && chained) {                            // (not under capture - side_join)
     // the end of the backward stays on the side stream (pfo_tgn_batch.defer_join): it waits for the caller's stream's last
     // launch instead of the other way round - the caller's stream is free for the next batch's neighbour sampling
     if (!main_done_bound) HIPOK(hipEventRecord(sd.main_done, s), "event record failed");
@@ -1493,9 +1444,60 @@ extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state*
     HIPOK(hipEventRecord(sd.done, ss), "event record failed");
     HIPOK(hipStreamWaitEvent(s, sd.done, 0), "event wait failed");
   }
-  PFO_MARK("bwd.end", s);
   return PFO_OK;
 }
+
+extern "C" int pfo_tgn_backward(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, void* workspace,
+                                const float* d_emb, float* grad, void* stream) {
+  return pfo_tgn_backward_ev(c, st, b, workspace, d_emb, grad, 0, nullptr, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int pfo_tgn_backward_ev(const pfo_tgn_config* c, const pfo_tgn_state* st, const pfo_tgn_batch* b, void* workspace,
+                                   const float* d_emb, float* grad, int32_t zero_grad_first, void* top_ready_event,
+                                   const float* mean_src, int64_t mean_n, float* mean_out, void* stream) {
+  if (int rc = check_cfg(c)) return rc;
+  PFO_REQUIRE(st && workspace && d_emb && grad && st->params, "null argument");
+  PFO_REQUIRE(!mean_src || (mean_n > 0 && mean_out), "bad deferred mean");
+  Step S(side());
+  RUN(open_step(S, c, st, b, workspace, stream));      // (the composites and images the forward used)
+  bind(S.lay, grad, S.G, S.d.L, c->use_memory != 0);
+  S.d_emb = d_emb; S.top_ready_event = top_ready_event;
+  S.mean_src = mean_src; S.mean_n = mean_n; S.mean_out = mean_out;
+  S.seg_fwd = b->seg_in_forward && b->upd_src != nullptr && c->use_memory && S.d.L >= 2;
+
+  PfoRange range_call("pfo_tgn_backward");
+  PFO_REQUIRE(S.sd.ok, "could not create the side stream");
+  RUN(side_join(S.sd, S.s));
+  PFO_MARK("bwd.begin", S.s);
+  // (the gradient buffer is cleared on the caller's stream, before the fork: every writer on any stream comes after it)
+  if (zero_grad_first) HIPOK(hipMemsetAsync(grad, 0, (size_t)S.lay.total * sizeof(float), S.s), "memset failed");
+  RUN(backward_open(S));
+  // A layer's chain back to the parameters: for a layer >= 2 the HOST issues it only after the next layer's data-gradient
+  // launches are queued (r3 timeline: the caller's stream sat idle for ~60 us behind them while the host was the slower side);
+  // the event that releases it on the device (layer[l]) stays where it was.  (Layer 1 never waits: nothing is left pending.)
+  Chain pending;
+  for (int l = S.d.L; l >= 1; --l) {
+    PfoRange range_layer(LAYER_NAMES[NM_BWD][l]);
+    LayerBack lb;
+    lb.v = layer_view(S, l);
+    lb.ch.l = l;
+    if (l == S.d.L) RUN(backward_top_dh1(S, lb));
+    else lb.dh1 = S.w.dH[l];
+    RUN(backward_dctx(S, lb));
+    RUN(backward_attn(S, lb));
+    if (pending.l) { RUN(chain_back(S, pending)); pending.l = 0; }     // the layer above's chain-back (side streams)
+    if (l == 1) RUN(backward_table_side(S, lb));
+    else RUN(backward_x_side(S, lb));
+    if (l > 1 && !pfo_prof_on()) pending = lb.ch;
+    else RUN(chain_back(S, lb.ch));
+  }
+  bool main_done_bound = false;
+  if (c->use_memory) RUN(backward_gru(S, &main_done_bound));
+  RUN(backward_close(S, main_done_bound));
+  PFO_MARK("bwd.end", S.s);
+  return PFO_OK;
+}
+
 
 int pfo_adam_step_ranges_impl(float*, float*, float*, float*, int32_t, const int64_t*, const int64_t*, const int32_t*, float, float, float,
                               float, bool, void*);
@@ -1628,9 +1630,7 @@ extern "C" int pfo_tgn_observe(const pfo_tgn_config* c, const pfo_tgn_state* st,
   // GRU weight images: the parameter cache's when it is valid, else built here, once - parameters cannot change inside a call
   const void *iWih = o.iWih, *iWhh = o.iWhh;
   if (st->pcache && st->pcache_valid) {
-    Ws pw;
-    memset(&pw, 0, sizeof(pw));
-    pcache_bind(c, st->pcache, pw);
+    const Ws pw = carve(c, nullptr, st->pcache, true);
     iWih = pw.iWih; iWhh = pw.iWhh;
   } else {
     Ws bw;
