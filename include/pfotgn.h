@@ -802,6 +802,32 @@ int pfo_debug_bimg(const pfo_bimg_desc* list, int32_t n, void* stream);
 int pfo_debug_gru_fused(const pfo_gru_desc* f, void* stream);
 int pfo_debug_rank1_multi(const pfo_rank1_desc* list, int32_t n, void* stream);
 int pfo_debug_sum_slabs(const pfo_sum_slabs_desc* list, int32_t n, void* stream);
+/* The launchers' dispatch, asked without launching (additive: the abi version stays).  pfo_debug_gemm_plan /
+ * pfo_debug_gemm_tn_group_plan return what pfo_debug_gemm / pfo_debug_gemm_tn_group would do with the same arguments - pure
+ * host code, the function the launchers themselves switch on: the form below, or -1 (with the launcher's own message) where
+ * the launcher refuses.  Operand layout (a_kmajor / b_kmajor) and `vec` are flags beside the form, not part of it.
+ * out[PFO_GEMM_PLAN_INTS] = form, vec (float4 operand loads: the fp32 kernels' flag), grid x, y, z, block, nsplit, chunk
+ * (split-K: slabs and k-rows per slab; 1 and 0 where the launch does not split), profiler kind (PFO_PROF_*) of the contraction
+ * kernel.  PFO_GEMM_FORM_TN_GROUP: a k-major launch pfo_gemm_launch hands to the grouped split-K launch as one problem -
+ * nsplit / chunk are the sizing that made it do so, grid, block are 0 and kind is -1 (the grouped plan of that problem has
+ * them).  PFO_GEMM_FORM_MULTI names pfo_gemm_multi_launch's one kernel; it has no query (its only decision is `vec`, which the
+ * single-problem query reports per problem). */
+#define PFO_GEMM_FORM_F32_128 0     /* gemm_f32_kernel, 128-row tiles                         */
+#define PFO_GEMM_FORM_F32_32 1      /* gemm_f32_kernel, 32-row tiles                          */
+#define PFO_GEMM_FORM_SKINNY4 2     /* gemm_bx_skinny_kernel<4, 1>: 32 rows x 64 columns      */
+#define PFO_GEMM_FORM_SKINNY11 3    /* gemm_bx_skinny_kernel<11, 1>: 32 rows x 176 columns    */
+#define PFO_GEMM_FORM_AREG 4        /* gemm_bx_areg_kernel<1>                                 */
+#define PFO_GEMM_FORM_AREG8 5       /* gemm_bx_areg8_kernel<1>: eight wavefronts              */
+#define PFO_GEMM_FORM_ASTAT 6       /* gemm_bx_astat_kernel: A-stationary                     */
+#define PFO_GEMM_FORM_TN_GROUP 7    /* handed to the grouped split-K launch                   */
+#define PFO_GEMM_FORM_TN_F32 8      /* gemm_tn_group_kernel                                   */
+#define PFO_GEMM_FORM_TN_BX 9       /* gemm_tn_group_bx_kernel<1>: 128-row tiles              */
+#define PFO_GEMM_FORM_TN_BX8 10     /* gemm_tn_group_bx_kernel<1, 8>: 256-row tiles           */
+#define PFO_GEMM_FORM_MULTI 11      /* gemm_multi_kernel                                      */
+#define PFO_GEMM_PLAN_INTS 9
+int32_t pfo_debug_gemm_plan(const pfo_gemm_desc* g, int32_t* out /* HOST, PFO_GEMM_PLAN_INTS */);
+int32_t pfo_debug_gemm_tn_group_plan(const pfo_tn_desc* probs, int32_t n, int32_t K, int64_t slab_floats,
+                                     int32_t* out /* HOST, PFO_GEMM_PLAN_INTS */);
 
 /* debug / test probes of the internal attention interface (csrc/attn.hpp) and of the grouping its run-merged backward
  * consumes (csrc/memory.hpp pfo_seg_build_launch).  As above: the struct mirrors PfoAttn field for field, every call forwards

@@ -108,6 +108,9 @@ class AttnDesc(C.Structure):
                 ("members", _FP), ("seg_ptr", _FP), ("n_rows", _FP), ("run_cnt", _FP)]
 
 
+# PFO_GEMM_FORM_* and the fields of a plan query's out[PFO_GEMM_PLAN_INTS]
+GEMM_FORMS = ["f32_128", "f32_32", "skinny4", "skinny11", "areg", "areg8", "astat", "tn_group", "tn_f32", "tn_bx", "tn_bx8", "multi"]
+GEMM_PLAN_FIELDS = ["form", "vec", "grid_x", "grid_y", "grid_z", "block", "nsplit", "chunk", "kind"]
 ATTN_FORMS = ["fwd_ring", "fwd_reg", "bwd_runs", "bwd_ring_none", "bwd_ring_direct", "bwd_none", "bwd_atomic", "bwd_det", "bwd_direct"]
 
 
@@ -213,6 +216,8 @@ PROTOTYPES = {
     "pfo_debug_gemm": (C.c_int, [C.POINTER(GemmDesc), _VP]),
     "pfo_debug_gemm_multi": (C.c_int, [C.POINTER(GemmDesc), C.c_int32, _VP]),
     "pfo_debug_gemm_tn_group": (C.c_int, [C.POINTER(TnDesc), C.c_int32, C.c_int32, _VP, _VP, C.c_int64, _VP]),
+    "pfo_debug_gemm_plan": (C.c_int32, [C.POINTER(GemmDesc), C.POINTER(C.c_int32)]),
+    "pfo_debug_gemm_tn_group_plan": (C.c_int32, [C.POINTER(TnDesc), C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "pfo_debug_bimg_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "pfo_debug_gru_img_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "pfo_debug_bimg": (C.c_int, [C.POINTER(BimgDesc), C.c_int32, _VP]),
@@ -348,6 +353,19 @@ def byte_count(name, *args):
     if n < 0:
         raise PfoError("%s: %s" % (name, lib.pfo_last_error().decode()))
     return n
+
+
+def gemm_plan(name, *args):
+    """A ``pfo_debug_gemm*_plan`` query: its ``out`` array as a dict, ``form`` by its name in ``GEMM_FORMS`` and ``kind`` by its
+    name in ``PROF_KINDS``; ``PfoError`` with the launcher's message where the launcher would refuse the arguments."""
+    lib = load()
+    out = (C.c_int32 * len(GEMM_PLAN_FIELDS))()
+    if getattr(lib, name)(*args, out) < 0:
+        raise PfoError("%s: %s" % (name, lib.pfo_last_error().decode()))
+    plan = dict(zip(GEMM_PLAN_FIELDS, out))
+    plan["form"] = GEMM_FORMS[plan["form"]]
+    plan["kind"] = PROF_KINDS[plan["kind"]] if plan["kind"] >= 0 else None
+    return plan
 
 
 _GPU_SEEN = [False]

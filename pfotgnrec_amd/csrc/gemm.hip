@@ -57,6 +57,7 @@ struct GemmDev {
 static bool aligned4(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // launch thresholds of the dispatch (pfo_gemm_launch, pfo_gemm_tn_group_launch)
+constexpr int F32_BIG_MIN_TILES = 400;   // row-major launches of the fp32 kernel: fewer 128 x 176 tiles take its 32-row tile (a threshold of its own)
 constexpr int BX_MIN_TILES = 400;   // row-major launches with images: fewer 128 x 176 tiles take the 32-row kernel, more the 128-row ones
 constexpr int BX_AREG8_MIN = 512;   // ... the 128-row form as eight single-strip wavefronts (gemm_bx_areg8_kernel) from this many tiles on
 constexpr int TN8_MIN_ROWS = 500;   // weight-gradient launches whose problems all have >= this many rows take 256-row tiles
@@ -2071,7 +2072,7 @@ struct TnGroupDev {
   float* slabs;
 };
 
-template <bool VEC>
+// (scalar loads: operands that admit float4 loads take the bf16x3 kernel below)
 __global__ __launch_bounds__(GEMM_THREADS) void gemm_tn_group_kernel(const TnGroupDev g) {
   GEMM_LDS_DECL;
   int q = 0;
@@ -2095,7 +2096,7 @@ __global__ __launch_bounds__(GEMM_THREADS) void gemm_tn_group_kernel(const TnGro
   d.slab_base = g.slabs + pr.slab_off - (int64_t)0;
   d.nsplit = g.nsplit > 1 ? g.nsplit : 2;
   d.dyn_chunk = (g.k_dev != nullptr && g.nsplit > 1) ? 1 : 0;
-  gemm_tile<true, true, 0, VEC>(d, t / pr.tn, t % pr.tn, 0, blockIdx.y, lds_a, lds_b);
+  gemm_tile<true, true, 0, false>(d, t / pr.tn, t % pr.tn, 0, blockIdx.y, lds_a, lds_b);
 }
 
 // shader-clock pair of the grouped weight-gradient kernel (common.hpp pfo_clock_*)
@@ -2180,63 +2181,204 @@ __global__ __launch_bounds__(256) void tn_group_reduce_kernel(const TnGroupDev g
   }
 }
 
-int pfo_gemm_tn_group_launch(const PfoTnProblem* probs, int n, int K, const int32_t* k_dev, float* slabs,
-                             int64_t slab_floats, hipStream_t stream) {
-  PFO_REQUIRE(n >= 1 && n <= TN_MAX_PROBLEMS && K > 0 && probs && slabs, "bad arguments");
-  TnGroupDev g;
-  memset(&g, 0, sizeof(g));
-  bool vec = true;
-  int tiles = 0;
-  // 256-row tiles of eight wavefronts (one workgroup per CU) when every problem is at least that tall
-  bool tn8 = true;
-  for (int i = 0; i < n; ++i) {
-    const PfoTnProblem& q = probs[i];
-    tn8 = tn8 && q.M >= TN8_MIN_ROWS && aligned4(q.A) && aligned4(q.B) && (q.lda % 4) == 0 && (q.ldb % 4) == 0 && (q.M % 4) == 0 && (q.N % 4) == 0;
+// ---------------------------------------------------------------------------------------------
+// The dispatch.  What a launcher decides before it touches the device is one plain record, filled by a pure function of the
+// descriptor: pointers are tested for null and alignment and never followed, no HIP call is made.  The launcher switches on
+// the record and the pfo_*_plan queries (gemm.hpp) return it, so the tests' statement of the rule is held to the rule that runs.
+struct GemmPlan {
+  int form = -1;                 // PFO_GEMM_FORM_*
+  bool vec = false;              // float4 operand loads (the fp32 kernels' template flag)
+  dim3 grid;
+  int block = GEMM_THREADS;
+  int kind = -1;                 // PFO_PROF_* of the contraction kernel
+  int nsplit = 1, chunk = 0;     // split-K
+  int xcd_tm = 0, xcd_tn = 0;    // pfo_gemm_launch: GemmDev's tile order
+  int b_img_rows = 0;            // pfo_gemm_launch: > 0 = an image kernel reads b_img / b_img2
+  int xcd_map = 0, tiles = 0;    // the grouped launch: TnGroupDev's grid order, tiles of one split ...
+  int64_t per_split = 0;         // ... and floats of one split's slabs
+  struct { int tile_begin, tn; int64_t slab_off; } prob[TN_MAX_PROBLEMS];
+};
+// a refusal names the launcher the plan belongs to (`who`), as it did when the checks stood in the launcher's body
+#define PLAN_REQUIRE(cond, msg)                                                                  \
+  do { if (!(cond)) { pfo_set_error("%s: %s", who, msg); return PFO_ERR_INVALID; } } while (0)
+
+// K in nsplit chunks of whole k-tiles: at most `want` of them and none that four k-tiles would not fill
+static void split_k(int K, int64_t want, int& nsplit, int& chunk) {
+  nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(want, pfo_ceil_div(K, 4 * BK)));
+  chunk = (int)pfo_align_up(pfo_ceil_div(K, nsplit), BK);
+  nsplit = (int)pfo_ceil_div(K, chunk);
+}
+
+// float4 loads of the A operands / of the B operands of every source in use
+static void gemm_vec_ok(const PfoGemm& g, bool& a_vec, bool& b_vec) {
+  a_vec = b_vec = true;
+  for (int s = 0; s < 2; ++s) {
+    if (s == 1 && g.K[1] == 0) continue;
+    a_vec = a_vec && aligned4(g.A[s]) && (g.lda[s] % 4) == 0 && (g.a_bs[s] % 4) == 0 &&
+            (g.a_kmajor ? (g.M % 4) == 0 : (g.K[s] % 4) == 0);
+    b_vec = b_vec && aligned4(g.B[s]) && (g.ldb[s] % 4) == 0 && (g.b_bs[s] % 4) == 0 &&
+            (g.b_kmajor ? (g.N % 4) == 0 : (g.K[s] % 4) == 0);
   }
-  // workgroups the split count is sized for: 2 per CU in the 128-row form (768 = 3 per CU also fits: LDS 3 x 49.6 KB, 3 x 120 registers)
-  const int tbm = tn8 ? 256 : BM, slots = tn8 ? 256 : 512;
-  int64_t per_split = 0;
+}
+
+static int gemm_plan(const PfoGemm& g, GemmPlan& p) {
+  const char* const who = "pfo_gemm_launch";
+  PLAN_REQUIRE(g.M > 0 && g.N > 0 && g.K[0] > 0 && g.batch >= 1, "bad sizes");
+  PLAN_REQUIRE(g.A[0] && g.B[0] && g.C, "null operand");
+  PLAN_REQUIRE(g.K[1] == 0 || (g.A[1] && g.B[1]), "null operand (source 2)");
+  bool a_vec, b_vec;
+  gemm_vec_ok(g, a_vec, b_vec);
+  p.vec = a_vec && b_vec;
+  // the launch takes an image kernel (below) exactly when this holds; what those kernels, or the fp32 one, would not read
+  // is refused, not dropped
+  const bool img_launch = !g.a_kmajor && g.b_img && (g.K[1] == 0 || g.b_img2) && a_vec && g.batch == 1;
+  // b_idx gathers the k rows of a k-major B in the fp32 kernel; a weight image is built from the ungathered operand
+  PLAN_REQUIRE(!g.b_idx || (g.b_kmajor && !img_launch), "b_idx needs a k-major B and a launch that takes no weight image");
+  PLAN_REQUIRE(!g.a_kmajor || (!g.a_idx[0] && !g.a_idx[1]), "a_idx needs a row-major A");
+  // the row-gathered addend exists in the epilogue of the image kernels only
+  PLAN_REQUIRE(!g.add_src || img_launch, "add_src needs a weight-image launch (row-major 16-byte aligned A, b_img, batch 1)");
+  p.kind = g.m_dev ? PFO_PROF_GEMM_DEVM : (g.a_kmajor ? PFO_PROF_GEMM_TN : (g.b_kmajor ? PFO_PROF_GEMM_NN : PFO_PROF_GEMM_NT));
+  const int tm = (int)pfo_ceil_div(g.M, BM), tn = (int)pfo_ceil_div(g.N, BN);
+  if (g.a_kmajor) {
+    PLAN_REQUIRE(g.K[1] == 0, "k-major A supports one source");
+    // weight gradient: few output tiles, long K -> split K over workgroups, deterministic slab reduce
+    int nsplit, chunk;
+    split_k(g.K[0], (int)pfo_ceil_div(512, (int64_t)tm * tn * g.batch), nsplit, chunk);
+    if (nsplit > 1 && g.b_kmajor && g.slabs) {
+      // the weight-gradient form goes through the grouped split-K launch (one problem), which plans its own grid and split
+      PLAN_REQUIRE(g.batch == 1, "split-K with batch is not supported");
+      PLAN_REQUIRE(!g.bias && !g.relu && !g.row_zero && !g.relu_src, "split-K takes no epilogue");
+      p.form = PFO_GEMM_FORM_TN_GROUP; p.nsplit = nsplit; p.chunk = chunk; p.grid = dim3(0, 0, 0); p.block = 0; p.kind = -1;
+      return PFO_OK;
+    }
+    p.form = PFO_GEMM_FORM_F32_128; p.grid = dim3(tm, tn, g.batch);
+    return PFO_OK;
+  }
+  const int64_t big_tiles = (int64_t)tm * tn * g.batch;
+  if (!img_launch) {
+    // the caller fused two sources whose float B operands may differ in layout: only the image kernels can take that
+    if (g.K[1] > 0 && g.b_img2) {
+      pfo_set_error("%s: a two-source launch with weight images needs 16-byte aligned row-major A operands", who);
+      return PFO_ERR_INVALID;
+    }
+    // tile rows per workgroup: 128, or 32 for launches where 128-row tiles would leave most of the 256 CUs without work
+    const bool small = big_tiles < F32_BIG_MIN_TILES;
+    p.form = small ? PFO_GEMM_FORM_F32_32 : PFO_GEMM_FORM_F32_128;
+    p.grid = dim3((unsigned)pfo_ceil_div(g.M, small ? 32 : BM), tn, g.batch);
+    return PFO_OK;
+  }
+  // the split contraction on the caller's pre-split image of B (pfo_bimg_launch): 32-row workgroups for launches of fewer
+  // than BX_MIN_TILES 128-row tiles, the 128-row kernels above (bx_force: tests pick one)
+  p.b_img_rows = (int)pfo_align_up(g.N, BN);
+  if (g.bx_force == 2 || (!g.bx_force && big_tiles < BX_MIN_TILES)) {
+    p.kind = PFO_PROF_GEMM_BX_SKINNY;
+    // few row tiles (< one per CU even with 176-column workgroups): 64-column workgroups fill the chip three times better
+    const int64_t rows = pfo_ceil_div(g.M, SK_ROWS);
+    const bool narrow = rows * tn < 512;
+    p.form = narrow ? PFO_GEMM_FORM_SKINNY4 : PFO_GEMM_FORM_SKINNY11;
+    p.grid = dim3((unsigned)rows, narrow ? (unsigned)pfo_ceil_div(g.N, 64) : tn, 1);
+    return PFO_OK;
+  }
+  p.kind = PFO_PROF_GEMM_BX;
+  p.grid = dim3((unsigned)tm, tn, 1);
+  if (tn > 1) { p.xcd_tm = tm; p.xcd_tn = tn; p.grid = dim3((unsigned)(pfo_ceil_div(tm, 8) * 8 * tn), 1, 1); }
+  // short contraction, many columns, plain stores: the A-stationary form (gemm_bx_astat_kernel)
+  const bool astat = g.K[1] == 0 && g.K[0] <= AS_TMAX * BK && (g.N % 32) == 0 && g.N >= 352 && g.N <= AS_NMAX && (g.ldc % 4) == 0 &&
+                     aligned4(g.C) && !g.bias && !g.relu && !g.relu_src && !g.add_src && !g.accumulate && !g.row_scale && !g.row_zero &&
+                     g.M >= 128 * 256;
+  // (eight single-strip wavefronts from BX_AREG8_MIN workgroups on; below one workgroup per slot the four-wavefront form's
+  //  fewer barriers win - QX / GRU shapes at 470 workgroups: 32.0 against 35.7 us)
+  if (astat) { p.form = PFO_GEMM_FORM_ASTAT; p.grid = dim3((unsigned)pfo_ceil_div(g.M, 128)); }
+  else if (big_tiles >= BX_AREG8_MIN) { p.form = PFO_GEMM_FORM_AREG8; p.block = 512; }
+  else p.form = PFO_GEMM_FORM_AREG;
+  return PFO_OK;
+}
+
+static int tn_group_plan(const PfoTnProblem* probs, int n, int K, int64_t slab_floats, GemmPlan& p) {
+  const char* const who = "pfo_gemm_tn_group_launch";
+  PLAN_REQUIRE(n >= 1 && n <= TN_MAX_PROBLEMS && K > 0 && probs, "bad arguments");
+  // flattened tile starts with 128-row tiles [0] and with 256-row tiles of eight wavefronts [1] (one workgroup per CU): the
+  // latter when every problem admits float4 loads and is at least TN8_MIN_ROWS tall
+  int begin[2][TN_MAX_PROBLEMS], tiles[2] = {0, 0};
+  bool vec = true, tall = true;
   for (int i = 0; i < n; ++i) {
     const PfoTnProblem& s = probs[i];
-    PFO_REQUIRE(s.A && s.B && s.C && s.M > 0 && s.N > 0, "bad problem");
+    PLAN_REQUIRE(s.A && s.B && s.C && s.M > 0 && s.N > 0, "bad problem");
+    vec = vec && aligned4(s.A) && aligned4(s.B) && (s.lda % 4) == 0 && (s.ldb % 4) == 0 && (s.M % 4) == 0 && (s.N % 4) == 0;
+    tall = tall && s.M >= TN8_MIN_ROWS;
+    const int N = s.N + (s.bias_out ? 1 : 0);     // the bias gradient is carried as column N
+    p.prob[i].tn = (int)pfo_ceil_div(N, BN);
+    for (int h = 0; h < 2; ++h) { begin[h][i] = tiles[h]; tiles[h] += (int)pfo_ceil_div(s.M, BM << h) * p.prob[i].tn; }
+    p.prob[i].slab_off = p.per_split;             // scaled by nsplit below
+    p.per_split += (int64_t)s.M * N;
+  }
+  const int tn8 = vec && tall;
+  p.vec = vec;
+  p.tiles = tiles[tn8];
+  // one full round of resident workgroups, never a nearly empty second one: 2 per CU x 256 CUs in the 128-row form (768 = 3 per
+  // CU also fits: LDS 3 x 49.6 KB, 3 x 120 registers)
+  split_k(K, (tn8 ? 256 : 512) / std::max(1, p.tiles), p.nsplit, p.chunk);
+  PLAN_REQUIRE(slab_floats >= p.per_split * p.nsplit, "split-K workspace too small");
+  for (int i = 0; i < n; ++i) { p.prob[i].tile_begin = begin[tn8][i]; p.prob[i].slab_off *= p.nsplit; }
+  p.form = !vec ? PFO_GEMM_FORM_TN_F32 : (tn8 ? PFO_GEMM_FORM_TN_BX8 : PFO_GEMM_FORM_TN_BX);
+  p.kind = !vec ? PFO_PROF_GEMM_TN : (tn8 ? PFO_PROF_GEMM_TN_BX8 : PFO_PROF_GEMM_TN_BX);
+  p.block = tn8 ? 512 : GEMM_THREADS;
+  p.xcd_map = vec && p.nsplit > 1;
+  p.grid = p.xcd_map ? dim3(p.tiles * p.nsplit, 1) : dim3(p.tiles, p.nsplit);
+  return PFO_OK;
+}
+
+// the queries: the plan as int32 out[PFO_GEMM_PLAN_INTS] (include/pfotgn.h); the form, or -1 with the launcher's message
+static int plan_out(const GemmPlan& p, int32_t* out) {
+  const int32_t v[PFO_GEMM_PLAN_INTS] = {p.form, p.vec, (int32_t)p.grid.x, (int32_t)p.grid.y, (int32_t)p.grid.z, p.block, p.nsplit, p.chunk, p.kind};
+  memcpy(out, v, sizeof(v));
+  return p.form;
+}
+int pfo_gemm_plan(const PfoGemm& g, int32_t* out) {
+  GemmPlan p;
+  return gemm_plan(g, p) == PFO_OK ? plan_out(p, out) : -1;
+}
+int pfo_gemm_tn_group_plan(const PfoTnProblem* probs, int n, int K, int64_t slab_floats, int32_t* out) {
+  GemmPlan p;
+  return tn_group_plan(probs, n, K, slab_floats, p) == PFO_OK ? plan_out(p, out) : -1;
+}
+
+int pfo_gemm_tn_group_launch(const PfoTnProblem* probs, int n, int K, const int32_t* k_dev, float* slabs,
+                             int64_t slab_floats, hipStream_t stream) {
+  PFO_REQUIRE(slabs, "bad arguments");
+  GemmPlan p;
+  if (int rc = tn_group_plan(probs, n, K, slab_floats, p)) return rc;
+  TnGroupDev g;
+  memset(&g, 0, sizeof(g));
+  double flops = 0;
+  for (int i = 0; i < n; ++i) {
+    const PfoTnProblem& s = probs[i];
     TnProbDev& d = g.p[i];
     d.A = s.A; d.lda = s.lda; d.B = s.B; d.ldb = s.ldb; d.b_idx = s.b_idx;
     d.C = s.C; d.ldc = s.ldc;
     d.bias_out = s.bias_out; d.bias_accumulate = s.bias_accumulate; d.c_accumulate = s.c_accumulate;
     d.M = s.M; d.N_real = s.N; d.N = s.N + (s.bias_out ? 1 : 0);
-    d.tn = (int)pfo_ceil_div(d.N, BN);
-    d.tile_begin = tiles;
-    tiles += (int)pfo_ceil_div(d.M, tbm) * d.tn;
-    d.slab_off = per_split;            // scaled by nsplit below
-    per_split += (int64_t)d.M * d.N;
-    vec = vec && aligned4(s.A) && aligned4(s.B) && (s.lda % 4) == 0 && (s.ldb % 4) == 0 && (s.M % 4) == 0 && (s.N % 4) == 0;
+    d.tn = p.prob[i].tn; d.tile_begin = p.prob[i].tile_begin; d.slab_off = p.prob[i].slab_off;
+    flops += 2.0 * s.M * s.N * (double)K;
   }
-  // one full round of resident workgroups (2 per CU x 256 CUs), never a nearly empty second one
-  int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(slots / std::max(1, tiles), pfo_ceil_div(K, 4 * BK)));
-  int chunk = (int)pfo_align_up(pfo_ceil_div(K, nsplit), BK);
-  nsplit = (int)pfo_ceil_div(K, chunk);
-  PFO_REQUIRE(slab_floats >= per_split * nsplit, "split-K workspace too small");
-  for (int i = 0; i < n; ++i) g.p[i].slab_off *= nsplit;
-  g.n = n; g.K = K; g.nsplit = nsplit; g.chunk = chunk; g.total_tiles = tiles; g.k_dev = k_dev; g.slabs = slabs;
-  double flops = 0;
-  for (int i = 0; i < n; ++i) flops += 2.0 * probs[i].M * probs[i].N * (double)K;
-  const bool use_bx = vec;
+  g.n = n; g.K = K; g.nsplit = p.nsplit; g.chunk = p.chunk; g.total_tiles = p.tiles; g.k_dev = k_dev; g.slabs = slabs;
+  g.xcd_map = p.xcd_map;
+  const bool bx = p.form != PFO_GEMM_FORM_TN_F32;
   pfo_prof_begin(stream);
-  g.xcd_map = use_bx && nsplit > 1;
-  const dim3 grid_bx = g.xcd_map ? dim3(tiles * nsplit, 1) : dim3(tiles, nsplit);
-  if (use_bx && tn8) PFO_KLAUNCH((gemm_tn_group_bx_kernel<1, 8>), grid_bx, dim3(512), 0, stream, g);
-  else if (use_bx) PFO_KLAUNCH(gemm_tn_group_bx_kernel<1>, grid_bx, dim3(GEMM_THREADS), 0, stream, g);
-  else if (vec) PFO_KLAUNCH(gemm_tn_group_kernel<true>, dim3(tiles, nsplit), dim3(GEMM_THREADS), 0, stream, g);
-  else PFO_KLAUNCH(gemm_tn_group_kernel<false>, dim3(tiles, nsplit), dim3(GEMM_THREADS), 0, stream, g);
+  switch (p.form) {
+    case PFO_GEMM_FORM_TN_BX8: PFO_KLAUNCH((gemm_tn_group_bx_kernel<1, 8>), p.grid, dim3(p.block), 0, stream, g); break;
+    case PFO_GEMM_FORM_TN_BX: PFO_KLAUNCH(gemm_tn_group_bx_kernel<1>, p.grid, dim3(p.block), 0, stream, g); break;
+    default: PFO_KLAUNCH(gemm_tn_group_kernel, p.grid, dim3(p.block), 0, stream, g); break;
+  }
   PFO_LAUNCH_CHECK();
   // the GEMM kernel alone; with a device-side K bound the work is (flops per k-row) x the count read back at collect time
-  if (use_bx) pfo_prof_end_dev(tn8 ? PFO_PROF_GEMM_TN_BX8 : PFO_PROF_GEMM_TN_BX, flops / (double)K, k_dev, K, stream);
-  if (use_bx) pfo_prof_begin(stream);                           // the slab fold is a family of its own: slabs in, matrices out
-  PFO_KLAUNCH(tn_group_reduce_kernel, dim3((unsigned)std::min<int64_t>(1024, pfo_ceil_div(per_split, 256))), dim3(256), 0,
+  if (bx) pfo_prof_end_dev(p.kind, flops / (double)K, k_dev, K, stream);
+  if (bx) pfo_prof_begin(stream);                               // the slab fold is a family of its own: slabs in, matrices out
+  PFO_KLAUNCH(tn_group_reduce_kernel, dim3((unsigned)std::min<int64_t>(1024, pfo_ceil_div(p.per_split, 256))), dim3(256), 0,
                      stream, g);
   PFO_LAUNCH_CHECK();
-  if (!use_bx) pfo_prof_end_dev(PFO_PROF_GEMM_TN, flops / (double)K, k_dev, K, stream);
-  else pfo_prof_end(PFO_PROF_TN_REDUCE, (double)per_split * (nsplit + 1) * sizeof(float), stream);
+  if (!bx) pfo_prof_end_dev(p.kind, flops / (double)K, k_dev, K, stream);
+  else pfo_prof_end(PFO_PROF_TN_REDUCE, (double)p.per_split * (p.nsplit + 1) * sizeof(float), stream);
   return PFO_OK;
 }
 
@@ -2299,117 +2441,45 @@ int pfo_bimg_launch(const PfoBimg* list, int n, hipStream_t stream) {
 
 
 int pfo_gemm_launch(const PfoGemm& g, hipStream_t stream) {
-  PFO_REQUIRE(g.M > 0 && g.N > 0 && g.K[0] > 0 && g.batch >= 1, "bad sizes");
-  PFO_REQUIRE(g.A[0] && g.B[0] && g.C, "null operand");
-  bool a_vec = true, b_vec = true;
-  for (int s = 0; s < 2; ++s) {
-    if (s == 1 && g.K[1] == 0) continue;
-    PFO_REQUIRE(g.A[s] && g.B[s], "null operand (source 2)");
-    a_vec = a_vec && aligned4(g.A[s]) && (g.lda[s] % 4) == 0 && (g.a_bs[s] % 4) == 0 &&
-            (g.a_kmajor ? (g.M % 4) == 0 : (g.K[s] % 4) == 0);
-    b_vec = b_vec && aligned4(g.B[s]) && (g.ldb[s] % 4) == 0 && (g.b_bs[s] % 4) == 0 &&
-            (g.b_kmajor ? (g.N % 4) == 0 : (g.K[s] % 4) == 0);
+  GemmPlan p;
+  if (int rc = gemm_plan(g, p)) return rc;
+  if (p.form == PFO_GEMM_FORM_TN_GROUP) {
+    PfoTnProblem q;
+    q.A = g.A[0]; q.lda = g.lda[0]; q.B = g.B[0]; q.ldb = g.ldb[0]; q.b_idx = g.b_idx; q.M = g.M; q.N = g.N;
+    q.C = g.C; q.ldc = g.ldc; q.c_accumulate = g.accumulate;
+    return pfo_gemm_tn_group_launch(&q, 1, g.K[0], g.m_dev, g.slabs, g.slab_floats, stream);
   }
   GemmDev d;
   to_dev(g, d);
-  const bool vec = a_vec && b_vec;
-  // the launch takes an image kernel (below) exactly when this holds; what those kernels, or the fp32 one, would not read
-  // is refused, not dropped
-  const bool img_launch = !g.a_kmajor && g.b_img && (g.K[1] == 0 || g.b_img2) && a_vec && g.batch == 1;
-  // b_idx gathers the k rows of a k-major B in the fp32 kernel; a weight image is built from the ungathered operand
-  PFO_REQUIRE(!g.b_idx || (g.b_kmajor && !img_launch), "b_idx needs a k-major B and a launch that takes no weight image");
-  PFO_REQUIRE(!g.a_kmajor || (!g.a_idx[0] && !g.a_idx[1]), "a_idx needs a row-major A");
-  // the row-gathered addend exists in the epilogue of the image kernels only
-  PFO_REQUIRE(!g.add_src || img_launch, "add_src needs a weight-image launch (row-major 16-byte aligned A, b_img, batch 1)");
-  const double flops = 2.0 * g.M * g.N * ((double)g.K[0] + g.K[1]) * g.batch;
-  int kind = g.m_dev ? PFO_PROF_GEMM_DEVM : (g.a_kmajor ? PFO_PROF_GEMM_TN : (g.b_kmajor ? PFO_PROF_GEMM_NN : PFO_PROF_GEMM_NT));
+  d.xcd_tm = p.xcd_tm; d.xcd_tn = p.xcd_tn;
+  if (p.b_img_rows) { d.b_img = g.b_img; d.b_img_rows = p.b_img_rows; d.b_img2 = g.b_img2; }
+  const dim3 block(p.block);
   pfo_prof_begin(stream);
-  const int tn = (int)pfo_ceil_div(g.N, BN);
-#define GEMM_GO(AK, BK_, SM, grid)                                                                                   \
+#define GEMM_GO(AK, BK_, SM)                                                                                         \
   do {                                                                                                                \
-    if (vec) PFO_KLAUNCH((gemm_f32_kernel<AK, BK_, SM, true>), grid, dim3(GEMM_THREADS), 0, stream, d);        \
-    else PFO_KLAUNCH((gemm_f32_kernel<AK, BK_, SM, false>), grid, dim3(GEMM_THREADS), 0, stream, d);           \
+    if (p.vec) PFO_KLAUNCH((gemm_f32_kernel<AK, BK_, SM, true>), p.grid, block, 0, stream, d);                       \
+    else PFO_KLAUNCH((gemm_f32_kernel<AK, BK_, SM, false>), p.grid, block, 0, stream, d);                            \
   } while (0)
-  if (g.a_kmajor) {
-    const int tm = (int)pfo_ceil_div(g.M, BM);
-    PFO_REQUIRE(g.K[1] == 0, "k-major A supports one source");
-    // weight gradient: few output tiles, long K -> split K over workgroups, deterministic slab reduce
-    const int K = g.K[0];
-    int want = (int)pfo_ceil_div(512, (int64_t)tm * tn * g.batch);
-    int nsplit = (int)std::max<int64_t>(1, std::min<int64_t>(want, pfo_ceil_div(K, 4 * BK)));
-    int chunk = (int)pfo_align_up(pfo_ceil_div(K, nsplit), BK);
-    nsplit = (int)pfo_ceil_div(K, chunk);
-    if (nsplit > 1 && g.b_kmajor && g.slabs) {
-      // the weight-gradient form goes through the grouped split-K launch (one problem)
-      PFO_REQUIRE(g.batch == 1, "split-K with batch is not supported");
-      PFO_REQUIRE(!g.bias && !g.relu && !g.row_zero && !g.relu_src, "split-K takes no epilogue");
-      PfoTnProblem q;
-      q.A = g.A[0]; q.lda = g.lda[0]; q.B = g.B[0]; q.ldb = g.ldb[0]; q.b_idx = g.b_idx; q.M = g.M; q.N = g.N;
-      q.C = g.C; q.ldc = g.ldc; q.c_accumulate = g.accumulate;
-      return pfo_gemm_tn_group_launch(&q, 1, K, g.m_dev, g.slabs, g.slab_floats, stream);
-    }
-    if (g.b_kmajor) GEMM_GO(true, true, 0, dim3(tm, tn, g.batch)); else GEMM_GO(true, false, 0, dim3(tm, tn, g.batch));
-  } else {
-    // tile rows per workgroup: 128 (BIG) or 32 (SMALL: launches where 128-row tiles would leave most of the 256 CUs
-    // without work)
-    const int64_t big_tiles = (int64_t)pfo_ceil_div(g.M, BM) * tn * g.batch;
-    const int tile = big_tiles < 400 ? 1 : 0;
-    const int rows = tile == 1 ? 32 : BM;
-    const dim3 grid((unsigned)pfo_ceil_div(g.M, rows), tn, g.batch);
-    // the split contraction on the caller's pre-split image of B (pfo_bimg_launch): 32-row workgroups for launches of fewer
-    // than BX_MIN_TILES 128-row tiles, the 128-row kernels above (bx_force: tests pick one)
-    const bool img_ok = img_launch;
-    if (img_ok && (g.bx_force == 2 || (!g.bx_force && big_tiles < BX_MIN_TILES))) {
-      d.b_img = g.b_img; d.b_img_rows = (int)pfo_align_up(g.N, BN); d.b_img2 = g.b_img2;
-      kind = PFO_PROF_GEMM_BX_SKINNY;
-      // few row tiles (< one per CU even with 176-column workgroups): 64-column workgroups fill the chip three times better
-      const int64_t sk_wgs = (int64_t)pfo_ceil_div(g.M, SK_ROWS) * tn;
-      const dim3 g4((unsigned)pfo_ceil_div(g.M, SK_ROWS), (unsigned)pfo_ceil_div(g.N, 64), 1), g11((unsigned)pfo_ceil_div(g.M, SK_ROWS), tn, 1);
-      if (sk_wgs < 512) PFO_KLAUNCH((gemm_bx_skinny_kernel<4, 1>), g4, dim3(GEMM_THREADS), 0, stream, d);
-      else PFO_KLAUNCH((gemm_bx_skinny_kernel<11, 1>), g11, dim3(GEMM_THREADS), 0, stream, d);
-    } else if (img_ok) {
-      d.b_img = g.b_img; d.b_img_rows = (int)pfo_align_up(g.N, BN); d.b_img2 = g.b_img2;
-      kind = PFO_PROF_GEMM_BX;
-      const int tmr = (int)pfo_ceil_div(g.M, BM);
-      dim3 grid_x((unsigned)tmr, tn, 1);
-      if (tn > 1) { d.xcd_tm = tmr; d.xcd_tn = (int)tn; grid_x = dim3((unsigned)(pfo_ceil_div(tmr, 8) * 8 * tn), 1, 1); }
-      // short contraction, many columns, plain stores: the A-stationary form (gemm_bx_astat_kernel)
-      const bool astat = g.K[1] == 0 && g.K[0] <= AS_TMAX * BK && (g.N % 32) == 0 && g.N >= 352 && g.N <= AS_NMAX && (g.ldc % 4) == 0 &&
-                         aligned4(g.C) && !g.bias && !g.relu && !g.relu_src && !g.add_src && !g.accumulate && !g.row_scale && !g.row_zero &&
-                         g.M >= 128 * 256;
-      // (eight single-strip wavefronts from BX_AREG8_MIN workgroups on; below one workgroup per slot the four-wavefront form's
-      //  fewer barriers win - QX / GRU shapes at 470 workgroups: 32.0 against 35.7 us)
-      if (astat) PFO_KLAUNCH(gemm_bx_astat_kernel, dim3((unsigned)pfo_ceil_div(g.M, 128)), dim3(GEMM_THREADS), 0, stream, d);
-      else if (big_tiles >= BX_AREG8_MIN) PFO_KLAUNCH(gemm_bx_areg8_kernel<1>, grid_x, dim3(512), 0, stream, d);
-      else PFO_KLAUNCH(gemm_bx_areg_kernel<1>, grid_x, dim3(GEMM_THREADS), 0, stream, d);
-    } else if (g.K[1] > 0 && g.b_img2) {
-      // the caller fused two sources whose float B operands may differ in layout: only the image kernels can take that
-      pfo_set_error("pfo_gemm_launch: a two-source launch with weight images needs 16-byte aligned row-major A operands");
-      return PFO_ERR_INVALID;
-    } else if (g.b_kmajor) {
-      if (tile == 1) GEMM_GO(false, true, 1, grid); else GEMM_GO(false, true, 0, grid);
-    } else {
-      if (tile == 1) GEMM_GO(false, false, 1, grid); else GEMM_GO(false, false, 0, grid);
-    }
+  switch (p.form) {
+    case PFO_GEMM_FORM_F32_128:
+      if (g.a_kmajor) { if (g.b_kmajor) GEMM_GO(true, true, 0); else GEMM_GO(true, false, 0); }
+      else if (g.b_kmajor) GEMM_GO(false, true, 0);
+      else GEMM_GO(false, false, 0);
+      break;
+    case PFO_GEMM_FORM_F32_32: if (g.b_kmajor) GEMM_GO(false, true, 1); else GEMM_GO(false, false, 1); break;
+    case PFO_GEMM_FORM_SKINNY4: PFO_KLAUNCH((gemm_bx_skinny_kernel<4, 1>), p.grid, block, 0, stream, d); break;
+    case PFO_GEMM_FORM_SKINNY11: PFO_KLAUNCH((gemm_bx_skinny_kernel<11, 1>), p.grid, block, 0, stream, d); break;
+    case PFO_GEMM_FORM_ASTAT: PFO_KLAUNCH(gemm_bx_astat_kernel, p.grid, block, 0, stream, d); break;
+    case PFO_GEMM_FORM_AREG8: PFO_KLAUNCH(gemm_bx_areg8_kernel<1>, p.grid, block, 0, stream, d); break;
+    case PFO_GEMM_FORM_AREG: PFO_KLAUNCH(gemm_bx_areg_kernel<1>, p.grid, block, 0, stream, d); break;
   }
 #undef GEMM_GO
   PFO_LAUNCH_CHECK();
   // a device-side extent (rows, or the K of a k-major A) scales the work: read back when the records are collected
-  if (g.m_dev) pfo_prof_end_dev(kind, flops / (double)(g.a_kmajor ? g.K[0] : g.M), g.m_dev, g.a_kmajor ? g.K[0] : g.M, stream);
-  else pfo_prof_end(kind, flops, stream);
+  const double flops = 2.0 * g.M * g.N * ((double)g.K[0] + g.K[1]) * g.batch;
+  if (g.m_dev) pfo_prof_end_dev(p.kind, flops / (double)(g.a_kmajor ? g.K[0] : g.M), g.m_dev, g.a_kmajor ? g.K[0] : g.M, stream);
+  else pfo_prof_end(p.kind, flops, stream);
   return PFO_OK;
-}
-
-static bool gemm_vec_ok(const PfoGemm& g) {
-  bool a_vec = true, b_vec = true;
-  for (int s = 0; s < 2; ++s) {
-    if (s == 1 && g.K[1] == 0) continue;
-    a_vec = a_vec && aligned4(g.A[s]) && (g.lda[s] % 4) == 0 && (g.a_bs[s] % 4) == 0 &&
-            (g.a_kmajor ? (g.M % 4) == 0 : (g.K[s] % 4) == 0);
-    b_vec = b_vec && aligned4(g.B[s]) && (g.ldb[s] % 4) == 0 && (g.b_bs[s] % 4) == 0 &&
-            (g.b_kmajor ? (g.N % 4) == 0 : (g.K[s] % 4) == 0);
-  }
-  return a_vec && b_vec;
 }
 
 int pfo_gemm_multi_launch(const PfoGemm* list, int n, hipStream_t stream) {
@@ -2431,7 +2501,9 @@ int pfo_gemm_multi_launch(const PfoGemm* list, int n, hipStream_t stream) {
       g.tn[i] = (int)pfo_ceil_div(s.N, 64);            // gemm_tile's TINY shape: 32 x 64
       g.tile_begin[i] = tiles;
       tiles += g.tm[i] * g.tn[i] * s.batch;
-      vec = vec && gemm_vec_ok(s);
+      bool a_vec, b_vec;
+      gemm_vec_ok(s, a_vec, b_vec);
+      vec = vec && a_vec && b_vec;
     }
     g.n = cnt;
     double mflops = 0;

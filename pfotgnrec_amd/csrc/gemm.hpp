@@ -105,3 +105,9 @@ struct PfoTnProblem {
 // all problems share the K extent (and its optional device-side bound); one GEMM launch + one reduce launch
 int pfo_gemm_tn_group_launch(const PfoTnProblem* probs, int n, int K, const int32_t* k_dev, float* slabs,
                              int64_t slab_floats, hipStream_t stream);
+
+// What pfo_gemm_launch / pfo_gemm_tn_group_launch would do with these arguments: pure host code (pointers are tested for null
+// and alignment, never followed), the function the launchers themselves dispatch on.  Returns the form (PFO_GEMM_FORM_*) with
+// out[PFO_GEMM_PLAN_INTS] filled as include/pfotgn.h lays it out, or -1 with the launcher's own message where it would refuse.
+int pfo_gemm_plan(const PfoGemm& g, int32_t* out);
+int pfo_gemm_tn_group_plan(const PfoTnProblem* probs, int n, int K, int64_t slab_floats, int32_t* out);

@@ -41,17 +41,33 @@ extern "C" int pfo_debug_gemm_multi(const pfo_gemm_desc* list, int32_t n, void* 
 }
 
 #define PROBE_TN_MAX 16
-extern "C" int pfo_debug_gemm_tn_group(const pfo_tn_desc* probs, int32_t n, int32_t K, const int32_t* k_dev, float* slabs,
-                                       int64_t slab_floats, void* stream) {
-  PFO_REQUIRE(probs && n >= 1 && n <= PROBE_TN_MAX, "bad problem list");
-  PfoTnProblem q[PROBE_TN_MAX];
+static void to_tn(const pfo_tn_desc* probs, int n, PfoTnProblem* q) {
   for (int i = 0; i < n; ++i) {
     const pfo_tn_desc& s = probs[i];
     q[i].A = s.A; q[i].lda = s.lda; q[i].B = s.B; q[i].ldb = s.ldb; q[i].b_idx = s.b_idx; q[i].M = s.M; q[i].N = s.N;
     q[i].C = s.C; q[i].ldc = s.ldc; q[i].c_accumulate = s.c_accumulate;
     q[i].bias_out = s.bias_out; q[i].bias_accumulate = s.bias_accumulate;
   }
+}
+extern "C" int pfo_debug_gemm_tn_group(const pfo_tn_desc* probs, int32_t n, int32_t K, const int32_t* k_dev, float* slabs,
+                                       int64_t slab_floats, void* stream) {
+  PFO_REQUIRE(probs && n >= 1 && n <= PROBE_TN_MAX, "bad problem list");
+  PfoTnProblem q[PROBE_TN_MAX];
+  to_tn(probs, n, q);
   return pfo_gemm_tn_group_launch(q, n, K, k_dev, slabs, slab_floats, (hipStream_t)stream);
+}
+
+extern "C" int32_t pfo_debug_gemm_plan(const pfo_gemm_desc* g, int32_t* out) {
+  if (!g || !out) { pfo_set_error("%s: null argument", __func__); return -1; }
+  PfoGemm q;
+  to_gemm(*g, q);
+  return pfo_gemm_plan(q, out);
+}
+extern "C" int32_t pfo_debug_gemm_tn_group_plan(const pfo_tn_desc* probs, int32_t n, int32_t K, int64_t slab_floats, int32_t* out) {
+  if (!probs || n < 1 || n > PROBE_TN_MAX || !out) { pfo_set_error("%s: bad problem list", __func__); return -1; }
+  PfoTnProblem q[PROBE_TN_MAX];
+  to_tn(probs, n, q);
+  return pfo_gemm_tn_group_plan(q, n, K, slab_floats, out);
 }
 
 extern "C" int64_t pfo_debug_bimg_bytes(int32_t N, int32_t K) {

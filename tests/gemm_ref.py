@@ -185,6 +185,119 @@ def tn_group_ref(probs, K, k_dev=None, a_block=None, b_block=176):
     return res
 
 
+# ------------------------------------------------------------------------------------------------ the launchers' dispatch
+# The rule by which pfo_gemm_launch and pfo_gemm_tn_group_launch pick a kernel, a grid and a K split, stated here a second time
+# and independently of gemm.hip: tests/test_gemm_plan_cpu.py holds it to the library's own answer (pfo_debug_gemm_plan /
+# pfo_debug_gemm_tn_group_plan, the function the launchers switch on) over a sweep that sits on every threshold below, so a
+# change of the rule on one side alone fails there - on the CPU, without a launch.  The descriptors are the ctypes structs of
+# pfotgnrec_amd/_lib.py (or anything with their fields); a pointer is an integer or None and is never followed.
+BM, BN, BK = 128, 176, 32                        # the workgroup tile: rows, columns, k-rows
+F32_BIG_MIN_TILES = 400                          # fp32 kernel, row-major A: 128-row tiles from this many 128 x 176 tiles on, else 32-row
+BX_MIN_TILES, BX_AREG8_MIN = 400, 512            # image launches: the 128-row kernels from / their eight-wavefront form from
+SK_ROWS, SK_WIDE_MIN_WGS = 32, 512               # the 32-row image kernel: 176-column workgroups from this many of them on, else 64
+AS_KMAX, AS_NMIN, AS_NMAX, AS_MMIN = 6 * BK, 352, 1024, 128 * 256      # the A-stationary form's shape window
+SPLIT_WGS, SPLIT_MIN_KTILES = 512, 4             # a k-major launch splits K towards this many workgroups, >= 4 k-tiles a slab
+TN8_MIN_ROWS, TN_SLOTS, TN8_SLOTS = 500, 512, 256                      # grouped launches: 256-row tiles when every M >= ...; workgroup slots
+
+
+class PlanRefused(Exception):
+    """The launcher refuses the descriptor; str() is a word of its message."""
+
+
+def cdiv(a, b):
+    return -(-a // b)
+
+
+def _aligned(p):
+    return (p or 0) % 16 == 0
+
+
+def split_k(K, want):
+    """(nsplit, chunk): at most ``want`` slabs of whole k-tiles, sized evenly, none planned below SPLIT_MIN_KTILES k-tiles."""
+    nsplit = max(1, min(want, cdiv(K, SPLIT_MIN_KTILES * BK)))
+    chunk = cdiv(cdiv(K, nsplit), BK) * BK
+    return cdiv(K, chunk), chunk
+
+
+def gemm_plan_ref(g):
+    """What pfo_gemm_launch does with descriptor ``g``: dict(form, vec, grid_x, grid_y, grid_z, block, nsplit, chunk, kind), form
+    a name of _lib.GEMM_FORMS and kind one of _lib.PROF_KINDS - or PlanRefused."""
+    K = (g.K[0], g.K[1])
+    if not (g.M > 0 and g.N > 0 and K[0] > 0 and g.batch >= 1):
+        raise PlanRefused("bad sizes")
+    if not (g.A[0] and g.B[0] and g.C):
+        raise PlanRefused("null operand")
+    srcs = (0, 1) if K[1] != 0 else (0,)
+    if not all(g.A[s] and g.B[s] for s in srcs):
+        raise PlanRefused("source 2")
+    a_vec = all(_aligned(g.A[s]) and g.lda[s] % 4 == 0 and g.a_bs[s] % 4 == 0 and (g.M if g.a_kmajor else K[s]) % 4 == 0 for s in srcs)
+    b_vec = all(_aligned(g.B[s]) and g.ldb[s] % 4 == 0 and g.b_bs[s] % 4 == 0 and (g.N if g.b_kmajor else K[s]) % 4 == 0 for s in srcs)
+    image = bool(not g.a_kmajor and g.b_img and (K[1] == 0 or g.b_img2) and a_vec and g.batch == 1)
+    if g.b_idx and not (g.b_kmajor and not image):
+        raise PlanRefused("b_idx")
+    if g.a_kmajor and (g.a_idx[0] or g.a_idx[1]):
+        raise PlanRefused("a_idx")
+    if g.add_src and not image:
+        raise PlanRefused("add_src")
+    tm, tn = cdiv(g.M, BM), cdiv(g.N, BN)
+    plan = dict(vec=int(a_vec and b_vec), block=256, nsplit=1, chunk=0, grid_z=1,
+                kind="gemm_devm" if g.m_dev else ("gemm_tn" if g.a_kmajor else ("gemm_nn" if g.b_kmajor else "gemm_nt")))
+    if g.a_kmajor:
+        if K[1] != 0:
+            raise PlanRefused("one source")
+        nsplit, chunk = split_k(K[0], cdiv(SPLIT_WGS, tm * tn * g.batch))
+        if nsplit > 1 and g.b_kmajor and g.slabs:
+            if g.batch != 1:
+                raise PlanRefused("split-K with batch")
+            if g.bias or g.relu or g.row_zero or g.relu_src:
+                raise PlanRefused("no epilogue")
+            return dict(plan, form="tn_group", grid_x=0, grid_y=0, grid_z=0, block=0, nsplit=nsplit, chunk=chunk, kind=None)
+        return dict(plan, form="f32_128", grid_x=tm, grid_y=tn, grid_z=g.batch)
+    tiles = tm * tn * g.batch
+    if not image:
+        if K[1] > 0 and g.b_img2:
+            raise PlanRefused("two-source")
+        small = tiles < F32_BIG_MIN_TILES
+        return dict(plan, form="f32_32" if small else "f32_128", grid_x=cdiv(g.M, 32 if small else BM), grid_y=tn, grid_z=g.batch)
+    if g.bx_force == 2 or (g.bx_force == 0 and tiles < BX_MIN_TILES):
+        rows = cdiv(g.M, SK_ROWS)
+        wide = rows * tn >= SK_WIDE_MIN_WGS
+        return dict(plan, form="skinny11" if wide else "skinny4", grid_x=rows, grid_y=tn if wide else cdiv(g.N, 64), kind="gemm_bx_skinny")
+    plain = not (g.bias or g.relu or g.relu_src or g.add_src or g.accumulate or g.row_scale or g.row_zero)
+    if (K[1] == 0 and K[0] <= AS_KMAX and g.N % 32 == 0 and AS_NMIN <= g.N <= AS_NMAX and g.ldc % 4 == 0 and _aligned(g.C) and plain
+            and g.M >= AS_MMIN):
+        return dict(plan, form="astat", grid_x=cdiv(g.M, 128), grid_y=1, kind="gemm_bx")
+    # one column tile: (row tile, column tile) = (x, y); more: a 1-D grid in the XCD tile order, row tiles padded to eights
+    grid = (tm, 1) if tn == 1 else (cdiv(tm, 8) * 8 * tn, 1)
+    eight = tiles >= BX_AREG8_MIN
+    return dict(plan, form="areg8" if eight else "areg", grid_x=grid[0], grid_y=grid[1], block=512 if eight else 256, kind="gemm_bx")
+
+
+def tn_plan_ref(probs, K, slab_floats=None):
+    """What pfo_gemm_tn_group_launch does with the problems (TnDesc-like) over the extent K: the dict of gemm_plan_ref, and
+    ``need`` = the slab floats the launch asks for, ``tile_rows`` = the A columns one workgroup tile takes (128 or 256; None
+    for the fp32 form, which keeps no per-tile scale), ``xcd_map``.  ``slab_floats`` below ``need``: PlanRefused."""
+    n = len(probs)
+    if not (1 <= n <= 16 and K > 0):
+        raise PlanRefused("bad arguments")
+    if not all(q.A and q.B and q.C and q.M > 0 and q.N > 0 for q in probs):
+        raise PlanRefused("bad problem")
+    vec = all(_aligned(q.A) and _aligned(q.B) and q.lda % 4 == 0 and q.ldb % 4 == 0 and q.M % 4 == 0 and q.N % 4 == 0 for q in probs)
+    tn8 = vec and all(q.M >= TN8_MIN_ROWS for q in probs)
+    cols = [q.N + (1 if q.bias_out else 0) for q in probs]                       # the bias gradient rides as one more column
+    rows = 256 if tn8 else BM
+    tiles = sum(cdiv(q.M, rows) * cdiv(c, BN) for q, c in zip(probs, cols))
+    nsplit, chunk = split_k(K, (TN8_SLOTS if tn8 else TN_SLOTS) // max(1, tiles))
+    need = sum(q.M * c for q, c in zip(probs, cols)) * nsplit
+    if slab_floats is not None and slab_floats < need:
+        raise PlanRefused("workspace too small")
+    xcd_map = int(vec and nsplit > 1)                                            # 1-D grid: every tile of one split on one XCD
+    return dict(form="tn_f32" if not vec else ("tn_bx8" if tn8 else "tn_bx"), vec=int(vec), grid_x=tiles * nsplit if xcd_map else tiles,
+                grid_y=1 if xcd_map else nsplit, grid_z=1, block=512 if tn8 else 256, nsplit=nsplit, chunk=chunk,
+                kind="gemm_tn" if not vec else ("gemm_tn_bx8" if tn8 else "gemm_tn_bx"), need=need, tile_rows=rows if vec else None,
+                xcd_map=xcd_map)
+
+
 def gru_ref(msg, h, W_ih, W_hh, b_ih, b_hh, hm, touched, node_feat, n_rows, gather):
     """The lazy GRU of pfo_gru_fused_launch in float64 for rows m < n_rows.  gather = 0: msg / h / hm are packed rows; gather =
     1: they are the per-node tables and row m is node touched[m] of them.  node_feat is always the per-node table.

@@ -29,10 +29,6 @@ DEV = "cuda:0"
 TOL = 4e-6
 f64 = np.float64
 
-# the launchers' rules (gemm.hip: pfo_gemm_launch, pfo_gemm_tn_group_launch), mirrored to derive the shapes below
-BM, BN, BK = 128, 176, 32
-BX_MIN_TILES, BX_AREG8_MIN, TN8_MIN_ROWS, SK_ROWS = 400, 512, 500, 32
-AS_TMAX, AS_NMAX = 6, 1024
 CONTRACTION_KINDS = ["gemm_nt", "gemm_nn", "gemm_tn", "gemm_devm", "gemm_bx", "gemm_tn_bx", "gemm_bx_skinny", "gru_fused", "gemm_multi",
                      "tn_reduce", "gemm_tn_bx8"]
 
@@ -140,13 +136,26 @@ def fill_gemm_desc(b, d, img=False, bx_force=0, mis=()):
     return g, (lambda: c_t[c_off:c_off + n].cpu().numpy())
 
 
-def launch_gemm(d, img=False, bx_force=0, mis=()):
+def gemm_plan(g, form=None):
+    """What the launcher will do with descriptor ``g`` (pfo_debug_gemm_plan: the function pfo_gemm_launch itself switches on),
+    held to the model of tests/gemm_ref.py on this very descriptor; ``form``: the kernel the case was written for."""
+    plan = _lib.gemm_plan("pfo_debug_gemm_plan", C.byref(g))
+    ref = G.gemm_plan_ref(g)
+    assert plan == {k: ref[k] for k in plan}, (plan, ref)
+    assert form is None or plan["form"] == form, (plan["form"], form)
+    return plan
+
+
+def launch_gemm(d, img=False, bx_force=0, mis=(), form=None):
+    """-> (the C buffer after the launch, the profiler families that ran, the launcher's plan); the plan is asked, and ``form``
+    asserted, before anything is launched."""
     b = Bufs()
     g, read = fill_gemm_desc(b, d, img, bx_force, mis)
+    plan = gemm_plan(g, form)
     with profiled() as p:
         _lib.call("pfo_debug_gemm", C.byref(g), _lib.stream_ptr())
         torch.cuda.synchronize()
-    return read(), p.kinds
+    return read(), p.kinds, plan
 
 
 def within(got, ref, mag, tol):
@@ -263,10 +272,6 @@ SKINNY4_SHAPES = [(1, 64, 36, 0), (33, 172, 148, 172), (77, 344, 172, 0), (77, 1
 AREG_SHAPES = [(128, 64, 36, 0), (300, 172, 148, 172), (300, 344, 172, 0), (128, 177, 36, 172), (300, 64, 172, 172), (128, 344, 148, 172)]
 
 
-def skinny_wgs(M, N):
-    return cdiv(M, SK_ROWS) * cdiv(N, BN)
-
-
 @pytest.mark.parametrize("on", IMG_SETS, ids=lambda o: "+".join(o) or "plain")
 @pytest.mark.parametrize("kernel", ["skinny4", "areg"])
 def test_image_kernels_every_feature_alone_and_together(kernel, on):
@@ -275,12 +280,8 @@ def test_image_kernels_every_feature_alone_and_together(kernel, on):
     for M, N, K0, K1 in (SKINNY4_SHAPES if kernel == "skinny4" else AREG_SHAPES):
         if not two_sources_ok(on, K1):
             continue
-        if kernel == "skinny4":
-            assert skinny_wgs(M, N) < 512
-        else:
-            assert cdiv(M, BM) * cdiv(N, BN) < BX_AREG8_MIN
         d = img_problem(rs, M, N, K0, K1, on)
-        got, kinds = launch_gemm(d, img=True, bx_force=2 if kernel == "skinny4" else 1)
+        got, kinds, _ = launch_gemm(d, img=True, bx_force=2 if kernel == "skinny4" else 1, form=kernel)
         assert kinds == ({"gemm_bx_skinny": 1} if kernel == "skinny4" else {"gemm_bx": 1}), kinds
         check_gemm(d, got)
 
@@ -292,7 +293,7 @@ def test_image_kernels_device_side_row_count(kernel, on):
     M, N, K0, K1 = (77, 172, 148, 172) if kernel == "skinny4" else (300, 344, 36, 172)
     for m_dev in (0, 1, M - 1, M, M + 5):
         d = img_problem(rs, M, N, K0, K1, on, m_dev=m_dev)
-        got, kinds = launch_gemm(d, img=True, bx_force=2 if kernel == "skinny4" else 1)
+        got, kinds, _ = launch_gemm(d, img=True, bx_force=2 if kernel == "skinny4" else 1, form=kernel)
         assert kinds == ({"gemm_bx_skinny": 1} if kernel == "skinny4" else {"gemm_bx": 1}), kinds
         check_gemm(d, got)
 
@@ -303,27 +304,10 @@ def test_image_kernel_skinny_176_column_form(on, K1, m_dev):
     """gemm_bx_skinny_kernel<11,1>: 512 or more (32-row x 176-column) blocks."""
     rs = np.random.RandomState(11)
     M, N, K0 = 32 * 256 + 5, 352, 44
-    assert skinny_wgs(M, N) >= 512
     d = img_problem(rs, M, N, K0, K1, on, m_dev=m_dev)
-    got, kinds = launch_gemm(d, img=True, bx_force=2)
+    got, kinds, _ = launch_gemm(d, img=True, bx_force=2, form="skinny11")
     assert kinds == {"gemm_bx_skinny": 1}, kinds
     check_gemm(d, got, big=True)
-
-
-def bx_form(d):
-    """The 128-row form pfo_gemm_launch picks without bx_force.  All three report the family gemm_bx, so which of them ran is
-    known only from this copy of the launcher's rule (BX_AREG8_MIN and the A-stationary condition of pfo_gemm_launch): if that
-    rule changes in gemm.hip and not here, the cases below still pass but may all run the same form - re-derive this
-    function with it."""
-    d = G.gemm_desc(**d)
-    tiles = cdiv(d["M"], BM) * cdiv(d["N"], BN)
-    assert tiles >= BX_MIN_TILES
-    plain = not (d["bias"] is not None or d["relu"] or d["relu_src"] is not None or d["add_src"] is not None or d["accumulate"]
-                 or d["row_scale"] is not None or d["row_zero"] is not None)
-    if (d["K"][1] == 0 and d["K"][0] <= AS_TMAX * BK and d["N"] % 32 == 0 and 352 <= d["N"] <= AS_NMAX and d["ldc"] % 4 == 0 and plain
-            and d["M"] >= 128 * 256):
-        return "astat"
-    return "areg8" if tiles >= BX_AREG8_MIN else "areg"
 
 
 @pytest.mark.parametrize("on,K1,m_dev", [(("scalar_epilogue",), 0, None), ((), 36, None), (tuple(IMG_FEATURES), 36, None),
@@ -334,8 +318,8 @@ def test_image_kernel_eight_wavefront_form(on, K1, m_dev):
     rs = np.random.RandomState(13)
     M, N, K0 = 128 * 256 + 77, 352, 44
     d = img_problem(rs, M, N, K0, K1, on, m_dev=m_dev)
-    assert bx_form(d) == "areg8" and cdiv(N, BN) > 1
-    got, kinds = launch_gemm(d, img=True)
+    got, kinds, plan = launch_gemm(d, img=True, form="areg8")
+    assert plan["grid_y"] == 1 and plan["grid_x"] == 2 * 8 * cdiv(cdiv(M, 128), 8)   # two column tiles: the 1-D grid of the XCD tile order
     assert kinds == {"gemm_bx": 1}, kinds
     check_gemm(d, got, big=True)
 
@@ -349,8 +333,8 @@ def test_image_kernel_a_stationary_form_and_its_boundary(N, K0, on):
     rs = np.random.RandomState(17)
     M = 128 * 256 + 5
     d = img_problem(rs, M, N, K0, 0, on)
-    assert d["ldc"] != N and bx_form(d) == ("astat" if not on else "areg8")
-    got, kinds = launch_gemm(d, img=True)
+    assert d["ldc"] != N
+    got, kinds, _ = launch_gemm(d, img=True, form="astat" if not on else "areg8")
     assert kinds == {"gemm_bx": 1}, kinds
     check_gemm(d, got, big=True)
 
@@ -374,8 +358,9 @@ def test_image_kernels_stacked_image():
     d["ldb"] = [K, 0]
     g, read = fill_gemm_desc(b, d)
     g.b_img = dst
-    for force, kind in ((2, "gemm_bx_skinny"), (1, "gemm_bx")):
+    for force, kind, form in ((2, "gemm_bx_skinny", "skinny4"), (1, "gemm_bx", "areg")):
         g.bx_force = force
+        gemm_plan(g, form)
         with profiled() as p:
             _lib.call("pfo_debug_gemm", C.byref(g), _lib.stream_ptr())
             torch.cuda.synchronize()
@@ -440,11 +425,6 @@ def f32_problem(rs, M, N, K, akm, bkm, on=(), pad=4, K1=0, m_dev=None):
     return d
 
 
-def f32_kind(d):
-    d = G.gemm_desc(**d)
-    return "gemm_devm" if d["m_dev"] is not None else ("gemm_tn" if d["a_kmajor"] else ("gemm_nn" if d["b_kmajor"] else "gemm_nt"))
-
-
 F32_FEATURES = ["a_idx0", "a_idx1", "b_idx", "bias", "row_scale", "row_zero", "relu", "relu_src", "accumulate"]
 
 
@@ -458,8 +438,9 @@ def test_f32_kernel_layouts_and_vector_loads(akm, bkm, vec):
     for M, N, K in ((76, 200, 68), (1, 4, 4), (132, 180, 36)):
         for on in ((), tuple(F32_FEATURES)):
             d = f32_problem(rs, M, N, K, akm, bkm, on, pad=3 if vec == "odd_ld" else 4, K1=(40 if on and not akm else 0))
-            got, kinds = launch_gemm(d, mis=("A0", "B0") if vec == "pointer+1" else ())
-            assert kinds == {f32_kind(d): 1}, kinds
+            got, kinds, plan = launch_gemm(d, mis=("A0", "B0") if vec == "pointer+1" else (), form="f32_128" if akm else "f32_32")
+            assert kinds == {plan["kind"]: 1} and plan["kind"] == ("gemm_tn" if akm else ("gemm_nn" if bkm else "gemm_nt")), kinds
+            assert plan["vec"] == (vec == "float4" and K % 4 == 0 and (not akm or M % 4 == 0) and (not bkm or N % 4 == 0))
             check_f32(d, got)
 
 
@@ -468,10 +449,9 @@ def test_f32_kernel_128_row_tiles(bkm):
     """400 or more tiles of 128 x 176 select the 128-row tile for a row-major A; the last row tile holds 5 rows."""
     rs = np.random.RandomState(23 + bkm)
     M, N, K = 128 * 200 + 5, 352, 36
-    assert cdiv(M, BM) * cdiv(N, BN) >= 400
     d = f32_problem(rs, M, N, K, 0, bkm, ("bias", "relu", "accumulate"))
-    got, kinds = launch_gemm(d)
-    assert kinds == {f32_kind(d): 1}, kinds
+    got, kinds, _ = launch_gemm(d, form="f32_128")
+    assert kinds == {"gemm_nn" if bkm else "gemm_nt": 1}, kinds
     check_f32(d, got, big=True)
 
 
@@ -482,7 +462,7 @@ def test_f32_kernel_device_side_extent(akm):
     M, N, K = 76, 180, 68
     for m_dev in ((0, 1, M - 1, M, M + 3) if not akm else (0, 1, 31, 33, K - 1, K, K + 3)):
         d = f32_problem(rs, M, N, K, akm, 1, ("bias", "accumulate") if not akm else ("accumulate",), m_dev=m_dev)
-        got, kinds = launch_gemm(d)
+        got, kinds, _ = launch_gemm(d, form="f32_128" if akm else "f32_32")
         assert kinds == {"gemm_devm": 1}, kinds
         check_f32(d, got)
 
@@ -512,9 +492,9 @@ def test_f32_kernel_batched_with_the_strides_of_the_step():
     cases.append(dict(A=(G.wide(rs, H, M, K + 4), None), lda=(K + 4, 0), B=(G.wide(rs, H, N, K), None), ldb=(K, 0), K=(K, 0), M=M, N=N,
                       batch=H, a_bs=(M * (K + 4), 0), b_bs=(N * K, 0), C=canary(H * (M + 1) * (N + 3)), ldc=N + 3, c_bs=(M + 1) * (N + 3),
                       bias=G.wide(rs, H, N + 2), bias_bs=N + 2, row_scale=G.wide(rs, H, 3 * M + 1), rs_ld=3, rs_bs=3 * M + 1, relu=1))
-    for d in cases:
-        got, kinds = launch_gemm(d)
-        assert kinds == {f32_kind(d): 1}, kinds
+    for d, (form, kind) in zip(cases, (("f32_32", "gemm_nn"), ("f32_128", "gemm_tn"), ("f32_32", "gemm_nn"), ("f32_32", "gemm_nt"))):
+        got, kinds, _ = launch_gemm(d, form=form)
+        assert kinds == {kind: 1}, kinds
         check_f32(d, got)
 
 
@@ -631,7 +611,10 @@ def tn_problem(rs, K, M, N, bias, gather, c_acc, b_acc):
                 M=M, N=N, C=C0, ldc=ldc, c_accumulate=c_acc, bias_out=b0, bias_accumulate=b_acc)
 
 
-def launch_tn(probs, K, k_dev=None, mis=False, slab_floats=None):
+def launch_tn(probs, K, k_dev=None, mis=False, slab_floats=None, form=None):
+    """-> (outputs, the profiler families that ran, the launcher's plan); the plan (pfo_debug_gemm_tn_group_plan: the function
+    pfo_gemm_tn_group_launch itself switches on) is asked before the launch, held to the model of tests/gemm_ref.py on these
+    very descriptors, ``form`` asserted, and the slabs sized from its nsplit."""
     b = Bufs()
     n = len(probs)
     lst = (_lib.TnDesc * n)()
@@ -648,7 +631,12 @@ def launch_tn(probs, K, k_dev=None, mis=False, slab_floats=None):
             bt = b.keep[-1]
         outs.append((ct, bt))
     per_split = sum(q["M"] * (q["N"] + (q["bias_out"] is not None)) for q in probs)
-    need = per_split * (cdiv(K, 4 * BK) + 1)                          # (the launcher never splits finer than 4 k-tiles a slab)
+    plan = _lib.gemm_plan("pfo_debug_gemm_tn_group_plan", lst, n, K, 1 << 40)
+    ref = G.tn_plan_ref(list(lst), K)
+    assert plan == {k: ref[k] for k in plan}, (plan, ref)
+    assert form is None or plan["form"] == form, (plan["form"], form)
+    need = per_split * plan["nsplit"]
+    assert need == ref["need"]
     slabs = b.put(np.zeros(need, np.float32), np.float32)
     kd = b.put(None if k_dev is None else np.array([k_dev], np.int32), np.int32)
     with profiled() as p:
@@ -657,18 +645,17 @@ def launch_tn(probs, K, k_dev=None, mis=False, slab_floats=None):
     res = []
     for q, (ct, bt) in zip(probs, outs):
         res.append((ct[:q["C"].size].cpu().numpy(), None if bt is None else bt[:q["bias_out"].size].cpu().numpy()))
-    return res, p.kinds
+    return res, p.kinds, plan
 
 
-def tn_form(probs, mis=False):
-    vec = not mis and all(q["M"] % 4 == 0 and q["N"] % 4 == 0 and q["lda"] % 4 == 0 and q["ldb"] % 4 == 0 for q in probs)
-    if not vec:
-        return "gemm_tn", None
-    return ("gemm_tn_bx8", 256) if all(q["M"] >= TN8_MIN_ROWS for q in probs) else ("gemm_tn_bx", 128)
+# form -> (its profiler family, the columns of A one workgroup tile takes and keeps one scale for; None: exact fp32, no scale)
+TN_FORMS = {"tn_bx8": ("gemm_tn_bx8", 256), "tn_bx": ("gemm_tn_bx", 128), "tn_f32": ("gemm_tn", None)}
+FORM_OF = {kind: form for form, (kind, _) in TN_FORMS.items()}
 
 
-def check_tn(probs, K, k_dev, res, kinds, mis=False):
-    kind, a_block = tn_form(probs, mis)
+def check_tn(probs, K, k_dev, res, kinds, plan):
+    kind, a_block = TN_FORMS[plan["form"]]
+    assert kind == plan["kind"]
     assert kinds == ({kind: 1, "tn_reduce": 1} if kind != "gemm_tn" else {kind: 1}), kinds
     ref = G.tn_group_ref(probs, K, None if k_dev is None else np.array([k_dev]), a_block=a_block)
     for q, r, (gc, gb) in zip(probs, ref, res):
@@ -706,10 +693,10 @@ def test_grouped_weight_gradients(form, n):
     rs = np.random.RandomState(43 + n)
     for K in (333, 100):
         probs = tn_group(rs, form, n, K)
-        assert tn_form(probs)[0] == form
-        res, kinds = launch_tn(probs, K)
-        check_tn(probs, K, None, res, kinds)
-        again, _ = launch_tn(probs, K)
+        res, kinds, plan = launch_tn(probs, K, form=FORM_OF[form])
+        assert plan["kind"] == form
+        check_tn(probs, K, None, res, kinds, plan)
+        again, _, _ = launch_tn(probs, K)
         for (c1, b1), (c2, b2) in zip(res, again):
             assert np.array_equal(bits(c1), bits(c2)) and (b1 is None or np.array_equal(bits(b1), bits(b2)))
 
@@ -720,8 +707,8 @@ def test_grouped_weight_gradients_device_side_extent(form):
     K = 333
     probs = tn_group(rs, form, 3, K)
     for k_dev in (0, 1, 31, 33, K - 1, K, K + 9):
-        res, kinds = launch_tn(probs, K, k_dev)
-        check_tn(probs, K, k_dev, res, kinds)
+        res, kinds, plan = launch_tn(probs, K, k_dev, form=FORM_OF[form])
+        check_tn(probs, K, k_dev, res, kinds, plan)
 
 
 def test_grouped_weight_gradients_both_bias_settings_at_the_block_edge():
@@ -732,15 +719,15 @@ def test_grouped_weight_gradients_both_bias_settings_at_the_block_edge():
         for bias in (False, True):
             for M in (172, 504):
                 probs = [tn_problem(rs, K, M, N, bias=bias, gather=False, c_acc=0, b_acc=0)]
-                res, kinds = launch_tn(probs, K)
-                check_tn(probs, K, None, res, kinds)
+                res, kinds, plan = launch_tn(probs, K, form="tn_f32" if N != 176 else ("tn_bx8" if M == 504 else "tn_bx"))
+                check_tn(probs, K, None, res, kinds, plan)
 
 
 def test_grouped_weight_gradients_misaligned_pointer_takes_the_fp32_form():
     rs = np.random.RandomState(59)
     probs = tn_group(rs, "gemm_tn_bx", 3, 200)
-    res, kinds = launch_tn(probs, 200, mis=True)
-    check_tn(probs, 200, None, res, kinds, mis=True)
+    res, kinds, plan = launch_tn(probs, 200, mis=True, form="tn_f32")
+    check_tn(probs, 200, None, res, kinds, plan)
 
 
 def test_grouped_weight_gradients_small_workspace_is_refused():
