@@ -458,6 +458,13 @@ typedef struct pfo_tgn_config {
   int32_t max_roots;    /* capacity R the workspace is sized for */
   int32_t max_neighbors;/* capacity K */
   int32_t max_batch;    /* capacity B (positives = 2B) */
+  /* message function (modules/message_function.py): msg_dim == 0 = identity (the GRU reads the raw message, 3D+Ef wide);
+     msg_dim > 0 = the MLP Linear(3D+Ef, msg_hidden) -> ReLU -> Linear(msg_hidden, msg_dim) in front of the GRU, whose
+     weight_ih is then [3D, msg_dim].  msg_dim must be a multiple of 4 and needs use_memory; msg_hidden > 0 (the reference
+     takes (3D+Ef)/2) and is ignored with msg_dim == 0.  Appended (abi 6, additive): a config built from the ten fields above
+     with the rest zero is the identity model, bit for bit. */
+  int32_t msg_dim;
+  int32_t msg_hidden;
 } pfo_tgn_config;
 
 /* flat parameter layout (element offsets into the fp32 parameter / gradient buffers) */
@@ -469,6 +476,10 @@ typedef struct pfo_tgn_layout {
   int64_t gru_w_ih, gru_w_hh, gru_b_ih, gru_b_hh; /* memory_updater.memory_updater.* (-1 without memory) */
   pfo_tgn_layer_layout layer[PFO_MAX_LAYERS];
   int64_t total;
+  /* message_function.mlp.{0,2}.{weight,bias}: [msg_hidden, 3D+Ef], [msg_hidden], [msg_dim, msg_hidden], [msg_dim]; -1 without
+     the MLP.  The block sits right behind the GRU's and in front of layer[0] (its gradients finish last, with the GRU's:
+     pfo_tgn_grad_split), each tensor at an offset that is a multiple of 4 floats. */
+  int64_t mlp_w1, mlp_b1, mlp_w2, mlp_b2;
 } pfo_tgn_layout;
 
 int pfo_tgn_param_layout(const pfo_tgn_config* cfg, pfo_tgn_layout* out);
@@ -738,6 +749,9 @@ typedef struct pfo_tgn_debug {
   const float* gru_dgi;      /* [n_core, 3D]  d loss / d (GRU input-side pre-activations) (a operand of dW_ih)  */
   const float* gru_msg_rows; /* [n_core, 3D+Ef] packed message rows (b operand); dW_ih lands in the gradient buffer */
   int32_t Cp;                /* per-head row stride of ctx' */
+  /* the message MLP's activations of the last forward (NULL with msg_dim == 0): rows follow touched_ids */
+  const float* mlp_hid;      /* [n_touched, msg_hidden] relu(W1 raw + b1) */
+  const float* mlp_out;      /* [n_touched, msg_dim]    W2 hid + b2: the GRU's input rows */
 } pfo_tgn_debug;
 int pfo_tgn_debug_views(const pfo_tgn_config* cfg, void* workspace, pfo_tgn_debug* out);
 
@@ -800,6 +814,31 @@ int64_t pfo_debug_bimg_bytes(int32_t N, int32_t K);
 int64_t pfo_debug_gru_img_bytes(int32_t D, int32_t K);
 int pfo_debug_bimg(const pfo_bimg_desc* list, int32_t n, void* stream);
 int pfo_debug_gru_fused(const pfo_gru_desc* f, void* stream);
+/* The MLP message function's forward in one launch (csrc/gemm.hpp PfoMsgMlp / pfo_msg_mlp_fwd_launch): hid = relu(raw W1^T + b1),
+ * msg_out = hid W2^T + b2 over cap_rows rows (device count n_rows), W1 [Hm, Mr] and W2 [Md, Hm] as plain pfo_debug_bimg images
+ * (N = Hm, K = Mr and N = Md, K = Hm; pfo_debug_bimg_bytes each).  touched != NULL: raw / hm are per-node tables and row m is
+ * node touched[m]; NULL: packed rows.  Rows with hm == 0 are not read and give zeros; hid (may be NULL) and msg_out are written
+ * for rows < min(cap_rows, *n_rows) only.  Mr % 4 == 0, Md % 4 == 0, 16-byte aligned raw / msg_out / images. */
+typedef struct pfo_msg_mlp_desc {  /* PfoMsgMlp */
+  const float* raw; int64_t ld_raw;
+  const int32_t* touched; const uint8_t* hm;
+  const void* img_w1; const void* img_w2;
+  const float* b1; const float* b2;
+  float* hid; float* msg_out;
+  int32_t Mr, Hm, Md, cap_rows; const int32_t* n_rows;
+} pfo_msg_mlp_desc;
+int pfo_debug_msg_mlp_fwd(const pfo_msg_mlp_desc* f, void* stream);
+/* ... and the data path of its backward (PfoMsgMlpBwd / pfo_msg_mlp_bwd_launch): d_m = dgi W_ih (written when not NULL),
+ * d_hid = (d_m W2) where hid > 0, exactly 0 elsewhere; dgi [rows, D3], hid [rows, Hm] packed; the images are those of W_ih^T
+ * (pfo_debug_bimg with trans = 1, N = Md, K = D3, src = W_ih [D3, Md]) and of W2^T (trans = 1, N = Hm, K = Md, src = W2 [Md, Hm]).
+ * Md <= 128 and a multiple of 4, D3 a multiple of 4. */
+typedef struct pfo_msg_mlp_bwd_desc {  /* PfoMsgMlpBwd */
+  const float* dgi; const float* hid;
+  const void* img_wihT; const void* img_w2T;
+  float* d_m; float* d_hid;
+  int32_t D3, Hm, Md, cap_rows; const int32_t* n_rows;
+} pfo_msg_mlp_bwd_desc;
+int pfo_debug_msg_mlp_bwd(const pfo_msg_mlp_bwd_desc* f, void* stream);
 int pfo_debug_rank1_multi(const pfo_rank1_desc* list, int32_t n, void* stream);
 int pfo_debug_sum_slabs(const pfo_sum_slabs_desc* list, int32_t n, void* stream);
 /* The launchers' dispatch, asked without launching (additive: the abi version stays).  pfo_debug_gemm_plan /

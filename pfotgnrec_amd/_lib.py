@@ -22,7 +22,7 @@ EVAL_RANK_NONE = (1 << 31) - 1  # PFO_EVAL_RANK_NONE: the positive is not ranked
 class TgnConfig(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_edges_p1", C.c_int32), ("D", C.c_int32), ("Ef", C.c_int32),
                 ("n_layers", C.c_int32), ("n_heads", C.c_int32), ("use_memory", C.c_int32), ("max_roots", C.c_int32),
-                ("max_neighbors", C.c_int32), ("max_batch", C.c_int32)]
+                ("max_neighbors", C.c_int32), ("max_batch", C.c_int32), ("msg_dim", C.c_int32), ("msg_hidden", C.c_int32)]
 
 
 class TgnLayerLayout(C.Structure):
@@ -32,7 +32,7 @@ class TgnLayerLayout(C.Structure):
 class TgnLayout(C.Structure):
     _fields_ = [("time_w", C.c_int64), ("time_b", C.c_int64), ("gru_w_ih", C.c_int64), ("gru_w_hh", C.c_int64),
                 ("gru_b_ih", C.c_int64), ("gru_b_hh", C.c_int64), ("layer", TgnLayerLayout * MAX_LAYERS),
-                ("total", C.c_int64)]
+                ("total", C.c_int64), ("mlp_w1", C.c_int64), ("mlp_b1", C.c_int64), ("mlp_w2", C.c_int64), ("mlp_b2", C.c_int64)]
 
 
 class TgnState(C.Structure):
@@ -51,7 +51,7 @@ class TgnBatch(C.Structure):
 
 class TgnDebug(C.Structure):
     _fields_ = [(n, _VP) for n in ("n_touched", "touched_ids", "h0_table", "slot", "n_core", "l1_ctx", "l1_dh1", "l1_dW1ovT",
-                                   "gru_dgi", "gru_msg_rows")] + [("Cp", C.c_int32)]
+                                   "gru_dgi", "gru_msg_rows")] + [("Cp", C.c_int32), ("mlp_hid", _VP), ("mlp_out", _VP)]
 
 
 # debug / test probes of the internal contraction interface (csrc/gemm.hpp through csrc/probe.hip); the package never calls them
@@ -82,6 +82,17 @@ class GruDesc(C.Structure):
     _fields_ = [("msg_rows", _FP), ("K_msg", C.c_int32), ("h_rows", _FP), ("img_ih", _FP), ("img_hh", _FP), ("b_ih", _FP),
                 ("b_hh", _FP), ("hm", _FP), ("touched", _FP), ("node_feat", _FP), ("upd_mem", _FP), ("h0_tab", _FP), ("gates", _FP),
                 ("D", C.c_int32), ("cap_rows", C.c_int32), ("n_rows", _FP), ("gather", C.c_int32)]
+
+
+class MsgMlpDesc(C.Structure):
+    _fields_ = [("raw", _FP), ("ld_raw", C.c_int64), ("touched", _FP), ("hm", _FP), ("img_w1", _FP), ("img_w2", _FP), ("b1", _FP),
+                ("b2", _FP), ("hid", _FP), ("msg_out", _FP), ("Mr", C.c_int32), ("Hm", C.c_int32), ("Md", C.c_int32),
+                ("cap_rows", C.c_int32), ("n_rows", _FP)]
+
+
+class MsgMlpBwdDesc(C.Structure):
+    _fields_ = [("dgi", _FP), ("hid", _FP), ("img_wihT", _FP), ("img_w2T", _FP), ("d_m", _FP), ("d_hid", _FP), ("D3", C.c_int32),
+                ("Hm", C.c_int32), ("Md", C.c_int32), ("cap_rows", C.c_int32), ("n_rows", _FP)]
 
 
 class Rank1Desc(C.Structure):
@@ -222,6 +233,8 @@ PROTOTYPES = {
     "pfo_debug_gru_img_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "pfo_debug_bimg": (C.c_int, [C.POINTER(BimgDesc), C.c_int32, _VP]),
     "pfo_debug_gru_fused": (C.c_int, [C.POINTER(GruDesc), _VP]),
+    "pfo_debug_msg_mlp_fwd": (C.c_int, [C.POINTER(MsgMlpDesc), _VP]),
+    "pfo_debug_msg_mlp_bwd": (C.c_int, [C.POINTER(MsgMlpBwdDesc), _VP]),
     "pfo_debug_rank1_multi": (C.c_int, [C.POINTER(Rank1Desc), C.c_int32, _VP]),
     "pfo_debug_sum_slabs": (C.c_int, [C.POINTER(SumSlabsDesc), C.c_int32, _VP]),
     "pfo_debug_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), _VP]),

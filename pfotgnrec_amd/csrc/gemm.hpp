@@ -66,9 +66,36 @@ struct PfoGruFused {
   int D = 0, cap_rows = 0; const int32_t* n_rows = nullptr;
   // gather = 1: msg_rows / h_rows / hm are the FULL per-node tables (message table, memory, has_msg) and row m of the launch is
   // node touched[m] of them - the packed copies the backward needs are then made off the critical path
+  // gather = 2: h_rows / hm are the per-node tables as with 1, msg_rows are PACKED rows [cap_rows, K_msg] (the message MLP's
+  // output, computed per touched row in front of this launch)
   int gather = 0;
 };
 int pfo_gru_fused_launch(const PfoGruFused& f, hipStream_t stream);
+
+// The MLP message function of cap_rows (device count n_rows) rows in one launch (gemm.hip msg_mlp_fwd_kernel):
+// hid = relu(raw W1^T + b1), msg_out = hid W2^T + b2, W1 [Hm, Mr] and W2 [Md, Hm] as plain pfo_bimg_launch images.
+// touched != null: raw / hm are the FULL per-node tables and row m is node touched[m]; null: packed rows.  Rows with hm == 0 are
+// not read and give zeros.  hid [cap_rows, Hm] is written only when given; msg_out [cap_rows, Md] always.  Rows >= n_rows and
+// rows >= cap_rows are untouched.
+struct PfoMsgMlp {
+  const float* raw = nullptr; int64_t ld_raw = 0;
+  const int32_t* touched = nullptr; const uint8_t* hm = nullptr;
+  const void* img_w1 = nullptr; const void* img_w2 = nullptr;
+  const float* b1 = nullptr; const float* b2 = nullptr;
+  float* hid = nullptr; float* msg_out = nullptr;
+  int Mr = 0, Hm = 0, Md = 0, cap_rows = 0; const int32_t* n_rows = nullptr;
+};
+int pfo_msg_mlp_fwd_launch(const PfoMsgMlp& f, hipStream_t stream);
+// The data path of its backward in one launch (msg_mlp_bwd_kernel): d m = dgi W_ih [rows, Md], d hid = (d m W2) where hid > 0
+// and exactly 0 elsewhere [rows, Hm]; dgi [rows, D3 = 3 D] and hid [rows, Hm] packed rows, the operands as TRANSPOSED images
+// (pfo_bimg_launch trans = 1: W_ih^T with N = Md, K = D3; W2^T with N = Hm, K = Md).  Md <= 128.  d_m is written only when given.
+struct PfoMsgMlpBwd {
+  const float* dgi = nullptr; const float* hid = nullptr;
+  const void* img_wihT = nullptr; const void* img_w2T = nullptr;
+  float* d_m = nullptr; float* d_hid = nullptr;
+  int D3 = 0, Hm = 0, Md = 0, cap_rows = 0; const int32_t* n_rows = nullptr;
+};
+int pfo_msg_mlp_bwd_launch(const PfoMsgMlpBwd& f, hipStream_t stream);
 int64_t pfo_bimg_bytes(int N, int K);
 int pfo_bimg_launch(const PfoBimg* list, int n, hipStream_t stream);
 

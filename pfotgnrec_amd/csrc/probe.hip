@@ -90,6 +90,23 @@ extern "C" int pfo_debug_bimg(const pfo_bimg_desc* list, int32_t n, void* stream
   return pfo_bimg_launch(q, n, (hipStream_t)stream);
 }
 
+extern "C" int pfo_debug_msg_mlp_fwd(const pfo_msg_mlp_desc* f, void* stream) {
+  PFO_REQUIRE(f, "null descriptor");
+  PfoMsgMlp q;
+  q.raw = f->raw; q.ld_raw = f->ld_raw; q.touched = f->touched; q.hm = f->hm; q.img_w1 = f->img_w1; q.img_w2 = f->img_w2;
+  q.b1 = f->b1; q.b2 = f->b2; q.hid = f->hid; q.msg_out = f->msg_out; q.Mr = f->Mr; q.Hm = f->Hm; q.Md = f->Md;
+  q.cap_rows = f->cap_rows; q.n_rows = f->n_rows;
+  return pfo_msg_mlp_fwd_launch(q, (hipStream_t)stream);
+}
+
+extern "C" int pfo_debug_msg_mlp_bwd(const pfo_msg_mlp_bwd_desc* f, void* stream) {
+  PFO_REQUIRE(f, "null descriptor");
+  PfoMsgMlpBwd q;
+  q.dgi = f->dgi; q.hid = f->hid; q.img_wihT = f->img_wihT; q.img_w2T = f->img_w2T; q.d_m = f->d_m; q.d_hid = f->d_hid;
+  q.D3 = f->D3; q.Hm = f->Hm; q.Md = f->Md; q.cap_rows = f->cap_rows; q.n_rows = f->n_rows;
+  return pfo_msg_mlp_bwd_launch(q, (hipStream_t)stream);
+}
+
 extern "C" int pfo_debug_gru_fused(const pfo_gru_desc* f, void* stream) {
   PFO_REQUIRE(f, "null descriptor");
   PfoGruFused q;

@@ -47,6 +47,10 @@ struct Ws {
   uint8_t* hm;
   float *cosb, *zero, *tb_part;
   void *iWih, *iWhh;
+  // message MLP (msg_dim > 0): hidden activations and output of the touched rows (kept for the backward), their gradients,
+  // and the weight images of the four contractions (forward W1, W2; backward W_ih^T, W2^T)
+  float *mlp_hid, *mlp_out, *d_m, *d_hid;
+  void *iMW1, *iMW2, *iWihT, *iMW2T;
   // layer 1 works on the touched-node table: QX[s] = h0_tab[s] [Wqk ; W1[:, E:]]^T + [cqk | 0] for every touched row s
   // (the query-side projections of all instances that sit on node s), Dq = per-row sums of the instances' gradients
   float *QX, *Dq, *dx_tab, *l1_bias;
@@ -71,6 +75,7 @@ struct Ws {
 
 struct Dims {
   int L, D, Ef, H, E, C, Cp, dh, M;
+  int Mg, Hm;                            // the GRU's input width (msg_dim, or M with the identity message function); msg_hidden (0 = no MLP)
   int64_t ncap[PFO_MAX_LAYERS + 1];
   int64_t capP;
 };
@@ -79,6 +84,8 @@ Dims dims_of(const pfo_tgn_config* c) {
   Dims d;
   d.L = c->n_layers; d.D = c->D; d.Ef = c->Ef; d.H = c->n_heads;
   d.E = 2 * d.D; d.C = 2 * d.D + d.Ef; d.dh = d.E / d.H; d.M = 3 * d.D + d.Ef;
+  d.Hm = c->msg_dim > 0 ? c->msg_hidden : 0;
+  d.Mg = c->msg_dim > 0 ? c->msg_dim : d.M;
   d.Cp = (int)pfo_align_up(d.C + 2, 4);   // key columns + (sum of weights) + (valid flag), padded for 16-byte rows
   d.ncap[d.L] = c->max_roots;
   for (int l = d.L; l >= 1; --l) d.ncap[l - 1] = d.ncap[l] * (1 + (int64_t)c->max_neighbors);
@@ -203,8 +210,18 @@ Ws carve(const pfo_tgn_config* c, void* base, void* cache = nullptr, bool cached
     w.msg_rows = k.ws<float>(d.capP * d.M);
     w.h_rows = k.ws<float>(d.capP * d.D);
     w.hm = k.ws<uint8_t>(d.capP);
-    w.iWih = k.par<char>(pfo_gru_img_bytes(d.D, d.M));
+    w.iWih = k.par<char>(pfo_gru_img_bytes(d.D, d.Mg));
     w.iWhh = k.par<char>(pfo_gru_img_bytes(d.D, d.D));
+    if (d.Hm > 0) {
+      w.mlp_hid = k.ws<float>(d.capP * d.Hm);
+      w.mlp_out = k.ws<float>(d.capP * d.Mg);
+      w.d_m = k.ws<float>(d.capP * d.Mg);
+      w.d_hid = k.ws<float>(d.capP * d.Hm);
+      w.iMW1 = k.par<char>(pfo_bimg_bytes(d.Hm, d.M));
+      w.iMW2 = k.par<char>(pfo_bimg_bytes(d.Mg, d.Hm));
+      w.iWihT = k.par<char>(pfo_bimg_bytes(d.Mg, 3 * d.D));
+      w.iMW2T = k.par<char>(pfo_bimg_bytes(d.Hm, d.Mg));
+    }
   }
   for (int l = 1; l <= d.L; ++l) carve_layer(k, d, l, Km, w);
   const int64_t N1 = d.ncap[1];
@@ -237,15 +254,20 @@ int check_cfg(const pfo_tgn_config* c) {
   PFO_REQUIRE(c->max_batch >= 0, "bad max_batch");
   PFO_REQUIRE(c->n_nodes >= 2 && c->n_edges_p1 >= 1, "bad graph sizes");
   PFO_REQUIRE(c->max_roots >= 1 && c->max_neighbors >= 1 && c->max_neighbors <= PFO_MAX_NEIGHBORS, "bad capacities");
+  PFO_REQUIRE(c->msg_dim >= 0 && c->msg_dim <= 4096 && (c->msg_dim % 4) == 0, "msg_dim must be a multiple of 4 in [0, 4096]");
+  PFO_REQUIRE(c->msg_dim == 0 || c->use_memory, "the MLP message function needs use_memory");
+  PFO_REQUIRE(c->msg_dim == 0 || (c->msg_hidden >= 1 && c->msg_hidden <= 4096), "msg_hidden must be in [1, 4096] with the MLP message function");
   return PFO_OK;
 }
 
 struct Params {
   const float *tw, *tb, *w_ih, *w_hh, *b_ih, *b_hh;
+  const float *m_w1, *m_b1, *m_w2, *m_b2;
   struct { const float *wq, *wk, *wv, *b_in, *wo, *bo, *w1, *b1, *w2, *b2; } l[PFO_MAX_LAYERS + 1];
 };
 struct Grads {
   float *tw, *tb, *w_ih, *w_hh, *b_ih, *b_hh;
+  float *m_w1, *m_b1, *m_w2, *m_b2;
   struct { float *wq, *wk, *wv, *b_in, *wo, *bo, *w1, *b1, *w2, *b2; } l[PFO_MAX_LAYERS + 1];
 };
 
@@ -257,6 +279,9 @@ void bind(const pfo_tgn_layout& lay, FT* base, PT& p, int L, bool mem) {
   } else {
     p.w_ih = p.w_hh = p.b_ih = p.b_hh = nullptr;
   }
+  const bool mlp = mem && lay.mlp_w1 >= 0;
+  p.m_w1 = mlp ? base + lay.mlp_w1 : nullptr; p.m_b1 = mlp ? base + lay.mlp_b1 : nullptr;
+  p.m_w2 = mlp ? base + lay.mlp_w2 : nullptr; p.m_b2 = mlp ? base + lay.mlp_b2 : nullptr;
   for (int l = 1; l <= L; ++l) {
     const pfo_tgn_layer_layout& q = lay.layer[l - 1];
     p.l[l].wq = base + q.wq; p.l[l].wk = base + q.wk; p.l[l].wv = base + q.wv; p.l[l].b_in = base + q.b_in;
@@ -389,12 +414,23 @@ extern "C" int pfo_tgn_param_layout(const pfo_tgn_config* c, pfo_tgn_layout* out
   out->time_w = put(d.D);
   out->time_b = put(d.D);
   if (c->use_memory) {
-    out->gru_w_ih = put((int64_t)3 * d.D * d.M);
+    out->gru_w_ih = put((int64_t)3 * d.D * d.Mg);
     out->gru_w_hh = put((int64_t)3 * d.D * d.D);
     out->gru_b_ih = put(3 * d.D);
     out->gru_b_hh = put(3 * d.D);
   } else {
     out->gru_w_ih = out->gru_w_hh = out->gru_b_ih = out->gru_b_hh = -1;
+  }
+  out->mlp_w1 = out->mlp_b1 = out->mlp_w2 = out->mlp_b2 = -1;
+  if (d.Hm > 0) {
+    // behind the GRU's block, not at the end: its gradients finish last, with the GRU's (pfo_tgn_grad_split).  Every tensor
+    // starts at a multiple of 4 floats (msg_hidden may be odd), and so does what follows the block
+    auto put4 = [&](int64_t n) { o = pfo_align_up(o, 4); return put(n); };
+    out->mlp_w1 = put4((int64_t)d.Hm * d.M);
+    out->mlp_b1 = put4(d.Hm);
+    out->mlp_w2 = put4((int64_t)d.Mg * d.Hm);
+    out->mlp_b2 = put4(d.Mg);
+    o = pfo_align_up(o, 4);
   }
   for (int l = 0; l < d.L; ++l) {
     pfo_tgn_layer_layout& q = out->layer[l];
@@ -431,6 +467,7 @@ extern "C" int pfo_tgn_debug_views(const pfo_tgn_config* c, void* workspace, pfo
   out->gru_dgi = c->use_memory ? w.gi : nullptr;
   out->gru_msg_rows = c->use_memory ? w.msg_rows : nullptr;
   out->Cp = d.Cp;
+  out->mlp_hid = w.mlp_hid; out->mlp_out = w.mlp_out;
   return PFO_OK;
 }
 
@@ -658,15 +695,39 @@ static int prepare_pack(const Step& S, hipStream_t s) {
 // (pfo_tgn_forward runs them on its side stream when the parameter cache is absent or stale; pfo_tgn_refresh right behind the
 // optimizer).  Stage A: cos(b), the composite weights of every layer and the weight images layer 1 and the top layer's fc2
 // need.  Stage B ("fc2 fold"): the composites of the layers >= 2 with the fc2 of the layer below folded in, and their images.
-static int build_gru_images(const pfo_tgn_config* c, const Dims& d, const Ws& w, const Params& P, hipStream_t s) {
+static int build_gru_images(const pfo_tgn_config* c, const Dims& d, const Ws& w, const Params& P, hipStream_t s, bool forward_only = false) {
   // gate-ordered rows: r | z | n_i | n_h per 16 hidden units (gemm.hip gru_fused_kernel)
   const int D = d.D;
   PfoBimg im[2];
-  im[0].src = P.w_ih; im[0].ld = d.M; im[0].N = 3 * D; im[0].K = d.M; im[0].trans = 0; im[0].dst = w.iWih;
+  im[0].src = P.w_ih; im[0].ld = d.Mg; im[0].N = 3 * D; im[0].K = d.Mg; im[0].trans = 0; im[0].dst = w.iWih;
   im[1].src = P.w_hh; im[1].ld = D; im[1].N = 3 * D; im[1].K = D; im[1].trans = 0; im[1].dst = w.iWhh;
   im[0].gate = 1; im[0].gate_D = D; im[1].gate = 2; im[1].gate_D = D;
   (void)c;
-  return pfo_bimg_launch(im, 2, s);
+  RUN(pfo_bimg_launch(im, 2, s));
+  if (d.Hm == 0) return PFO_OK;
+  // the message MLP's operands, both ways: W1, W2 for the forward, W_ih^T and W2^T for d m = dgi W_ih, d hid = d m W2
+  PfoBimg mm[4];
+  auto img = [&](int i, const float* src, int64_t ld, int N_, int K_, int trans, void* dst) {
+    mm[i].src = src; mm[i].ld = ld; mm[i].N = N_; mm[i].K = K_; mm[i].trans = trans; mm[i].dst = dst;
+  };
+  img(0, P.m_w1, d.M, d.Hm, d.M, 0, w.iMW1);
+  img(1, P.m_w2, d.Hm, d.Mg, d.Hm, 0, w.iMW2);
+  if (forward_only) return pfo_bimg_launch(mm, 2, s);             // (pfo_tgn_observe: no backward reads the transposed pair)
+  img(2, P.w_ih, d.Mg, d.Mg, 3 * D, 1, w.iWihT);
+  img(3, P.m_w2, d.Hm, d.Hm, d.Mg, 1, w.iMW2T);
+  return pfo_bimg_launch(mm, 4, s);
+}
+// The MLP message function (modules/message_function.py:13-26) over the touched rows, in front of the lazy GRU:
+// hid = relu(raw W1^T + b1), out = hid W2^T + b2.  raw rows: packed [rows, M] (idx null) or gathered from the message table.
+// Rows without a pending message are computed like the others - the GRU keeps their memory row and their gate gradients are zero.
+static int message_mlp(const Dims& d, const Params& P, const float* raw, const int32_t* idx, const void* iW1, const void* iW2,
+                       float* hid, float* out, int cap_rows, const int32_t* n_rows, hipStream_t s) {
+  PfoGemm g1 = g_nt(raw, d.M, idx, P.m_w1, d.M, hid, d.Hm, cap_rows, d.Hm, d.M, P.m_b1);
+  g1.relu = 1; g1.m_dev = n_rows; g1.b_img = iW1;
+  RUN(pfo_gemm_launch(g1, s));
+  PfoGemm g2 = g_nt(hid, d.Hm, nullptr, P.m_w2, d.Hm, out, d.Mg, cap_rows, d.Mg, d.Hm, P.m_b2);
+  g2.m_dev = n_rows; g2.b_img = iW2;
+  return pfo_gemm_launch(g2, s);
 }
 static int build_stage_a(const Dims& d, const Ws& w, const Params& P, hipStream_t ss) {
   const int L = d.L, D = d.D, H = d.H, E = d.E, C = d.C, dh = d.dh, Cp = d.Cp, HCp = d.H * d.Cp;
@@ -1005,11 +1066,17 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
   if (c->use_memory) {
     PfoRange range_gru("forward lazy GRU");
     // both GRU contractions and the gate math in ONE launch (gemm.hip gru_fused_kernel): gi / gh never exist in HBM
+    const bool mlp = S.d.Hm > 0;
+    if (mlp) {
+      RUN(message_mlp(S.d, S.P, S.pack_side ? st->msg_table : w.msg_rows, S.pack_side ? w.touched : nullptr, w.iMW1, w.iMW2,
+                      w.mlp_hid, w.mlp_out, S.capP, w.n_touched, s));
+      PFO_MARK("fwd.msg_mlp", s);
+    }
     PfoGruFused f;
-    f.msg_rows = w.msg_rows; f.K_msg = S.d.M; f.h_rows = w.h_rows; f.img_ih = w.iWih; f.img_hh = w.iWhh;
+    f.msg_rows = mlp ? w.mlp_out : w.msg_rows; f.K_msg = S.d.Mg; f.h_rows = w.h_rows; f.img_ih = w.iWih; f.img_hh = w.iWhh;
     f.b_ih = S.P.b_ih; f.b_hh = S.P.b_hh; f.hm = w.hm; f.touched = w.touched; f.node_feat = st->node_feat;
     f.upd_mem = w.upd_mem; f.h0_tab = w.h0_tab; f.gates = w.gates; f.D = S.d.D; f.cap_rows = S.capP; f.n_rows = w.n_touched;
-    if (S.pack_side) { f.gather = 1; f.msg_rows = st->msg_table; f.h_rows = st->memory; f.hm = st->has_msg; }
+    if (S.pack_side) { f.gather = mlp ? 2 : 1; if (!mlp) f.msg_rows = st->msg_table; f.h_rows = st->memory; f.hm = st->has_msg; }
     PFO_RUN_BOUND(S.fused_state && bind_events, sd.gru_done, 0, s, pfo_gru_fused_launch(f, s));
     if (S.fused_state && !bind_events) HIPOK(hipEventRecord(sd.gru_done, s), "event record failed");
     PFO_MARK("fwd.gru", s);
@@ -1392,12 +1459,29 @@ static int backward_gru(const Step& S, bool* main_done_bound) {
   RUN(pfo_gru_gates_bwd_launch(w.gates, w.gi, w.gh, w.h_rows, w.hm, w.n_core, S.capP, D, w.d_h0, S.n_rep, S.rep_stride,
                                w.dx_tab, S.det, S.s));
   PFO_MARK("bwd.gru.gates", S.s);
-  PfoTnProblem gp[2];
+  PfoTnProblem gp[4];
+  int ngp = 2;
   gp[0] = tn_of(w.gi, 3 * D, w.msg_rows, M, nullptr, 3 * D, M, S.G.w_ih, M, S.G.b_ih);
   gp[1] = tn_of(w.gh, 3 * D, w.h_rows, D, nullptr, 3 * D, D, S.G.w_hh, D, S.G.b_hh);
+  if (S.d.Hm > 0) {
+    // the MLP message function's data path: d m = dgi W_ih, d hid = (d m W2) where hid > 0; then its two weight gradients
+    // join the GRU's group (dW_ih now contracts against the MLP's output rows)
+    const int Mg = S.d.Mg, Hm = S.d.Hm;
+    PfoGemm q1 = g_nn(w.gi, 3 * D, S.P.w_ih, Mg, w.d_m, Mg, S.capP, Mg, 3 * D);
+    q1.m_dev = w.n_core; q1.b_img = w.iWihT;
+    RUN(pfo_gemm_launch(q1, S.s));
+    PfoGemm q2 = g_nn(w.d_m, Mg, S.P.m_w2, Hm, w.d_hid, Hm, S.capP, Hm, Mg);
+    q2.m_dev = w.n_core; q2.b_img = w.iMW2T; q2.relu_src = w.mlp_hid; q2.relu_ld = Hm;
+    RUN(pfo_gemm_launch(q2, S.s));
+    PFO_MARK("bwd.msg_mlp", S.s);
+    gp[0] = tn_of(w.gi, 3 * D, w.mlp_out, Mg, nullptr, 3 * D, Mg, S.G.w_ih, Mg, S.G.b_ih);
+    gp[2] = tn_of(w.d_m, Mg, w.mlp_hid, Hm, nullptr, Mg, Hm, S.G.m_w2, Hm, S.G.m_b2);
+    gp[3] = tn_of(w.d_hid, Hm, w.msg_rows, M, nullptr, Hm, M, S.G.m_w1, M, S.G.m_b1);
+    ngp = 4;
+  }
   // (a deferred join's main_done event rides on the slab reduce, the caller's stream's last launch of this call)
   *main_done_bound = S.b->defer_join && !S.capturing;
-  PFO_RUN_BOUND(*main_done_bound, S.sd.main_done, 1, S.s, pfo_gemm_tn_group_launch(gp, 2, S.capP, w.n_core, w.slabs, w.slab_floats, S.s));
+  PFO_RUN_BOUND(*main_done_bound, S.sd.main_done, 1, S.s, pfo_gemm_tn_group_launch(gp, ngp, S.capP, w.n_core, w.slabs, w.slab_floats, S.s));
   PFO_MARK("bwd.gru.tn", S.s);
   return PFO_OK;
 }
@@ -1574,6 +1658,8 @@ struct ObsWs {
   int32_t *rep, *slot, *touched, *n_rows, *winner;
   float *upd_mem, *h0_tab, *gates;
   void *iWih, *iWhh;
+  float *mlp_hid, *mlp_out;                 // message MLP (msg_dim > 0)
+  void *iMW1, *iMW2;
   int64_t cap, bytes;
 };
 ObsWs carve_observe(const pfo_tgn_config* c, int32_t B, void* base) {
@@ -1590,8 +1676,14 @@ ObsWs carve_observe(const pfo_tgn_config* c, int32_t B, void* base) {
   o.upd_mem = take<float>(p, o.cap * d.D);
   o.h0_tab = take<float>(p, o.cap * d.D);                         // (by-products of the fused launch, not read here)
   o.gates = take<float>(p, o.cap * 4 * d.D);
-  o.iWih = take<char>(p, pfo_gru_img_bytes(d.D, d.M));            // (used when the state carries no valid parameter cache)
+  o.iWih = take<char>(p, pfo_gru_img_bytes(d.D, d.Mg));           // (used when the state carries no valid parameter cache)
   o.iWhh = take<char>(p, pfo_gru_img_bytes(d.D, d.D));
+  if (d.Hm > 0) {
+    o.mlp_hid = take<float>(p, o.cap * d.Hm);
+    o.mlp_out = take<float>(p, o.cap * d.Mg);
+    o.iMW1 = take<char>(p, pfo_bimg_bytes(d.Hm, d.M));
+    o.iMW2 = take<char>(p, pfo_bimg_bytes(d.Mg, d.Hm));
+  }
   o.bytes = p - reinterpret_cast<char*>(base);
   return o;
 }
@@ -1628,15 +1720,15 @@ extern "C" int pfo_tgn_observe(const pfo_tgn_config* c, const pfo_tgn_state* st,
   PfoRange range("pfo_tgn_observe");
   RUN(side_join(side(), s));                                      // (a deferred optimizer step may still be writing the parameters)
   // GRU weight images: the parameter cache's when it is valid, else built here, once - parameters cannot change inside a call
-  const void *iWih = o.iWih, *iWhh = o.iWhh;
+  const void *iWih = o.iWih, *iWhh = o.iWhh, *iMW1 = o.iMW1, *iMW2 = o.iMW2;
   if (st->pcache && st->pcache_valid) {
     const Ws pw = carve(c, nullptr, st->pcache, true);
-    iWih = pw.iWih; iWhh = pw.iWhh;
+    iWih = pw.iWih; iWhh = pw.iWhh; iMW1 = pw.iMW1; iMW2 = pw.iMW2;
   } else {
     Ws bw;
     memset(&bw, 0, sizeof(bw));
-    bw.iWih = o.iWih; bw.iWhh = o.iWhh;
-    RUN(build_gru_images(c, d, bw, P, s));
+    bw.iWih = o.iWih; bw.iWhh = o.iWhh; bw.iMW1 = o.iMW1; bw.iMW2 = o.iMW2;
+    RUN(build_gru_images(c, d, bw, P, s, true));
   }
   HIPOK(hipMemsetAsync(o.rep, 0, (size_t)c->n_nodes * sizeof(int32_t), s), "memset failed");
   Ws w;                                                           // what state_update() reads of a step's workspace
@@ -1652,10 +1744,14 @@ extern "C" int pfo_tgn_observe(const pfo_tgn_config* c, const pfo_tgn_state* st,
     RUN(pfo_observe_select_launch(src + k0, dst + k0, b, st->has_msg, o.rep, (int)base, o.slot, o.touched, o.n_rows, s));
     base += 2 * (int64_t)b;
     PfoGruFused f;
-    f.gather = 1; f.msg_rows = st->msg_table; f.K_msg = d.M; f.h_rows = st->memory; f.hm = st->has_msg;
+    f.gather = 1; f.msg_rows = st->msg_table; f.K_msg = d.Mg; f.h_rows = st->memory; f.hm = st->has_msg;
     f.img_ih = iWih; f.img_hh = iWhh; f.b_ih = P.b_ih; f.b_hh = P.b_hh; f.touched = o.touched; f.node_feat = st->node_feat;
     f.upd_mem = o.upd_mem; f.h0_tab = o.h0_tab; f.gates = o.gates; f.D = d.D;
     f.cap_rows = (int)std::min<int64_t>(c->n_nodes, 2 * (int64_t)b); f.n_rows = o.n_rows;
+    if (d.Hm > 0) {                                               // the step's own MLP stage over the selected rows
+      RUN(message_mlp(d, P, st->msg_table, o.touched, iMW1, iMW2, o.mlp_hid, o.mlp_out, f.cap_rows, o.n_rows, s));
+      f.gather = 2; f.msg_rows = o.mlp_out;
+    }
     RUN(pfo_gru_fused_launch(f, s));
     RUN(state_update(c, st, w, src + k0, dst + k0, ts + k0, eidx + k0, b, s));
   }

@@ -199,8 +199,8 @@ class TGN(nn.Module):
         if embedding_module_type != "graph_attention":
             raise ValueError("Embedding Module {} not supported".format(embedding_module_type))
         if use_memory:
-            if message_function != "identity":
-                raise ValueError("Message function {} not supported (identity only)".format(message_function))
+            if message_function not in ("identity", "mlp"):
+                raise ValueError("Message function {} not implemented".format(message_function))
             if aggregator_type != "last":
                 raise ValueError("Message aggregator {} not implemented".format(aggregator_type))
             if memory_updater_type != "gru":
@@ -236,8 +236,17 @@ class TGN(nn.Module):
             raise ValueError("memory_dimension must equal the node-feature dimension (embedding_module.py:98)")
         self.memory_dimension = D
 
+        # message function (modules/message_function.py): "identity" hands the raw message [3D+Ef] to the GRU (tgn.py:66 then
+        # ignores message_dimension); "mlp" puts Linear(3D+Ef, (3D+Ef)//2) -> ReLU -> Linear(., message_dimension) in front of it
+        self.message_function_type = message_function if self.use_memory else None
+        mlp = self.use_memory and message_function == "mlp"
+        if mlp and (int(message_dimension) <= 0 or int(message_dimension) % 4 != 0):
+            raise ValueError("message_dimension must be a positive multiple of 4 (got {})".format(message_dimension))
+        if mlp and (3 * D + Ef) // 2 < 1:
+            raise ValueError("the raw message is too short for the MLP message function")
+        self.message_dimension = int(message_dimension) if mlp else 3 * D + Ef
         self._cfg = _lib.TgnConfig(self.n_nodes, self.edge_raw_features.shape[0], D, Ef, self.n_layers, self.n_heads,
-                                   int(self.use_memory), 1, 1, 1)
+                                   int(self.use_memory), 1, 1, 1, self.message_dimension if mlp else 0, (3 * D + Ef) // 2 if mlp else 0)
         self._layout = _lib.TgnLayout()
         _lib.call("pfo_tgn_param_layout", ctypes.byref(self._cfg), ctypes.byref(self._layout))
         self._flat = torch.zeros(self._layout.total, dtype=torch.float32, device=self.device)
@@ -289,17 +298,36 @@ class TGN(nn.Module):
         self._gru_params = set()
         self._gru_applied_now = True
         if self.use_memory:
-            self.memory = Memory(n_nodes=self.n_nodes, memory_dimension=D, input_dimension=M, message_dimension=M,
+            Mg = self.message_dimension
+            self.memory = Memory(n_nodes=self.n_nodes, memory_dimension=D, input_dimension=M, message_dimension=Mg,
                                  device=self.device)
+            if mlp:
+                # the reference writes ``self.mlp = self.layers = nn.Sequential(...)``: one module under two names, so the
+                # state dict carries every tensor twice and parameters() yields it once
+                self.message_function = _Holder()
+                seq = _Holder()
+                lin0, lin2 = _Holder(), _Holder()
+                seq.add_module("0", lin0)
+                seq.add_module("2", lin2)
+                self._register(lin0, "weight", lay.mlp_w1, (M // 2, M))
+                self._register(lin0, "bias", lay.mlp_b1, (M // 2,))
+                self._register(lin2, "weight", lay.mlp_w2, (Mg, M // 2))
+                self._register(lin2, "bias", lay.mlp_b2, (Mg,))
+                self.message_function.mlp = seq
+                self.message_function.layers = seq
             self.memory_updater = _Holder()
             self.memory_updater.layer_norm = nn.LayerNorm(D).to(self.device)     # constructed, never applied (memory_updater.py:14)
             self.memory_updater.memory_updater = _Holder()
             gru = self.memory_updater.memory_updater
-            self._register(gru, "weight_ih", lay.gru_w_ih, (3 * D, M))
+            self._register(gru, "weight_ih", lay.gru_w_ih, (3 * D, Mg))
             self._register(gru, "weight_hh", lay.gru_w_hh, (3 * D, D))
             self._register(gru, "bias_ih", lay.gru_b_ih, (3 * D,))
             self._register(gru, "bias_hh", lay.gru_b_hh, (3 * D,))
+            # (with them the MLP's: message_aggregator / memory_updater return before either module is called when no node
+            #  holds a pending message, and autograd leaves all eight gradients at None)
             self._gru_params = set(gru.parameters())
+            if mlp:
+                self._gru_params |= set(self.message_function.parameters())
 
         self.embedding_module = _Holder()
         self.embedding_module.neighbor_finder = neighbor_finder       # main.py:427 assigns this attribute directly
@@ -362,6 +390,11 @@ class TGN(nn.Module):
                 k = 1.0 / math.sqrt(D)
                 for p in self.memory_updater.memory_updater.parameters():
                     p.uniform_(-k, k)
+                if self.message_function_type == "mlp":
+                    for lin in (getattr(self.message_function.mlp, "0"), getattr(self.message_function.mlp, "2")):   # nn.Linear.reset_parameters
+                        nn.init.kaiming_uniform_(lin.weight, a=math.sqrt(5))
+                        bound = 1.0 / math.sqrt(lin.weight.shape[1])
+                        lin.bias.uniform_(-bound, bound)
             for att in self.embedding_module.attention_models:
                 mha = att.multi_head_target
                 for w in (mha.q_proj_weight, mha.k_proj_weight, mha.v_proj_weight):
@@ -458,7 +491,8 @@ class TGN(nn.Module):
 
     def _cfg_for(self, caps):
         c = self._cfg
-        return _lib.TgnConfig(c.n_nodes, c.n_edges_p1, c.D, c.Ef, c.n_layers, c.n_heads, c.use_memory, caps[0], caps[1], caps[2])
+        return _lib.TgnConfig(c.n_nodes, c.n_edges_p1, c.D, c.Ef, c.n_layers, c.n_heads, c.use_memory, caps[0], caps[1], caps[2],
+                              c.msg_dim, c.msg_hidden)
 
     def _torch_versions(self):
         # every parameter's own counter too: after .to(device) / .float() they no longer share the flat buffer's
@@ -1693,6 +1727,17 @@ class TGN(nn.Module):
             out.update(dgi=view(dbg.gru_dgi, nc * 3 * D).view(nc, 3 * D).cpu().numpy(),
                        msg_rows=view(dbg.gru_msg_rows, nc * M).view(nc, M).cpu().numpy())
         return out
+
+    def debug_message_mlp(self):
+        """(touched node ids [n], hidden activations [n, msg_hidden], MLP output [n, message_dimension]) of the last forward
+        with message_function="mlp" (before the next forward reuses the workspace); row i belongs to node ids[i]."""
+        dbg, view = self._debug_views()
+        if not dbg.mlp_hid or not dbg.mlp_out:
+            raise RuntimeError("the model has no MLP message function")
+        n = int(view(dbg.n_touched, 1, torch.int32).item())
+        Hm, Mg = int(self._cfg.msg_hidden), int(self._cfg.msg_dim)
+        return (view(dbg.touched_ids, n, torch.int32).clone(), view(dbg.mlp_hid, n * Hm).view(n, Hm).clone(),
+                view(dbg.mlp_out, n * Mg).view(n, Mg).clone())
 
     def debug_touched(self):
         """(touched node ids, layer-0 feature table rows) of the last forward (use_memory only)."""

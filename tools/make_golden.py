@@ -7,7 +7,7 @@ reference's outputs.  The fixtures are data only - no reference source text is
 stored.  The inline MV block of main.py (not importable: wandb/CUDA/data files)
 is executed in place from the reference tree, as SURVEY.md App. E describes.
 
-Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8 g9a g9b g10]  (default: all)
+Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8 g9a g9b g10 g11]  (default: all)
 g10 = the g1 / g5 recipes on ``yyyymmddHHMMSS`` timestamps (~2.02e13: one f32 step is 2**21, about two calendar days).
 Library versions used are recorded in each fixture (``versions``).
 """
@@ -280,17 +280,23 @@ def g5():
     step_fixtures("g5_step_", 16)
 
 
-def step_fixtures(prefix, dim, timestamps=None):
+G5_CASES = (("L1_mem", 1, True, False, 2, "base"), ("L2_mem", 2, True, False, 2, "base"),
+            ("L2_nomem_uniform", 2, False, True, 4, "base"), ("L1_mem_p", 1, True, False, 2, "p"))
+
+
+def step_fixtures(prefix, dim, timestamps=None, cases=G5_CASES, message_function="identity", seed=1, recorded=(2, 3, 4), write=True):
     # Note: every recorded step stores its own inputs (state_dict, memory, pending messages, batch, draws) next to its
     # outputs, so a fixture is self-contained.  The 5-step trajectory itself is not bit-reproducible across runs of this
     # script for the 2-layer memory case (multi-threaded CPU reductions in the reference's torch ops); regenerating
     # replaces that fixture with an equally valid one.
     # ``timestamps`` (g10): f64[E] sorted, replace the synthetic graph's; the uniform case then also records every sampler
     # call's output in the reference's own slot order and the draws re-addressed to the canonical order (readdress_draws).
+    # ``cases`` / ``message_function`` / ``seed`` / ``recorded`` (g11): the same recipe on other configurations; with the MLP
+    # message function the smallest |hidden pre-activation| the reference computed over the recorded steps is stored as
+    # ``mlp_min_abs_preact``.  ``write`` = False returns the arrays of the (single) case instead of saving them.
     R = ref_modules()
-    for tag, L, use_mem, uniform, H, path in (("L1_mem", 1, True, False, 2, "base"), ("L2_mem", 2, True, False, 2, "base"),
-                                               ("L2_nomem_uniform", 2, False, True, 4, "base"), ("L1_mem_p", 1, True, False, 2, "p")):
-        torch.manual_seed(1); np.random.seed(1)
+    for tag, L, use_mem, uniform, H, path in cases:
+        torch.manual_seed(seed); np.random.seed(seed)
         cfg = SyntheticConfig("g5", 120, 20, 1500, dim, L, 5, H)
         g = make_graph(cfg, with_prices=False)
         d = g.data
@@ -303,23 +309,29 @@ def step_fixtures(prefix, dim, timestamps=None):
         nf = R.get_neighbor_finder(rdata, uniform=uniform)
         tgn = R.TGN(neighbor_finder=nf, node_features=g.node_features, edge_features=g.edge_features.copy(), device=torch.device("cpu"),
                     n_layers=L, n_heads=H, dropout=0.0, use_memory=use_mem, message_dimension=100, memory_dimension=D,
-                    memory_update_at_start=True, embedding_module_type="graph_attention", message_function="identity",
+                    memory_update_at_start=True, embedding_module_type="graph_attention", message_function=message_function,
                     aggregator_type="last", memory_updater_type="gru", n_neighbors=K)
         with torch.no_grad():
             tgn.time_encoder.w.bias.copy_(torch.randn(D) * 0.3)
+        preact = []                                  # (step, min |Linear 0 output|) of every MLP call
+        cur_step = [0]
+        if message_function == "mlp":
+            tgn.message_function.mlp[0].register_forward_hook(
+                lambda mod, inp, res: preact.append((cur_step[0], float(res.detach().abs().min()) if res.numel() else np.inf)))
         opt = torch.optim.Adam(tgn.parameters(), lr=1e-3)
         rs = np.random.RandomState(2)
         out = dict(L=np.array(L), H=np.array(H), K=np.array(K), use_memory=np.array(use_mem), uniform=np.array(uniform),
                    path=np.array(path), src_all=d.sources, dst_all=d.destinations, ts_all=d.timestamps, eidx_all=d.edge_idxs,
                    node_features=g.node_features, edge_features=g.edge_features, lr=np.array(1e-3))
-        n_steps, first = 5, 700
+        n_steps, first = max(recorded) + 1, 700
         for step in range(n_steps):
+            cur_step[0] = step
             s = first + step * B
             sb, db, tb, eb = d.sources[s:s + B], d.destinations[s:s + B], d.timestamps[s:s + B], d.edge_idxs[s:s + B]
             n_neg = 3
             neg = rs.randint(cfg.n_users + 1, cfg.n_users + cfg.n_items + 1, size=(B, n_neg))
             ppos = rs.randint(cfg.n_users + 1, cfg.n_users + cfg.n_items + 1, size=B)
-            record = step >= 2
+            record = step in recorded
             pre = "s%d_" % step
             if record:
                 sd = {k: v.detach().numpy().copy() for k, v in tgn.state_dict().items()
@@ -405,12 +417,41 @@ def step_fixtures(prefix, dim, timestamps=None):
                     out.update({pre + "after_memory": tgn.memory.memory.detach().numpy().copy(),
                                 pre + "after_last_update": tgn.memory.last_update.detach().numpy().copy(),
                                 pre + "after_msg_tab": tab, pre + "after_msg_t": mt, pre + "after_msg_cnt": cnt})
-        out["recorded_steps"] = np.array([2, 3, 4])
+        out["recorded_steps"] = np.array(list(recorded))
+        if message_function == "mlp":
+            out["mlp_min_abs_preact"] = np.array(min(v for st_, v in preact if st_ in recorded), np.float64)
+        if not write:
+            assert len(cases) == 1
+            return out
         if uniform and timestamps is not None:
             n_moved = sum(int(out["s%d_n_readdressed_roots" % s_]) for s_ in (2, 3, 4))
             assert n_moved > 0, "no root whose reference slot order differs from the stable one: the fixture would not pin the tie policy"
             print("%s%s: %d roots re-addressed over the recorded steps" % (prefix, tag, n_moved))
         save(prefix + tag, **out)
+
+
+# ------------------------------------------------------------------ G11: the same steps with the MLP message function
+def g11():
+    """g5's recipe with message_function="mlp", message_dimension=100 (the reference's and main.py's defaults): memory, most-recent
+    sampling.  L = 1 (main.py's own layer count): D 16 / Ef 4 -> raw message 52, hidden 26 (not a multiple of 4); L = 2: D 12 ->
+    raw message 40, hidden 20 (at D 16 its two steps do not fit a committed file).  Two consecutive recorded steps each; the state dict carries every MLP tensor under both of the reference's names
+    (message_function.mlp.* and message_function.layers.*).
+    A hidden unit whose pre-activation sits within rounding distance of zero could take the other ReLU branch on another
+    implementation whose forward agrees to ~1e-6; the seed is moved until the smallest |pre-activation| the reference computed
+    over the recorded steps is at least parity.KINK_THR, and that minimum is stored in the fixture."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from parity import KINK_THR
+    for dim, case in ((16, ("L1_mem_mlp", 1, True, False, 2, "base")), (12, ("L2_mem_mlp", 2, True, False, 2, "base"))):
+        for seed in range(1, 40):
+            out = step_fixtures("g11_step_", dim, cases=(case,), message_function="mlp", seed=seed, recorded=(2, 3), write=False)
+            lo = float(out["mlp_min_abs_preact"])
+            print("g11 %s seed %d: min |hidden pre-activation| %.3g" % (case[0], seed, lo))
+            if lo >= KINK_THR:
+                break
+        else:
+            raise AssertionError("no seed keeps the hidden pre-activations away from the kink")
+        out["seed"] = np.array(seed)
+        save("g11_step_" + case[0], **out)
 
 
 def g6():
@@ -1063,6 +1104,6 @@ def g10():
 if __name__ == "__main__":
     import warnings
     warnings.filterwarnings("ignore")
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9a", "g9b", "g10"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9a", "g9b", "g10", "g11"]
     for w in which:
         globals()[w]()
