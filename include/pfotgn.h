@@ -443,6 +443,27 @@ int pfo_adam_step_ranges(float* param, const float* grad, float* exp_avg, float*
                          const int64_t* lo, const int64_t* hi, const int32_t* step, float lr, float beta1, float beta2,
                          float eps, void* stream);
 
+/* What goes in FRONT of the Adam launch when FusedAdam clips or decays (csrc/optim.hip): global-norm clipping after
+ * torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) and the decoupled weight decay of torch.optim.AdamW, over
+ * the same (n_ranges <= PFO_ADAM_MAX_RANGES, lo[], hi[]) description of the flat buffers (HOST arrays, arbitrary element
+ * offsets, lo[r] == hi[r] allowed).  Both queue on `stream` and never synchronise with the host.
+ *   pfo_grad_sumsq_ranges   : partial[PFO_GRAD_NORM_PARTS] (f64, device) = / += the sum of squares of the listed elements of
+ *                             grad, one slot per workgroup.  Which element feeds which slot, and in which order, is a function
+ *                             of (lo, hi, PFO_GRAD_NORM_PARTS) alone - no float atomics, no dependence on timing: two runs give
+ *                             the same bits.  accumulate = 0 overwrites EVERY slot, 1 adds to it (a step of more than
+ *                             PFO_ADAM_MAX_RANGES ranges: chunks in stream order).
+ *   pfo_grad_prestep_ranges : every workgroup folds partial in index order (the same bits everywhere), total = (float)sqrt(sum),
+ *                             coef = max_norm / (total + 1e-6f) clamped to at most 1 (fp32; a NaN stays a NaN), then
+ *                             grad[i] *= coef and param[i] *= decay over the ranges; workgroup 0 stores total to norm_out (f32[1]).
+ *                             max_norm <= 0: no clipping - partial and norm_out may be NULL, grad is not written.
+ *                             decay == 1: param is not written.  Elements outside the ranges are never touched.
+ * PFO_ERR_INVALID - nothing is queued: a NULL pointer that is needed, n_ranges outside [1, PFO_ADAM_MAX_RANGES], lo > hi, lo < 0. */
+#define PFO_GRAD_NORM_PARTS 256
+int pfo_grad_sumsq_ranges(const float* grad, int32_t n_ranges, const int64_t* lo, const int64_t* hi, double* partial,
+                          int32_t accumulate, void* stream);
+int pfo_grad_prestep_ranges(float* param, float* grad, int32_t n_ranges, const int64_t* lo, const int64_t* hi,
+                            const double* partial, float max_norm, float decay, float* norm_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The TGN step (model/tgn.py:102-378 + modules/).  One POD config, one flat parameter buffer,
  * caller-owned state tables and workspace.

@@ -17,6 +17,8 @@ RECOMMEND_MAX_ITEMS = 65536     # PFO_RECOMMEND_MAX_ITEMS
 RECOMMEND_MV_MAX_ITEMS = 2048   # PFO_RECOMMEND_MV_MAX_ITEMS
 RECOMMEND_MV_WIDE_MAX_ITEMS = 65536   # PFO_RECOMMEND_MV_WIDE_MAX_ITEMS
 EVAL_RANK_NONE = (1 << 31) - 1  # PFO_EVAL_RANK_NONE: the positive is not ranked
+ADAM_MAX_RANGES = 16            # PFO_ADAM_MAX_RANGES
+GRAD_NORM_PARTS = 256           # PFO_GRAD_NORM_PARTS
 
 
 class TgnConfig(C.Structure):
@@ -186,6 +188,9 @@ PROTOTYPES = {
                                        C.POINTER(C.c_int32), C.c_float, C.c_float, C.c_float, C.c_float, _VP]),
     "pfo_adam_step_ranges_dev": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                            C.POINTER(C.c_int32), _VP, C.c_float, C.c_float, C.c_float, C.c_float, _VP]),
+    "pfo_grad_sumsq_ranges": (C.c_int, [_VP, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _VP, C.c_int32, _VP]),
+    "pfo_grad_prestep_ranges": (C.c_int, [_VP, _VP, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _VP, C.c_float, C.c_float,
+                                          _VP, _VP]),
     "pfo_tgn_param_layout": (C.c_int, [C.POINTER(TgnConfig), C.POINTER(TgnLayout)]),
     "pfo_tgn_workspace_bytes": (C.c_int64, [C.POINTER(TgnConfig)]),
     "pfo_tgn_adam_side": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),

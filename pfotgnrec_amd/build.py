@@ -10,7 +10,7 @@ CSRC = os.environ.get("PFO_CSRC") or os.path.join(HERE, "csrc")     # override: 
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpfotgn.so")
 SOURCES = ["sampler.hip", "gemm.hip", "attn.hip", "memory.hip", "misc.hip", "csr.hip", "tgn.hip", "eval.hip", "recommend.hip", "ingest.hip",
-           "holdings.hip", "prices.hip", "probe.hip"]
+           "holdings.hip", "prices.hip", "optim.hip", "probe.hip"]
 ARCH = "gfx950"
 
 

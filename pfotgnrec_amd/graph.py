@@ -95,7 +95,7 @@ class GraphedTrainStep:
         nf = tgn.neighbor_finder
         mem = tgn.memory
         self._keep = (tgn._last_ws, tgn._adj_cache, tgn._pcache, tgn.flat_parameters, tgn.flat_grad, self.opt._m, self.opt._v,
-                      tgn.node_raw_features, tgn.edge_raw_features,
+                      getattr(self.opt, "_partial", None), getattr(self.opt, "last_grad_norm", None), tgn.node_raw_features, tgn.edge_raw_features,
                       None if mem is None else (mem.memory, mem.last_update, mem.msg_table, mem.msg_time, mem.has_msg))
         self._guard = (nf, getattr(nf, "_version", 0), tgn._ws_caps, tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(),
                        tgn._tables_version)

@@ -5,8 +5,13 @@ reference hits that on the first batch after every ``__init_memory__`` (main.py:
 is never called (memory_updater.py:38-40) and its four tensors stay one step behind for the rest of the run.  The same
 bookkeeping is done here on the host; the device work is still ONE launch (``pfo_adam_step_ranges``: contiguous runs of
 tensors with equal step counts).
+
+``weight_decay`` (torch.optim.AdamW's decoupled form) and ``max_grad_norm`` (torch.nn.utils.clip_grad_norm_) put one or two
+small launches of csrc/optim.hip in front of that kernel, on the stream the step goes to; ``state_dict()`` / ``load_state_dict()``
+speak the layout of torch.optim.Adam / AdamW, so a run resumes and moves between the two optimizers.
 """
 import ctypes
+import math
 
 import torch
 
@@ -37,7 +42,8 @@ class _StepCounts(dict):
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, tgn, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, zero_grads_in_step=False, overlap_backward=False):
+    def __init__(self, tgn, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, zero_grads_in_step=False,
+                 overlap_backward=False):
         """``overlap_backward``: for the reference's own loop (main.py:160-394), which reads ``loss.item()`` after every batch.
         ``loss.backward()`` leaves the native backward on a stream of its own and ``step()`` queues the optimizer's kernel behind
         it there, so that ``loss.item()`` waits for the forward only and the host prepares the next batch (candidate draw,
@@ -50,16 +56,151 @@ class FusedAdam(torch.optim.Optimizer):
         ``zero_grads_in_step``: a side-stream step (``step(side=True)``, i.e. ``bpr_step(..., optimizer=)``) also CLEARS the
         gradients it consumed - ``optimizer.zero_grad()`` folded into the optimizer's kernel, for loops that zero the gradients
         right after the step anyway (main.py:388-390 does): the next native backward then clears nothing on its critical path.
-        ``.grad`` reads zero after such a step."""
+        ``.grad`` reads zero after such a step.
+        ``weight_decay`` (>= 0): torch.optim.AdamW's decoupled decay - every tensor that takes part in the step is multiplied by
+        ``float32(1 - lr * weight_decay)`` (formed in double, rounded once, as ``param.mul_(1 - lr * wd)``) before the Adam update;
+        tensors whose ``.grad`` is None are left alone entirely.
+        ``max_grad_norm`` (None, or > 0 and finite): ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm, norm_type=2)`` in
+        front of the update, where the step runs: ``total`` = the L2 norm of the gradients of the tensors that take part in the
+        step, ``coef = min(1, max_grad_norm / (total + 1e-6))`` in fp32, every such gradient multiplied by ``coef`` IN PLACE.
+        ``last_grad_norm`` (f32[1] on the device, None before the first clipped step) holds ``total`` of the newest step; the
+        device writes it and the library never reads it back - read it behind ``tgn.join()``.  The sum of squares is accumulated
+        in fp64: a gradient whose squares overflow fp32 gets a finite norm where torch's fp32 norm is ``inf``.  A non-finite
+        gradient gives a non-finite ``total``; the arithmetic above is then applied as written under IEEE rules (``coef`` is 0 or
+        NaN, and so are the products).  The sum is taken in a fixed order: the same gradient gives the same bits in every step
+        form and on every data-parallel rank (the norm is that of the all-reduced gradient).
+        Both live in ``param_groups[0]`` and may be changed between steps.  Clipping puts two small launches
+        (``pfo_grad_sumsq_ranges``, ``pfo_grad_prestep_ranges``; decay alone the second) in front of the Adam kernel on the same stream - the caller's, the
+        backward's (``overlap_backward``), the library's side stream (``bpr_step(..., optimizer=)``) or the capturing one
+        (``GraphedTrainStep``); with both off nothing is launched or allocated for them.  A data-parallel rank with either one on
+        does not take the two-bucket ``dp_ordered`` route (a global norm needs the WHOLE reduced gradient before the first
+        parameter moves): the step waits for the communication stream and takes the single side step.
+        ``state_dict()`` / ``load_state_dict()`` use torch.optim.Adam's layout (see there)."""
+        self._check_options(weight_decay, max_grad_norm)
         self.tgn = tgn
         self.zero_grads_in_step = bool(zero_grads_in_step)
         if overlap_backward:
             tgn.overlap_backward = True
-        super().__init__(list(tgn.parameters()), dict(lr=lr, betas=betas, eps=eps))
+        super().__init__(list(tgn.parameters()), dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
         self._m = None
         self._v = None
+        self._partial = None        # f64[PFO_GRAD_NORM_PARTS]: the norm's partial sums (allocated with the moments when clipping is on)
+        self.last_grad_norm = None  # f32[1]: the newest step's gradient norm, written by the device
         self._steps = _StepCounts() # id(parameter) -> steps taken (torch.optim.Adam's state[p]["step"]; ids: hashing a tensor is a Python call)
         self._sorted_views = None   # (the model's views in flat-buffer order, sorted once)
+
+    @staticmethod
+    def _check_options(weight_decay, max_grad_norm):
+        if not (isinstance(weight_decay, (int, float)) and weight_decay >= 0.0 and math.isfinite(weight_decay)):
+            raise ValueError("weight_decay must be a finite number >= 0, got %r" % (weight_decay,))
+        if max_grad_norm is not None and not (isinstance(max_grad_norm, (int, float)) and max_grad_norm > 0.0 and math.isfinite(max_grad_norm)):
+            raise ValueError("max_grad_norm must be None or a finite number > 0, got %r" % (max_grad_norm,))
+
+    def _alloc_state(self, clip):
+        """The moments - and, when clipping is on, the norm's buffers with them: nothing is allocated later (a captured step)."""
+        flat = self.tgn.flat_parameters
+        if self._m is None or self._m.device != flat.device:
+            self._m = torch.zeros_like(flat)
+            self._v = torch.zeros_like(flat)
+            self._partial, self.last_grad_norm = None, None
+        if clip and self._partial is None:
+            self._partial = torch.zeros(_lib.GRAD_NORM_PARTS, dtype=torch.float64, device=flat.device)
+            self.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=flat.device)
+
+    def _prestep(self, lo, hi, lr, weight_decay, max_grad_norm):
+        """Global-norm clipping and decoupled decay over the step's ranges, on the CURRENT stream, in front of the Adam launch."""
+        tgn = self.tgn
+        clip = max_grad_norm is not None
+        decay = 1.0 - lr * float(weight_decay)           # (a Python double; the float argument rounds it once)
+        MAXR = _lib.ADAM_MAX_RANGES
+        stream = _lib.stream_ptr()
+        chunks = []
+        for i in range(0, len(lo), MAXR):
+            k = min(MAXR, len(lo) - i)
+            chunks.append((k, (ctypes.c_int64 * k)(*lo[i:i + k]), (ctypes.c_int64 * k)(*hi[i:i + k])))
+        if clip:
+            for j, ch in enumerate(chunks):              # the whole norm first: every chunk's elements, in stream order
+                _lib.call("pfo_grad_sumsq_ranges", tgn.flat_grad.data_ptr(), *ch, self._partial.data_ptr(), 1 if j else 0, stream)
+        for ch in chunks:
+            _lib.call("pfo_grad_prestep_ranges", tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), *ch,
+                      self._partial.data_ptr() if clip else None, float(max_grad_norm) if clip else 0.0, decay,
+                      self.last_grad_norm.data_ptr() if clip else None, stream)
+
+    # ------------------------------------------------------------------ torch.optim.Adam's state-dict layout
+    def state_dict(self):
+        """The layout of ``torch.optim.Adam.state_dict()``: ``state`` keyed by the index of the parameter in ``tgn.parameters()``
+        order, each entry ``step`` (a float32 scalar tensor), ``exp_avg`` and ``exp_avg_sq`` in the parameter's shape - copies,
+        not views of the flat buffers - for the tensors that have taken a step; ``param_groups[0]`` carries ``lr``, ``betas``,
+        ``eps``, ``weight_decay``, ``max_grad_norm`` and ``params``.  Joins first (``tgn.join()``)."""
+        tgn = self.tgn
+        tgn.join()
+        index = {id(p): i for i, p in enumerate(self.param_groups[0]["params"])}
+        state = {}
+        for p, off, n, shape in tgn._views:
+            t = self._steps.get(id(p), 0)
+            if t <= 0:
+                continue
+            if self._m is None:
+                m = v = torch.zeros(shape, dtype=torch.float32, device=p.device)
+            else:
+                m, v = self._m[off:off + n].view(shape), self._v[off:off + n].view(shape)
+            state[index[id(p)]] = {"step": torch.tensor(float(t), dtype=torch.float32), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+        g = self.param_groups[0]
+        group = {k: g[k] for k in ("lr", "betas", "eps", "weight_decay", "max_grad_norm")}
+        group["params"] = list(range(len(g["params"])))
+        return {"state": dict(sorted(state.items())), "param_groups": [group]}
+
+    def load_state_dict(self, state_dict):
+        """A dict written by ``torch.optim.Adam``, ``torch.optim.AdamW`` or ``FusedAdam`` over the same model.  Group keys torch
+        writes and this optimizer has no use for (``foreach``, ``capturable``, ``fused`` ...) are ignored; ``amsgrad=True`` and
+        ``maximize=True`` are refused.  Step counts are kept PER TENSOR (the GRU's tensors lag one step after
+        ``__init_memory__``); a tensor absent from ``state`` has zero moments and step 0.  Joins first (``tgn.join()``)."""
+        tgn = self.tgn
+        tgn.join()
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise ValueError("FusedAdam holds one parameter group, the state dict has %d" % len(groups))
+        src = groups[0]
+        params = self.param_groups[0]["params"]
+        if len(src["params"]) != len(params):
+            raise ValueError("the state dict names %d parameters, the model has %d" % (len(src["params"]), len(params)))
+        for flag in ("amsgrad", "maximize"):
+            if src.get(flag):
+                raise ValueError("FusedAdam has no %s: a state dict written with %s=True cannot be loaded" % (flag, flag))
+        wd = src.get("weight_decay", self.param_groups[0]["weight_decay"])
+        mx = src.get("max_grad_norm", self.param_groups[0]["max_grad_norm"])
+        self._check_options(wd, mx)
+        by_id = {id(p): (off, n, shape) for p, off, n, shape in tgn._views}
+        entries = []
+        for key, pos in zip(src["params"], range(len(params))):      # (the dict's own indices, in order, name the positions)
+            st = state_dict["state"].get(key)
+            if st is None:
+                continue
+            p = params[pos]
+            if id(p) not in by_id:
+                raise ValueError("parameter %d has optimizer state but FusedAdam never steps it (it is not in the flat buffer)" % pos)
+            off, n, shape = by_id[id(p)]
+            if tuple(st["exp_avg"].shape) != shape or tuple(st["exp_avg_sq"].shape) != shape:
+                raise ValueError("parameter %d: moments of shape %s, the tensor has %s" % (pos, tuple(st["exp_avg"].shape), shape))
+            step = st["step"]
+            entries.append((p, off, n, int(round(float(step.item() if torch.is_tensor(step) else step))), st["exp_avg"], st["exp_avg_sq"]))
+        flat = tgn.flat_parameters
+        if entries or self._m is not None:
+            self._m, self._v = torch.zeros_like(flat), torch.zeros_like(flat)
+            if self._partial is not None and self._partial.device != flat.device:
+                self._partial, self.last_grad_norm = None, None
+        steps = _StepCounts()
+        for p, off, n, t, m, v in entries:
+            self._m[off:off + n].copy_(m.detach().reshape(-1))
+            self._v[off:off + n].copy_(v.detach().reshape(-1))
+            if t > 0:
+                steps[id(p)] = t
+        self._steps = steps
+        g = self.param_groups[0]
+        for k in ("lr", "betas", "eps"):
+            if k in src:
+                g[k] = tuple(src[k]) if k == "betas" else src[k]
+        g["weight_decay"], g["max_grad_norm"] = wd, mx
 
     def zero_grad(self, set_to_none=True):
         if not set_to_none:
@@ -101,7 +242,13 @@ class FusedAdam(torch.optim.Optimizer):
 
     def _step(self, closure, step_dev, side):
         tgn = self.tgn
-        if side and (self._m is None or self._m.device != tgn.flat_parameters.device):
+        g = self.param_groups[0]
+        weight_decay, max_grad_norm = g["weight_decay"], g["max_grad_norm"]
+        clip = max_grad_norm is not None
+        pre = clip or weight_decay != 0        # (both off: nothing below this line is launched, allocated or branched on for them)
+        if pre:
+            self._check_options(weight_decay, max_grad_norm)
+        if side and (self._m is None or self._m.device != tgn.flat_parameters.device or (clip and self._partial is None)):
             side = False            # the moments are allocated (and cleared) on the caller's stream below: this one step runs there
         if not side:
             tgn.join()
@@ -112,10 +259,8 @@ class FusedAdam(torch.optim.Optimizer):
         if tgn.flat_grad is None:
             return None
         _lib.require_gpu(tgn.flat_parameters.device)
-        if self._m is None or self._m.device != tgn.flat_parameters.device:
-            self._m = torch.zeros_like(tgn.flat_parameters)
-            self._v = torch.zeros_like(tgn.flat_parameters)
-        g = self.param_groups[0]
+        if self._m is None or self._m.device != tgn.flat_parameters.device or (clip and self._partial is None):
+            self._alloc_state(clip)
         lo, hi, st = [], [], []
         sv = self._sorted_views
         if sv is None or sv[0] is not tgn._views or len(sv[1]) != len(tgn._views):
@@ -137,7 +282,9 @@ class FusedAdam(torch.optim.Optimizer):
         zero_all = bool(side and self.zero_grads_in_step and step_dev is None and covered and len(lo) <= MAXR)
         args = (tgn.flat_parameters.data_ptr(), tgn.flat_grad.data_ptr(), self._m.data_ptr(), self._v.data_ptr())
         hyp = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]))
-        ordered = side and getattr(tgn, "dp_ordered", False) and step_dev is None and 0 < tgn.grad_split < tgn.flat_parameters.numel()
+        # (clipping / decay: a global norm needs the whole reduced gradient before the first parameter moves - no two-bucket route)
+        ordered = (side and getattr(tgn, "dp_ordered", False) and step_dev is None and not pre
+                   and 0 < tgn.grad_split < tgn.flat_parameters.numel())
         if ordered:
             # Two buckets in order of first use: [0, split) = time encoder, GRU, layer 1 - the next forward reads them on the
             # caller's stream ~70 us into the step and waits for THIS kernel alone; [split, total) = the top layer's block, whose
@@ -170,6 +317,13 @@ class FusedAdam(torch.optim.Optimizer):
             tgn.wait_comm_stream()                    # (nothing to cut: the plain side step below, behind the top block's all-reduce)
         elif side and getattr(tgn, "_comm_pending", None) is not None:
             tgn.wait_comm_stream()
+        if pre and lo:
+            # in front of the Adam launch(es), on the stream they go to, over the same ranges
+            if side:
+                with _lib.on_stream(tgn.side_stream()):          # behind the backward's end and the collective, as bpr_step queues that
+                    self._prestep(lo, hi, hyp[0], weight_decay, max_grad_norm)
+            else:
+                self._prestep(lo, hi, hyp[0], weight_decay, max_grad_norm)
         for i in range(0, len(lo), MAXR):
             k = min(MAXR, len(lo) - i)
             ranges = (k, (ctypes.c_int64 * k)(*lo[i:i + k]), (ctypes.c_int64 * k)(*hi[i:i + k]), (ctypes.c_int32 * k)(*st[i:i + k]))
