@@ -271,6 +271,42 @@ int pfo_eval_metrics_mv(const float* emb, int64_t B, int32_t D, int32_t n_neg, c
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A served list scored against what happened (abi 6, additive): the place in the list of the item the user then took, and what
+ * the first c stocks of the list would have done to the user's portfolio, at every cutoff c of a caller's choice - whatever
+ * order produced the list (pfo_recommend_topk, _mv_topk, _mv_topk_wide, _basket_topk or anything else).  One launch, one
+ * wavefront per user; nothing but the outputs is written.
+ *   list_item i32[U, L]: item NODE ids, best first, 1 <= L <= 64.  n_valid i32[U] or NULL (= L everywhere), clamped to [0, L]:
+ *   the slots in front of it count.  A slot holding a negative id is skipped; it ends nothing and keeps its place.
+ *   truth i32[U]: the item the user took; < 0: none.
+ *   cutoffs: a HOST array of n_c ints, 1 <= n_c <= 8, strictly increasing, each in [1, L].  Cutoff c = the first c SLOTS.
+ *   port_idx i32[U, port_stride] stock indices, port_len i32[U] clamped to [0, port_stride] (both may be NULL with port_stride
+ *   0); a list item's stock is its id - upper_u - 1; a stock that occurs twice - in the portfolio, in the list, or in both -
+ *   counts twice.
+ *   ret_past f64[past_days, past_stocks, n_ret] read at day_past i32[U], ret_future f64[future_days, future_stocks, n_ret] read
+ *   at day_future i32[U]; 2 <= n_ret <= 128.  The two tables may be the same storage (a price ledger's, the days then ring
+ *   slots).  A day outside a table turns THAT table's figures of the row into NaN; a stock outside a table those of that
+ *   table from the first series it takes part in (a portfolio stock: all of them; the stock in slot t: the cutoffs > t).
+ *   Nothing is read out of bounds, and the other table's figures are untouched (pfo_eval_metrics has one day index).
+ * Rows [out_row0, out_row0 + U) of buffers that hold out_rows rows are written; any output pointer may be NULL:
+ *   rank_out i32: the first counted slot that holds truth, else PFO_EVAL_RANK_NONE.
+ *   hits_out f32[., n_c] = rank < c; ndcg_out f32[., n_c] = 1.f / log2f(rank + 2) where hit, else 0: pfo_eval_metrics's
+ *   expression, bit-equal to its values at the ranks it can state (< 5).  log2f is the device library's (1 ulp): the value lies
+ *   within 3 ulp of the correctly rounded 1 / log2(rank + 2) and is exact where rank + 2 is a power of two.
+ *   invest_out f64[., 4 n_c] = (return@c.. | sharpe@c..) in-sample, then the same out-of-sample: pfo_eval_metrics's investment
+ *   stage at the cutoffs - per table the per-day sum over the portfolio rows, then the list's rows added one at a time, divided
+ *   by the row count at each cutoff (a list shorter than a cutoff adds what there is); mean and population deviation in numpy's
+ *   summation order; return = mean * 251, sharpe = return / (sd * sqrt(251)); an empty portfolio alone is 0, 0; no guards.
+ *   fp64, no contraction: with cutoffs (1, 3, 5) on pfo_eval_metrics's top5_item this is its invest_out to the bit.
+ * Errors: all bounds are checked before any device pointer is looked at (PFO_ERR_INVALID, nothing queued).  U == 0: PFO_OK.
+ */
+int pfo_list_metrics(const int32_t* list_item, const int32_t* n_valid, const int32_t* truth, int64_t U, int32_t L,
+                     const int32_t* cutoffs, int32_t n_c, const int32_t* port_idx, const int32_t* port_len, int32_t port_stride,
+                     int32_t upper_u, const double* ret_past, const int32_t* day_past, int32_t past_days, int32_t past_stocks,
+                     const double* ret_future, const int32_t* day_future, int32_t future_days, int32_t future_stocks,
+                     int32_t n_ret, int64_t out_row0, int64_t out_rows, int32_t* rank_out, float* hits_out, float* ndcg_out,
+                     double* invest_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Read-only top-k recommendation: scores a tile of users against ONE shared candidate matrix and keeps the k best per user
  * (one launch; the U x I score matrix never reaches memory).
  *   user_emb f32[U,D]; item_emb f32[n_t*I, D]: n_t blocks of the same I candidates embedded at n_t times;

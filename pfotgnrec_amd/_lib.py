@@ -164,6 +164,9 @@ PROTOTYPES = {
                                       C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP,
                                       _VP, C.c_int32, C.c_int32, C.c_int32, _VP, C.c_double, C.c_double, C.c_int32, _VP, _VP, _VP, _VP,
                                       _VP, _VP]),
+    "pfo_list_metrics": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _VP, _VP, C.c_int32,
+                                   C.c_int32, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                   C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "pfo_recommend_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int32,
                                      _VP, _VP, _VP, _VP]),
     "pfo_recommend_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,

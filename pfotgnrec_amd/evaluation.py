@@ -28,6 +28,7 @@ class InvestTables:
 
     def __init__(self, time_feature_past, time_feature_future, map_item_id, upper_u=None):
         self.map_item_id = map_item_id
+        self.upper_u = None if upper_u is None else int(upper_u)
         self.days, past = prices_from_time_feature(time_feature_past, map_item_id, upper_u)
         days_f, future = prices_from_time_feature(time_feature_future, map_item_id, upper_u)
         if [str(d) for d in self.days] != [str(d) for d in days_f]:
@@ -36,10 +37,12 @@ class InvestTables:
         self._dev = {}
 
     @classmethod
-    def from_prices(cls, days, prices_past, prices_future, map_item_id):
-        """Dense form: ``days`` the day keys of axis 0, prices f64[day, item, n_prices]."""
+    def from_prices(cls, days, prices_past, prices_future, map_item_id, upper_u=None):
+        """Dense form: ``days`` the day keys of axis 0, prices f64[day, item, n_prices]; ``upper_u`` is only recorded (``backtest``
+        reads it)."""
         self = cls.__new__(cls)
         self.map_item_id, self.days = map_item_id, list(days)
+        self.upper_u = None if upper_u is None else int(upper_u)
         self.returns_past, self.returns_future = log_returns(prices_past), log_returns(prices_future)
         if self.returns_past.shape != self.returns_future.shape or len(self.days) != self.returns_past.shape[0]:
             raise ValueError("past / future prices and the day keys differ in shape")

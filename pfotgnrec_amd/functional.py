@@ -297,6 +297,113 @@ def eval_metrics_mv(emb, batch, n_neg, cand, day_idx, port_idx, port_len, ret_pa
     return rows + extra if want_all else rows
 
 
+def check_cutoffs(cutoffs, depth, what="L"):
+    """``cutoffs`` as a tuple of ints: 1 to 8 of them, strictly increasing, each in [1, depth] (ValueError)."""
+    import operator
+    try:
+        cuts = tuple(operator.index(c) for c in cutoffs)
+    except TypeError:
+        raise ValueError("cutoffs must be a sequence of integers") from None
+    if not 1 <= len(cuts) <= 8:
+        raise ValueError("between 1 and 8 cutoffs, got %d" % len(cuts))
+    if any(b <= a for a, b in zip(cuts, cuts[1:])):
+        raise ValueError("cutoffs must be strictly increasing, got %s" % (cuts,))
+    if cuts[0] < 1 or cuts[-1] > depth:
+        raise ValueError("cutoffs must lie in [1, %s] = [1, %d], got %s" % (what, depth, cuts))
+    return cuts
+
+
+def list_buffers(rows, n_cutoffs, device):
+    """Preallocated outputs of ``list_metrics`` for ``rows`` lists and ``n_cutoffs`` cutoffs: (rank i32[rows], recall
+    f32[rows, n_c], ndcg f32[rows, n_c], invest f64[rows, 4 n_c])."""
+    _lib.require_gpu(device)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+    return (e(rows, torch.int32), e((rows, n_cutoffs), torch.float32), e((rows, n_cutoffs), torch.float32),
+            e((rows, 4 * n_cutoffs), torch.float64))
+
+
+def list_metrics(list_item, truth, cutoffs, port_idx, port_len, upper_u, ret_past, day_past, ret_future, day_future, n_valid=None,
+                 out=None, out_row0=0):
+    """A served list scored against what happened, in one launch (``pfo_list_metrics``); whatever order produced the list.
+
+    list_item i32[U, L]: item node ids, best first, as ``TGN.recommend`` returns them (L <= 64); n_valid i32[U] or None (all L):
+    the slots in front of it count; a slot holding -1 is skipped and keeps its place.  truth i32[U]: the item the user took,
+    < 0 for none.  cutoffs: up to 8 ints, strictly increasing, each in [1, L]; cutoff c = the first c slots.  port_idx i32[U, W]
+    stock indices and port_len i32[U] as ``eval_metrics`` reads them (None, None: empty portfolios); a list item's stock is its
+    id - upper_u - 1; duplicates count as often as they occur.  ret_past f64[pd, ps, n_ret] read at day_past i32[U], ret_future
+    f64[fd, fs, n_ret] at day_future i32[U] - two tables with their own extents and day numbering, or one storage twice (a
+    ``PriceLedger``'s ``returns`` with ring slots).  A day or stock outside a table makes that table's figures of the row NaN
+    and leaves the other table's alone.
+
+    Returns (rank i32[U], recall f32[U, n_c], ndcg f32[U, n_c], invest f64[U, 4 n_c]): rank = the first counted slot holding
+    truth or ``_lib.EVAL_RANK_NONE``; recall = rank < c, NDCG = 1 / log2(rank + 2) where hit; invest = (return@c.. |
+    sharpe@c..) in-sample, then out-of-sample - ``eval_metrics``'s investment stage at the cutoffs, bit for bit its [., 12] at
+    (1, 3, 5) on its own top-5.  ``out`` (``list_buffers``) and ``out_row0``: write rows [out_row0, out_row0 + U) of
+    preallocated buffers; the returned tensors are those rows.  ValueError for anything the shapes rule out, before any launch."""
+    import ctypes
+    import operator
+    if not isinstance(list_item, torch.Tensor) or list_item.dim() != 2 or list_item.dtype != torch.int32:
+        raise ValueError("list_item must be an int32 tensor [U, L]")
+    U, L = (int(v) for v in list_item.shape)
+    if not 1 <= L <= 64:
+        raise ValueError("L must be in [1, 64] (got %d)" % L)
+    cuts = check_cutoffs(cutoffs, L)
+    n_c = len(cuts)
+    for name, t in (("truth", truth), ("day_past", day_past), ("day_future", day_future), ("n_valid", n_valid)):
+        if name == "n_valid" and t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (U,) or t.dtype != torch.int32:
+            raise ValueError("%s must be int32 [U] with U = %d" % (name, U))
+    W = 0
+    if port_idx is not None:
+        if not isinstance(port_idx, torch.Tensor) or port_idx.dim() != 2 or port_idx.shape[0] != U or port_idx.dtype != torch.int32:
+            raise ValueError("port_idx must be int32 [U, W]")
+        W = int(port_idx.shape[1])
+        if W and (not isinstance(port_len, torch.Tensor) or tuple(port_len.shape) != (U,) or port_len.dtype != torch.int32):
+            raise ValueError("port_len must be int32 [U]")
+    for name, t in (("ret_past", ret_past), ("ret_future", ret_future)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float64 or 0 in t.shape or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 tensor [days, stocks, n_ret]" % name)
+        if max(t.shape[0], t.shape[1]) >= 1 << 31:
+            raise ValueError("%s does not fit 32-bit extents" % name)
+    n_ret = int(ret_past.shape[2])
+    if int(ret_future.shape[2]) != n_ret:
+        raise ValueError("ret_past holds %d returns per stock, ret_future %d" % (n_ret, int(ret_future.shape[2])))
+    if not 2 <= n_ret <= 128:
+        raise ValueError("n_ret must be in [2, 128] (got %d)" % n_ret)
+    try:
+        upper_u, out_row0 = operator.index(upper_u), operator.index(out_row0)
+    except TypeError:
+        raise ValueError("upper_u and out_row0 must be integers") from None
+    if not -(1 << 31) <= upper_u < (1 << 31):
+        raise ValueError("upper_u does not fit 32 bits")
+    dev = list_item.device
+    if out is not None:
+        want = ((), (n_c,), (n_c,), (4 * n_c,))
+        dts = (torch.int32, torch.float32, torch.float32, torch.float64)
+        if len(out) != 4 or any(not isinstance(o, torch.Tensor) or o.dim() < 1 or o.dtype != dt or tuple(o.shape[1:]) != w
+                                or o.shape[0] != out[0].shape[0] or not o.is_contiguous() or o.device != dev
+                                for o, w, dt in zip(out, want, dts)):
+            raise ValueError("out must be the four contiguous tensors of list_buffers(rows, %d, device)" % n_c)
+        if out_row0 < 0 or out_row0 + U > out[0].shape[0]:
+            raise ValueError("rows [%d, %d) exceed the output buffers (%d rows)" % (out_row0, out_row0 + U, out[0].shape[0]))
+    elif out_row0 != 0:
+        raise ValueError("out_row0 without out")
+    _lib.require_gpu(dev)
+    for t in (truth, day_past, day_future, n_valid, port_idx if W else None, port_len if W else None, ret_past, ret_future):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    if out is None:
+        out = list_buffers(U, n_c, dev)
+    c = lambda t: None if t is None else t.contiguous()
+    ins = [c(list_item), c(n_valid), c(truth), c(port_idx) if W else None, c(port_len) if W else None, c(day_past), c(day_future)]
+    _lib.call("pfo_list_metrics", _lib.ptr(ins[0]), _lib.ptr(ins[1]), _lib.ptr(ins[2]), U, L, (ctypes.c_int32 * n_c)(*cuts), n_c,
+              _lib.ptr(ins[3]), _lib.ptr(ins[4]), W, upper_u, ret_past.data_ptr(), _lib.ptr(ins[5]), int(ret_past.shape[0]),
+              int(ret_past.shape[1]), ret_future.data_ptr(), _lib.ptr(ins[6]), int(ret_future.shape[0]), int(ret_future.shape[1]),
+              n_ret, out_row0, int(out[0].shape[0]), *[o.data_ptr() for o in out], _lib.stream_ptr())
+    return tuple(o[out_row0:out_row0 + U] for o in out)
+
+
 def _recommend_check(user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, also=()):
     """The argument checks the three top-k forms share.  ``dims(U, rows)`` is the caller's part: it checks what only that form
     takes and returns ``(I, n_t)``; ``also``: its tensors, for the device check.  Returns the tensors as the library takes them

@@ -9,6 +9,7 @@ inference and - for the BPR loss - an autograd formula:
     torch.ops.pfotgn.time_encode(t, weight, bias)                              model/time_encoding.py:17-25
     torch.ops.pfotgn.bpr_loss(emb, batch, n_neg, pos_block, grad_scale)        main.py:321-337 / 364-381
     torch.ops.pfotgn.rank_metrics(emb, batch, n_items)                         evaluation.py:114-145
+    torch.ops.pfotgn.list_metrics(list_item, truth, cutoffs, upper_u, ...)     a served list against what happened (no reference form)
     torch.ops.pfotgn.recommend_topk(user_emb, item_emb, k, n_blocks, ...)      the k best candidates per user (no reference form)
     torch.ops.pfotgn.recommend_mv_topk(user_emb, item_emb, k, cand_stock, ...) the same under the rank fusion of main.py:243-289
     torch.ops.pfotgn.recommend_mv_topk_wide(...)                               its form for lists beyond 2048 candidates
@@ -100,6 +101,22 @@ def rank_metrics(emb: torch.Tensor, batch: int, n_items: int) -> tuple[torch.Ten
 def _(emb, batch, n_items):
     return (emb.new_empty((batch,), dtype=torch.int32), emb.new_empty((batch, 3), dtype=torch.float32),
             emb.new_empty((batch, 3), dtype=torch.float32))
+
+
+@torch.library.custom_op(_LIB_NS + "::list_metrics", mutates_args=(), device_types="cuda")
+def list_metrics(list_item: torch.Tensor, truth: torch.Tensor, cutoffs: list[int], upper_u: int, ret_past: torch.Tensor,
+                 day_past: torch.Tensor, ret_future: torch.Tensor, day_future: torch.Tensor, port_idx: Optional[torch.Tensor] = None,
+                 port_len: Optional[torch.Tensor] = None,
+                 n_valid: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return functional.list_metrics(list_item, truth, cutoffs, port_idx, port_len, upper_u, ret_past, day_past, ret_future, day_future,
+                                   n_valid)
+
+
+@list_metrics.register_fake
+def _(list_item, truth, cutoffs, upper_u, ret_past, day_past, ret_future, day_future, port_idx=None, port_len=None, n_valid=None):
+    U, n_c = list_item.shape[0], len(cutoffs)
+    return (list_item.new_empty((U,), dtype=torch.int32), list_item.new_empty((U, n_c), dtype=torch.float32),
+            list_item.new_empty((U, n_c), dtype=torch.float32), list_item.new_empty((U, 4 * n_c), dtype=torch.float64))
 
 
 @torch.library.custom_op(_LIB_NS + "::recommend_topk", mutates_args=(), device_types="cuda")

@@ -7,7 +7,7 @@ reference's outputs.  The fixtures are data only - no reference source text is
 stored.  The inline MV block of main.py (not importable: wandb/CUDA/data files)
 is executed in place from the reference tree, as SURVEY.md App. E describes.
 
-Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8 g9a g9b g10 g11]  (default: all)
+Usage:  python tools/make_golden.py [g1 g2 g3 g4 g5 g6 g7 g8 g9a g9b g10 g11 g12]  (default: all)
 g10 = the g1 / g5 recipes on ``yyyymmddHHMMSS`` timestamps (~2.02e13: one f32 step is 2**21, about two calendar days).
 Library versions used are recorded in each fixture (``versions``).
 """
@@ -771,6 +771,97 @@ def g9a():
          invest=invest, invest_ref_ranking=invest_refrank, invest_exact_hi=hi, invest_exact_lo=lo, invest_scale=scale)
 
 
+def g12():
+    """pfo_list_metrics at depths the reference's call sites never use: return_sharpe_at_k takes any k, only its callers say
+    1, 3, 5.  Lists of 20 ranked stocks, cutoffs (1, 2, 3, 5, 10, 20), portfolios of 0..7 stocks (some with a stock twice, some
+    lists naming a held stock), n_ret = 29, 4 days; expected values from the reference's return_sharpe_at_k and baseline lines
+    (g9a's pattern) and its recall_at_k / ndcg_at_k, plus the restatement of tests/list_metrics_ref.py in extended precision."""
+    import evaluation as ev
+    from pfotgnrec_amd.mv_sampler import log_returns
+    F = _finance_ref()
+    import list_metrics_ref as LR
+    block = _baseline_block()
+    rs = np.random.RandomState(1212)
+    B, L, U, I, n_days, W = 100, 20, 50, 40, 4, 7
+    cuts = (1, 2, 3, 5, 10, 20)
+    n_c = len(cuts)
+    codes = ["%06d" % (i + 1) for i in range(I)]
+    map_item_id = {c: i for i, c in enumerate(codes)}
+    days = ["2020010%d" % (d + 1) for d in range(n_days)]
+    past = 100.0 * np.exp(np.cumsum(rs.randn(n_days, I, 30) * 0.02, axis=2))
+    future = 100.0 * np.exp(np.cumsum(rs.randn(n_days, I, 30) * 0.02 + 0.001, axis=2))
+    tf_past = {d: {c: past[k, j] for j, c in enumerate(codes)} for k, d in enumerate(days)}
+    tf_future = {d: {c: future[k, j] for j, c in enumerate(codes)} for k, d in enumerate(days)}
+    ret_past, ret_future = log_returns(past), log_returns(future)
+    day_idx = rs.randint(0, n_days, B)
+    ts = np.array([float(days[d]) * 1e6 + rs.randint(0, 235959) for d in day_idx])
+    assert all(str(t)[:8] == days[d] for t, d in zip(ts, day_idx))
+    stocks = np.stack([rs.choice(I, L, replace=False) for _ in range(B)])              # the ranked lists, best first
+    list_item = (U + 1 + stocks).astype(np.int64)
+    portfolios, truth = [], np.zeros(B, np.int64)
+    for b in range(B):
+        k = b % 10
+        rest = np.setdiff1d(np.arange(I), stocks[b])
+        if k == 0:
+            pf = [""]
+        elif k == 1:
+            pf = [codes[stocks[b, 0]]]                       # the first pick is the whole portfolio: delta@1 = 0 exactly
+        elif k == 2:
+            j = rs.choice(rest, 2, replace=False)
+            pf = [codes[j[0]], codes[j[1]], codes[j[0]]]     # one stock held twice
+        elif k == 3:
+            pf = [codes[j] for j in rs.choice(I, W, replace=False)]                    # the packed width
+        elif k == 4:
+            pf = [codes[j] for j in rs.choice(rest, 3, replace=False)] + [codes[stocks[b, rs.randint(1, L)]]]   # a held stock in the list
+        elif k == 5:
+            j = stocks[b, rs.randint(0, 5)]
+            pf = [codes[j], codes[j], codes[rs.choice(rest)]]                          # ... held twice and recommended again
+        else:
+            pf = [codes[j] for j in rs.choice(I, rs.randint(1, W), replace=False)]
+        portfolios.append(pf)
+        m = (b // 10) % 5                                    # the item taken: first, inside, last, not in the list, none
+        truth[b] = (list_item[b, 0], list_item[b, rs.randint(1, L - 1)], list_item[b, L - 1], U + 1 + rs.choice(rest), -1)[m]
+    width = max(len(p) for p in portfolios)
+    port_codes = np.full((B, width), "", dtype="U6")
+    port_n = np.array([len(p) for p in portfolios])
+    port_idx = np.full((B, width), -1, np.int32)
+    port_len = np.zeros(B, np.int32)
+    for b, p in enumerate(portfolios):
+        port_codes[b, :len(p)] = p
+        if "" not in p:
+            port_idx[b, :len(p)] = [map_item_id[c] for c in p]
+            port_len[b] = len(p)
+    invest = np.zeros((B, 4 * n_c))
+    recall, ndcg = np.zeros((B, n_c)), np.zeros((B, n_c))
+    for b in range(B):
+        key = str(ts[b])[:8]
+        items = np.array([codes[i] for i in stocks[b]])
+        ns = dict(np=np, portfolio=portfolios[b], ts=key, time_feature_past=tf_past, time_feature_future=tf_future, period=30)
+        exec(block, ns)
+        for t, (pf, r, s, tf) in enumerate(((ns["port_feature"], ns["return_"], ns["sharpe"], tf_past),
+                                            (ns["port_feature_"], ns["return__"], ns["sharpe_"], tf_future))):
+            for i, c in enumerate(cuts):
+                dr, ds = ev.return_sharpe_at_k(key, pf, r, s, tf, items, c)
+                invest[b, t * 2 * n_c + i], invest[b, t * 2 * n_c + n_c + i] = dr, ds
+        if truth[b] >= 0:
+            for i, c in enumerate(cuts):
+                recall[b, i] = ev.recall_at_k(list(list_item[b]), [truth[b]], c)
+                ndcg[b, i] = ev.ndcg_at_k(list(list_item[b]), [truth[b]], c)
+    args = (list_item, None, truth, cuts, port_idx, port_len, U, ret_past, day_idx, ret_future, day_idx)
+    rank, hits, nd, x, scale = LR.list_metrics(*args, dtype=np.longdouble, parts=True)
+    hi = x.astype(np.float64)
+    lo = (x - hi).astype(np.float64)
+    scale = scale.astype(np.float64)
+    e_ref = _check_signs(F, invest, hi, lo, scale)
+    assert np.array_equal(hits.astype(np.float64), recall) and np.allclose(nd, ndcg, rtol=0, atol=1e-6)
+    assert np.all(invest[np.arange(B) % 10 == 1][:, [0, n_c, 2 * n_c, 3 * n_c]] == 0)
+    print("g12: max e_ref %.3g over %d values" % (e_ref.max(), invest.size))
+    save("g12_list_metrics", list_item=list_item, truth=truth, cutoffs=np.array(cuts), ts=ts, day_idx=day_idx, days=np.array(days),
+         codes=np.array(codes), upper_u=np.array(U), prices_past=past,
+         prices_future=future, port_codes=port_codes, port_n=port_n, port_idx=port_idx, port_len=port_len, rank=rank, recall=recall,
+         ndcg=ndcg, invest=invest, invest_exact_hi=hi, invest_exact_lo=lo, invest_scale=scale, e_ref_max=np.array(e_ref.max()))
+
+
 def _g9b_try(seed, L):
     import contextlib, io, pickle, tempfile
     import evaluation as ev
@@ -1104,6 +1195,6 @@ def g10():
 if __name__ == "__main__":
     import warnings
     warnings.filterwarnings("ignore")
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9a", "g9b", "g10", "g11"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8", "g9a", "g9b", "g10", "g11", "g12"]
     for w in which:
         globals()[w]()
