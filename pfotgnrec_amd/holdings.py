@@ -6,6 +6,8 @@ import collections
 import numpy as np
 import torch
 
+from .tables import RowStore
+
 MAX_WIDTH = 256
 
 # a validated write: host arrays (src any integer dtype, idx i32[N, Wp], len i32[N], ts f64[N]) or the same as device tensors
@@ -18,64 +20,40 @@ class Holdings:
     (-1, 0, -inf).  The item node of stock ``s`` is ``s + upper_u + 1``."""
 
     def __init__(self, n_nodes, capacity, width, upper_u, device):
-        self.width, self.upper_u, self.n_nodes = int(width), int(upper_u), int(n_nodes)
-        self._point(self._fresh(max(int(capacity), self.n_nodes), torch.device(device)))
+        self.width, self.upper_u = int(width), int(upper_u)
+        specs = [((self.width,), torch.int32, -1), ((), torch.int32, 0), ((), torch.float64, float("-inf"))]
+        self._store = RowStore.allocate(specs, capacity, n_nodes, torch.device(device))
+        self._scratch()
 
-    def _fresh(self, rows, device):
-        return [torch.full((rows, self.width), -1, dtype=torch.int32, device=device),
-                torch.zeros(rows, dtype=torch.int32, device=device),
-                torch.full((rows,), float("-inf"), dtype=torch.float64, device=device)]
+    def _scratch(self):
+        # scratch of the two native calls, kept between them and re-made with the storage: the store's stamp table, the
+        # gather's node id -> position table (neither needs an initial value: include/pfotgn.h)
+        self._stamp, self._pos = (torch.empty(self.capacity, dtype=torch.int32, device=self.device) for _ in range(2))
 
-    def _point(self, stores):
-        self._stores = list(stores)
-        rows, dev = int(stores[0].shape[0]), stores[0].device
-        # scratch of the two native calls, kept between them: the store's stamp table, the gather's node id -> position table
-        # (neither needs an initial value: include/pfotgn.h)
-        self._stamp = torch.empty(rows, dtype=torch.int32, device=dev)
-        self._pos = torch.empty(rows, dtype=torch.int32, device=dev)
-
-    @property
-    def capacity(self):
-        return int(self._stores[0].shape[0])
-
-    @property
-    def device(self):
-        return self._stores[0].device
-
-    @property
-    def idx(self):
-        return self._stores[0][:self.n_nodes]
-
-    @property
-    def len(self):
-        return self._stores[1][:self.n_nodes]
-
-    @property
-    def time(self):
-        return self._stores[2][:self.n_nodes]
+    n_nodes = property(lambda self: self._store.rows)
+    capacity = property(lambda self: self._store.capacity)
+    device = property(lambda self: self._store.storage[0].device)
+    idx = property(lambda self: self._store.views()[0])
+    len = property(lambda self: self._store.views()[1])
+    time = property(lambda self: self._store.views()[2])
 
     def resize(self, n_nodes, capacity=None):
         """``n_nodes`` live rows (never fewer than now) in storage of ``capacity`` rows (None: what is there, or just enough):
         live rows keep every bit, new rows hold the initial values."""
-        n_nodes = int(n_nodes)
-        if n_nodes < self.n_nodes:
-            raise ValueError("the holdings ledger does not shrink (%d rows live, %d asked for)" % (self.n_nodes, n_nodes))
-        want = max(self.capacity if capacity is None else int(capacity), n_nodes)
-        if want != self.capacity:
-            grown = self._fresh(want, self.device)
-            for g, t in zip(grown, self._stores):
-                g[:self.n_nodes].copy_(t[:self.n_nodes])
-            self._point(grown)
-        self.n_nodes = n_nodes
+        if int(n_nodes) < self.n_nodes:
+            raise ValueError("the holdings ledger does not shrink (%d rows live, %d asked for)" % (self.n_nodes, int(n_nodes)))
+        if self._store.resize(n_nodes, capacity):
+            self._scratch()
 
     def move(self, device):
         """A device move (``TGN._apply``): the storage travels as a whole, every bit kept (a cast of the model's floating
         tensors does not reach the fp64 times)."""
-        self._point([t.to(device).contiguous() for t in self._stores])
+        self._store.move(lambda t: t.to(device))
+        self._scratch()
 
     def store(self, src, port_idx, port_len, ts):
         from .functional import holdings_store
-        holdings_store(src, port_idx, port_len, ts, self.idx, self.len, self.time, self._stamp)
+        holdings_store(src, port_idx, port_len, ts, *self._store.views(), self._stamp)
 
     def gather(self, users, items=None):
         """(port_idx i32[U, width], port_len i32[U], excl_pos i32[U, width] or None without ``items``) for device ``users``."""

@@ -14,6 +14,8 @@ from collections import defaultdict
 import torch
 from torch import nn
 
+from .tables import RowStore
+
 
 class Memory(nn.Module):
     def __init__(self, n_nodes, memory_dimension, input_dimension, message_dimension=None, device="cpu",
@@ -37,47 +39,36 @@ class Memory(nn.Module):
         # counts the rewrites of the tables from outside the training step (a batch prepared ahead of time holds packed copies
         # of memory rows: TGN.prefetch stamps them with this number)
         self._state_version = 0
-        # capacity storage of the five tables (``resize``): the attributes above are its leading ``n_nodes`` rows; rows behind
-        # them are zero at all times (nothing addresses them), so a node that arrives later starts from the initial state
-        self._storage = None
+        # capacity storage of the five tables (tables.RowStore, fill 0): the attributes above are its live rows; a node that
+        # arrives later starts from the initial state
+        self._store = RowStore([self.memory.data, self.last_update.data, self.msg_table, self.msg_time, self.has_msg])
 
     # ------------------------------------------------------------------ tables with capacity (TGN.reserve / TGN.add_nodes)
-    def _stores(self):
-        if self._storage is None:
-            self._storage = [self.memory.data, self.last_update.data, self.msg_table, self.msg_time, self.has_msg]
-        return self._storage
+    capacity = property(lambda self: self._store.capacity, doc="Rows the tables hold before they are reallocated (>= ``n_nodes``).")
 
-    @property
-    def capacity(self):
-        """Rows the tables can hold before they are reallocated (>= ``n_nodes``)."""
-        return int(self._stores()[0].shape[0])
-
-    def _point(self, stores, n_nodes):
-        """The attributes become the leading ``n_nodes`` rows of ``stores`` (contiguous views, same dtypes); the two
-        parameters are re-pointed through ``.data`` like a device move does."""
-        self._storage = list(stores)
+    def _point(self):
+        """The attributes become the store's live rows; the two parameters are re-pointed through ``.data`` like a device
+        move does."""
+        views = self._store.views()
         with torch.no_grad():
-            self.memory.data = stores[0][:n_nodes]
-            self.last_update.data = stores[1][:n_nodes]
-        self.msg_table, self.msg_time, self.has_msg = stores[2][:n_nodes], stores[3][:n_nodes], stores[4][:n_nodes]
-        self.n_nodes = int(n_nodes)
+            self.memory.data, self.last_update.data = views[:2]
+        self.msg_table, self.msg_time, self.has_msg = views[2:]
+        self.n_nodes = self._store.rows
 
     def resize(self, n_nodes, capacity=None):
         """``n_nodes`` live rows (never fewer than now) in storage of ``capacity`` rows (None: what is there, or just enough).
         Live rows keep every bit, new rows are zero: no memory, last update 0, no pending message."""
-        n_nodes, cap = int(n_nodes), self.capacity
-        if n_nodes < self.n_nodes:
-            raise ValueError("the memory tables do not shrink (%d rows live, %d asked for)" % (self.n_nodes, n_nodes))
-        want = max(cap if capacity is None else int(capacity), n_nodes)
-        stores = self._stores()
-        if want != cap:
-            live = self.n_nodes
-            grown = [torch.zeros((want,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in stores]
-            for g, t in zip(grown, stores):
-                g[:live].copy_(t[:live])
-            stores = grown
-        self._point(stores, n_nodes)
+        if int(n_nodes) < self.n_nodes:
+            raise ValueError("the memory tables do not shrink (%d rows live, %d asked for)" % (self.n_nodes, int(n_nodes)))
+        self._store.resize(n_nodes, capacity)
+        self._point()
         self._state_version += 1
+
+    def move(self, fn, device):
+        """A device move or cast (``TGN._apply``): ``fn`` reaches the four float tables, the u8 flags only change device."""
+        self._store.move(fn, fn, fn, fn, lambda t: t.to(device))
+        self._point()
+        self.device = device
 
     def __init_memory__(self):
         """Zero the memory and drop every pending message (modules/memory.py:23-33); called per epoch (main.py:153).
@@ -85,11 +76,8 @@ class Memory(nn.Module):
         In place, so that device pointers held by the native state stay valid.
         """
         with torch.no_grad():
-            self.memory.zero_()
-            self.last_update.zero_()
-            self.msg_table.zero_()
-            self.msg_time.zero_()
-            self.has_msg.zero_()
+            for table in self._store.views():
+                table.zero_()
         self._any_msg = False
         self._state_version += 1
 
@@ -117,8 +105,7 @@ class Memory(nn.Module):
         if k > self.n_nodes or any(int(a.shape[0]) != k for a in (memory_backup[1], tab, t, has)):
             raise ValueError("the backup holds %d rows, the memory %d: only a backup of this or an earlier size restores" % (k, self.n_nodes))
         with torch.no_grad():
-            for dst, src in ((self.memory, memory_backup[0]), (self.last_update, memory_backup[1]), (self.msg_table, tab),
-                             (self.msg_time, t), (self.has_msg, has)):
+            for dst, src in zip(self._store.views(), (memory_backup[0], memory_backup[1], tab, t, has)):
                 dst[:k].copy_(src)
                 if k < self.n_nodes:
                     dst[k:].zero_()

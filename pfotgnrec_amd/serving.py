@@ -1,0 +1,488 @@
+"""The serving surface of the model: everything a served ``TGN`` does between training steps - ``recommend`` (read-only),
+``observe`` / ``ingest`` (state advance), the tables that grow (``reserve``, ``add_nodes``, ``add_edge_features``), the holdings
+ledger and the retention window (``expire``).  A plain mixin that ``TGN`` inherits ahead of ``nn.Module``: the training step
+calls nothing in here."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def _check_log(batch_size, **columns):
+    """The argument check ``observe`` and ``ingest`` open with, over ``name=(array, device dtype or None)`` columns of one log
+    -> ``(on_dev, N, arrays)``.  The first column says whether the log is on the host or on the device; all columns have its
+    length; ``batch_size`` is None or at least 1; on the device every column with a dtype is a 1-d tensor of it.  Host columns
+    come back as numpy arrays, device columns as they are."""
+    names, arrays = list(columns), [a for a, _ in columns.values()]
+    on_dev = torch.is_tensor(arrays[0])
+    N = int(arrays[0].shape[0]) if on_dev else len(arrays[0])
+    if any(len(a) != N for a in arrays[1:]):
+        raise ValueError("%s and %s must have the same length" % (", ".join(names[:-1]), names[-1]))
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("batch_size must be at least 1")
+    typed = [(a, dt) for a, dt in columns.values() if on_dev and dt is not None]
+    if any((not torch.is_tensor(a)) or a.dtype != dt or a.dim() != 1 for a, dt in typed):
+        raise ValueError("device inputs must be 1-d tensors " + " / ".join(str(dt)[6:] for _, dt in typed))
+    return on_dev, N, arrays if on_dev else [np.asarray(a) for a in arrays]
+
+
+class Serving:
+    # ------------------------------------------------------------------ serving: read-only top-k
+    def _embed_readonly(self, roots, root_ts, K):
+        """Embeddings of (node, time) roots exactly as a forward would give them - pending messages applied lazily
+        (tgn.py:251), L layers over the neighbours strictly before each root's time - with NOTHING written to the model: no
+        persist, no message store, dropout 0 whatever ``train()`` says, the data-parallel sharding ignored.  The roots walk
+        through the forward-only passes in chunks of ``eval_chunk_roots``.  The host-side step counter (position of the Philox
+        streams: uniform sampling draws from it) and the "a GRU took part" flag are put back, so the next training step is the
+        one it would have been."""
+        K, root_ts = self._no_neighbours(int(K), root_ts)
+        saved = (self._step, self._gru_applied_now)
+        self._drop_prefetched()          # (a batch prepared ahead of time is simply prepared again by its own call)
+        try:
+            with torch.no_grad():
+                emb, call = self._forward_chunks(roots, root_ts, K, 0.0, max(1, self._ws_caps[2]),
+                                                 [(c0, None) for c0 in range(0, int(roots.shape[0]), max(1, int(self.eval_chunk_roots)))])
+                if call is not None:
+                    call.release()
+        finally:
+            self._step, self._gru_applied_now = saved
+        return emb
+
+    def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
+                  mv=None, portfolios=None, day_idx=None, basket=False):
+        """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
+        written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
+        is left as found), no gradient is recorded and dropout is off.
+
+        users: [U] node ids (numpy / list, or an integer tensor); timestamps: a scalar or f64 [U]; items: [I] candidate item
+        node ids, distinct and non-zero (shared by all users); exclude: None, a list of per-user lists of item NODE IDS (what
+        the user already holds), or a packed pair (ids i32[U,W] padded with -1, lens i32[U]) - ids that are not in ``items``
+        are ignored; item_ok: optional bool / u8 [I], 0 = never offer this candidate; n_neighbors: default the model's (20).
+
+        Every (item, distinct timestamp) pair is embedded once (the grid of ``TGN._dedup_roots``), users and grid go through
+        the forward-only chunk walk, and one launch of ``pfo_recommend_topk`` scores and selects.  Returns, on the device,
+        (item_ids i32[U,k], scores f32[U,k], n_valid i32[U]): score descending, among equal scores the later entry of
+        ``items`` first; slots beyond the admissible candidates hold id -1 and score -inf.  With
+        ``return_embeddings`` also (user_emb [U,D], item_emb [n_t*I,D], user_block i32[U]): the block of n_t = number of
+        distinct timestamps each user was scored against.
+
+        With ``mv`` (an ``MVSampler``, or any object with ``returns``, ``upper_u``, ``gamma``, ``lambda_mv``, ``day_of``) the
+        order is the mean-variance rank fusion the model is trained towards (main.py:243-289) over the whole candidate list:
+        ``lambda_mv * rank(y_mv) + (1 - lambda_mv) * rank(score)``, one launch of ``pfo_recommend_mv_topk``.  portfolios: the
+        stock indices each user holds, packed (port_idx i32[U,W], port_len i32[U]) on host or device, or a list of per-user
+        lists (entries outside the return table are ignored; they weigh on y_mv, ``exclude`` still decides what is offered);
+        day_idx: an int or one per user, None: ``mv.day_of(timestamps)`` (host timestamps only); a candidate's stock row is
+        ``item - upper_u - 1``.  Up to 2048 candidates that is the one launch; beyond, up to 65536, the same list comes from
+        ``pfo_recommend_mv_topk_wide``: ranks by sorting in a workspace of 36 bytes per user and candidate (256 MiB at the
+        most, the users served in slabs), two launches a slab.  Returns (item_ids, scores, n_valid, fused f64[U,k]) - fused
+        descending, -inf in empty slots - then the embeddings as above.
+
+        ``basket=True`` (needs ``mv``): the list is taken one pick at a time - pick r is ranked with the stocks of picks
+        0 .. r-1 counted as held behind the user's portfolio, so two near-identical stocks no longer both make the list; one
+        launch of ``pfo_recommend_basket_topk`` in place of ``pfo_recommend_mv_topk``, equal to k calls with ``k=1`` and each
+        pick appended to ``portfolios`` and ``exclude``.  The same return tuple; ``fused[u, r]`` is the pick's value in round r.
+        The basket has no wide form: at most 2048 candidates.
+
+        ``exclude="held"`` / ``portfolios="held"`` (either alone, or both): the rows of the holdings ledger
+        (``track_holdings``) in place of the argument - one ``pfo_holdings_gather`` over the users already on the device, no
+        lists packed or uploaded per query; ``portfolios="held"`` still needs ``mv``, whose ``upper_u`` must be the ledger's.
+
+        ``mv`` may be a ``PriceLedger`` (prices.py): its return table grows by the day on the device.  ``day_idx`` is then the
+        ordinal among the ledger's live days (0 = oldest); ``day_idx=None`` also takes DEVICE timestamps - one
+        ``pfo_day_lookup``, no read-back - and a user whose day the ledger does not hold gets an empty answer there, where host
+        timestamps raise ``KeyError``.
+
+        Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` are not (it would cost a
+        read-back).  ``items`` is read back once when it is a device tensor."""
+        from . import recommend as R
+        query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
+                           portfolios, day_idx, self.holdings, basket)
+        _lib.require_gpu(self.device)
+        return R.assemble(self, query, return_embeddings)
+
+    # ------------------------------------------------------------------ serving: write-only state advance
+    def _observe_workspace(self, B):
+        """A workspace of ``pfo_tgn_observe`` from the pool (its entries carry the capacities (0, 0, 0): no forward takes them,
+        and they go with the other undersized buffers when the step's workspace grows)."""
+        need = _lib.byte_count("pfo_tgn_observe_workspace_bytes", ctypes.byref(self._cfg), B)
+        for i, (caps, ws) in enumerate(self._ws_pool):
+            if caps == (0, 0, 0) and ws.numel() >= need:
+                return self._ws_pool.pop(i)[1]
+        return torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def observe(self, sources, destinations, edge_times, edge_idxs, batch_size=None, append=False):
+        """Takes in interactions WITHOUT embedding anything - the write-only counterpart of ``recommend``: a chronological log
+        is walked on the device in batches of ``batch_size`` and ``memory``, ``last_update`` and the pending-message tables
+        end exactly where ``compute_temporal_embeddings[_p]`` would leave them batch by batch (tgn.py:295-317: the GRU on the
+        batch's own positives that hold a message, the persist, the raw-message store) - no negatives, no sampling, no
+        attention.  One native call (``pfo_tgn_observe``), no Python work per batch.  Nothing else is written: parameters,
+        gradients, optimizer state, the step counter and the random streams stay as they are; no gradient is recorded
+        whatever ``train()`` says.  Returns the number of interactions consumed.
+
+        sources / destinations / edge_times / edge_idxs: numpy i64 / i64 / f64 / i64 like the entry points (range-checked:
+        IndexError), or device tensors i32 / i32 / f64 / i32 (not checked: it would cost a read-back).  ``edge_idxs`` must
+        address EXISTING rows of the edge-feature table: interactions whose features (or nodes) the model has never seen go
+        through ``ingest``, which grows the tables and then calls this.
+        ``batch_size``: interactions per batch, None = the whole input is one batch.  Batch boundaries are part of the
+        semantics (messages are built from the memory as of their batch's persist): replay a log with the batch size it
+        was - or would have been - trained with.  Chronological order is the caller's contract (``debug_checks`` asserts, like
+        ``embed_device``, that no pending message is older than its node's last update).
+        ``append``: the edges also go into the model's neighbour finder (``NeighborFinder.append``) behind the state update, so
+        that a later ``recommend`` sees them; a ``GraphedTrainStep`` captured over the finder goes stale - as does one captured
+        before ``reserve`` / ``add_nodes`` / ``add_edge_features`` moved or grew a table it holds the address of.  Off by default:
+        a replay over a finder that already holds the log must not duplicate its edges.
+        The data-parallel sharding is ignored (every rank observes the whole input: the state is replicated).
+        Without memory there is no state: only the optional append happens."""
+        on_dev, N, (sources, destinations, edge_times, edge_idxs) = _check_log(
+            batch_size, sources=(sources, torch.int32), destinations=(destinations, torch.int32),
+            edge_times=(edge_times, torch.float64), edge_idxs=(edge_idxs, torch.int32))
+        if not on_dev:
+            sources, destinations = self._check_nodes(sources, "sources"), self._check_nodes(destinations, "destinations")
+            edge_idxs = self._check_edges(edge_idxs)
+        if self.use_memory and N > 0:
+            _lib.require_gpu(self.device)
+            with torch.no_grad():
+                self.join()                   # a side-stream optimizer step / a backward beside the host loop may still be running
+                self._drop_prefetched()       # (its packed memory / message rows would be stale)
+                if on_dev:
+                    src, dst, ts, eidx = (a.contiguous() for a in (sources, destinations, edge_times, edge_idxs))
+                else:
+                    ts, src, dst, eidx = self._batch_to_dev([(edge_times, np.float64), (sources, np.int32), (destinations, np.int32),
+                                                             (edge_idxs, np.int32)])
+                if self.debug_checks:
+                    m = self.memory
+                    late = (m.has_msg > 0) & (m.last_update > m.msg_time)
+                    assert not bool(late.any()), "Trying to update memory to time in the past"      # memory_updater.py:25,41
+                B = N if batch_size is None else min(int(batch_size), N)
+                ws = self._observe_workspace(B)
+                st = self._state_struct(adjacency=False)
+                try:
+                    _lib.call("pfo_tgn_observe", ctypes.byref(self._cfg), ctypes.byref(st), src.data_ptr(), dst.data_ptr(),
+                              ts.data_ptr(), eidx.data_ptr(), N, B, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
+                finally:
+                    self._ws_pool.append(((0, 0, 0), ws))
+                self.memory._any_msg = True
+                self.memory._state_version += 1
+        if append and N > 0:
+            host = (lambda a: a.cpu().numpy()) if on_dev else np.asarray
+            self.neighbor_finder.append(host(sources), host(destinations), host(edge_idxs), host(edge_times))
+        return N
+
+    # ------------------------------------------------------------------ serving: tables that grow
+    @property
+    def edge_feature_stats(self):
+        """``(mean f32[Ef], std f32[Ef])`` on the host: the column statistics the constructor normalised the edge-feature
+        table with - the mean of the table, the standard deviation of the centred table, both fp32 as numpy computed them.
+        FROZEN: rows added later (``add_edge_features``) are scaled with these and never with recomputed ones - the weights
+        were trained against this scaling.  They are NOT part of ``state_dict()`` (existing checkpoints keep loading): a model
+        restored next to a table that has grown since takes them from ``set_edge_feature_stats``."""
+        return self._edge_stats
+
+    def _set_stats(self, mean, std):
+        mean = np.ascontiguousarray(np.asarray(mean), dtype=np.float32).reshape(-1)
+        std = np.ascontiguousarray(np.asarray(std), dtype=np.float32).reshape(-1)
+        self._edge_stats = (mean, std)
+        self._edge_stats_dev = torch.from_numpy(np.stack([mean, std])).to(self.device).contiguous()     # [2, Ef]: mean | std
+
+    def set_edge_feature_stats(self, mean, std):
+        """Replaces the frozen statistics (``edge_feature_stats``), e.g. with those saved beside a checkpoint.  The table is
+        NOT re-normalised: only rows added from now on are scaled with the new vectors."""
+        mean, std = np.asarray(mean), np.asarray(std)
+        if mean.shape != (self.n_edge_features,) or std.shape != (self.n_edge_features,):
+            raise ValueError("mean and std must have shape (%d,)" % self.n_edge_features)
+        self._set_stats(mean, std)
+
+    node_capacity = property(lambda self: self._nodes.capacity)
+    edge_capacity = property(lambda self: self._edges.capacity)
+
+    def _quiesce(self):
+        # a side-stream optimizer step / a backward beside the host loop may still read the tables that are about to move
+        if self._flat.is_cuda:
+            self.join()
+            self._drop_prefetched()
+
+    def reserve(self, n_nodes=None, n_edges=None):
+        """Capacity for ``n_nodes`` rows of the node tables (``node_raw_features``, ``memory.memory``, ``memory.last_update``,
+        the pending-message table, its times and flags) and ``n_edges`` rows of the edge-feature table - rows, the padding
+        row 0 included.  Live rows are copied across bit for bit, rows behind them are zero; the attributes stay what they
+        were - contiguous leading-row views of the storage, same dtypes and shapes - but their addresses change when storage
+        is reallocated.  Capacity never shrinks (asking for what is there, or less, does nothing); asking for less than the
+        live rows raises ``ValueError``.  Without ``reserve`` the tables grow geometrically on demand.  Call it between steps
+        (see ``add_nodes``); a ``GraphedTrainStep`` captured before goes stale."""
+        for what, want, store in (("n_nodes", n_nodes, self._nodes), ("n_edges", n_edges, self._edges)):
+            if want is not None and int(want) < store.rows:
+                raise ValueError("reserve(%s=%d) is below the %d live rows" % (what, int(want), store.rows))
+        # (the memory tables and the ledger follow the node capacity)
+        for want, store, followers in ((n_edges, self._edges, ()), (n_nodes, self._nodes, (self.memory, self.holdings))):
+            if want is not None and int(want) > store.capacity:
+                self._quiesce()
+                store.reserve(want)
+                for tables in followers:
+                    if tables is not None:
+                        tables.resize(store.rows, want)
+                self._tables_changed(rows=False)
+        return self
+
+    def add_edge_features(self, raw):
+        """Appends ``raw`` f32[m, Ef] RAW edge-feature rows - a host array (checked: width, finite values; staged through the
+        batch ring) or an fp32 device tensor (shape checked only) - behind the live rows, normalised with the frozen
+        ``edge_feature_stats`` by ONE launch of ``pfo_edge_rows_append`` (numpy's two fp32 operations, bit for bit).  Returns
+        the new rows' edge indices, i64[m]: the old row count onwards.  Nothing else changes; live rows keep every bit (they
+        move only when the capacity is exceeded: ``reserve``)."""
+        Ef = self.n_edge_features
+        if torch.is_tensor(raw):
+            if raw.dim() != 2 or raw.shape[1] != Ef or raw.dtype != torch.float32:
+                raise ValueError("device edge features must be an fp32 tensor [m, %d]" % Ef)
+            dev_rows = raw
+        else:
+            raw = np.asarray(raw)
+            if raw.ndim != 2 or raw.shape[1] != Ef:
+                raise ValueError("edge features must have shape [m, %d], got %s" % (Ef, raw.shape))
+            raw = raw.astype(np.float32, copy=False)
+            if not np.isfinite(raw).all():
+                raise ValueError("edge features must be finite")
+            dev_rows = None
+        m, n0 = int(raw.shape[0]), int(self.edge_raw_features.shape[0])
+        if n0 + m >= 2 ** 31:
+            raise ValueError("edge indices must fit in int32")
+        if m == 0:
+            return np.zeros(0, np.int64)
+        _lib.require_gpu(self.device)
+        if dev_rows is None:
+            dev_rows = self._batch_to_dev([(raw, np.float32)])[0]
+        dev_rows = dev_rows.contiguous()
+        if n0 + m > self.edge_capacity:           # (every tick comes through here: no call when the rows fit)
+            self.reserve(n_edges=self._edges.capacity_for(n0 + m))
+        st = self._edge_stats_dev
+        _lib.call("pfo_edge_rows_append", dev_rows.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), m, Ef, self.edge_raw_features.data_ptr(),
+                  n0, self.edge_capacity, _lib.stream_ptr())
+        self._edges.set_rows(n0 + m)
+        self._point_edges()
+        return np.arange(n0, n0 + m, dtype=np.int64)
+
+    def add_nodes(self, n, node_features=None):
+        """``n`` new nodes behind the last one; returns the first new node id (= the old ``n_nodes``).  Their rows of
+        ``node_raw_features`` are ``node_features`` f32[n, D] or zeros (the reference's node features are all zeros,
+        main.py:87); their memory, last update and pending-message state are the initial ones (zero, none pending).
+        Parameters, their ``.grad`` views, the flat buffers, the optimizer state, the step counter and the parameter cache
+        (its size does not depend on the node count) are untouched.  Invalidated: the workspace pool (workspaces are carved
+        per node count), the padded device adjacency, a batch prepared ahead of time, the ``debug_*`` views of the last
+        forward, and any ``GraphedTrainStep`` captured before.
+
+        Call it BETWEEN steps: a forward whose backward is still pending keeps the workspace and config it ran with, and must
+        have its backward run first."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must not be negative")
+        D = self.n_node_features
+        rows = None
+        if node_features is not None:
+            rows = node_features if torch.is_tensor(node_features) else torch.from_numpy(
+                np.ascontiguousarray(np.asarray(node_features), dtype=np.float32))
+            if rows.dim() != 2 or tuple(rows.shape) != (n, D):
+                raise ValueError("node_features must have shape [%d, %d], got %s" % (n, D, tuple(rows.shape)))
+        first = self.n_nodes
+        if n == 0:
+            return first
+        if first + n >= 2 ** 31:
+            raise ValueError("node ids must fit in int32")
+        self._quiesce()
+        self.reserve(n_nodes=self._nodes.capacity_for(first + n))
+        self._nodes.set_rows(first + n)
+        for tables in (self.memory, self.holdings):               # (rows behind the live ones hold the initial values already;
+            if tables is not None:                                #  the memory bumps its _state_version)
+                tables.resize(first + n)
+        self._tables_changed(node_count=True)
+        if rows is not None:                                      # (the new rows were zero)
+            self.node_raw_features[first:].copy_(rows.to(dtype=torch.float32))
+        return first
+
+    def ingest(self, sources, destinations, edge_times, edge_features, batch_size=None, node_features=None, portfolios=None):
+        """The serving tick: takes in interactions the model has NEVER seen - their feature rows are not in the edge-feature
+        table, their nodes may not exist yet - so that the next ``recommend`` accounts for them.  A thin chain of
+        ``add_nodes`` (when the input names new nodes), ``add_edge_features`` and ``observe(..., append=True)``: the state
+        semantics are ``observe``'s by shared code (batch boundaries included: ``batch_size``), every rank of a data-parallel
+        group ingests the whole input, and nothing else is written.  Per tick: one launch for the feature rows, ONE
+        ``pfo_tgn_observe`` call (4 launches per batch) and the CSR append; no Python work per batch.  Without memory only the
+        tables and the finder grow.  Returns ``(n_consumed, edge_idxs i64[N])`` - the indices the new rows got.
+
+        sources / destinations / edge_times: numpy i64 / i64 / f64 like ``observe``; edge_features: RAW rows f32[N, Ef]
+        (normalised here with the frozen ``edge_feature_stats``).  Node ids >= ``n_nodes`` are allowed only as exactly the
+        next consecutive ids; those nodes are added first, with ``node_features`` f32[n_new, D] as their rows in ascending id
+        order, zeros otherwise.  Host inputs are validated BEFORE anything is written (``ValueError``: lengths, feature width,
+        non-finite features, decreasing ``edge_times``, node ids < 1, ids that skip ahead, ``batch_size`` < 1): a rejected call
+        leaves the model bit for bit as it was.  Device tensors (i32 / i32 / f64 and f32[N, Ef]) are checked for shape and
+        dtype only and must name existing nodes (``add_nodes`` first).
+
+        ``portfolios``: what each record says its user holds at that moment, in a form ``update_holdings`` takes (host forms
+        with host inputs, the device pair with device inputs); needs a ledger (``track_holdings``).  Its checks join the ones
+        above - a rejected call leaves the ledger too - and the ledger is written ONCE per call behind ``add_nodes`` (last
+        record per user over the whole input: batch boundaries do not matter to it).  None: the ledger is not touched."""
+        if portfolios is not None and self.holdings is None:
+            raise ValueError("portfolios need a holdings ledger: call track_holdings(width, upper_u) first")
+        on_dev, N, (sources, destinations, edge_times, edge_features) = _check_log(
+            batch_size, sources=(sources, torch.int32), destinations=(destinations, torch.int32),
+            edge_times=(edge_times, torch.float64), edge_features=(edge_features, None))
+        Ef, n_new = self.n_edge_features, 0
+        if on_dev:
+            if not torch.is_tensor(edge_features) or edge_features.dim() != 2 or edge_features.shape[1] != Ef or edge_features.dtype != torch.float32:
+                raise ValueError("device edge features must be an fp32 tensor [N, %d]" % Ef)
+            if node_features is not None:
+                raise ValueError("device inputs must name existing nodes: add_nodes first")
+        else:
+            edge_times = np.asarray(edge_times, np.float64)
+            if sources.ndim != 1 or destinations.ndim != 1 or edge_times.ndim != 1:
+                raise ValueError("sources, destinations and edge_times must be 1-d")
+            if edge_features.ndim != 2 or edge_features.shape[1] != Ef:
+                raise ValueError("edge features must have shape [N, %d], got %s" % (Ef, edge_features.shape))
+            if not np.isfinite(edge_features).all():
+                raise ValueError("edge features must be finite")
+            if N and (not np.isfinite(edge_times).all() or (np.diff(edge_times) < 0).any()):
+                raise ValueError("edge_times must be finite and chronological (non-decreasing)")
+            ids = np.concatenate([sources, destinations]).astype(np.int64)
+            if N and int(ids.min()) < 1:
+                raise ValueError("node ids must be >= 1 (node 0 is the padding node)")
+            fresh = np.unique(ids[ids >= self.n_nodes])
+            n_new = int(fresh.shape[0])
+            if n_new and not np.array_equal(fresh, np.arange(self.n_nodes, self.n_nodes + n_new)):
+                raise ValueError("new node ids must be exactly the next consecutive ids %d.. : got %s"
+                                 % (self.n_nodes, fresh[:8].tolist()))
+            if node_features is not None and tuple(np.shape(node_features)) != (n_new, self.n_node_features):
+                raise ValueError("node_features must have shape [%d, %d]: one row per new node" % (n_new, self.n_node_features))
+        held = None
+        if portfolios is not None:                # (the new nodes are rows of the ledger by the time it is written)
+            from . import holdings as H
+            held = H.validate(self.holdings.width, self.n_nodes + n_new, sources, portfolios, edge_times)
+        if N == 0:
+            return 0, np.zeros(0, np.int64)
+        _lib.require_gpu(self.device)             # (nothing below has a host path: refuse before the first table grows)
+        if n_new:
+            self.add_nodes(n_new, node_features)
+        if held is not None:
+            self._write_holdings(held)
+        new_idxs = self.add_edge_features(edge_features)
+        eidx = torch.arange(int(new_idxs[0]), int(new_idxs[0]) + N, dtype=torch.int32, device=self.device) if on_dev else new_idxs
+        return self.observe(sources, destinations, edge_times, eidx, batch_size, append=True), new_idxs
+
+    # ------------------------------------------------------------------ serving: the holdings ledger
+    def track_holdings(self, width, upper_u):
+        """Creates the holdings ledger (``self.holdings``, None before): per node row the portfolio its user's newest
+        interaction record carried - ``idx`` i32[n_nodes, width] STOCK indices padded with -1 (the packed form of
+        ``pack_portfolios``; the item node of stock ``s`` is ``s + upper_u + 1``), ``len`` i32[n_nodes], ``time`` f64[n_nodes]
+        (-1 / 0 / -inf until written) - in capacity storage that follows ``node_capacity`` (``reserve`` / ``add_nodes`` keep
+        live rows bit for bit) and the model's device.  ``update_holdings`` and ``ingest(portfolios=)`` write it,
+        ``recommend(exclude="held", portfolios="held")`` and ``holdings.rows(users)`` read it; the training step, ``observe``
+        and ``expire`` do not touch it, and it is not part of ``state_dict()``: persist ``holdings.idx / len / time`` and load
+        them with ``update_holdings``.  Once: a second call with other arguments raises ``ValueError``.  Returns the ledger."""
+        from . import holdings as H
+        try:
+            width, upper_u = int(width), int(upper_u)
+        except (TypeError, ValueError):
+            raise ValueError("width and upper_u must be integers") from None
+        if not 1 <= width <= H.MAX_WIDTH:
+            raise ValueError("width must lie in [1, %d] (got %d)" % (H.MAX_WIDTH, width))
+        if not 0 <= upper_u < 2 ** 31 - 1:
+            raise ValueError("upper_u must be a non-negative int32 (got %d)" % upper_u)
+        if self.holdings is not None:
+            if (self.holdings.width, self.holdings.upper_u) != (width, upper_u):
+                raise ValueError("the model already tracks holdings with width %d, upper_u %d"
+                                 % (self.holdings.width, self.holdings.upper_u))
+            return self.holdings
+        self.holdings = H.Holdings(self.n_nodes, self.node_capacity, width, upper_u, self.device)
+        return self.holdings
+
+    def update_holdings(self, sources, portfolios, edge_times):
+        """The one writer of the ledger: for every event in input order, ``holdings[sources[e]] = (portfolios[e], edge_times[e])``
+        - per user the LAST event of the call wins, an empty portfolio overwrites, entries are stored verbatim, nothing is
+        compared with the stored time (chronological input is the caller's contract, as for ``observe``); node 0 is skipped.
+        One native call (``pfo_holdings_store``: a memset and two launches).  Seeds a served model from the training log and
+        loads a saved ledger (``sources = arange(n_nodes)``, ``portfolios = (idx, len)``, ``edge_times = time``).
+
+        ``portfolios``: a packed pair (idx [N, Wp], len [N]) as numpy, one list of integer stock indices per event, or the pair
+        as i32 device tensors next to i32 / f64 device ``sources`` / ``edge_times``.  Host inputs are validated before anything
+        is written (``ValueError``: lengths, integer dtypes, values beyond int32, len outside [0, Wp], a row longer than the
+        ledger's width, node ids outside [0, n_nodes)) and staged in one copy; device inputs are checked for shape and dtype
+        only - the kernel skips ids outside [1, n_nodes) and clamps lengths to the row.  Returns the number of events."""
+        if self.holdings is None:
+            raise ValueError("no holdings ledger: call track_holdings(width, upper_u) first")
+        from . import holdings as H
+        w = H.validate(self.holdings.width, self.n_nodes, sources, portfolios, edge_times)
+        if w.N:
+            _lib.require_gpu(self.device)
+            self._write_holdings(w)
+        return w.N
+
+    def _write_holdings(self, w):
+        with torch.no_grad():
+            if w.on_dev:
+                src, idx, length, ts = w.src, w.idx, w.len, w.ts
+            else:
+                ts, src, idx, length = self._batch_to_dev([(w.ts, np.float64), (w.src, np.int32), (w.idx, np.int32), (w.len, np.int32)])
+            self.holdings.store(src, idx, length, ts)
+
+    # ------------------------------------------------------------------ serving: the retention window
+    def expire(self, cutoff, compact_edges=True, finders=None):
+        """"Keep the last N days": every adjacency entry with ``ts < cutoff`` (strict, fp64) leaves the neighbour finder
+        (``NeighborFinder.expire``) and, with ``compact_edges``, the rows of the edge-feature table that only expired entries
+        named are released.  Returns ``(n_entries_dropped, remap)``: the entries dropped over all finders taking part, and the
+        DEVICE tensor ``remap`` i32[old row count] - old edge index -> new one, ``remap[0] == 0``, -1 for a released row - or
+        ``None`` when ``compact_edges=False`` or no row was released (edge indices then mean what they meant).
+
+        The table is shared between finders (a train finder and a full finder over one table): ``finders`` names the OTHER
+        ``NeighborFinder``s over this model's table; the model's own finder always takes part.  All are expired with the same
+        cutoff and remapped with the same map.  A row ``r >= 1`` is released iff some expired entry of a finder taking part
+        names it and no surviving entry of any of them does; rows nobody names stay, row 0 always stays.  A finder over this
+        table that is NOT passed keeps its old edge indices and is wrong afterwards.  Surviving rows keep their order and are
+        renumbered densely; they move down inside the unchanged storage through a temporary (``pfo_edge_rows_compact``), the
+        rows behind the new live count are zero again, capacity never shrinks, and the next ``add_edge_features`` / ``ingest``
+        continues from the new row count.
+
+        Order: ``_quiesce()``, the finders, then the table.  Node memory, ``last_update``, the pending messages (they hold the
+        feature VALUES, not edge indices), parameters, gradients, optimizer state, the step counter and the random streams are
+        not touched.  Invalidated after a compaction: the padded device adjacency, the ``debug_*`` views of the last forward,
+        a batch prepared ahead of time and any ``GraphedTrainStep`` captured before (an expiry alone already stales the
+        latter through the finder's version).  Two read-backs (the surviving entry total per finder, the new row count): a
+        maintenance call, not a step.
+
+        Call it BETWEEN steps, like ``add_nodes``: a forward whose backward is still pending must have that backward run
+        first.  On a data-parallel group EVERY rank calls it with the same cutoff: state is replicated, there is no
+        collective.  ``cutoff`` must be finite (``ValueError`` before anything is written); without a device it raises like
+        every compute method."""
+        cutoff = float(cutoff)
+        if not np.isfinite(cutoff):
+            raise ValueError("the cutoff must be finite, got %r" % cutoff)
+        _lib.require_gpu(self.device)
+        taking_part = [self.neighbor_finder]
+        for nf in (finders or ()):
+            if not any(nf is f for f in taking_part):
+                taking_part.append(nf)
+        n_rows, Ef = int(self.edge_raw_features.shape[0]), self.n_edge_features
+        if compact_edges:
+            for nf in taking_part:
+                if nf.max_edge_idx() >= n_rows:
+                    raise ValueError("a neighbour finder references edge index %d but edge features have %d rows"
+                                     % (nf.max_edge_idx(), n_rows))
+        self._quiesce()
+        flags = torch.zeros(n_rows, dtype=torch.int32, device=self.device) if compact_edges else None
+        dropped = sum(nf.expire(cutoff, self.device, _row_flags=flags) for nf in taking_part)
+        if not compact_edges or dropped == 0:                        # (nothing expired: nothing can be released)
+            return dropped, None
+        nbytes = _lib.byte_count("pfo_edge_rows_plan_scratch_bytes", n_rows)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        remap = torch.empty(n_rows, dtype=torch.int32, device=self.device)
+        n_keep_dev = torch.empty(1, dtype=torch.int32, device=self.device)
+        _lib.call("pfo_edge_rows_plan", flags.data_ptr(), n_rows, remap.data_ptr(), n_keep_dev.data_ptr(), scratch.data_ptr(),
+                  nbytes, _lib.stream_ptr())
+        n_keep = int(n_keep_dev.item())
+        if n_keep == n_rows:
+            return dropped, None
+        tmp = torch.empty((n_keep, Ef), dtype=torch.float32, device=self.device)
+        _lib.call("pfo_edge_rows_compact", self.edge_raw_features.data_ptr(), n_rows, n_keep, Ef, remap.data_ptr(), tmp.data_ptr(),
+                  _lib.stream_ptr())
+        for nf in taking_part:
+            nf.remap_edge_idxs(remap, self.device)
+        self._edges.trim(n_keep)                  # (the kernel zeroed the rows behind the new live count)
+        self._tables_changed()
+        return dropped, remap

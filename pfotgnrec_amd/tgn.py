@@ -23,6 +23,8 @@ from torch import nn
 
 from . import _lib
 from .memory import Memory
+from .serving import Serving
+from .tables import RowStore
 
 
 class _Holder(nn.Module):
@@ -42,11 +44,6 @@ def _normalise_with_stats(edge_features):
 
 def _normalise_edge_features(edge_features):
     return _normalise_with_stats(edge_features)[0]
-
-
-def _grown(capacity, need):
-    # geometric growth: a stream of serving ticks reallocates O(log n) times
-    return max(int(need), int(capacity) + (int(capacity) >> 1) + 16)
 
 
 class _Call:
@@ -188,7 +185,7 @@ class _EmbedFn(torch.autograd.Function):
         return (None, None, None, None) + (None,) * ctx.n_params
 
 
-class TGN(nn.Module):
+class TGN(Serving, nn.Module):
     def __init__(self, neighbor_finder, node_features, edge_features, device, n_layers=2, n_heads=2, dropout=0.1,
                  use_memory=False, memory_update_at_start=True, message_dimension=100, memory_dimension=500,
                  embedding_module_type="graph_attention", message_function="mlp", mean_time_shift_src=0,
@@ -223,8 +220,8 @@ class TGN(nn.Module):
         self.node_raw_features = torch.from_numpy(np.asarray(node_features).astype(np.float32)).to(self.device).contiguous()
         ef, ef_mean, ef_std = _normalise_with_stats(edge_features)
         self.edge_raw_features = torch.from_numpy(ef).to(self.device).contiguous()
-        # capacity storage of the two feature tables (``reserve``): the attributes are its leading rows
-        self._node_store, self._edge_store = self.node_raw_features, self.edge_raw_features
+        # capacity storage of the two feature tables (tables.RowStore, ``reserve``): the attributes are its live rows
+        self._nodes, self._edges = RowStore([self.node_raw_features]), RowStore([self.edge_raw_features])
         self._tables_version = 0          # bumped whenever a table grows or moves (a captured step goes stale)
         self.holdings = None              # the holdings ledger (``track_holdings``): serving state the step never reads
         self._set_stats(ef_mean, ef_std)
@@ -371,6 +368,31 @@ class TGN(nn.Module):
         self._bucket_event, self._bucket_event_fresh = None, False
         self._mid_event, self._mid_event_fresh = None, False   # recorded by the native backward in front of layer 1's attention backward
 
+    def _point_edges(self):
+        """The edge-feature table and its row count re-made from the store.  Alone, and past ``nn.Module.__setattr__``'s walk
+        of its tables (plain attributes): ``add_edge_features`` comes through here every tick."""
+        self.__dict__["edge_raw_features"], self._cfg.n_edges_p1 = self._edges.views()[0], self._edges.rows
+
+    def _point_nodes(self):
+        self.__dict__.update(node_raw_features=self._nodes.views()[0], n_nodes=self._nodes.rows)
+        self._cfg.n_nodes = self._nodes.rows
+
+    def _tables_changed(self, rows=True, node_count=False):
+        """A store moved, or lost or renumbered live rows: the attributes are re-made and what the change stales goes, in this
+        one place.  Always: a captured step (``GraphedTrainStep`` compares the version; it holds the tables' addresses).
+        ``rows`` - live rows were added, renumbered or released: the padded device adjacency and the ``debug_*`` views of the
+        last forward.  ``node_count``: also the workspace pool (carved per node count) and a parameter cache of another size."""
+        self._point_edges()
+        self._point_nodes()
+        self._tables_version += 1
+        if rows:
+            self._adj_cache = self._keepalive = self._last_ws = self._last_call = None    # (the indptr padding depends on n_nodes)
+        if node_count:
+            # outstanding calls hand their - now undersized - workspaces back to the list they took them from, not to the new one
+            self._ws_pool = []
+            if self._pcache is not None and self._pcache.numel() != _lib.byte_count("pfo_tgn_pcache_bytes", ctypes.byref(self._cfg)):
+                self._pcache, self._pcache_key = None, None       # (parameter-only buffers: today its size ignores the node count)
+
     # ------------------------------------------------------------------ parameters
     def _register(self, module, name, offset, shape):
         n = int(np.prod(shape))
@@ -427,20 +449,16 @@ class TGN(nn.Module):
         for p, off, n, shape in self._views:
             p.data = self._flat[off:off + n].view(shape)
             p.grad = None
-        # the capacity storage moves as a whole; the attributes are re-made as its leading rows
-        self._node_store, self._edge_store = fn(self._node_store).contiguous(), fn(self._edge_store).contiguous()
-        self.node_raw_features = self._node_store[:self.node_raw_features.shape[0]]
-        self.edge_raw_features = self._edge_store[:self.edge_raw_features.shape[0]]
+        # the capacity storage moves as a whole; the attributes are re-made as its live rows
+        self._nodes.move(fn)
+        self._edges.move(fn)
         self._edge_stats_dev = fn(self._edge_stats_dev).contiguous()
         if self.holdings is not None:
             self.holdings.move(self._flat.device)
-        self._tables_version += 1
         if self.use_memory:
-            mem = self.memory
-            st = mem._stores()
-            mem._point([fn(st[0]), fn(st[1]), fn(st[2]), fn(st[3]), st[4].to(self._flat.device)], mem.n_nodes)
-            mem.device = self._flat.device
+            self.memory.move(fn, self._flat.device)
             self.memory_updater.layer_norm._apply(fn)
+        self._tables_changed(rows=False)
         self.device = self._flat.device
         if self._prefetched is not None and self._prefetched[2].ws is not None and self._prefetched[2].ws.is_cuda:
             torch.cuda.current_stream(self._prefetched[2].ws.device).wait_event(self._prefetched[2].ready)
@@ -1160,506 +1178,6 @@ class TGN(nn.Module):
         out, _ = self.embed_device(src, dst, [pp, pn], [n_pos, n_neg], ts, eidx, n_neighbors, self._dev_draws(draws),
                                    split_blocks=(1, 1, n_pos, n_neg))
         return out
-
-    # ------------------------------------------------------------------ serving: read-only top-k
-    def _embed_readonly(self, roots, root_ts, K):
-        """Embeddings of (node, time) roots exactly as a forward would give them - pending messages applied lazily
-        (tgn.py:251), L layers over the neighbours strictly before each root's time - with NOTHING written to the model: no
-        persist, no message store, dropout 0 whatever ``train()`` says, the data-parallel sharding ignored.  The roots walk
-        through the forward-only passes in chunks of ``eval_chunk_roots``.  The host-side step counter (position of the Philox
-        streams: uniform sampling draws from it) and the "a GRU took part" flag are put back, so the next training step is the
-        one it would have been."""
-        K, root_ts = self._no_neighbours(int(K), root_ts)
-        saved = (self._step, self._gru_applied_now)
-        self._drop_prefetched()          # (a batch prepared ahead of time is simply prepared again by its own call)
-        try:
-            with torch.no_grad():
-                emb, call = self._forward_chunks(roots, root_ts, K, 0.0, max(1, self._ws_caps[2]),
-                                                 [(c0, None) for c0 in range(0, int(roots.shape[0]), max(1, int(self.eval_chunk_roots)))])
-                if call is not None:
-                    call.release()
-        finally:
-            self._step, self._gru_applied_now = saved
-        return emb
-
-    def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
-                  mv=None, portfolios=None, day_idx=None, basket=False):
-        """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
-        written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
-        is left as found), no gradient is recorded and dropout is off.
-
-        users: [U] node ids (numpy / list, or an integer tensor); timestamps: a scalar or f64 [U]; items: [I] candidate item
-        node ids, distinct and non-zero (shared by all users); exclude: None, a list of per-user lists of item NODE IDS (what
-        the user already holds), or a packed pair (ids i32[U,W] padded with -1, lens i32[U]) - ids that are not in ``items``
-        are ignored; item_ok: optional bool / u8 [I], 0 = never offer this candidate; n_neighbors: default the model's (20).
-
-        Every (item, distinct timestamp) pair is embedded once (the grid of ``TGN._dedup_roots``), users and grid go through
-        the forward-only chunk walk, and one launch of ``pfo_recommend_topk`` scores and selects.  Returns, on the device,
-        (item_ids i32[U,k], scores f32[U,k], n_valid i32[U]): score descending, among equal scores the later entry of
-        ``items`` first; slots beyond the admissible candidates hold id -1 and score -inf.  With
-        ``return_embeddings`` also (user_emb [U,D], item_emb [n_t*I,D], user_block i32[U]): the block of n_t = number of
-        distinct timestamps each user was scored against.
-
-        With ``mv`` (an ``MVSampler``, or any object with ``returns``, ``upper_u``, ``gamma``, ``lambda_mv``, ``day_of``) the
-        order is the mean-variance rank fusion the model is trained towards (main.py:243-289) over the whole candidate list:
-        ``lambda_mv * rank(y_mv) + (1 - lambda_mv) * rank(score)``, one launch of ``pfo_recommend_mv_topk``.  portfolios: the
-        stock indices each user holds, packed (port_idx i32[U,W], port_len i32[U]) on host or device, or a list of per-user
-        lists (entries outside the return table are ignored; they weigh on y_mv, ``exclude`` still decides what is offered);
-        day_idx: an int or one per user, None: ``mv.day_of(timestamps)`` (host timestamps only); a candidate's stock row is
-        ``item - upper_u - 1``.  Up to 2048 candidates that is the one launch; beyond, up to 65536, the same list comes from
-        ``pfo_recommend_mv_topk_wide``: ranks by sorting in a workspace of 36 bytes per user and candidate (256 MiB at the
-        most, the users served in slabs), two launches a slab.  Returns (item_ids, scores, n_valid, fused f64[U,k]) - fused
-        descending, -inf in empty slots - then the embeddings as above.
-
-        ``basket=True`` (needs ``mv``): the list is taken one pick at a time - pick r is ranked with the stocks of picks
-        0 .. r-1 counted as held behind the user's portfolio, so two near-identical stocks no longer both make the list; one
-        launch of ``pfo_recommend_basket_topk`` in place of ``pfo_recommend_mv_topk``, equal to k calls with ``k=1`` and each
-        pick appended to ``portfolios`` and ``exclude``.  The same return tuple; ``fused[u, r]`` is the pick's value in round r.
-        The basket has no wide form: at most 2048 candidates.
-
-        ``exclude="held"`` / ``portfolios="held"`` (either alone, or both): the rows of the holdings ledger
-        (``track_holdings``) in place of the argument - one ``pfo_holdings_gather`` over the users already on the device, no
-        lists packed or uploaded per query; ``portfolios="held"`` still needs ``mv``, whose ``upper_u`` must be the ledger's.
-
-        ``mv`` may be a ``PriceLedger`` (prices.py): its return table grows by the day on the device.  ``day_idx`` is then the
-        ordinal among the ledger's live days (0 = oldest); ``day_idx=None`` also takes DEVICE timestamps - one
-        ``pfo_day_lookup``, no read-back - and a user whose day the ledger does not hold gets an empty answer there, where host
-        timestamps raise ``KeyError``.
-
-        Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` are not (it would cost a
-        read-back).  ``items`` is read back once when it is a device tensor."""
-        from . import recommend as R
-        query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
-                           portfolios, day_idx, self.holdings, basket)
-        _lib.require_gpu(self.device)
-        return R.assemble(self, query, return_embeddings)
-
-    # ------------------------------------------------------------------ serving: write-only state advance
-    def _observe_workspace(self, B):
-        """A workspace of ``pfo_tgn_observe`` from the pool (its entries carry the capacities (0, 0, 0): no forward takes them,
-        and they go with the other undersized buffers when the step's workspace grows)."""
-        need = _lib.byte_count("pfo_tgn_observe_workspace_bytes", ctypes.byref(self._cfg), B)
-        for i, (caps, ws) in enumerate(self._ws_pool):
-            if caps == (0, 0, 0) and ws.numel() >= need:
-                return self._ws_pool.pop(i)[1]
-        return torch.empty(need, dtype=torch.uint8, device=self.device)
-
-    def observe(self, sources, destinations, edge_times, edge_idxs, batch_size=None, append=False):
-        """Takes in interactions WITHOUT embedding anything - the write-only counterpart of ``recommend``: a chronological log
-        is walked on the device in batches of ``batch_size`` and ``memory``, ``last_update`` and the pending-message tables
-        end exactly where ``compute_temporal_embeddings[_p]`` would leave them batch by batch (tgn.py:295-317: the GRU on the
-        batch's own positives that hold a message, the persist, the raw-message store) - no negatives, no sampling, no
-        attention.  One native call (``pfo_tgn_observe``), no Python work per batch.  Nothing else is written: parameters,
-        gradients, optimizer state, the step counter and the random streams stay as they are; no gradient is recorded
-        whatever ``train()`` says.  Returns the number of interactions consumed.
-
-        sources / destinations / edge_times / edge_idxs: numpy i64 / i64 / f64 / i64 like the entry points (range-checked:
-        IndexError), or device tensors i32 / i32 / f64 / i32 (not checked: it would cost a read-back).  ``edge_idxs`` must
-        address EXISTING rows of the edge-feature table: interactions whose features (or nodes) the model has never seen go
-        through ``ingest``, which grows the tables and then calls this.
-        ``batch_size``: interactions per batch, None = the whole input is one batch.  Batch boundaries are part of the
-        semantics (messages are built from the memory as of their batch's persist): replay a log with the batch size it
-        was - or would have been - trained with.  Chronological order is the caller's contract (``debug_checks`` asserts, like
-        ``embed_device``, that no pending message is older than its node's last update).
-        ``append``: the edges also go into the model's neighbour finder (``NeighborFinder.append``) behind the state update, so
-        that a later ``recommend`` sees them; a ``GraphedTrainStep`` captured over the finder goes stale - as does one captured
-        before ``reserve`` / ``add_nodes`` / ``add_edge_features`` moved or grew a table it holds the address of.  Off by default:
-        a replay over a finder that already holds the log must not duplicate its edges.
-        The data-parallel sharding is ignored (every rank observes the whole input: the state is replicated).
-        Without memory there is no state: only the optional append happens."""
-        on_dev = torch.is_tensor(sources)
-        N = int(sources.shape[0]) if on_dev else len(sources)
-        if any(len(a) != N for a in (destinations, edge_times, edge_idxs)):
-            raise ValueError("sources, destinations, edge_times and edge_idxs must have the same length")
-        if batch_size is not None and int(batch_size) < 1:
-            raise ValueError("batch_size must be at least 1")
-        if on_dev:
-            want = (torch.int32, torch.int32, torch.float64, torch.int32)
-            if any((not torch.is_tensor(a)) or a.dtype != dt or a.dim() != 1 for a, dt in zip((sources, destinations, edge_times, edge_idxs), want)):
-                raise ValueError("device inputs must be 1-d tensors i32 / i32 / f64 / i32")
-        else:
-            sources, destinations = self._check_nodes(sources, "sources"), self._check_nodes(destinations, "destinations")
-            edge_idxs = self._check_edges(edge_idxs)
-        if self.use_memory and N > 0:
-            _lib.require_gpu(self.device)
-            with torch.no_grad():
-                self.join()                   # a side-stream optimizer step / a backward beside the host loop may still be running
-                self._drop_prefetched()       # (its packed memory / message rows would be stale)
-                if on_dev:
-                    src, dst, ts, eidx = (a.contiguous() for a in (sources, destinations, edge_times, edge_idxs))
-                else:
-                    ts, src, dst, eidx = self._batch_to_dev([(edge_times, np.float64), (sources, np.int32), (destinations, np.int32),
-                                                             (edge_idxs, np.int32)])
-                if self.debug_checks:
-                    m = self.memory
-                    late = (m.has_msg > 0) & (m.last_update > m.msg_time)
-                    assert not bool(late.any()), "Trying to update memory to time in the past"      # memory_updater.py:25,41
-                B = N if batch_size is None else min(int(batch_size), N)
-                ws = self._observe_workspace(B)
-                st = self._state_struct(adjacency=False)
-                try:
-                    _lib.call("pfo_tgn_observe", ctypes.byref(self._cfg), ctypes.byref(st), src.data_ptr(), dst.data_ptr(),
-                              ts.data_ptr(), eidx.data_ptr(), N, B, ws.data_ptr(), ws.numel(), _lib.stream_ptr())
-                finally:
-                    self._ws_pool.append(((0, 0, 0), ws))
-                self.memory._any_msg = True
-                self.memory._state_version += 1
-        if append and N > 0:
-            host = (lambda a: a.cpu().numpy()) if on_dev else np.asarray
-            self.neighbor_finder.append(host(sources), host(destinations), host(edge_idxs), host(edge_times))
-        return N
-
-    # ------------------------------------------------------------------ serving: tables that grow
-    @property
-    def edge_feature_stats(self):
-        """``(mean f32[Ef], std f32[Ef])`` on the host: the column statistics the constructor normalised the edge-feature
-        table with - the mean of the table, the standard deviation of the centred table, both fp32 as numpy computed them.
-        FROZEN: rows added later (``add_edge_features``) are scaled with these and never with recomputed ones - the weights
-        were trained against this scaling.  They are NOT part of ``state_dict()`` (existing checkpoints keep loading): a model
-        restored next to a table that has grown since takes them from ``set_edge_feature_stats``."""
-        return self._edge_stats
-
-    def _set_stats(self, mean, std):
-        mean = np.ascontiguousarray(np.asarray(mean), dtype=np.float32).reshape(-1)
-        std = np.ascontiguousarray(np.asarray(std), dtype=np.float32).reshape(-1)
-        self._edge_stats = (mean, std)
-        self._edge_stats_dev = torch.from_numpy(np.stack([mean, std])).to(self.device).contiguous()     # [2, Ef]: mean | std
-
-    def set_edge_feature_stats(self, mean, std):
-        """Replaces the frozen statistics (``edge_feature_stats``), e.g. with those saved beside a checkpoint.  The table is
-        NOT re-normalised: only rows added from now on are scaled with the new vectors."""
-        mean, std = np.asarray(mean), np.asarray(std)
-        if mean.shape != (self.n_edge_features,) or std.shape != (self.n_edge_features,):
-            raise ValueError("mean and std must have shape (%d,)" % self.n_edge_features)
-        self._set_stats(mean, std)
-
-    @property
-    def node_capacity(self):
-        return int(self._node_store.shape[0])
-
-    @property
-    def edge_capacity(self):
-        return int(self._edge_store.shape[0])
-
-    def _quiesce(self):
-        # a side-stream optimizer step / a backward beside the host loop may still read the tables that are about to move
-        if self._flat.is_cuda:
-            self.join()
-            self._drop_prefetched()
-
-    def reserve(self, n_nodes=None, n_edges=None):
-        """Capacity for ``n_nodes`` rows of the node tables (``node_raw_features``, ``memory.memory``, ``memory.last_update``,
-        the pending-message table, its times and flags) and ``n_edges`` rows of the edge-feature table - rows, the padding
-        row 0 included.  Live rows are copied across bit for bit, rows behind them are zero; the attributes stay what they
-        were - contiguous leading-row views of the storage, same dtypes and shapes - but their addresses change when storage
-        is reallocated.  Capacity never shrinks (asking for what is there, or less, does nothing); asking for less than the
-        live rows raises ``ValueError``.  Without ``reserve`` the tables grow geometrically on demand.  Call it between steps
-        (see ``add_nodes``); a ``GraphedTrainStep`` captured before goes stale."""
-        if n_nodes is not None and int(n_nodes) < self.n_nodes:
-            raise ValueError("reserve(n_nodes=%d) is below the %d live rows" % (int(n_nodes), self.n_nodes))
-        if n_edges is not None and int(n_edges) < self.edge_raw_features.shape[0]:
-            raise ValueError("reserve(n_edges=%d) is below the %d live rows" % (int(n_edges), self.edge_raw_features.shape[0]))
-        if n_edges is not None and int(n_edges) > self.edge_capacity:
-            self._quiesce()
-            live = self.edge_raw_features.shape[0]
-            store = torch.zeros((int(n_edges), self.n_edge_features), dtype=torch.float32, device=self.device)
-            store[:live].copy_(self.edge_raw_features)
-            self._edge_store, self.edge_raw_features = store, store[:live]
-            self._tables_version += 1
-        if n_nodes is not None and int(n_nodes) > self.node_capacity:
-            self._quiesce()
-            live = self.n_nodes
-            store = torch.zeros((int(n_nodes), self.n_node_features), dtype=torch.float32, device=self.device)
-            store[:live].copy_(self.node_raw_features)
-            self._node_store, self.node_raw_features = store, store[:live]
-            if self.use_memory:
-                self.memory.resize(live, int(n_nodes))
-            if self.holdings is not None:
-                self.holdings.resize(live, int(n_nodes))
-            self._tables_version += 1
-        return self
-
-    def add_edge_features(self, raw):
-        """Appends ``raw`` f32[m, Ef] RAW edge-feature rows - a host array (checked: width, finite values; staged through the
-        batch ring) or an fp32 device tensor (shape checked only) - behind the live rows, normalised with the frozen
-        ``edge_feature_stats`` by ONE launch of ``pfo_edge_rows_append`` (numpy's two fp32 operations, bit for bit).  Returns
-        the new rows' edge indices, i64[m]: the old row count onwards.  Nothing else changes; live rows keep every bit (they
-        move only when the capacity is exceeded: ``reserve``)."""
-        Ef = self.n_edge_features
-        if torch.is_tensor(raw):
-            if raw.dim() != 2 or raw.shape[1] != Ef or raw.dtype != torch.float32:
-                raise ValueError("device edge features must be an fp32 tensor [m, %d]" % Ef)
-            dev_rows = raw
-        else:
-            raw = np.asarray(raw)
-            if raw.ndim != 2 or raw.shape[1] != Ef:
-                raise ValueError("edge features must have shape [m, %d], got %s" % (Ef, raw.shape))
-            raw = raw.astype(np.float32, copy=False)
-            if not np.isfinite(raw).all():
-                raise ValueError("edge features must be finite")
-            dev_rows = None
-        m, n0 = int(raw.shape[0]), int(self.edge_raw_features.shape[0])
-        if n0 + m >= 2 ** 31:
-            raise ValueError("edge indices must fit in int32")
-        if m == 0:
-            return np.zeros(0, np.int64)
-        _lib.require_gpu(self.device)
-        if dev_rows is None:
-            dev_rows = self._batch_to_dev([(raw, np.float32)])[0]
-        dev_rows = dev_rows.contiguous()
-        if n0 + m > self.edge_capacity:
-            self.reserve(n_edges=_grown(self.edge_capacity, n0 + m))
-        st = self._edge_stats_dev
-        _lib.call("pfo_edge_rows_append", dev_rows.data_ptr(), st[0].data_ptr(), st[1].data_ptr(), m, Ef, self._edge_store.data_ptr(),
-                  n0, self.edge_capacity, _lib.stream_ptr())
-        self.edge_raw_features = self._edge_store[:n0 + m]
-        self._cfg.n_edges_p1 = n0 + m
-        return np.arange(n0, n0 + m, dtype=np.int64)
-
-    def add_nodes(self, n, node_features=None):
-        """``n`` new nodes behind the last one; returns the first new node id (= the old ``n_nodes``).  Their rows of
-        ``node_raw_features`` are ``node_features`` f32[n, D] or zeros (the reference's node features are all zeros,
-        main.py:87); their memory, last update and pending-message state are the initial ones (zero, none pending).
-        Parameters, their ``.grad`` views, the flat buffers, the optimizer state, the step counter and the parameter cache
-        (its size does not depend on the node count) are untouched.  Invalidated: the workspace pool (workspaces are carved
-        per node count), the padded device adjacency, a batch prepared ahead of time, the ``debug_*`` views of the last
-        forward, and any ``GraphedTrainStep`` captured before.
-
-        Call it BETWEEN steps: a forward whose backward is still pending keeps the workspace and config it ran with, and must
-        have its backward run first."""
-        n = int(n)
-        if n < 0:
-            raise ValueError("n must not be negative")
-        D = self.n_node_features
-        rows = None
-        if node_features is not None:
-            rows = node_features if torch.is_tensor(node_features) else torch.from_numpy(
-                np.ascontiguousarray(np.asarray(node_features), dtype=np.float32))
-            if rows.dim() != 2 or tuple(rows.shape) != (n, D):
-                raise ValueError("node_features must have shape [%d, %d], got %s" % (n, D, tuple(rows.shape)))
-        first = self.n_nodes
-        if n == 0:
-            return first
-        if first + n >= 2 ** 31:
-            raise ValueError("node ids must fit in int32")
-        self._quiesce()
-        if first + n > self.node_capacity:
-            self.reserve(n_nodes=_grown(self.node_capacity, first + n))
-        if rows is not None:                                      # (rows behind the live ones are zero already)
-            self._node_store[first:first + n].copy_(rows.to(dtype=torch.float32))
-        self.node_raw_features = self._node_store[:first + n]
-        self.n_nodes = first + n
-        self._cfg.n_nodes = first + n
-        if self.use_memory:
-            self.memory.resize(first + n)                         # (bumps memory._state_version)
-        if self.holdings is not None:
-            self.holdings.resize(first + n)                       # (rows behind the live ones hold the initial values already)
-        # outstanding calls hand their - now undersized - workspaces back to the list they took them from, not to the new one
-        self._ws_pool = []
-        self._adj_cache, self._keepalive = None, None             # (the indptr padding depends on n_nodes)
-        self._last_ws, self._last_call = None, None
-        self._tables_version += 1
-        if self._pcache is not None and self._pcache.numel() != _lib.byte_count("pfo_tgn_pcache_bytes", ctypes.byref(self._cfg)):
-            self._pcache, self._pcache_key = None, None           # (parameter-only buffers: today its size ignores the node count)
-        return first
-
-    def ingest(self, sources, destinations, edge_times, edge_features, batch_size=None, node_features=None, portfolios=None):
-        """The serving tick: takes in interactions the model has NEVER seen - their feature rows are not in the edge-feature
-        table, their nodes may not exist yet - so that the next ``recommend`` accounts for them.  A thin chain of
-        ``add_nodes`` (when the input names new nodes), ``add_edge_features`` and ``observe(..., append=True)``: the state
-        semantics are ``observe``'s by shared code (batch boundaries included: ``batch_size``), every rank of a data-parallel
-        group ingests the whole input, and nothing else is written.  Per tick: one launch for the feature rows, ONE
-        ``pfo_tgn_observe`` call (4 launches per batch) and the CSR append; no Python work per batch.  Without memory only the
-        tables and the finder grow.  Returns ``(n_consumed, edge_idxs i64[N])`` - the indices the new rows got.
-
-        sources / destinations / edge_times: numpy i64 / i64 / f64 like ``observe``; edge_features: RAW rows f32[N, Ef]
-        (normalised here with the frozen ``edge_feature_stats``).  Node ids >= ``n_nodes`` are allowed only as exactly the
-        next consecutive ids; those nodes are added first, with ``node_features`` f32[n_new, D] as their rows in ascending id
-        order, zeros otherwise.  Host inputs are validated BEFORE anything is written (``ValueError``: lengths, feature width,
-        non-finite features, decreasing ``edge_times``, node ids < 1, ids that skip ahead, ``batch_size`` < 1): a rejected call
-        leaves the model bit for bit as it was.  Device tensors (i32 / i32 / f64 and f32[N, Ef]) are checked for shape and
-        dtype only and must name existing nodes (``add_nodes`` first).
-
-        ``portfolios``: what each record says its user holds at that moment, in a form ``update_holdings`` takes (host forms
-        with host inputs, the device pair with device inputs); needs a ledger (``track_holdings``).  Its checks join the ones
-        above - a rejected call leaves the ledger too - and the ledger is written ONCE per call behind ``add_nodes`` (last
-        record per user over the whole input: batch boundaries do not matter to it).  None: the ledger is not touched."""
-        on_dev = torch.is_tensor(sources)
-        N = int(sources.shape[0]) if on_dev else len(sources)
-        if portfolios is not None and self.holdings is None:
-            raise ValueError("portfolios need a holdings ledger: call track_holdings(width, upper_u) first")
-        if any(len(a) != N for a in (destinations, edge_times, edge_features)):
-            raise ValueError("sources, destinations, edge_times and edge_features must have the same length")
-        if batch_size is not None and int(batch_size) < 1:
-            raise ValueError("batch_size must be at least 1")
-        Ef, n_new = self.n_edge_features, 0
-        if on_dev:
-            want = (torch.int32, torch.int32, torch.float64)
-            if any((not torch.is_tensor(a)) or a.dtype != dt or a.dim() != 1 for a, dt in zip((sources, destinations, edge_times), want)):
-                raise ValueError("device inputs must be 1-d tensors i32 / i32 / f64")
-            if not torch.is_tensor(edge_features) or edge_features.dim() != 2 or edge_features.shape[1] != Ef or edge_features.dtype != torch.float32:
-                raise ValueError("device edge features must be an fp32 tensor [N, %d]" % Ef)
-            if node_features is not None:
-                raise ValueError("device inputs must name existing nodes: add_nodes first")
-        else:
-            sources, destinations = np.asarray(sources), np.asarray(destinations)
-            edge_times, edge_features = np.asarray(edge_times, np.float64), np.asarray(edge_features)
-            if sources.ndim != 1 or destinations.ndim != 1 or edge_times.ndim != 1:
-                raise ValueError("sources, destinations and edge_times must be 1-d")
-            if edge_features.ndim != 2 or edge_features.shape[1] != Ef:
-                raise ValueError("edge features must have shape [N, %d], got %s" % (Ef, edge_features.shape))
-            if not np.isfinite(edge_features).all():
-                raise ValueError("edge features must be finite")
-            if N and (not np.isfinite(edge_times).all() or (np.diff(edge_times) < 0).any()):
-                raise ValueError("edge_times must be finite and chronological (non-decreasing)")
-            ids = np.concatenate([sources, destinations]).astype(np.int64)
-            if N and int(ids.min()) < 1:
-                raise ValueError("node ids must be >= 1 (node 0 is the padding node)")
-            fresh = np.unique(ids[ids >= self.n_nodes])
-            n_new = int(fresh.shape[0])
-            if n_new and not np.array_equal(fresh, np.arange(self.n_nodes, self.n_nodes + n_new)):
-                raise ValueError("new node ids must be exactly the next consecutive ids %d.. : got %s"
-                                 % (self.n_nodes, fresh[:8].tolist()))
-            if node_features is not None and tuple(np.shape(node_features)) != (n_new, self.n_node_features):
-                raise ValueError("node_features must have shape [%d, %d]: one row per new node" % (n_new, self.n_node_features))
-        held = None
-        if portfolios is not None:                # (the new nodes are rows of the ledger by the time it is written)
-            from . import holdings as H
-            held = H.validate(self.holdings.width, self.n_nodes + n_new, sources, portfolios, edge_times)
-        if N == 0:
-            return 0, np.zeros(0, np.int64)
-        _lib.require_gpu(self.device)             # (nothing below has a host path: refuse before the first table grows)
-        if n_new:
-            self.add_nodes(n_new, node_features)
-        if held is not None:
-            self._write_holdings(held)
-        new_idxs = self.add_edge_features(edge_features)
-        eidx = torch.arange(int(new_idxs[0]), int(new_idxs[0]) + N, dtype=torch.int32, device=self.device) if on_dev else new_idxs
-        return self.observe(sources, destinations, edge_times, eidx, batch_size, append=True), new_idxs
-
-    # ------------------------------------------------------------------ serving: the holdings ledger
-    def track_holdings(self, width, upper_u):
-        """Creates the holdings ledger (``self.holdings``, None before): per node row the portfolio its user's newest
-        interaction record carried - ``idx`` i32[n_nodes, width] STOCK indices padded with -1 (the packed form of
-        ``pack_portfolios``; the item node of stock ``s`` is ``s + upper_u + 1``), ``len`` i32[n_nodes], ``time`` f64[n_nodes]
-        (-1 / 0 / -inf until written) - in capacity storage that follows ``node_capacity`` (``reserve`` / ``add_nodes`` keep
-        live rows bit for bit) and the model's device.  ``update_holdings`` and ``ingest(portfolios=)`` write it,
-        ``recommend(exclude="held", portfolios="held")`` and ``holdings.rows(users)`` read it; the training step, ``observe``
-        and ``expire`` do not touch it, and it is not part of ``state_dict()``: persist ``holdings.idx / len / time`` and load
-        them with ``update_holdings``.  Once: a second call with other arguments raises ``ValueError``.  Returns the ledger."""
-        from . import holdings as H
-        try:
-            width, upper_u = int(width), int(upper_u)
-        except (TypeError, ValueError):
-            raise ValueError("width and upper_u must be integers") from None
-        if not 1 <= width <= H.MAX_WIDTH:
-            raise ValueError("width must lie in [1, %d] (got %d)" % (H.MAX_WIDTH, width))
-        if not 0 <= upper_u < 2 ** 31 - 1:
-            raise ValueError("upper_u must be a non-negative int32 (got %d)" % upper_u)
-        if self.holdings is not None:
-            if (self.holdings.width, self.holdings.upper_u) != (width, upper_u):
-                raise ValueError("the model already tracks holdings with width %d, upper_u %d"
-                                 % (self.holdings.width, self.holdings.upper_u))
-            return self.holdings
-        self.holdings = H.Holdings(self.n_nodes, self.node_capacity, width, upper_u, self.device)
-        return self.holdings
-
-    def update_holdings(self, sources, portfolios, edge_times):
-        """The one writer of the ledger: for every event in input order, ``holdings[sources[e]] = (portfolios[e], edge_times[e])``
-        - per user the LAST event of the call wins, an empty portfolio overwrites, entries are stored verbatim, nothing is
-        compared with the stored time (chronological input is the caller's contract, as for ``observe``); node 0 is skipped.
-        One native call (``pfo_holdings_store``: a memset and two launches).  Seeds a served model from the training log and
-        loads a saved ledger (``sources = arange(n_nodes)``, ``portfolios = (idx, len)``, ``edge_times = time``).
-
-        ``portfolios``: a packed pair (idx [N, Wp], len [N]) as numpy, one list of integer stock indices per event, or the pair
-        as i32 device tensors next to i32 / f64 device ``sources`` / ``edge_times``.  Host inputs are validated before anything
-        is written (``ValueError``: lengths, integer dtypes, values beyond int32, len outside [0, Wp], a row longer than the
-        ledger's width, node ids outside [0, n_nodes)) and staged in one copy; device inputs are checked for shape and dtype
-        only - the kernel skips ids outside [1, n_nodes) and clamps lengths to the row.  Returns the number of events."""
-        if self.holdings is None:
-            raise ValueError("no holdings ledger: call track_holdings(width, upper_u) first")
-        from . import holdings as H
-        w = H.validate(self.holdings.width, self.n_nodes, sources, portfolios, edge_times)
-        if w.N:
-            _lib.require_gpu(self.device)
-            self._write_holdings(w)
-        return w.N
-
-    def _write_holdings(self, w):
-        with torch.no_grad():
-            if w.on_dev:
-                src, idx, length, ts = w.src, w.idx, w.len, w.ts
-            else:
-                ts, src, idx, length = self._batch_to_dev([(w.ts, np.float64), (w.src, np.int32), (w.idx, np.int32), (w.len, np.int32)])
-            self.holdings.store(src, idx, length, ts)
-
-    # ------------------------------------------------------------------ serving: the retention window
-    def expire(self, cutoff, compact_edges=True, finders=None):
-        """"Keep the last N days": every adjacency entry with ``ts < cutoff`` (strict, fp64) leaves the neighbour finder
-        (``NeighborFinder.expire``) and, with ``compact_edges``, the rows of the edge-feature table that only expired entries
-        named are released.  Returns ``(n_entries_dropped, remap)``: the entries dropped over all finders taking part, and the
-        DEVICE tensor ``remap`` i32[old row count] - old edge index -> new one, ``remap[0] == 0``, -1 for a released row - or
-        ``None`` when ``compact_edges=False`` or no row was released (edge indices then mean what they meant).
-
-        The table is shared between finders (a train finder and a full finder over one table): ``finders`` names the OTHER
-        ``NeighborFinder``s over this model's table; the model's own finder always takes part.  All are expired with the same
-        cutoff and remapped with the same map.  A row ``r >= 1`` is released iff some expired entry of a finder taking part
-        names it and no surviving entry of any of them does; rows nobody names stay, row 0 always stays.  A finder over this
-        table that is NOT passed keeps its old edge indices and is wrong afterwards.  Surviving rows keep their order and are
-        renumbered densely; they move down inside the unchanged storage through a temporary (``pfo_edge_rows_compact``), the
-        rows behind the new live count are zero again, capacity never shrinks, and the next ``add_edge_features`` / ``ingest``
-        continues from the new row count.
-
-        Order: ``_quiesce()``, the finders, then the table.  Node memory, ``last_update``, the pending messages (they hold the
-        feature VALUES, not edge indices), parameters, gradients, optimizer state, the step counter and the random streams are
-        not touched.  Invalidated after a compaction: the padded device adjacency, the ``debug_*`` views of the last forward,
-        a batch prepared ahead of time and any ``GraphedTrainStep`` captured before (an expiry alone already stales the
-        latter through the finder's version).  Two read-backs (the surviving entry total per finder, the new row count): a
-        maintenance call, not a step.
-
-        Call it BETWEEN steps, like ``add_nodes``: a forward whose backward is still pending must have that backward run
-        first.  On a data-parallel group EVERY rank calls it with the same cutoff: state is replicated, there is no
-        collective.  ``cutoff`` must be finite (``ValueError`` before anything is written); without a device it raises like
-        every compute method."""
-        cutoff = float(cutoff)
-        if not np.isfinite(cutoff):
-            raise ValueError("the cutoff must be finite, got %r" % cutoff)
-        _lib.require_gpu(self.device)
-        taking_part = [self.neighbor_finder]
-        for nf in (finders or ()):
-            if not any(nf is f for f in taking_part):
-                taking_part.append(nf)
-        n_rows, Ef = int(self.edge_raw_features.shape[0]), self.n_edge_features
-        if compact_edges:
-            for nf in taking_part:
-                if nf.max_edge_idx() >= n_rows:
-                    raise ValueError("a neighbour finder references edge index %d but edge features have %d rows"
-                                     % (nf.max_edge_idx(), n_rows))
-        self._quiesce()
-        flags = torch.zeros(n_rows, dtype=torch.int32, device=self.device) if compact_edges else None
-        dropped = sum(nf.expire(cutoff, self.device, _row_flags=flags) for nf in taking_part)
-        if not compact_edges or dropped == 0:                        # (nothing expired: nothing can be released)
-            return dropped, None
-        nbytes = _lib.byte_count("pfo_edge_rows_plan_scratch_bytes", n_rows)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        remap = torch.empty(n_rows, dtype=torch.int32, device=self.device)
-        n_keep_dev = torch.empty(1, dtype=torch.int32, device=self.device)
-        _lib.call("pfo_edge_rows_plan", flags.data_ptr(), n_rows, remap.data_ptr(), n_keep_dev.data_ptr(), scratch.data_ptr(),
-                  nbytes, _lib.stream_ptr())
-        n_keep = int(n_keep_dev.item())
-        if n_keep == n_rows:
-            return dropped, None
-        tmp = torch.empty((n_keep, Ef), dtype=torch.float32, device=self.device)
-        _lib.call("pfo_edge_rows_compact", self._edge_store.data_ptr(), n_rows, n_keep, Ef, remap.data_ptr(), tmp.data_ptr(),
-                  _lib.stream_ptr())
-        for nf in taking_part:
-            nf.remap_edge_idxs(remap, self.device)
-        self.edge_raw_features = self._edge_store[:n_keep]
-        self._cfg.n_edges_p1 = n_keep
-        self._adj_cache, self._keepalive = None, None
-        self._last_ws, self._last_call = None, None
-        self._tables_version += 1
-        return dropped, remap
 
     def _dev_keep(self, masks):
         """Injected dropout decisions for a parity test: ``{l: multipliers or booleans [n_l, H, K]}`` (level order, the layout

@@ -285,15 +285,15 @@ def test_compaction_over_two_finders_bit_for_bit():
     assert (alone[late_rows] == -1).all() and (want_remap[late_rows] >= 0).all(), "expired in one finder, surviving in the other: stays"
     assert (want_remap[unnamed_rows] >= 0).all() and len(unnamed_rows) > 100, "rows nobody names stay"
     assert 1 < want_keep < n_rows - 100
-    store_ptr, cap, tv = tgn._edge_store.data_ptr(), tgn.edge_capacity, tgn._tables_version
+    store_ptr, cap, tv = tgn._edges.storage[0].data_ptr(), tgn.edge_capacity, tgn._tables_version
     tgn._adj_cache, tgn._last_ws, tgn._last_call = ("x",), ("y",), ("z",)
     dropped, remap = tgn.expire(cutoff, finders=[nf_train])
     torch.cuda.synchronize()
     assert dropped == want_dropped and remap.device.type == "cuda" and remap.dtype == torch.int32
     assert _bits(_host(remap), want_remap) and int(remap[0]) == 0
     assert tgn.edge_raw_features.shape[0] == want_keep == tgn._cfg.n_edges_p1
-    assert tgn._edge_store.data_ptr() == store_ptr == tgn.edge_raw_features.data_ptr() and tgn.edge_capacity == cap
-    assert _bits(_host(tgn._edge_store), R.compact_table(table, want_remap, capacity=cap)), "table: kept rows, zero rows behind"
+    assert tgn._edges.storage[0].data_ptr() == store_ptr == tgn.edge_raw_features.data_ptr() and tgn.edge_capacity == cap
+    assert _bits(_host(tgn._edges.storage[0]), R.compact_table(table, want_remap, capacity=cap)), "table: kept rows, zero rows behind"
     for nf, want, tag in ((nf_full, want_csr[0], "full"), (nf_train, want_csr[1], "train")):
         _assert_csr(_dev_csr(nf), want, tag)
         assert nf._version == 2 and nf._max_eidx is None and nf.max_edge_idx() < want_keep
@@ -310,12 +310,12 @@ def test_without_compaction_the_table_and_the_ids_stay():
     cutoff = _cutoff_of(g, 0.6)
     csr = _host_csr(nf_full)
     train_before = _host_csr(nf_train)
-    table, tv = _host(tgn._edge_store).copy(), tgn._tables_version
+    table, tv = _host(tgn._edges.storage[0]).copy(), tgn._tables_version
     want, keep = R.expire_csr(*csr, cutoff)
     dropped, remap = tgn.expire(cutoff, compact_edges=False)
     assert remap is None and dropped == int((~keep).sum()) > 0
     _assert_csr(_dev_csr(nf_full), want, "ids untouched")
-    assert _bits(_host(tgn._edge_store), table) and tgn._tables_version == tv and tgn._cfg.n_edges_p1 == N_EDGES + 1
+    assert _bits(_host(tgn._edges.storage[0]), table) and tgn._tables_version == tv and tgn._cfg.n_edges_p1 == N_EDGES + 1
     _assert_csr(_dev_csr(nf_train), train_before, "a finder that does not take part")
     assert nf_train._version == 0 and nf_full._version == 1
     # a cutoff below everything: nothing at all happens, whatever compact_edges says

@@ -320,8 +320,8 @@ def test_reserve_and_add_nodes_grow_the_ledger():
     tgn.reserve(n_nodes=n + 7)
     assert h.capacity == tgn.node_capacity == n + 7 and h.n_nodes == n
     assert all(HR.same_bits(a, b) for a, b in zip(_ledger(tgn), before)), "live rows are copied bit for bit"
-    assert _initial(h._stores, n), "rows behind the live count hold the initial values"
-    for view, store in zip((h.idx, h.len, h.time), h._stores):
+    assert _initial(h._store.storage, n), "rows behind the live count hold the initial values"
+    for view, store in zip((h.idx, h.len, h.time), h._store.storage):
         assert view.data_ptr() == store.data_ptr() and view.is_contiguous() and view.shape[0] == n
     ptr = h.idx.data_ptr()
     assert tgn.add_nodes(3) == n                                # within capacity: nothing moves
@@ -333,7 +333,7 @@ def test_reserve_and_add_nodes_grow_the_ledger():
     assert tgn.add_nodes(20) == n + 3                           # across it: reallocated with the node tables
     assert h.n_nodes == tgn.n_nodes == n + 23 and h.capacity == tgn.node_capacity >= n + 23 and h.idx.data_ptr() != ptr
     assert all(HR.same_bits(a[:n], b) for a, b in zip(_ledger(tgn), before))
-    assert _initial(h._stores, n)
+    assert _initial(h._store.storage, n)
     assert h._stamp.shape[0] == h._pos.shape[0] == h.capacity, "the scratch tables follow the capacity"
     with pytest.raises(ValueError, match="shrink"):
         h.resize(n)
@@ -348,4 +348,4 @@ def test_device_move_and_cast_carry_the_ledger():
     h = tgn.holdings
     assert h.capacity == cap and h.time.dtype == torch.float64 and h.idx.dtype == torch.int32
     assert all(HR.same_bits(a, b) for a, b in zip(_ledger(tgn), before))
-    assert h.idx.data_ptr() == h._stores[0].data_ptr()
+    assert h.idx.data_ptr() == h._store.storage[0].data_ptr()

@@ -192,9 +192,9 @@ def test_reserve_keeps_rows_and_attributes():
     assert isinstance(tgn.memory.memory, torch.nn.Parameter) and not tgn.memory.memory.requires_grad
     assert isinstance(tgn.memory.last_update, torch.nn.Parameter) and not tgn.memory.last_update.requires_grad
     # the attributes are leading-row views of the storage, and the rows behind them are zero
-    stores = [tgn._node_store, tgn._edge_store] + tgn.memory._stores()
+    stores = [tgn._nodes.storage[0], tgn._edges.storage[0]] + tgn.memory._store.storage
     for t, s, live in zip(after.values(), stores, [n, e, n, n, n, n, n]):
-        assert t.data_ptr() == s.data_ptr() and s.shape[0] == (e + 13 if s is tgn._edge_store else n + 7)
+        assert t.data_ptr() == s.data_ptr() and s.shape[0] == (e + 13 if s is tgn._edges.storage[0] else n + 7)
         assert not s[live:].any()
     assert (tgn.n_nodes, tgn._cfg.n_nodes, tgn._cfg.n_edges_p1, tgn.memory.n_nodes) == (n, n, e, n)
     # idempotent: the same request again - or a smaller one that still covers the live rows - moves nothing
@@ -276,11 +276,11 @@ def test_add_nodes_without_memory_and_device_move_keep_the_storage():
     mean, std = tgn.edge_feature_stats
     tgn.to("cpu")                                               # _apply: the capacity storage and the statistics travel along
     assert (tgn.node_capacity, tgn.edge_capacity) == (n + 4, e + 4)
-    assert tgn.node_raw_features.data_ptr() == tgn._node_store.data_ptr() and tgn.node_raw_features.shape[0] == n + 1
-    assert tgn.edge_raw_features.data_ptr() == tgn._edge_store.data_ptr() and tgn.edge_raw_features.shape[0] == e
+    assert tgn.node_raw_features.data_ptr() == tgn._nodes.storage[0].data_ptr() and tgn.node_raw_features.shape[0] == n + 1
+    assert tgn.edge_raw_features.data_ptr() == tgn._edges.storage[0].data_ptr() and tgn.edge_raw_features.shape[0] == e
     assert np.array_equal(tgn._edge_stats_dev.numpy(), np.stack([mean, std]))
     mem, _ = _host_model(True)
     mem.reserve(n_nodes=n + 4)
     mem.float()
     assert mem.memory.capacity == n + 4 and mem.memory.memory.shape[0] == n and mem.memory.has_msg.dtype == torch.uint8
-    assert mem.memory.memory.data_ptr() == mem.memory._stores()[0].data_ptr()
+    assert mem.memory.memory.data_ptr() == mem.memory._store.storage[0].data_ptr()

@@ -65,7 +65,7 @@ def main():
     saved = tgn.memory.backup_memory()
     params = {k: v.clone() for k, v in tgn.state_dict().items() if not k.startswith("memory.")}
     tgn.reserve(n_edges=HISTORY + 1 + 2 * TICK)
-    table = tgn._edge_store.clone()                               # (rows behind the live ones are zero)
+    table = tgn._edges.storage[0].clone()                              # (rows behind the live ones are zero)
     cutoff = float(d.timestamps[HISTORY // 2])
     keep = d.timestamps[hist] >= cutoff
     kept_rows = np.concatenate([[0], d.edge_idxs[hist][keep]])    # the filtered log's feature rows, padding row first
@@ -73,9 +73,9 @@ def main():
 
     def restore():
         """The served model as it was: table rows, row count, finder, state."""
-        tgn._edge_store.copy_(table)
-        tgn.edge_raw_features = tgn._edge_store[:HISTORY + 1]
-        tgn._cfg.n_edges_p1 = HISTORY + 1
+        tgn._edges.storage[0].copy_(table)
+        tgn._edges.rows = HISTORY + 1                             # (back UP after an expiry, back down after a tick)
+        tgn._point_edges()
         tgn.set_neighbor_finder(full_finder())
         tgn.memory.restore_memory(saved)
     out = {}

@@ -82,8 +82,8 @@ def main():
     tgn.reserve(n_edges=HISTORY + 1 + 2 * (T_WARM + T_REPS + 1) * TICK)
 
     def restore():
-        tgn.edge_raw_features = tgn._edge_store[:HISTORY + 1]
-        tgn._cfg.n_edges_p1 = HISTORY + 1
+        tgn._edges.trim(HISTORY + 1)
+        tgn._point_edges()
         tgn.set_neighbor_finder(finder(hist))
         tgn.memory.restore_memory(saved)
     ticks = (("with_portfolios", lambda: tgn.ingest(s_t, d_t, t_t, raw_t, batch_size=B, portfolios=ports_t)),

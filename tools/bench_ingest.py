@@ -61,8 +61,8 @@ def main():
 
     def restore():
         """The served model as it was in front of the tick: tables, row count, finder, state."""
-        tgn.edge_raw_features = tgn._edge_store[:HISTORY + 1]
-        tgn._cfg.n_edges_p1 = HISTORY + 1
+        tgn._edges.trim(HISTORY + 1)
+        tgn._point_edges()
         tgn.set_neighbor_finder(finder(hist))
         tgn.memory.restore_memory(saved)
 
