@@ -428,11 +428,17 @@ int pfo_recommend_basket_topk(const float* user_emb, const float* item_emb, cons
  * ties in edge order (Python's stable sorted(key=ts), utils.py:139).  A stable LSD radix sort of the 2E entries; the eight
  * timestamp passes are skipped when the log is already chronological.  All pointers are device pointers; `workspace` holds
  * pfo_csr_build_workspace_bytes(E, n_nodes) bytes; indptr has n_nodes + 1 entries, the adjacency arrays 2E.
+ * -0.0 and +0.0 are ONE timestamp to the sort (a tie, kept in edge order); adj_ts keeps the bits it was given.  NaN timestamps
+ * have no place in the order: the Python callers refuse them, this entry does not look.
  */
 int64_t pfo_csr_build_workspace_bytes(int64_t E, int64_t n_nodes);
 int pfo_csr_build(const int32_t* src, const int32_t* dst, const int32_t* eidx, const double* ts, int64_t E, int64_t n_nodes,
                   int64_t* indptr, int32_t* adj_nbr, int32_t* adj_eidx, double* adj_ts, void* workspace,
                   int64_t workspace_bytes, void* stream);
+/* What pfo_csr_build would launch for these sizes, asked without launching (pure host code; additive: the abi version stays):
+ * out[0] = 1024-entry tiles of a radix pass, out[1] = owner passes (one per byte of the largest node id), out[2] = sweeps of
+ * the scan over the 256 * tiles tile histograms (pfo_debug_scan_sweeps).  -1 with a message on sizes pfo_csr_build refuses. */
+int pfo_debug_csr_build_plan(int64_t E, int64_t n_nodes, int32_t* out /* HOST, 3 entries */);
 /* Merge of a CSR of NEW edges (built by pfo_csr_build over n_nodes rows) into an existing one (n_old_nodes <= n_nodes rows):
  * the result equals a rebuild over [old edges ; new edges] - inside a row a new entry goes behind every old entry whose
  * timestamp is <= its own.  Output arrays hold old + new entries; new_indptr has n_nodes + 1 entries.

@@ -183,6 +183,7 @@ PROTOTYPES = {
                                 _VP]),
     "pfo_csr_build_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "pfo_csr_build": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    "pfo_debug_csr_build_plan": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_int32)]),
     "pfo_csr_append": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "pfo_csr_expire_scratch_bytes": (C.c_int64, [C.c_int64]),
     "pfo_csr_expire_plan": (C.c_int, [_VP, _VP, C.c_int64, C.c_double, _VP, _VP, _VP, C.c_int64, _VP]),
@@ -387,6 +388,14 @@ def gemm_plan(name, *args):
     plan["form"] = GEMM_FORMS[plan["form"]]
     plan["kind"] = PROF_KINDS[plan["kind"]] if plan["kind"] >= 0 else None
     return plan
+
+
+def csr_build_plan(E, n_nodes):
+    """``pfo_debug_csr_build_plan``: ``(tiles, owner passes, histogram-scan sweeps)`` of a ``pfo_csr_build`` over these sizes;
+    ``PfoError`` with the message where the build would refuse them."""
+    out = (C.c_int32 * 3)()
+    call("pfo_debug_csr_build_plan", int(E), int(n_nodes), out)
+    return tuple(out)
 
 
 _GPU_SEEN = [False]

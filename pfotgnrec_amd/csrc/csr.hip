@@ -27,7 +27,8 @@ struct Edges {
 };
 
 __device__ __forceinline__ uint64_t sortable_f64(double x) {
-  const uint64_t u = (uint64_t)__double_as_longlong(x);
+  uint64_t u = (uint64_t)__double_as_longlong(x);
+  if ((u << 1) == 0) u = 0;                                   // -0.0 == +0.0: ONE key (a tie, kept in edge order); integer test, nothing to fold
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);        // ascending order of doubles == ascending order of keys
 }
 // digit of entry `idx` (edge idx >> 1, side idx & 1) for pass `pass`: passes 0..7 = timestamp bytes, 8.. = owner bytes
@@ -149,6 +150,20 @@ __global__ void csr_merge_kernel(const int64_t* __restrict__ optr, const int32_t
 
 int64_t tiles_of(int64_t n) { return pfo_ceil_div(n, RS_TILE); }
 
+// what pfo_csr_build launches for (E, n_nodes): the grid of a radix pass, the length of its histogram scan and the owner
+// passes behind the eight timestamp passes.  pfo_csr_build, its workspace size and pfo_debug_csr_build_plan all read this.
+struct BuildPlan { int64_t tiles, hist_n; int owner_passes; };
+BuildPlan build_plan_of(int64_t E, int64_t n_nodes) {
+  BuildPlan p;
+  p.tiles = std::max<int64_t>(1, tiles_of(2 * E));
+  p.hist_n = 256 * p.tiles;
+  int owner_bits = 1;
+  while (((int64_t)1 << owner_bits) < n_nodes) ++owner_bits;
+  p.owner_passes = (owner_bits + 7) / 8;
+  return p;
+}
+bool build_sizes_ok(int64_t E, int64_t n_nodes) { return E >= 0 && n_nodes > 0 && 2 * E < ((int64_t)1 << 31); }
+
 // retention: first_kept[v] = the first position of row v with ts >= cutoff (fp64, strict <: a tie group at the cutoff stays
 // whole); the value scanned is the row's kept count
 struct ExpireCount {
@@ -184,8 +199,7 @@ __global__ void csr_expire_copy_kernel(const int64_t* __restrict__ optr, const i
 
 extern "C" int64_t pfo_csr_build_workspace_bytes(int64_t E, int64_t n_nodes) {
   if (E < 0 || n_nodes <= 0) return -1;
-  const int64_t n = 2 * E, nt = std::max<int64_t>(1, tiles_of(n));
-  const int64_t hist = 256 * nt;
+  const int64_t n = 2 * E, hist = build_plan_of(E, n_nodes).hist_n;
   int64_t b = 0;
   b += 2 * pfo_align_up(n * 4, 256);                                   // two permutation buffers
   b += 2 * pfo_align_up(hist * 4, 256);                                // tile histograms and their scan
@@ -198,10 +212,11 @@ extern "C" int64_t pfo_csr_build_workspace_bytes(int64_t E, int64_t n_nodes) {
 extern "C" int pfo_csr_build(const int32_t* src, const int32_t* dst, const int32_t* eidx, const double* ts, int64_t E,
                              int64_t n_nodes, int64_t* indptr, int32_t* adj_nbr, int32_t* adj_eidx, double* adj_ts,
                              void* workspace, int64_t workspace_bytes, void* stream) {
-  PFO_REQUIRE(E >= 0 && n_nodes > 0 && 2 * E < ((int64_t)1 << 31), "bad sizes (2E must fit in int32)");
+  PFO_REQUIRE(build_sizes_ok(E, n_nodes), "bad sizes (2E must fit in int32)");
   PFO_REQUIRE(indptr && workspace && workspace_bytes >= pfo_csr_build_workspace_bytes(E, n_nodes), "null / short workspace");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t n = 2 * E, nt = std::max<int64_t>(1, tiles_of(n)), hist_n = 256 * nt;
+  const BuildPlan plan = build_plan_of(E, n_nodes);
+  const int64_t n = 2 * E, nt = plan.tiles, hist_n = plan.hist_n;
   char* p = reinterpret_cast<char*>(workspace);
   auto take = [&](int64_t bytes) { char* r = p; p += pfo_align_up(bytes, 256); return r; };
   int32_t* perm[2] = {(int32_t*)take(n * 4), (int32_t*)take(n * 4)};
@@ -236,14 +251,22 @@ extern "C" int pfo_csr_build(const int32_t* src, const int32_t* dst, const int32
   for (int b = 0; b < 8; ++b)
     if (int rc = pass(0, 8 * b, unsorted)) return rc;
   // when skipped, the data still sits in perm[0] and cur == 0 again after eight swaps: consistent either way
-  int owner_bits = 1;
-  while (((int64_t)1 << owner_bits) < n_nodes) ++owner_bits;
-  for (int b = 0; b * 8 < owner_bits; ++b)
+  for (int b = 0; b < plan.owner_passes; ++b)
     if (int rc = pass(1, 8 * b, nullptr)) return rc;
   PFO_KLAUNCH(owner_count_kernel, dim3(blk), dim3(256), 0, s, g, n, n_nodes, cnt);
   if (int rc = pfo_iscan_launch(cnt, n_nodes + 1, ptr32, scratch, s)) return rc;
   PFO_KLAUNCH(csr_emit_kernel, dim3(blk), dim3(256), 0, s, g, perm[cur], n, ptr32, n_nodes, indptr, adj_nbr, adj_eidx, adj_ts);
   PFO_LAUNCH_CHECK();
+  return PFO_OK;
+}
+
+extern "C" int pfo_debug_csr_build_plan(int64_t E, int64_t n_nodes, int32_t* out) {
+  PFO_REQUIRE(build_sizes_ok(E, n_nodes), "bad sizes (2E must fit in int32)");
+  PFO_REQUIRE(out, "null output");
+  const BuildPlan plan = build_plan_of(E, n_nodes);
+  out[0] = (int32_t)plan.tiles;
+  out[1] = plan.owner_passes;
+  out[2] = pfo_scan_sweeps(plan.hist_n);             // of the scan pfo_iscan_launch runs over the tile histograms in every pass
   return PFO_OK;
 }
 

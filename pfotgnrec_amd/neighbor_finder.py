@@ -55,6 +55,7 @@ def build_csr_device(sources, destinations, edge_idxs, timestamps, device, max_n
     csrc/csr.hip): the reference's Python build takes 3.8 s per million edges, the host lexsort ~1 s, this milliseconds.
     Returns device tensors (indptr i64[n+1], nbr i32[2E], eidx i32[2E], ts f64[2E])."""
     import torch
+    _check_timestamps(timestamps)
     _lib.require_gpu(device)
     dev = torch.device(device)
     t = lambda a, dt: torch.as_tensor(np.ascontiguousarray(np.asarray(a)), dtype=dt, device=dev).contiguous()
@@ -77,6 +78,16 @@ def _check_ids(sources, destinations, max_node_idx):
     hi = max(int(np.max(sources)), int(np.max(destinations)))
     if lo < 0 or hi > max_node_idx:
         raise ValueError("node ids must lie in [0, %d]: found %d .. %d" % (max_node_idx, lo, hi))
+
+
+def _check_timestamps(timestamps):
+    """Rows are searched by timestamp ever after: a NaN has no place in that order (the device check for a chronological log
+    cannot see it, and the radix key of a NaN depends on its sign bit), so it is refused here, before anything reaches the
+    device.  Infinities order like any other value and stay legal."""
+    ts = np.asarray(timestamps, np.float64)
+    bad = np.flatnonzero(np.isnan(ts))
+    if len(bad):
+        raise ValueError("timestamps must not be NaN: %d found, the first at position %d" % (len(bad), int(bad[0])))
 
 
 def _csr_build_native(src, dst, eid, ts, n_nodes, dev):
@@ -189,6 +200,7 @@ class NeighborFinder:
         every older entry with the same timestamp.  The new edges are sorted on the device (``pfo_csr_build``) and merged
         row by row (``pfo_csr_append``); node ids beyond the current table grow it."""
         import torch
+        _check_timestamps(timestamps)
         _lib.require_gpu(device)
         if device is None:
             device = next(iter(self._dev)) if self._dev else "cuda"

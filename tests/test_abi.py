@@ -149,6 +149,11 @@ def _memory_refusals():
         ("fold-short-scratch", "pfo_debug_fold_parts", fold(scratch=32 * 65 - 1), "short scratch"),
         ("fold-null-tickets", "pfo_debug_fold_parts", fold(tickets=None), "null argument"),
         ("fold-no-output", "pfo_debug_fold_parts", fold(out=None), "null argument"),
+        # ... and of the graph side's plan query (host only: its array is a HOST array, there is no stream argument)
+        ("csr-plan-negative-edges", "pfo_debug_csr_build_plan", [-1, 5, (C.c_int32 * 3)()], "bad sizes"),
+        ("csr-plan-no-nodes", "pfo_debug_csr_build_plan", [5, 0, (C.c_int32 * 3)()], "bad sizes"),
+        ("csr-plan-too-many-entries", "pfo_debug_csr_build_plan", [1 << 30, 5, (C.c_int32 * 3)()], "must fit in int32"),
+        ("csr-plan-null-output", "pfo_debug_csr_build_plan", [5, 5, None], "null output"),
     ]
 
 
