@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.environ.get("PFO_CSRC") or os.path.join(HERE, "csrc")     # override: A/B build of another checkout's kernels
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpfotgn.so")
-SOURCES = ["sampler.hip", "gemm.hip", "attn.hip", "memory.hip", "misc.hip", "csr.hip", "tgn.hip", "eval.hip", "backtest.hip", "recommend.hip", "ingest.hip",
+SOURCES = ["sampler.hip", "gemm.hip", "gemm_f32.hip", "gemm_bx.hip", "gemm_tn_bx.hip", "gemm_fused.hip", "bimg.hip", "attn.hip", "memory.hip", "misc.hip", "csr.hip", "tgn.hip", "eval.hip", "backtest.hip", "recommend.hip", "ingest.hip",
            "holdings.hip", "prices.hip", "optim.hip", "probe.hip"]
 ARCH = "gfx950"
 
@@ -48,7 +48,7 @@ def build(force=False, verbose=False, defines=(), tag=""):
             subprocess.check_call(cmd)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16, os.cpu_count() or 1)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     if force or _newer(lib, objs):
         cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=" + ARCH, "-o", lib] + objs

@@ -1,4 +1,4 @@
-// Internal interface of the fp32 MFMA contraction (gemm.hip).
+// Internal interface of the fp32 contraction: gemm.hip dispatches, the kernels live one family per file (gemm_dev.hpp).
 #pragma once
 #include "common.hpp"
 
@@ -72,7 +72,7 @@ struct PfoGruFused {
 };
 int pfo_gru_fused_launch(const PfoGruFused& f, hipStream_t stream);
 
-// The MLP message function of cap_rows (device count n_rows) rows in one launch (gemm.hip msg_mlp_fwd_kernel):
+// The MLP message function of cap_rows (device count n_rows) rows in one launch (gemm_fused.hip msg_mlp_fwd_kernel):
 // hid = relu(raw W1^T + b1), msg_out = hid W2^T + b2, W1 [Hm, Mr] and W2 [Md, Hm] as plain pfo_bimg_launch images.
 // touched != null: raw / hm are the FULL per-node tables and row m is node touched[m]; null: packed rows.  Rows with hm == 0 are
 // not read and give zeros.  hid [cap_rows, Hm] is written only when given; msg_out [cap_rows, Md] always.  Rows >= n_rows and

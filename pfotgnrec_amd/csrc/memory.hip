@@ -529,7 +529,7 @@ int pfo_pack_remap_launch(const float* msg_table, int M, const float* memory, in
   return PFO_OK;
 }
 
-// GRU backward, gate part (torch.nn.GRUCell): from d h' and the gates the fused forward kept (gemm.hip gru_fused_kernel:
+// GRU backward, gate part (torch.nn.GRUCell): from d h' and the gates the fused forward kept (gemm_fused.hip gru_fused_kernel:
 // gates[s] = r | z | n | gh_n) to the gradients of the two pre-activation blocks, d gi = (dr', dz', dn'), d gh = (dr', dz', dn' r)
 // - the A operands of the GRU's weight-gradient launch.  d h' = the key-side rows the attention scattered (n_rep float replicas,
 // or ONE int64 fixed-point table in deterministic mode) + d_extra (the rows' query-side gradient, already summed per row).

@@ -34,7 +34,7 @@ struct LayerWs {
   float *T1, *tq, *Wqk_f, *cqk_f, *W1ovT_f, *W1b_f, *b1_f;
   float *dT1, *dWqk_f, *gqk_f, *dW1ovT_f, *dW1b_f, *db1_f, *fold_slabs, *fold_vslabs;
   uint8_t* inv;
-  // pre-split bf16x3 images of the weight operands of the large contractions (gemm.hpp PfoBimg): per step, side stream
+  // pre-split images of the weight operands of the large contractions (gemm.hpp PfoBimg): per step, side stream
   void *iWqk, *iWqkT, *iW1ov, *iW1ovT, *iW1b, *iW1bT, *iW2, *iW2T;
 };
 struct Ws {
@@ -696,7 +696,7 @@ static int prepare_pack(const Step& S, hipStream_t s) {
 // optimizer).  Stage A: cos(b), the composite weights of every layer and the weight images layer 1 and the top layer's fc2
 // need.  Stage B ("fc2 fold"): the composites of the layers >= 2 with the fc2 of the layer below folded in, and their images.
 static int build_gru_images(const pfo_tgn_config* c, const Dims& d, const Ws& w, const Params& P, hipStream_t s, bool forward_only = false) {
-  // gate-ordered rows: r | z | n_i | n_h per 16 hidden units (gemm.hip gru_fused_kernel)
+  // gate-ordered rows: r | z | n_i | n_h per 16 hidden units (gemm_fused.hip gru_fused_kernel)
   const int D = d.D;
   PfoBimg im[2];
   im[0].src = P.w_ih; im[0].ld = d.Mg; im[0].N = 3 * D; im[0].K = d.Mg; im[0].trans = 0; im[0].dst = w.iWih;
@@ -1065,7 +1065,7 @@ extern "C" int pfo_tgn_forward(const pfo_tgn_config* c, const pfo_tgn_state* st,
   PFO_MARK("fwd.compacted", s);
   if (c->use_memory) {
     PfoRange range_gru("forward lazy GRU");
-    // both GRU contractions and the gate math in ONE launch (gemm.hip gru_fused_kernel): gi / gh never exist in HBM
+    // both GRU contractions and the gate math in ONE launch (gemm_fused.hip gru_fused_kernel): gi / gh never exist in HBM
     const bool mlp = S.d.Hm > 0;
     if (mlp) {
       RUN(message_mlp(S.d, S.P, S.pack_side ? st->msg_table : w.msg_rows, S.pack_side ? w.touched : nullptr, w.iMW1, w.iMW2,

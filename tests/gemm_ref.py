@@ -19,7 +19,7 @@ def wide(rs, *shape):
 def tn_scale_floor(X, col_block, k_tile=32, floor=2.0 ** -14):
     """max(|x_kc|, floor * S(k, block(c))) with S = the largest magnitude of the operand's column block over every row up to
     the end of k's tile: an upper bound of the ONE running scale the weight-gradient tile keeps per operand, workgroup tile
-    (128 columns of A, 176 of B: gemm.hip BM / BN) and K-slab (a slab starts later than row 0, so its running maximum is at
+    (128 columns of A, 176 of B: gemm_dev.hpp BM / BN) and K-slab (a slab starts later than row 0, so its running maximum is at
     most this one).  ``floor``: 2^-16 of the scaled top, which sits up to HX_GROW = 2 binades above the maximum."""
     K, C = X.shape
     out = np.abs(X).astype(np.float64)
