@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.environ.get("PFO_CSRC") or os.path.join(HERE, "csrc")     # override: A/B build of another checkout's kernels
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpfotgn.so")
-SOURCES = ["sampler.hip", "gemm.hip", "gemm_f32.hip", "gemm_bx.hip", "gemm_tn_bx.hip", "gemm_fused.hip", "bimg.hip", "attn.hip", "memory.hip", "misc.hip", "csr.hip", "tgn.hip", "eval.hip", "backtest.hip", "recommend.hip", "ingest.hip",
+SOURCES = ["sampler.hip", "gemm.hip", "gemm_f32.hip", "gemm_bx.hip", "gemm_tn_bx.hip", "gemm_fused.hip", "bimg.hip", "attn.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_runs.hip", "memory.hip", "misc.hip", "csr.hip", "tgn.hip", "eval.hip", "backtest.hip", "recommend.hip", "ingest.hip",
            "holdings.hip", "prices.hip", "optim.hip", "probe.hip"]
 ARCH = "gfx950"
 

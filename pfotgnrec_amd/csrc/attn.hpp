@@ -1,4 +1,5 @@
-// Internal interface of the neighbour-tile attention kernels (attn.hip).
+// Internal interface of the neighbour-tile attention kernels (attn.hip dispatches; the kernels: attn_fwd.hip, attn_bwd.hip,
+// attn_bwd_runs.hip).
 #pragma once
 #include "common.hpp"
 

@@ -78,7 +78,8 @@ struct PfoRange {
   PfoRange& operator=(const PfoRange&) = delete;
 };
 
-// per-TU clock accumulators (attn.hip, gemm_tn_bx.hip), read by misc.hip's pfo_shader_clock
+// per-TU clock accumulators (attn_fwd.hip and attn_bwd_runs.hip, joined by attn.hip; gemm_tn_bx.hip), read by misc.hip's
+// pfo_shader_clock
 int pfo_attn_clock_read(double* cycles_ticks /* [2 kernels][2] */, int reset);
 int pfo_gemm_clock_read(double* cycles_ticks /* [1 kernel][2] */, int reset);
 

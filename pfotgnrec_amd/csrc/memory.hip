@@ -239,7 +239,7 @@ int pfo_seg_build_launch(const int32_t* idx, const int32_t* nodes, int N, int ca
 // groups without members get zeros.  One wavefront per group, fixed member order -> reproducible.
 #define SEGSUM_R 16
 // src0_live (optional, with src0_by_position): byte flags per position - a row whose flag is 0 holds nothing (its producer
-// folded it into a later row of the same group, attn.hip) and is not read
+// folded it into a later row of the same group, attn_bwd_runs.hip) and is not read
 __global__ __launch_bounds__(256) void segsum_kernel(const float* __restrict__ src0, int W0, const float* __restrict__ src1, int W1,
                                                      const int32_t* __restrict__ seg_ptr, const int32_t* __restrict__ members,
                                                      const int32_t* __restrict__ n_rows, int src0_by_position,

@@ -56,7 +56,7 @@ struct Ws {
   float *QX, *Dq, *dx_tab, *l1_bias;
   void* iQX;
   int32_t *seg_ptr, *seg_cur, *seg_tmp, *seg_mem, *seg_of, *seg_scratch;
-  uint8_t* dqk_live;           // per layer-1 member position: does dQK row m hold a sum (attn.hip, run-merged backward)
+  uint8_t* dqk_live;           // per layer-1 member position: does dQK row m hold a sum (attn_bwd_runs.hip)
   int32_t* cnt1;               // per layer-1 instance: entries of its node's row before its time (the run key, sampler.hip)
   LayerWs layer[PFO_MAX_LAYERS + 1];
   float *dh1, *dctx, *dQK;
@@ -206,7 +206,7 @@ Ws carve(const pfo_tgn_config* c, void* base, void* cache = nullptr, bool cached
     w.gh = k.ws<float>(d.capP * 3 * d.D);
     w.gates = k.ws<float>(d.capP * 4 * d.D);
     w.upd_mem = k.ws<float>(d.capP * d.D);
-    w.d_h0 = k.ws<float>(PFO_GRAD_REPLICAS * d.capP * d.D);     // one replica per XCD (attn.hip, DMODE 1)
+    w.d_h0 = k.ws<float>(PFO_GRAD_REPLICAS * d.capP * d.D);     // one replica per XCD (attn_bwd.hip, DMODE 1)
     w.msg_rows = k.ws<float>(d.capP * d.M);
     w.h_rows = k.ws<float>(d.capP * d.D);
     w.hm = k.ws<uint8_t>(d.capP);
@@ -1212,7 +1212,7 @@ static int backward_attn(Step& S, LayerBack& lb) {
   int n_parts = 0;
   if (l == 1 && c->use_memory && !S.seg_fwd) HIPOK(hipStreamWaitEvent(s, S.sd.seg_done, 0), "event wait failed");   // d_h0 is clear, the groups exist
   if (l == 1 && c->use_memory && !b->uniform) {
-    // key-side gradients of instances with identical neighbour lists leave as one set of atomics (attn.hip)
+    // key-side gradients of instances with identical neighbour lists leave as one set of atomics (attn_bwd_runs.hip)
     a.members = w.seg_mem; a.seg_ptr = w.seg_ptr; a.n_rows = w.n_core; a.run_cnt = w.cnt1; a.dqk_live = w.dqk_live;
   }
   lb.dqk_by_member = pfo_attn_bwd_uses_runs(a) ? 1 : 0;

@@ -21,7 +21,7 @@ f32, f64 = np.float32, np.float64
 ATTN_MARGIN = 8.0
 EPS_FLOOR = 2.0 ** -23
 DET_SCALE = 2.0 ** 40
-RUN_CHUNK = 4            # attn.hip: members a wavefront of the run-merged kernel walks
+RUN_CHUNK = 4            # attn_dev.hpp: members a wavefront of the run-merged kernel walks
 FORMS = ["fwd_ring", "fwd_reg", "bwd_runs", "bwd_ring_none", "bwd_ring_direct", "bwd_none", "bwd_atomic", "bwd_det", "bwd_direct"]
 
 PERTURBATIONS = ["drop_last_key", "no_dsb", "no_keep_scale_cA", "no_scale_key_side", "time_col_off", "shift_off", "no_relu",

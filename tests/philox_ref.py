@@ -1,6 +1,6 @@
 """Host model of the library's random streams: Philox4x32-10 and the three consumers that turn its words into decisions
 (uniform neighbour positions, the candidate / negative draw, the attention dropout keep bits).  Numpy only, no import of the
-package: written from the kernel text (csrc/common.hpp ``pfo_philox``, csrc/sampler.hip, csrc/attn.hip ``attn_keep_bits``),
+package: written from the kernel text (csrc/common.hpp ``pfo_philox``, csrc/sampler.hip, csrc/attn_dev.hpp ``attn_keep_bits``),
 vectorised in uint64.  All three consumers are pure functions of integers, so the kernels are held to this bit for bit.
 
 | consumer                 | counter (lo, hi)              | word -> decision                                                    |

@@ -123,7 +123,7 @@ def test_run_merged_layout_equals_group_sums(name, kw):
 
 
 def model_live(p, members, seg_of):
-    """The live flags the run-merged kernel produces (attn.hip attn_bwd_runs_kernel), for the layout test only: a sum is stored
+    """The live flags the run-merged kernel produces (attn_bwd_runs.hip attn_bwd_runs_kernel), for the layout test only: a sum is stored
     at the last member WITH a neighbour before the row changes, the count steps by more than 64 - K from the run's first, or
     the chunk of four positions ends."""
     M, K = len(members), p["K"]
