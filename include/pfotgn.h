@@ -423,6 +423,43 @@ int pfo_recommend_basket_topk(const float* user_emb, const float* item_emb, cons
                               int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The list form of the two top-k entries (abi 6, additive): every user ranks a list of its OWN, not the shared candidate list
+ * minus an exclusion list.  user_emb, item_emb, user_block, U, I, n_t, D, item_ok, k and the mean-variance arguments mean what
+ * they mean in pfo_recommend_topk / pfo_recommend_mv_topk; the exclusion triple gives way to
+ *   list_pos i32[U, list_stride], list_len i32[U]: candidate POSITIONS into the I candidates of a block.
+ *   Admissible set A(u): the DISTINCT positions p among the first min(max(list_len[u], 0), list_stride) entries of row u with
+ *   0 <= p < I and (item_ok == NULL || item_ok[p] != 0); in the mean-variance form also with a y (day and cand_stock inside the
+ *   tables, y not NaN: pfo_recommend_mv_topk's rule).  Entries outside [0, I) are ignored (the -1 padding, a holding that is
+ *   not among the candidates); a position named more than once counts once, for the selection and for both ranks; an empty list
+ *   gives an empty answer.
+ *   score(u, p) = user_emb[u] . item_emb[user_block[u]*I + p] in fp32 - four partial sums per lane, then across four lanes, NOT
+ *   the matrix-core order of pfo_recommend_topk: a score is within the any-order fp32 dot-product bound of the exact value and
+ *   equals pfo_recommend_topk's only where both are exact.  The two list entries compute the same score to the bit.
+ *   Order, -0 == +0, empty slots (-1 / -inf / -inf), n_valid = min(k, |A(u)|), a zero score as +0, y (pfo_recommend_mv_topk's
+ *   arithmetic), the average-tie ranks over A(u) and the blend: as in pfo_recommend_topk / pfo_recommend_mv_topk.  The portfolio
+ *   is used as given: a list of a user's own holdings is ranked against those holdings, itself among them.
+ *   Diagnostics, each optional, BY LIST SLOT: score_out f32[U, list_stride], y_out / fused_out f64[U, list_stride]; NaN in every
+ *   slot that is not the first occurrence of an admissible position.
+ *   Bounds, all checked before any pointer is looked at (PFO_ERR_INVALID, nothing queued): D % 4 == 0, D <= 256, 1 <= k <= 64,
+ *   1 <= I <= PFO_RECOMMEND_MAX_ITEMS (no 2048 here: only the list is ranked), 1 <= n_t,
+ *   1 <= list_stride <= PFO_RECOMMEND_LIST_MAX_WIDTH, 2 <= n_ret <= 128, port_stride >= 0.  U == 0: PFO_OK, no pointer is
+ *   looked at.  One launch, one wavefront per user; the users need not be sorted by block.  W D multiply-adds and about 3 W^2
+ *   comparisons (mean-variance form) per user, W = the list's length.
+ */
+#define PFO_RECOMMEND_LIST_MAX_WIDTH 256
+int pfo_recommend_list_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                            int32_t n_t, int32_t D, const int32_t* list_pos, const int32_t* list_len, int32_t list_stride,
+                            const uint8_t* item_ok, int32_t k, int32_t* top_pos, float* top_score, int32_t* n_valid,
+                            float* score_out, void* stream);
+int pfo_recommend_list_mv_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                               int32_t n_t, int32_t D, const int32_t* list_pos, const int32_t* list_len, int32_t list_stride,
+                               const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                               int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                               const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                               int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                               double* y_out, double* fused_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Time-sorted adjacency built on the device: replaces get_neighbor_finder / NeighborFinder.__init__ (utils/utils.py:117-148).
  * Every edge e contributes (dst, eidx, ts) to row src[e] and (src, eidx, ts) to row dst[e]; rows are sorted by timestamp,
  * ties in edge order (Python's stable sorted(key=ts), utils.py:139).  A stable LSD radix sort of the 2E entries; the eight

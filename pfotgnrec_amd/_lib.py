@@ -16,6 +16,7 @@ MAX_LAYERS = 4
 RECOMMEND_MAX_ITEMS = 65536     # PFO_RECOMMEND_MAX_ITEMS
 RECOMMEND_MV_MAX_ITEMS = 2048   # PFO_RECOMMEND_MV_MAX_ITEMS
 RECOMMEND_MV_WIDE_MAX_ITEMS = 65536   # PFO_RECOMMEND_MV_WIDE_MAX_ITEMS
+RECOMMEND_LIST_MAX_WIDTH = 256  # PFO_RECOMMEND_LIST_MAX_WIDTH
 EVAL_RANK_NONE = (1 << 31) - 1  # PFO_EVAL_RANK_NONE: the positive is not ranked
 ADAM_MAX_RANGES = 16            # PFO_ADAM_MAX_RANGES
 GRAD_NORM_PARTS = 256           # PFO_GRAD_NORM_PARTS
@@ -179,6 +180,11 @@ PROTOTYPES = {
     "pfo_recommend_basket_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                             _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double,
                                             C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_list_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                          C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_list_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                             _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
+                                             C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_adam_step": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                 _VP]),
     "pfo_csr_build_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),

@@ -26,7 +26,9 @@
 // check per argument block (rec_check_common, rec_check_mv) and one launcher (rec_launch: the NJ dispatch, the LDS attribute,
 // the launch and its check) serve the three entries.  Behind the three kernels stands the wide form of the mean-variance one
 // (two kernels over a workspace, ranks by sorting: its own comment), which shares the opening, stage A, RecMvUser, the rec_mv_*
-// pieces and the host checks with them.
+// pieces and the host checks with them.  Last, the list form (every user ranks a list of its own, one wavefront per user: its
+// own comment) takes the key, rec_better, RecMvUser, rec_mv_stock, the empty-slot tail, the host checks and the launcher from
+// here and nothing of stage A: a gathered row is no tile.
 #include "common.hpp"
 #include "mv_value.hpp"
 #include <algorithm>
@@ -915,6 +917,240 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_wide_rank_kernel
 }
 
 // ---------------------------------------------------------------------------------------------
+// The list form: every user ranks a list of its own - list_pos[u, 0:list_len[u]], at most PFO_RECOMMEND_LIST_MAX_WIDTH candidate
+// positions - by score or in the mean-variance order (MV), in one launch.  W D multiply-adds per user instead of I D, and I is
+// bounded by nothing but the position's 31 bits: only the list is scored and ranked.
+// One wavefront per user, four users per workgroup; everything a user needs lives in its wavefront's quarter of LDS (slot s of
+// the list belongs to lane s & 63).  The wavefronts of a workgroup share nothing but the barriers, which stand outside every
+// data-dependent branch (a wavefront beyond U walks through them with an empty list).
+//   1  staging.  The row into LDS, -1 where the entry counts for nothing (beyond the length, outside [0, I), item_ok); then each
+//      lane settles "first occurrence" for its at most four slots by a walk over the entries before them - a position named twice
+//      counts once, for the selection and for both ranks.  MV: y of the slot in fp64 by the slot's lane (RecMvUser, rec_mv_stock,
+//      pfo_mv_value<true>: the bounded kernel's calls), a NaN y leaves the list as well.
+//   2  scores.  Sixteen slots a pass, four lanes per candidate row: lane (c, q) reads 16-byte pieces q, q + 4, ... of the row of
+//      slot 16 t + c and holds the same pieces of the user row in registers; four fp32 partial sums per lane (fmaf), added, then
+//      across the four lanes.  NOT the matrix-core order of rec_score_tile: the contract of a score here is the any-order fp32
+//      dot-product bound, and both forms of this kernel run this one sequence, so they agree with each other to the bit.
+//   3  plain: k rounds of a wave-wide maximum over the 64-bit keys (rec_ordered | position), as recommend_topk_kernel.
+//      MV: average-tie ranks of y and of the score by counting over the list in LDS (NaN where a slot is out: every comparison
+//      is false), pfo_mv_blend, and each slot's place by counting once more (rec_better); places below k write the output row.
+// LDS: 2 KB per user (positions, scores), MV 4 KB more (y, fused): 8 / 24 KB a workgroup.
+#define PFO_RL_USERS (PFO_REC_THREADS / 64)                  // users per workgroup
+#define PFO_RL_SLOTS (PFO_RECOMMEND_LIST_MAX_WIDTH / 64)     // list slots per lane
+
+struct RecListArgs {
+  const int32_t *list_pos, *list_len;
+  int list_stride;
+};
+
+template <int NJ, bool MV>
+__device__ __forceinline__ void recommend_list_body(const RecArgs& a, const RecMvArgs& m, const RecListArgs& l, PFO_REC_MV_TABLES) {
+  const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
+  const int32_t* __restrict__ list_pos = l.list_pos;
+  const uint8_t* __restrict__ item_ok = a.item_ok;
+  int32_t* __restrict__ top_pos = a.top_pos;
+  float *__restrict__ top_score = a.top_score, *__restrict__ score_out = m.score_out;
+  const int I = a.I, D = a.D, k = a.k, W = l.list_stride;
+  constexpr int LW = PFO_RECOMMEND_LIST_MAX_WIDTH;
+  __shared__ int lp[PFO_RL_USERS][LW];                               // the position of a slot, -1: the slot is out
+  __shared__ float ls[PFO_RL_USERS][LW];                             // its score (NaN where it is out)
+  __shared__ double ly[MV ? PFO_RL_USERS : 1][MV ? LW : 1];          // its y
+  __shared__ double lf[MV ? PFO_RL_USERS : 1][MV ? LW : 1];          // its fused
+  __shared__ int n_of[PFO_RL_USERS];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int64_t u_first = ((int64_t)blockIdx.x * gridDim.y + blockIdx.y) * PFO_RL_USERS, u = u_first + wave;
+  const bool live = u < a.U;
+  const int64_t ur = live ? u : a.U - 1;                             // (the row a wavefront beyond U reads; it writes nothing)
+  int* const wp = lp[wave];
+  float* const ws = ls[wave];
+  const float nanf = __builtin_nanf("");
+
+  // this lane's pieces of the user row: 16-byte pieces q, q + 4, ... (NJ of them cover D <= 16 NJ floats)
+  const int q = lane & 3;
+  float4 uf[NJ];
+  {
+    const float4* up = reinterpret_cast<const float4*>(user_emb + ur * D);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) uf[j] = 16 * j + 4 * q < D ? up[4 * j + q] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const int b = a.user_block ? min(max(a.user_block[ur], 0), a.n_t - 1) : 0;
+  const float* items = item_emb + (int64_t)b * I * D;
+
+  // ---- 1: the list
+  const int n = live ? min(max(l.list_len[u], 0), W) : 0;
+  int mine[PFO_RL_SLOTS];
+#pragma unroll
+  for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4) {
+    const int s = lane + 64 * s4;
+    int p = -1;
+    if (s < n) {
+      p = list_pos[u * W + s];
+      if (p < 0 || p >= I || (item_ok && !item_ok[p])) p = -1;
+    }
+    mine[s4] = p;
+    wp[s] = p;
+  }
+  __syncthreads();
+  {
+    unsigned dup = 0;                                                // bit s4: an earlier slot names the same position
+    for (int j = 0; j < n; ++j) {
+      const int pj = wp[j];
+#pragma unroll
+      for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4) dup |= (pj == mine[s4] && j < lane + 64 * s4 ? 1u : 0u) << s4;
+    }
+#pragma unroll
+    for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4)
+      if ((dup >> s4) & 1u) mine[s4] = -1;
+  }
+  double yv[PFO_RL_SLOTS];
+  if constexpr (MV) {
+    const RecMvUser h(m, returns, day_idx, port_idx, port_len, ur);
+#pragma unroll
+    for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4) {
+      yv[s4] = __builtin_nan("");
+      if (mine[s4] < 0) continue;
+      const int stock = rec_mv_stock(a, cand_stock, m.n_stocks, mine[s4], h.day_ok);
+      if (stock >= 0) yv[s4] = pfo_mv_value<true>(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + ur * m.port_stride, h.plen, m.gamma);
+      if (!(yv[s4] == yv[s4])) mine[s4] = -1;
+    }
+  }
+  __syncthreads();                                                   // every entry of the row has been compared
+#pragma unroll
+  for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4) {
+    const int s = lane + 64 * s4;
+    wp[s] = mine[s4];
+    if constexpr (MV) ly[wave][s] = yv[s4];
+  }
+  __syncthreads();
+
+  // ---- 2: scores, sixteen slots a pass
+  for (int s0 = 0; s0 < n; s0 += 16) {
+    const int s = s0 + (lane >> 2);                                  // (s0 <= 240: inside the row)
+    const int p = wp[s];
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (p >= 0) {
+      const float4* ip = reinterpret_cast<const float4*>(items + (int64_t)p * D);
+      float4 v[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) v[j] = 16 * j + 4 * q < D ? ip[4 * j + q] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        acc.x = fmaf(uf[j].x, v[j].x, acc.x);
+        acc.y = fmaf(uf[j].y, v[j].y, acc.y);
+        acc.z = fmaf(uf[j].z, v[j].z, acc.z);
+        acc.w = fmaf(uf[j].w, v[j].w, acc.w);
+      }
+    }
+    float sum = (acc.x + acc.y) + (acc.z + acc.w);
+    sum += __shfl_xor(sum, 1, 64);
+    sum += __shfl_xor(sum, 2, 64);
+    if (q == 0) ws[s] = p >= 0 ? sum : nanf;
+  }
+  __syncthreads();
+
+  // ---- 3
+  if constexpr (!MV) {
+    unsigned long long key[PFO_RL_SLOTS];
+#pragma unroll
+    for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4) {
+      const int s = lane + 64 * s4;
+      const bool in = mine[s4] >= 0;
+      const float sv = in ? ws[s] : nanf;
+      key[s4] = in ? ((unsigned long long)rec_ordered(sv) << 32) | (unsigned)mine[s4] : 0ull;
+      if (score_out && live && s < W) score_out[u * W + s] = sv;
+    }
+    unsigned long long won = 0ull;                                   // lane t: rank t
+    for (int t = 0; t < k; ++t) {
+      unsigned long long best = key[0];
+#pragma unroll
+      for (int s4 = 1; s4 < PFO_RL_SLOTS; ++s4) best = rec_max(best, key[s4]);
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) best = rec_max(best, __shfl_xor(best, off, 64));
+      if (best == 0ull) break;                                       // (the same for the whole wavefront; no barrier follows)
+      // positions are distinct, so exactly one key of the wavefront equals the winner: its owner clears it
+#pragma unroll
+      for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4)
+        if (key[s4] == best) key[s4] = 0ull;
+      if (lane == t) won = best;
+    }
+    const bool got = lane < k && won != 0ull;
+    const int cnt = __popcll(__ballot(got));
+    if (live) {
+      if (lane < k) {
+        top_pos[u * k + lane] = got ? (int32_t)(uint32_t)(won & 0xffffffffull) : -1;
+        top_score[u * k + lane] = got ? rec_unordered((uint32_t)(won >> 32)) : -__builtin_inff();
+      }
+      if (lane == 0 && a.n_valid) a.n_valid[u] = cnt;
+    }
+  } else {
+    double *__restrict__ top_fused = m.top_fused, *__restrict__ y_out = m.y_out, *__restrict__ fused_out = m.fused_out;
+    const double* wy = ly[wave];
+    double* wf = lf[wave];
+    double fused[PFO_RL_SLOTS];
+    int cnt = 0;
+#pragma unroll
+    for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4) {
+      const int s = lane + 64 * s4;
+      const bool in = mine[s4] >= 0;
+      cnt += __popcll(__ballot(in));
+      fused[s4] = __builtin_nan("");
+      if (in) {
+        const double yi = yv[s4];
+        const float si = ws[s];
+        int ly_ = 0, ey = 0, ls_ = 0, es = 0;
+        for (int j = 0; j < n; ++j) {                                // (a slot that is out holds NaN in both)
+          const double yj = wy[j];
+          const float sj = ws[j];
+          ly_ += (yj < yi);
+          ey += (yj == yi);
+          ls_ += (sj < si);
+          es += (sj == si);                                          // (-0 == +0)
+        }
+        fused[s4] = pfo_mv_blend(pfo_mv_avg_rank(ly_, ey), pfo_mv_avg_rank(ls_, es), m.lam);   // main.py:282-286
+      }
+      wf[s] = fused[s4];
+      if (live && s < W) {
+        if (score_out) score_out[u * W + s] = in ? ws[s] : nanf;
+        if (y_out) y_out[u * W + s] = yv[s4];
+        if (fused_out) fused_out[u * W + s] = fused[s4];
+      }
+    }
+    if (lane == 0) n_of[wave] = min(k, cnt);
+    __syncthreads();
+#pragma unroll
+    for (int s4 = 0; s4 < PFO_RL_SLOTS; ++s4) {
+      const double fi = fused[s4];
+      if (!(fi == fi)) continue;                                     // (out, or a NaN blend: lambda_mv is the caller's)
+      const int c = mine[s4];
+      int before = 0;
+      for (int j = 0; j < n; ++j) {
+        const double fj = wf[j];
+        before += rec_better(fj, wp[j], fi, c);                       // (false for the slot itself, and for a NaN)
+      }
+      if (before < k) {
+        const float sv = ws[lane + 64 * s4];
+        top_pos[u * k + before] = c;
+        top_score[u * k + before] = sv == 0.f ? 0.f : sv;            // a zero score is handed out as +0
+        top_fused[u * k + before] = fi;
+      }
+    }
+    for (int w = 0; w < PFO_RL_USERS; ++w)                           // the tail of each user's row, by the whole workgroup
+      if (u_first + w < a.U) rec_mv_empty_slots(top_pos, top_score, top_fused, a.n_valid, u_first + w, k, n_of[w]);
+  }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_list_topk_kernel(const RecArgs a, const RecMvArgs m, const RecListArgs l,
+                                                                              PFO_REC_MV_TABLES) {
+  recommend_list_body<NJ, false>(a, m, l, cand_stock, returns, day_idx, port_idx, port_len);
+}
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_list_mv_topk_kernel(const RecArgs a, const RecMvArgs m, const RecListArgs l,
+                                                                                 PFO_REC_MV_TABLES) {
+  recommend_list_body<NJ, true>(a, m, l, cand_stock, returns, day_idx, port_idx, port_len);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Host side.  The checks speak in the name of the entry that called them (`who`), as PFO_REQUIRE does with __func__.
 #define PFO_REC_REQUIRE(cond, msg) \
   do { if (!(cond)) { pfo_set_error("%s: %s", who, msg); return PFO_ERR_INVALID; } } while (0)
@@ -935,15 +1171,22 @@ int rec_check_common(const char* who, const RecArgs& a, int max_items, const cha
   return PFO_OK;
 }
 
+// the bounds of the mean-variance side (the list form runs them ahead of rec_check_mv too: rec_check_common ends on pointers)
+#define PFO_REC_MV_STRIDE_MSG "excl_stride and port_stride must not be negative"
+int rec_check_mv_bounds(const char* who, const RecMvArgs& m) {
+  PFO_REC_REQUIRE(m.port_stride >= 0, PFO_REC_MV_STRIDE_MSG);
+  PFO_REC_REQUIRE(m.n_ret >= 2 && m.n_ret <= 128, "n_ret must be in [2, 128]");
+  PFO_REC_REQUIRE(m.n_days > 0 && m.n_stocks > 0, "n_days and n_stocks must be positive");
+  return PFO_OK;
+}
+
 // (`max_items` / `items_msg`: the bounded kernels' bound unless the entry names its own)
 int rec_check_mv(const char* who, const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES, int max_items = PFO_RECOMMEND_MV_MAX_ITEMS,
                  const char* items_msg = "I must be in [1, PFO_RECOMMEND_MV_MAX_ITEMS]") {
-  const char* stride_msg = "excl_stride and port_stride must not be negative";
-  const int rc = rec_check_common(who, a, max_items, items_msg, stride_msg);
+  int rc = rec_check_common(who, a, max_items, items_msg, PFO_REC_MV_STRIDE_MSG);
   if (rc != PFO_OK) return rc;
-  PFO_REC_REQUIRE(m.port_stride >= 0, stride_msg);
-  PFO_REC_REQUIRE(m.n_ret >= 2 && m.n_ret <= 128, "n_ret must be in [2, 128]");
-  PFO_REC_REQUIRE(m.n_days > 0 && m.n_stocks > 0, "n_days and n_stocks must be positive");
+  rc = rec_check_mv_bounds(who, m);
+  if (rc != PFO_OK) return rc;
   if (a.U == 0) return PFO_OK;
   PFO_REC_REQUIRE(m.top_fused, "null input or output");
   PFO_REC_REQUIRE(cand_stock && returns && day_idx, "null mean-variance input");
@@ -956,6 +1199,16 @@ int rec_check_wide(const char* who, const RecArgs& a, const void* workspace, int
   PFO_REC_REQUIRE(workspace, "null workspace");
   PFO_REC_REQUIRE(workspace_bytes >= rec_wide_bytes(1, a.I), "workspace shorter than pfo_recommend_mv_wide_workspace_bytes(min(U, 16), I)");
   PFO_REC_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  return PFO_OK;
+}
+
+// the list form's own bound, ahead of the common checks (which end on the pointers), and its rows (U > 0), behind them
+int rec_check_list_stride(const char* who, int list_stride) {
+  PFO_REC_REQUIRE(list_stride >= 1 && list_stride <= PFO_RECOMMEND_LIST_MAX_WIDTH, "list_stride must be in [1, PFO_RECOMMEND_LIST_MAX_WIDTH]");
+  return PFO_OK;
+}
+int rec_check_list_rows(const char* who, const int32_t* list_pos, const int32_t* list_len) {
+  PFO_REC_REQUIRE(list_pos && list_len, "null list_pos or list_len");
   return PFO_OK;
 }
 #undef PFO_REC_REQUIRE
@@ -1111,4 +1364,52 @@ extern "C" int pfo_recommend_mv_topk_wide(const float* user_emb, const float* it
     }
   }
   return PFO_OK;
+}
+
+// The list form has no exclusion side: its RecArgs carry none.  Four users a workgroup, so four workgroups (grid y) to the
+// launcher's 16-user column.
+#define PFO_REC_LIST_ARGS()                                               \
+  const int32_t *excl_pos = nullptr, *excl_len = nullptr;                 \
+  const int32_t excl_stride = 0;                                          \
+  const RecArgs a = PFO_REC_ARGS(0);                                      \
+  const RecListArgs l = {list_pos, list_len, list_stride}
+
+extern "C" int pfo_recommend_list_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                       int32_t n_t, int32_t D, const int32_t* list_pos, const int32_t* list_len, int32_t list_stride,
+                                       const uint8_t* item_ok, int32_t k, int32_t* top_pos, float* top_score, int32_t* n_valid,
+                                       float* score_out, void* stream) {
+  PFO_REC_LIST_ARGS();
+  RecMvArgs m = {};
+  m.score_out = score_out;
+  int rc = rec_check_list_stride(__func__, list_stride);
+  if (rc == PFO_OK)
+    rc = rec_check_common(__func__, a, PFO_RECOMMEND_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MAX_ITEMS]", "excl_stride must not be negative");
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_list_rows(__func__, list_pos, list_len);
+  if (rc != PFO_OK) return rc;
+  const int32_t* none = nullptr;
+  const double* no_returns = nullptr;
+  return rec_launch_grid(__func__, PFO_REC_KERNEL(recommend_list_topk_kernel), 0, PFO_REC_TILE / PFO_RL_USERS, stream, a, m, l, none,
+                         no_returns, none, none, none);
+}
+
+extern "C" int pfo_recommend_list_mv_topk(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                          int32_t n_t, int32_t D, const int32_t* list_pos, const int32_t* list_len, int32_t list_stride,
+                                          const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                          int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                          const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                          int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                          double* y_out, double* fused_out, void* stream) {
+  PFO_REC_LIST_ARGS();
+  const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
+  int rc = rec_check_list_stride(__func__, list_stride);
+  if (rc == PFO_OK) rc = rec_check_mv_bounds(__func__, m);
+  if (rc == PFO_OK)
+    rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len, PFO_RECOMMEND_MAX_ITEMS,
+                      "I must be in [1, PFO_RECOMMEND_MAX_ITEMS]");
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_list_rows(__func__, list_pos, list_len);
+  if (rc != PFO_OK) return rc;
+  return rec_launch_grid(__func__, PFO_REC_KERNEL(recommend_list_mv_topk_kernel), 0, PFO_REC_TILE / PFO_RL_USERS, stream, a, m, l, cand_stock,
+                         returns, day_idx, port_idx, port_len);
 }

@@ -451,18 +451,9 @@ def _recommend_check(user_emb, item_emb, k, user_block, excl_pos, excl_len, item
             excl_pos.contiguous() if W else None, excl_len.contiguous() if W else None, item_ok, U, D, k, I, n_t, W)
 
 
-def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_len=None, item_ok=None, n_blocks=None):
-    """The k best candidates per user in one launch (``pfo_recommend_topk``); nothing but its outputs is written.
-
-    user_emb f32[U,D]; item_emb f32[n_t*I,D]: n_t blocks of the same I candidates (embedded at n_t times); user_block
-    i32[U] in [0,n_t): the block each user is scored against (None: one block).  ``n_blocks`` = n_t; when None it is 1 without
-    ``user_block`` and rows / len(item_ok) with ``item_ok`` - with ``user_block`` alone it must be given.  score(u,i) =
-    user_emb[u] . item_emb[user_block[u]*I + i] in fp32.  Candidate i is skipped for user u when ``item_ok[i] == 0`` (u8 / bool
-    [I]) or when i occurs in ``excl_pos[u, :excl_len[u]]`` (i32[U,W] candidate POSITIONS, entries outside [0,I) ignored;
-    excl_len i32[U], None: the whole row).
-
-    Returns (top_pos i32[U,k], top_score f32[U,k], n_valid i32[U]): score descending, the larger position first among equal
-    scores (SURVEY App. A-9, the order of ``eval_metrics``); slots beyond the admissible candidates hold -1 / -inf."""
+def _score_dims(n_blocks, item_ok, user_block):
+    """``dims`` of ``_recommend_check`` for the score forms: (I, n_t) from the rows of item_emb and ``n_blocks`` - when None, 1
+    without ``user_block`` and rows / len(item_ok) with ``item_ok``."""
     def dims(U, rows):
         n_t = n_blocks
         if n_t is None:
@@ -478,7 +469,22 @@ def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_l
         if rows // n_t > _lib.RECOMMEND_MAX_ITEMS:
             raise ValueError("%d candidates, at most %d" % (rows // n_t, _lib.RECOMMEND_MAX_ITEMS))
         return rows // n_t, n_t
+    return dims
 
+
+def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_len=None, item_ok=None, n_blocks=None):
+    """The k best candidates per user in one launch (``pfo_recommend_topk``); nothing but its outputs is written.
+
+    user_emb f32[U,D]; item_emb f32[n_t*I,D]: n_t blocks of the same I candidates (embedded at n_t times); user_block
+    i32[U] in [0,n_t): the block each user is scored against (None: one block).  ``n_blocks`` = n_t; when None it is 1 without
+    ``user_block`` and rows / len(item_ok) with ``item_ok`` - with ``user_block`` alone it must be given.  score(u,i) =
+    user_emb[u] . item_emb[user_block[u]*I + i] in fp32.  Candidate i is skipped for user u when ``item_ok[i] == 0`` (u8 / bool
+    [I]) or when i occurs in ``excl_pos[u, :excl_len[u]]`` (i32[U,W] candidate POSITIONS, entries outside [0,I) ignored;
+    excl_len i32[U], None: the whole row).
+
+    Returns (top_pos i32[U,k], top_score f32[U,k], n_valid i32[U]): score descending, the larger position first among equal
+    scores (SURVEY App. A-9, the order of ``eval_metrics``); slots beyond the admissible candidates hold -1 / -inf."""
+    dims = _score_dims(n_blocks, item_ok, user_block)
     user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
         user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims)
     dev = user_emb.device
@@ -494,27 +500,17 @@ _NO_WORKSPACE = object()     # ``_recommend_mv_launch``: the symbol takes no wor
 _WIDE_WORKSPACE_CAP = 256 << 20
 
 
-def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
-                         user_block, excl_pos, excl_len, item_ok, n_blocks, max_items=_lib.RECOMMEND_MV_MAX_ITEMS, workspace=_NO_WORKSPACE):
-    """The argument checks, output rows and launch that ``recommend_mv_topk``, ``recommend_mv_topk_wide`` and
-    ``recommend_basket_topk`` share: ``symbol`` takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays
-    (``diagnostics``: allocate them or pass NULL) or without them (None).  ``max_items``: the symbol's bound on I.
-    ``workspace``: for a symbol that takes (workspace, workspace_bytes) before the stream - a uint8 tensor, or None: allocated
-    (what serves all users at once, 256 MiB at the most, the minimum at the least)."""
+def _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, then=None):
+    """``dims`` of ``_recommend_check`` for the mean-variance forms: the checks of their own tensors, (I, n_t) from ``cand_stock``
+    and ``n_blocks``.  ``max_items``: the form's bound on I; ``then(U, I)``: the caller's checks that need I, run behind it."""
     def dims(U, rows):
         if not isinstance(cand_stock, torch.Tensor) or cand_stock.dim() != 1 or cand_stock.dtype != torch.int32 or cand_stock.shape[0] < 1:
             raise ValueError("cand_stock must be int32 [I]")
         I = int(cand_stock.shape[0])
         if I > max_items:
             raise ValueError("%d candidates, at most %d with the mean-variance rank" % (I, max_items))
-        if workspace is not _NO_WORKSPACE and workspace is not None:
-            if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-                raise ValueError("workspace must be a contiguous uint8 tensor")
-            if workspace.device != user_emb.device:
-                raise ValueError("workspace lives on %s, the embeddings on %s" % (workspace.device, user_emb.device))
-            need = _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", min(U, 16), I)
-            if U and workspace.numel() < need:
-                raise ValueError("workspace holds %d bytes, %d users of %d candidates need at least %d" % (workspace.numel(), U, I, need))
+        if then is not None:
+            then(U, I)
         n_t = 1 if n_blocks is None else int(n_blocks)
         if n_t < 1 or rows != n_t * I:
             raise ValueError("item_emb holds %d rows: not n_blocks = %d blocks of %d candidates" % (rows, n_t, I))
@@ -532,6 +528,26 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
         elif port_len is not None:
             raise ValueError("port_len without port_idx")
         return I, n_t
+    return dims
+
+
+def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
+                         user_block, excl_pos, excl_len, item_ok, n_blocks, max_items=_lib.RECOMMEND_MV_MAX_ITEMS, workspace=_NO_WORKSPACE):
+    """The argument checks, output rows and launch that ``recommend_mv_topk``, ``recommend_mv_topk_wide`` and
+    ``recommend_basket_topk`` share: ``symbol`` takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays
+    (``diagnostics``: allocate them or pass NULL) or without them (None).  ``max_items``: the symbol's bound on I.
+    ``workspace``: for a symbol that takes (workspace, workspace_bytes) before the stream - a uint8 tensor, or None: allocated
+    (what serves all users at once, 256 MiB at the most, the minimum at the least)."""
+    def check_workspace(U, I):
+        if workspace is not _NO_WORKSPACE and workspace is not None:
+            if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+                raise ValueError("workspace must be a contiguous uint8 tensor")
+            if workspace.device != user_emb.device:
+                raise ValueError("workspace lives on %s, the embeddings on %s" % (workspace.device, user_emb.device))
+            need = _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", min(U, 16), I)
+            if U and workspace.numel() < need:
+                raise ValueError("workspace holds %d bytes, %d users of %d candidates need at least %d" % (workspace.numel(), U, I, need))
+    dims = _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, check_workspace)
 
     user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
         user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, (cand_stock, returns, day_idx, port_idx, port_len))
@@ -610,6 +626,74 @@ def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, p
     exclusion row."""
     return _recommend_mv_launch("pfo_recommend_basket_topk", None, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
                                 port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks)
+
+
+def _recommend_list_check(user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, dims, also=()):
+    """``_recommend_check`` for the list forms: the list pair in place of the exclusion pair (it takes the same checks, under
+    its own names), at least one and at most ``RECOMMEND_LIST_MAX_WIDTH`` columns.  Returns what ``_recommend_check`` returns."""
+    if not isinstance(list_pos, torch.Tensor) or list_pos.dim() != 2 or list_pos.dtype != torch.int32 or list_pos.shape[0] != user_emb.shape[0]:
+        raise ValueError("list_pos must be int32 [U, W]")
+    if not 1 <= list_pos.shape[1] <= _lib.RECOMMEND_LIST_MAX_WIDTH:
+        raise ValueError("list_pos must have between 1 and %d columns (got %d)" % (_lib.RECOMMEND_LIST_MAX_WIDTH, list_pos.shape[1]))
+    if list_len is not None and (not isinstance(list_len, torch.Tensor) or list_len.dim() != 1 or list_len.shape[0] != list_pos.shape[0]
+                                 or list_len.dtype != torch.int32):
+        raise ValueError("list_len must be int32 [U]")
+    return _recommend_check(user_emb, item_emb, k, user_block, list_pos, list_len, item_ok, dims, also)
+
+
+def recommend_list_topk(user_emb, item_emb, k, list_pos, list_len, user_block=None, item_ok=None, n_blocks=None, want_all=False):
+    """The k best of every user's OWN list in one launch (``pfo_recommend_list_topk``): ``recommend_topk`` with
+    ``list_pos`` i32[U,W] (1 <= W <= 256) / ``list_len`` i32[U] (None: whole rows) naming the candidate POSITIONS user u may be
+    offered, in place of an exclusion list.  Entries outside [0,I) are ignored, a position named more than once counts once, an
+    empty list gives an empty answer; ``item_ok`` still removes candidates.  The other arguments and their checks are
+    ``recommend_topk``'s; the users need not be sorted by block, and I is bounded by 65536 alone.
+
+    The score is an fp32 dot product within the any-order error bound - not ``recommend_topk``'s bits (another summation order).
+
+    Returns (top_pos i32[U,k], top_score f32[U,k], n_valid i32[U]) as ``recommend_topk`` does.  ``want_all`` adds score
+    f32[U,W] BY LIST SLOT, NaN in every slot that is not the first occurrence of an admissible position."""
+    dims = _score_dims(n_blocks, item_ok, user_block)
+    user_emb, item_emb, user_block, list_pos, list_len, item_ok, U, D, k, I, n_t, W = _recommend_list_check(
+        user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, dims)
+    dev = user_emb.device
+    top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
+    top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
+    n_valid = torch.empty(U, dtype=torch.int32, device=dev)
+    score = torch.empty((U, W), dtype=torch.float32, device=dev) if want_all else None
+    _lib.call("pfo_recommend_list_topk", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(list_pos),
+              _lib.ptr(list_len), W, _lib.ptr(item_ok), k, top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(), _lib.ptr(score),
+              _lib.stream_ptr())
+    return (top_pos, top_score, n_valid, score) if want_all else (top_pos, top_score, n_valid)
+
+
+def recommend_list_mv_topk(user_emb, item_emb, k, list_pos, list_len, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
+                           user_block=None, item_ok=None, n_blocks=None, want_all=False):
+    """``recommend_list_topk`` in the mean-variance order (``pfo_recommend_list_mv_topk``): the rank fusion of
+    ``recommend_mv_topk`` - its arguments, its y, its average-tie ranks, its blend - over every user's own list.  A listed
+    candidate must also have a y (day and ``cand_stock`` inside the tables, y not NaN).  No bound of 2048 on I and no workspace:
+    only the list, 256 entries at the most, is ranked.  The portfolio is used as given - a list of the user's own holdings is
+    ranked against those holdings, itself among them.  At ``lambda_mv = 0`` positions and scores are ``recommend_list_topk``'s
+    bit for bit where every listed candidate has a y.
+
+    Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]); ``want_all`` adds (score f32[U,W],
+    y f64[U,W], fused f64[U,W]) BY LIST SLOT, NaN in every slot that is not the first occurrence of an admissible position."""
+    dims = _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, _lib.RECOMMEND_MAX_ITEMS)
+    user_emb, item_emb, user_block, list_pos, list_len, item_ok, U, D, k, I, n_t, W = _recommend_list_check(
+        user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, dims, (cand_stock, returns, day_idx, port_idx, port_len))
+    dev = user_emb.device
+    n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
+    Wp = int(port_idx.shape[1]) if port_idx is not None else 0
+    if Wp and port_len is None:
+        port_len = torch.full((U,), Wp, dtype=torch.int32, device=dev)
+    out = (torch.empty((U, k), dtype=torch.int32, device=dev), torch.empty((U, k), dtype=torch.float32, device=dev),
+           torch.empty((U, k), dtype=torch.float64, device=dev), torch.empty(U, dtype=torch.int32, device=dev))
+    extra = tuple(torch.empty((U, W), dtype=dt, device=dev) if want_all else None for dt in (torch.float32, torch.float64, torch.float64))
+    _lib.call("pfo_recommend_list_mv_topk", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(list_pos),
+              _lib.ptr(list_len), W, _lib.ptr(item_ok), _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks,
+              n_ret, _lib.ptr(day_idx.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None),
+              _lib.ptr(port_len.contiguous() if Wp else None), Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out),
+              *(_lib.ptr(t) for t in extra), _lib.stream_ptr())
+    return out + extra if want_all else out
 
 
 def holdings_store(src, port_idx, port_len, ts, hold_idx, hold_len, hold_time, scratch=None):

@@ -13,6 +13,8 @@ inference and - for the BPR loss - an autograd formula:
     torch.ops.pfotgn.recommend_topk(user_emb, item_emb, k, n_blocks, ...)      the k best candidates per user (no reference form)
     torch.ops.pfotgn.recommend_mv_topk(user_emb, item_emb, k, cand_stock, ...) the same under the rank fusion of main.py:243-289
     torch.ops.pfotgn.recommend_mv_topk_wide(...)                               its form for lists beyond 2048 candidates
+    torch.ops.pfotgn.recommend_list_topk(user_emb, item_emb, k, list_pos, ...) the k best of every user's own list
+    torch.ops.pfotgn.recommend_list_mv_topk(...)                               the same in the mean-variance order
 
 Only a HIP implementation is registered ("cuda" dispatch key = ROCm here): on any other device the dispatcher raises,
 there is no CPU fallback.  The TGN step itself keeps its ``autograd.Function`` (``tgn._EmbedFn``): it owns state (memory,
@@ -167,6 +169,38 @@ def recommend_mv_topk_wide(user_emb: torch.Tensor, item_emb: torch.Tensor, k: in
 @recommend_mv_topk_wide.register_fake
 def _(user_emb, item_emb, k, cand_stock, returns, day_idx, gamma, lambda_mv, n_blocks=1, port_idx=None, port_len=None,
       user_block=None, excl_pos=None, excl_len=None, item_ok=None):
+    U = user_emb.shape[0]
+    return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
+            user_emb.new_empty((U, k), dtype=torch.float64), user_emb.new_empty((U,), dtype=torch.int32))
+
+
+@torch.library.custom_op(_LIB_NS + "::recommend_list_topk", mutates_args=(), device_types="cuda")
+def recommend_list_topk(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int, list_pos: torch.Tensor,
+                        list_len: Optional[torch.Tensor] = None, n_blocks: int = 1, user_block: Optional[torch.Tensor] = None,
+                        item_ok: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return functional.recommend_list_topk(user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, n_blocks=n_blocks)
+
+
+@recommend_list_topk.register_fake
+def _(user_emb, item_emb, k, list_pos, list_len=None, n_blocks=1, user_block=None, item_ok=None):
+    U = user_emb.shape[0]
+    return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
+            user_emb.new_empty((U,), dtype=torch.int32))
+
+
+@torch.library.custom_op(_LIB_NS + "::recommend_list_mv_topk", mutates_args=(), device_types="cuda")
+def recommend_list_mv_topk(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int, list_pos: torch.Tensor, cand_stock: torch.Tensor,
+                           returns: torch.Tensor, day_idx: torch.Tensor, gamma: float, lambda_mv: float,
+                           list_len: Optional[torch.Tensor] = None, n_blocks: int = 1, port_idx: Optional[torch.Tensor] = None,
+                           port_len: Optional[torch.Tensor] = None, user_block: Optional[torch.Tensor] = None,
+                           item_ok: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return functional.recommend_list_mv_topk(user_emb, item_emb, k, list_pos, list_len, cand_stock, returns, day_idx, port_idx, port_len,
+                                             gamma, lambda_mv, user_block, item_ok, n_blocks=n_blocks)
+
+
+@recommend_list_mv_topk.register_fake
+def _(user_emb, item_emb, k, list_pos, cand_stock, returns, day_idx, gamma, lambda_mv, list_len=None, n_blocks=1, port_idx=None,
+      port_len=None, user_block=None, item_ok=None):
     U = user_emb.shape[0]
     return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
             user_emb.new_empty((U, k), dtype=torch.float64), user_emb.new_empty((U,), dtype=torch.int32))

@@ -2,7 +2,8 @@
 asked for), ``assemble`` embeds users and candidates on the device and lets ``pfo_recommend_topk`` score and select - or, with
 a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` (beyond 2048 candidates ``pfo_recommend_mv_topk_wide``) score,
 rank twice, blend and select; with ``basket`` on top
-of that, ``pfo_recommend_basket_topk`` re-rank after every pick."""
+of that, ``pfo_recommend_basket_topk`` re-rank after every pick.  With ``only=`` every user ranks a list of its own:
+``pfo_recommend_list_topk`` / ``pfo_recommend_list_mv_topk``."""
 import collections
 import operator
 
@@ -12,8 +13,8 @@ import torch
 from . import _lib
 from .prices import PriceLedger
 
-Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held basket",
-                               defaults=(None, None, False))
+Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held "
+                               "only_ids only_len only_held basket", defaults=(None, None, None, None, False, False))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
 # (with a PriceLedger as the owner: the ORDINAL among its live days, or None - the day is looked up on the device)
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
@@ -129,9 +130,13 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None, *
 
 
 def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
-             day_idx=None, holdings=None, basket=False):
+             day_idx=None, holdings=None, basket=False, only=None):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
+    if only is not None and exclude is not None:
+        raise ValueError("only and exclude cannot be combined: list what may be offered, or what may not")
+    if only is not None and basket:
+        raise ValueError("only and basket=True cannot be combined: the basket has no list form")
     try:
         k = operator.index(k)
     except TypeError:
@@ -179,11 +184,23 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
     if basket and I > _lib.RECOMMEND_MV_MAX_ITEMS:
         raise ValueError("with basket=True, items may hold at most %d candidates (got %d): only the plain mean-variance order has "
                          "a form for longer lists" % (_lib.RECOMMEND_MV_MAX_ITEMS, I))
+    only_ids = only_len = None
+    if _is_held(only):
+        if holdings is None:
+            raise ValueError('only="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
+    elif only is not None:
+        only_ids, only_len = _pack_rows(
+            only, U, False, "packed only must be (ids [U,W], lens [U]) with U = %d", "packed only %s must be integers",
+            ("ids", "lens"), 'only must be None, "held", a list of per-user lists of item ids or a packed (ids, lens) pair',
+            "only lists %d users, users holds %d", "only holds ids that do not fit 32 bits")
+        if only_ids.shape[1] > _lib.RECOMMEND_LIST_MAX_WIDTH:
+            raise ValueError("only lists up to %d ids for a user, at most %d" % (only_ids.shape[1], _lib.RECOMMEND_LIST_MAX_WIDTH))
+    # (the list form ranks the list alone: with ``only`` the mean-variance order is bound by nothing but the plain bound on I)
     mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings,
                       max_items=_lib.RECOMMEND_MV_MAX_ITEMS if basket else _lib.RECOMMEND_MV_WIDE_MAX_ITEMS)
     held = (_is_held(exclude), mvq is not None and mvq.port_idx is None)
     return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
-                 held if any(held) else None, bool(basket))
+                 held if any(held) else None, only_ids, only_len, _is_held(only), bool(basket))
 
 
 def _to_dev(dev, a, dtype):
@@ -212,7 +229,7 @@ def mv_device_side(mv, dev, day_idx, user_ts=None):
 def assemble(tgn, q, return_embeddings=False):
     """The device side of ``TGN.recommend`` for a validated query: every (item, distinct timestamp) pair is embedded once (the
     grid of ``TGN._dedup_roots``), users and grid go through ``TGN._embed_readonly``, ``recommend_topk`` scores and selects."""
-    from .functional import recommend_topk
+    from .functional import recommend_list_topk, recommend_topk
     dev, k, U, I = tgn.device, q.k, q.U, q.I
 
     to_dev = lambda a, dtype: _to_dev(dev, a, dtype)
@@ -248,37 +265,49 @@ def assemble(tgn, q, return_embeddings=False):
                 out += (user_emb, item_emb, torch.empty(0, dtype=torch.int32, device=dev))
             return out
         excl_pos = excl_len = held_ports = None
-        if q.held is not None:
-            # one gather for whichever of the two asks: the ledger rows of the users, and their stocks as candidate positions
-            h_idx, h_len, h_pos = tgn.holdings.gather(users_d, items_d if q.held[0] else None)
-            if q.held[0]:
-                excl_pos, excl_len = h_pos, h_len
-            if q.held[1]:
+        ex_held, port_held = q.held or (False, False)
+        if ex_held or port_held or q.only_held:
+            # one gather for whoever asks: the ledger rows of the users, and their stocks as candidate positions
+            h_idx, h_len, h_pos = tgn.holdings.gather(users_d, items_d if ex_held or q.only_held else None)
+            if ex_held or q.only_held:
+                excl_pos, excl_len = h_pos, h_len                     # (with ``only``: the list - see ``listed`` below)
+            if port_held:
                 held_ports = (h_idx, h_len)
-        if q.ex_ids is not None and q.ex_ids.shape[1] > 0:
+        listed = q.only_held or q.only_ids is not None               # pos / len are the users' own lists, not exclusion lists
+        id_rows = (q.only_ids, q.only_len) if q.only_ids is not None else (q.ex_ids, q.ex_len)
+        if id_rows[0] is not None and id_rows[0].shape[1] > 0:
             # node id -> position in ``items`` through a table over the node ids (-1: not a candidate)
             pos_of = torch.full((tgn.n_nodes,), -1, dtype=torch.int32, device=dev)
             pos_of[items_d.long()] = torch.arange(I, dtype=torch.int32, device=dev)
-            ids = to_dev(q.ex_ids, torch.int64)
+            ids = to_dev(id_rows[0], torch.int64)
             inside = (ids >= 0) & (ids < tgn.n_nodes)
             excl_pos = torch.where(inside, pos_of[ids.clamp(0, tgn.n_nodes - 1)], torch.full_like(ids, -1, dtype=torch.int32))
             excl_pos = excl_pos.contiguous()
-            excl_len = to_dev(q.ex_len, torch.int32)
+            excl_len = to_dev(id_rows[1], torch.int32)
+        if listed and (excl_pos is None or excl_pos.shape[1] == 0):  # (lists without a column: nobody is offered anything)
+            excl_pos = torch.full((U, 1), -1, dtype=torch.int32, device=dev)
+            excl_len = torch.zeros(U, dtype=torch.int32, device=dev)
         ok_d = None
         if q.item_ok is not None:
             ok_d = (to_dev(q.item_ok if q.ok_h is None else q.ok_h, torch.int64) != 0).to(torch.uint8)
         if q.mv is not None:
             return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                                held_ports, user_ts)
-        launch = lambda ub, ue, pos, ln: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t)
-        return _select(launch, (user_emb, excl_pos, excl_len), user_block, n_t, items_d, item_emb, return_embeddings)
+                                held_ports, user_ts, listed)
+        if listed:
+            launch = lambda ub, ue, pos, ln: recommend_list_topk(ue, item_emb, k, pos, ln, ub, ok_d, n_blocks=n_t)
+        else:
+            launch = lambda ub, ue, pos, ln: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t)
+        return _select(launch, (user_emb, excl_pos, excl_len), user_block, n_t, items_d, item_emb, return_embeddings, sort=not listed)
 
 
-def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddings):
+def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddings, sort=True):
     """The tail of ``assemble``: ``launch(user_block, *per_user)`` -> (top_pos, ...) with the users of one block side by side
     (the kernels serve a tile of 16 users in one pass per distinct block), so ``per_user`` - the user embeddings first - follows
-    the stable sort by block and the results are put back; positions become item ids."""
-    if user_block is not None and n_t > 1:
+    the stable sort by block and the results are put back; positions become item ids.  ``sort`` False: the kernel serves a user
+    at a time and takes ``user_block`` as it is (the list forms)."""
+    if user_block is not None and n_t > 1 and not sort:
+        res = launch(user_block, *per_user)
+    elif user_block is not None and n_t > 1:
         order = torch.argsort(user_block, stable=True)
         sel = lambda t: None if t is None else t.index_select(0, order).contiguous()
         res = launch(sel(user_block), *(sel(t) for t in per_user))
@@ -296,12 +325,14 @@ def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddi
 
 
 def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                 held_ports=None, user_ts=None):
+                 held_ports=None, user_ts=None, listed=False):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
     portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held").
     ``q.basket``: ``recommend_basket_topk`` in its place; more than 2048 candidates: ``recommend_mv_topk_wide``.  With a ``PriceLedger`` the kernels index its storage by ring slot:
-    day ordinals become slots, no day index at all is ``pfo_day_lookup`` over ``user_ts`` f64[U] on the device."""
-    from .functional import recommend_basket_topk, recommend_mv_topk, recommend_mv_topk_wide
+    day ordinals become slots, no day index at all is ``pfo_day_lookup`` over ``user_ts`` f64[U] on the device.
+    ``listed``: ``excl_pos`` / ``excl_len`` are the users' own lists (``only=``) - ``recommend_list_mv_topk`` whatever I is, no
+    workspace and no sort by block."""
+    from .functional import recommend_basket_topk, recommend_list_mv_topk, recommend_mv_topk, recommend_mv_topk_wide
     topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
     if q.I > _lib.RECOMMEND_MV_MAX_ITEMS:                             # (never the basket: validate refuses it)
         topk = recommend_mv_topk_wide
@@ -315,7 +346,13 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
         port_len = to_dev(q.mv.port_len, torch.int32) if port_idx is not None else None
 
     def launch(ub, ue, pos, ln, day, port_idx, port_len):
-        top_pos, top_score, top_fused, n_valid = topk(ue, item_emb, q.k, cand_stock, returns, day, port_idx, port_len, float(mv.gamma),
-                                                      float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t)
+        if listed:
+            top_pos, top_score, top_fused, n_valid = recommend_list_mv_topk(ue, item_emb, q.k, pos, ln, cand_stock, returns, day, port_idx,
+                                                                            port_len, float(mv.gamma), float(mv.lambda_mv), ub, ok_d,
+                                                                            n_blocks=n_t)
+        else:
+            top_pos, top_score, top_fused, n_valid = topk(ue, item_emb, q.k, cand_stock, returns, day, port_idx, port_len, float(mv.gamma),
+                                                          float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t)
         return top_pos, top_score, n_valid, top_fused
-    return _select(launch, (user_emb, excl_pos, excl_len, day, port_idx, port_len), user_block, n_t, items_d, item_emb, return_embeddings)
+    return _select(launch, (user_emb, excl_pos, excl_len, day, port_idx, port_len), user_block, n_t, items_d, item_emb, return_embeddings,
+                   sort=not listed)

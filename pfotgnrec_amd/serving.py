@@ -51,7 +51,7 @@ class Serving:
         return emb
 
     def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
-                  mv=None, portfolios=None, day_idx=None, basket=False):
+                  mv=None, portfolios=None, day_idx=None, basket=False, only=None):
         """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
         written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
         is left as found), no gradient is recorded and dropout is off.
@@ -94,11 +94,23 @@ class Serving:
         ``pfo_day_lookup``, no read-back - and a user whose day the ledger does not hold gets an empty answer there, where host
         timestamps raise ``KeyError``.
 
-        Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` are not (it would cost a
-        read-back).  ``items`` is read back once when it is a device tensor."""
+        ``only``: every user is offered the best of a list of its OWN - a watchlist, a tradable universe, what it holds - in
+        place of all of ``items`` minus ``exclude``: a list of per-user lists of item NODE IDS (256 at the most), a packed pair
+        (ids i32[U,W] padded with -1, lens i32[U]) on host or device, or ``"held"``: the user's row of the holdings ledger, from
+        the one ``pfo_holdings_gather`` the query makes anyway.  Ids that are not in ``items`` are ignored, an id named twice
+        counts once, an empty list gives an empty answer; ``item_ok`` still applies.  One launch of ``pfo_recommend_list_topk``,
+        with ``mv`` of ``pfo_recommend_list_mv_topk``: both ranks run over the user's list alone, ``items`` may hold any number
+        of candidates up to 65536 and no workspace is taken.  The portfolio is used as given: with ``portfolios="held"`` and
+        ``only="held"`` a candidate is ranked against holdings it is itself among.  Not with ``exclude`` and not with
+        ``basket=True`` (ValueError).  The scores are fp32 dot products in another summation order than the shared-list
+        kernels': equal within the fp32 error bound, not to the bit.  The grid that is embedded is still every item of
+        ``items`` - to embed less, pass the union of the lists as ``items``.  The return tuple is the same.
+
+        Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` / ``only`` are not (it would
+        cost a read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
         query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
-                           portfolios, day_idx, self.holdings, basket)
+                           portfolios, day_idx, self.holdings, basket, only)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
