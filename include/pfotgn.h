@@ -423,6 +423,51 @@ int pfo_recommend_basket_topk(const float* user_emb, const float* item_emb, cons
                               int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Group caps (abi 6, additive): the three entries above with a concentration limit - at most group_cap picks of a group (a
+ * sector, an exchange, an issuer, a risk bucket) in a user's list - in the same one launch.  Each takes its sibling's parameter
+ * list with two arguments behind item_ok:
+ *   cand_group i32[I], aligned with the candidates: the group of candidate c, any non-negative int32 (the kernels compare ids:
+ *   no table by group, no bound on the number of groups); cand_group[c] < 0: c is in no group and is never capped.
+ *   group_cap >= 1.
+ * pfo_recommend_topk_capped / pfo_recommend_mv_topk_capped: the admissible set, the scores, y, the two average-tie ranks (counted
+ *   over the WHOLE admissible set: a cap changes no rank), the blend and the canonical order are the sibling's.  The list is the
+ *   walk over that order that takes a candidate unless its group is >= 0 and holds group_cap picks already, and stops at k.
+ *   top_score / top_fused: the uncapped values of the picks.  n_valid = the number taken = min(k, #groupless admissible +
+ *   sum over groups of min(group_cap, #admissible of the group)); the other slots -1 / -inf / -inf.  The diagnostics of the
+ *   mean-variance form (score_out, y_out, fused_out) hold the uncapped values of every admissible candidate.
+ *   Equivalently: a candidate survives iff fewer than group_cap admissible candidates of its group stand before it in the
+ *   canonical order, and the list is the first k survivors.
+ * pfo_recommend_basket_topk_capped: the pool of round r is A(u) minus the picks minus every candidate of a group that holds
+ *   group_cap picks; a candidate outside the pool takes part in no rank count of the round, exactly like an excluded one.  The
+ *   rest of a round is pfo_recommend_basket_topk's.  Hence: any k equals k calls of pfo_recommend_mv_topk(k = 1) with each pick
+ *   appended to the portfolio row and the exclusion row and, once the pick's group is full, every other candidate of that group
+ *   appended to the exclusion row as well.
+ * With group_cap >= k, with every cand_group < 0, or with every candidate in a group of its own, every output is the sibling's
+ * bit for bit.  There is no capped wide form and no capped list form.
+ * Bounds and errors: the sibling's, plus group_cap < 1 (checked with the bounds) and, with U > 0, a null cand_group.  U == 0:
+ * PFO_OK, no pointer is looked at.  Work on top of the sibling's: a few wave-wide operations per round (plain), one pass of
+ * I^2 comparisons per user (mean-variance), at most k LDS reads per pick (basket); 4 bytes of LDS per candidate held.
+ */
+int pfo_recommend_topk_capped(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                              int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                              const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap, int32_t k, int32_t* top_pos,
+                              float* top_score, int32_t* n_valid, void* stream);
+int pfo_recommend_mv_topk_capped(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                 int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                 const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap, const int32_t* cand_stock,
+                                 const double* returns, int32_t n_days, int32_t n_stocks, int32_t n_ret, const int32_t* day_idx,
+                                 const int32_t* port_idx, const int32_t* port_len, int32_t port_stride, double gamma,
+                                 double lambda_mv, int32_t k, int32_t* top_pos, float* top_score, double* top_fused,
+                                 int32_t* n_valid, float* score_out, double* y_out, double* fused_out, void* stream);
+int pfo_recommend_basket_topk_capped(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                     int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                     const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap,
+                                     const int32_t* cand_stock, const double* returns, int32_t n_days, int32_t n_stocks,
+                                     int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx, const int32_t* port_len,
+                                     int32_t port_stride, double gamma, double lambda_mv, int32_t k, int32_t* top_pos,
+                                     float* top_score, double* top_fused, int32_t* n_valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The list form of the two top-k entries (abi 6, additive): every user ranks a list of its OWN, not the shared candidate list
  * minus an exclusion list.  user_emb, item_emb, user_block, U, I, n_t, D, item_ok, k and the mean-variance arguments mean what
  * they mean in pfo_recommend_topk / pfo_recommend_mv_topk; the exclusion triple gives way to

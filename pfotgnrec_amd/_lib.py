@@ -180,6 +180,15 @@ PROTOTYPES = {
     "pfo_recommend_basket_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                             _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double,
                                             C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    # the capped forms: (cand_group, group_cap) behind item_ok
+    "pfo_recommend_topk_capped": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP,
+                                            C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_mv_topk_capped": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP,
+                                               C.c_int32, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double,
+                                               C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_basket_topk_capped": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                                   _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32,
+                                                   C.c_double, C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     "pfo_recommend_list_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                           C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     "pfo_recommend_list_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,

@@ -69,9 +69,10 @@ def _rows_of_log(arg, N, what):
 
 
 def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
-          portfolios, upper_u):
+          portfolios, upper_u, groups=None, group_cap=None):
     """Everything ``backtest`` refuses on the host, before any device work (ValueError) -> (N, k, cutoffs, batch_size, horizon,
-    upper_u, exclude, portfolios), the last two over the whole log as ``_rows_of_log`` leaves them."""
+    upper_u, exclude, portfolios), the last two over the whole log as ``_rows_of_log`` leaves them.  ``groups`` / ``group_cap``:
+    the checks of ``recommend`` (``recommend.validate_groups``), made here once for the whole log."""
     from .functional import check_cutoffs
     try:
         k = operator.index(k)
@@ -106,6 +107,7 @@ def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, 
         raise ValueError("tables must be an InvestTables or a PriceLedger")
     if basket and mv is None:
         raise ValueError("basket=True needs mv")
+    R.validate_groups(_length(items), groups, group_cap, None, mv)
     if mv is not None and portfolios is None:
         raise ValueError("mv needs portfolios: a packed pair over the log, one list of stock indices per interaction, or \"held\"")
     if (R._is_held(exclude) or R._is_held(portfolios)) and tgn.holdings is None:
@@ -156,16 +158,20 @@ def _without(ids, truth):
 
 def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
                   mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
-                  upper_u=None):
+                  upper_u=None, groups=None, group_cap=None):
     """The walk of ``backtest``; returns its per-interaction rows as host arrays after ONE read-back: dict(rank i32[n],
     recall f32[n, n_c], ndcg f32[n, n_c], invest f64[n, 4 n_c], list_item i32[n, k], n_valid i32[n]) - ``list_item`` the served
     lists, rank ``_lib.EVAL_RANK_NONE`` where the item taken is not in the list."""
     from .functional import list_buffers, list_metrics
     N, k, cuts, batch_size, horizon, upper_u, ex_log, pf_log = check(
         tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
-        portfolios, upper_u)
+        portfolios, upper_u, groups, group_cap)
     dev = tgn.device
     _lib.require_gpu(dev)
+    cap = {}
+    if groups is not None:
+        # on the device once, not once per batch (``recommend`` takes an integer device tensor as it is)
+        cap = dict(groups=R._to_dev(dev, groups if torch.is_tensor(groups) else np.asarray(groups), torch.int32), group_cap=group_cap)
     if torch.is_tensor(items):
         items = items.detach().cpu().numpy()                         # (``recommend`` would read it back per query)
     ledger = isinstance(tables, PriceLedger)
@@ -202,7 +208,7 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
         mv_side = {}
         if mv is not None:
             mv_side = dict(mv=mv, portfolios=pf_log if held_pf else _cut(pf_log, lo, hi), basket=bool(basket))
-        res = tgn.recommend(sources[lo:hi], edge_times[lo:hi], k, items, exclude=ex, item_ok=item_ok, n_neighbors=n_neighbors, **mv_side)
+        res = tgn.recommend(sources[lo:hi], edge_times[lo:hi], k, items, exclude=ex, item_ok=item_ok, n_neighbors=n_neighbors, **mv_side, **cap)
         item_ids, n_valid = res[0], res[2]
         pidx, plen = held_rows if held_pf else (_cut(pf_dev, lo, hi) if pf_dev is not None else (None, None))
         list_metrics(item_ids, truth[lo:hi], cuts, pidx, plen, upper_u, ret_past, day_past[lo:hi], ret_future, day_future[lo:hi],
@@ -225,12 +231,12 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
 
 def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
              mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
-             name="backtest", upper_u=None):
+             name="backtest", upper_u=None, groups=None, group_cap=None):
     """The served lists of a model held against what happened: a prequential walk over a chronological log (numpy arrays like
     the entry points, or device tensors i32 / i32 / f64 / i32).  Per batch ``[lo, hi)`` of ``batch_size`` interactions:
 
     1. ``tgn.recommend(sources[lo:hi], edge_times[lo:hi], k, items, ...)`` - ``exclude``, ``item_ok``, ``n_neighbors``, ``mv``,
-       ``portfolios`` and ``basket`` are passed through, so every served order, the wide mean-variance form, ``"held"`` and a
+       ``portfolios``, ``basket``, ``groups`` and ``group_cap`` are passed through, so every served order, the wide mean-variance form, ``"held"`` and a
        ``PriceLedger`` as ``mv`` work as they do there.  ``exclude`` / ``portfolios`` cover the whole LOG here: a packed pair
        (rows [N, W], lens [N]) on host or device, one list per interaction, or ``"held"``.
     2. ``list_metrics`` of the lists against ``destinations[lo:hi]`` - the place of the item the user took, and what the first
@@ -261,8 +267,10 @@ def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cut
     ``backtest_rows`` returns the per-interaction rows instead.
 
     ValueError before any device work: cutoffs not strictly increasing or outside [1, k], k > 64, arrays of unequal length,
-    batch_size < 1, ``tables`` of neither kind, a ledger with horizon < 1, ``mv.upper_u`` different from ``tables``'."""
+    batch_size < 1, ``tables`` of neither kind, a ledger with horizon < 1, ``mv.upper_u`` different from ``tables``', and what
+    ``recommend`` refuses of ``groups`` / ``group_cap`` (one without the other, a wrong length, non-integers, a cap below 1,
+    with ``mv`` more than 2048 candidates)."""
     rows = backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs=cutoffs, batch_size=batch_size,
                          tables=tables, horizon=horizon, mv=mv, basket=basket, exclude=exclude, portfolios=portfolios, item_ok=item_ok,
-                         n_neighbors=n_neighbors, keep_truth=keep_truth, append=append, upper_u=upper_u)
+                         n_neighbors=n_neighbors, keep_truth=keep_truth, append=append, upper_u=upper_u, groups=groups, group_cap=group_cap)
     return backtest_result_dict(name, rows["rank"], rows["invest"], cutoffs)

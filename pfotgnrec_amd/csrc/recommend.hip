@@ -52,6 +52,8 @@ struct RecArgs {
   int I, n_t, D, excl_stride, k, IC;
   int32_t *top_pos, *n_valid;
   float* top_score;
+  const int32_t* cand_group;                  // the capped forms alone: [I], < 0 = in no group; at most group_cap picks a group
+  int group_cap;
 };
 // The mean-variance side (pfo_recommend_mv_topk) but for its five read-only tables, which the kernels take as __restrict__
 // parameters of their own (PFO_REC_MV_TABLES); the three diagnostic outputs are the mv kernel's alone.
@@ -205,7 +207,12 @@ __device__ __forceinline__ void rec_mv_empty_slots(int32_t* __restrict__ top_pos
 __device__ __forceinline__ bool rec_better(double f, int c, double bf, int bc) { return bc < 0 || f > bf || (f == bf && c > bc); }
 
 // ---------------------------------------------------------------------------------------------
-template <int NJ>
+// CAPPED (pfo_recommend_topk_capped): the walk skips a candidate whose group holds group_cap picks already.  The capped top-k of
+// A u B is the capped top-k of (capped top-k of A) u B, so the walk over chunks stays as it is and the counts start from zero in
+// every chunk: once a round's winner is known its group is read (a chunk candidate's from LDS grp[IC] beside ok[], a carried
+// one's from its owner's lg), the picks of that group in next[] are counted with a ballot, and at the cap every lane clears
+// its keys of that group - the chunk's, and the carried list's.
+template <int NJ, bool CAPPED = false>
 __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const RecArgs a) {
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   const int32_t* __restrict__ excl_pos = a.excl_pos;
@@ -217,6 +224,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
   extern __shared__ float lds[];
   float* sc = lds;                                                    // [16][ICS]
   uint8_t* ok = reinterpret_cast<uint8_t*>(sc + PFO_REC_TILE * ICS);  // [IC]
+  int* grp = reinterpret_cast<int*>(ok + IC);                         // [IC], CAPPED: the group of a chunk candidate (IC is a multiple of 16)
   __shared__ int ub[PFO_REC_TILE];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
@@ -230,12 +238,15 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
     const float* items = item_emb + (int64_t)b * I * D;
 
     unsigned long long list[4] = {0ull, 0ull, 0ull, 0ull};           // lane t: rank t of user 4 * wave + i so far
+    int lg[4] = {-1, -1, -1, -1};                                    // CAPPED: the group of list[i]
     for (int c0 = 0; c0 < I; c0 += IC) {
       const int n = min(IC, I - c0);
       __syncthreads();                                               // the previous chunk's keys have been taken from LDS
       // ---- A: scores of candidates [c0, c0 + n)
       rec_score_chunk<NJ>(uf, items, c0, n, I, D, sc, ICS);
       for (int c = tid; c < n; c += PFO_REC_THREADS) ok[c] = item_ok ? item_ok[c0 + c] : (uint8_t)1;
+      if constexpr (CAPPED)
+        for (int c = tid; c < n; c += PFO_REC_THREADS) grp[c] = a.cand_group[c0 + c];
       __syncthreads();
 
       // ---- B: this wavefront's four users
@@ -278,6 +289,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
       }
       if (any_member) {
         unsigned long long next[4] = {0ull, 0ull, 0ull, 0ull};
+        int ng[4] = {-1, -1, -1, -1};                                // CAPPED: the group of next[i]
         for (int t = 0; t < k; ++t) {
           unsigned long long best[4];
 #pragma unroll
@@ -295,16 +307,35 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             if (best[i] == 0ull) continue;
+            int gw = -1;                                             // CAPPED: the winner's group (the same for every lane)
+            if constexpr (CAPPED) {
+              const int rel = (int)(uint32_t)(best[i] & 0xffffffffull) - c0;
+              if (rel >= 0) gw = grp[rel];                           // (a carried candidate lies before the chunk)
+              else gw = __shfl(lg[i], __ffsll((unsigned long long)__ballot(list[i] == best[i])) - 1, 64);
+            }
             // positions are distinct, so exactly one key of the wavefront equals the winner: its owner clears it
             if (list[i] == best[i]) list[i] = 0ull;
 #pragma unroll
             for (int m = 0; m < PFO_REC_SLOTS; ++m)
               if (key[i][m] == best[i]) key[i][m] = 0ull;
             if (lane == t) next[i] = best[i];
+            if constexpr (CAPPED) {
+              if (lane == t) ng[i] = gw;
+              if (gw >= 0 && __popcll(__ballot(ng[i] == gw)) >= a.group_cap) {   // the group is full: nobody else of it is taken
+                if (lg[i] == gw) list[i] = 0ull;
+#pragma unroll
+                for (int m = 0; m < PFO_REC_SLOTS; ++m)
+                  if (key[i][m] != 0ull && grp[lane + 64 * m] == gw) key[i][m] = 0ull;   // (a key: lane + 64 m < n)
+              }
+            }
           }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) list[i] = next[i];
+        if constexpr (CAPPED) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) lg[i] = ng[i];
+        }
       }
     }
 
@@ -346,7 +377,13 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
 #define PFO_REC_MV_TABLES                                                                                     \
   const int32_t *__restrict__ cand_stock, const double *__restrict__ returns, const int32_t *__restrict__ day_idx, \
       const int32_t *__restrict__ port_idx, const int32_t *__restrict__ port_len
-template <int NJ>
+// CAPPED (pfo_recommend_mv_topk_capped): a candidate survives iff fewer than group_cap admissible candidates of its own group
+// stand before it in the canonical order, and the capped list is the first k survivors.  So one more counting pass between C
+// and D, over fused and the group ids in LDS (grp[IC] behind the scores, 4 I bytes more: 152 KB at I = 2048): a candidate at
+// or beyond the cap becomes a NaN in LDS and in its owner's register, and D runs over the survivors as it is.  The diagnostics
+// keep the uncapped values.  About I^2 comparisons more per user, four candidates per LDS read (fused and grp are NaN / -1
+// from I up to the next multiple of 16, and the dynamic part starts 16-byte aligned here).
+template <int NJ, bool CAPPED>
 __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES) {
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   int32_t* __restrict__ top_pos = a.top_pos;
@@ -357,7 +394,12 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
   const int ICS = IC + 4;
   extern __shared__ double lds_mv[];
   double* yv = lds_mv;                                               // [IC]: y, then fused, of the user being ranked
+  if constexpr (CAPPED) {                                            // (16-byte aligned for the cap pass's wide reads)
+    extern __shared__ __attribute__((aligned(16))) double lds_mv_capped[];
+    yv = lds_mv_capped;
+  }
   float* sc = reinterpret_cast<float*>(yv + IC);                     // [16][ICS]
+  int* grp = reinterpret_cast<int*>(sc + PFO_REC_TILE * ICS);        // [IC], CAPPED: the group of every candidate
   __shared__ int ub[PFO_REC_TILE];
   __shared__ int n_adm;
   const int tid = threadIdx.x;
@@ -366,6 +408,12 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
 
   float4 uf[NJ];
   rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  if constexpr (CAPPED) {
+    // (the block table's barrier stands behind it; from I up to the next multiple of 16 a NaN that nobody overwrites: the cap
+    // pass reads four candidates at a time)
+    for (int c = tid; c < IC; c += PFO_REC_THREADS) grp[c] = c < I ? a.cand_group[c] : -1;
+    for (int c = I + tid; c < IC; c += PFO_REC_THREADS) yv[c] = nan;
+  }
   unsigned pending = rec_block_table(ub, a, u0);
   while (pending) {
     int b;
@@ -423,8 +471,43 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
           if (fused_out) fused_out[u * I + c] = fused[s];
         }
       }
-      if (mine) atomicAdd(&n_adm, mine);
+      if constexpr (!CAPPED)
+        if (mine) atomicAdd(&n_adm, mine);
       __syncthreads();
+      if constexpr (CAPPED) {
+        // ---- the cap: the same-group candidates before this one in the canonical order, counted
+        unsigned full = 0;                                           // bit s: candidate tid + 256 s finds its group full
+#pragma unroll
+        for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+          const int c = tid + PFO_REC_THREADS * s;
+          if (PFO_REC_THREADS * s >= I) break;
+          const double fi = fused[s];
+          if (c >= I || !(fi == fi)) continue;
+          const int g = grp[c];
+          if (g < 0) continue;
+          int before = 0;
+          const double2* f2 = reinterpret_cast<const double2*>(yv);
+          const int4* g4 = reinterpret_cast<const int4*>(grp);
+#pragma unroll 2
+          for (int j = 0; j < IC; j += 4) {                          // (every comparison with a NaN is false)
+            const double2 fa = f2[j >> 1], fb = f2[(j >> 1) + 1];
+            const int4 gj = g4[j >> 2];
+            before += ((gj.x == g) & ((fa.x > fi) | ((fa.x == fi) & (j > c)))) + ((gj.y == g) & ((fa.y > fi) | ((fa.y == fi) & (j + 1 > c)))) +
+                      ((gj.z == g) & ((fb.x > fi) | ((fb.x == fi) & (j + 2 > c)))) + ((gj.w == g) & ((fb.y > fi) | ((fb.y == fi) & (j + 3 > c))));
+          }
+          if (before >= a.group_cap) full |= 1u << s;
+        }
+        __syncthreads();                                             // every fused has been read
+#pragma unroll
+        for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+          if (!((full >> s) & 1u)) continue;
+          yv[tid + PFO_REC_THREADS * s] = nan;
+          fused[s] = nan;
+          --mine;
+        }
+        if (mine) atomicAdd(&n_adm, mine);
+        __syncthreads();
+      }
       // ---- D: the first k of the canonical order
 #pragma unroll
       for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
@@ -452,9 +535,9 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
 
 // (the body inlined into its kernel, not the kernel itself: written as the kernel, the D <= 176 instantiation takes 165 VGPRs
 // instead of 163 and loses its third wave per SIMD)
-template <int NJ>
+template <int NJ, bool CAPPED = false>
 __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES) {
-  recommend_mv_topk_body<NJ>(a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  recommend_mv_topk_body<NJ, CAPPED>(a, m, cand_stock, returns, day_idx, port_idx, port_len);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -475,7 +558,11 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(cons
 // LDS as above (the per-candidate values are registers; the dynamic part starts 16-byte aligned for the wide reads).
 // 2 k I^2 comparisons and (held + k - 1) I n_ret multiply-adds per user.
 // Two barriers per round; every loop bound between them depends on k, I and the pick (the same for all threads) alone.
-template <int NJ>
+// CAPPED (pfo_recommend_basket_topk_capped): a group that holds group_cap picks leaves the pool.  After a pick every thread
+// reads the pick's group from LDS (grp[IC] behind the scores - no group id lives in a register across a round), counts it among
+// the earlier picks' groups (pick_g[], k ints of LDS: slot r is written in round r and read from round r + 1 on, two barriers
+// later) and, once the group is full, takes its own candidates of that group out: the alive bit, NaN in y and in the score row.
+template <int NJ, bool CAPPED = false>
 __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES) {
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   int32_t* __restrict__ top_pos = a.top_pos;
@@ -490,6 +577,8 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
   __shared__ int ub[PFO_REC_TILE];
   __shared__ double wave_f[PFO_REC_THREADS / 64];                    // the best (fused, position) of each wavefront
   __shared__ int wave_c[PFO_REC_THREADS / 64];
+  int* grp = reinterpret_cast<int*>(sc + PFO_REC_TILE * ICS);        // [IC], CAPPED: the group of every candidate
+  __shared__ int pick_g[CAPPED ? 64 : 1];                            // CAPPED: the group of pick r of the user being served
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
   const double nan = __builtin_nan("");
@@ -497,6 +586,8 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
 
   float4 uf[NJ];
   rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  if constexpr (CAPPED)
+    for (int c = tid; c < I; c += PFO_REC_THREADS) grp[c] = a.cand_group[c];   // (the block table's barrier stands behind it)
   unsigned pending = rec_block_table(ub, a, u0);
   while (pending) {
     int b;
@@ -626,6 +717,25 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
           top_pos[u * k + rd] = bc;
           top_score[u * k + rd] = sv == 0.f ? 0.f : sv;              // a zero score is handed out as +0
           top_fused[u * k + rd] = bf;
+        }
+        if constexpr (CAPPED) {
+          const int gw = grp[bc];                                    // (the same for every thread)
+          if (tid == 0) pick_g[rd] = gw;
+          if (gw >= 0) {
+            int held = 1;
+            for (int r = 0; r < rd; ++r) held += (pick_g[r] == gw);
+            if (held >= a.group_cap) {                               // the group is full: it leaves the pool
+#pragma unroll
+              for (int s = 0; s < PFO_RMV_PER_THREAD; ++s) {
+                const int c = tid + PFO_REC_THREADS * s;
+                if (((alive >> s) & 1u) && grp[c] == gw) {
+                  alive &= ~(1u << s);
+                  yv[c] = nan;
+                  su[c] = __builtin_nanf("");
+                }
+              }
+            }
+          }
         }
         ++n_pick;
         if (rd + 1 < k) {
@@ -1207,6 +1317,15 @@ int rec_check_list_stride(const char* who, int list_stride) {
   PFO_REC_REQUIRE(list_stride >= 1 && list_stride <= PFO_RECOMMEND_LIST_MAX_WIDTH, "list_stride must be in [1, PFO_RECOMMEND_LIST_MAX_WIDTH]");
   return PFO_OK;
 }
+// the capped forms' own bound, ahead of the common checks (which end on the pointers), and their group row (U > 0), behind them
+int rec_check_cap(const char* who, int group_cap) {
+  PFO_REC_REQUIRE(group_cap >= 1, "group_cap must be at least 1");
+  return PFO_OK;
+}
+int rec_check_groups(const char* who, const int32_t* cand_group) {
+  PFO_REC_REQUIRE(cand_group, "null cand_group");
+  return PFO_OK;
+}
 int rec_check_list_rows(const char* who, const int32_t* list_pos, const int32_t* list_len) {
   PFO_REC_REQUIRE(list_pos && list_len, "null list_pos or list_len");
   return PFO_OK;
@@ -1217,11 +1336,13 @@ constexpr size_t rec_score_bytes(int IC) { return (size_t)PFO_REC_TILE * (IC + 4
 // the mean-variance kernels hold every candidate of a block at once, and y[IC] in fp64 before the scores
 inline int rec_mv_ic(int I) { return (int)pfo_align_up(I, 16); }
 constexpr size_t rec_mv_bytes(int IC) { return (size_t)IC * sizeof(double) + rec_score_bytes(IC); }
+constexpr size_t rec_group_bytes(int IC) { return (size_t)IC * sizeof(int32_t); }   // grp[IC] of a capped kernel, behind the rest
 
 // One workgroup per 16 users of a kernel template (times `grid_y`: the wide form's candidate chunks), in the instantiation that
 // covers a row of a.D floats, with `shmem` bytes of LDS.  `kernel_of` (PFO_REC_KERNEL) names the template: it maps
 // std::integral_constant<int, NJ> to the instantiation.
 #define PFO_REC_KERNEL(name) [](auto nj) { return &name<decltype(nj)::value>; }
+#define PFO_REC_KERNEL_CAPPED(name) [](auto nj) { return &name<decltype(nj)::value, true>; }
 template <class KernelOf, class... Args>
 int rec_launch_grid(const char* who, KernelOf kernel_of, size_t shmem, unsigned grid_y, void* stream, const RecArgs& a, const Args&... more) {
   auto launch = [&](auto nj) -> int {
@@ -1304,6 +1425,67 @@ extern "C" int pfo_recommend_basket_topk(const float* user_emb, const float* ite
   if (rc != PFO_OK || U == 0) return rc;
   return rec_launch(__func__, PFO_REC_KERNEL(recommend_basket_topk_kernel), rec_mv_bytes(a.IC), stream, a, m, cand_stock, returns, day_idx,
                     port_idx, port_len);
+}
+
+// The capped forms: the sibling's argument blocks and checks, the two cap arguments on top, the CAPPED instantiation.
+#define PFO_REC_CAPPED_ARGS(ic)    \
+  RecArgs a = PFO_REC_ARGS(ic);    \
+  a.cand_group = cand_group;       \
+  a.group_cap = group_cap
+
+extern "C" int pfo_recommend_topk_capped(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                         int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                         const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap, int32_t k,
+                                         int32_t* top_pos, float* top_score, int32_t* n_valid, void* stream) {
+  PFO_REC_CAPPED_ARGS((int)pfo_align_up(I < PFO_REC_CHUNK ? I : PFO_REC_CHUNK, 16));
+  int rc = rec_check_cap(__func__, group_cap);
+  if (rc == PFO_OK)
+    rc = rec_check_common(__func__, a, PFO_RECOMMEND_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MAX_ITEMS]", "excl_stride must not be negative");
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_groups(__func__, cand_group);
+  if (rc != PFO_OK) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL_CAPPED(recommend_topk_kernel), rec_score_bytes(a.IC) + (size_t)a.IC + rec_group_bytes(a.IC), stream,
+                    a);                                              // (+ ok[IC] + grp[IC])
+}
+
+extern "C" int pfo_recommend_mv_topk_capped(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                            int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                            const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap,
+                                            const int32_t* cand_stock, const double* returns, int32_t n_days, int32_t n_stocks,
+                                            int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx, const int32_t* port_len,
+                                            int32_t port_stride, double gamma, double lambda_mv, int32_t k, int32_t* top_pos,
+                                            float* top_score, double* top_fused, int32_t* n_valid, float* score_out, double* y_out,
+                                            double* fused_out, void* stream) {
+  PFO_REC_CAPPED_ARGS(rec_mv_ic(I));
+  const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
+  int rc = rec_check_cap(__func__, group_cap);
+  if (rc == PFO_OK) rc = rec_check_mv_bounds(__func__, m);         // (ahead of rec_check_mv, which ends on the pointers)
+  if (rc == PFO_OK) rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_groups(__func__, cand_group);
+  if (rc != PFO_OK) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL_CAPPED(recommend_mv_topk_kernel), rec_mv_bytes(a.IC) + rec_group_bytes(a.IC), stream, a, m, cand_stock,
+                    returns, day_idx, port_idx, port_len);
+}
+
+extern "C" int pfo_recommend_basket_topk_capped(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U,
+                                                int32_t I, int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len,
+                                                int32_t excl_stride, const uint8_t* item_ok, const int32_t* cand_group,
+                                                int32_t group_cap, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                                int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                                const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv,
+                                                int32_t k, int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid,
+                                                void* stream) {
+  PFO_REC_CAPPED_ARGS(rec_mv_ic(I));
+  const RecMvArgs m = PFO_REC_MV_ARGS(nullptr, nullptr, nullptr);
+  int rc = rec_check_cap(__func__, group_cap);
+  if (rc == PFO_OK) rc = rec_check_mv_bounds(__func__, m);         // (ahead of rec_check_mv, which ends on the pointers)
+  if (rc == PFO_OK) rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_groups(__func__, cand_group);
+  if (rc != PFO_OK) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL_CAPPED(recommend_basket_topk_kernel), rec_mv_bytes(a.IC) + rec_group_bytes(a.IC), stream, a, m,
+                    cand_stock, returns, day_idx, port_idx, port_len);
 }
 
 extern "C" int64_t pfo_recommend_mv_wide_workspace_bytes(int64_t U, int32_t I) {

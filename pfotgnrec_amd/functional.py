@@ -472,7 +472,40 @@ def _score_dims(n_blocks, item_ok, user_block):
     return dims
 
 
-def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_len=None, item_ok=None, n_blocks=None):
+def _recommend_cap(cand_group, group_cap):
+    """The two cap keywords of the shared-list top-k forms, checked: None without them, else (cand_group, group_cap) - the
+    length of ``cand_group`` is checked where I is known (``_capped_dims``), its device with the other tensors'."""
+    import operator
+    if cand_group is None and group_cap is None:
+        return None
+    if cand_group is None or group_cap is None:
+        raise ValueError("cand_group and group_cap go together: give both or neither")
+    if not isinstance(cand_group, torch.Tensor) or cand_group.dim() != 1 or cand_group.dtype != torch.int32:
+        raise ValueError("cand_group must be int32 [I]")
+    try:
+        group_cap = operator.index(group_cap)
+    except TypeError:
+        raise ValueError("group_cap must be an integer") from None
+    if group_cap < 1:
+        raise ValueError("group_cap must be at least 1 (got %d)" % group_cap)
+    return cand_group, min(group_cap, 64)                            # (k <= 64: a cap beyond it never binds)
+
+
+def _capped_dims(dims, cap):
+    """``dims`` of ``_recommend_check`` with the length of ``cand_group`` held to the I it finds (``cap`` None: ``dims`` itself)."""
+    if cap is None:
+        return dims
+
+    def capped(U, rows):
+        I, n_t = dims(U, rows)
+        if cap[0].shape[0] != I:
+            raise ValueError("cand_group holds %d entries, the candidate list %d" % (cap[0].shape[0], I))
+        return I, n_t
+    return capped
+
+
+def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, cand_group=None,
+                   group_cap=None):
     """The k best candidates per user in one launch (``pfo_recommend_topk``); nothing but its outputs is written.
 
     user_emb f32[U,D]; item_emb f32[n_t*I,D]: n_t blocks of the same I candidates (embedded at n_t times); user_block
@@ -483,14 +516,24 @@ def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_l
     excl_len i32[U], None: the whole row).
 
     Returns (top_pos i32[U,k], top_score f32[U,k], n_valid i32[U]): score descending, the larger position first among equal
-    scores (the order of ``eval_metrics``); slots beyond the admissible candidates hold -1 / -inf."""
-    dims = _score_dims(n_blocks, item_ok, user_block)
+    scores (the order of ``eval_metrics``); slots beyond the admissible candidates hold -1 / -inf.
+
+    ``cand_group`` i32[I] with ``group_cap`` >= 1 (both or neither; ``pfo_recommend_topk_capped``): the list is the walk over
+    that order that skips a candidate whose group - any non-negative id; negative: no group, never capped - holds ``group_cap``
+    picks already.  Scores are the uncapped ones; n_valid counts what was taken."""
+    cap = _recommend_cap(cand_group, group_cap)
+    dims = _capped_dims(_score_dims(n_blocks, item_ok, user_block), cap)
     user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
-        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims)
+        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, cap[:1] if cap else ())
     dev = user_emb.device
     top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
     top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
     n_valid = torch.empty(U, dtype=torch.int32, device=dev)
+    if cap is not None:
+        _lib.call("pfo_recommend_topk_capped", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D,
+                  _lib.ptr(excl_pos), _lib.ptr(excl_len), W, _lib.ptr(item_ok), _lib.ptr(cap[0].contiguous()), cap[1], k, top_pos.data_ptr(),
+                  top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
+        return top_pos, top_score, n_valid
     _lib.call("pfo_recommend_topk", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos),
               _lib.ptr(excl_len), W, _lib.ptr(item_ok), k, top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
     return top_pos, top_score, n_valid
@@ -532,12 +575,14 @@ def _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_ite
 
 
 def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
-                         user_block, excl_pos, excl_len, item_ok, n_blocks, max_items=_lib.RECOMMEND_MV_MAX_ITEMS, workspace=_NO_WORKSPACE):
+                         user_block, excl_pos, excl_len, item_ok, n_blocks, max_items=_lib.RECOMMEND_MV_MAX_ITEMS, workspace=_NO_WORKSPACE,
+                         cap=None):
     """The argument checks, output rows and launch that ``recommend_mv_topk``, ``recommend_mv_topk_wide`` and
     ``recommend_basket_topk`` share: ``symbol`` takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays
     (``diagnostics``: allocate them or pass NULL) or without them (None).  ``max_items``: the symbol's bound on I.
     ``workspace``: for a symbol that takes (workspace, workspace_bytes) before the stream - a uint8 tensor, or None: allocated
-    (what serves all users at once, 256 MiB at the most, the minimum at the least)."""
+    (what serves all users at once, 256 MiB at the most, the minimum at the least).  ``cap``: what ``_recommend_cap`` returns -
+    with one, ``symbol`` + "_capped" is called, the two cap arguments behind item_ok."""
     def check_workspace(U, I):
         if workspace is not _NO_WORKSPACE and workspace is not None:
             if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
@@ -547,10 +592,11 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
             need = _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", min(U, 16), I)
             if U and workspace.numel() < need:
                 raise ValueError("workspace holds %d bytes, %d users of %d candidates need at least %d" % (workspace.numel(), U, I, need))
-    dims = _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, check_workspace)
+    dims = _capped_dims(_mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, check_workspace), cap)
 
     user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
-        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, (cand_stock, returns, day_idx, port_idx, port_len))
+        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims,
+        (cand_stock, returns, day_idx, port_idx, port_len) + (cap[:1] if cap else ()))
     dev = user_emb.device
     n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
     Wp = int(port_idx.shape[1]) if port_idx is not None else 0
@@ -572,15 +618,18 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
             size = max(min(size, _WIDE_WORKSPACE_CAP), _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", min(U, 16), I))
             workspace = torch.empty(size, dtype=torch.uint8, device=dev)
         ws = (workspace.data_ptr(), workspace.numel())
+    cap_args = ()
+    if cap is not None:
+        symbol, cap_args = symbol + "_capped", (_lib.ptr(cap[0].contiguous()), cap[1])
     _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos), _lib.ptr(excl_len),
-              W, _lib.ptr(item_ok), _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks, n_ret,
+              W, _lib.ptr(item_ok), *cap_args, _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks, n_ret,
               _lib.ptr(day_idx.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None),
               Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), *ws, _lib.stream_ptr())
     return out + extra if diagnostics else out
 
 
 def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
-                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False):
+                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False, cand_group=None, group_cap=None):
     """``recommend_topk`` with the mean-variance rank fusion of main.py:243-289 over every user's whole candidate list, in one
     launch (``pfo_recommend_mv_topk``).
 
@@ -593,9 +642,14 @@ def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_
 
     Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]): fused descending, the larger position
     first among equal values; empty slots -1 / -inf / -inf.  ``want_all`` adds (score f32[U,I], y f64[U,I],
-    fused f64[U,I]), NaN in the last two where a candidate is not admissible."""
+    fused f64[U,I]), NaN in the last two where a candidate is not admissible.
+
+    ``cand_group`` i32[I] with ``group_cap`` >= 1 (both or neither; ``pfo_recommend_mv_topk_capped``): the walk over that order
+    skips a candidate whose group (negative: none) holds ``group_cap`` picks already.  Ranks, fused and the ``want_all`` arrays
+    are the uncapped ones - a cap changes no rank."""
     return _recommend_mv_launch("pfo_recommend_mv_topk", bool(want_all), user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
-                                port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks)
+                                port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks,
+                                cap=_recommend_cap(cand_group, group_cap))
 
 
 def recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
@@ -614,7 +668,7 @@ def recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, 
 
 
 def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
-                          excl_pos=None, excl_len=None, item_ok=None, n_blocks=None):
+                          excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, cand_group=None, group_cap=None):
     """``recommend_mv_topk`` taken one pick at a time, in one launch (``pfo_recommend_basket_topk``): pick r is the first of the
     canonical order of round r, in which the stocks of picks 0 .. r-1 count as held behind ``port_idx[u]`` (in pick order) and
     their positions have left the pool; only the position leaves - another candidate on the same stock stays.  Arguments and
@@ -623,9 +677,14 @@ def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, p
     Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]): ``top_fused[u, r]`` is the pick's fused
     value OF ROUND r (a row need not descend); the list ends when no candidate is left, empty slots -1 / -inf / -inf.  k = 1 is
     ``recommend_mv_topk`` bit for bit; any k equals k calls of it with k = 1, each pick appended to the user's portfolio row and
-    exclusion row."""
+    exclusion row.
+
+    ``cand_group`` i32[I] with ``group_cap`` >= 1 (both or neither; ``pfo_recommend_basket_topk_capped``): a group (negative:
+    none) that holds ``group_cap`` picks leaves the pool - its candidates take part in no later round, like excluded ones.  Any
+    k then equals the k = 1 loop above with every other candidate of a full group appended to the exclusion row as well."""
     return _recommend_mv_launch("pfo_recommend_basket_topk", None, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
-                                port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks)
+                                port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks,
+                                cap=_recommend_cap(cand_group, group_cap))
 
 
 def _recommend_list_check(user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, dims, also=()):

@@ -3,7 +3,8 @@ asked for), ``assemble`` embeds users and candidates on the device and lets ``pf
 a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` (beyond 2048 candidates ``pfo_recommend_mv_topk_wide``) score,
 rank twice, blend and select; with ``basket`` on top
 of that, ``pfo_recommend_basket_topk`` re-rank after every pick.  With ``only=`` every user ranks a list of its own:
-``pfo_recommend_list_topk`` / ``pfo_recommend_list_mv_topk``."""
+``pfo_recommend_list_topk`` / ``pfo_recommend_list_mv_topk``.  With ``groups=`` / ``group_cap=`` (``validate_groups``) the three
+shared-list launches take their capped entries: at most ``group_cap`` picks of a group in a user's list."""
 import collections
 import operator
 
@@ -14,7 +15,8 @@ from . import _lib
 from .prices import PriceLedger
 
 Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held "
-                               "only_ids only_len only_held basket", defaults=(None, None, None, None, False, False))
+                               "only_ids only_len only_held groups group_cap basket",
+                               defaults=(None, None, None, None, False, None, None, False))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
 # (with a PriceLedger as the owner: the ORDINAL among its live days, or None - the day is looked up on the device)
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
@@ -129,8 +131,43 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None, *
     return MVQuery(mv, port_idx, port_len, day)
 
 
+def validate_groups(I, groups, group_cap, only=None, mv=None):
+    """``groups`` / ``group_cap`` of ``TGN.recommend`` and ``backtest`` checked on the host (ValueError) -> (groups, group_cap):
+    (None, None) without them, else one int32 per candidate (a host array, or the caller's integer device tensor as it is: it
+    is not read back) and an int >= 1.  ``only`` / ``mv``: what else the query carries - the cap has no list form and no wide
+    mean-variance form."""
+    if groups is None and group_cap is None:
+        return None, None
+    if groups is None or group_cap is None:
+        raise ValueError("groups and group_cap go together: one group id per candidate, and how many picks a group may hold")
+    try:
+        group_cap = operator.index(group_cap)
+    except TypeError:
+        raise ValueError("group_cap must be an integer") from None
+    if group_cap < 1:
+        raise ValueError("group_cap must be at least 1 (got %d)" % group_cap)
+    try:
+        g = groups if isinstance(groups, torch.Tensor) else np.asarray(groups)
+    except (TypeError, ValueError):
+        raise ValueError("groups must hold one integer per candidate") from None
+    if g.ndim != 1 or not _is_int_array(g) and (isinstance(g, torch.Tensor) or g.size):
+        raise ValueError("groups must hold one integer per candidate: a 1-D array of integer group ids (negative: no group)")
+    if int(g.shape[0]) != I:
+        raise ValueError("groups holds %d entries, items %d candidates" % (int(g.shape[0]), I))
+    if isinstance(g, np.ndarray):
+        if g.size and (int(g.min()) < -(1 << 31) or int(g.max()) >= (1 << 31)):
+            raise ValueError("groups holds ids that do not fit 32 bits")
+        g = g.astype(np.int32)
+    if only is not None:
+        raise ValueError("groups and only cannot be combined: the list forms have no capped order")
+    if mv is not None and I > _lib.RECOMMEND_MV_MAX_ITEMS:
+        raise ValueError("with mv and groups, items may hold at most %d candidates (got %d): the capped order has no wide form"
+                         % (_lib.RECOMMEND_MV_MAX_ITEMS, I))
+    return g, group_cap
+
+
 def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
-             day_idx=None, holdings=None, basket=False, only=None):
+             day_idx=None, holdings=None, basket=False, only=None, *, groups=None, group_cap=None):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
     if only is not None and exclude is not None:
@@ -195,12 +232,13 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
             "only lists %d users, users holds %d", "only holds ids that do not fit 32 bits")
         if only_ids.shape[1] > _lib.RECOMMEND_LIST_MAX_WIDTH:
             raise ValueError("only lists up to %d ids for a user, at most %d" % (only_ids.shape[1], _lib.RECOMMEND_LIST_MAX_WIDTH))
+    groups, group_cap = validate_groups(I, groups, group_cap, only, mv)
     # (the list form ranks the list alone: with ``only`` the mean-variance order is bound by nothing but the plain bound on I)
     mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings,
                       max_items=_lib.RECOMMEND_MV_MAX_ITEMS if basket else _lib.RECOMMEND_MV_WIDE_MAX_ITEMS)
     held = (_is_held(exclude), mvq is not None and mvq.port_idx is None)
     return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
-                 held if any(held) else None, only_ids, only_len, _is_held(only), bool(basket))
+                 held if any(held) else None, only_ids, only_len, _is_held(only), groups, group_cap, bool(basket))
 
 
 def _to_dev(dev, a, dtype):
@@ -290,13 +328,16 @@ def assemble(tgn, q, return_embeddings=False):
         ok_d = None
         if q.item_ok is not None:
             ok_d = (to_dev(q.item_ok if q.ok_h is None else q.ok_h, torch.int64) != 0).to(torch.uint8)
+        cap = {}                                                     # (never with ``only``: validate refuses it)
+        if q.groups is not None:
+            cap = dict(cand_group=to_dev(q.groups, torch.int32), group_cap=q.group_cap)
         if q.mv is not None:
             return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                                held_ports, user_ts, listed)
+                                held_ports, user_ts, listed, cap)
         if listed:
             launch = lambda ub, ue, pos, ln: recommend_list_topk(ue, item_emb, k, pos, ln, ub, ok_d, n_blocks=n_t)
         else:
-            launch = lambda ub, ue, pos, ln: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t)
+            launch = lambda ub, ue, pos, ln: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t, **cap)
         return _select(launch, (user_emb, excl_pos, excl_len), user_block, n_t, items_d, item_emb, return_embeddings, sort=not listed)
 
 
@@ -325,13 +366,14 @@ def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddi
 
 
 def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                 held_ports=None, user_ts=None, listed=False):
+                 held_ports=None, user_ts=None, listed=False, cap=None):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
     portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held").
     ``q.basket``: ``recommend_basket_topk`` in its place; more than 2048 candidates: ``recommend_mv_topk_wide``.  With a ``PriceLedger`` the kernels index its storage by ring slot:
     day ordinals become slots, no day index at all is ``pfo_day_lookup`` over ``user_ts`` f64[U] on the device.
     ``listed``: ``excl_pos`` / ``excl_len`` are the users' own lists (``only=``) - ``recommend_list_mv_topk`` whatever I is, no
-    workspace and no sort by block."""
+    workspace and no sort by block.  ``cap``: the cap keywords of the bounded and the basket launch (empty: uncapped; validate
+    lets them through with neither ``only`` nor more than 2048 candidates)."""
     from .functional import recommend_basket_topk, recommend_list_mv_topk, recommend_mv_topk, recommend_mv_topk_wide
     topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
     if q.I > _lib.RECOMMEND_MV_MAX_ITEMS:                             # (never the basket: validate refuses it)
@@ -352,7 +394,7 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
                                                                             n_blocks=n_t)
         else:
             top_pos, top_score, top_fused, n_valid = topk(ue, item_emb, q.k, cand_stock, returns, day, port_idx, port_len, float(mv.gamma),
-                                                          float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t)
+                                                          float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t, **(cap or {}))
         return top_pos, top_score, n_valid, top_fused
     return _select(launch, (user_emb, excl_pos, excl_len, day, port_idx, port_len), user_block, n_t, items_d, item_emb, return_embeddings,
                    sort=not listed)

@@ -51,7 +51,7 @@ class Serving:
         return emb
 
     def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
-                  mv=None, portfolios=None, day_idx=None, basket=False, only=None):
+                  mv=None, portfolios=None, day_idx=None, basket=False, only=None, *, groups=None, group_cap=None):
         """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
         written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
         is left as found), no gradient is recorded and dropout is off.
@@ -106,11 +106,21 @@ class Serving:
         kernels': equal within the fp32 error bound, not to the bit.  The grid that is embedded is still every item of
         ``items`` - to embed less, pass the union of the lists as ``items``.  The return tuple is the same.
 
+        ``groups`` with ``group_cap`` (both or neither): a concentration limit - at most ``group_cap`` (an int >= 1) items of a
+        group in a user's list.  groups: one integer per entry of ``items`` - its sector, exchange, issuer, risk bucket; any
+        non-negative int32, a negative id puts the item in no group and it is never capped - as a host array or list, or an
+        integer device tensor (brought to int32 on the device once).  The order is the one served without the cap, walked with a
+        candidate skipped when its group is full: ranks, scores and fused values are the uncapped ones, n_valid counts what was
+        taken.  With ``basket=True`` a full group leaves the pool of the later rounds, like excluded items.  Still one launch
+        (``pfo_recommend_topk_capped`` / ``pfo_recommend_mv_topk_capped`` / ``pfo_recommend_basket_topk_capped``) and the same
+        return tuple.  Not with ``only`` (the list forms have no capped order) and, with ``mv``, not beyond 2048 candidates (the
+        capped order has no wide form): ValueError.
+
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` / ``only`` are not (it would
         cost a read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
         query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
-                           portfolios, day_idx, self.holdings, basket, only)
+                           portfolios, day_idx, self.holdings, basket, only, groups=groups, group_cap=group_cap)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
