@@ -468,6 +468,51 @@ int pfo_recommend_basket_topk_capped(const float* user_emb, const float* item_em
                                      float* top_score, double* top_fused, int32_t* n_valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Group caps that count holdings (abi 6, additive): the three capped entries with a per-user starting count - what a user
+ * already holds of a group uses up that much of the group's quota.  Each takes its _capped sibling's parameter list with three
+ * arguments directly behind group_cap:
+ *   held_group i32[U, held_stride], padded with -1: one group id per holding of user u;  held_len i32[U], clamped to
+ *   [0, held_stride];  0 <= held_stride <= PFO_RECOMMEND_HELD_MAX_WIDTH.
+ *   h_u(g) = the number of entries p < held_len[u] with held_group[u, p] == g.  A negative entry is a holding in no group and
+ *   counts for nothing; an id named twice counts twice.
+ * pfo_recommend_topk_capped_held / pfo_recommend_mv_topk_capped_held: the walk of the sibling takes a candidate of group g >= 0
+ *   unless (picks of g so far) + h_u(g) >= group_cap; a group with h_u(g) >= group_cap is closed from the start.  The
+ *   admissible set, ranks (over the WHOLE admissible set), values and diagnostics are the uncapped ones.  Equivalently: a
+ *   candidate survives iff (admissible candidates of its group before it in the canonical order) + h_u(g) < group_cap.
+ * pfo_recommend_basket_topk_capped_held: the pool of round r is A(u) minus the picks minus every candidate of a group with
+ *   picks + h_u(g) >= group_cap - in round 0 too, so a group closed from the start takes part in no rank count, exactly like
+ *   excluded candidates.
+ * n_valid = min(k, #groupless admissible + sum over groups of min(max(group_cap - h_u(g), 0), #admissible of the group)).
+ * With every held_len 0, or held_stride 0 (the two pointers may then be null), every output is the _capped sibling's bit for bit.
+ * Bounds and errors: the sibling's, plus held_stride outside [0, PFO_RECOMMEND_HELD_MAX_WIDTH] (checked with the bounds) and,
+ * with U > 0 and held_stride > 0, a null held_group or held_len.  LDS on top of the sibling's: 4 held_stride bytes (mean-variance,
+ * basket: the row of the user being served), 128 held_stride + 128 bytes (plain: the rows of a tile's 16 users, twice, and
+ * their lengths).
+ */
+#define PFO_RECOMMEND_HELD_MAX_WIDTH 256
+int pfo_recommend_topk_capped_held(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                   int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                   const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap, const int32_t* held_group,
+                                   const int32_t* held_len, int32_t held_stride, int32_t k, int32_t* top_pos, float* top_score,
+                                   int32_t* n_valid, void* stream);
+int pfo_recommend_mv_topk_capped_held(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                      int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                      const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap, const int32_t* held_group,
+                                      const int32_t* held_len, int32_t held_stride, const int32_t* cand_stock, const double* returns,
+                                      int32_t n_days, int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                      const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                      int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                      double* y_out, double* fused_out, void* stream);
+int pfo_recommend_basket_topk_capped_held(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                          int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                          const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap,
+                                          const int32_t* held_group, const int32_t* held_len, int32_t held_stride,
+                                          const int32_t* cand_stock, const double* returns, int32_t n_days, int32_t n_stocks,
+                                          int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx, const int32_t* port_len,
+                                          int32_t port_stride, double gamma, double lambda_mv, int32_t k, int32_t* top_pos,
+                                          float* top_score, double* top_fused, int32_t* n_valid, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The list form of the two top-k entries (abi 6, additive): every user ranks a list of its OWN, not the shared candidate list
  * minus an exclusion list.  user_emb, item_emb, user_block, U, I, n_t, D, item_ok, k and the mean-variance arguments mean what
  * they mean in pfo_recommend_topk / pfo_recommend_mv_topk; the exclusion triple gives way to

@@ -17,6 +17,7 @@ RECOMMEND_MAX_ITEMS = 65536     # PFO_RECOMMEND_MAX_ITEMS
 RECOMMEND_MV_MAX_ITEMS = 2048   # PFO_RECOMMEND_MV_MAX_ITEMS
 RECOMMEND_MV_WIDE_MAX_ITEMS = 65536   # PFO_RECOMMEND_MV_WIDE_MAX_ITEMS
 RECOMMEND_LIST_MAX_WIDTH = 256  # PFO_RECOMMEND_LIST_MAX_WIDTH
+RECOMMEND_HELD_MAX_WIDTH = 256  # PFO_RECOMMEND_HELD_MAX_WIDTH
 EVAL_RANK_NONE = (1 << 31) - 1  # PFO_EVAL_RANK_NONE: the positive is not ranked
 ADAM_MAX_RANGES = 16            # PFO_ADAM_MAX_RANGES
 GRAD_NORM_PARTS = 256           # PFO_GRAD_NORM_PARTS
@@ -189,6 +190,17 @@ PROTOTYPES = {
     "pfo_recommend_basket_topk_capped": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                                    _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32,
                                                    C.c_double, C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
+    # the _held forms: (held_group, held_len, held_stride) behind group_cap
+    "pfo_recommend_topk_capped_held": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP,
+                                                 C.c_int32, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_mv_topk_capped_held": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                                    _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP,
+                                                    _VP, _VP, C.c_int32, C.c_double, C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                                    _VP, _VP]),
+    "pfo_recommend_basket_topk_capped_held": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32,
+                                                        _VP, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32,
+                                                        C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double, C.c_int32, _VP, _VP,
+                                                        _VP, _VP, _VP]),
     "pfo_recommend_list_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                           C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     "pfo_recommend_list_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,

@@ -124,6 +124,17 @@ def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, 
     return N, k, cuts, batch_size, horizon, known[0][1], _rows_of_log(exclude, N, "exclude"), _rows_of_log(portfolios, N, "portfolios")
 
 
+def check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log):
+    """``held_groups`` / ``stock_groups`` of ``backtest`` over the whole log, checked once and before any device work (ValueError,
+    the checks of ``recommend``: ``recommend.validate_held_groups``) -> (mode, rows, stock_groups): mode None without them;
+    ``"rows"`` with the packed pair (ids [N, W], lens [N]) on host or device, cut per batch; ``"held"`` / ``"portfolios"`` with
+    ``stock_groups`` as one int32 per stock index.  ``pf_log``: the portfolios as ``check`` left them."""
+    mode, ids, lens, sg = R.validate_held_groups(N, held_groups, stock_groups, groups, tgn.holdings, pf_log, what="the log holds")
+    if mode == R.PORTFOLIOS and not R._is_held(pf_log):
+        R.check_held_width(pf_log[0].shape[1])
+    return mode, (ids, lens) if mode == "rows" else None, sg
+
+
 def ledger_days(ledger, timestamps, horizon, device):
     """(past, future) ring slots i32[n] on ``device`` of a ``PriceLedger`` for the interactions' timestamps (host array, or f64
     device tensor: ``lookup``, no read-back): the slot of the interaction's day and of the day ``horizon`` trading days later;
@@ -158,7 +169,7 @@ def _without(ids, truth):
 
 def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
                   mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
-                  upper_u=None, groups=None, group_cap=None):
+                  upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None):
     """The walk of ``backtest``; returns its per-interaction rows as host arrays after ONE read-back: dict(rank i32[n],
     recall f32[n, n_c], ndcg f32[n, n_c], invest f64[n, 4 n_c], list_item i32[n, k], n_valid i32[n]) - ``list_item`` the served
     lists, rank ``_lib.EVAL_RANK_NONE`` where the item taken is not in the list."""
@@ -166,12 +177,17 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
     N, k, cuts, batch_size, horizon, upper_u, ex_log, pf_log = check(
         tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
         portfolios, upper_u, groups, group_cap)
+    hg_mode, hg_log, stock_groups = check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log)
     dev = tgn.device
     _lib.require_gpu(dev)
     cap = {}
     if groups is not None:
         # on the device once, not once per batch (``recommend`` takes an integer device tensor as it is)
         cap = dict(groups=R._to_dev(dev, groups if torch.is_tensor(groups) else np.asarray(groups), torch.int32), group_cap=group_cap)
+    if hg_mode == "rows":
+        hg_log = (R._to_dev(dev, hg_log[0], torch.int32), R._to_dev(dev, hg_log[1], torch.int32))
+    elif hg_mode is not None:
+        cap.update(held_groups=hg_mode, stock_groups=R._to_dev(dev, stock_groups, torch.int32))
     if torch.is_tensor(items):
         items = items.detach().cpu().numpy()                         # (``recommend`` would read it back per query)
     ledger = isinstance(tables, PriceLedger)
@@ -208,6 +224,10 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
         mv_side = {}
         if mv is not None:
             mv_side = dict(mv=mv, portfolios=pf_log if held_pf else _cut(pf_log, lo, hi), basket=bool(basket))
+        if hg_mode == "rows":
+            cap["held_groups"] = _cut(hg_log, lo, hi)
+        elif hg_mode == R.PORTFOLIOS and mv is None:                  # (the score order: the rows go along for the groups alone)
+            cap["portfolios"] = pf_log if held_pf else _cut(pf_log, lo, hi)
         res = tgn.recommend(sources[lo:hi], edge_times[lo:hi], k, items, exclude=ex, item_ok=item_ok, n_neighbors=n_neighbors, **mv_side, **cap)
         item_ids, n_valid = res[0], res[2]
         pidx, plen = held_rows if held_pf else (_cut(pf_dev, lo, hi) if pf_dev is not None else (None, None))
@@ -231,7 +251,7 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
 
 def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
              mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
-             name="backtest", upper_u=None, groups=None, group_cap=None):
+             name="backtest", upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None):
     """The served lists of a model held against what happened: a prequential walk over a chronological log (numpy arrays like
     the entry points, or device tensors i32 / i32 / f64 / i32).  Per batch ``[lo, hi)`` of ``batch_size`` interactions:
 
@@ -269,8 +289,11 @@ def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cut
     ValueError before any device work: cutoffs not strictly increasing or outside [1, k], k > 64, arrays of unequal length,
     batch_size < 1, ``tables`` of neither kind, a ledger with horizon < 1, ``mv.upper_u`` different from ``tables``', and what
     ``recommend`` refuses of ``groups`` / ``group_cap`` (one without the other, a wrong length, non-integers, a cap below 1,
-    with ``mv`` more than 2048 candidates)."""
+    with ``mv`` more than 2048 candidates) and of ``held_groups`` / ``stock_groups`` - forwarded too, ``held_groups`` over the whole
+    LOG like ``exclude``: a packed pair (ids [N, W], lens [N]), one list of group ids per interaction, ``"held"`` or
+    ``"portfolios"`` (without ``groups``, ``"held"`` without a ledger or ``stock_groups``, rows longer than 256, non-integers)."""
     rows = backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs=cutoffs, batch_size=batch_size,
                          tables=tables, horizon=horizon, mv=mv, basket=basket, exclude=exclude, portfolios=portfolios, item_ok=item_ok,
-                         n_neighbors=n_neighbors, keep_truth=keep_truth, append=append, upper_u=upper_u, groups=groups, group_cap=group_cap)
+                         n_neighbors=n_neighbors, keep_truth=keep_truth, append=append, upper_u=upper_u, groups=groups, group_cap=group_cap,
+                         held_groups=held_groups, stock_groups=stock_groups)
     return backtest_result_dict(name, rows["rank"], rows["invest"], cutoffs)

@@ -54,6 +54,8 @@ struct RecArgs {
   float* top_score;
   const int32_t* cand_group;                  // the capped forms alone: [I], < 0 = in no group; at most group_cap picks a group
   int group_cap;
+  int held_stride;                            // the _held forms alone: held_group i32[U, held_stride], held_len i32[U] - one group id
+  const int32_t *held_group, *held_len;       // per holding of the user (< 0: in no group); a group's count starts from them
 };
 // The mean-variance side (pfo_recommend_mv_topk) but for its five read-only tables, which the kernels take as __restrict__
 // parameters of their own (PFO_REC_MV_TABLES); the three diagnostic outputs are the mv kernel's alone.
@@ -159,6 +161,24 @@ __device__ __forceinline__ int rec_excl_len(const RecArgs& a, int64_t u) {
   return (a.excl_pos && a.excl_stride > 0) ? min(max(a.excl_len[u], 0), a.excl_stride) : 0;
 }
 
+// HELD: how much of user u's held-group row counts
+__device__ __forceinline__ int rec_held_len(const RecArgs& a, int64_t u) {
+  return (a.held_group && a.held_stride > 0) ? min(max(a.held_len[u], 0), a.held_stride) : 0;
+}
+// HELD, the mean-variance and the basket kernel: the row of the user being served into LDS hg[held_stride] (all threads; the
+// caller's next barrier stands behind it); returns its length.  h_u(g) is then rec_held_count(hg, len, g) - every lane reads
+// the same word, a broadcast.
+__device__ __forceinline__ int rec_held_row(int* hg, const RecArgs& a, int64_t u) {
+  const int len = rec_held_len(a, u);
+  for (int p = threadIdx.x; p < len; p += PFO_REC_THREADS) hg[p] = a.held_group[u * a.held_stride + p];
+  return len;
+}
+__device__ __forceinline__ int rec_held_count(const int* hg, int len, int g) {   // (g >= 0: a negative entry matches nothing)
+  int h = 0;
+  for (int p = 0; p < len; ++p) h += (hg[p] == g);
+  return h;
+}
+
 // ---- what the mean-variance and the basket kernel share per user
 struct RecMvUser {
   bool day_ok;          // no day: nothing of this user's is read
@@ -212,8 +232,17 @@ __device__ __forceinline__ bool rec_better(double f, int c, double bf, int bc) {
 // every chunk: once a round's winner is known its group is read (a chunk candidate's from LDS grp[IC] beside ok[], a carried
 // one's from its owner's lg), the picks of that group in next[] are counted with a ballot, and at the cap every lane clears
 // its keys of that group - the chunk's, and the carried list's.
-template <int NJ, bool CAPPED = false>
+// HELD (pfo_recommend_topk_capped_held): the count of a group starts from h_u(g), the entries of the user's held-group row that
+// name it - in every chunk, for a candidate dropped over A has cap - h_u(g) members of its group before it in A, hence in A u B.
+// The rows of the tile's 16 users go to LDS once (hg[16][held_stride], an entry that does not count as -1), and beside them
+// hc[16][held_stride]: the ids whose h_u has reached the cap already - the groups closed from the start - packed to the front of
+// the row, with hn[32]: how much of each hg row counts and how many closed ids each hc row holds.  A user that holds nothing
+// costs nothing: when a chunk is loaded a lane clears the admissible bit of its candidates of every closed group (one broadcast
+// read per candidate and closed id); in a round the entries that name the winner's group are counted with a ballot per 64
+// entries of the row and added to the ballot count of the picks.
+template <int NJ, bool CAPPED = false, bool HELD = false>
 __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const RecArgs a) {
+  static_assert(CAPPED || !HELD, "held rows count against a cap");
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   const int32_t* __restrict__ excl_pos = a.excl_pos;
   const uint8_t* __restrict__ item_ok = a.item_ok;
@@ -225,12 +254,42 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
   float* sc = lds;                                                    // [16][ICS]
   uint8_t* ok = reinterpret_cast<uint8_t*>(sc + PFO_REC_TILE * ICS);  // [IC]
   int* grp = reinterpret_cast<int*>(ok + IC);                         // [IC], CAPPED: the group of a chunk candidate (IC is a multiple of 16)
+  const int HS = HELD ? a.held_stride : 0;
+  int* hg = grp + IC;                                                 // [16][HS], HELD: the held-group rows of the tile's users
+  int* hc = hg + PFO_REC_TILE * HS;                                   // [16][HS], HELD: the ids of the groups closed from the start, packed
+  int* hn = hc + PFO_REC_TILE * HS;                                   // [32], HELD: the length of each hg row, then of each hc row
   __shared__ int ub[PFO_REC_TILE];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
 
   float4 uf[NJ];
   rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  if constexpr (HELD) {
+    if (tid < PFO_REC_TILE) hn[tid] = u0 + tid < a.U ? rec_held_len(a, u0 + tid) : 0;
+    __syncthreads();
+    for (int e = tid; e < PFO_REC_TILE * HS; e += PFO_REC_THREADS) {  // (HS == 0: no entry, and nothing below divides)
+      const int us = e / HS, p = e - us * HS;
+      int g = -1;
+      if (p < hn[us]) g = a.held_group[(u0 + us) * HS + p];
+      hg[e] = g < 0 ? -1 : g;
+    }
+    __syncthreads();
+    for (int e = tid; e < PFO_REC_TILE * HS; e += PFO_REC_THREADS) {
+      const int us = e / HS, g = hg[e];
+      int cnt = 0;
+      if (g >= 0) cnt = rec_held_count(hg + us * HS, hn[us], g);
+      hc[e] = cnt >= a.group_cap ? g : -1;                            // (group_cap >= 1: cnt == 0 closes nothing)
+    }
+    __syncthreads();
+    if (tid < PFO_REC_TILE) {                                         // the closed ids to the front of the row (nc <= p: in place)
+      int nc = 0;
+      for (int p = 0; p < hn[tid]; ++p) {
+        const int g = hc[tid * HS + p];
+        if (g >= 0) hc[tid * HS + nc++] = g;
+      }
+      hn[PFO_REC_TILE + tid] = nc;
+    }                                                                 // (the block table's barrier stands behind it)
+  }
   unsigned pending = rec_block_table(ub, a, u0);
   while (pending) {
     int b;
@@ -278,6 +337,18 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
               if (rj >= 0 && (rj & 63) == lane) adm &= ~(1u << (rj >> 6));
             }
           }
+          if constexpr (HELD) {                                      // the groups closed from the start take no part
+            const int nc = __builtin_amdgcn_readfirstlane(hn[PFO_REC_TILE + us]);
+            if (nc > 0) {
+#pragma unroll 1
+              for (int m = 0; m < PFO_REC_SLOTS; ++m) {                // (a slot at a time: one group id in a register)
+                if (!((adm >> m) & 1u)) continue;
+                const int gc = grp[lane + 64 * m];                     // (an admissible bit: lane + 64 m < n)
+                for (int p = 0; p < nc; ++p)
+                  if (hc[us * HS + p] == gc) adm &= ~(1u << m);        // (the same word for every lane; gc < 0 matches nothing)
+              }
+            }
+          }
         }
 #pragma unroll
         for (int m = 0; m < PFO_REC_SLOTS; ++m) {
@@ -321,7 +392,14 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
             if (lane == t) next[i] = best[i];
             if constexpr (CAPPED) {
               if (lane == t) ng[i] = gw;
-              if (gw >= 0 && __popcll(__ballot(ng[i] == gw)) >= a.group_cap) {   // the group is full: nobody else of it is taken
+              int h = 0;                                             // HELD: what the user holds of the winner's group
+              if constexpr (HELD) {
+                if (gw >= 0) {                                       // (the same for every lane)
+                  const int len = __builtin_amdgcn_readfirstlane(hn[4 * wave + i]);
+                  for (int p0 = 0; p0 < len; p0 += 64) h += __popcll(__ballot(p0 + lane < len && hg[(4 * wave + i) * HS + p0 + lane] == gw));
+                }
+              }
+              if (gw >= 0 && __popcll(__ballot(ng[i] == gw)) + h >= a.group_cap) {   // the group is full: nobody else of it is taken
                 if (lg[i] == gw) list[i] = 0ull;
 #pragma unroll
                 for (int m = 0; m < PFO_REC_SLOTS; ++m)
@@ -383,8 +461,13 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
 // or beyond the cap becomes a NaN in LDS and in its owner's register, and D runs over the survivors as it is.  The diagnostics
 // keep the uncapped values.  About I^2 comparisons more per user, four candidates per LDS read (fused and grp are NaN / -1
 // from I up to the next multiple of 16, and the dynamic part starts 16-byte aligned here).
-template <int NJ, bool CAPPED>
+// HELD (pfo_recommend_mv_topk_capped_held): the count form with a start - a candidate survives iff the same-group candidates
+// before it plus h_u(g) stay below the cap.  The row of the user being ranked lies in LDS behind grp (hg[held_stride], at most
+// 1 KB: 156 928 bytes at I = 2048); a thread counts h for each candidate of its own and, where that alone reaches the cap - a
+// group closed from the start - skips the counting pass for it.
+template <int NJ, bool CAPPED, bool HELD = false>
 __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES) {
+  static_assert(CAPPED || !HELD, "held rows count against a cap");
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   int32_t* __restrict__ top_pos = a.top_pos;
   float *__restrict__ top_score = a.top_score, *__restrict__ score_out = m.score_out;
@@ -400,6 +483,7 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
   }
   float* sc = reinterpret_cast<float*>(yv + IC);                     // [16][ICS]
   int* grp = reinterpret_cast<int*>(sc + PFO_REC_TILE * ICS);        // [IC], CAPPED: the group of every candidate
+  int* hg = grp + IC;                                                // [held_stride], HELD: the held-group row of the user being ranked
   __shared__ int ub[PFO_REC_TILE];
   __shared__ int n_adm;
   const int tid = threadIdx.x;
@@ -427,6 +511,8 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
       const int64_t u = u0 + us;
       const float* su = sc + us * ICS;
       if (tid == 0) n_adm = 0;
+      int hlen = 0;                                                  // HELD: how much of hg counts (rec_mv_exclude's barriers stand behind the row)
+      if constexpr (HELD) hlen = rec_held_row(hg, a, u);
       // ---- B: y_mv, NaN where the candidate is not admissible
       const RecMvUser h(m, returns, day_idx, port_idx, port_len, u);
       for (int c = tid; c < I; c += PFO_REC_THREADS) {
@@ -486,6 +572,13 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
           const int g = grp[c];
           if (g < 0) continue;
           int before = 0;
+          if constexpr (HELD) {                                      // the count starts from what the user holds of the group
+            before = rec_held_count(hg, hlen, g);
+            if (before >= a.group_cap) {                             // closed from the start
+              full |= 1u << s;
+              continue;
+            }
+          }
           const double2* f2 = reinterpret_cast<const double2*>(yv);
           const int4* g4 = reinterpret_cast<const int4*>(grp);
 #pragma unroll 2
@@ -535,9 +628,9 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
 
 // (the body inlined into its kernel, not the kernel itself: written as the kernel, the D <= 176 instantiation takes 165 VGPRs
 // instead of 163 and loses its third wave per SIMD)
-template <int NJ, bool CAPPED = false>
+template <int NJ, bool CAPPED = false, bool HELD = false>
 __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES) {
-  recommend_mv_topk_body<NJ, CAPPED>(a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  recommend_mv_topk_body<NJ, CAPPED, HELD>(a, m, cand_stock, returns, day_idx, port_idx, port_len);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -562,8 +655,13 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(cons
 // reads the pick's group from LDS (grp[IC] behind the scores - no group id lives in a register across a round), counts it among
 // the earlier picks' groups (pick_g[], k ints of LDS: slot r is written in round r and read from round r + 1 on, two barriers
 // later) and, once the group is full, takes its own candidates of that group out: the alive bit, NaN in y and in the score row.
-template <int NJ, bool CAPPED = false>
+// HELD (pfo_recommend_basket_topk_capped_held): the row of the user being served lies in LDS behind grp (hg[held_stride], as in
+// the mean-variance kernel).  In B the owner of a candidate counts h_u of its group and keeps a candidate of a group closed from
+// the start out of the pool - no alive bit, NaN in y and in the score row, so it takes part in no rank count of round 0 either;
+// after a pick every thread starts the pick's count from h_u(gw), one broadcast read per entry of the row.
+template <int NJ, bool CAPPED = false, bool HELD = false>
 __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES) {
+  static_assert(CAPPED || !HELD, "held rows count against a cap");
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   int32_t* __restrict__ top_pos = a.top_pos;
   float* __restrict__ top_score = a.top_score;
@@ -579,6 +677,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
   __shared__ int wave_c[PFO_REC_THREADS / 64];
   int* grp = reinterpret_cast<int*>(sc + PFO_REC_TILE * ICS);        // [IC], CAPPED: the group of every candidate
   __shared__ int pick_g[CAPPED ? 64 : 1];                            // CAPPED: the group of pick r of the user being served
+  int* hg = grp + IC;                                                // [held_stride], HELD: the held-group row of the user being served
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
   const double nan = __builtin_nan("");
@@ -602,6 +701,8 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
       float* su = sc + us * ICS;                                     // the user's scores; NaN where the candidate takes no part
       const RecMvUser h(m, returns, day_idx, port_idx, port_len, u);
       const double* dayp = h.dayp;
+      int hlen = 0;                                                  // HELD: how much of hg counts (rec_mv_exclude's barriers stand behind the row)
+      if constexpr (HELD) hlen = rec_held_row(hg, a, u);
       // ---- B: the admissible set, then mu, var and the covariance sum over the portfolio
       for (int c = tid; c < IC; c += PFO_REC_THREADS) yv[c] = c < I && rec_mv_stock(a, cand_stock, m.n_stocks, c, h.day_ok) >= 0 ? 0.0 : nan;
       rec_mv_exclude(yv, a, u);
@@ -613,6 +714,12 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
         const int c = tid + PFO_REC_THREADS * s;
         mu[s] = var[s] = ssum[s] = 0.0;
         score[s] = 0.f;
+        if constexpr (HELD) {                                        // a group closed from the start is not in the pool of round 0
+          if (c < I && yv[c] == yv[c]) {
+            const int g = grp[c];
+            if (g >= 0 && rec_held_count(hg, hlen, g) >= a.group_cap) yv[c] = nan;   // (the owner's slot: nobody else reads it here)
+          }
+        }
         if (c < I && yv[c] == yv[c]) {
           alive |= 1u << s;
           score[s] = su[c];
@@ -723,6 +830,7 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_basket_topk_kernel(
           if (tid == 0) pick_g[rd] = gw;
           if (gw >= 0) {
             int held = 1;
+            if constexpr (HELD) held += rec_held_count(hg, hlen, gw);
             for (int r = 0; r < rd; ++r) held += (pick_g[r] == gw);
             if (held >= a.group_cap) {                               // the group is full: it leaves the pool
 #pragma unroll
@@ -1326,6 +1434,15 @@ int rec_check_groups(const char* who, const int32_t* cand_group) {
   PFO_REC_REQUIRE(cand_group, "null cand_group");
   return PFO_OK;
 }
+// the _held forms' own bound, with the cap's, and their rows (U > 0), with the group row
+int rec_check_held_stride(const char* who, int held_stride) {
+  PFO_REC_REQUIRE(held_stride >= 0 && held_stride <= PFO_RECOMMEND_HELD_MAX_WIDTH, "held_stride must be in [0, PFO_RECOMMEND_HELD_MAX_WIDTH]");
+  return PFO_OK;
+}
+int rec_check_held_rows(const char* who, const int32_t* held_group, const int32_t* held_len, int held_stride) {
+  PFO_REC_REQUIRE(held_stride == 0 || (held_group && held_len), "null held_group or held_len");
+  return PFO_OK;
+}
 int rec_check_list_rows(const char* who, const int32_t* list_pos, const int32_t* list_len) {
   PFO_REC_REQUIRE(list_pos && list_len, "null list_pos or list_len");
   return PFO_OK;
@@ -1337,12 +1454,16 @@ constexpr size_t rec_score_bytes(int IC) { return (size_t)PFO_REC_TILE * (IC + 4
 inline int rec_mv_ic(int I) { return (int)pfo_align_up(I, 16); }
 constexpr size_t rec_mv_bytes(int IC) { return (size_t)IC * sizeof(double) + rec_score_bytes(IC); }
 constexpr size_t rec_group_bytes(int IC) { return (size_t)IC * sizeof(int32_t); }   // grp[IC] of a capped kernel, behind the rest
+// the held-group rows of a _held kernel, behind grp: `rows` of them (the plain kernel holds hg and hc of its 16 users, the other
+// two the row of the user being served)
+constexpr size_t rec_held_bytes(int rows, int held_stride) { return (size_t)rows * held_stride * sizeof(int32_t); }
 
 // One workgroup per 16 users of a kernel template (times `grid_y`: the wide form's candidate chunks), in the instantiation that
 // covers a row of a.D floats, with `shmem` bytes of LDS.  `kernel_of` (PFO_REC_KERNEL) names the template: it maps
 // std::integral_constant<int, NJ> to the instantiation.
 #define PFO_REC_KERNEL(name) [](auto nj) { return &name<decltype(nj)::value>; }
 #define PFO_REC_KERNEL_CAPPED(name) [](auto nj) { return &name<decltype(nj)::value, true>; }
+#define PFO_REC_KERNEL_HELD(name) [](auto nj) { return &name<decltype(nj)::value, true, true>; }
 template <class KernelOf, class... Args>
 int rec_launch_grid(const char* who, KernelOf kernel_of, size_t shmem, unsigned grid_y, void* stream, const RecArgs& a, const Args&... more) {
   auto launch = [&](auto nj) -> int {
@@ -1486,6 +1607,81 @@ extern "C" int pfo_recommend_basket_topk_capped(const float* user_emb, const flo
   if (rc != PFO_OK) return rc;
   return rec_launch(__func__, PFO_REC_KERNEL_CAPPED(recommend_basket_topk_kernel), rec_mv_bytes(a.IC) + rec_group_bytes(a.IC), stream, a, m,
                     cand_stock, returns, day_idx, port_idx, port_len);
+}
+
+// The _held forms: the capped sibling's argument blocks and checks, the three held arguments on top, the HELD instantiation.
+#define PFO_REC_HELD_ARGS(ic)      \
+  PFO_REC_CAPPED_ARGS(ic);         \
+  a.held_stride = held_stride;     \
+  a.held_group = held_group;       \
+  a.held_len = held_len
+
+extern "C" int pfo_recommend_topk_capped_held(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U,
+                                              int32_t I, int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len,
+                                              int32_t excl_stride, const uint8_t* item_ok, const int32_t* cand_group, int32_t group_cap,
+                                              const int32_t* held_group, const int32_t* held_len, int32_t held_stride, int32_t k,
+                                              int32_t* top_pos, float* top_score, int32_t* n_valid, void* stream) {
+  PFO_REC_HELD_ARGS((int)pfo_align_up(I < PFO_REC_CHUNK ? I : PFO_REC_CHUNK, 16));
+  int rc = rec_check_cap(__func__, group_cap);
+  if (rc == PFO_OK) rc = rec_check_held_stride(__func__, held_stride);
+  if (rc == PFO_OK)
+    rc = rec_check_common(__func__, a, PFO_RECOMMEND_MAX_ITEMS, "I must be in [1, PFO_RECOMMEND_MAX_ITEMS]", "excl_stride must not be negative");
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_groups(__func__, cand_group);
+  if (rc == PFO_OK) rc = rec_check_held_rows(__func__, held_group, held_len, held_stride);
+  if (rc != PFO_OK) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL_HELD(recommend_topk_kernel),
+                    rec_score_bytes(a.IC) + (size_t)a.IC + rec_group_bytes(a.IC) + rec_held_bytes(2 * PFO_REC_TILE, held_stride) +
+                        2 * PFO_REC_TILE * sizeof(int32_t),
+                    stream, a);                                      // (+ ok[IC] + grp[IC] + hg, hc[16][held_stride] + hn[32])
+}
+
+extern "C" int pfo_recommend_mv_topk_capped_held(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U,
+                                                 int32_t I, int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len,
+                                                 int32_t excl_stride, const uint8_t* item_ok, const int32_t* cand_group,
+                                                 int32_t group_cap, const int32_t* held_group, const int32_t* held_len,
+                                                 int32_t held_stride, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                                 int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                                 const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                                 int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid,
+                                                 float* score_out, double* y_out, double* fused_out, void* stream) {
+  PFO_REC_HELD_ARGS(rec_mv_ic(I));
+  const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
+  int rc = rec_check_cap(__func__, group_cap);
+  if (rc == PFO_OK) rc = rec_check_held_stride(__func__, held_stride);
+  if (rc == PFO_OK) rc = rec_check_mv_bounds(__func__, m);         // (ahead of rec_check_mv, which ends on the pointers)
+  if (rc == PFO_OK) rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_groups(__func__, cand_group);
+  if (rc == PFO_OK) rc = rec_check_held_rows(__func__, held_group, held_len, held_stride);
+  if (rc != PFO_OK) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL_HELD(recommend_mv_topk_kernel),
+                    rec_mv_bytes(a.IC) + rec_group_bytes(a.IC) + rec_held_bytes(1, held_stride), stream, a, m, cand_stock, returns, day_idx,
+                    port_idx, port_len);
+}
+
+extern "C" int pfo_recommend_basket_topk_capped_held(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U,
+                                                     int32_t I, int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len,
+                                                     int32_t excl_stride, const uint8_t* item_ok, const int32_t* cand_group,
+                                                     int32_t group_cap, const int32_t* held_group, const int32_t* held_len,
+                                                     int32_t held_stride, const int32_t* cand_stock, const double* returns,
+                                                     int32_t n_days, int32_t n_stocks, int32_t n_ret, const int32_t* day_idx,
+                                                     const int32_t* port_idx, const int32_t* port_len, int32_t port_stride, double gamma,
+                                                     double lambda_mv, int32_t k, int32_t* top_pos, float* top_score, double* top_fused,
+                                                     int32_t* n_valid, void* stream) {
+  PFO_REC_HELD_ARGS(rec_mv_ic(I));
+  const RecMvArgs m = PFO_REC_MV_ARGS(nullptr, nullptr, nullptr);
+  int rc = rec_check_cap(__func__, group_cap);
+  if (rc == PFO_OK) rc = rec_check_held_stride(__func__, held_stride);
+  if (rc == PFO_OK) rc = rec_check_mv_bounds(__func__, m);         // (ahead of rec_check_mv, which ends on the pointers)
+  if (rc == PFO_OK) rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_groups(__func__, cand_group);
+  if (rc == PFO_OK) rc = rec_check_held_rows(__func__, held_group, held_len, held_stride);
+  if (rc != PFO_OK) return rc;
+  return rec_launch(__func__, PFO_REC_KERNEL_HELD(recommend_basket_topk_kernel),
+                    rec_mv_bytes(a.IC) + rec_group_bytes(a.IC) + rec_held_bytes(1, held_stride), stream, a, m, cand_stock, returns, day_idx,
+                    port_idx, port_len);
 }
 
 extern "C" int64_t pfo_recommend_mv_wide_workspace_bytes(int64_t U, int32_t I) {

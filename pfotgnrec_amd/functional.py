@@ -472,10 +472,16 @@ def _score_dims(n_blocks, item_ok, user_block):
     return dims
 
 
-def _recommend_cap(cand_group, group_cap):
-    """The two cap keywords of the shared-list top-k forms, checked: None without them, else (cand_group, group_cap) - the
-    length of ``cand_group`` is checked where I is known (``_capped_dims``), its device with the other tensors'."""
+def _recommend_cap(cand_group, group_cap, held_group=None, held_len=None):
+    """The cap keywords of the shared-list top-k forms, checked: None without them, else (cand_group, group_cap) - the
+    length of ``cand_group`` is checked where I is known (``_capped_dims``), its device with the other tensors'.  With
+    ``held_group`` i32[U, W] (W at most ``RECOMMEND_HELD_MAX_WIDTH``; ``held_len`` i32[U], None: the whole row) the tuple is
+    (cand_group, group_cap, held_group, held_len) and the ``_held`` entry is called; the rows need the cap pair."""
     import operator
+    if held_group is None and held_len is not None:
+        raise ValueError("held_len without held_group")
+    if held_group is not None and (cand_group is None or group_cap is None):
+        raise ValueError("held_group needs cand_group and group_cap: holdings count against a cap")
     if cand_group is None and group_cap is None:
         return None
     if cand_group is None or group_cap is None:
@@ -488,11 +494,21 @@ def _recommend_cap(cand_group, group_cap):
         raise ValueError("group_cap must be an integer") from None
     if group_cap < 1:
         raise ValueError("group_cap must be at least 1 (got %d)" % group_cap)
-    return cand_group, min(group_cap, 64)                            # (k <= 64: a cap beyond it never binds)
+    if held_group is None:
+        return cand_group, min(group_cap, 64)                        # (k <= 64: a cap beyond it never binds)
+    if not isinstance(held_group, torch.Tensor) or held_group.dim() != 2 or held_group.dtype != torch.int32:
+        raise ValueError("held_group must be int32 [U, W]")
+    if held_group.shape[1] > _lib.RECOMMEND_HELD_MAX_WIDTH:
+        raise ValueError("held_group must have at most %d columns (got %d)" % (_lib.RECOMMEND_HELD_MAX_WIDTH, held_group.shape[1]))
+    if held_len is not None and (not isinstance(held_len, torch.Tensor) or held_len.dim() != 1 or held_len.dtype != torch.int32):
+        raise ValueError("held_len must be int32 [U]")
+    # (picks and holdings together stay below 64 + 256: a cap beyond int32 never binds either)
+    return cand_group, min(group_cap, (1 << 31) - 1), held_group, held_len
 
 
 def _capped_dims(dims, cap):
-    """``dims`` of ``_recommend_check`` with the length of ``cand_group`` held to the I it finds (``cap`` None: ``dims`` itself)."""
+    """``dims`` of ``_recommend_check`` with the length of ``cand_group`` held to the I it finds, and the held rows to U
+    (``cap`` None: ``dims`` itself)."""
     if cap is None:
         return dims
 
@@ -500,12 +516,30 @@ def _capped_dims(dims, cap):
         I, n_t = dims(U, rows)
         if cap[0].shape[0] != I:
             raise ValueError("cand_group holds %d entries, the candidate list %d" % (cap[0].shape[0], I))
+        if len(cap) > 2 and (cap[2].shape[0] != U or cap[3] is not None and cap[3].shape[0] != U):
+            raise ValueError("held_group and held_len must hold one row per user (%d)" % U)
         return I, n_t
     return capped
 
 
+def _cap_call(symbol, cap, dev):
+    """(symbol, arguments, the tensors the arguments point into) of a capped launch behind item_ok: ``symbol`` + "_capped" with
+    (cand_group, group_cap), or ``symbol`` + "_capped_held" with (held_group, held_len, held_stride) behind them - null
+    pointers without a column."""
+    group = cap[0].contiguous()
+    args = (_lib.ptr(group), cap[1])
+    if len(cap) == 2:
+        return symbol + "_capped", args, (group,)
+    held_group, held_len = cap[2], cap[3]
+    W = int(held_group.shape[1])
+    if W and held_len is None:
+        held_len = torch.full((held_group.shape[0],), W, dtype=torch.int32, device=dev)
+    rows = (held_group.contiguous(), held_len.contiguous()) if W else (None, None)
+    return symbol + "_capped_held", args + (_lib.ptr(rows[0]), _lib.ptr(rows[1]), W), (group,) + rows
+
+
 def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, cand_group=None,
-                   group_cap=None):
+                   group_cap=None, held_group=None, held_len=None):
     """The k best candidates per user in one launch (``pfo_recommend_topk``); nothing but its outputs is written.
 
     user_emb f32[U,D]; item_emb f32[n_t*I,D]: n_t blocks of the same I candidates (embedded at n_t times); user_block
@@ -520,19 +554,25 @@ def recommend_topk(user_emb, item_emb, k, user_block=None, excl_pos=None, excl_l
 
     ``cand_group`` i32[I] with ``group_cap`` >= 1 (both or neither; ``pfo_recommend_topk_capped``): the list is the walk over
     that order that skips a candidate whose group - any non-negative id; negative: no group, never capped - holds ``group_cap``
-    picks already.  Scores are the uncapped ones; n_valid counts what was taken."""
-    cap = _recommend_cap(cand_group, group_cap)
+    picks already.  Scores are the uncapped ones; n_valid counts what was taken.
+
+    ``held_group`` i32[U,Wh] (at most 256 columns, padded with -1) with ``held_len`` i32[U] (None: the whole row), beside the
+    cap pair (``pfo_recommend_topk_capped_held``): one group id per holding of the user; the count of a group starts from the
+    entries of the row that name it, so a held name uses up quota and a group held ``group_cap`` times is closed from the
+    start.  Negative entries count for nothing, an id named twice counts twice."""
+    cap = _recommend_cap(cand_group, group_cap, held_group, held_len)
     dims = _capped_dims(_score_dims(n_blocks, item_ok, user_block), cap)
     user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
-        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, cap[:1] if cap else ())
+        user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims, cap[:1] + cap[2:] if cap else ())
     dev = user_emb.device
     top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
     top_score = torch.empty((U, k), dtype=torch.float32, device=dev)
     n_valid = torch.empty(U, dtype=torch.int32, device=dev)
     if cap is not None:
-        _lib.call("pfo_recommend_topk_capped", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D,
-                  _lib.ptr(excl_pos), _lib.ptr(excl_len), W, _lib.ptr(item_ok), _lib.ptr(cap[0].contiguous()), cap[1], k, top_pos.data_ptr(),
-                  top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
+        symbol, cap_args, _alive = _cap_call("pfo_recommend_topk", cap, dev)
+        _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos),
+                  _lib.ptr(excl_len), W, _lib.ptr(item_ok), *cap_args, k, top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(),
+                  _lib.stream_ptr())
         return top_pos, top_score, n_valid
     _lib.call("pfo_recommend_topk", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos),
               _lib.ptr(excl_len), W, _lib.ptr(item_ok), k, top_pos.data_ptr(), top_score.data_ptr(), n_valid.data_ptr(), _lib.stream_ptr())
@@ -582,7 +622,7 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
     (``diagnostics``: allocate them or pass NULL) or without them (None).  ``max_items``: the symbol's bound on I.
     ``workspace``: for a symbol that takes (workspace, workspace_bytes) before the stream - a uint8 tensor, or None: allocated
     (what serves all users at once, 256 MiB at the most, the minimum at the least).  ``cap``: what ``_recommend_cap`` returns -
-    with one, ``symbol`` + "_capped" is called, the two cap arguments behind item_ok."""
+    with one, ``symbol`` + "_capped" (with held rows: + "_capped_held") is called, its arguments behind item_ok (``_cap_call``)."""
     def check_workspace(U, I):
         if workspace is not _NO_WORKSPACE and workspace is not None:
             if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
@@ -596,7 +636,7 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
 
     user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
         user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims,
-        (cand_stock, returns, day_idx, port_idx, port_len) + (cap[:1] if cap else ()))
+        (cand_stock, returns, day_idx, port_idx, port_len) + (cap[:1] + cap[2:] if cap else ()))
     dev = user_emb.device
     n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
     Wp = int(port_idx.shape[1]) if port_idx is not None else 0
@@ -620,7 +660,7 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
         ws = (workspace.data_ptr(), workspace.numel())
     cap_args = ()
     if cap is not None:
-        symbol, cap_args = symbol + "_capped", (_lib.ptr(cap[0].contiguous()), cap[1])
+        symbol, cap_args, _alive = _cap_call(symbol, cap, dev)
     _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos), _lib.ptr(excl_len),
               W, _lib.ptr(item_ok), *cap_args, _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks, n_ret,
               _lib.ptr(day_idx.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None),
@@ -629,7 +669,8 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
 
 
 def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
-                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False, cand_group=None, group_cap=None):
+                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False, cand_group=None, group_cap=None,
+                      held_group=None, held_len=None):
     """``recommend_topk`` with the mean-variance rank fusion of main.py:243-289 over every user's whole candidate list, in one
     launch (``pfo_recommend_mv_topk``).
 
@@ -646,10 +687,11 @@ def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_
 
     ``cand_group`` i32[I] with ``group_cap`` >= 1 (both or neither; ``pfo_recommend_mv_topk_capped``): the walk over that order
     skips a candidate whose group (negative: none) holds ``group_cap`` picks already.  Ranks, fused and the ``want_all`` arrays
-    are the uncapped ones - a cap changes no rank."""
+    are the uncapped ones - a cap changes no rank.  ``held_group`` / ``held_len`` beside them (``recommend_topk`` describes the
+    rows; ``pfo_recommend_mv_topk_capped_held``): the count of a group starts from what the user holds of it."""
     return _recommend_mv_launch("pfo_recommend_mv_topk", bool(want_all), user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
                                 port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks,
-                                cap=_recommend_cap(cand_group, group_cap))
+                                cap=_recommend_cap(cand_group, group_cap, held_group, held_len))
 
 
 def recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
@@ -668,7 +710,8 @@ def recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, 
 
 
 def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
-                          excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, cand_group=None, group_cap=None):
+                          excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, cand_group=None, group_cap=None, held_group=None,
+                          held_len=None):
     """``recommend_mv_topk`` taken one pick at a time, in one launch (``pfo_recommend_basket_topk``): pick r is the first of the
     canonical order of round r, in which the stocks of picks 0 .. r-1 count as held behind ``port_idx[u]`` (in pick order) and
     their positions have left the pool; only the position leaves - another candidate on the same stock stays.  Arguments and
@@ -681,10 +724,12 @@ def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, p
 
     ``cand_group`` i32[I] with ``group_cap`` >= 1 (both or neither; ``pfo_recommend_basket_topk_capped``): a group (negative:
     none) that holds ``group_cap`` picks leaves the pool - its candidates take part in no later round, like excluded ones.  Any
-    k then equals the k = 1 loop above with every other candidate of a full group appended to the exclusion row as well."""
+    k then equals the k = 1 loop above with every other candidate of a full group appended to the exclusion row as well.
+    ``held_group`` / ``held_len`` beside them (``recommend_topk`` describes the rows; ``pfo_recommend_basket_topk_capped_held``):
+    a group is full at picks + holdings >= ``group_cap``, and one that the holdings alone fill is out of the pool of round 0 too."""
     return _recommend_mv_launch("pfo_recommend_basket_topk", None, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
                                 port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks,
-                                cap=_recommend_cap(cand_group, group_cap))
+                                cap=_recommend_cap(cand_group, group_cap, held_group, held_len))
 
 
 def _recommend_list_check(user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, dims, also=()):

@@ -4,7 +4,8 @@ a mean-variance side (``validate_mv``), ``pfo_recommend_mv_topk`` (beyond 2048 c
 rank twice, blend and select; with ``basket`` on top
 of that, ``pfo_recommend_basket_topk`` re-rank after every pick.  With ``only=`` every user ranks a list of its own:
 ``pfo_recommend_list_topk`` / ``pfo_recommend_list_mv_topk``.  With ``groups=`` / ``group_cap=`` (``validate_groups``) the three
-shared-list launches take their capped entries: at most ``group_cap`` picks of a group in a user's list."""
+shared-list launches take their capped entries: at most ``group_cap`` picks of a group in a user's list; with ``held_groups=``
+(``validate_held_groups``) their ``_held`` entries: the count of a group starts from what the user holds of it."""
 import collections
 import operator
 
@@ -15,12 +16,13 @@ from . import _lib
 from .prices import PriceLedger
 
 Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held "
-                               "only_ids only_len only_held groups group_cap basket",
-                               defaults=(None, None, None, None, False, None, None, False))
+                               "only_ids only_len only_held groups group_cap held_mode hg_ids hg_len stock_groups basket",
+                               defaults=(None, None, None, None, False, None, None, None, None, None, None, False))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
 # (with a PriceLedger as the owner: the ORDINAL among its live days, or None - the day is looked up on the device)
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
 HELD = "held"     # ``exclude`` / ``portfolios``: take the rows of the model's holdings ledger (port_idx is None in the MVQuery then)
+PORTFOLIOS = "portfolios"   # ``held_groups``: the rows of ``portfolios=``, mapped to groups through ``stock_groups``
 
 
 def _is_held(a):
@@ -166,8 +168,60 @@ def validate_groups(I, groups, group_cap, only=None, mv=None):
     return g, group_cap
 
 
+def check_held_width(width):
+    """A row of ``held_groups="portfolios"`` is a portfolio row: ``width`` columns must fit the held-group row (ValueError)."""
+    if width > _lib.RECOMMEND_HELD_MAX_WIDTH:
+        raise ValueError('held_groups="portfolios": rows of up to %d stocks, at most %d' % (width, _lib.RECOMMEND_HELD_MAX_WIDTH))
+
+
+def validate_held_groups(U, held_groups, stock_groups, groups, holdings=None, portfolios=None, what="users holds"):
+    """``held_groups`` / ``stock_groups`` of ``TGN.recommend`` and ``backtest`` checked on the host (ValueError) ->
+    (mode, ids, lens, stock_groups): all None without ``held_groups``; mode ``HELD`` / ``PORTFOLIOS`` - the rows are the
+    ledger's / the query's portfolios, mapped through ``stock_groups`` (one int32 per stock index, host array or the caller's
+    integer device tensor) on the device; mode ``"rows"`` - ids i32[U, W] padded with -1 and lens [U], group ids as given (lists
+    packed on the host, a packed pair as it is).  ``U`` rows are expected (``what``: who counts them)."""
+    if held_groups is None:
+        if stock_groups is not None:
+            raise ValueError("stock_groups without held_groups: it maps the stocks of held_groups=\"held\" / \"portfolios\" to groups")
+        return None, None, None, None
+    if groups is None:
+        raise ValueError("held_groups needs groups and group_cap: holdings count against a cap")
+    by_stock = isinstance(held_groups, str)
+    if by_stock:
+        if held_groups not in (HELD, PORTFOLIOS):
+            raise ValueError('held_groups must be "held", "portfolios", a list of per-user lists of group ids or a packed (ids, lens) pair')
+        if held_groups == HELD and holdings is None:
+            raise ValueError('held_groups="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
+        if held_groups == PORTFOLIOS and portfolios is None:
+            raise ValueError('held_groups="portfolios" needs portfolios (and mv): the rows it maps to groups')
+        if stock_groups is None:
+            raise ValueError('held_groups="%s" needs stock_groups: one group id per stock index' % held_groups)
+        try:
+            sg = stock_groups if isinstance(stock_groups, torch.Tensor) else np.asarray(stock_groups)
+        except (TypeError, ValueError):
+            raise ValueError("stock_groups must hold one integer per stock index") from None
+        if sg.ndim != 1 or not _is_int_array(sg) and (isinstance(sg, torch.Tensor) or sg.size):
+            raise ValueError("stock_groups must hold one integer per stock index: a 1-D array of integer group ids (negative: no group)")
+        if isinstance(sg, np.ndarray):
+            if sg.size and (int(sg.min()) < -(1 << 31) or int(sg.max()) >= (1 << 31)):
+                raise ValueError("stock_groups holds ids that do not fit 32 bits")
+            sg = sg.astype(np.int32)
+        return held_groups, None, None, sg
+    if stock_groups is not None:
+        raise ValueError("stock_groups goes with held_groups=\"held\" / \"portfolios\": explicit rows hold group ids already")
+    ids, lens = _pack_rows(
+        held_groups, U, True, "packed held_groups must be (ids [U,W], lens [U]) with U = %d", "packed held_groups: %s must be integers",
+        ("ids", "lens"), 'held_groups must be "held", "portfolios", a list of per-user lists of integer group ids or a packed (ids, lens) pair',
+        "held_groups lists %d users, " + what + " %d", "held_groups holds ids that do not fit 32 bits")
+    if ids.shape[1] > _lib.RECOMMEND_HELD_MAX_WIDTH:
+        raise ValueError("held_groups lists up to %d ids for a user, at most %d" % (ids.shape[1], _lib.RECOMMEND_HELD_MAX_WIDTH))
+    if isinstance(ids, np.ndarray) and ids.size and (int(ids.min()) < -(1 << 31) or int(ids.max()) >= (1 << 31)):
+        raise ValueError("held_groups holds ids that do not fit 32 bits")
+    return "rows", ids, lens, None
+
+
 def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
-             day_idx=None, holdings=None, basket=False, only=None, *, groups=None, group_cap=None):
+             day_idx=None, holdings=None, basket=False, only=None, *, groups=None, group_cap=None, held_groups=None, stock_groups=None):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
     if only is not None and exclude is not None:
@@ -233,12 +287,32 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
         if only_ids.shape[1] > _lib.RECOMMEND_LIST_MAX_WIDTH:
             raise ValueError("only lists up to %d ids for a user, at most %d" % (only_ids.shape[1], _lib.RECOMMEND_LIST_MAX_WIDTH))
     groups, group_cap = validate_groups(I, groups, group_cap, only, mv)
+    hg_ports = None                                                  # held_groups="portfolios" in the score order: the rows serve it alone
+    if mv is None and day_idx is None and portfolios is not None and isinstance(held_groups, str) and held_groups == PORTFOLIOS:
+        hg_ports, portfolios = portfolios, None
     # (the list form ranks the list alone: with ``only`` the mean-variance order is bound by nothing but the plain bound on I)
     mvq = validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings,
                       max_items=_lib.RECOMMEND_MV_MAX_ITEMS if basket else _lib.RECOMMEND_MV_WIDE_MAX_ITEMS)
+    held_mode, hg_ids, hg_len, stock_groups = validate_held_groups(U, held_groups, stock_groups, groups, holdings,
+                                                                   hg_ports if mvq is None else portfolios)
+    if held_mode == PORTFOLIOS and mvq is None:
+        if _is_held(hg_ports):                                       # the ledger's rows under their other name
+            if holdings is None:
+                raise ValueError('portfolios="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
+            held_mode = HELD
+        else:
+            hg_ids, hg_len = _pack_rows(
+                hg_ports, U, True, "packed portfolios must be (port_idx [U,W], port_len [U]) with U = %d",
+                "packed portfolios: %s must be integers", ("port_idx", "port_len"),
+                "portfolios must be a packed (port_idx, port_len) pair or one list of integer stock indices per user",
+                "portfolios lists %d users, users holds %d", "portfolios holds indices that do not fit 32 bits")
+            check_held_width(hg_ids.shape[1])
+    elif held_mode == PORTFOLIOS and mvq.port_idx is not None:
+        check_held_width(mvq.port_idx.shape[1])
     held = (_is_held(exclude), mvq is not None and mvq.port_idx is None)
     return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
-                 held if any(held) else None, only_ids, only_len, _is_held(only), groups, group_cap, bool(basket))
+                 held if any(held) else None, only_ids, only_len, _is_held(only), groups, group_cap, held_mode, hg_ids, hg_len,
+                 stock_groups, bool(basket))
 
 
 def _to_dev(dev, a, dtype):
@@ -304,7 +378,9 @@ def assemble(tgn, q, return_embeddings=False):
             return out
         excl_pos = excl_len = held_ports = None
         ex_held, port_held = q.held or (False, False)
-        if ex_held or port_held or q.only_held:
+        group_held = q.held_mode == HELD                               # held_groups="held": the ledger rows, as groups
+        h_idx = h_len = None
+        if ex_held or port_held or q.only_held or group_held:
             # one gather for whoever asks: the ledger rows of the users, and their stocks as candidate positions
             h_idx, h_len, h_pos = tgn.holdings.gather(users_d, items_d if ex_held or q.only_held else None)
             if ex_held or q.only_held:
@@ -331,14 +407,40 @@ def assemble(tgn, q, return_embeddings=False):
         cap = {}                                                     # (never with ``only``: validate refuses it)
         if q.groups is not None:
             cap = dict(cand_group=to_dev(q.groups, torch.int32), group_cap=q.group_cap)
+        held_rows = ()                                               # (held_group, held_len): per-user rows, they follow the block sort
+        if q.held_mode == "rows":
+            held_rows = (to_dev(q.hg_ids, torch.int32), to_dev(q.hg_len, torch.int32))
+        elif q.held_mode is not None:
+            if q.hg_ids is not None:                                 # held_groups="portfolios" in the score order: the rows are the query's own
+                s_idx, s_len = to_dev(q.hg_ids, torch.int32), to_dev(q.hg_len, torch.int32)
+            elif group_held or q.mv.port_idx is None:                # the ledger's rows (also portfolios="held" asked for as groups)
+                s_idx, s_len = h_idx, h_len
+            else:
+                s_idx, s_len = to_dev(q.mv.port_idx, torch.int32), to_dev(q.mv.port_len, torch.int32)
+            held_rows = (stock_rows_to_groups(s_idx, to_dev(q.stock_groups, torch.int32)), s_len)
         if q.mv is not None:
             return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                                held_ports, user_ts, listed, cap)
+                                held_ports, user_ts, listed, cap, held_rows)
         if listed:
             launch = lambda ub, ue, pos, ln: recommend_list_topk(ue, item_emb, k, pos, ln, ub, ok_d, n_blocks=n_t)
         else:
-            launch = lambda ub, ue, pos, ln: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t, **cap)
-        return _select(launch, (user_emb, excl_pos, excl_len), user_block, n_t, items_d, item_emb, return_embeddings, sort=not listed)
+            launch = lambda ub, ue, pos, ln, *held: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t, **cap, **_held_kw(held))
+        return _select(launch, (user_emb, excl_pos, excl_len) + held_rows, user_block, n_t, items_d, item_emb, return_embeddings,
+                       sort=not listed)
+
+
+def stock_rows_to_groups(idx, stock_groups):
+    """Rows of stock indices i32[U, W] -> rows of group ids through ``stock_groups`` i32[S], both on the device: an index outside
+    [0, S) - the -1 padding too - gives -1, a holding in no group.  No read-back."""
+    S = int(stock_groups.shape[0])
+    if S == 0 or idx.shape[1] == 0:
+        return torch.full_like(idx, -1)
+    inside = (idx >= 0) & (idx < S)
+    return torch.where(inside, stock_groups[idx.clamp(0, S - 1).long()], torch.full_like(idx, -1)).contiguous()
+
+
+def _held_kw(held):
+    return dict(held_group=held[0], held_len=held[1]) if held else {}
 
 
 def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddings, sort=True):
@@ -366,14 +468,15 @@ def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddi
 
 
 def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                 held_ports=None, user_ts=None, listed=False, cap=None):
+                 held_ports=None, user_ts=None, listed=False, cap=None, held_rows=()):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
     portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held").
     ``q.basket``: ``recommend_basket_topk`` in its place; more than 2048 candidates: ``recommend_mv_topk_wide``.  With a ``PriceLedger`` the kernels index its storage by ring slot:
     day ordinals become slots, no day index at all is ``pfo_day_lookup`` over ``user_ts`` f64[U] on the device.
     ``listed``: ``excl_pos`` / ``excl_len`` are the users' own lists (``only=``) - ``recommend_list_mv_topk`` whatever I is, no
     workspace and no sort by block.  ``cap``: the cap keywords of the bounded and the basket launch (empty: uncapped; validate
-    lets them through with neither ``only`` nor more than 2048 candidates)."""
+    lets them through with neither ``only`` nor more than 2048 candidates).  ``held_rows``: (held_group, held_len) of the users
+    or nothing - they follow the users through the block sort like the portfolio rows."""
     from .functional import recommend_basket_topk, recommend_list_mv_topk, recommend_mv_topk, recommend_mv_topk_wide
     topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
     if q.I > _lib.RECOMMEND_MV_MAX_ITEMS:                             # (never the basket: validate refuses it)
@@ -387,14 +490,15 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
         port_idx = to_dev(q.mv.port_idx, torch.int32) if q.mv.port_idx.shape[1] > 0 else None
         port_len = to_dev(q.mv.port_len, torch.int32) if port_idx is not None else None
 
-    def launch(ub, ue, pos, ln, day, port_idx, port_len):
+    def launch(ub, ue, pos, ln, day, port_idx, port_len, *held):
         if listed:
             top_pos, top_score, top_fused, n_valid = recommend_list_mv_topk(ue, item_emb, q.k, pos, ln, cand_stock, returns, day, port_idx,
                                                                             port_len, float(mv.gamma), float(mv.lambda_mv), ub, ok_d,
                                                                             n_blocks=n_t)
         else:
             top_pos, top_score, top_fused, n_valid = topk(ue, item_emb, q.k, cand_stock, returns, day, port_idx, port_len, float(mv.gamma),
-                                                          float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t, **(cap or {}))
+                                                          float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t, **(cap or {}),
+                                                          **_held_kw(held))
         return top_pos, top_score, n_valid, top_fused
-    return _select(launch, (user_emb, excl_pos, excl_len, day, port_idx, port_len), user_block, n_t, items_d, item_emb, return_embeddings,
-                   sort=not listed)
+    return _select(launch, (user_emb, excl_pos, excl_len, day, port_idx, port_len) + tuple(held_rows), user_block, n_t, items_d, item_emb,
+                   return_embeddings, sort=not listed)

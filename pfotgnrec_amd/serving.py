@@ -51,7 +51,8 @@ class Serving:
         return emb
 
     def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
-                  mv=None, portfolios=None, day_idx=None, basket=False, only=None, *, groups=None, group_cap=None):
+                  mv=None, portfolios=None, day_idx=None, basket=False, *, held_groups=None, stock_groups=None, only=None, groups=None,
+                  group_cap=None):
         """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
         written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
         is left as found), no gradient is recorded and dropout is off.
@@ -116,11 +117,24 @@ class Serving:
         return tuple.  Not with ``only`` (the list forms have no capped order) and, with ``mv``, not beyond 2048 candidates (the
         capped order has no wide form): ValueError.
 
+        ``held_groups`` (with ``groups`` / ``group_cap``): the cap counts what a user already HOLDS - every holding named here
+        uses up one slot of its group's quota, so a user who holds ``group_cap`` names of a sector is offered none of it, and one
+        who holds one of two is offered one more.  Given as one list of group ids per user (one id per holding, the ids of
+        ``groups``; a negative id: a holding in no group; an id named twice counts twice), as a packed pair (ids i32[U, W] padded
+        with -1, lens i32[U]) on host or device, or by name: ``"held"`` - the rows of the holdings ledger, from the one gather the
+        query makes anyway - or ``"portfolios"`` - the rows of ``portfolios=`` - both mapped on the device through
+        ``stock_groups``, one integer per stock index (item node - upper_u - 1; an index outside it: no group).  At most 256 ids
+        per user.  Still one launch (``pfo_recommend_topk_capped_held`` / ``pfo_recommend_mv_topk_capped_held`` /
+        ``pfo_recommend_basket_topk_capped_held``); with no holding named, the lists are those of ``groups`` / ``group_cap`` alone.
+        In the basket a group that the holdings alone fill takes part in no round.  (``held_groups``, ``stock_groups``, ``only``,
+        ``groups`` and ``group_cap`` go by name.)
+
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` / ``only`` are not (it would
         cost a read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
         query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
-                           portfolios, day_idx, self.holdings, basket, only, groups=groups, group_cap=group_cap)
+                           portfolios, day_idx, self.holdings, basket, only, groups=groups, group_cap=group_cap,
+                           held_groups=held_groups, stock_groups=stock_groups)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
