@@ -883,6 +883,41 @@ int pfo_holdings_gather(const int32_t* users, int64_t U, const int32_t* hold_idx
                         int32_t* port_len_out, int32_t* excl_pos_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * History gather (abi 6, additive): what a user has interacted with, read from the temporal adjacency the finder keeps on the
+ * device - the time-sorted CSR indptr i64[n_nodes + 1], adj_nbr i32, adj_ts f64.  All pointers are device pointers.
+ *
+ * pfo_history_gather: for q < U, u = users[q] i32, t = ts[q] f64:
+ *   - u outside [0, n_nodes) or t not finite: the answer is empty.
+ *   - hi = the number of entries of row u with adj_ts < t: strict, compared in fp64 on the stored fp64 timestamps (the rule of
+ *     pfo_csr_expire_plan; none of the sampler's fp32 casts apply).
+ *   - lo = the number of entries with adj_ts < since[q] (an entry AT since[q] is inside); 0 when since is NULL or since[q] is
+ *     NaN.  With max_scan > 0: lo = max(lo, hi - max_scan) - at most the max_scan newest entries are looked at.  hi <= lo: empty.
+ *   - the window is walked NEWEST FIRST, e = hi - 1, hi - 2, .., lo (among equal timestamps the later row entry first): a
+ *     neighbour met for the first time takes the next free slot while fewer than W are kept; a neighbour met again adds one to
+ *     its slot's count; a first meeting when W slots are taken is dropped, and so are its repeats.
+ *   node_out  i32[U, W]: the distinct neighbour node ids, newest first, padded with -1;  len_out i32[U]: the slots used;
+ *   time_out  f64[U, W] or NULL: the newest timestamp of each kept neighbour, copied bit for bit, padding NaN;
+ *   count_out i32[U, W] or NULL: the entries of the window that name it, padding 0;
+ *   pos_out   i32[U, W] or NULL: the position of the node in items i32[I] (distinct node ids), else -1 - through pos_scratch
+ *             i32[n_nodes] exactly as in pfo_holdings_gather: pos_scratch[items[i]] = i is scattered (ids outside [0, n_nodes)
+ *             skipped), an entry p is trusted only if 0 <= p < I and items[p] names the node; no initialisation needed;
+ *   stock_out i32[U, W] or NULL: node - upper_u - 1 when that lies in [0, 2^31), else -1 (checked in 64 bits: nothing wraps).
+ *   Every slot of every requested output row is written, padding included; nothing else is written.  One user per 64-thread
+ *   workgroup, bounds by a wave-wide 64-ary search, the walk in chunks of 64 entries; once W are kept the walk goes on only
+ *   for count_out.  Integer arithmetic only: the same answer on every run.  One launch, two with pos_out (the scatter).
+ * PFO_ERR_INVALID - checked before any pointer is looked at, nothing is queued: W outside [1, PFO_HISTORY_MAX_WIDTH], U outside
+ * [0, INT64_MAX / PFO_HISTORY_MAX_WIDTH] (the output rows are indexed in 64 bits),
+ * n_nodes < 1 (or >= 2^31), max_scan < 0, pos_out given and I outside [1, PFO_RECOMMEND_MAX_ITEMS]; then a null pointer that is
+ * needed (items and pos_scratch only with pos_out; since, time_out, count_out, pos_out, stock_out may be NULL).  U == 0 queues
+ * nothing and returns PFO_OK.
+ */
+#define PFO_HISTORY_MAX_WIDTH 256
+int pfo_history_gather(const int64_t* indptr, const int32_t* adj_nbr, const double* adj_ts, int64_t n_nodes, const int32_t* users,
+                       const double* ts, const double* since, int64_t U, int32_t W, int64_t max_scan, const int32_t* items,
+                       int32_t I, int32_t* pos_scratch, int32_t upper_u, int32_t* node_out, int32_t* len_out, double* time_out,
+                       int32_t* count_out, int32_t* pos_out, int32_t* stock_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Price ledger (abi 6, additive): the log-return table of the mean-variance rank kept on the device and grown by the day.
  * returns f64[day_cap, stock_cap, n_ret]: the day axis is a ring of slots, a slot holds stock_cap rows of n_ret doubles, row s
  * of a day is the window of stock s's n_ret newest log-returns as of that day, oldest first.  pfo_mv_select,

@@ -18,6 +18,7 @@ RECOMMEND_MV_MAX_ITEMS = 2048   # PFO_RECOMMEND_MV_MAX_ITEMS
 RECOMMEND_MV_WIDE_MAX_ITEMS = 65536   # PFO_RECOMMEND_MV_WIDE_MAX_ITEMS
 RECOMMEND_LIST_MAX_WIDTH = 256  # PFO_RECOMMEND_LIST_MAX_WIDTH
 RECOMMEND_HELD_MAX_WIDTH = 256  # PFO_RECOMMEND_HELD_MAX_WIDTH
+HISTORY_MAX_WIDTH = 256         # PFO_HISTORY_MAX_WIDTH
 EVAL_RANK_NONE = (1 << 31) - 1  # PFO_EVAL_RANK_NONE: the positive is not ranked
 ADAM_MAX_RANGES = 16            # PFO_ADAM_MAX_RANGES
 GRAD_NORM_PARTS = 256           # PFO_GRAD_NORM_PARTS
@@ -254,6 +255,8 @@ PROTOTYPES = {
                                      _VP]),
     "pfo_holdings_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP,
                                       _VP]),
+    "pfo_history_gather": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int64, _VP, C.c_int32, _VP, C.c_int32,
+                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_returns_scatter_scratch_bytes": (C.c_int64, [C.c_int64]),
     "pfo_returns_scatter_closes": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP]),
     "pfo_returns_append_day": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _VP, C.c_int64, _VP, _VP,

@@ -59,8 +59,9 @@ def _length(a):
 
 
 def _rows_of_log(arg, N, what):
-    """``exclude`` / ``portfolios`` over the whole log -> None, "held", or a packed pair (rows [N, W], lens [N]) on host or device."""
-    if arg is None or R._is_held(arg):
+    """``exclude`` / ``portfolios`` over the whole log -> None, "held", "seen", or a packed pair (rows [N, W], lens [N]) on host or
+    device."""
+    if arg is None or R._is_held(arg) or R._is_seen(arg):
         return arg
     return R._pack_rows(arg, N, what == "portfolios", "packed " + what + " must be (rows [N,W], lens [N]) with N = %d",
                         "packed " + what + ": %s must be integers", ("rows", "lens"),
@@ -69,9 +70,10 @@ def _rows_of_log(arg, N, what):
 
 
 def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
-          portfolios, upper_u, groups=None, group_cap=None):
+          portfolios, upper_u, groups=None, group_cap=None, seen_since=None, seen_width=None, seen_max_scan=0):
     """Everything ``backtest`` refuses on the host, before any device work (ValueError) -> (N, k, cutoffs, batch_size, horizon,
-    upper_u, exclude, portfolios), the last two over the whole log as ``_rows_of_log`` leaves them.  ``groups`` / ``group_cap``:
+    upper_u, exclude, portfolios, seen), the exclude / portfolios over the whole log as ``_rows_of_log`` leaves them, seen =
+    (since, width, max_scan) as ``recommend.validate_seen`` leaves them (since over the whole log).  ``groups`` / ``group_cap``:
     the checks of ``recommend`` (``recommend.validate_groups``), made here once for the whole log."""
     from .functional import check_cutoffs
     try:
@@ -108,6 +110,9 @@ def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, 
     if basket and mv is None:
         raise ValueError("basket=True needs mv")
     R.validate_groups(_length(items), groups, group_cap, None, mv)
+    seen = R.validate_seen(N, R._is_seen(exclude) or R._is_seen(portfolios), seen_since, seen_width, seen_max_scan, "the log holds")
+    if R._is_seen(portfolios) and mv is None:
+        raise ValueError('portfolios="seen" needs mv (an MVSampler): its upper_u turns the seen item nodes into stock indices')
     if mv is not None and portfolios is None:
         raise ValueError("mv needs portfolios: a packed pair over the log, one list of stock indices per interaction, or \"held\"")
     if (R._is_held(exclude) or R._is_held(portfolios)) and tgn.holdings is None:
@@ -121,7 +126,8 @@ def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, 
     for what, v in known[1:]:
         if v != known[0][1]:
             raise ValueError("%s is %d, %s %d: they number the stocks differently" % (known[0][0], known[0][1], what, v))
-    return N, k, cuts, batch_size, horizon, known[0][1], _rows_of_log(exclude, N, "exclude"), _rows_of_log(portfolios, N, "portfolios")
+    return (N, k, cuts, batch_size, horizon, known[0][1], _rows_of_log(exclude, N, "exclude"), _rows_of_log(portfolios, N, "portfolios"),
+            seen)
 
 
 def check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log):
@@ -130,7 +136,7 @@ def check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log):
     ``"rows"`` with the packed pair (ids [N, W], lens [N]) on host or device, cut per batch; ``"held"`` / ``"portfolios"`` with
     ``stock_groups`` as one int32 per stock index.  ``pf_log``: the portfolios as ``check`` left them."""
     mode, ids, lens, sg = R.validate_held_groups(N, held_groups, stock_groups, groups, tgn.holdings, pf_log, what="the log holds")
-    if mode == R.PORTFOLIOS and not R._is_held(pf_log):
+    if mode == R.PORTFOLIOS and not R._is_held(pf_log) and not R._is_seen(pf_log):   # (a ledger row and a seen row fit: 256 at the most)
         R.check_held_width(pf_log[0].shape[1])
     return mode, (ids, lens) if mode == "rows" else None, sg
 
@@ -169,14 +175,15 @@ def _without(ids, truth):
 
 def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
                   mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
-                  upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None):
+                  upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None, seen_since=None, seen_width=None,
+                  seen_max_scan=0):
     """The walk of ``backtest``; returns its per-interaction rows as host arrays after ONE read-back: dict(rank i32[n],
     recall f32[n, n_c], ndcg f32[n, n_c], invest f64[n, 4 n_c], list_item i32[n, k], n_valid i32[n]) - ``list_item`` the served
     lists, rank ``_lib.EVAL_RANK_NONE`` where the item taken is not in the list."""
     from .functional import list_buffers, list_metrics
-    N, k, cuts, batch_size, horizon, upper_u, ex_log, pf_log = check(
+    N, k, cuts, batch_size, horizon, upper_u, ex_log, pf_log, (since_log, seen_width, seen_max_scan) = check(
         tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
-        portfolios, upper_u, groups, group_cap)
+        portfolios, upper_u, groups, group_cap, seen_since, seen_width, seen_max_scan)
     hg_mode, hg_log, stock_groups = check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log)
     dev = tgn.device
     _lib.require_gpu(dev)
@@ -201,8 +208,13 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
     truth = R._to_dev(dev, destinations, torch.int32)
     users_d = R._to_dev(dev, sources, torch.int32)
     held_ex, held_pf = R._is_held(ex_log), R._is_held(pf_log)
+    seen_ex, seen_pf = R._is_seen(ex_log), R._is_seen(pf_log)
+    if seen_ex or seen_pf:
+        times_d = R._to_dev(dev, edge_times, torch.float64)
+        if since_log is not None and not isinstance(since_log, float):
+            since_log = R._to_dev(dev, since_log, torch.float64)       # on the device once, cut per batch
     pf_dev = None
-    if pf_log is not None and not held_pf and pf_log[0].shape[1] > 0:
+    if pf_log is not None and not held_pf and not seen_pf and pf_log[0].shape[1] > 0:
         pf_dev = (R._to_dev(dev, pf_log[0], torch.int32), R._to_dev(dev, pf_log[1], torch.int32))
     n_c = len(cuts)
     out = list_buffers(max(N, 1), n_c, dev)
@@ -212,25 +224,40 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
         hi = min(N, lo + batch_size)
         held_rows = tgn.holdings.rows(users_d[lo:hi]) if (held_pf or (held_ex and keep_truth)) else None
         ex = ex_log
+        seen_pair = None
+        if seen_ex or seen_pf:
+            # ONE gather a batch for whoever asks - the query and the metrics: ``recommend`` gets the rows as packed device pairs
+            # (item nodes to exclude, the truth taken out on the device with ``keep_truth``; stock indices as the portfolio)
+            since = since_log if since_log is None or isinstance(since_log, float) else since_log[lo:hi]
+            want = ("len",) + (("node",) if seen_ex else ()) + (("stock",) if seen_pf else ())
+            seen_rows = dict(zip(want, R.seen_rows(tgn, users_d[lo:hi], times_d[lo:hi], since, seen_width, seen_max_scan, want,
+                                                   None, upper_u if seen_pf else None)))
+            if seen_ex:
+                ex = (_without(seen_rows["node"], truth[lo:hi]) if keep_truth else seen_rows["node"], seen_rows["len"])
+            if seen_pf:
+                seen_pair = (seen_rows["stock"], seen_rows["len"])
         if held_ex and keep_truth:
             # the ledger's rows as item ids, the truth taken out on the device: what exclude="held" excludes, minus that item
             h_idx, h_len = held_rows
             ids = torch.where(h_idx >= 0, h_idx + (tgn.holdings.upper_u + 1), torch.full_like(h_idx, -1))
             ex = (_without(ids, truth[lo:hi]), h_len)
-        elif ex_log is not None and not held_ex:
+        elif ex_log is not None and not held_ex and not seen_ex:
             ex = _cut(ex_log, lo, hi)
             if keep_truth:
                 ex = (_without(ex[0], truth[lo:hi] if torch.is_tensor(ex[0]) else destinations[lo:hi]), ex[1])
         mv_side = {}
         if mv is not None:
-            mv_side = dict(mv=mv, portfolios=pf_log if held_pf else _cut(pf_log, lo, hi), basket=bool(basket))
+            mv_side = dict(mv=mv, portfolios=seen_pair if seen_pf else pf_log if held_pf else _cut(pf_log, lo, hi), basket=bool(basket))
         if hg_mode == "rows":
             cap["held_groups"] = _cut(hg_log, lo, hi)
         elif hg_mode == R.PORTFOLIOS and mv is None:                  # (the score order: the rows go along for the groups alone)
-            cap["portfolios"] = pf_log if held_pf else _cut(pf_log, lo, hi)
+            cap["portfolios"] = pf_log if held_pf else _cut(pf_log, lo, hi)     # (never "seen": that needs mv)
         res = tgn.recommend(sources[lo:hi], edge_times[lo:hi], k, items, exclude=ex, item_ok=item_ok, n_neighbors=n_neighbors, **mv_side, **cap)
         item_ids, n_valid = res[0], res[2]
-        pidx, plen = held_rows if held_pf else (_cut(pf_dev, lo, hi) if pf_dev is not None else (None, None))
+        if seen_pf:
+            pidx, plen = seen_pair
+        else:
+            pidx, plen = held_rows if held_pf else (_cut(pf_dev, lo, hi) if pf_dev is not None else (None, None))
         list_metrics(item_ids, truth[lo:hi], cuts, pidx, plen, upper_u, ret_past, day_past[lo:hi], ret_future, day_future[lo:hi],
                      n_valid, out=out, out_row0=lo)
         lists[lo:hi].copy_(item_ids)
@@ -251,14 +278,18 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
 
 def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
              mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
-             name="backtest", upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None):
+             name="backtest", upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None, seen_since=None,
+             seen_width=None, seen_max_scan=0):
     """The served lists of a model held against what happened: a prequential walk over a chronological log (numpy arrays like
     the entry points, or device tensors i32 / i32 / f64 / i32).  Per batch ``[lo, hi)`` of ``batch_size`` interactions:
 
     1. ``tgn.recommend(sources[lo:hi], edge_times[lo:hi], k, items, ...)`` - ``exclude``, ``item_ok``, ``n_neighbors``, ``mv``,
        ``portfolios``, ``basket``, ``groups`` and ``group_cap`` are passed through, so every served order, the wide mean-variance form, ``"held"`` and a
        ``PriceLedger`` as ``mv`` work as they do there.  ``exclude`` / ``portfolios`` cover the whole LOG here: a packed pair
-       (rows [N, W], lens [N]) on host or device, one list per interaction, or ``"held"``.
+       (rows [N, W], lens [N]) on host or device, one list per interaction, ``"held"``, or ``"seen"``: what the user's row of the
+       finder names strictly before the interaction's time (``seen_since`` - a scalar or one value per interaction -,
+       ``seen_width`` and ``seen_max_scan`` as in ``recommend``).  The comparison being strict, a finder built over the FULL log
+       serves the walk without ``append``: at every step a user has seen exactly its earlier interactions.
     2. ``list_metrics`` of the lists against ``destinations[lo:hi]`` - the place of the item the user took, and what the first
        c stocks of the list would have done to the portfolio (``portfolios``; None: empty) for every c of ``cutoffs`` (each in
        [1, k]) - written into one set of device buffers for the whole log.
@@ -276,7 +307,7 @@ def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cut
     upper_u + 1) is taken from ``tables``, ``mv`` or the holdings ledger, or passed; they must agree.
 
     ``keep_truth=True``: the item the user is about to take is removed from the user's exclusion row before the query (entries
-    set to -1, on the device for ``"held"`` and packed device rows), so it is always admissible - as the positive is in the
+    set to -1, on the device for ``"held"``, ``"seen"`` and packed device rows), so it is always admissible - as the positive is in the
     reference's protocol; ``False`` leaves the rows alone, and a user who re-buys a held stock can only be missed.
 
     Returns a dict in the style of ``eval_result_dict`` (``backtest_result_dict``): ``{name}_recall_avg_{c}``,
@@ -295,5 +326,6 @@ def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cut
     rows = backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs=cutoffs, batch_size=batch_size,
                          tables=tables, horizon=horizon, mv=mv, basket=basket, exclude=exclude, portfolios=portfolios, item_ok=item_ok,
                          n_neighbors=n_neighbors, keep_truth=keep_truth, append=append, upper_u=upper_u, groups=groups, group_cap=group_cap,
-                         held_groups=held_groups, stock_groups=stock_groups)
+                         held_groups=held_groups, stock_groups=stock_groups, seen_since=seen_since, seen_width=seen_width,
+                         seen_max_scan=seen_max_scan)
     return backtest_result_dict(name, rows["rank"], rows["invest"], cutoffs)

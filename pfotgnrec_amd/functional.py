@@ -865,6 +865,81 @@ def holdings_gather(users, hold_idx, hold_len, upper_u, items=None, pos_scratch=
     return port_idx, port_len, excl_pos
 
 
+HISTORY_OUTPUTS = ("node", "len", "time", "count", "pos", "stock")
+
+
+def history_gather(indptr, adj_nbr, adj_ts, users, ts, width, since=None, max_scan=0, items=None, pos_scratch=None, upper_u=None,
+                   want=("node", "len", "time", "count")):
+    """What each user has interacted with before its time, from a finder's device CSR (``pfo_history_gather``; the semantics
+    are stated in include/pfotgn.h): per query the distinct neighbours of row ``users[q]`` among the entries with
+    ``since[q] <= adj_ts < ts[q]`` (fp64, strict at the top), newest first, at most ``width`` of them; ``max_scan`` > 0 looks at
+    the newest ``max_scan`` entries of that window only.  Returns the tensors ``want`` names, in its order:
+
+    node i32[U, W] padded with -1, len i32[U], time f64[U, W] (the newest timestamp of each kept neighbour, NaN padding), count
+    i32[U, W] (the window's entries that name it, once the list is full the walk goes on for the counts alone), pos i32[U, W]
+    (position in ``items`` i32[I], distinct node ids, -1 for a non-candidate; ``pos_scratch``: contiguous i32[>= n_nodes] kept
+    between queries with any content - anything else is refused, never replaced -, None: allocated), stock i32[U, W] (node - ``upper_u`` - 1, -1 outside [0, 2^31)).
+
+    indptr i64[n_nodes + 1], adj_nbr i32, adj_ts f64 as ``NeighborFinder.device_arrays`` returns them; users i32[U], ts f64[U],
+    since f64[U] or None (a NaN entry: no lower end for that user).  ValueError: what the C entry refuses."""
+    try:
+        want = tuple(want)
+    except TypeError:
+        raise ValueError("want must name outputs among %s" % (HISTORY_OUTPUTS,)) from None
+    if any(w not in HISTORY_OUTPUTS for w in want):
+        raise ValueError("want must name outputs among %s, got %s" % (HISTORY_OUTPUTS, want))
+    try:
+        W, max_scan = int(width), int(max_scan)
+    except (TypeError, ValueError):
+        raise ValueError("width and max_scan must be integers") from None
+    if not 1 <= W <= _lib.HISTORY_MAX_WIDTH:
+        raise ValueError("width must lie in [1, %d] (got %d)" % (_lib.HISTORY_MAX_WIDTH, W))
+    if max_scan < 0:
+        raise ValueError("max_scan must not be negative (got %d)" % max_scan)
+    if indptr.dim() != 1 or indptr.dtype != torch.int64 or indptr.shape[0] < 2 or indptr.shape[0] - 1 >= 2 ** 31:
+        raise ValueError("indptr must be int64 [n_nodes + 1] with 1 <= n_nodes < 2^31")
+    if adj_nbr.dtype != torch.int32 or adj_ts.dtype != torch.float64 or adj_nbr.dim() != 1 or adj_nbr.shape != adj_ts.shape:
+        raise ValueError("the adjacency must be adj_nbr i32[n] next to adj_ts f64[n]")
+    if not (indptr.is_contiguous() and adj_nbr.is_contiguous() and adj_ts.is_contiguous()):
+        raise ValueError("the adjacency arrays must be contiguous")
+    if users.dim() != 1 or users.dtype != torch.int32:
+        raise ValueError("users must be int32 [U]")
+    U, n_nodes, I = int(users.shape[0]), int(indptr.shape[0]) - 1, 1
+    if ts.dtype != torch.float64 or tuple(ts.shape) != (U,):
+        raise ValueError("ts must be float64 [U] (U = %d)" % U)
+    if since is not None and (since.dtype != torch.float64 or tuple(since.shape) != (U,)):
+        raise ValueError("since must be float64 [U] (U = %d) or None" % U)
+    dev = indptr.device
+    if "pos" in want:
+        if items is None or items.dim() != 1 or items.dtype != torch.int32:
+            raise ValueError("positions need items: int32 [I]")
+        I = int(items.shape[0])
+        if not 1 <= I <= _lib.RECOMMEND_MAX_ITEMS:
+            raise ValueError("items must hold between 1 and %d candidates (got %d)" % (_lib.RECOMMEND_MAX_ITEMS, I))
+        if pos_scratch is None:
+            pos_scratch = torch.empty(n_nodes, dtype=torch.int32, device=dev)
+        elif pos_scratch.dtype != torch.int32 or pos_scratch.numel() < n_nodes or not pos_scratch.is_contiguous():
+            raise ValueError("pos_scratch must be a contiguous int32 tensor of at least n_nodes = %d entries (or None)" % n_nodes)
+    else:
+        items = pos_scratch = None
+    if "stock" in want:
+        if upper_u is None or not 0 <= int(upper_u) < 2 ** 31 - 1:
+            raise ValueError("stock indices need upper_u: a non-negative int32")
+    _lib.require_gpu(dev)
+    for t in (adj_nbr, adj_ts, users, ts, since, items, pos_scratch):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    out = dict(node=torch.empty((U, W), dtype=torch.int32, device=dev), len=torch.empty(U, dtype=torch.int32, device=dev))
+    for name, dt in (("time", torch.float64), ("count", torch.int32), ("pos", torch.int32), ("stock", torch.int32)):
+        out[name] = torch.empty((U, W), dtype=dt, device=dev) if name in want else None
+    _lib.call("pfo_history_gather", indptr.data_ptr(), _lib.ptr(adj_nbr), _lib.ptr(adj_ts), n_nodes, _lib.ptr(users.contiguous()),
+              _lib.ptr(ts.contiguous()), _lib.ptr(None if since is None else since.contiguous()), U, W, max_scan,
+              _lib.ptr(None if items is None else items.contiguous()), I, _lib.ptr(pos_scratch), int(upper_u or 0),
+              out["node"].data_ptr(), out["len"].data_ptr(), _lib.ptr(out["time"]), _lib.ptr(out["count"]), _lib.ptr(out["pos"]),
+              _lib.ptr(out["stock"]), _lib.stream_ptr())
+    return tuple(out[w] for w in want)
+
+
 def returns_scatter_closes(stocks, closes, n_stocks, stamp=None):
     """The sparse form of a day's closes -> the stamp table ``pfo_returns_append_day`` reads (``pfo_returns_scatter_closes``: a
     memset and one launch).  stocks i32[m], closes f64[m]; positions whose index lies outside [0, n_stocks) or whose close is

@@ -15,6 +15,7 @@ inference and - for the BPR loss - an autograd formula:
     torch.ops.pfotgn.recommend_mv_topk_wide(...)                               its form for lists beyond 2048 candidates
     torch.ops.pfotgn.recommend_list_topk(user_emb, item_emb, k, list_pos, ...) the k best of every user's own list
     torch.ops.pfotgn.recommend_list_mv_topk(...)                               the same in the mean-variance order
+    torch.ops.pfotgn.history_gather(indptr, adj_nbr, adj_ts, users, ts, width, ...)  what each user interacted with before its time
 
 Only a HIP implementation is registered ("cuda" dispatch key = ROCm here): on any other device the dispatcher raises,
 there is no CPU fallback.  The TGN step itself keeps its ``autograd.Function`` (``tgn._EmbedFn``): it owns state (memory,
@@ -204,3 +205,24 @@ def _(user_emb, item_emb, k, list_pos, cand_stock, returns, day_idx, gamma, lamb
     U = user_emb.shape[0]
     return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
             user_emb.new_empty((U, k), dtype=torch.float64), user_emb.new_empty((U,), dtype=torch.int32))
+
+
+@torch.library.custom_op(_LIB_NS + "::history_gather", mutates_args=(), device_types="cuda")
+def history_gather(indptr: torch.Tensor, adj_nbr: torch.Tensor, adj_ts: torch.Tensor, users: torch.Tensor, ts: torch.Tensor,
+                   width: int, since: Optional[torch.Tensor] = None, max_scan: int = 0, items: Optional[torch.Tensor] = None,
+                   upper_u: Optional[int] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                           torch.Tensor]:
+    """(node, len, time, count, pos, stock) of ``functional.history_gather``; pos / stock have no column without ``items`` /
+    ``upper_u`` (an op returns tensors, not None)."""
+    want = ("node", "len", "time", "count") + (("pos",) if items is not None else ()) + (("stock",) if upper_u is not None else ())
+    got = dict(zip(want, functional.history_gather(indptr, adj_nbr, adj_ts, users, ts, width, since, max_scan, items, None, upper_u, want)))
+    none = lambda: got["node"].new_empty((users.shape[0], 0))
+    return got["node"], got["len"], got["time"], got["count"], got.get("pos", none()), got.get("stock", none())
+
+
+@history_gather.register_fake
+def _(indptr, adj_nbr, adj_ts, users, ts, width, since=None, max_scan=0, items=None, upper_u=None):
+    U = users.shape[0]
+    rows = lambda dt, w=width: users.new_empty((U, w), dtype=dt)
+    return (rows(torch.int32), users.new_empty((U,), dtype=torch.int32), rows(torch.float64), rows(torch.int32),
+            rows(torch.int32, width if items is not None else 0), rows(torch.int32, width if upper_u is not None else 0))

@@ -16,21 +16,63 @@ from . import _lib
 from .prices import PriceLedger
 
 Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held "
-                               "only_ids only_len only_held groups group_cap held_mode hg_ids hg_len stock_groups basket",
-                               defaults=(None, None, None, None, False, None, None, None, None, None, None, False))
+                               "only_ids only_len only_held groups group_cap held_mode hg_ids hg_len stock_groups "
+                               "seen seen_since seen_width seen_max_scan basket",
+                               defaults=(None, None, None, None, False, None, None, None, None, None, None, None, None, None, 0, False))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
 # (with a PriceLedger as the owner: the ORDINAL among its live days, or None - the day is looked up on the device)
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
 HELD = "held"     # ``exclude`` / ``portfolios``: take the rows of the model's holdings ledger (port_idx is None in the MVQuery then)
 PORTFOLIOS = "portfolios"   # ``held_groups``: the rows of ``portfolios=``, mapped to groups through ``stock_groups``
+SEEN = "seen"     # ``exclude`` / ``only`` / ``portfolios``: what the user's row of the temporal adjacency names before its time
 
 
 def _is_held(a):
     return isinstance(a, str) and a == HELD
 
 
+def _is_seen(a):
+    return isinstance(a, str) and a == SEEN
+
+
 def _host(a):
     return None if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def validate_seen(U, any_seen, seen_since=None, seen_width=None, seen_max_scan=0, what="users holds",
+                  names=("seen_since", "seen_width", "seen_max_scan")):
+    """``seen_since`` / ``seen_width`` / ``seen_max_scan`` of ``TGN.recommend`` and ``backtest`` checked on the host (ValueError)
+    -> (since, width, max_scan): since None, a float, or f64 [U] (a host array, or the caller's device tensor as it is).
+    ``any_seen``: whether one of ``exclude`` / ``only`` / ``portfolios`` is ``"seen"`` - without it the three are refused.
+    ``names``: what the caller calls the three (``TGN.history``: since, width, max_scan) - the messages speak of those."""
+    n_since, n_width, n_scan = names
+    if not any_seen:
+        if seen_since is not None or seen_width is not None or seen_max_scan not in (0, None):
+            raise ValueError('seen_since / seen_width / seen_max_scan go with exclude="seen", only="seen" or portfolios="seen"')
+        return None, None, 0
+    try:
+        width = _lib.HISTORY_MAX_WIDTH if seen_width is None else operator.index(seen_width)
+        max_scan = 0 if seen_max_scan is None else operator.index(seen_max_scan)
+    except TypeError:
+        raise ValueError("%s and %s must be integers" % (n_width, n_scan)) from None
+    if not 1 <= width <= _lib.HISTORY_MAX_WIDTH:
+        raise ValueError("%s must lie in [1, %d] (got %d)" % (n_width, _lib.HISTORY_MAX_WIDTH, width))
+    if max_scan < 0:
+        raise ValueError("%s must not be negative (got %d)" % (n_scan, max_scan))
+    since = seen_since
+    if since is not None:
+        if not isinstance(since, torch.Tensor):
+            try:
+                since = np.asarray(since, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError("%s must be a number or hold one per user" % n_since) from None
+        elif not since.dtype.is_floating_point:
+            since = since.to(torch.float64)
+        if since.ndim == 0:
+            since = float(since)
+        elif tuple(since.shape) != (U,):
+            raise ValueError("%s must be a scalar or hold one value per entry: %s %d, got shape %s" % (n_since, what, U, tuple(since.shape)))
+    return since, width, max_scan
 
 
 def _int_vector(a, what, n_nodes):
@@ -86,6 +128,8 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None, *
     ``max_items``: the bound on I of the kernel the query will take."""
     if _is_held(portfolios) and holdings is None:
         raise ValueError('portfolios="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
+    if _is_seen(portfolios) and mv is None:
+        raise ValueError('portfolios="seen" needs mv (an MVSampler): its upper_u turns the seen item nodes into stock indices')
     if mv is None:
         if portfolios is not None or day_idx is not None:
             raise ValueError("portfolios / day_idx need mv (an MVSampler): without it the portfolio can only be excluded")
@@ -94,7 +138,7 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None, *
         if not hasattr(mv, name):
             raise ValueError("mv must carry returns, upper_u, gamma, lambda_mv and day_of (an MVSampler); %s is missing" % name)
     if portfolios is None:
-        raise ValueError("mv needs portfolios: packed (port_idx [U,W], port_len [U]), one list of stock indices per user, or \"held\"")
+        raise ValueError("mv needs portfolios: packed (port_idx [U,W], port_len [U]), one list of stock indices per user, \"held\" or \"seen\"")
     if _is_held(portfolios) and int(mv.upper_u) != holdings.upper_u:
         raise ValueError("mv.upper_u is %d, the holdings ledger's %d: they number the stocks differently" % (int(mv.upper_u), holdings.upper_u))
     if len(mv.returns.shape) != 3:
@@ -103,7 +147,7 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None, *
         raise ValueError("with mv, items may hold at most %d candidates (got %d)" % (max_items, I))
     ledger = isinstance(mv, PriceLedger)
     n_days = mv.n_days if ledger else int(mv.returns.shape[0])   # (a ledger's day_idx counts its LIVE days, 0 = oldest)
-    if _is_held(portfolios):
+    if _is_held(portfolios) or _is_seen(portfolios):
         port_idx = port_len = None
     else:
         port_idx, port_len = _pack_rows(
@@ -221,7 +265,8 @@ def validate_held_groups(U, held_groups, stock_groups, groups, holdings=None, po
 
 
 def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
-             day_idx=None, holdings=None, basket=False, only=None, *, groups=None, group_cap=None, held_groups=None, stock_groups=None):
+             day_idx=None, holdings=None, basket=False, only=None, *, groups=None, group_cap=None, held_groups=None, stock_groups=None,
+             seen_since=None, seen_width=None, seen_max_scan=0):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
     if only is not None and exclude is not None:
@@ -265,7 +310,7 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
     if _is_held(exclude):
         if holdings is None:
             raise ValueError('exclude="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
-    elif exclude is not None:
+    elif exclude is not None and not _is_seen(exclude):
         ex_ids, ex_len = _pack_rows(
             exclude, U, False, "packed exclude must be (ids [U,W], lens [U]) with U = %d", "packed exclude %s must be integers",
             ("ids", "lens"), "exclude must be None, a list of per-user lists of item ids or a packed (ids, lens) pair",
@@ -279,13 +324,17 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
     if _is_held(only):
         if holdings is None:
             raise ValueError('only="held" needs a holdings ledger: call track_holdings(width, upper_u) first')
-    elif only is not None:
+    elif only is not None and not _is_seen(only):
         only_ids, only_len = _pack_rows(
             only, U, False, "packed only must be (ids [U,W], lens [U]) with U = %d", "packed only %s must be integers",
             ("ids", "lens"), 'only must be None, "held", a list of per-user lists of item ids or a packed (ids, lens) pair',
             "only lists %d users, users holds %d", "only holds ids that do not fit 32 bits")
         if only_ids.shape[1] > _lib.RECOMMEND_LIST_MAX_WIDTH:
             raise ValueError("only lists up to %d ids for a user, at most %d" % (only_ids.shape[1], _lib.RECOMMEND_LIST_MAX_WIDTH))
+    seen = (_is_seen(exclude), _is_seen(only), _is_seen(portfolios))
+    seen_since, seen_width, seen_max_scan = validate_seen(U, any(seen), seen_since, seen_width, seen_max_scan)
+    if seen[2] and mv is None:
+        raise ValueError('portfolios="seen" needs mv (an MVSampler): its upper_u turns the seen item nodes into stock indices')
     groups, group_cap = validate_groups(I, groups, group_cap, only, mv)
     hg_ports = None                                                  # held_groups="portfolios" in the score order: the rows serve it alone
     if mv is None and day_idx is None and portfolios is not None and isinstance(held_groups, str) and held_groups == PORTFOLIOS:
@@ -309,10 +358,10 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
             check_held_width(hg_ids.shape[1])
     elif held_mode == PORTFOLIOS and mvq.port_idx is not None:
         check_held_width(mvq.port_idx.shape[1])
-    held = (_is_held(exclude), mvq is not None and mvq.port_idx is None)
+    held = (_is_held(exclude), mvq is not None and mvq.port_idx is None and not seen[2])
     return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
                  held if any(held) else None, only_ids, only_len, _is_held(only), groups, group_cap, held_mode, hg_ids, hg_len,
-                 stock_groups, bool(basket))
+                 stock_groups, seen if any(seen) else None, seen_since, seen_width, seen_max_scan, bool(basket))
 
 
 def _to_dev(dev, a, dtype):
@@ -387,7 +436,20 @@ def assemble(tgn, q, return_embeddings=False):
                 excl_pos, excl_len = h_pos, h_len                     # (with ``only``: the list - see ``listed`` below)
             if port_held:
                 held_ports = (h_idx, h_len)
-        listed = q.only_held or q.only_ids is not None               # pos / len are the users' own lists, not exclusion lists
+        ex_seen, only_seen, port_seen = q.seen or (False, False, False)
+        seen_stock = seen_len = None
+        if ex_seen or only_seen or port_seen:
+            # one gather over the finder's device CSR for whoever asks: the distinct neighbours before each user's time, as
+            # candidate positions (exclude / only) and as stock indices (portfolios)
+            want = ("len",) + (("pos",) if ex_seen or only_seen else ()) + (("stock",) if port_seen else ())
+            rows = dict(zip(want, seen_rows(tgn, users_d, user_ts, q.seen_since, q.seen_width, q.seen_max_scan, want, items_d,
+                                            int(q.mv.src.upper_u) if port_seen else None)))
+            seen_len, seen_stock = rows["len"], rows.get("stock")
+            if ex_seen or only_seen:
+                excl_pos, excl_len = rows["pos"], seen_len            # (with ``only``: the list, newest first)
+            if port_seen:
+                held_ports = (seen_stock, seen_len)
+        listed = q.only_held or q.only_ids is not None or only_seen  # pos / len are the users' own lists, not exclusion lists
         id_rows = (q.only_ids, q.only_len) if q.only_ids is not None else (q.ex_ids, q.ex_len)
         if id_rows[0] is not None and id_rows[0].shape[1] > 0:
             # node id -> position in ``items`` through a table over the node ids (-1: not a candidate)
@@ -413,6 +475,8 @@ def assemble(tgn, q, return_embeddings=False):
         elif q.held_mode is not None:
             if q.hg_ids is not None:                                 # held_groups="portfolios" in the score order: the rows are the query's own
                 s_idx, s_len = to_dev(q.hg_ids, torch.int32), to_dev(q.hg_len, torch.int32)
+            elif port_seen and not group_held:                       # held_groups="portfolios" over portfolios="seen"
+                s_idx, s_len = seen_stock, seen_len
             elif group_held or q.mv.port_idx is None:                # the ledger's rows (also portfolios="held" asked for as groups)
                 s_idx, s_len = h_idx, h_len
             else:
@@ -427,6 +491,17 @@ def assemble(tgn, q, return_embeddings=False):
             launch = lambda ub, ue, pos, ln, *held: recommend_topk(ue, item_emb, k, ub, pos, ln, ok_d, n_blocks=n_t, **cap, **_held_kw(held))
         return _select(launch, (user_emb, excl_pos, excl_len) + held_rows, user_block, n_t, items_d, item_emb, return_embeddings,
                        sort=not listed)
+
+
+def seen_rows(tgn, users_d, ts_d, since, width, max_scan, want, items_d=None, upper_u=None):
+    """``history_gather`` over the model's own finder for device ``users_d`` i32[n] at ``ts_d`` f64[n] -> the tensors ``want``
+    names.  ``since``: None, a float, or f64 [n] on host or device (``validate_seen``)."""
+    from .functional import history_gather
+    dev, n = tgn.device, int(users_d.shape[0])
+    indptr, nbr, _, adj_ts = tgn.neighbor_finder.device_arrays(dev)
+    if since is not None:
+        since = torch.full((n,), since, dtype=torch.float64, device=dev) if isinstance(since, float) else _to_dev(dev, since, torch.float64)
+    return history_gather(indptr, nbr, adj_ts, users_d, ts_d.contiguous(), width, since, max_scan, items_d, None, upper_u, want)
 
 
 def stock_rows_to_groups(idx, stock_groups):

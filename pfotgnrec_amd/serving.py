@@ -51,8 +51,8 @@ class Serving:
         return emb
 
     def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
-                  mv=None, portfolios=None, day_idx=None, basket=False, *, held_groups=None, stock_groups=None, only=None, groups=None,
-                  group_cap=None):
+                  mv=None, portfolios=None, day_idx=None, basket=False, *, held_groups=None, stock_groups=None, seen_since=None,
+                  seen_width=None, seen_max_scan=0, only=None, groups=None, group_cap=None):
         """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
         written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
         is left as found), no gradient is recorded and dropout is off.
@@ -129,14 +129,69 @@ class Serving:
         In the basket a group that the holdings alone fill takes part in no round.  (``held_groups``, ``stock_groups``, ``only``,
         ``groups`` and ``group_cap`` go by name.)
 
+        ``exclude="seen"`` / ``only="seen"`` / ``portfolios="seen"`` (any of them, also beside ``"held"``): the rows come from the
+        graph's own history - what the user's row of the temporal adjacency names STRICTLY before the user's query time (fp64 on
+        the stored timestamps), distinct, newest first: "do not offer what this user has already traded", "rank the names this
+        user has traded before", "the names traded are the portfolio".  No ledger and no lists packed per query: one
+        ``pfo_history_gather`` over the finder's device CSR and the per-user timestamps already on the device serves whoever
+        asks.  ``seen_since`` (a scalar or f64 [U] on host or device; None / NaN: no lower end) keeps the entries at or after that
+        time only; ``seen_width`` (1 .. 256, default 256) is how many distinct names a user's row holds - the newest win;
+        ``seen_max_scan`` > 0 looks at the newest that many entries of the window only.  ``portfolios="seen"`` needs ``mv``: a seen
+        node is stock ``node - mv.upper_u - 1``, nodes outside the return table are ignored as always;
+        ``held_groups="portfolios"`` maps these rows through ``stock_groups`` like any portfolio rows.  What is refused for
+        explicit rows stays refused (``only`` with ``exclude``, ``basket=True`` or ``groups``); the three ``seen_*`` without any
+        ``"seen"`` are refused too.  Entries removed by ``expire`` are no longer seen; interactions taken in by ``ingest`` /
+        ``observe(append=True)`` are.
+
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` / ``only`` are not (it would
         cost a read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
         query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
                            portfolios, day_idx, self.holdings, basket, only, groups=groups, group_cap=group_cap,
-                           held_groups=held_groups, stock_groups=stock_groups)
+                           held_groups=held_groups, stock_groups=stock_groups, seen_since=seen_since, seen_width=seen_width,
+                           seen_max_scan=seen_max_scan)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
+
+    def history(self, users, timestamps, width, since=None, max_scan=0, items=None):
+        """What each user interacted with before its time, read from the temporal adjacency the model's finder keeps on the
+        device (``pfo_history_gather``) - a query: NO model state, ledger row or finder array is written.  Per user the distinct
+        neighbours among the row entries with ``since <= t < timestamp`` (fp64, strict at the top), newest first, at most
+        ``width`` (1 .. 256); ``max_scan`` > 0 looks at the newest ``max_scan`` entries of that window only.
+
+        users: [U] node ids (host array or integer tensor); timestamps / since: a scalar or f64 [U] on host or device (since
+        None / NaN: no lower end).  Returns, on the device, (nodes i32[U, width] padded with -1, lens i32[U], times f64[U, width]
+        - the newest timestamp of each neighbour, NaN padding -, counts i32[U, width] - how many entries of the window name it),
+        and with ``items`` (distinct candidate node ids) also positions i32[U, width]: the neighbour's place in ``items`` or -1.
+        A non-finite timestamp gives an empty row.  Host ``users`` / ``items`` are checked like ``recommend``'s (ValueError for an
+        id outside [0, n_nodes)); ids in a device tensor are not - one outside the finder's table gives an empty row.  Entries
+        ``expire`` removed are gone."""
+        from . import recommend as R
+        users_h = R._int_vector(users, "users", self.n_nodes)
+        U = int(users.shape[0]) if users_h is None else int(users_h.shape[0])
+        since, width, max_scan = R.validate_seen(U, True, since, width, max_scan, names=("since", "width", "max_scan"))
+        ts = timestamps if torch.is_tensor(timestamps) else np.asarray(timestamps)
+        if ts.ndim != 0 and tuple(ts.shape) != (U,):
+            raise ValueError("timestamps must be a scalar or hold one value per user (%d), got shape %s" % (U, tuple(ts.shape)))
+        if not torch.is_tensor(ts) and ts.dtype.kind not in "fiu":
+            raise ValueError("timestamps must be numbers")
+        want = ("node", "len", "time", "count")
+        items_d = None
+        if items is not None:
+            items_h = R._int_vector(items.detach().cpu().numpy() if torch.is_tensor(items) else items, "items", self.n_nodes)
+            if not 1 <= items_h.shape[0] <= _lib.RECOMMEND_MAX_ITEMS:
+                raise ValueError("items must hold between 1 and %d candidates (got %d)" % (_lib.RECOMMEND_MAX_ITEMS, items_h.shape[0]))
+            if np.unique(items_h).shape[0] != items_h.shape[0]:
+                raise ValueError("items holds duplicates")
+            want += ("pos",)
+        _lib.require_gpu(self.device)
+        with torch.no_grad():
+            if items is not None:
+                items_d = R._to_dev(self.device, items_h, torch.int32)
+            users_d = R._to_dev(self.device, users if users_h is None else users_h, torch.int32)
+            ts_d = R._to_dev(self.device, ts, torch.float64).reshape(-1)
+            ts_d = ts_d.expand(U) if ts.ndim == 0 else ts_d
+            return R.seen_rows(self, users_d, ts_d, since, width, max_scan, want, items_d)
 
     # ------------------------------------------------------------------ serving: write-only state advance
     def _observe_workspace(self, B):
