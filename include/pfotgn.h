@@ -852,6 +852,45 @@ int pfo_edge_rows_compact(float* table, int64_t n_rows, int64_t n_keep, int32_t 
 int pfo_eidx_remap(int32_t* eidx, int64_t n, const int32_t* remap, int64_t n_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Erasure by node (abi 6, additive): the sibling of the retention calls, by node instead of by time.  gone u8[n_nodes] on the
+ * device, 1 = forgotten.  Entry i of row v is DROPPED iff gone[v] or gone[adj_nbr[i]]; a neighbour id outside [0, n_nodes)
+ * counts as not gone.  The survivors of a row are no suffix and rows are skewed, so every pass runs one lane per ENTRY.
+ *   pfo_nodes_flag           : gone = 0, then gone[ids[j]] = 1 for ids i32[m]; ids outside [1, n_nodes) are skipped (node 0 is
+ *                              the padding node), duplicates are fine.  A memset and one launch (m == 0: the memset alone).
+ *   pfo_csr_forget_plan      : keep u8[total] = 1 for an entry that stays; new_pos i64[total + 1] = the exclusive scan of keep
+ *                              over the flat entries (new_pos[total] = the surviving total); new_indptr i64[n_nodes + 1] =
+ *                              new_pos at the row starts - the exclusive scan of the kept count per row - so
+ *                              new_indptr[n_nodes] is the surviving total, which the caller reads back to size the output.
+ *                              Three launches; scratch holds pfo_csr_forget_scratch_bytes(n_nodes, total) bytes.  total == 0:
+ *                              new_indptr and new_pos[0] are zeroed, adj_nbr and keep may be NULL.
+ *   pfo_csr_forget_copy      : entry i with keep[i] goes to position new_pos[i] of new arrays of `total` entries: the old order
+ *                              inside every row, equal to boolean-masking the flat arrays with keep, bit for bit (timestamps
+ *                              keep their bits).  One launch; total == 0 queues nothing.
+ *   pfo_edge_rows_mark_nodes : the by-node form of pfo_edge_rows_mark, one call per finder over its adjacency as it was BEFORE
+ *                              the removal: flags[eidx[i]] |= (dropped ? 1 : 2); entries outside [0, n_rows) are ignored.
+ *                              pfo_edge_rows_plan / _compact and pfo_eidx_remap then run as they stand.  n == 0 queues nothing.
+ *   pfo_node_rows_reset      : ONE launch; every row v with gone[v] returns to what a new node holds - memory f32[., D],
+ *                              last_update f32, msg_table f32[., M], msg_time f32, has_msg u8 and the node-feature row
+ *                              f32[., Dn] to 0, the holdings ledger's hold_idx i32[., W] to -1, hold_len i32 to 0 and
+ *                              hold_time f64 to -inf.  Every table is optional (NULL: skipped); no row width needs a multiple
+ *                              of 4; rows that are not flagged keep every bit.
+ * PFO_ERR_INVALID - all checks are made on the host and nothing is queued: bad sizes (n_nodes < 1, a negative count, counts of
+ * 2^31 and above, total > old_total, a table given with a width < 1), a null pointer where one is needed, a short scratch.
+ */
+int pfo_nodes_flag(const int32_t* ids, int64_t m, int64_t n_nodes, uint8_t* gone, void* stream);
+int64_t pfo_csr_forget_scratch_bytes(int64_t n_nodes, int64_t total);
+int pfo_csr_forget_plan(const int64_t* indptr, const int32_t* adj_nbr, int64_t n_nodes, int64_t total, const uint8_t* gone,
+                        uint8_t* keep, int64_t* new_pos, int64_t* new_indptr, void* scratch, int64_t scratch_bytes, void* stream);
+int pfo_csr_forget_copy(const int32_t* old_nbr, const int32_t* old_eidx, const double* old_ts, int64_t old_total,
+                        const uint8_t* keep, const int64_t* new_pos, int64_t total, int32_t* new_nbr, int32_t* new_eidx,
+                        double* new_ts, void* stream);
+int pfo_edge_rows_mark_nodes(const int64_t* indptr, const int32_t* adj_nbr, const int32_t* adj_eidx, int64_t n, int64_t n_nodes,
+                             const uint8_t* gone, int64_t n_rows, int32_t* flags, void* stream);
+int pfo_node_rows_reset(const uint8_t* gone, int64_t n_nodes, float* memory, int32_t D, float* last_update, float* msg_table,
+                        int32_t M, float* msg_time, uint8_t* has_msg, float* node_feat, int32_t Dn, int32_t* hold_idx, int32_t W,
+                        int32_t* hold_len, double* hold_time, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Holdings ledger (abi 6, additive): per node row the portfolio its newest interaction record carried.  hold_idx i32[n_nodes, W]
  * STOCK indices padded with -1 (the packed form of port_idx everywhere else; the item node of stock s is s + upper_u + 1),
  * hold_len i32[n_nodes] valid leading entries, hold_time f64[n_nodes] the record's time.  All pointers are device pointers.

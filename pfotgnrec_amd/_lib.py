@@ -250,6 +250,13 @@ PROTOTYPES = {
     "pfo_edge_rows_plan": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
     "pfo_edge_rows_compact": (C.c_int, [_VP, C.c_int64, C.c_int64, C.c_int32, _VP, _VP, _VP]),
     "pfo_eidx_remap": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP]),
+    "pfo_nodes_flag": (C.c_int, [_VP, C.c_int64, C.c_int64, _VP, _VP]),
+    "pfo_csr_forget_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "pfo_csr_forget_plan": (C.c_int, [_VP, _VP, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    "pfo_csr_forget_copy": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
+    "pfo_edge_rows_mark_nodes": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP]),
+    "pfo_node_rows_reset": (C.c_int, [_VP, C.c_int64, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32,
+                                      _VP, _VP, _VP]),
     "pfo_holdings_store_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "pfo_holdings_store": (C.c_int, [_VP, _VP, _VP, C.c_int32, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int64,
                                      _VP]),

@@ -1,5 +1,5 @@
 // Exclusive scan of n int64 values in two launches, shared by the retention kernels (csr.hip pfo_csr_expire_plan, ingest.hip
-// pfo_edge_rows_plan).  The values are PRODUCED by a functor and the scanned offsets are CONSUMED by one, so the pass that
+// pfo_edge_rows_plan) and the erasure by node (forget.hip pfo_csr_forget_plan, over entries).  The values are PRODUCED by a functor and the scanned offsets are CONSUMED by one, so the pass that
 // makes the counts and the pass that uses the offsets need no launch of their own:
 //
 //   xs_tile_kernel   : one workgroup per tile of XS_TILE values; v = f(i); local[i] = exclusive sum inside the tile (wave scan

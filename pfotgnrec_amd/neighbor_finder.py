@@ -281,6 +281,79 @@ class NeighborFinder:
         self._version += 1
         return old_total - total
 
+    def forget(self, nodes_or_gone, device=None, _row_flags=None):
+        """Erasure by node, ``expire``'s sibling: removes every adjacency entry that touches a forgotten node - the node's own
+        row and the entries of other rows that name it as the neighbour - and returns how many went.  ``n_nodes`` is unchanged:
+        a forgotten id stays valid, its row is empty and ``append`` may name it again.  The survivors keep their order inside
+        every row: the result equals boolean-masking the flat ``nbr / eidx / ts`` with the keep decision and re-accumulating
+        ``indptr``, bit for bit (which is a rebuild over the log without the interactions that touch a forgotten node).
+
+        ``nodes_or_gone``: node ids - a host list / array of integers or an integer device tensor; ids outside
+        ``[1, n_nodes)`` are skipped on the device (node 0 is the padding node), duplicates are fine - or the flags themselves,
+        a ``uint8`` device tensor ``[n_nodes]`` with 1 = forgotten.  ``ValueError`` (nothing is written) for host ids that are
+        no integers or do not fit int32, and for a tensor that is neither.
+
+        On the device: ``pfo_nodes_flag`` (ids only), ``pfo_csr_forget_plan`` (the keep decision per entry, a scan over the
+        entries, the new ``indptr``) and ``pfo_csr_forget_copy``, all one lane per entry - a hub row costs what its entries
+        cost.  The new total is read back to size the output - ONE synchronisation: a maintenance call, not a step.  When
+        nothing is dropped nothing is written and ``_version`` stays; otherwise the version is bumped (consumers re-fetch the
+        device arrays, a captured step goes stale), the host mirrors go stale and the tracked extrema are unknown again until
+        somebody asks."""
+        import torch
+        ids = gone = None
+        if torch.is_tensor(nodes_or_gone) and nodes_or_gone.dtype == torch.uint8:
+            if tuple(nodes_or_gone.shape) != (self.n_nodes,):
+                raise ValueError("the flags must be a uint8 tensor [%d], got shape %s" % (self.n_nodes, tuple(nodes_or_gone.shape)))
+            gone = nodes_or_gone
+        elif torch.is_tensor(nodes_or_gone):
+            if nodes_or_gone.dim() != 1 or nodes_or_gone.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError("nodes must be a 1-d integer tensor (ids) or a uint8 tensor [n_nodes] (flags)")
+            ids = nodes_or_gone
+        else:
+            ids = np.asarray(nodes_or_gone).reshape(-1)
+            if ids.size and ids.dtype.kind not in "iu":
+                raise ValueError("node ids must be integers, got %s" % ids.dtype)
+            if ids.size and (int(ids.min()) < -2 ** 31 or int(ids.max()) >= 2 ** 31):
+                raise ValueError("node ids must fit in int32")
+            ids = ids.astype(np.int32)
+        _lib.require_gpu(device)
+        if device is None:
+            device = next(iter(self._dev)) if self._dev else "cuda"
+        dev = torch.device(device)
+        o_ptr, o_nbr, o_eid, o_ts = self.device_arrays(dev)
+        n, old_total = self.n_nodes, int(o_nbr.shape[0])
+        if gone is None:
+            ids = torch.as_tensor(ids).to(device=dev, dtype=torch.int32).contiguous()
+            gone = torch.empty(n, dtype=torch.uint8, device=dev)
+            _lib.call("pfo_nodes_flag", _lib.ptr(ids), int(ids.shape[0]), n, _lib.ptr(gone), _lib.stream_ptr())
+        else:
+            gone = gone.to(dev).contiguous()
+        if _row_flags is not None:             # (TGN.forget: which edge-table rows the dropped / the surviving entries name)
+            _lib.call("pfo_edge_rows_mark_nodes", _lib.ptr(o_ptr), _lib.ptr(o_nbr), _lib.ptr(o_eid), old_total, n, _lib.ptr(gone),
+                      int(_row_flags.shape[0]), _lib.ptr(_row_flags), _lib.stream_ptr())
+        if old_total == 0:
+            return 0
+        nbytes = _lib.byte_count("pfo_csr_forget_scratch_bytes", n, old_total)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        keep = torch.empty(old_total, dtype=torch.uint8, device=dev)
+        new_pos = torch.empty(old_total + 1, dtype=torch.int64, device=dev)
+        n_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        _lib.call("pfo_csr_forget_plan", _lib.ptr(o_ptr), _lib.ptr(o_nbr), n, old_total, _lib.ptr(gone), _lib.ptr(keep),
+                  _lib.ptr(new_pos), _lib.ptr(n_ptr), _lib.ptr(scratch), nbytes, _lib.stream_ptr())
+        total = int(n_ptr[n].item())                                 # the one read-back
+        if total == old_total:
+            return 0
+        n_nbr = torch.empty(total, dtype=torch.int32, device=dev)
+        n_eid = torch.empty(total, dtype=torch.int32, device=dev)
+        n_ts = torch.empty(total, dtype=torch.float64, device=dev)
+        _lib.call("pfo_csr_forget_copy", _lib.ptr(o_nbr), _lib.ptr(o_eid), _lib.ptr(o_ts), old_total, _lib.ptr(keep), _lib.ptr(new_pos),
+                  total, _lib.ptr(n_nbr), _lib.ptr(n_eid), _lib.ptr(n_ts), _lib.stream_ptr())
+        self._dev = {_dev_key(dev): (n_ptr, n_nbr, n_eid, n_ts)}
+        self._host = None
+        self._max_nbr, self._max_eidx = None, None
+        self._version += 1
+        return old_total - total
+
     def remap_edge_idxs(self, remap, device=None):
         """``eidx[i] = remap[eidx[i]]`` in place on the device (``pfo_eidx_remap``), after the edge-feature table this finder
         points into has been compacted (``TGN.expire``).  ``remap`` i32[old row count] on the device; no entry of this finder

@@ -1,6 +1,6 @@
 """The serving surface of the model: everything a served ``TGN`` does between training steps - ``recommend`` (read-only),
 ``observe`` / ``ingest`` (state advance), the tables that grow (``reserve``, ``add_nodes``, ``add_edge_features``), the holdings
-ledger and the retention window (``expire``).  A plain mixin that ``TGN`` inherits ahead of ``nn.Module``: the training step
+ledger, the retention window (``expire``) and erasure by node (``forget``).  A plain mixin that ``TGN`` inherits ahead of ``nn.Module``: the training step
 calls nothing in here."""
 import ctypes
 
@@ -545,21 +545,37 @@ class Serving:
         if not np.isfinite(cutoff):
             raise ValueError("the cutoff must be finite, got %r" % cutoff)
         _lib.require_gpu(self.device)
+        taking_part = self._finders_over_table(finders, compact_edges)
+        self._quiesce()
+        flags = self._edge_row_flags() if compact_edges else None
+        dropped = sum(nf.expire(cutoff, self.device, _row_flags=flags) for nf in taking_part)
+        if not compact_edges or dropped == 0:                        # (nothing expired: nothing can be released)
+            return dropped, None
+        return dropped, self._release_edge_rows(flags, taking_part)
+
+    def _finders_over_table(self, finders, compact_edges):
+        """The finders a removal runs over: the model's own, then ``finders`` (each once).  Before a compaction every one of
+        them must name rows of this table only (``ValueError``)."""
         taking_part = [self.neighbor_finder]
         for nf in (finders or ()):
             if not any(nf is f for f in taking_part):
                 taking_part.append(nf)
-        n_rows, Ef = int(self.edge_raw_features.shape[0]), self.n_edge_features
+        n_rows = int(self.edge_raw_features.shape[0])
         if compact_edges:
             for nf in taking_part:
                 if nf.max_edge_idx() >= n_rows:
                     raise ValueError("a neighbour finder references edge index %d but edge features have %d rows"
                                      % (nf.max_edge_idx(), n_rows))
-        self._quiesce()
-        flags = torch.zeros(n_rows, dtype=torch.int32, device=self.device) if compact_edges else None
-        dropped = sum(nf.expire(cutoff, self.device, _row_flags=flags) for nf in taking_part)
-        if not compact_edges or dropped == 0:                        # (nothing expired: nothing can be released)
-            return dropped, None
+        return taking_part
+
+    def _edge_row_flags(self):
+        return torch.zeros(int(self.edge_raw_features.shape[0]), dtype=torch.int32, device=self.device)
+
+    def _release_edge_rows(self, flags, taking_part):
+        """The table side of ``expire`` and ``forget``, behind the finders: ``flags`` (``pfo_edge_rows_mark[_nodes]`` over every
+        finder taking part) decide which rows are released, the kept ones move down, the finders' edge indices follow.
+        Returns the device ``remap``, or None when no row was released (nothing was written then)."""
+        n_rows, Ef = int(self.edge_raw_features.shape[0]), self.n_edge_features
         nbytes = _lib.byte_count("pfo_edge_rows_plan_scratch_bytes", n_rows)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         remap = torch.empty(n_rows, dtype=torch.int32, device=self.device)
@@ -568,7 +584,7 @@ class Serving:
                   nbytes, _lib.stream_ptr())
         n_keep = int(n_keep_dev.item())
         if n_keep == n_rows:
-            return dropped, None
+            return None
         tmp = torch.empty((n_keep, Ef), dtype=torch.float32, device=self.device)
         _lib.call("pfo_edge_rows_compact", self.edge_raw_features.data_ptr(), n_rows, n_keep, Ef, remap.data_ptr(), tmp.data_ptr(),
                   _lib.stream_ptr())
@@ -576,4 +592,90 @@ class Serving:
             nf.remap_edge_idxs(remap, self.device)
         self._edges.trim(n_keep)                  # (the kernel zeroed the rows behind the new live count)
         self._tables_changed()
-        return dropped, remap
+        return remap
+
+    # ------------------------------------------------------------------ serving: erasure by node
+    def _forget_ids(self, nodes):
+        """``forget``'s argument check -> the ids as a numpy int32 array (host input, fully checked: ``ValueError``) or as the
+        device tensor they came in (shape and dtype only: reading the ids would cost a read-back)."""
+        if torch.is_tensor(nodes):
+            if nodes.dim() != 1 or nodes.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError("nodes must be a 1-d integer tensor of node ids")
+            return nodes
+        ids = np.asarray(nodes)
+        if ids.ndim > 1:
+            raise ValueError("nodes must be a flat list of node ids, got shape %s" % (ids.shape,))
+        ids = ids.reshape(-1)
+        if ids.size == 0:
+            return np.zeros(0, np.int32)
+        if ids.dtype.kind not in "iu":
+            raise ValueError("node ids must be integers, got %s" % ids.dtype)
+        if int(ids.min()) == 0:
+            raise ValueError("node 0 is the padding node and cannot be forgotten")
+        if int(ids.min()) < 1 or int(ids.max()) >= self.n_nodes:
+            raise ValueError("node ids must lie in [1, %d): found %d .. %d" % (self.n_nodes, int(ids.min()), int(ids.max())))
+        return ids.astype(np.int32)
+
+    def forget(self, nodes, compact_edges=True, finders=None):
+        """Erasure by node - ``expire``'s sibling, by node instead of by time: an account is closed and its history has to go,
+        a stock is delisted, an id was ingested by mistake.  Every adjacency entry that touches a node of ``nodes`` leaves the
+        neighbour finder (``NeighborFinder.forget``: the node's own row and the entries of other rows that name it), with
+        ``compact_edges`` the rows of the edge-feature table that only those entries named are released, and the node's own
+        rows return to what ``add_nodes`` gives a new node: memory, ``last_update``, the pending message, its time and flag
+        and the node-feature row to zero, the holdings ledger's row (when there is a ledger) to (-1.., 0, -inf) - ONE launch of
+        ``pfo_node_rows_reset``, also for a node that had no adjacency entry.  Returns ``(n_entries_dropped, remap)`` exactly
+        as ``expire`` does: the entries dropped over all finders taking part, and the device tensor ``remap`` i32[old row
+        count] (old edge index -> new one, -1 for a released row), or ``None`` when ``compact_edges=False`` or no row was
+        released.
+
+        ``nodes``: a host list / array of node ids, or an integer device tensor.  Host ids are checked before anything is
+        written (``ValueError``): they must be integers, node 0 (the padding node) is refused, ids outside ``[1, n_nodes)``
+        are refused; duplicates are fine.  Device ids are not read back - the kernels skip ids outside ``[1, n_nodes)``.  An
+        empty list returns ``(0, None)`` with nothing written.  ``finders`` names the OTHER finders over this model's table, as
+        for ``expire``: all are swept with the same ids and remapped with the same map, and a finder over this table that is
+        not passed is wrong afterwards.
+
+        Order: ``_quiesce()``, the finders, the node rows, then the table.  Left untouched, bit for bit: parameters and
+        gradients, optimizer state, the step counter, the random streams and every row of a node that is not forgotten.
+        Invalidated: what ``expire`` invalidates (the finders' versions stale a captured ``GraphedTrainStep``; after a
+        compaction the padded device adjacency, the ``debug_*`` views of the last forward and a batch prepared ahead of
+        time); in addition the memory's ``_state_version`` is bumped (packed copies of memory rows are stale).  The host-side
+        "some message is pending" knowledge is never lowered.  A forgotten id stays valid and reusable: ``ingest`` /
+        ``observe`` may name it again, and it then starts like a new node.  ``history``, ``exclude="seen"`` and
+        ``only="seen"`` read the finder and follow at once.
+
+        THE LIMIT: what OTHER nodes hold stays.  Their memory and pending messages were computed from past interactions with
+        the forgotten node; they hold derived values, not ids, and they are not recomputed (that takes a replay of the log
+        without the node).  Other users' holdings rows that name a forgotten stock stay too: ``item_ok`` at query time or
+        ``update_holdings`` deal with those.
+
+        Call it BETWEEN steps, like ``add_nodes`` and ``expire``.  On a data-parallel group EVERY rank calls it with the
+        same ids: state is replicated, there is no collective.  Two read-backs at the most per call (the surviving entry total
+        per finder, the new row count); without a device it raises like every compute method."""
+        ids = self._forget_ids(nodes)
+        if int(ids.shape[0]) == 0:
+            return 0, None
+        _lib.require_gpu(self.device)
+        n, m, h = self.n_nodes, self.memory, self.holdings
+        floats = [self.node_raw_features] + ([] if m is None else [m.memory, m.last_update, m.msg_table, m.msg_time])
+        if any(t.dtype != torch.float32 for t in floats):
+            raise _lib.PfoError("the node tables must be fp32 to be reset on the device")
+        taking_part = self._finders_over_table(finders, compact_edges)
+        self._quiesce()
+        with torch.no_grad():
+            ids = torch.as_tensor(ids).to(device=self.device, dtype=torch.int32).contiguous()
+            flags = self._edge_row_flags() if compact_edges else None
+            dropped = sum(nf.forget(ids, self.device, _row_flags=flags) for nf in taking_part)
+            gone = torch.empty(n, dtype=torch.uint8, device=self.device)
+            _lib.call("pfo_nodes_flag", ids.data_ptr(), int(ids.shape[0]), n, gone.data_ptr(), _lib.stream_ptr())
+            mem =[None, 0, None, None, 0, None, None] if m is None else [
+                m.memory.data_ptr(), int(m.memory.shape[1]), m.last_update.data_ptr(), m.msg_table.data_ptr(), int(m.msg_table.shape[1]),
+                m.msg_time.data_ptr(), m.has_msg.data_ptr()]
+            held = [None, 0, None, None] if h is None else [h.idx.data_ptr(), h.width, h.len.data_ptr(), h.time.data_ptr()]
+            _lib.call("pfo_node_rows_reset", gone.data_ptr(), n, *mem, self.node_raw_features.data_ptr(), self.n_node_features,
+                      *held, _lib.stream_ptr())
+            if m is not None:
+                m._state_version += 1
+        if not compact_edges or dropped == 0:                        # (no entry went: no row can be released)
+            return dropped, None
+        return dropped, self._release_edge_rows(flags, taking_part)
