@@ -922,6 +922,36 @@ int pfo_holdings_gather(const int32_t* users, int64_t U, const int32_t* hold_idx
                         int32_t* port_len_out, int32_t* excl_pos_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Holdings from trades (abi 6, additive): the ledger's second writer - buys and sells applied to the rows in event order.
+ * Tables as above, and optionally hold_qty f64[n_nodes, W]: the share count of every slot, 0.0 at and behind hold_len.
+ *
+ * pfo_holdings_apply: for e = 0..N-1 in input order, u = src[e] i32, s = stock[e] i32, side[e] i32, t = ts[e] f64:
+ *   - valid iff 1 <= u < n_nodes, s >= 0, side is +1 (buy) or -1 (sell) and - when hold_qty AND qty are given - q = qty[e] is
+ *     finite and > 0.  An invalid event is skipped whole.  With hold_qty and qty NULL every q is 1.0; without hold_qty, qty is
+ *     not read.
+ *   - L = clamp(hold_len[u], 0, W); j = the FIRST position of hold_idx[u, :L] that holds s (rows the snapshot writer seeded
+ *     may hold duplicates and negative entries).
+ *   - buy, present: hold_qty[u, j] += q (one fp64 add), nothing without quantities.  Buy, absent, L < W: hold_idx[u, L] = s,
+ *     hold_qty[u, L] = q, hold_len[u] = L + 1.  Buy, absent, row full: the row is unchanged, counters[0] (overflow) += 1.
+ *   - sell, absent: unchanged, counters[1] (unmatched) += 1.  Sell, present: with quantities rem = hold_qty[u, j] - q; rem > 0:
+ *     hold_qty[u, j] = rem.  Otherwise (always without quantities) the position is closed: entries j+1 .. L-1 of hold_idx and
+ *     hold_qty move one slot to the front, slot L-1 becomes (-1, 0.0), hold_len[u] = L - 1 - a row lists positions oldest first.
+ *   - every valid event: hold_time[u] = t (nothing is compared with the stored time).
+ *   Rows of users no valid event names keep every bit; the inputs are never written; counters i64[2] (nullable) are ADDED to.
+ *   The result is that loop's on every run and for every launch geometry: the event indices are grouped by user with a stable
+ *   radix (8 bits a pass, ceil(log256(n_nodes)) passes; N <= 1024 in one launch), then one wavefront walks a user's chain over
+ *   the row held in registers and writes it once; only the two integer counters meet in atomics.  A user with many events
+ *   in one call is walked serially.  scratch: pfo_holdings_apply_scratch_bytes(n_nodes, N) bytes (-1 for bad sizes), content
+ *   on entry irrelevant.
+ * PFO_ERR_INVALID - checked before anything is read, nothing is written: W outside [1, 256], N outside [0, 2^31), n_nodes
+ * outside [1, 2^31); then a null pointer (qty, hold_qty and counters may be NULL), a short scratch.  N == 0 queues nothing.
+ */
+int64_t pfo_holdings_apply_scratch_bytes(int64_t n_nodes, int64_t N);
+int pfo_holdings_apply(const int32_t* src, const int32_t* stock, const int32_t* side, const double* qty, const double* ts, int64_t N,
+                       int32_t* hold_idx, int32_t* hold_len, double* hold_time, double* hold_qty, int64_t n_nodes, int32_t W,
+                       int64_t* counters, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * History gather (abi 6, additive): what a user has interacted with, read from the temporal adjacency the finder keeps on the
  * device - the time-sorted CSR indptr i64[n_nodes + 1], adj_nbr i32, adj_ts f64.  All pointers are device pointers.
  *

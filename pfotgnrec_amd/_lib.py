@@ -262,6 +262,9 @@ PROTOTYPES = {
                                      _VP]),
     "pfo_holdings_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP,
                                       _VP]),
+    "pfo_holdings_apply_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "pfo_holdings_apply": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32, _VP, _VP, C.c_int64,
+                                     _VP]),
     "pfo_history_gather": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int64, _VP, C.c_int32, _VP, C.c_int32,
                                      _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_returns_scatter_scratch_bytes": (C.c_int64, [C.c_int64]),

@@ -70,11 +70,13 @@ def _rows_of_log(arg, N, what):
 
 
 def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
-          portfolios, upper_u, groups=None, group_cap=None, seen_since=None, seen_width=None, seen_max_scan=0):
+          portfolios, upper_u, groups=None, group_cap=None, seen_since=None, seen_width=None, seen_max_scan=0, *,
+          advance_holdings=False):
     """Everything ``backtest`` refuses on the host, before any device work (ValueError) -> (N, k, cutoffs, batch_size, horizon,
     upper_u, exclude, portfolios, seen), the exclude / portfolios over the whole log as ``_rows_of_log`` leaves them, seen =
     (since, width, max_scan) as ``recommend.validate_seen`` leaves them (since over the whole log).  ``groups`` / ``group_cap``:
-    the checks of ``recommend`` (``recommend.validate_groups``), made here once for the whole log."""
+    the checks of ``recommend`` (``recommend.validate_groups``), made here once for the whole log.  ``advance_holdings`` needs a
+    ledger, whose ``upper_u`` must agree with the others like every known one."""
     from .functional import check_cutoffs
     try:
         k = operator.index(k)
@@ -117,6 +119,8 @@ def check(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, 
         raise ValueError("mv needs portfolios: a packed pair over the log, one list of stock indices per interaction, or \"held\"")
     if (R._is_held(exclude) or R._is_held(portfolios)) and tgn.holdings is None:
         raise ValueError('"held" needs a holdings ledger: call track_holdings(width, upper_u) first')
+    if advance_holdings and tgn.holdings is None:
+        raise ValueError("advance_holdings needs a holdings ledger: call track_holdings(width, upper_u) first")
     known = [(what, int(v)) for what, v in (("upper_u", upper_u), ("tables.upper_u", getattr(tables, "upper_u", None)),
                                             ("mv.upper_u", getattr(mv, "upper_u", None)),
                                             ("the holdings ledger's upper_u", tgn.holdings.upper_u if tgn.holdings is not None else None))
@@ -176,14 +180,14 @@ def _without(ids, truth):
 def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
                   mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
                   upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None, seen_since=None, seen_width=None,
-                  seen_max_scan=0):
+                  seen_max_scan=0, advance_holdings=False):
     """The walk of ``backtest``; returns its per-interaction rows as host arrays after ONE read-back: dict(rank i32[n],
     recall f32[n, n_c], ndcg f32[n, n_c], invest f64[n, 4 n_c], list_item i32[n, k], n_valid i32[n]) - ``list_item`` the served
     lists, rank ``_lib.EVAL_RANK_NONE`` where the item taken is not in the list."""
     from .functional import list_buffers, list_metrics
     N, k, cuts, batch_size, horizon, upper_u, ex_log, pf_log, (since_log, seen_width, seen_max_scan) = check(
         tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
-        portfolios, upper_u, groups, group_cap, seen_since, seen_width, seen_max_scan)
+        portfolios, upper_u, groups, group_cap, seen_since, seen_width, seen_max_scan, advance_holdings=bool(advance_holdings))
     hg_mode, hg_log, stock_groups = check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log)
     dev = tgn.device
     _lib.require_gpu(dev)
@@ -208,6 +212,9 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
     truth = R._to_dev(dev, destinations, torch.int32)
     users_d = R._to_dev(dev, sources, torch.int32)
     held_ex, held_pf = R._is_held(ex_log), R._is_held(pf_log)
+    if advance_holdings:                                              # the batch's interactions as buys, all on the device once
+        buy_stock, buy_side = truth - (upper_u + 1), torch.ones_like(users_d)
+        buy_ts = R._to_dev(dev, edge_times, torch.float64)
     seen_ex, seen_pf = R._is_seen(ex_log), R._is_seen(pf_log)
     if seen_ex or seen_pf:
         times_d = R._to_dev(dev, edge_times, torch.float64)
@@ -263,6 +270,8 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
         lists[lo:hi].copy_(item_ids)
         n_valid_all[lo:hi].copy_(n_valid)
         tgn.observe(sources[lo:hi], destinations[lo:hi], edge_times[lo:hi], edge_idxs[lo:hi], batch_size=None, append=append)
+        if advance_holdings:
+            tgn.holdings.apply(users_d[lo:hi], buy_stock[lo:hi], buy_side[lo:hi], buy_ts[lo:hi])
     names = ("rank", "recall", "ndcg", "invest", "list_item", "n_valid")
     bufs = out + (lists, n_valid_all)
     # one read-back: every buffer's rows as bytes of one device tensor, one copy
@@ -279,7 +288,7 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
 def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
              mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
              name="backtest", upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None, seen_since=None,
-             seen_width=None, seen_max_scan=0):
+             seen_width=None, seen_max_scan=0, advance_holdings=False):
     """The served lists of a model held against what happened: a prequential walk over a chronological log (numpy arrays like
     the entry points, or device tensors i32 / i32 / f64 / i32).  Per batch ``[lo, hi)`` of ``batch_size`` interactions:
 
@@ -294,7 +303,11 @@ def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cut
        c stocks of the list would have done to the portfolio (``portfolios``; None: empty) for every c of ``cutoffs`` (each in
        [1, k]) - written into one set of device buffers for the whole log.
     3. ``tgn.observe`` of the batch (``batch_size=None``, ``append``): the model's state advances exactly as ``observe`` over
-       the log with this ``batch_size`` would advance it.  The holdings ledger is not written.
+       the log with this ``batch_size`` would advance it.  The holdings ledger is not written - unless
+       ``advance_holdings=True`` (needs a ledger): then
+    4. the batch's interactions are applied to the ledger as buys of stock ``destination - upper_u - 1`` by their sources
+       (``pfo_holdings_apply``; quantity 1.0 on a ledger with quantities), so that ``"held"`` is what the user held before THAT
+       batch, not before the log.  No sells: a walk observes interactions only.
 
     One read-back at the end.  The LAST batch is not skipped and there is no ``is_test_run``: this is not the reference's
     evaluation protocol (``eval_recommendation`` is) and shares none of its limits - any k up to 64, up to 65536 candidates.
@@ -327,5 +340,5 @@ def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cut
                          tables=tables, horizon=horizon, mv=mv, basket=basket, exclude=exclude, portfolios=portfolios, item_ok=item_ok,
                          n_neighbors=n_neighbors, keep_truth=keep_truth, append=append, upper_u=upper_u, groups=groups, group_cap=group_cap,
                          held_groups=held_groups, stock_groups=stock_groups, seen_since=seen_since, seen_width=seen_width,
-                         seen_max_scan=seen_max_scan)
+                         seen_max_scan=seen_max_scan, advance_holdings=advance_holdings)
     return backtest_result_dict(name, rows["rank"], rows["invest"], cutoffs)

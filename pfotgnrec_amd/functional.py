@@ -831,6 +831,45 @@ def holdings_store(src, port_idx, port_len, ts, hold_idx, hold_len, hold_time, s
               hold_time.data_ptr(), n_nodes, W, scratch.data_ptr(), scratch.numel() * scratch.element_size(), _lib.stream_ptr())
 
 
+def holdings_apply(src, stock, side, ts, hold_idx, hold_len, hold_time, qty=None, hold_qty=None, counters=None, scratch=None):
+    """Applies buys and sells to the ledger rows in place, in event order (``pfo_holdings_apply``; the rules are stated in
+    include/pfotgn.h): a buy appends the stock behind the row's live entries or adds to its share count, a sell takes from the
+    count or closes the position - the entries behind it move one slot to the front -, every valid event sets the row's time.
+    Invalid events (user outside [1, n_nodes), negative stock, a side that is not +1 / -1, with both ``hold_qty`` and ``qty`` a
+    quantity that is not finite and positive) are skipped whole.
+
+    src / stock / side i32[N], ts f64[N], qty f64[N] or None (every quantity 1.0; ignored without ``hold_qty``); hold_idx
+    i32[n_nodes, W], hold_len i32[n_nodes], hold_time f64[n_nodes], hold_qty f64[n_nodes, W] or None, all contiguous; counters:
+    int64[2] (overflow: buys into a full row; unmatched: sells of a stock the row does not hold) the call ADDS to, or None;
+    scratch: a uint8 / int32 tensor of ``pfo_holdings_apply_scratch_bytes`` bytes or None (allocated)."""
+    if (hold_idx.dim() != 2 or hold_idx.dtype != torch.int32 or hold_len.dtype != torch.int32 or hold_time.dtype != torch.float64
+            or tuple(hold_len.shape) != (hold_idx.shape[0],) or tuple(hold_time.shape) != (hold_idx.shape[0],)):
+        raise ValueError("the ledger must be (i32 [n_nodes, W], i32 [n_nodes], f64 [n_nodes])")
+    if hold_qty is not None and (hold_qty.dtype != torch.float64 or tuple(hold_qty.shape) != tuple(hold_idx.shape)):
+        raise ValueError("the ledger's quantities must be f64 [n_nodes, W]")
+    if not all(t is None or t.is_contiguous() for t in (hold_idx, hold_len, hold_time, hold_qty, counters)):
+        raise ValueError("the ledger tables must be contiguous")
+    if counters is not None and (counters.dtype != torch.int64 or tuple(counters.shape) != (2,)):
+        raise ValueError("counters must be int64 [2]")
+    n_nodes, W = (int(v) for v in hold_idx.shape)
+    N = int(src.shape[0]) if src.dim() == 1 else -1
+    if (N < 0 or any(t.dtype != torch.int32 or tuple(t.shape) != (N,) for t in (src, stock, side)) or ts.dtype != torch.float64
+            or tuple(ts.shape) != (N,) or (qty is not None and (qty.dtype != torch.float64 or tuple(qty.shape) != (N,)))):
+        raise ValueError("events must be src i32[N], stock i32[N], side i32[N], ts f64[N] and qty f64[N] or None")
+    dev = hold_idx.device
+    _lib.require_gpu(dev)
+    for t in (src, stock, side, ts, qty, hold_len, hold_time, hold_qty, counters, scratch):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    need = _lib.byte_count("pfo_holdings_apply_scratch_bytes", n_nodes, N)
+    if scratch is None or scratch.numel() * scratch.element_size() < need or not scratch.is_contiguous():
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    _lib.call("pfo_holdings_apply", _lib.ptr(src.contiguous()), _lib.ptr(stock.contiguous()), _lib.ptr(side.contiguous()),
+              _lib.ptr(qty.contiguous() if qty is not None else None), _lib.ptr(ts.contiguous()), N, hold_idx.data_ptr(),
+              hold_len.data_ptr(), hold_time.data_ptr(), _lib.ptr(hold_qty), n_nodes, W, _lib.ptr(counters), scratch.data_ptr(),
+              scratch.numel() * scratch.element_size(), _lib.stream_ptr())
+
+
 def holdings_gather(users, hold_idx, hold_len, upper_u, items=None, pos_scratch=None):
     """The ledger rows of ``users`` i32[U] (``pfo_holdings_gather``): (port_idx i32[U, W], port_len i32[U], excl_pos) - users
     outside [0, n_nodes) give (-1.., 0).  With ``items`` i32[I] (distinct candidate node ids) excl_pos i32[U, W] holds, per

@@ -16,6 +16,7 @@ inference and - for the BPR loss - an autograd formula:
     torch.ops.pfotgn.recommend_list_topk(user_emb, item_emb, k, list_pos, ...) the k best of every user's own list
     torch.ops.pfotgn.recommend_list_mv_topk(...)                               the same in the mean-variance order
     torch.ops.pfotgn.history_gather(indptr, adj_nbr, adj_ts, users, ts, width, ...)  what each user interacted with before its time
+    torch.ops.pfotgn.holdings_apply(src, stock, side, ts, hold_idx, hold_len, hold_time, ...)  buys and sells applied to ledger rows, in place
 
 Only a HIP implementation is registered ("cuda" dispatch key = ROCm here): on any other device the dispatcher raises,
 there is no CPU fallback.  The TGN step itself keeps its ``autograd.Function`` (``tgn._EmbedFn``): it owns state (memory,
@@ -226,3 +227,19 @@ def _(indptr, adj_nbr, adj_ts, users, ts, width, since=None, max_scan=0, items=N
     rows = lambda dt, w=width: users.new_empty((U, w), dtype=dt)
     return (rows(torch.int32), users.new_empty((U,), dtype=torch.int32), rows(torch.float64), rows(torch.int32),
             rows(torch.int32, width if items is not None else 0), rows(torch.int32, width if upper_u is not None else 0))
+
+
+@torch.library.custom_op(_LIB_NS + "::holdings_apply", mutates_args=("hold_idx", "hold_len", "hold_time", "hold_qty", "counters"),
+                         device_types="cuda")
+def holdings_apply(src: torch.Tensor, stock: torch.Tensor, side: torch.Tensor, ts: torch.Tensor, hold_idx: torch.Tensor,
+                   hold_len: torch.Tensor, hold_time: torch.Tensor, hold_qty: Optional[torch.Tensor], counters: Optional[torch.Tensor],
+                   qty: Optional[torch.Tensor] = None) -> None:
+    """``functional.holdings_apply``: the ledger tables (and the counters) are written in place, nothing is returned.  The two
+    optional tables that are written take no default (pass None): the dispatcher bumps the version of every mutated
+    argument by position."""
+    functional.holdings_apply(src, stock, side, ts, hold_idx, hold_len, hold_time, qty, hold_qty, counters)
+
+
+@holdings_apply.register_fake
+def _(src, stock, side, ts, hold_idx, hold_len, hold_time, hold_qty, counters, qty=None):
+    return None

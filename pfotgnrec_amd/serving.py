@@ -410,9 +410,18 @@ class Serving:
         ``portfolios``: what each record says its user holds at that moment, in a form ``update_holdings`` takes (host forms
         with host inputs, the device pair with device inputs); needs a ledger (``track_holdings``).  Its checks join the ones
         above - a rejected call leaves the ledger too - and the ledger is written ONCE per call behind ``add_nodes`` (last
-        record per user over the whole input: batch boundaries do not matter to it).  None: the ledger is not touched."""
+        record per user over the whole input: batch boundaries do not matter to it).  None: the ledger is not touched.
+
+        ``portfolios="buys"``: the interactions themselves are the feed - every ingested interaction is a buy of stock
+        ``destination - upper_u - 1`` by its source (quantity 1.0 on a ledger with quantities), applied to the ledger by
+        ``pfo_holdings_apply`` once per call, where the snapshot is written otherwise: the ledger ends where ``ingest`` followed
+        by ``trade_holdings`` of the same interactions leaves it.  A destination that is not an item node gives a negative
+        stock and is skipped by the kernel's rule."""
         if portfolios is not None and self.holdings is None:
             raise ValueError("portfolios need a holdings ledger: call track_holdings(width, upper_u) first")
+        buys = isinstance(portfolios, str) and portfolios == "buys"
+        if portfolios is not None and not buys and self.holdings.quantities:
+            raise ValueError("a ledger with quantities is written by trades only: portfolios=\"buys\" or trade_holdings")
         on_dev, N, (sources, destinations, edge_times, edge_features) = _check_log(
             batch_size, sources=(sources, torch.int32), destinations=(destinations, torch.int32),
             edge_times=(edge_times, torch.float64), edge_features=(edge_features, None))
@@ -443,7 +452,7 @@ class Serving:
             if node_features is not None and tuple(np.shape(node_features)) != (n_new, self.n_node_features):
                 raise ValueError("node_features must have shape [%d, %d]: one row per new node" % (n_new, self.n_node_features))
         held = None
-        if portfolios is not None:                # (the new nodes are rows of the ledger by the time it is written)
+        if portfolios is not None and not buys:   # (the new nodes are rows of the ledger by the time it is written)
             from . import holdings as H
             held = H.validate(self.holdings.width, self.n_nodes + n_new, sources, portfolios, edge_times)
         if N == 0:
@@ -453,21 +462,29 @@ class Serving:
             self.add_nodes(n_new, node_features)
         if held is not None:
             self._write_holdings(held)
+        if buys:
+            self._buy_holdings(sources, destinations, edge_times)
         new_idxs = self.add_edge_features(edge_features)
         eidx = torch.arange(int(new_idxs[0]), int(new_idxs[0]) + N, dtype=torch.int32, device=self.device) if on_dev else new_idxs
         return self.observe(sources, destinations, edge_times, eidx, batch_size, append=True), new_idxs
 
     # ------------------------------------------------------------------ serving: the holdings ledger
-    def track_holdings(self, width, upper_u):
+    def track_holdings(self, width, upper_u, quantities=False):
         """Creates the holdings ledger (``self.holdings``, None before): per node row the portfolio its user's newest
         interaction record carried - ``idx`` i32[n_nodes, width] STOCK indices padded with -1 (the packed form of
         ``pack_portfolios``; the item node of stock ``s`` is ``s + upper_u + 1``), ``len`` i32[n_nodes], ``time`` f64[n_nodes]
         (-1 / 0 / -inf until written) - in capacity storage that follows ``node_capacity`` (``reserve`` / ``add_nodes`` keep
-        live rows bit for bit) and the model's device.  ``update_holdings`` and ``ingest(portfolios=)`` write it,
+        live rows bit for bit) and the model's device.  ``update_holdings`` and ``ingest(portfolios=)`` write it from snapshots,
+        ``trade_holdings``, ``ingest(portfolios="buys")`` and ``backtest(advance_holdings=True)`` from trades,
         ``recommend(exclude="held", portfolios="held")`` and ``holdings.rows(users)`` read it; the training step, ``observe``
         and ``expire`` do not touch it, and it is not part of ``state_dict()``: persist ``holdings.idx / len / time`` and load
-        them with ``update_holdings``.  Once: a second call with other arguments raises ``ValueError``.  Returns the ledger."""
+        them with ``update_holdings``.  Once: a second call with other arguments raises ``ValueError``.  Returns the ledger.
+
+        ``quantities=True``: the ledger also keeps ``qty`` f64[n_nodes, width], the share count of every slot (0.0 at and behind
+        ``len``), in the same capacity storage.  Such a ledger is written by trades only (``trade_holdings``,
+        ``ingest(portfolios="buys")``): the snapshot writers raise ``ValueError`` on it, a snapshot carries no share counts."""
         from . import holdings as H
+        quantities = bool(quantities)
         try:
             width, upper_u = int(width), int(upper_u)
         except (TypeError, ValueError):
@@ -477,15 +494,16 @@ class Serving:
         if not 0 <= upper_u < 2 ** 31 - 1:
             raise ValueError("upper_u must be a non-negative int32 (got %d)" % upper_u)
         if self.holdings is not None:
-            if (self.holdings.width, self.holdings.upper_u) != (width, upper_u):
-                raise ValueError("the model already tracks holdings with width %d, upper_u %d"
-                                 % (self.holdings.width, self.holdings.upper_u))
+            if (self.holdings.width, self.holdings.upper_u, self.holdings.quantities) != (width, upper_u, quantities):
+                raise ValueError("the model already tracks holdings with width %d, upper_u %d, %s quantities"
+                                 % (self.holdings.width, self.holdings.upper_u, "with" if self.holdings.quantities else "without"))
             return self.holdings
-        self.holdings = H.Holdings(self.n_nodes, self.node_capacity, width, upper_u, self.device)
+        self.holdings = H.Holdings(self.n_nodes, self.node_capacity, width, upper_u, self.device, quantities)
         return self.holdings
 
     def update_holdings(self, sources, portfolios, edge_times):
-        """The one writer of the ledger: for every event in input order, ``holdings[sources[e]] = (portfolios[e], edge_times[e])``
+        """The snapshot writer of the ledger (``trade_holdings`` is the other writer, and the only one of a ledger with
+        quantities): for every event in input order, ``holdings[sources[e]] = (portfolios[e], edge_times[e])``
         - per user the LAST event of the call wins, an empty portfolio overwrites, entries are stored verbatim, nothing is
         compared with the stored time (chronological input is the caller's contract, as for ``observe``); node 0 is skipped.
         One native call (``pfo_holdings_store``: a memset and two launches).  Seeds a served model from the training log and
@@ -498,6 +516,8 @@ class Serving:
         only - the kernel skips ids outside [1, n_nodes) and clamps lengths to the row.  Returns the number of events."""
         if self.holdings is None:
             raise ValueError("no holdings ledger: call track_holdings(width, upper_u) first")
+        if self.holdings.quantities:
+            raise ValueError("a ledger with quantities is written by trades only: trade_holdings")
         from . import holdings as H
         w = H.validate(self.holdings.width, self.n_nodes, sources, portfolios, edge_times)
         if w.N:
@@ -512,6 +532,59 @@ class Serving:
             else:
                 ts, src, idx, length = self._batch_to_dev([(w.ts, np.float64), (w.src, np.int32), (w.idx, np.int32), (w.len, np.int32)])
             self.holdings.store(src, idx, length, ts)
+
+    def trade_holdings(self, sources, stocks, sides, edge_times, quantities=None):
+        """The ledger's second writer: a feed of trades applied to the rows in event order on the device - one native call
+        (``pfo_holdings_apply``), no row read back.  Event e: user ``sources[e]``, STOCK index ``stocks[e]``,
+        ``sides[e]`` +1 (buy) or -1 (sell), time ``edge_times[e]``, and on a ledger with quantities ``quantities[e]`` shares (None:
+        1.0 each).  A buy of a stock the row holds adds to its share count (nothing without quantities), of another one appends it
+        behind the row's entries - a full row stays as it is and counts as an overflow.  A sell takes from the count; when
+        nothing is left, and always without quantities, the position is closed and the entries behind it move one slot to the
+        front (a row lists positions oldest first); a sell of a stock the row does not hold counts as unmatched.  Every event
+        sets the row's time; nothing is compared with the stored time.  ``holdings_counters()`` reads the two counts.
+
+        Host inputs are validated before anything is written (``ValueError``: lengths, integer dtypes, values beyond int32, node
+        ids outside [0, n_nodes), sides outside {-1, +1}, quantities that are not finite and positive) - a rejected call leaves
+        the ledger bit for bit - and staged in one copy.  Device inputs (i32 / i32 / i32 / f64 [/ f64]) are checked for shape and
+        dtype only: the kernel skips an event with a user outside [1, n_nodes), a negative stock, another side or such a
+        quantity, whole.  ``quantities=`` on a ledger without them raises ``ValueError``.  Returns the number of events.
+
+        A saved ledger reloads through here: one buy per stored slot in slot order at the row's time (with its share count on
+        a ledger with quantities) reproduces every row with ``len > 0`` bit for bit; a row with ``len == 0`` keeps time -inf."""
+        if self.holdings is None:
+            raise ValueError("no holdings ledger: call track_holdings(width, upper_u) first")
+        from . import holdings as H
+        t = H.validate_trades(self.n_nodes, self.holdings.quantities, sources, stocks, sides, edge_times, quantities)
+        if t.N:
+            _lib.require_gpu(self.device)
+            with torch.no_grad():
+                if t.on_dev:
+                    cols = [c if c is None else c.contiguous() for c in (t.src, t.stock, t.side, t.ts, t.qty)]
+                else:
+                    host = [(t.ts, np.float64)] + ([(t.qty, np.float64)] if t.qty is not None else []) + [
+                        (t.src, np.int32), (t.stock, np.int32), (t.side, np.int32)]
+                    dev = self._batch_to_dev(host)
+                    cols = [dev[-3], dev[-2], dev[-1], dev[0], dev[1] if t.qty is not None else None]
+                self.holdings.apply(*cols)
+        return t.N
+
+    def holdings_counters(self):
+        """``(overflow, unmatched)`` since the ledger was made - buys that found their row full, sells of a stock the row did not
+        hold - read back from the device (the one synchronisation; no write makes it)."""
+        if self.holdings is None:
+            raise ValueError("no holdings ledger: call track_holdings(width, upper_u) first")
+        return tuple(int(v) for v in self.holdings.counters.cpu().tolist())
+
+    def _buy_holdings(self, sources, destinations, edge_times):
+        """Interactions (host arrays or device tensors, validated by the caller) as buys of stock ``destination - upper_u - 1``."""
+        h = self.holdings
+        with torch.no_grad():
+            if torch.is_tensor(sources):
+                src, dst, ts = (a.contiguous() for a in (sources, destinations, edge_times))
+            else:
+                ts, src, dst = self._batch_to_dev([(np.asarray(edge_times), np.float64), (np.asarray(sources), np.int32),
+                                                   (np.asarray(destinations), np.int32)])
+            h.apply(src, dst - (h.upper_u + 1), torch.ones_like(src), ts)
 
     # ------------------------------------------------------------------ serving: the retention window
     def expire(self, cutoff, compact_edges=True, finders=None):
@@ -622,7 +695,8 @@ class Serving:
         neighbour finder (``NeighborFinder.forget``: the node's own row and the entries of other rows that name it), with
         ``compact_edges`` the rows of the edge-feature table that only those entries named are released, and the node's own
         rows return to what ``add_nodes`` gives a new node: memory, ``last_update``, the pending message, its time and flag
-        and the node-feature row to zero, the holdings ledger's row (when there is a ledger) to (-1.., 0, -inf) - ONE launch of
+        and the node-feature row to zero, the holdings ledger's row (when there is a ledger) to (-1.., 0, -inf; its share
+        counts to 0.0 by a fill) - ONE launch of
         ``pfo_node_rows_reset``, also for a node that had no adjacency entry.  Returns ``(n_entries_dropped, remap)`` exactly
         as ``expire`` does: the entries dropped over all finders taking part, and the device tensor ``remap`` i32[old row
         count] (old edge index -> new one, -1 for a released row), or ``None`` when ``compact_edges=False`` or no row was
@@ -674,6 +748,8 @@ class Serving:
             held = [None, 0, None, None] if h is None else [h.idx.data_ptr(), h.width, h.len.data_ptr(), h.time.data_ptr()]
             _lib.call("pfo_node_rows_reset", gone.data_ptr(), n, *mem, self.node_raw_features.data_ptr(), self.n_node_features,
                       *held, _lib.stream_ptr())
+            if h is not None and h.quantities:                       # (not the hot path: a fill by the same flags)
+                h.qty.masked_fill_(gone.bool().unsqueeze(1), 0.0)
             if m is not None:
                 m._state_version += 1
         if not compact_edges or dropped == 0:                        # (no entry went: no row can be released)
