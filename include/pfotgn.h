@@ -550,6 +550,44 @@ int pfo_recommend_list_mv_topk(const float* user_emb, const float* item_emb, con
                                double* y_out, double* fused_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Position-weighted mean-variance order (abi 6, additive): the three entries that compute y from a portfolio and serve a list,
+ * with a weight per holding in place of 1 / n_holding.  Each takes its sibling's parameter list with port_w f64[U, port_stride]
+ * (row stride port_stride, aligned with port_idx) behind port_len.
+ *   Holding p of user u counts iff port_idx[u, p] is in [0, n_stocks) AND port_w[u, p] is finite and > 0 - a zero, negative, NaN
+ *   or infinite weight leaves the holding out exactly as an out-of-range stock is left out.  Over the counted holdings in row
+ *   order, fp64, every product rounded before it is added: ssum_w = sequential sum of port_w[u, p] * cov(i, p) (the covariance as
+ *   in pfo_recommend_mv_topk, one rounded product, one rounded add), wsum = sequential sum of port_w[u, p],
+ *   y = (mu / gamma - 0.5 * ((1.0 / wsum) * ssum_w)) / var; no counted holding: y = (mu / gamma) / var.
+ *   With every weight exactly 1.0 that is the sibling's y bit for bit; scaling a user's weights by a power of two changes no bit.
+ *   Everything else - scores, admissible set, ranks, blend, canonical order, empty slots, diagnostics - is the sibling's.
+ *   port_w == NULL forwards to the sibling, bit for bit.  port_w without port_idx (port_stride > 0, U > 0) is PFO_ERR_INVALID,
+ *   checked where port_idx without port_len is.  Bounds, error order and U == 0 behaviour are the sibling's.
+ *   There is no weighted basket and no weighted capped form.
+ */
+int pfo_recommend_mv_topk_weighted(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                   int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                   const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                   int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                   const int32_t* port_len, const double* port_w, int32_t port_stride, double gamma, double lambda_mv,
+                                   int32_t k, int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                   double* y_out, double* fused_out, void* stream);
+int pfo_recommend_mv_topk_wide_weighted(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                        int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                        const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                        int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                        const int32_t* port_len, const double* port_w, int32_t port_stride, double gamma,
+                                        double lambda_mv, int32_t k, int32_t* top_pos, float* top_score, double* top_fused,
+                                        int32_t* n_valid, float* score_out, double* y_out, double* fused_out, void* workspace,
+                                        int64_t workspace_bytes, void* stream);
+int pfo_recommend_list_mv_topk_weighted(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                        int32_t n_t, int32_t D, const int32_t* list_pos, const int32_t* list_len, int32_t list_stride,
+                                        const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                        int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                        const int32_t* port_len, const double* port_w, int32_t port_stride, double gamma,
+                                        double lambda_mv, int32_t k, int32_t* top_pos, float* top_score, double* top_fused,
+                                        int32_t* n_valid, float* score_out, double* y_out, double* fused_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Time-sorted adjacency built on the device: replaces get_neighbor_finder / NeighborFinder.__init__ (utils/utils.py:117-148).
  * Every edge e contributes (dst, eidx, ts) to row src[e] and (src, eidx, ts) to row dst[e]; rows are sorted by timestamp,
  * ties in edge order (Python's stable sorted(key=ts), utils.py:139).  A stable LSD radix sort of the 2E entries; the eight
@@ -950,6 +988,23 @@ int64_t pfo_holdings_apply_scratch_bytes(int64_t n_nodes, int64_t N);
 int pfo_holdings_apply(const int32_t* src, const int32_t* stock, const int32_t* side, const double* qty, const double* ts, int64_t N,
                        int32_t* hold_idx, int32_t* hold_len, double* hold_time, double* hold_qty, int64_t n_nodes, int32_t W,
                        int64_t* counters, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Position weights from the ledger (abi 6, additive): the rows port_w of the weighted recommend entries, aligned with
+ * pfo_holdings_gather's port_idx_out.  For q < U, u = users[q], L = clamp(hold_len[u], 0, W) when 0 <= u < n_nodes, else 0:
+ *   w_out[q, j] = 0.0                                         for j >= L;
+ *   mode 0 (shares): hold_qty[u, j]                           for j < L;
+ *   mode 1 (value):  hold_qty[u, j] * last_close[hold_idx[u, j]] (one rounded product) for j < L and the stock in [0, n_stocks),
+ *                    0.0 for a stock outside it.  A stock never quoted has last_close NaN: its weight is NaN, and the ranking
+ *                    kernel leaves it out.
+ * Every slot of w_out f64[U, W] is written; one launch, one lane per slot; every index read from device memory is range-checked
+ * before use.  last_close f64[>= n_stocks].  PFO_ERR_INVALID before any pointer is looked at: W outside [1, 256], U < 0,
+ * n_nodes < 1 (or >= 2^31), n_stocks < 0, mode outside {0, 1}; then (U > 0) a null pointer - hold_qty always, last_close with
+ * mode 1.  U == 0 queues nothing.
+ */
+int pfo_holdings_gather_weights(const int32_t* users, int64_t U, const int32_t* hold_idx, const int32_t* hold_len, const double* hold_qty,
+                                int64_t n_nodes, int32_t W, const double* last_close, int64_t n_stocks, int32_t mode, double* w_out,
+                                void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * History gather (abi 6, additive): what a user has interacted with, read from the temporal adjacency the finder keeps on the

@@ -40,7 +40,7 @@ from .prices import PriceLedger  # noqa: F401
 from .memory import Memory  # noqa: F401
 from .tgn import TGN  # noqa: F401
 from .optim import FusedAdam, overlap_backward  # noqa: F401
-from .functional import bpr_loss, bpr_loss_blocks, bpr_step, time_encode, rank_metrics, eval_metrics, eval_buffers, eval_metrics_mv, eval_buffers_mv, recommend_topk, recommend_mv_topk, recommend_mv_topk_wide, recommend_basket_topk, recommend_list_topk, recommend_list_mv_topk, holdings_store, holdings_apply, holdings_gather, history_gather, returns_append_day, returns_scatter_closes, day_lookup, list_metrics, list_buffers  # noqa: F401
+from .functional import bpr_loss, bpr_loss_blocks, bpr_step, time_encode, rank_metrics, eval_metrics, eval_buffers, eval_metrics_mv, eval_buffers_mv, recommend_topk, recommend_mv_topk, recommend_mv_topk_wide, recommend_basket_topk, recommend_list_topk, recommend_list_mv_topk, holdings_store, holdings_apply, holdings_gather, holdings_gather_weights, history_gather, returns_append_day, returns_scatter_closes, day_lookup, list_metrics, list_buffers  # noqa: F401
 from .evaluation import eval_recommendation, InvestTables  # noqa: F401
 from .backtest import backtest, backtest_rows, backtest_result_dict  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401,E402

@@ -207,6 +207,16 @@ PROTOTYPES = {
     "pfo_recommend_list_mv_topk": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
                                              _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
                                              C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    # the weighted forms: port_w behind port_len
+    "pfo_recommend_mv_topk_weighted": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                                 _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, C.c_double,
+                                                 C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "pfo_recommend_mv_topk_wide_weighted": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                                      _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, C.c_double,
+                                                      C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    "pfo_recommend_list_mv_topk_weighted": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                                      _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, C.c_double,
+                                                      C.c_double, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_adam_step": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
                                 _VP]),
     "pfo_csr_build_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
@@ -265,6 +275,7 @@ PROTOTYPES = {
     "pfo_holdings_apply_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "pfo_holdings_apply": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32, _VP, _VP, C.c_int64,
                                      _VP]),
+    "pfo_holdings_gather_weights": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int32, _VP, C.c_int64, C.c_int32, _VP, _VP]),
     "pfo_history_gather": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int64, _VP, C.c_int32, _VP, C.c_int32,
                                      _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_returns_scatter_scratch_bytes": (C.c_int64, [C.c_int64]),

@@ -145,6 +145,16 @@ def check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log):
     return mode, (ids, lens) if mode == "rows" else None, sg
 
 
+def check_weights(tgn, N, portfolio_weights, mv, basket, groups, portfolios, pf_log):
+    """``portfolio_weights`` of ``backtest`` over the whole log, checked once and before any device work (ValueError, the checks
+    of ``recommend``: ``recommend.validate_weights``) -> None, ``"shares"`` / ``"value"``, or f64 rows [N, W] on host or device,
+    cut per batch.  ``pf_log``: the portfolios as ``check`` left them."""
+    mvq = None
+    if mv is not None and pf_log is not None:
+        mvq = R.MVQuery(mv, None, None, None) if isinstance(pf_log, str) else R.MVQuery(mv, pf_log[0], pf_log[1], None)
+    return R.validate_weights(N, portfolio_weights, mv, mvq, portfolios, tgn.holdings, basket, groups, what="the log holds")
+
+
 def ledger_days(ledger, timestamps, horizon, device):
     """(past, future) ring slots i32[n] on ``device`` of a ``PriceLedger`` for the interactions' timestamps (host array, or f64
     device tensor: ``lookup``, no read-back): the slot of the interaction's day and of the day ``horizon`` trading days later;
@@ -180,7 +190,7 @@ def _without(ids, truth):
 def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
                   mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
                   upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None, seen_since=None, seen_width=None,
-                  seen_max_scan=0, advance_holdings=False):
+                  seen_max_scan=0, portfolio_weights=None, advance_holdings=False):
     """The walk of ``backtest``; returns its per-interaction rows as host arrays after ONE read-back: dict(rank i32[n],
     recall f32[n, n_c], ndcg f32[n, n_c], invest f64[n, 4 n_c], list_item i32[n, k], n_valid i32[n]) - ``list_item`` the served
     lists, rank ``_lib.EVAL_RANK_NONE`` where the item taken is not in the list."""
@@ -189,8 +199,11 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
         tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs, batch_size, tables, horizon, mv, basket, exclude,
         portfolios, upper_u, groups, group_cap, seen_since, seen_width, seen_max_scan, advance_holdings=bool(advance_holdings))
     hg_mode, hg_log, stock_groups = check_held_groups(tgn, N, held_groups, stock_groups, groups, pf_log)
+    w_log = check_weights(tgn, N, portfolio_weights, mv, basket, groups, portfolios, pf_log)
     dev = tgn.device
     _lib.require_gpu(dev)
+    if w_log is not None and not isinstance(w_log, str):
+        w_log = R._to_dev(dev, w_log, torch.float64)                    # on the device once, cut per batch
     cap = {}
     if groups is not None:
         # on the device once, not once per batch (``recommend`` takes an integer device tensor as it is)
@@ -255,6 +268,8 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
         mv_side = {}
         if mv is not None:
             mv_side = dict(mv=mv, portfolios=seen_pair if seen_pf else pf_log if held_pf else _cut(pf_log, lo, hi), basket=bool(basket))
+            if w_log is not None:
+                mv_side["portfolio_weights"] = w_log if isinstance(w_log, str) else w_log[lo:hi]
         if hg_mode == "rows":
             cap["held_groups"] = _cut(hg_log, lo, hi)
         elif hg_mode == R.PORTFOLIOS and mv is None:                  # (the score order: the rows go along for the groups alone)
@@ -288,7 +303,7 @@ def backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, *
 def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cutoffs=(1, 3, 5), batch_size, tables, horizon=None,
              mv=None, basket=False, exclude=None, portfolios=None, item_ok=None, n_neighbors=None, keep_truth=True, append=False,
              name="backtest", upper_u=None, groups=None, group_cap=None, held_groups=None, stock_groups=None, seen_since=None,
-             seen_width=None, seen_max_scan=0, advance_holdings=False):
+             seen_width=None, seen_max_scan=0, portfolio_weights=None, advance_holdings=False):
     """The served lists of a model held against what happened: a prequential walk over a chronological log (numpy arrays like
     the entry points, or device tensors i32 / i32 / f64 / i32).  Per batch ``[lo, hi)`` of ``batch_size`` interactions:
 
@@ -335,10 +350,15 @@ def backtest(tgn, sources, destinations, edge_times, edge_idxs, items, k, *, cut
     ``recommend`` refuses of ``groups`` / ``group_cap`` (one without the other, a wrong length, non-integers, a cap below 1,
     with ``mv`` more than 2048 candidates) and of ``held_groups`` / ``stock_groups`` - forwarded too, ``held_groups`` over the whole
     LOG like ``exclude``: a packed pair (ids [N, W], lens [N]), one list of group ids per interaction, ``"held"`` or
-    ``"portfolios"`` (without ``groups``, ``"held"`` without a ledger or ``stock_groups``, rows longer than 256, non-integers)."""
+    ``"portfolios"`` (without ``groups``, ``"held"`` without a ledger or ``stock_groups``, rows longer than 256, non-integers).
+
+    ``portfolio_weights`` (by name) is forwarded as well, over the whole LOG like ``portfolios``: one list of numbers per
+    interaction, an f64 [N, W] array or tensor in the shape of the packed portfolios, or ``"shares"`` / ``"value"`` beside
+    ``portfolios="held"`` - and what ``recommend`` refuses of it is refused here, before any device work.  With
+    ``advance_holdings=True`` the buys the walk applies carry one share each, as without weights."""
     rows = backtest_rows(tgn, sources, destinations, edge_times, edge_idxs, items, k, cutoffs=cutoffs, batch_size=batch_size,
                          tables=tables, horizon=horizon, mv=mv, basket=basket, exclude=exclude, portfolios=portfolios, item_ok=item_ok,
                          n_neighbors=n_neighbors, keep_truth=keep_truth, append=append, upper_u=upper_u, groups=groups, group_cap=group_cap,
                          held_groups=held_groups, stock_groups=stock_groups, seen_since=seen_since, seen_width=seen_width,
-                         seen_max_scan=seen_max_scan, advance_holdings=advance_holdings)
+                         seen_max_scan=seen_max_scan, advance_holdings=advance_holdings, portfolio_weights=portfolio_weights)
     return backtest_result_dict(name, rows["rank"], rows["invest"], cutoffs)

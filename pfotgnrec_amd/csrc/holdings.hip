@@ -498,3 +498,49 @@ extern "C" int pfo_holdings_gather(const int32_t* users, int64_t U, const int32_
   PFO_LAUNCH_CHECK();
   return PFO_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ gather: position weights
+// The weight rows of the position-weighted mean-variance order, aligned with pfo_holdings_gather's port_idx_out:
+// one lane per slot of w_out[U, W], every slot written.  mode 0: the share count; mode 1: share count x last close (one rounded
+// product; a stock outside the close table weighs 0.0, a stock never quoted NaN - the ranking kernel leaves both out).
+namespace {
+__global__ void __launch_bounds__(HOLD_BLOCK)
+holdings_gather_weights_kernel(const int32_t* __restrict__ users, int64_t U, const int32_t* __restrict__ hold_idx,
+                               const int32_t* __restrict__ hold_len, const double* __restrict__ hold_qty, int64_t n_nodes, int32_t W,
+                               const double* __restrict__ last_close, int64_t n_stocks, int32_t mode, double* __restrict__ w_out) {
+#pragma clang fp contract(off)
+  const int64_t total = U * (int64_t)W, stride = (int64_t)gridDim.x * HOLD_BLOCK;
+  for (int64_t i = (int64_t)blockIdx.x * HOLD_BLOCK + threadIdx.x; i < total; i += stride) {
+    const int64_t q = i / W;
+    const int32_t j = (int32_t)(i - q * W);
+    const int64_t u = users[q];
+    double w = 0.0;
+    if (u >= 0 && u < n_nodes && j < std::min(std::max(hold_len[u], 0), W)) {
+      w = hold_qty[u * W + j];
+      if (mode == 1) {
+        const int64_t s = hold_idx[u * W + j];
+        w = (s >= 0 && s < n_stocks) ? w * last_close[s] : 0.0;
+      }
+    }
+    w_out[i] = w;
+  }
+}
+}  // namespace
+
+extern "C" int pfo_holdings_gather_weights(const int32_t* users, int64_t U, const int32_t* hold_idx, const int32_t* hold_len,
+                                           const double* hold_qty, int64_t n_nodes, int32_t W, const double* last_close, int64_t n_stocks,
+                                           int32_t mode, double* w_out, void* stream) {
+  PFO_REQUIRE(W >= 1 && W <= 256, "W must lie in [1, 256]");
+  PFO_REQUIRE(U >= 0 && U <= INT64_MAX / 256, "U must not be negative");
+  PFO_REQUIRE(n_nodes >= 1 && n_nodes < ((int64_t)1 << 31), "n_nodes must lie in [1, 2^31)");
+  PFO_REQUIRE(n_stocks >= 0, "n_stocks must not be negative");
+  PFO_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (shares) or 1 (value)");
+  if (U == 0) return PFO_OK;
+  PFO_REQUIRE(users && hold_idx && hold_len && w_out, "null pointer");
+  PFO_REQUIRE(hold_qty, "null hold_qty: the weights are share counts (a ledger with quantities)");
+  PFO_REQUIRE(mode == 0 || last_close, "null last_close with mode 1 (value)");
+  hipLaunchKernelGGL(holdings_gather_weights_kernel, dim3(hold_grid(U * (int64_t)W)), dim3(HOLD_BLOCK), 0, (hipStream_t)stream, users, U, hold_idx,
+                     hold_len, hold_qty, n_nodes, W, last_close, n_stocks, mode, w_out);
+  PFO_LAUNCH_CHECK();
+  return PFO_OK;
+}

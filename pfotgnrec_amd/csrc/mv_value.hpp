@@ -68,6 +68,54 @@ __device__ __forceinline__ double pfo_mv_value(const double* __restrict__ day, i
   return pfo_mv_finish(mu, gamma, var, ssum, n_hold);
 }
 
+// ---- the position-weighted form: holding p weighs pw[p] in place of 1 / n_hold.
+// A weight counts iff it is finite and > 0 (a NaN compares false both times).
+__device__ __forceinline__ bool pfo_mv_weight_counts(double w) { return w > 0.0 && w <= 1.79769313486231570815e308; }
+
+// ssum + w * cov(ri, rp): the covariance as in pfo_mv_add_cov, then one rounded product, then one rounded add.  w == 1.0 is
+// pfo_mv_add_cov to the bit.
+__device__ __forceinline__ double pfo_mv_add_wcov(double ssum, double w, const double* ri, double mu, const double* rp, double mp,
+                                                  int n_ret, double inv) {
+#pragma clang fp contract(off)
+  double cv = 0.0;
+  for (int t = 0; t < n_ret; ++t) cv += (ri[t] - mu) * (rp[t] - mp);
+  const double wc = w * (cv * inv);
+  return ssum + wc;
+}
+
+// y_mv from the pieces; ssum_w: the weighted sum over the n_hold counted holdings, wsum: the sum of their weights (all ones:
+// wsum == n_hold exactly, and this is pfo_mv_finish to the bit)
+__device__ __forceinline__ double pfo_mv_finish_weighted(double mu, double gamma, double var, double ssum_w, double wsum, int n_hold) {
+#pragma clang fp contract(off)
+  if (n_hold == 0) return (mu / gamma) / var;                           // main.py:254
+  const double sum_sigma = (1.0 / wsum) * ssum_w;
+  return (mu / gamma - 0.5 * sum_sigma) / var;                          // main.py:271
+}
+
+// pfo_mv_value<true> with the weight row pw[0:plen] beside port[0:plen]: a holding counts iff its stock is in [0, n_stocks) and
+// its weight counts; wsum is the sequential sum of the counted weights in row order.
+__device__ __forceinline__ double pfo_mv_value_weighted(const double* __restrict__ day, int stock, int n_stocks, int n_ret,
+                                                        const int32_t* __restrict__ port, const double* __restrict__ pw, int plen,
+                                                        double gamma) {
+#pragma clang fp contract(off)
+  const double* ri = day + (int64_t)stock * n_ret;
+  const double mu = pfo_mv_mean(ri, n_ret);
+  const double inv = pfo_mv_inv(n_ret);
+  const double var = pfo_mv_var(ri, mu, n_ret, inv);
+  int n_hold = 0;
+  double ssum = 0.0, wsum = 0.0;
+  for (int p = 0; p < plen; ++p) {
+    const int s = port[p];
+    const double w = pw[p];
+    if ((unsigned)s >= (unsigned)n_stocks || !pfo_mv_weight_counts(w)) continue;
+    ++n_hold;
+    wsum += w;
+    const double* rp = day + (int64_t)s * n_ret;
+    ssum = pfo_mv_add_wcov(ssum, w, ri, mu, rp, pfo_mv_mean(rp, n_ret), n_ret, inv);
+  }
+  return pfo_mv_finish_weighted(mu, gamma, var, ssum, wsum, n_hold);
+}
+
 // scipy.stats.rankdata's average-tie rank of a value with `less` smaller and `eq` equal values (itself among them), main.py:282
 __device__ __forceinline__ double pfo_mv_avg_rank(int less, int eq) {
 #pragma clang fp contract(off)

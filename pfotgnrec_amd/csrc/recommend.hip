@@ -28,7 +28,9 @@
 // (two kernels over a workspace, ranks by sorting: its own comment), which shares the opening, stage A, RecMvUser, the rec_mv_*
 // pieces and the host checks with them.  Last, the list form (every user ranks a list of its own, one wavefront per user: its
 // own comment) takes the key, rec_better, RecMvUser, rec_mv_stock, the empty-slot tail, the host checks and the launcher from
-// here and nothing of stage A: a gathered row is no tile.
+// here and nothing of stage A: a gathered row is no tile.  The three kernels that compute y from a portfolio and serve a list -
+// the bounded mean-variance kernel, the wide score kernel, the list form - each have a WEIGHTED form (a weight per
+// holding, port_w, in place of 1 / n_holding): new __global__ shells over the shared bodies, a sibling for the wide score kernel.
 #include "common.hpp"
 #include "mv_value.hpp"
 #include <algorithm>
@@ -465,9 +467,14 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_topk_kernel(const R
 // before it plus h_u(g) stay below the cap.  The row of the user being ranked lies in LDS behind grp (hg[held_stride], at most
 // 1 KB: 156 928 bytes at I = 2048); a thread counts h for each candidate of its own and, where that alone reaches the cap - a
 // group closed from the start - skips the counting pass for it.
-template <int NJ, bool CAPPED, bool HELD = false>
-__device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES) {
+// WEIGHTED (pfo_recommend_mv_topk_weighted): y is pfo_mv_value_weighted over the user's row of port_w f64[U, port_stride]
+// beside port_idx - one more __restrict__ kernel parameter, for the reason given above the table macro.  Nothing else changes, and
+// the unweighted instantiations never see the parameter (their kernels do not have it).
+template <int NJ, bool CAPPED, bool HELD = false, bool WEIGHTED = false>
+__device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const RecMvArgs& m, PFO_REC_MV_TABLES,
+                                                       const double* __restrict__ port_w = nullptr) {
   static_assert(CAPPED || !HELD, "held rows count against a cap");
+  static_assert(!WEIGHTED || !CAPPED, "the capped forms take no weights");
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   int32_t* __restrict__ top_pos = a.top_pos;
   float *__restrict__ top_score = a.top_score, *__restrict__ score_out = m.score_out;
@@ -518,7 +525,12 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
       for (int c = tid; c < I; c += PFO_REC_THREADS) {
         if (score_out) score_out[u * I + c] = su[c];
         const int stock = rec_mv_stock(a, cand_stock, m.n_stocks, c, h.day_ok);
-        yv[c] = stock < 0 ? nan : pfo_mv_value<true>(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + u * m.port_stride, h.plen, m.gamma);
+        if constexpr (WEIGHTED)
+          yv[c] = stock < 0 ? nan
+                            : pfo_mv_value_weighted(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + u * m.port_stride,
+                                                    port_w + u * m.port_stride, h.plen, m.gamma);
+        else
+          yv[c] = stock < 0 ? nan : pfo_mv_value<true>(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + u * m.port_stride, h.plen, m.gamma);
       }
       rec_mv_exclude(yv, a, u);
       // ---- C: ranks over the admissible candidates, blended
@@ -631,6 +643,11 @@ __device__ __forceinline__ void recommend_mv_topk_body(const RecArgs& a, const R
 template <int NJ, bool CAPPED = false, bool HELD = false>
 __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES) {
   recommend_mv_topk_body<NJ, CAPPED, HELD>(a, m, cand_stock, returns, day_idx, port_idx, port_len);
+}
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_topk_weighted_kernel(const RecArgs a, const RecMvArgs m, PFO_REC_MV_TABLES,
+                                                                                     const double* __restrict__ port_w) {
+  recommend_mv_topk_body<NJ, false, false, true>(a, m, cand_stock, returns, day_idx, port_idx, port_len, port_w);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -939,6 +956,50 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_wide_score_kerne
     }
   }
 }
+// WEIGHTED (pfo_recommend_mv_topk_wide_weighted): the kernel above with pfo_mv_value_weighted over the user's row of port_w.  A
+// sibling, not an instantiation of one shared body: written as a body inlined into two kernels the unweighted instantiations spill
+// two more SGPRs, and they are to stay what they were.
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_mv_wide_score_weighted_kernel(const RecArgs a, const RecMvArgs m, const RecWideWs w,
+                                                                                           PFO_REC_MV_TABLES, const double* __restrict__ port_w) {
+  const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
+  float* __restrict__ score_out = m.score_out;
+  const int I = a.I, D = a.D;
+  constexpr int ICS = PFO_REC_CHUNK + 4;
+  __shared__ float sc[PFO_REC_TILE * ICS];                           // 33 KB
+  __shared__ int ub[PFO_REC_TILE];
+  const int tid = threadIdx.x;
+  const int64_t u0 = (int64_t)blockIdx.x * PFO_REC_TILE;
+  const int c0 = (int)blockIdx.y * PFO_REC_CHUNK, n = min(PFO_REC_CHUNK, I - c0);   // (the grid has ceil(I / chunk) chunks: n >= 1)
+  const double nan = __builtin_nan("");
+
+  float4 uf[NJ];
+  rec_user_fragments<NJ>(uf, user_emb, u0, a.U, D);
+  unsigned pending = rec_block_table(ub, a, u0);
+  while (pending) {
+    int b;
+    const unsigned members = rec_next_pass(pending, ub, b);
+    __syncthreads();                                                 // the previous pass's scores have been read
+    rec_score_chunk<NJ>(uf, item_emb + (int64_t)b * I * D, c0, n, I, D, sc, ICS);
+    __syncthreads();
+    for (int us = 0; us < PFO_REC_TILE; ++us) {
+      if (!((members >> us) & 1u)) continue;                         // (the same for every thread; a row beyond U is no member)
+      const int64_t u = u0 + us;
+      const float* su = sc + us * ICS;
+      const RecMvUser h(m, returns, day_idx, port_idx, port_len, u);
+      for (int c = tid; c < n; c += PFO_REC_THREADS) {
+        const int g = c0 + c;
+        const float s = su[c];
+        w.sc[u * w.IP + g] = s;
+        if (score_out) score_out[u * I + g] = s;
+        const int stock = rec_mv_stock(a, cand_stock, m.n_stocks, g, h.day_ok);
+        w.y[u * w.IP + g] = stock < 0 ? nan
+                                      : pfo_mv_value_weighted(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + u * m.port_stride,
+                                                              port_w + u * m.port_stride, h.plen, m.gamma);
+      }
+    }
+  }
+}
 
 // the first position of sorted key[0, n) that holds a key >= v (UPPER: > v)
 template <bool UPPER, class K>
@@ -1161,8 +1222,10 @@ struct RecListArgs {
   int list_stride;
 };
 
-template <int NJ, bool MV>
-__device__ __forceinline__ void recommend_list_body(const RecArgs& a, const RecMvArgs& m, const RecListArgs& l, PFO_REC_MV_TABLES) {
+template <int NJ, bool MV, bool WEIGHTED = false>
+__device__ __forceinline__ void recommend_list_body(const RecArgs& a, const RecMvArgs& m, const RecListArgs& l, PFO_REC_MV_TABLES,
+                                                    const double* __restrict__ port_w = nullptr) {
+  static_assert(MV || !WEIGHTED, "weights weigh on y alone");
   const float *__restrict__ user_emb = a.user_emb, *__restrict__ item_emb = a.item_emb;
   const int32_t* __restrict__ list_pos = l.list_pos;
   const uint8_t* __restrict__ item_ok = a.item_ok;
@@ -1228,7 +1291,13 @@ __device__ __forceinline__ void recommend_list_body(const RecArgs& a, const RecM
       yv[s4] = __builtin_nan("");
       if (mine[s4] < 0) continue;
       const int stock = rec_mv_stock(a, cand_stock, m.n_stocks, mine[s4], h.day_ok);
-      if (stock >= 0) yv[s4] = pfo_mv_value<true>(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + ur * m.port_stride, h.plen, m.gamma);
+      if constexpr (WEIGHTED) {
+        if (stock >= 0)
+          yv[s4] = pfo_mv_value_weighted(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + ur * m.port_stride, port_w + ur * m.port_stride,
+                                         h.plen, m.gamma);
+      } else {
+        if (stock >= 0) yv[s4] = pfo_mv_value<true>(h.dayp, stock, m.n_stocks, m.n_ret, port_idx + ur * m.port_stride, h.plen, m.gamma);
+      }
       if (!(yv[s4] == yv[s4])) mine[s4] = -1;
     }
   }
@@ -1367,6 +1436,11 @@ __global__ __launch_bounds__(PFO_REC_THREADS) void recommend_list_mv_topk_kernel
                                                                                  PFO_REC_MV_TABLES) {
   recommend_list_body<NJ, true>(a, m, l, cand_stock, returns, day_idx, port_idx, port_len);
 }
+template <int NJ>
+__global__ __launch_bounds__(PFO_REC_THREADS) void recommend_list_mv_topk_weighted_kernel(const RecArgs a, const RecMvArgs m, const RecListArgs l,
+                                                                                          PFO_REC_MV_TABLES, const double* __restrict__ port_w) {
+  recommend_list_body<NJ, true, true>(a, m, l, cand_stock, returns, day_idx, port_idx, port_len, port_w);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Host side.  The checks speak in the name of the entry that called them (`who`), as PFO_REQUIRE does with __func__.
@@ -1409,6 +1483,12 @@ int rec_check_mv(const char* who, const RecArgs& a, const RecMvArgs& m, PFO_REC_
   PFO_REC_REQUIRE(m.top_fused, "null input or output");
   PFO_REC_REQUIRE(cand_stock && returns && day_idx, "null mean-variance input");
   PFO_REC_REQUIRE(!port_idx || m.port_stride == 0 || port_len, "port_idx without port_len");
+  return PFO_OK;
+}
+
+// the weighted entries' row (U > 0), behind rec_check_mv: weights weigh on holdings
+int rec_check_weights(const char* who, const double* port_w, const int32_t* port_idx, int port_stride) {
+  PFO_REC_REQUIRE(!port_w || port_stride == 0 || port_idx, "port_w without port_idx");
   return PFO_OK;
 }
 
@@ -1688,19 +1768,24 @@ extern "C" int64_t pfo_recommend_mv_wide_workspace_bytes(int64_t U, int32_t I) {
   return rec_wide_bytes(U > 0 ? pfo_ceil_div(U, PFO_REC_TILE) : 1, I > 0 ? I : 1);
 }
 
-extern "C" int pfo_recommend_mv_topk_wide(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
-                                          int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
-                                          const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
-                                          int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
-                                          const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
-                                          int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
-                                          double* y_out, double* fused_out, void* workspace, int64_t workspace_bytes, void* stream) {
+// The wide form behind both of its entries (`who`): port_w NULL is the unweighted score kernel, else the weighted one; the rank
+// kernel never sees the portfolio.
+static int rec_mv_topk_wide(const char* who, const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                            int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                            const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days, int32_t n_stocks,
+                            int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx, const int32_t* port_len, const double* port_w,
+                            int32_t port_stride, double gamma, double lambda_mv, int32_t k, int32_t* top_pos, float* top_score,
+                            double* top_fused, int32_t* n_valid, float* score_out, double* y_out, double* fused_out, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
   const RecArgs a = PFO_REC_ARGS(PFO_REC_CHUNK);
   const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
-  int rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len, PFO_RECOMMEND_MV_WIDE_MAX_ITEMS,
+  int rc = rec_check_mv(who, a, m, cand_stock, returns, day_idx, port_idx, port_len, PFO_RECOMMEND_MV_WIDE_MAX_ITEMS,
                         "I must be in [1, PFO_RECOMMEND_MV_WIDE_MAX_ITEMS]");
   if (rc != PFO_OK || U == 0) return rc;
-  rc = rec_check_wide(__func__, a, workspace, workspace_bytes);
+  rc = rec_check_weights(who, port_w, port_idx, port_stride);
+  if (rc != PFO_OK) return rc;
+  if (!port_idx || port_stride == 0) port_w = nullptr;                 // (no holding is read: the unweighted kernel serves)
+  rc = rec_check_wide(who, a, workspace, workspace_bytes);
   if (rc != PFO_OK) return rc;
   // slabs of as many whole tiles as the workspace holds, in stream order (which is what makes its reuse safe)
   const int64_t tiles = pfo_ceil_div(U, PFO_REC_TILE), slab_tiles = std::min(workspace_bytes / rec_wide_bytes(1, I), tiles);
@@ -1731,17 +1816,78 @@ extern "C" int pfo_recommend_mv_topk_wide(const float* user_emb, const float* it
     if (ms.fused_out) ms.fused_out += s * I;
     const int32_t* port_s = port_idx ? port_idx + s * port_stride : nullptr;
     const int32_t* plen_s = port_len ? port_len + s : nullptr;
-    rc = rec_launch_grid(__func__, PFO_REC_KERNEL(recommend_mv_wide_score_kernel), 0, (unsigned)pfo_ceil_div(I, PFO_REC_CHUNK), stream, as,
-                         ms, w, cand_stock, returns, day_idx + s, port_s, plen_s);
+    if (port_w) {
+      const double* pw_s = port_w + s * port_stride;
+      rc = rec_launch_grid(who, PFO_REC_KERNEL(recommend_mv_wide_score_weighted_kernel), 0, (unsigned)pfo_ceil_div(I, PFO_REC_CHUNK), stream,
+                           as, ms, w, cand_stock, returns, day_idx + s, port_s, plen_s, pw_s);
+    } else {
+      rc = rec_launch_grid(who, PFO_REC_KERNEL(recommend_mv_wide_score_kernel), 0, (unsigned)pfo_ceil_div(I, PFO_REC_CHUNK), stream, as, ms,
+                           w, cand_stock, returns, day_idx + s, port_s, plen_s);
+    }
     if (rc != PFO_OK) return rc;
     PFO_KLAUNCH(recommend_mv_wide_rank_kernel, dim3((unsigned)Us), dim3(PFO_REC_THREADS), 0, (hipStream_t)stream, as, ms, w);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-      pfo_set_error("%s: launch failed: %s", __func__, hipGetErrorString(e));
+      pfo_set_error("%s: launch failed: %s", who, hipGetErrorString(e));
       return PFO_ERR_HIP;
     }
   }
   return PFO_OK;
+}
+
+extern "C" int pfo_recommend_mv_topk_wide(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                          int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                          const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                          int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                          const int32_t* port_len, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                          int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                          double* y_out, double* fused_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  return rec_mv_topk_wide(__func__, user_emb, item_emb, user_block, U, I, n_t, D, excl_pos, excl_len, excl_stride, item_ok, cand_stock, returns,
+                          n_days, n_stocks, n_ret, day_idx, port_idx, port_len, nullptr, port_stride, gamma, lambda_mv, k, top_pos, top_score,
+                          top_fused, n_valid, score_out, y_out, fused_out, workspace, workspace_bytes, stream);
+}
+
+// The weighted entries: the sibling's argument blocks and checks, port_w behind port_len, the WEIGHTED kernel.  A null
+// port_w is the sibling itself.
+extern "C" int pfo_recommend_mv_topk_wide_weighted(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U,
+                                                   int32_t I, int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len,
+                                                   int32_t excl_stride, const uint8_t* item_ok, const int32_t* cand_stock,
+                                                   const double* returns, int32_t n_days, int32_t n_stocks, int32_t n_ret,
+                                                   const int32_t* day_idx, const int32_t* port_idx, const int32_t* port_len,
+                                                   const double* port_w, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                                   int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                                   double* y_out, double* fused_out, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!port_w)
+    return pfo_recommend_mv_topk_wide(user_emb, item_emb, user_block, U, I, n_t, D, excl_pos, excl_len, excl_stride, item_ok, cand_stock, returns,
+                                      n_days, n_stocks, n_ret, day_idx, port_idx, port_len, port_stride, gamma, lambda_mv, k, top_pos, top_score,
+                                      top_fused, n_valid, score_out, y_out, fused_out, workspace, workspace_bytes, stream);
+  return rec_mv_topk_wide(__func__, user_emb, item_emb, user_block, U, I, n_t, D, excl_pos, excl_len, excl_stride, item_ok, cand_stock, returns,
+                          n_days, n_stocks, n_ret, day_idx, port_idx, port_len, port_w, port_stride, gamma, lambda_mv, k, top_pos, top_score,
+                          top_fused, n_valid, score_out, y_out, fused_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pfo_recommend_mv_topk_weighted(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U, int32_t I,
+                                              int32_t n_t, int32_t D, const int32_t* excl_pos, const int32_t* excl_len, int32_t excl_stride,
+                                              const uint8_t* item_ok, const int32_t* cand_stock, const double* returns, int32_t n_days,
+                                              int32_t n_stocks, int32_t n_ret, const int32_t* day_idx, const int32_t* port_idx,
+                                              const int32_t* port_len, const double* port_w, int32_t port_stride, double gamma,
+                                              double lambda_mv, int32_t k, int32_t* top_pos, float* top_score, double* top_fused,
+                                              int32_t* n_valid, float* score_out, double* y_out, double* fused_out, void* stream) {
+  if (!port_w)
+    return pfo_recommend_mv_topk(user_emb, item_emb, user_block, U, I, n_t, D, excl_pos, excl_len, excl_stride, item_ok, cand_stock, returns, n_days,
+                                 n_stocks, n_ret, day_idx, port_idx, port_len, port_stride, gamma, lambda_mv, k, top_pos, top_score, top_fused,
+                                 n_valid, score_out, y_out, fused_out, stream);
+  const RecArgs a = PFO_REC_ARGS(rec_mv_ic(I));
+  const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
+  int rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len);
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_weights(__func__, port_w, port_idx, port_stride);
+  if (rc != PFO_OK) return rc;
+  if (!port_idx || port_stride == 0)                                   // (no holding is read: the unweighted kernel serves)
+    return rec_launch(__func__, PFO_REC_KERNEL(recommend_mv_topk_kernel), rec_mv_bytes(a.IC), stream, a, m, cand_stock, returns, day_idx,
+                      port_idx, port_len);
+  return rec_launch(__func__, PFO_REC_KERNEL(recommend_mv_topk_weighted_kernel), rec_mv_bytes(a.IC), stream, a, m, cand_stock, returns, day_idx,
+                    port_idx, port_len, port_w);
 }
 
 // The list form has no exclusion side: its RecArgs carry none.  Four users a workgroup, so four workgroups (grid y) to the
@@ -1790,4 +1936,34 @@ extern "C" int pfo_recommend_list_mv_topk(const float* user_emb, const float* it
   if (rc != PFO_OK) return rc;
   return rec_launch_grid(__func__, PFO_REC_KERNEL(recommend_list_mv_topk_kernel), 0, PFO_REC_TILE / PFO_RL_USERS, stream, a, m, l, cand_stock,
                          returns, day_idx, port_idx, port_len);
+}
+
+extern "C" int pfo_recommend_list_mv_topk_weighted(const float* user_emb, const float* item_emb, const int32_t* user_block, int64_t U,
+                                                   int32_t I, int32_t n_t, int32_t D, const int32_t* list_pos, const int32_t* list_len,
+                                                   int32_t list_stride, const uint8_t* item_ok, const int32_t* cand_stock,
+                                                   const double* returns, int32_t n_days, int32_t n_stocks, int32_t n_ret,
+                                                   const int32_t* day_idx, const int32_t* port_idx, const int32_t* port_len,
+                                                   const double* port_w, int32_t port_stride, double gamma, double lambda_mv, int32_t k,
+                                                   int32_t* top_pos, float* top_score, double* top_fused, int32_t* n_valid, float* score_out,
+                                                   double* y_out, double* fused_out, void* stream) {
+  if (!port_w)
+    return pfo_recommend_list_mv_topk(user_emb, item_emb, user_block, U, I, n_t, D, list_pos, list_len, list_stride, item_ok, cand_stock, returns,
+                                      n_days, n_stocks, n_ret, day_idx, port_idx, port_len, port_stride, gamma, lambda_mv, k, top_pos, top_score,
+                                      top_fused, n_valid, score_out, y_out, fused_out, stream);
+  PFO_REC_LIST_ARGS();
+  const RecMvArgs m = PFO_REC_MV_ARGS(score_out, y_out, fused_out);
+  int rc = rec_check_list_stride(__func__, list_stride);
+  if (rc == PFO_OK) rc = rec_check_mv_bounds(__func__, m);
+  if (rc == PFO_OK)
+    rc = rec_check_mv(__func__, a, m, cand_stock, returns, day_idx, port_idx, port_len, PFO_RECOMMEND_MAX_ITEMS,
+                      "I must be in [1, PFO_RECOMMEND_MAX_ITEMS]");
+  if (rc != PFO_OK || U == 0) return rc;
+  rc = rec_check_weights(__func__, port_w, port_idx, port_stride);
+  if (rc == PFO_OK) rc = rec_check_list_rows(__func__, list_pos, list_len);
+  if (rc != PFO_OK) return rc;
+  if (!port_idx || port_stride == 0)                                   // (no holding is read: the unweighted kernel serves)
+    return rec_launch_grid(__func__, PFO_REC_KERNEL(recommend_list_mv_topk_kernel), 0, PFO_REC_TILE / PFO_RL_USERS, stream, a, m, l, cand_stock,
+                           returns, day_idx, port_idx, port_len);
+  return rec_launch_grid(__func__, PFO_REC_KERNEL(recommend_list_mv_topk_weighted_kernel), 0, PFO_REC_TILE / PFO_RL_USERS, stream, a, m, l,
+                         cand_stock, returns, day_idx, port_idx, port_len, port_w);
 }

@@ -583,9 +583,10 @@ _NO_WORKSPACE = object()     # ``_recommend_mv_launch``: the symbol takes no wor
 _WIDE_WORKSPACE_CAP = 256 << 20
 
 
-def _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, then=None):
+def _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, then=None, port_w=None):
     """``dims`` of ``_recommend_check`` for the mean-variance forms: the checks of their own tensors, (I, n_t) from ``cand_stock``
-    and ``n_blocks``.  ``max_items``: the form's bound on I; ``then(U, I)``: the caller's checks that need I, run behind it."""
+    and ``n_blocks``.  ``max_items``: the form's bound on I; ``then(U, I)``: the caller's checks that need I, run behind it.
+    ``port_w``: the weight rows of the weighted forms, f64 in the shape of ``port_idx``."""
     def dims(U, rows):
         if not isinstance(cand_stock, torch.Tensor) or cand_stock.dim() != 1 or cand_stock.dtype != torch.int32 or cand_stock.shape[0] < 1:
             raise ValueError("cand_stock must be int32 [I]")
@@ -610,19 +611,30 @@ def _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_ite
                 raise ValueError("port_len must be int32 [U]")
         elif port_len is not None:
             raise ValueError("port_len without port_idx")
+        if port_w is not None:
+            if port_idx is None:
+                raise ValueError("port_w without port_idx: a weight weighs on a holding")
+            if not isinstance(port_w, torch.Tensor) or port_w.dtype != torch.float64 or tuple(port_w.shape) != tuple(port_idx.shape):
+                raise ValueError("port_w must be float64 [U, W], the shape of port_idx %s" % (tuple(port_idx.shape),))
         return I, n_t
     return dims
 
 
+def _no_weights_with_cap(port_w, cand_group, group_cap):
+    if port_w is not None and (cand_group is not None or group_cap is not None):
+        raise ValueError("port_w and cand_group / group_cap cannot be combined: the capped orders have no weighted form")
+
+
 def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
                          user_block, excl_pos, excl_len, item_ok, n_blocks, max_items=_lib.RECOMMEND_MV_MAX_ITEMS, workspace=_NO_WORKSPACE,
-                         cap=None):
+                         cap=None, port_w=None):
     """The argument checks, output rows and launch that ``recommend_mv_topk``, ``recommend_mv_topk_wide`` and
     ``recommend_basket_topk`` share: ``symbol`` takes pfo_recommend_mv_topk's arguments, with the three diagnostic arrays
     (``diagnostics``: allocate them or pass NULL) or without them (None).  ``max_items``: the symbol's bound on I.
     ``workspace``: for a symbol that takes (workspace, workspace_bytes) before the stream - a uint8 tensor, or None: allocated
     (what serves all users at once, 256 MiB at the most, the minimum at the least).  ``cap``: what ``_recommend_cap`` returns -
-    with one, ``symbol`` + "_capped" (with held rows: + "_capped_held") is called, its arguments behind item_ok (``_cap_call``)."""
+    with one, ``symbol`` + "_capped" (with held rows: + "_capped_held") is called, its arguments behind item_ok (``_cap_call``).
+    ``port_w``: f64 [U, W] beside ``port_idx`` - ``symbol`` + "_weighted" is called, the rows behind port_len (never with ``cap``)."""
     def check_workspace(U, I):
         if workspace is not _NO_WORKSPACE and workspace is not None:
             if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
@@ -632,14 +644,18 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
             need = _lib.byte_count("pfo_recommend_mv_wide_workspace_bytes", min(U, 16), I)
             if U and workspace.numel() < need:
                 raise ValueError("workspace holds %d bytes, %d users of %d candidates need at least %d" % (workspace.numel(), U, I, need))
-    dims = _capped_dims(_mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, check_workspace), cap)
+    dims = _capped_dims(_mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, max_items, check_workspace, port_w), cap)
 
     user_emb, item_emb, user_block, excl_pos, excl_len, item_ok, U, D, k, I, n_t, W = _recommend_check(
         user_emb, item_emb, k, user_block, excl_pos, excl_len, item_ok, dims,
-        (cand_stock, returns, day_idx, port_idx, port_len) + (cap[:1] + cap[2:] if cap else ()))
+        (cand_stock, returns, day_idx, port_idx, port_len, port_w) + (cap[:1] + cap[2:] if cap else ()))
     dev = user_emb.device
     n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
     Wp = int(port_idx.shape[1]) if port_idx is not None else 0
+    w_args = ()
+    if port_w is not None:
+        port_w = port_w.contiguous() if Wp else None
+        symbol, w_args = symbol + "_weighted", (_lib.ptr(port_w),)
     if Wp and port_len is None:
         port_len = torch.full((U,), Wp, dtype=torch.int32, device=dev)
     top_pos = torch.empty((U, k), dtype=torch.int32, device=dev)
@@ -664,13 +680,14 @@ def _recommend_mv_launch(symbol, diagnostics, user_emb, item_emb, k, cand_stock,
     _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(excl_pos), _lib.ptr(excl_len),
               W, _lib.ptr(item_ok), *cap_args, _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks, n_ret,
               _lib.ptr(day_idx.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None), _lib.ptr(port_len.contiguous() if Wp else None),
-              Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), *ws, _lib.stream_ptr())
+              *w_args, Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out), *(_lib.ptr(t) for t in extra), *ws,
+              _lib.stream_ptr())
     return out + extra if diagnostics else out
 
 
 def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
-                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False, cand_group=None, group_cap=None,
-                      held_group=None, held_len=None):
+                      excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, want_all=False, port_w=None, cand_group=None,
+                      group_cap=None, held_group=None, held_len=None):
     """``recommend_topk`` with the mean-variance rank fusion of main.py:243-289 over every user's whole candidate list, in one
     launch (``pfo_recommend_mv_topk``).
 
@@ -688,14 +705,20 @@ def recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_
     ``cand_group`` i32[I] with ``group_cap`` >= 1 (both or neither; ``pfo_recommend_mv_topk_capped``): the walk over that order
     skips a candidate whose group (negative: none) holds ``group_cap`` picks already.  Ranks, fused and the ``want_all`` arrays
     are the uncapped ones - a cap changes no rank.  ``held_group`` / ``held_len`` beside them (``recommend_topk`` describes the
-    rows; ``pfo_recommend_mv_topk_capped_held``): the count of a group starts from what the user holds of it."""
+    rows; ``pfo_recommend_mv_topk_capped_held``): the count of a group starts from what the user holds of it.
+
+    ``port_w`` f64[U,W] on the device, the shape of ``port_idx`` (``pfo_recommend_mv_topk_weighted``): holding p weighs
+    ``port_w[u, p]`` on y in place of 1 / n_holding - ``(1 / sum w) * sum(w * cov)`` over the holdings whose stock is in the
+    table and whose weight is finite and > 0; the others are left out.  All-ones rows give the unweighted result bit for bit.
+    None takes the unweighted path; with ``cand_group`` a ValueError (the capped orders have no weighted form)."""
+    _no_weights_with_cap(port_w, cand_group, group_cap)
     return _recommend_mv_launch("pfo_recommend_mv_topk", bool(want_all), user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx,
                                 port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks,
-                                cap=_recommend_cap(cand_group, group_cap, held_group, held_len))
+                                cap=_recommend_cap(cand_group, group_cap, held_group, held_len), port_w=port_w)
 
 
 def recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
-                           excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, workspace=None, want_all=False):
+                           excl_pos=None, excl_len=None, item_ok=None, n_blocks=None, workspace=None, want_all=False, port_w=None):
     """``recommend_mv_topk`` for candidate lists beyond its 2048 (``pfo_recommend_mv_topk_wide``, up to 65536): the same
     arguments, checks and return tuple, the same results to the bit where both apply.  The state of a user lives in
     ``workspace`` and the ranks are found by sorting, O(I log I) per user.
@@ -703,10 +726,12 @@ def recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, 
     ``workspace``: a contiguous uint8 tensor on the embeddings' device of at least
     ``pfo_recommend_mv_wide_workspace_bytes(min(U, 16), I)`` bytes (36 bytes per user and candidate, users in tiles of 16,
     candidates rounded up to 16); the users are served in slabs of as many tiles as it holds, and the result does not depend on
-    its size.  None: allocated - what serves all users at once, 256 MiB at the most."""
+    its size.  None: allocated - what serves all users at once, 256 MiB at the most.
+
+    ``port_w`` f64[U,W]: the weight rows of ``recommend_mv_topk`` (``pfo_recommend_mv_topk_wide_weighted``)."""
     return _recommend_mv_launch("pfo_recommend_mv_topk_wide", bool(want_all), user_emb, item_emb, k, cand_stock, returns, day_idx,
                                 port_idx, port_len, gamma, lambda_mv, user_block, excl_pos, excl_len, item_ok, n_blocks,
-                                _lib.RECOMMEND_MV_WIDE_MAX_ITEMS, workspace)
+                                _lib.RECOMMEND_MV_WIDE_MAX_ITEMS, workspace, port_w=port_w)
 
 
 def recommend_basket_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv, user_block=None,
@@ -771,7 +796,7 @@ def recommend_list_topk(user_emb, item_emb, k, list_pos, list_len, user_block=No
 
 
 def recommend_list_mv_topk(user_emb, item_emb, k, list_pos, list_len, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
-                           user_block=None, item_ok=None, n_blocks=None, want_all=False):
+                           user_block=None, item_ok=None, n_blocks=None, want_all=False, port_w=None):
     """``recommend_list_topk`` in the mean-variance order (``pfo_recommend_list_mv_topk``): the rank fusion of
     ``recommend_mv_topk`` - its arguments, its y, its average-tie ranks, its blend - over every user's own list.  A listed
     candidate must also have a y (day and ``cand_stock`` inside the tables, y not NaN).  No bound of 2048 on I and no workspace:
@@ -780,10 +805,13 @@ def recommend_list_mv_topk(user_emb, item_emb, k, list_pos, list_len, cand_stock
     bit for bit where every listed candidate has a y.
 
     Returns (top_pos i32[U,k], top_score f32[U,k], top_fused f64[U,k], n_valid i32[U]); ``want_all`` adds (score f32[U,W],
-    y f64[U,W], fused f64[U,W]) BY LIST SLOT, NaN in every slot that is not the first occurrence of an admissible position."""
-    dims = _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, _lib.RECOMMEND_MAX_ITEMS)
+    y f64[U,W], fused f64[U,W]) BY LIST SLOT, NaN in every slot that is not the first occurrence of an admissible position.
+
+    ``port_w`` f64[U,Wp], the shape of ``port_idx``: the weight rows of ``recommend_mv_topk``
+    (``pfo_recommend_list_mv_topk_weighted``)."""
+    dims = _mv_dims(cand_stock, returns, day_idx, port_idx, port_len, n_blocks, _lib.RECOMMEND_MAX_ITEMS, port_w=port_w)
     user_emb, item_emb, user_block, list_pos, list_len, item_ok, U, D, k, I, n_t, W = _recommend_list_check(
-        user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, dims, (cand_stock, returns, day_idx, port_idx, port_len))
+        user_emb, item_emb, k, list_pos, list_len, user_block, item_ok, dims, (cand_stock, returns, day_idx, port_idx, port_len, port_w))
     dev = user_emb.device
     n_days, n_stocks, n_ret = (int(v) for v in returns.shape)
     Wp = int(port_idx.shape[1]) if port_idx is not None else 0
@@ -792,10 +820,14 @@ def recommend_list_mv_topk(user_emb, item_emb, k, list_pos, list_len, cand_stock
     out = (torch.empty((U, k), dtype=torch.int32, device=dev), torch.empty((U, k), dtype=torch.float32, device=dev),
            torch.empty((U, k), dtype=torch.float64, device=dev), torch.empty(U, dtype=torch.int32, device=dev))
     extra = tuple(torch.empty((U, W), dtype=dt, device=dev) if want_all else None for dt in (torch.float32, torch.float64, torch.float64))
-    _lib.call("pfo_recommend_list_mv_topk", user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(list_pos),
+    symbol, w_args = "pfo_recommend_list_mv_topk", ()
+    if port_w is not None:
+        port_w = port_w.contiguous() if Wp else None
+        symbol, w_args = symbol + "_weighted", (_lib.ptr(port_w),)
+    _lib.call(symbol, user_emb.data_ptr(), item_emb.data_ptr(), _lib.ptr(user_block), U, I, n_t, D, _lib.ptr(list_pos),
               _lib.ptr(list_len), W, _lib.ptr(item_ok), _lib.ptr(cand_stock.contiguous()), returns.contiguous().data_ptr(), n_days, n_stocks,
               n_ret, _lib.ptr(day_idx.contiguous()), _lib.ptr(port_idx.contiguous() if Wp else None),
-              _lib.ptr(port_len.contiguous() if Wp else None), Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out),
+              _lib.ptr(port_len.contiguous() if Wp else None), *w_args, Wp, float(gamma), float(lambda_mv), k, *(t.data_ptr() for t in out),
               *(_lib.ptr(t) for t in extra), _lib.stream_ptr())
     return out + extra if want_all else out
 
@@ -902,6 +934,43 @@ def holdings_gather(users, hold_idx, hold_len, upper_u, items=None, pos_scratch=
               _lib.ptr(pos_scratch if items is not None else None), port_idx.data_ptr(), port_len.data_ptr(), _lib.ptr(excl_pos),
               _lib.stream_ptr())
     return port_idx, port_len, excl_pos
+
+
+WEIGHT_MODES = {"shares": 0, "value": 1}
+
+
+def holdings_gather_weights(users, hold_idx, hold_len, hold_qty, mode, last_close=None):
+    """The weight rows of ``users`` i32[U] beside ``holdings_gather``'s port_idx (``pfo_holdings_gather_weights``): f64[U, W],
+    0.0 at and behind the row's length and for users outside [0, n_nodes).  ``mode`` "shares" (or 0): the share counts
+    ``hold_qty[u, j]``; "value" (or 1): share count x ``last_close[stock]`` f64[n_stocks] (one rounded product), 0.0 for a stock
+    outside the table, NaN for a stock never quoted - ``recommend_mv_topk`` leaves both out.  One launch, every slot written."""
+    mode = WEIGHT_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if mode not in (0, 1) or isinstance(mode, bool):
+        raise ValueError('mode must be "shares" (0) or "value" (1)')
+    if hold_idx.dim() != 2 or hold_idx.dtype != torch.int32 or hold_len.dtype != torch.int32 or tuple(hold_len.shape) != (hold_idx.shape[0],):
+        raise ValueError("the ledger must be (i32 [n_nodes, W], i32 [n_nodes])")
+    if not isinstance(hold_qty, torch.Tensor) or hold_qty.dtype != torch.float64 or tuple(hold_qty.shape) != tuple(hold_idx.shape):
+        raise ValueError("the ledger's quantities must be f64 [n_nodes, W]: the weights are share counts")
+    if not (hold_idx.is_contiguous() and hold_len.is_contiguous() and hold_qty.is_contiguous()):
+        raise ValueError("the ledger tables must be contiguous")
+    if users.dim() != 1 or users.dtype != torch.int32:
+        raise ValueError("users must be int32 [U]")
+    n_stocks = 0
+    if mode == 1:
+        if not isinstance(last_close, torch.Tensor) or last_close.dim() != 1 or last_close.dtype != torch.float64:
+            raise ValueError('mode "value" needs last_close f64 [n_stocks]')
+        n_stocks = int(last_close.shape[0])
+    n_nodes, W = (int(v) for v in hold_idx.shape)
+    U = int(users.shape[0])
+    dev = hold_idx.device
+    _lib.require_gpu(dev)
+    for t in (users, hold_len, hold_qty, last_close if mode == 1 else None):
+        if t is not None and t.device != dev:
+            raise ValueError("all tensors must live on %s" % dev)
+    w_out = torch.empty((U, W), dtype=torch.float64, device=dev)
+    _lib.call("pfo_holdings_gather_weights", _lib.ptr(users.contiguous()), U, hold_idx.data_ptr(), hold_len.data_ptr(), hold_qty.data_ptr(),
+              n_nodes, W, _lib.ptr(last_close.contiguous() if mode == 1 else None), n_stocks, mode, w_out.data_ptr(), _lib.stream_ptr())
+    return w_out
 
 
 HISTORY_OUTPUTS = ("node", "len", "time", "count", "pos", "stock")

@@ -84,6 +84,14 @@ class Holdings:
         from .functional import holdings_gather
         return holdings_gather(users, self.idx, self.len, self.upper_u, items, self._pos)
 
+    def gather_weights(self, users, mode, last_close=None):
+        """The weight rows f64[U, width] of device ``users`` beside ``gather``'s port_idx (``pfo_holdings_gather_weights``):
+        ``mode`` "shares" - the share counts - or "value" - share count x ``last_close[stock]`` (f64 [n_stocks] on the device)."""
+        from .functional import holdings_gather_weights
+        if not self.quantities:
+            raise ValueError("weights need a ledger that keeps quantities: track_holdings(width, upper_u, quantities=True)")
+        return holdings_gather_weights(users, self.idx, self.len, self.qty, mode, last_close)
+
     def rows(self, users):
         """``(port_idx i32[U, width], port_len i32[U])`` on the device: the rows of ``users`` (node ids: a host array or an
         integer device tensor); ids outside the table give (-1.., 0)."""

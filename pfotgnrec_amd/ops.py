@@ -17,6 +17,7 @@ inference and - for the BPR loss - an autograd formula:
     torch.ops.pfotgn.recommend_list_mv_topk(...)                               the same in the mean-variance order
     torch.ops.pfotgn.history_gather(indptr, adj_nbr, adj_ts, users, ts, width, ...)  what each user interacted with before its time
     torch.ops.pfotgn.holdings_apply(src, stock, side, ts, hold_idx, hold_len, hold_time, ...)  buys and sells applied to ledger rows, in place
+    torch.ops.pfotgn.holdings_gather_weights(users, hold_idx, hold_len, hold_qty, mode, ...)   the weight rows of the weighted mean-variance order
 
 Only a HIP implementation is registered ("cuda" dispatch key = ROCm here): on any other device the dispatcher raises,
 there is no CPU fallback.  The TGN step itself keeps its ``autograd.Function`` (``tgn._EmbedFn``): it owns state (memory,
@@ -143,15 +144,15 @@ def recommend_mv_topk(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int, ca
                       day_idx: torch.Tensor, gamma: float, lambda_mv: float, n_blocks: int = 1,
                       port_idx: Optional[torch.Tensor] = None, port_len: Optional[torch.Tensor] = None,
                       user_block: Optional[torch.Tensor] = None, excl_pos: Optional[torch.Tensor] = None,
-                      excl_len: Optional[torch.Tensor] = None,
-                      item_ok: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                      excl_len: Optional[torch.Tensor] = None, item_ok: Optional[torch.Tensor] = None,
+                      port_w: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     return functional.recommend_mv_topk(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
-                                        user_block, excl_pos, excl_len, item_ok, n_blocks=n_blocks)
+                                        user_block, excl_pos, excl_len, item_ok, n_blocks=n_blocks, port_w=port_w)
 
 
 @recommend_mv_topk.register_fake
 def _(user_emb, item_emb, k, cand_stock, returns, day_idx, gamma, lambda_mv, n_blocks=1, port_idx=None, port_len=None,
-      user_block=None, excl_pos=None, excl_len=None, item_ok=None):
+      user_block=None, excl_pos=None, excl_len=None, item_ok=None, port_w=None):
     U = user_emb.shape[0]
     return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
             user_emb.new_empty((U, k), dtype=torch.float64), user_emb.new_empty((U,), dtype=torch.int32))
@@ -162,15 +163,15 @@ def recommend_mv_topk_wide(user_emb: torch.Tensor, item_emb: torch.Tensor, k: in
                            day_idx: torch.Tensor, gamma: float, lambda_mv: float, n_blocks: int = 1,
                            port_idx: Optional[torch.Tensor] = None, port_len: Optional[torch.Tensor] = None,
                            user_block: Optional[torch.Tensor] = None, excl_pos: Optional[torch.Tensor] = None,
-                           excl_len: Optional[torch.Tensor] = None,
-                           item_ok: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                           excl_len: Optional[torch.Tensor] = None, item_ok: Optional[torch.Tensor] = None,
+                           port_w: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     return functional.recommend_mv_topk_wide(user_emb, item_emb, k, cand_stock, returns, day_idx, port_idx, port_len, gamma, lambda_mv,
-                                             user_block, excl_pos, excl_len, item_ok, n_blocks=n_blocks)   # (its own workspace)
+                                             user_block, excl_pos, excl_len, item_ok, n_blocks=n_blocks, port_w=port_w)   # (its own workspace)
 
 
 @recommend_mv_topk_wide.register_fake
 def _(user_emb, item_emb, k, cand_stock, returns, day_idx, gamma, lambda_mv, n_blocks=1, port_idx=None, port_len=None,
-      user_block=None, excl_pos=None, excl_len=None, item_ok=None):
+      user_block=None, excl_pos=None, excl_len=None, item_ok=None, port_w=None):
     U = user_emb.shape[0]
     return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
             user_emb.new_empty((U, k), dtype=torch.float64), user_emb.new_empty((U,), dtype=torch.int32))
@@ -195,14 +196,15 @@ def recommend_list_mv_topk(user_emb: torch.Tensor, item_emb: torch.Tensor, k: in
                            returns: torch.Tensor, day_idx: torch.Tensor, gamma: float, lambda_mv: float,
                            list_len: Optional[torch.Tensor] = None, n_blocks: int = 1, port_idx: Optional[torch.Tensor] = None,
                            port_len: Optional[torch.Tensor] = None, user_block: Optional[torch.Tensor] = None,
-                           item_ok: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                           item_ok: Optional[torch.Tensor] = None,
+                           port_w: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     return functional.recommend_list_mv_topk(user_emb, item_emb, k, list_pos, list_len, cand_stock, returns, day_idx, port_idx, port_len,
-                                             gamma, lambda_mv, user_block, item_ok, n_blocks=n_blocks)
+                                             gamma, lambda_mv, user_block, item_ok, n_blocks=n_blocks, port_w=port_w)
 
 
 @recommend_list_mv_topk.register_fake
 def _(user_emb, item_emb, k, list_pos, cand_stock, returns, day_idx, gamma, lambda_mv, list_len=None, n_blocks=1, port_idx=None,
-      port_len=None, user_block=None, item_ok=None):
+      port_len=None, user_block=None, item_ok=None, port_w=None):
     U = user_emb.shape[0]
     return (user_emb.new_empty((U, k), dtype=torch.int32), user_emb.new_empty((U, k), dtype=torch.float32),
             user_emb.new_empty((U, k), dtype=torch.float64), user_emb.new_empty((U,), dtype=torch.int32))
@@ -243,3 +245,15 @@ def holdings_apply(src: torch.Tensor, stock: torch.Tensor, side: torch.Tensor, t
 @holdings_apply.register_fake
 def _(src, stock, side, ts, hold_idx, hold_len, hold_time, hold_qty, counters, qty=None):
     return None
+
+
+@torch.library.custom_op(_LIB_NS + "::holdings_gather_weights", mutates_args=(), device_types="cuda")
+def holdings_gather_weights(users: torch.Tensor, hold_idx: torch.Tensor, hold_len: torch.Tensor, hold_qty: torch.Tensor, mode: int,
+                            last_close: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``functional.holdings_gather_weights``: mode 0 = shares, 1 = value (needs ``last_close``)."""
+    return functional.holdings_gather_weights(users, hold_idx, hold_len, hold_qty, mode, last_close)
+
+
+@holdings_gather_weights.register_fake
+def _(users, hold_idx, hold_len, hold_qty, mode, last_close=None):
+    return users.new_empty((users.shape[0], hold_idx.shape[1]), dtype=torch.float64)

@@ -5,7 +5,9 @@ rank twice, blend and select; with ``basket`` on top
 of that, ``pfo_recommend_basket_topk`` re-rank after every pick.  With ``only=`` every user ranks a list of its own:
 ``pfo_recommend_list_topk`` / ``pfo_recommend_list_mv_topk``.  With ``groups=`` / ``group_cap=`` (``validate_groups``) the three
 shared-list launches take their capped entries: at most ``group_cap`` picks of a group in a user's list; with ``held_groups=``
-(``validate_held_groups``) their ``_held`` entries: the count of a group starts from what the user holds of it."""
+(``validate_held_groups``) their ``_held`` entries: the count of a group starts from what the user holds of it.  With
+``portfolio_weights=`` (``validate_weights``) the mean-variance launches take their ``_weighted`` entries: every holding weighs
+on y by its size."""
 import collections
 import operator
 
@@ -17,13 +19,14 @@ from .prices import PriceLedger
 
 Query = collections.namedtuple("Query", "k U I K users users_h items_h timestamps ts_h scalar_ts item_ok ok_h ex_ids ex_len mv held "
                                "only_ids only_len only_held groups group_cap held_mode hg_ids hg_len stock_groups "
-                               "seen seen_since seen_width seen_max_scan basket",
-                               defaults=(None, None, None, None, False, None, None, None, None, None, None, None, None, None, 0, False))
+                               "weights seen seen_since seen_width seen_max_scan basket",
+                               defaults=(None, None, None, None, False, None, None, None, None, None, None, None, None, None, None, 0, False))
 # the mean-variance side of a query: the return tables' owner, packed portfolios (host or device), one day index per user
 # (with a PriceLedger as the owner: the ORDINAL among its live days, or None - the day is looked up on the device)
 MVQuery = collections.namedtuple("MVQuery", "src port_idx port_len day_idx")
 HELD = "held"     # ``exclude`` / ``portfolios``: take the rows of the model's holdings ledger (port_idx is None in the MVQuery then)
 PORTFOLIOS = "portfolios"   # ``held_groups``: the rows of ``portfolios=``, mapped to groups through ``stock_groups``
+SHARES, VALUE = "shares", "value"   # ``portfolio_weights``: the ledger's share counts / share count x the price ledger's last close
 SEEN = "seen"     # ``exclude`` / ``only`` / ``portfolios``: what the user's row of the temporal adjacency names before its time
 
 
@@ -177,6 +180,58 @@ def validate_mv(U, I, mv, portfolios, day_idx, ts_h, scalar_ts, holdings=None, *
     return MVQuery(mv, port_idx, port_len, day)
 
 
+def validate_weights(U, portfolio_weights, mv, mvq, portfolios, holdings=None, basket=False, groups=None, what="users holds"):
+    """``portfolio_weights`` of ``TGN.recommend`` and ``backtest`` checked on the host (ValueError) -> None without it, ``SHARES``
+    / ``VALUE``, or the rows: f64 [U, W] in the shape of the packed portfolios (a host array, or the caller's device tensor as
+    it is), lists packed with 0.0 behind each row's length.  ``mvq``: what ``validate_mv`` made of ``portfolios``."""
+    if portfolio_weights is None:
+        return None
+    if mv is None or mvq is None:
+        raise ValueError("portfolio_weights needs mv and portfolios: the weights weigh on the mean-variance value alone")
+    if basket:
+        raise ValueError("portfolio_weights and basket=True cannot be combined: the weight a pick joins the holdings with is undefined")
+    if groups is not None:
+        raise ValueError("portfolio_weights and groups / group_cap cannot be combined: the capped orders have no weighted form")
+    if _is_seen(portfolios):
+        raise ValueError('portfolio_weights and portfolios="seen" cannot be combined: the caller cannot align rows it never sees')
+    if isinstance(portfolio_weights, str):
+        if portfolio_weights not in (SHARES, VALUE):
+            raise ValueError('portfolio_weights must be "shares", "value", one list of numbers per user or an f64 [U, W] array')
+        if not _is_held(portfolios):
+            raise ValueError('portfolio_weights="%s" needs portfolios="held": the weights are the ledger\'s' % portfolio_weights)
+        if not holdings.quantities:
+            raise ValueError('portfolio_weights="%s" needs a ledger that keeps quantities: track_holdings(width, upper_u, '
+                             'quantities=True)' % portfolio_weights)
+        if portfolio_weights == VALUE and not isinstance(mv, PriceLedger):
+            raise ValueError('portfolio_weights="value" needs mv to be a PriceLedger: the price is its last close')
+        return portfolio_weights
+    if mvq.port_idx is None:
+        raise ValueError('explicit portfolio_weights need explicit portfolios (packed or lists): with portfolios="held" pass "shares" or "value"')
+    shape = tuple(mvq.port_idx.shape)
+    if isinstance(portfolio_weights, (torch.Tensor, np.ndarray)):
+        w = portfolio_weights
+        if w.ndim != 2 or tuple(w.shape) != shape:
+            raise ValueError("portfolio_weights has shape %s, the packed portfolios %s" % (tuple(w.shape), shape))
+        if not (w.dtype.is_floating_point if isinstance(w, torch.Tensor) else w.dtype.kind in "fiu"):
+            raise ValueError("portfolio_weights must be numbers")
+        return w if isinstance(w, torch.Tensor) else w.astype(np.float64)
+    try:
+        rows = [np.asarray(list(r), dtype=np.float64).reshape(-1) for r in portfolio_weights]
+    except (TypeError, ValueError):
+        raise ValueError('portfolio_weights must be "shares", "value", one list of numbers per user or an f64 [U, W] array') from None
+    if len(rows) != U:
+        raise ValueError("portfolio_weights lists %d users, %s %d" % (len(rows), what, U))
+    if isinstance(mvq.port_len, torch.Tensor):
+        raise ValueError("portfolio_weights as lists need portfolios on the host: beside device rows pass an f64 [U, W] tensor")
+    lens = np.asarray(mvq.port_len).reshape(-1)
+    w = np.zeros(shape, np.float64)
+    for i, r in enumerate(rows):
+        if r.size != int(lens[i]):
+            raise ValueError("portfolio_weights lists %d weights for user %d, portfolios %d holdings" % (r.size, i, int(lens[i])))
+        w[i, :r.size] = r
+    return w
+
+
 def validate_groups(I, groups, group_cap, only=None, mv=None):
     """``groups`` / ``group_cap`` of ``TGN.recommend`` and ``backtest`` checked on the host (ValueError) -> (groups, group_cap):
     (None, None) without them, else one int32 per candidate (a host array, or the caller's integer device tensor as it is: it
@@ -265,8 +320,8 @@ def validate_held_groups(U, held_groups, stock_groups, groups, holdings=None, po
 
 
 def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv=None, portfolios=None,
-             day_idx=None, holdings=None, basket=False, only=None, *, groups=None, group_cap=None, held_groups=None, stock_groups=None,
-             seen_since=None, seen_width=None, seen_max_scan=0):
+             day_idx=None, holdings=None, basket=False, only=None, *, portfolio_weights=None, groups=None, group_cap=None, held_groups=None,
+             stock_groups=None, seen_since=None, seen_width=None, seen_max_scan=0):
     """The arguments of ``TGN.recommend`` checked (ValueError) and brought into one form; what lives in device tensors is
     not read back, except ``items`` once."""
     if only is not None and exclude is not None:
@@ -358,10 +413,11 @@ def validate(n_nodes, default_neighbors, users, timestamps, k, items, exclude, i
             check_held_width(hg_ids.shape[1])
     elif held_mode == PORTFOLIOS and mvq.port_idx is not None:
         check_held_width(mvq.port_idx.shape[1])
+    weights = validate_weights(U, portfolio_weights, mv, mvq, portfolios, holdings, basket, groups)
     held = (_is_held(exclude), mvq is not None and mvq.port_idx is None and not seen[2])
     return Query(k, U, I, int(n_neighbors), users, users_h, items_h, ts_any, ts_h, scalar_ts, item_ok, ok_h, ex_ids, ex_len, mvq,
                  held if any(held) else None, only_ids, only_len, _is_held(only), groups, group_cap, held_mode, hg_ids, hg_len,
-                 stock_groups, seen if any(seen) else None, seen_since, seen_width, seen_max_scan, bool(basket))
+                 stock_groups, weights, seen if any(seen) else None, seen_since, seen_width, seen_max_scan, bool(basket))
 
 
 def _to_dev(dev, a, dtype):
@@ -484,7 +540,7 @@ def assemble(tgn, q, return_embeddings=False):
             held_rows = (stock_rows_to_groups(s_idx, to_dev(q.stock_groups, torch.int32)), s_len)
         if q.mv is not None:
             return _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                                held_ports, user_ts, listed, cap, held_rows)
+                                held_ports, user_ts, listed, cap, held_rows, users_d)
         if listed:
             launch = lambda ub, ue, pos, ln: recommend_list_topk(ue, item_emb, k, pos, ln, ub, ok_d, n_blocks=n_t)
         else:
@@ -543,7 +599,7 @@ def _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddi
 
 
 def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, excl_pos, excl_len, ok_d, return_embeddings,
-                 held_ports=None, user_ts=None, listed=False, cap=None, held_rows=()):
+                 held_ports=None, user_ts=None, listed=False, cap=None, held_rows=(), users_d=None):
     """The tail of ``assemble`` under a mean-variance side: ``recommend_mv_topk`` in place of ``recommend_topk``, day and
     portfolio rows following the users through the block sort.  ``held_ports``: the ledger's rows (portfolios="held").
     ``q.basket``: ``recommend_basket_topk`` in its place; more than 2048 candidates: ``recommend_mv_topk_wide``.  With a ``PriceLedger`` the kernels index its storage by ring slot:
@@ -551,7 +607,9 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
     ``listed``: ``excl_pos`` / ``excl_len`` are the users' own lists (``only=``) - ``recommend_list_mv_topk`` whatever I is, no
     workspace and no sort by block.  ``cap``: the cap keywords of the bounded and the basket launch (empty: uncapped; validate
     lets them through with neither ``only`` nor more than 2048 candidates).  ``held_rows``: (held_group, held_len) of the users
-    or nothing - they follow the users through the block sort like the portfolio rows."""
+    or nothing - they follow the users through the block sort like the portfolio rows.  ``q.weights``: the weight rows
+    (``portfolio_weights``) - explicit ones go to the device, ``"shares"`` / ``"value"`` are one ``pfo_holdings_gather_weights``
+    over ``users_d``; they follow the users through the block sort like ``port_idx`` and the weighted entries are called."""
     from .functional import recommend_basket_topk, recommend_list_mv_topk, recommend_mv_topk, recommend_mv_topk_wide
     topk = recommend_basket_topk if q.basket else recommend_mv_topk   # (the same arguments and return tuple)
     if q.I > _lib.RECOMMEND_MV_MAX_ITEMS:                             # (never the basket: validate refuses it)
@@ -564,16 +622,24 @@ def _assemble_mv(tgn, q, to_dev, items_d, user_emb, item_emb, user_block, n_t, e
     else:
         port_idx = to_dev(q.mv.port_idx, torch.int32) if q.mv.port_idx.shape[1] > 0 else None
         port_len = to_dev(q.mv.port_len, torch.int32) if port_idx is not None else None
+    port_w, weighted = None, q.weights is not None
+    if isinstance(q.weights, str):
+        port_w = tgn.holdings.gather_weights(users_d, q.weights, mv.last_close if q.weights == VALUE else None)
+    elif weighted and port_idx is not None:
+        port_w = to_dev(q.weights, torch.float64)
 
     def launch(ub, ue, pos, ln, day, port_idx, port_len, *held):
+        wkw = {}
+        if weighted:                                                  # (never with a cap or the basket: validate refuses both)
+            held, wkw = (), dict(port_w=held[0])
         if listed:
             top_pos, top_score, top_fused, n_valid = recommend_list_mv_topk(ue, item_emb, q.k, pos, ln, cand_stock, returns, day, port_idx,
                                                                             port_len, float(mv.gamma), float(mv.lambda_mv), ub, ok_d,
-                                                                            n_blocks=n_t)
+                                                                            n_blocks=n_t, **wkw)
         else:
             top_pos, top_score, top_fused, n_valid = topk(ue, item_emb, q.k, cand_stock, returns, day, port_idx, port_len, float(mv.gamma),
                                                           float(mv.lambda_mv), ub, pos, ln, ok_d, n_blocks=n_t, **(cap or {}),
-                                                          **_held_kw(held))
+                                                          **_held_kw(held), **wkw)
         return top_pos, top_score, n_valid, top_fused
-    return _select(launch, (user_emb, excl_pos, excl_len, day, port_idx, port_len) + tuple(held_rows), user_block, n_t, items_d, item_emb,
-                   return_embeddings, sort=not listed)
+    per_user = (user_emb, excl_pos, excl_len, day, port_idx, port_len) + ((port_w,) if weighted else tuple(held_rows))
+    return _select(launch, per_user, user_block, n_t, items_d, item_emb, return_embeddings, sort=not listed)

@@ -51,8 +51,8 @@ class Serving:
         return emb
 
     def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
-                  mv=None, portfolios=None, day_idx=None, basket=False, *, held_groups=None, stock_groups=None, seen_since=None,
-                  seen_width=None, seen_max_scan=0, only=None, groups=None, group_cap=None):
+                  mv=None, portfolios=None, day_idx=None, basket=False, *, portfolio_weights=None, held_groups=None, stock_groups=None,
+                  seen_since=None, seen_width=None, seen_max_scan=0, only=None, groups=None, group_cap=None):
         """The ``k`` items of ``items`` this model would offer each user at its time, best first - a query: NO model state is
         written (memory, last_update, the pending-message tables, parameters and gradients keep every bit; ``self.training``
         is left as found), no gradient is recorded and dropout is off.
@@ -143,13 +143,28 @@ class Serving:
         ``"seen"`` are refused too.  Entries removed by ``expire`` are no longer seen; interactions taken in by ``ingest`` /
         ``observe(append=True)`` are.
 
+        ``portfolio_weights`` (with ``mv``; by name): every holding weighs on the mean-variance value by its size, not 1 /
+        n_holding each - ``y = (mu / gamma - 0.5 * (1 / sum w) * sum_p w_p cov(i, p)) / var``, so a user with 95 % of the money in
+        one stock is ranked against that stock.  Given as rows - one list of numbers per user matching ``portfolios`` entry for
+        entry, or an f64 [U, W] array or tensor in the shape of packed ``portfolios`` - or by name beside ``portfolios="held"`` on a
+        ledger made with ``quantities=True``: ``"shares"`` - the ledger's share counts - or ``"value"`` - share count x last close,
+        which needs ``mv`` to be a ``PriceLedger`` on the ledger's ``upper_u``.  A holding whose weight is not finite and
+        positive (a stock never quoted under ``"value"``) is left out like a stock outside the return table; all-ones rows give
+        the unweighted lists bit for bit.  The named forms cost one ``pfo_holdings_gather_weights`` over the users already on the
+        device: nothing is packed or read back.  ``"value"`` uses the ledger's NEWEST close whatever the query day is - the
+        ledger keeps returns, not prices, per day.  One launch of ``pfo_recommend_mv_topk_weighted`` (beyond 2048 candidates
+        ``pfo_recommend_mv_topk_wide_weighted``, with ``only`` ``pfo_recommend_list_mv_topk_weighted``).  Refused (ValueError):
+        without ``mv``, with ``basket=True`` (the weight a pick joins the holdings with is undefined), with ``groups`` (the capped
+        orders have no weighted form), with ``portfolios="seen"`` (the caller cannot align rows it never sees), explicit rows
+        beside ``portfolios="held"``, a shape that is not the portfolios'.
+
         Host inputs are checked (ValueError); node ids in device tensors of ``users`` / ``exclude`` / ``only`` are not (it would
         cost a read-back).  ``items`` is read back once when it is a device tensor."""
         from . import recommend as R
         query = R.validate(self.n_nodes, self.n_neighbors, users, timestamps, k, items, exclude, item_ok, n_neighbors, mv,
                            portfolios, day_idx, self.holdings, basket, only, groups=groups, group_cap=group_cap,
                            held_groups=held_groups, stock_groups=stock_groups, seen_since=seen_since, seen_width=seen_width,
-                           seen_max_scan=seen_max_scan)
+                           seen_max_scan=seen_max_scan, portfolio_weights=portfolio_weights)
         _lib.require_gpu(self.device)
         return R.assemble(self, query, return_embeddings)
 
