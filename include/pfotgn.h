@@ -1104,6 +1104,47 @@ typedef struct pfo_tgn_debug {
 } pfo_tgn_debug;
 int pfo_tgn_debug_views(const pfo_tgn_config* cfg, void* workspace, pfo_tgn_debug* out);
 
+/* ------------------------------------------------------------------------------------------
+ * Explanation query (abi 6, additive): which past interactions an embedding attends to, read from the workspace of the
+ * pfo_tgn_forward call that computed it - before that workspace is used again.  `cfg` is the configuration the workspace was
+ * carved with, R and K are that call's (cfg->n_layers = L, cfg->n_heads = H).  Nothing of the workspace is written.
+ *
+ * What is read (level l holds n_l instances: n_L = R, n_(l-1) = n_l (1 + K); all tables have stride K of the call, not
+ * max_neighbors): the neighbour ids of level l's instances (behind that level's own n_l nodes in the list the sampler wrote for
+ * level l - 1), its edge ids eidx [n_l, K], its dt f32 [n_l, K] (the instance's time minus the edge's time: the value the time
+ * encoder saw; every level's instance time is its root's) and the layer's softmax weights attw f32 [n_l, H, K] (before dropout,
+ * 0 on padding, all 0 on an instance without a neighbour).
+ *
+ *   head mean   p_l[n, k] = (sum over h ascending of (double) attw_l[n, h, k]) / (double) H - what nn.MultiheadAttention
+ *               returns beside its output.  A slot COUNTS iff its neighbour id is not 0.
+ *   hops == 1   root r: the entries are its counting slots k of level L, entry k names node nbr_L[r, k] with weight p_L[r, k],
+ *               age dt_L[r, k] and edge eidx_L[r, k].
+ *   hops == 2   (attention rollout) for every counting slot j of root r, row = R + r K + j of level L - 1 is that neighbour's
+ *               instance; the entries are the paths q = j K + i whose slot i of that row counts: node nbr_(L-1)[row, i],
+ *               weight p_L[r, j] * p_(L-1)[row, i] (ONE rounded fp64 product), age and edge of the path's LAST hop
+ *               (dt_(L-1)[row, i], eidx_(L-1)[row, i]).  The root's own level-(L-1) row is not part of the rollout.
+ *   merge       entries that name the same node become one: weight = the sum of theirs taken sequentially in ascending k / q
+ *               from 0.0, count = how many, age = the smallest of theirs, eidx = that entry's (among equal ages the lowest k / q).
+ *   order       weight descending (fp64), then age ascending, then node id ascending.
+ * All arithmetic is fp64 without contraction; nothing is added out of order: the same input gives the same bits on every run.
+ *
+ *   node_out i32[R, m] padded with -1;  weight_out f64[R, m] padded with 0.0;  n_valid_out i32[R] = min(m, distinct nodes);
+ *   count_out i32[R, m] padded with 0;  age_out f32[R, m] padded with NaN;  eidx_out i32[R, m] padded with -1.
+ *   Every slot of every row is written.  A hops == 1 row sums to 1 up to rounding (0 when empty), a hops == 2 row to at most 1.
+ *   raw_nbr i32[R, K], raw_w f32[R, H, K], raw_dt f32[R, K], raw_eidx i32[R, K]: copies of level L's tables - all four or all
+ *   NULL.  raw_nbr2 i32[R, K, K], raw_w2 f32[R, K, H, K], raw_dt2 f32[R, K, K], raw_eidx2 i32[R, K, K]: level L - 1's rows
+ *   R .. R + R K - all four or all NULL, written with hops == 2 only.
+ * One launch (csrc/explain.hip), a workgroup per root.  PFO_ERR_INVALID - checked before any pointer is looked at, nothing is
+ * queued: a bad configuration, m outside [1, PFO_EXPLAIN_MAX_WIDTH], hops outside [1, min(2, n_layers)], K outside
+ * [1, min(PFO_MAX_NEIGHBORS, max_neighbors)], R outside [0, max_roots]; then a null workspace or output, or a raw group given
+ * in part.  R == 0 queues nothing and returns PFO_OK.
+ */
+#define PFO_EXPLAIN_MAX_WIDTH 256
+int pfo_tgn_explain(const pfo_tgn_config* cfg, const void* workspace, int32_t R, int32_t K, int32_t hops, int32_t m,
+                    int32_t* node_out, double* weight_out, int32_t* n_valid_out, int32_t* count_out, float* age_out,
+                    int32_t* eidx_out, int32_t* raw_nbr, float* raw_w, float* raw_dt, int32_t* raw_eidx, int32_t* raw_nbr2,
+                    float* raw_w2, float* raw_dt2, int32_t* raw_eidx2, void* stream);
+
 /* debug / test probes of the internal contraction interface (csrc/gemm.hpp).  Every struct mirrors the internal one field
  * for field and every call forwards to the internal launcher unchanged; the comments of gemm.hpp are the contract.  Not part
  * of the drop-in surface: the package's own Python never calls them, the kernel tests do. */

@@ -19,6 +19,9 @@ RECOMMEND_MV_WIDE_MAX_ITEMS = 65536   # PFO_RECOMMEND_MV_WIDE_MAX_ITEMS
 RECOMMEND_LIST_MAX_WIDTH = 256  # PFO_RECOMMEND_LIST_MAX_WIDTH
 RECOMMEND_HELD_MAX_WIDTH = 256  # PFO_RECOMMEND_HELD_MAX_WIDTH
 HISTORY_MAX_WIDTH = 256         # PFO_HISTORY_MAX_WIDTH
+EXPLAIN_MAX_WIDTH = 256         # PFO_EXPLAIN_MAX_WIDTH
+MAX_NEIGHBORS = 64              # PFO_MAX_NEIGHBORS
+DEFAULT_NEIGHBORS = 20          # n_neighbors of the entry points (compute_temporal_embeddings) when model and caller name none
 EVAL_RANK_NONE = (1 << 31) - 1  # PFO_EVAL_RANK_NONE: the positive is not ranked
 ADAM_MAX_RANGES = 16            # PFO_ADAM_MAX_RANGES
 GRAD_NORM_PARTS = 256           # PFO_GRAD_NORM_PARTS
@@ -284,6 +287,8 @@ PROTOTYPES = {
                                          _VP, C.c_int64, _VP, _VP]),
     "pfo_day_lookup": (C.c_int, [_VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_double, _VP, _VP]),
     "pfo_tgn_debug_views": (C.c_int,[C.POINTER(TgnConfig), _VP, C.POINTER(TgnDebug)]),
+    "pfo_tgn_explain": (C.c_int, [C.POINTER(TgnConfig), _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                  _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "pfo_debug_gemm": (C.c_int, [C.POINTER(GemmDesc), _VP]),
     "pfo_debug_gemm_multi": (C.c_int, [C.POINTER(GemmDesc), C.c_int32, _VP]),
     "pfo_debug_gemm_tn_group": (C.c_int, [C.POINTER(TnDesc), C.c_int32, C.c_int32, _VP, _VP, C.c_int64, _VP]),

@@ -10,7 +10,7 @@ CSRC = os.environ.get("PFO_CSRC") or os.path.join(HERE, "csrc")     # override: 
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libpfotgn.so")
 SOURCES = ["sampler.hip", "gemm.hip", "gemm_f32.hip", "gemm_bx.hip", "gemm_tn_bx.hip", "gemm_fused.hip", "bimg.hip", "attn.hip", "attn_fwd.hip", "attn_bwd.hip", "attn_bwd_runs.hip", "memory.hip", "misc.hip", "csr.hip", "tgn.hip", "eval.hip", "backtest.hip", "recommend.hip", "ingest.hip",
-           "forget.hip", "holdings.hip", "history.hip", "prices.hip", "optim.hip", "probe.hip"]
+           "forget.hip", "holdings.hip", "history.hip", "explain.hip", "prices.hip", "optim.hip", "probe.hip"]
 ARCH = "gfx950"
 
 

@@ -11,6 +11,7 @@
 #include "gemm.hpp"
 #include "attn.hpp"
 #include "memory.hpp"
+#include "explain.hpp"
 #include <algorithm>
 #include <math.h>
 #include <string.h>
@@ -469,6 +470,43 @@ extern "C" int pfo_tgn_debug_views(const pfo_tgn_config* c, void* workspace, pfo
   out->Cp = d.Cp;
   out->mlp_hid = w.mlp_hid; out->mlp_out = w.mlp_out;
   return PFO_OK;
+}
+
+// The explanation query reads what a forward left in its workspace (include/pfotgn.h): level L's tables for the roots, level
+// L - 1's for their neighbours' instances (rows R .. R + R K).  Level l's neighbour ids sit behind the n_l nodes of nodes[l - 1].
+// (a weak reference: this file also links host-only, without the kernels' objects - tests/host/step_trace.cpp)
+int pfo_explain_launch(const PfoExplain& a, hipStream_t s) __attribute__((weak));
+extern "C" int pfo_tgn_explain(const pfo_tgn_config* c, const void* workspace, int32_t R, int32_t K, int32_t hops, int32_t m,
+                               int32_t* node_out, double* weight_out, int32_t* n_valid_out, int32_t* count_out, float* age_out,
+                               int32_t* eidx_out, int32_t* raw_nbr, float* raw_w, float* raw_dt, int32_t* raw_eidx,
+                               int32_t* raw_nbr2, float* raw_w2, float* raw_dt2, int32_t* raw_eidx2, void* stream) {
+  if (int rc = check_cfg(c)) return rc;
+  PFO_REQUIRE(m >= 1 && m <= PFO_EXPLAIN_MAX_WIDTH, "m must lie in [1, PFO_EXPLAIN_MAX_WIDTH]");
+  PFO_REQUIRE(hops >= 1 && hops <= std::min(2, c->n_layers), "hops must lie in [1, min(2, n_layers)]");
+  PFO_REQUIRE(K >= 1 && K <= PFO_MAX_NEIGHBORS && K <= c->max_neighbors, "K must lie in [1, min(PFO_MAX_NEIGHBORS, max_neighbors)]");
+  PFO_REQUIRE(R >= 0 && R <= c->max_roots, "R must lie in [0, max_roots]");
+  if (R == 0) return PFO_OK;
+  PFO_REQUIRE(workspace && node_out && weight_out && n_valid_out && count_out && age_out && eidx_out, "null pointer");
+  const int n_raw = (raw_nbr != nullptr) + (raw_w != nullptr) + (raw_dt != nullptr) + (raw_eidx != nullptr);
+  const int n_raw2 = (raw_nbr2 != nullptr) + (raw_w2 != nullptr) + (raw_dt2 != nullptr) + (raw_eidx2 != nullptr);
+  PFO_REQUIRE((n_raw == 0 || n_raw == 4) && (n_raw2 == 0 || n_raw2 == 4), "null pointer: a raw group is given whole or not at all");
+  PFO_REQUIRE(&pfo_explain_launch != nullptr, "built without csrc/explain.hip");
+  const Ws w = carve(c, const_cast<void*>(workspace));
+  const int L = c->n_layers, H = c->n_heads;
+  PfoExplain a;
+  memset(&a, 0, sizeof(a));
+  a.R = R; a.K = K; a.H = H; a.hops = hops; a.m = m;
+  a.nbr = w.nodes[L - 1] + R; a.attw = w.layer[L].attw; a.dt = w.dt[L]; a.eidx = w.eidx[L];
+  if (hops == 2) {
+    const int64_t n_below = (int64_t)R * (1 + K), skip = (int64_t)R * K;     // level L - 1: its R self rows come first
+    a.nbr2 = w.nodes[L - 2] + n_below + skip; a.attw2 = w.layer[L - 1].attw + skip * H;
+    a.dt2 = w.dt[L - 1] + skip; a.eidx2 = w.eidx[L - 1] + skip;
+    a.raw_nbr2 = raw_nbr2; a.raw_w2 = raw_w2; a.raw_dt2 = raw_dt2; a.raw_eidx2 = raw_eidx2;
+  }
+  a.node_out = node_out; a.weight_out = weight_out; a.n_valid_out = n_valid_out; a.count_out = count_out; a.age_out = age_out;
+  a.eidx_out = eidx_out;
+  a.raw_nbr = raw_nbr; a.raw_w = raw_w; a.raw_dt = raw_dt; a.raw_eidx = raw_eidx;
+  return pfo_explain_launch(a, (hipStream_t)stream);
 }
 
 static int level_sizes(const pfo_tgn_config* c, const pfo_tgn_batch* b, int64_t* n) {

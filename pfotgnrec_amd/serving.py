@@ -50,6 +50,65 @@ class Serving:
             self._step, self._gru_applied_now = saved
         return emb
 
+    def _walk_readonly(self, roots, root_ts, K, visit):
+        """The forward-only chunk walk of ``_embed_readonly`` for a query that reads the WORKSPACE of each pass and not its
+        embeddings: ``visit(call, c0, c1)`` runs behind the pass over rows [c0, c1) and before that pass's workspace goes back to
+        the pool (``_forward_chunks`` hands it back first).  ``K`` is past ``_no_neighbours`` already.  Nothing of the model is
+        written; the step counter and the "a GRU took part" flag are put back."""
+        R, cap, B = int(roots.shape[0]), max(1, int(self.eval_chunk_roots)), max(1, self._ws_caps[2])
+        saved = (self._step, self._gru_applied_now)
+        self._drop_prefetched()
+        try:
+            with torch.no_grad():
+                for c0 in range(0, R, cap):
+                    c1 = min(R, c0 + cap)
+                    call = self._make_call(roots[c0:c1], root_ts[c0:c1], K, None, 0.0, None, B)
+                    try:
+                        self._native_forward(call)
+                        visit(call, c0, c1)
+                    finally:
+                        call.release()
+        finally:
+            self._step, self._gru_applied_now = saved
+
+    def explain(self, nodes, timestamps, m, hops=1, n_neighbors=None, return_raw=False):
+        """WHY an embedding is what it is: the ``m`` past interaction partners the embedding of each (node, time) attends to most,
+        most important first - "you are shown X because of your trades in A, B, C".  A query under ``recommend``'s contract: NO
+        model state is written (memory, last_update, the pending-message tables, parameters, gradients and the step counter
+        keep every bit; ``self.training`` is left as found), pending messages are applied lazily as every forward does, no
+        gradient is recorded and dropout is off.
+
+        nodes: [U] node ids (numpy / list, or an integer tensor) - users, or items to explain the item side of a pair;
+        timestamps: a scalar or f64 [U] on host or device; m: 1 .. 256; hops: 1 or 2 (at most ``n_layers``); n_neighbors:
+        default the model's.
+
+        The numbers are the head-averaged softmax weights of the temporal attention layers (what ``nn.MultiheadAttention``
+        returns beside its output, 0 on padding), read from the workspace of the forward-only pass by ``pfo_tgn_explain``
+        (DESIGN §4s), in fp64: ``p[k] = (sum_h w[h, k]) / H``.  A sampled slot counts iff its neighbour is not the padding node.
+        ``hops=1``: the weight of node v is the sum of the top layer's ``p[k]`` over the root's slots that name v - a user who
+        traded one stock five times gets ONE entry with ``count`` 5.  ``hops=2`` (attention rollout): every two-hop path root ->
+        slot j -> slot i of that neighbour's own row one layer down weighs ``p_L[j] * p_(L-1)[i]``, and the weight of v is the sum
+        over the paths that end in v; the root's OWN row of the lower layer (its self path) is not part of the rollout, so a row
+        sums to at most 1.  A ``hops=1`` row sums to 1 up to rounding, or to 0 when it is empty.
+
+        Returns, on the device, ``(node i32[U, m], weight f64[U, m], n_valid i32[U], count i32[U, m], age f32[U, m],
+        eidx i32[U, m])``: the distinct nodes by weight descending, then smaller age, then smaller id; ``n_valid`` = min(m,
+        distinct nodes); ``count`` the slots (paths) merged into the entry; ``age`` the smallest dt among them - the root's time
+        minus the edge's time, the value the time encoder saw, for a path that of its last edge - and ``eidx`` the edge id of
+        that entry (among equal ages the lowest slot / path).  Slots beyond ``n_valid`` hold -1 / 0.0 / 0 / NaN / -1.  A row is
+        empty when the node has no neighbour before its time, and every row is when ``n_neighbors`` <= 0.
+
+        ``return_raw=True`` appends a dict of the per-slot tables the answer was made from, copied out of the workspace: ``nbr``
+        i32[U, K], ``w`` f32[U, H, K], ``dt`` f32[U, K], ``eidx`` i32[U, K] of the top layer, and with ``hops=2`` ``nbr2``
+        i32[U, K, K], ``w2`` f32[U, K, H, K], ``dt2``, ``eidx2`` of the neighbours' rows one layer down - the per-edge explanation
+        the attention layer itself returns.
+
+        Host inputs are checked (ValueError) before a device is asked for; node ids in a device tensor are not."""
+        from . import explain as E
+        query = E.validate(self.n_nodes, self.n_layers, self.n_neighbors, nodes, timestamps, m, hops, n_neighbors)
+        _lib.require_gpu(self.device)
+        return E.assemble(self, query, return_raw)
+
     def recommend(self, users, timestamps, k, items, exclude=None, item_ok=None, n_neighbors=None, return_embeddings=False,
                   mv=None, portfolios=None, day_idx=None, basket=False, *, portfolio_weights=None, held_groups=None, stock_groups=None,
                   seen_since=None, seen_width=None, seen_max_scan=0, only=None, groups=None, group_cap=None):
